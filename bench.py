@@ -18,6 +18,12 @@ no masks).
 `python bench.py --gpus N` without a launcher starts the N ranks itself (fresh child processes, before this process
 touches the GPU) and relays rank 0's line.  Rank 0 prints ONE JSON line.
 
+A plain run sets up, warms up, times the --steps steps and prints the line (`value`, `ms_per_step`, and `roofline` /
+`stage_ms` / `step_roofline` from the timed steps' own events).  `--dump-outputs DIR` then writes what a caller of the
+timed step receives after its last step -- the loss and the six updated parameters -- as DIR/<name>.npy (float32).  The
+legs below that take runs of their own (`sustained`, `factored_z`, `zabs_kernels`, `random_init_values`, `predict`,
+`predict_sdss_shape`, `epoch`, `cpu_baseline`) run only with `--full`.
+
 `roofline` describes the dominant kernel (pass 2: at N_h <= 16 k_grads_t from 128 (N_h <= 8: 512) spectra on and k_grads_x below,
 k_grads / k_grads_x at N_h <= 8, the three launches k_s12_x + 2 k_grads_s3 at N_h = 17..32; its mean duration is measured with HIP events recorded by the library on the
 launch stream inside the timed region).  The contractions are float32 products ISSUED as 16-bit piece products on the XDL
@@ -75,6 +81,15 @@ def alg_flops(npix, k):
 def alg_bytes(npix, nb):
     """delta, sigma (4 B), mask (1 B) per pixel, zabs (4 B) per blue pixel, NLL out."""
     return npix * 9 + nb * 4 + 4
+
+
+def dump_outputs(out_dir, loss, params):
+    """What a caller of the timed step receives after the last one: the (1, 1) loss it returned and the six parameters
+    it left in the model (QFA.parameters), each as <out_dir>/<name>.npy in float32 (a few hundred kB at c3)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in [("loss", loss)] + sorted(params.items()):
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().float().cpu().numpy())
 
 
 def usable_cores():
@@ -316,8 +331,13 @@ def main():
     ap.add_argument("--config", default=None, choices=sorted(CONFIGS),
                     help="default: c3 (100 000 spectra per GPU); with --gpus 8: c4 (BASELINE configs[3]: 1M spectra over 8 GPUs)")
     ap.add_argument("--batch", type=int, default=0, help="spectra per GPU (default: the config's)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beyond the headline: sustained, factored z, zabs kernels, random-init values, "
+                         "predict, epoch, CPU baseline (the --no-* / --sustain options below select among them)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the last step's loss and updated parameters as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--sustain", type=float, default=3.0, help="seconds of extra steps after the timed region (0 = skip)")
+    ap.add_argument("--sustain", type=float, default=3.0, help="--full: seconds of extra steps after the timed region (0 = skip)")
     ap.add_argument("--no-predict", action="store_true")
     ap.add_argument("--no-epoch", action="store_true", help="skip the epoch leg (QFA.train over a resident, reshuffled data set)")
     ap.add_argument("--epoch-batches", type=int, default=0, help="batches resident in the epoch leg (default: 4, more for small batches)")
@@ -326,6 +346,8 @@ def main():
     ap.add_argument("--flags", type=lambda x: int(x, 0), default=0, help="QFA_F_* kernel-form flags (include/qfa_hip.h); 0 = defaults")
     ap.add_argument("--dry-run", action="store_true", help="launcher rehearsal without a GPU: no spectra are processed")
     args = ap.parse_args()
+    if args.steps == 0:
+        ap.error("--steps must be at least 1")
     if args.config is None:
         args.config = "c4" if args.gpus >= 8 else "c3"
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -444,10 +466,12 @@ def main():
     ms_prep, ms_p1, ms_solve, ms_p2 = [float(x) for x in stage]
     # the one collective of the step (packed sums + counts, qfa_accum_floats floats) between events on the launch stream
     ms_ar = float(np.mean([a.elapsed_time(b) for a, b in ar_evs])) if ar_evs is not None else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, losses[-1], model.parameters)
 
     # ---- sustained leg: the same step for >= --sustain seconds (held clock; lets rocm-smi sampling see the run)
     sustained = None
-    if args.sustain > 0:
+    if args.full and args.sustain > 0:
         n_s, t_s = 0, time.perf_counter()
         chunk = max(10, int(0.25 / max(dt / args.steps, 1e-4)))
         while time.perf_counter() - t_s < args.sustain:
@@ -479,7 +503,7 @@ def main():
                                   "pass2_grads": float(sst[3])}}
     # ---- the same step fed the factored-z input form (what DeviceDataloader batches carry): zabs is not read
     fz = None
-    if nb > 0:
+    if args.full and nb > 0:
         for _ in range(2):
             model.step(opt, batch[0], batch[1], None, batch[3], zfac=zfac)
         fev = [[torch.cuda.Event(enable_timing=True) for _ in range(5)] for _ in range(args.steps)]
@@ -511,7 +535,7 @@ def main():
     auto_on = bool(model.auto_factor_zabs) and nb > 0
     ent = model._zf_seen.get(id(batch[2])) if auto_on else None
     factored_headline = bool(ent is not None and isinstance(ent[2], tuple))
-    if auto_on:
+    if args.full and auto_on:
         model.auto_factor_zabs = False
         for _ in range(2):
             model.step(opt, *batch)
@@ -554,7 +578,7 @@ def main():
     # ---- SURVEY 8(d) "also a run at random_init_func values" (QFA/model.py:67-72: F ~ U(-0.5, 0.5), Psi = omega = 1, tau0 0.02,
     # c0 0.3, beta 2): the same batch through a freshly initialised model
     rinit = None
-    if world == 1 and args.config in ("c3", "c4", "c2"):
+    if args.full and world == 1 and args.config in ("c3", "c4", "c2"):
         torch.manual_seed(20220700)
         m2 = QFA(nb, nr, nh, dev)
         m2.flags, m2.deterministic = args.flags, bool(args.deterministic)
@@ -729,7 +753,7 @@ def main():
     if sustained is not None:
         out["sustained_ms_per_step"] = sustained["ms_per_step"]
         out["sustained"] = sustained
-    if world == 1 and not args.no_predict:
+    if args.full and world == 1 and not args.no_predict:
         out["predict"] = predict_leg(model, batch, mu, npix, nb, nh)
         if args.config == "c3":
             # the shape the reference ships and predicts with (N_pix = 1913, N_h = 8: data/model_parameters.npz)
@@ -742,7 +766,7 @@ def main():
                                              workload="50000 spectra x N_pix=1913 (N_b=720), N_h=8, masks")
             del b1, m1
             torch.cuda.empty_cache()
-    if world == 1 and not args.no_epoch:
+    if args.full and world == 1 and not args.no_epoch:
         nbat = args.epoch_batches or max(4, -(-131072 // B))
         graph = (B <= 2048) if args.epoch_graph < 0 else bool(args.epoch_graph)
         ep_epochs = max(2, min(50, int(1.0 / max(nbat * step_ms * 1e-3, 1e-3))))
@@ -751,7 +775,7 @@ def main():
         if fz is not None:
             ep["vs_step_only_factored_z"] = ep["value"] / fz["value"]
         out["epoch"] = ep
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(params, batch, n_cpu, npix, args.config)
     sys.stdout.flush()
     if rank == 0:
