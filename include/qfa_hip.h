@@ -198,6 +198,43 @@ int qfa_predict_ex_f32(const qfa_params_t *p, const float *mu, const qfa_batch_t
                        float *ll, float *hmean, float *hcov, float *cont, float *unc,
                        void *workspace, size_t workspace_bytes, unsigned flags, void *stream, void *const *events);
 
+/* Posterior draws (additive to ABI v4).  The reference stops at the posterior moments: nb/predict.ipynb cell 11 plots
+ * cont +- k uncertainty, and nb/generate_mock_continuum.ipynb cell 7 forms continua as `F@posterior_samples[idx]+mu`, one
+ * vector at a time in numpy.  These calls draw latent vectors from N(hmean, hcov) and write the continua on the device.
+ *
+ * The draw contract.  For spectrum b of a call, r = row0 + b is its global row (int64); for sample s (0 <= s < S) and
+ * latent component j (0 <= j < Nh):
+ *   generator  Philox4x32-10 (the constants and rounds of Random123's philox4x32_10),
+ *              key = (seed & 0xffffffff, seed >> 32), counter = (j >> 2, s, r & 0xffffffff, r >> 32) -> words x0..x3;
+ *   uniforms   u_i = (x_i + 0.5) 2^-32 in float64 (in (0, 1): the log below is always finite);
+ *   normals    Box-Muller in float64, each rounded once to float32:  z[4q+0] = sqrt(-2 ln u0) cos(2 pi u1),
+ *              z[4q+1] = sqrt(-2 ln u0) sin(2 pi u1), z[4q+2], z[4q+3] the same of (u2, u3), q = j >> 2;
+ *   latent     h[b,s,:] = hmean[b] + C_b z[b,s,:] in float64, rounded once, where C_b is the lower Cholesky factor of the
+ *              LOWER triangle of hcov[b] (float32, as qfa_predict_f32 writes it) computed in float64.  A pivot <= 0 zeroes
+ *              its column (the defined result for the near-singular hcov of high-S/N spectra); a NaN or Inf anywhere in
+ *              hcov[b] or hmean[b] makes every value of that spectrum's draws NaN and touches no other spectrum;
+ *   continuum  cont[r, p] = mu[p] + sum_j F[p, j] h[r, j] on ALL pixels (the `cont` of qfa_predict_f32), a float32 fma chain
+ *              from mu in order of j.
+ * Consequences: draws depend only on (seed, r, s, j) -- not on how a data set is split into calls, the launch shape or Nh
+ * (the draws at Nh = 8 are a prefix of those at Nh = 16); hmean = 0, hcov = I draws from the prior, h = z.  A captured
+ * graph replays the seed it was captured with: the same draws on every replay.
+ * Neither call synchronises or allocates (graph-capturable). */
+
+/* h (B, S, Nh) float32, contiguous: S draws of every spectrum of hmean (B, Nh), hcov (B, Nh, Nh).  row0 >= 0.
+ * Returns QFA_E_NULL, or QFA_E_SIZE for B < 0, S < 1, Nh outside 1..32, row0 < 0; B = 0 does nothing. */
+int qfa_sample_latent_f32(const float *hmean, const float *hcov, int B, int Nh, int S, uint64_t seed, int64_t row0,
+                          float *h, void *stream);
+
+/* bytes of scratch of qfa_continua_f32 (an image of F and mu, (Nh + 1) rows padded to 256 pixels); 0 = unsupported shape */
+size_t qfa_continua_workspace_bytes(int Npix, int Nh);
+
+/* out (R, Npix) = mu + F h for R latent rows h (R, Nh) -- the mock-continuum notebook's `F@h+mu` for a whole batch
+ * (h of qfa_sample_latent_f32 is R = B S rows).  F (Npix, Nh), mu (Npix,); out contiguous at any 4-byte alignment; 64-bit
+ * indices (R Npix may pass 2^31).  Returns QFA_E_NULL, QFA_E_SIZE (R < 0, Npix < 1, Nh outside 1..32) or QFA_E_WORKSPACE;
+ * R = 0 does nothing. */
+int qfa_continua_f32(const float *F, const float *mu, const float *h, int64_t R, int Npix, int Nh, float *out,
+                     void *workspace, size_t workspace_bytes, void *stream);
+
 /* Replaces Adam.update (reference QFA/optimizer.py:37-52) followed by the clamp of QFA.clip
  * (QFA/model.py:233-241) for ONE tensor of n elements:
  *   g' = g + wd*p; m = (1-b1) g' + b1 m; v = (1-b2) g'^2 + b2 v;

@@ -18,6 +18,7 @@ EXPORTS = (
     "qfa_adam_clip_f32",
     "qfa_adam_clip_multi_f32", "qfa_clip_f32", "qfa_smooth_f32", "qfa_tau_f32", "qfa_tauhi_f32", "qfa_omega_func_f32", "qfa_woodbury_f32", "qfa_build_batch_f32", "qfa_mu_estimate_f64",
     "qfa_mu_sums_f64", "qfa_mu_finish_f64", "qfa_build_resident_f32", "qfa_finalize_adam_clip_f32", "qfa_zabs_factor_f32",
+    "qfa_sample_latent_f32", "qfa_continua_workspace_bytes", "qfa_continua_f32",
 )
 
 TAU_IDS = {"becker": 0, "fg": 1, "kamble": 2, "mock": 3}
@@ -107,6 +108,9 @@ def lib():
         "qfa_mu_sums_f64": (i, [p, p, p, p, d, i, i, i, i, i64, p, p]),
         "qfa_mu_finish_f64": (i, [p, i, i, p, p, p]),
         "qfa_zabs_factor_f32": (i, [p, i, i, f, p, p, p, p]),
+        "qfa_sample_latent_f32": (i, [p, p, i, i, i, C.c_uint64, i64, p, p]),
+        "qfa_continua_workspace_bytes": (sz, [i, i]),
+        "qfa_continua_f32": (i, [p, p, p, i64, i, i, p, p, sz, p]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(h, name, None)

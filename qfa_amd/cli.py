@@ -4,7 +4,8 @@
     python -m qfa_amd.cli --cfg config.yaml --type predict
 
 Same flags, config keys and outputs as reference main.py:16-101: ``config.yaml`` and ``log.txt`` in OUTPUT_DIR,
-checkpoints every five epochs, ``predict/<name>.npz`` with ll, hmean, hcov, cont, uncertainty.  Spectra are read
+checkpoints every five epochs, ``predict/<name>.npz`` with ll, hmean, hcov, cont, uncertainty (and cont_samples, drawn
+from the posterior, with ``--opts MODEL.N_SAMPLES <S> MODEL.SAMPLE_SEED <seed>``).  Spectra are read
 on the host (qfa_amd.io), everything after that runs on the GPU; there is no CPU device.
 """
 from __future__ import annotations
@@ -124,7 +125,8 @@ def main(argv=None):
         print(f"=> Resume from {cfg.MODEL.RESUME}")
         load_model_file(model, cfg.MODEL.RESUME, cfg)         # parameters and mu of the trained model
         ts = time.time()
-        model.predict_to_npz(dataloader, os.path.join(cfg.DATA.OUTPUT_DIR, "predict"))
+        model.predict_to_npz(dataloader, os.path.join(cfg.DATA.OUTPUT_DIR, "predict"),
+                             n_samples=int(cfg.MODEL.N_SAMPLES), seed=int(cfg.MODEL.SAMPLE_SEED))
         print(f"Finish predicting {len(dataloader)} spectra in {time.time() - ts} seconds...")
     return 0
 

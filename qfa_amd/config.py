@@ -43,7 +43,10 @@ DEFAULTS = {                                        # reference QFA/config.py:15
               # not in the reference: its load_from_npz reads c0 from the file's 'beta' entry (QFA/model.py:295, quirk
               # Q1).  True keeps that (the reference's shipped models and stored answers need it); set it to False
               # for models trained and saved by this package, whose files hold the true c0.
-              "REFERENCE_C0_QUIRK": True},
+              "REFERENCE_C0_QUIRK": True,
+              # not in the reference: predict mode adds N_SAMPLES continua drawn from the posterior to every file
+              # (cont_samples, (N_SAMPLES, Npix)); SAMPLE_SEED seeds the counter-based generator (include/qfa_hip.h)
+              "N_SAMPLES": 0, "SAMPLE_SEED": 0},
     "TRAIN": {"NEPOCHS": 500, "LEARNING_RATE": 1e-3, "WEIGHT_DECAY": 1e-1, "DECAY_ALPHA": 0.9, "DECAY_STEP": 10,
               "WINDOW_LENGTH_FOR_MU": 16},
 }
@@ -60,7 +63,7 @@ ARG_KEYS = {
 }
 # keys of DEFAULTS the reference does not have (tests/test_cli_config.py pins everything else against
 # tests/golden/g12_config.json, extracted from the reference's config.py / main.py)
-EXTRA_KEYS = ("MODEL.REFERENCE_C0_QUIRK",)
+EXTRA_KEYS = ("MODEL.REFERENCE_C0_QUIRK", "MODEL.N_SAMPLES", "MODEL.SAMPLE_SEED")
 
 
 def _set(cfg, dotted, value):

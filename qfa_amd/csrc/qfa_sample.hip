@@ -1,0 +1,78 @@
+// qfa_sample.hip -- C-ABI of the posterior draws (include/qfa_hip.h: qfa_sample_latent_f32, qfa_continua_workspace_bytes,
+// qfa_continua_f32): argument checks and launch geometry.  Kernels in qfa_sample.h.
+#include "qfa_sample.h"
+#include "../../include/qfa_hip.h"
+
+namespace {
+
+using namespace qfa_sample;
+
+int pad_of(int Npix) { return (Npix + kWriterThreads - 1) / kWriterThreads * kWriterThreads; }
+
+template <int NH>
+void launch_cont(const float *img, int pad, const float *h, int64_t R, int Npix, float *out, hipStream_t st) {
+    const int strips = pad / kWriterThreads;
+    // about 32 blocks per CU-sized slice of 256 CUs; at least 16 rows per block so that the image loads are amortised,
+    // at most 256 so that the grid still spreads a large call over every CU
+    int64_t rpb = (R * strips + 8191) / 8192;
+    rpb = rpb < 16 ? 16 : (rpb > 256 ? 256 : rpb);
+    const int64_t cap = (R * strips + 0x3fffffff) / 0x40000000;      // grid.x stays below 2^30 blocks
+    if (rpb < cap) rpb = cap;
+    const int64_t chunks = (R + rpb - 1) / rpb;
+    k_sample_cont<NH><<<(unsigned)(chunks * strips), kWriterThreads, 0, st>>>(img, pad, h, R, Npix, strips, rpb, out);
+}
+
+template <int NH>
+void dispatch_cont(int Nh, const float *img, int pad, const float *h, int64_t R, int Npix, float *out, hipStream_t st) {
+    if constexpr (NH > 1) {
+        if (Nh < NH) return dispatch_cont<NH - 1>(Nh, img, pad, h, R, Npix, out, st);
+    }
+    launch_cont<NH>(img, pad, h, R, Npix, out, st);
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t qfa_continua_workspace_bytes(int Npix, int Nh) {
+    if (Npix < 1 || Nh < 1 || Nh > 32) return 0;
+    return (size_t)(Nh + 1) * pad_of(Npix) * sizeof(float);
+}
+
+int qfa_sample_latent_f32(const float *hmean, const float *hcov, int B, int Nh, int S, uint64_t seed, int64_t row0,
+                          float *h, void *stream) {
+    if (!hmean || !hcov || !h) return QFA_E_NULL;
+    if (B < 0 || S < 1 || Nh < 1 || Nh > 32 || row0 < 0 || row0 > INT64_MAX - B) return QFA_E_SIZE;
+    if (B == 0) return 0;
+    // at most 65535 chunks along grid y: 256 samples per wave (four per lane) or more when S is larger than 16.7 M
+    int spb = 4 * kLatentThreads;
+    const int64_t need = ((int64_t)S + 65534) / 65535;
+    if (need > spb) spb = (int)((need + kLatentThreads - 1) / kLatentThreads * kLatentThreads);
+    const dim3 grid((unsigned)B, (unsigned)((S + (int64_t)spb - 1) / spb));
+    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+    hipStream_t st = (hipStream_t)stream;
+    if (Nh <= 8)
+        k_sample_latent<8><<<grid, kLatentThreads, 0, st>>>(hmean, hcov, Nh, S, spb, k0, k1, row0, h);
+    else if (Nh <= 16)
+        k_sample_latent<16><<<grid, kLatentThreads, 0, st>>>(hmean, hcov, Nh, S, spb, k0, k1, row0, h);
+    else
+        k_sample_latent<32><<<grid, kLatentThreads, 0, st>>>(hmean, hcov, Nh, S, spb, k0, k1, row0, h);
+    return (int)hipGetLastError();
+}
+
+int qfa_continua_f32(const float *F, const float *mu, const float *h, int64_t R, int Npix, int Nh, float *out,
+                     void *workspace, size_t workspace_bytes, void *stream) {
+    if (!F || !mu || !h || !out || !workspace) return QFA_E_NULL;
+    if (R < 0 || Npix < 1 || Nh < 1 || Nh > 32) return QFA_E_SIZE;
+    if (workspace_bytes < qfa_continua_workspace_bytes(Npix, Nh)) return QFA_E_WORKSPACE;
+    if (R == 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    const int pad = pad_of(Npix);
+    float *img = (float *)workspace;
+    const int64_t n = (int64_t)(Nh + 1) * pad;
+    k_sample_image<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(F, mu, Npix, Nh, pad, img);
+    dispatch_cont<32>(Nh, img, pad, h, R, Npix, out, st);
+    return (int)hipGetLastError();
+}
+
+}  // extern "C"

@@ -7,6 +7,7 @@ here falls back to torch arithmetic when the library or the GPU is missing.
 
 Additions over the reference (none changes a reference call's result):
   * ``predict`` -- batched ``prediction_for_single_spectra``;
+  * ``sample_latent`` / ``continua_from_latent`` / ``sample_continua`` -- posterior draws on the device (include/qfa_hip.h);
   * ``step`` -- forward + Adam + clip without a host sync (what ``train`` and bench.py run);
   * data parallelism: ``enable_data_parallel()`` all-reduces the packed sum/count buffer over
     RCCL once per step before the normalisation (SURVEY.md 8(e));
@@ -493,10 +494,83 @@ class QFA(object):
             int(self.flags), _lib.current_stream(dev), evs), "qfa_predict_ex_f32")
         return ll, hmean, hcov, cont, unc
 
-    def predict_to_npz(self, dataloader, output_dir, batch_size=4096):
+    # ------------------------------------------------------------------ posterior draws
+    def sample_latent(self, hmean, hcov, n_samples, seed=0, offset=0, out=None):
+        """``n_samples`` draws h ~ N(hmean[b], hcov[b]) of every spectrum: (B, S, Nh) float32 (qfa_sample_latent_f32; the
+        draw contract is in include/qfa_hip.h).  ``offset`` is the global row of spectrum 0, so that the draws of a spectrum
+        depend only on (seed, its global row), not on how a data set is cut into calls.  ``out``: a (B, S, Nh) tensor to fill."""
+        S = int(n_samples)
+        if S < 1:
+            raise _lib.QFAHipError(f"sample_latent: n_samples = {n_samples}, expected >= 1")
+        if int(offset) < 0:
+            raise _lib.QFAHipError(f"sample_latent: offset = {offset}, expected >= 0")
+        if not 0 <= int(seed) < 2 ** 64:
+            raise _lib.QFAHipError(f"sample_latent: seed = {seed}, expected a uint64")
+        if hmean.dim() != 2 or hmean.shape[1] != self.Nh:
+            raise _lib.QFAHipError(f"hmean: shape {tuple(hmean.shape)}, expected (B, {self.Nh})")
+        B = hmean.shape[0]
+        if tuple(hcov.shape) != (B, self.Nh, self.Nh):
+            raise _lib.QFAHipError(f"hcov: shape {tuple(hcov.shape)}, expected ({B}, {self.Nh}, {self.Nh})")
+        pm = _lib.require_device_tensor(hmean, f32, "hmean")
+        pc = _lib.require_device_tensor(hcov, f32, "hcov")
+        if out is None:
+            out = torch.empty((B, S, self.Nh), dtype=f32, device=hmean.device)
+        elif tuple(out.shape) != (B, S, self.Nh):
+            raise _lib.QFAHipError(f"sample_latent(out=...): expected shape {(B, S, self.Nh)}, got {tuple(out.shape)}")
+        po = _lib.require_device_tensor(out, f32, "out")
+        _lib.check(_lib.lib().qfa_sample_latent_f32(pm, pc, B, self.Nh, S, C.c_uint64(int(seed)), int(offset), po,
+                                                    _lib.current_stream(hmean.device)), "qfa_sample_latent_f32")
+        return out
+
+    def continua_from_latent(self, h, out=None):
+        """mu + F h for latent vectors h (..., Nh): (..., Npix) float32 (qfa_continua_f32) -- the mock-continuum notebook's
+        ``F@h+mu`` for any number of vectors at once."""
+        if self.mu is None:
+            raise _lib.QFAHipError("continua_from_latent needs model.mu (load_from_npz or train first)")
+        if h.dim() < 1 or h.shape[-1] != self.Nh:
+            raise _lib.QFAHipError(f"h: shape {tuple(h.shape)}, expected (..., {self.Nh})")
+        ph = _lib.require_device_tensor(h, f32, "h")
+        R = h.numel() // self.Nh
+        shape = tuple(h.shape[:-1]) + (self.Npix,)
+        if out is None:
+            out = torch.empty(shape, dtype=f32, device=h.device)
+        elif tuple(out.shape) != shape:
+            raise _lib.QFAHipError(f"continua_from_latent(out=...): expected shape {shape}, got {tuple(out.shape)}")
+        po = _lib.require_device_tensor(out, f32, "out")
+        mu = self.mu.to(device=self.device, dtype=f32).contiguous()
+        need = _lib.lib().qfa_continua_workspace_bytes(self.Npix, self.Nh)
+        ws = self._ws.get("cont_ws")
+        if ws is None or ws.numel() < need:
+            ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+            self._ws["cont_ws"] = ws
+        _lib.check(_lib.lib().qfa_continua_f32(
+            _lib.require_device_tensor(self.F, f32, "F"), C.c_void_p(mu.data_ptr()), ph, R, self.Npix, self.Nh, po,
+            C.c_void_p(ws.data_ptr()), ws.numel(), _lib.current_stream(h.device)), "qfa_continua_f32")
+        return out
+
+    def sample_continua(self, flux=None, error=None, zabs=None, mask=None, n_samples=1, seed=0, offset=0, hmean=None,
+                        hcov=None, batch=None, zfac=None, out=None, return_latent=False):
+        """``n_samples`` continua per spectrum drawn from the posterior: (B, S, Npix) float32 (and h (B, S, Nh) with
+        ``return_latent``).  With ``hmean`` / ``hcov`` it only draws and writes; otherwise ``predict`` runs on the inputs first
+        (the four tensors, ``zfac`` or a resident ``batch``).  Bit-identical to sample_latent + continua_from_latent."""
+        if self.mu is None:
+            raise _lib.QFAHipError("sample_continua needs model.mu (load_from_npz or train first)")
+        if int(n_samples) < 1:
+            raise _lib.QFAHipError(f"sample_continua: n_samples = {n_samples}, expected >= 1")
+        if (hmean is None) != (hcov is None):
+            raise _lib.QFAHipError("sample_continua: pass hmean and hcov together")
+        if hmean is None:
+            _, hmean, hcov, _, _ = self.predict(flux, error, zabs, mask, zfac=zfac, batch=batch)
+        h = self.sample_latent(hmean, hcov, n_samples, seed=seed, offset=offset)
+        cont = self.continua_from_latent(h, out=out)
+        return (cont, h) if return_latent else cont
+
+    def predict_to_npz(self, dataloader, output_dir, batch_size=4096, n_samples=0, seed=0):
         """The predict mode of the reference's main.py:87-98 for a whole dataloader: one
         ``<basename>`` .npz per spectrum with keys ll, hmean, hcov, cont, uncertainty and the
-        reference's shapes ((1,1), (Nh,1), (Nh,Nh), (Npix,), (Npix,)); the posterior runs batched."""
+        reference's shapes ((1,1), (Nh,1), (Nh,Nh), (Npix,), (Npix,)); the posterior runs batched.
+        ``n_samples`` > 0 adds ``cont_samples`` (S, Npix): continua drawn from the posterior with ``seed``, the global row of a
+        spectrum being its dataloader index (so the files do not depend on ``batch_size``)."""
         os.makedirs(output_dir, exist_ok=True)
         n = len(dataloader)
         written = []
@@ -514,13 +588,17 @@ class QFA(object):
                 f, e, z, m = (torch.stack([it[j] for it in items]) for j in range(4))
                 paths = [it[4] for it in items]
                 res = self.predict(f, e, z, m)
+            samples = None
+            if n_samples > 0:
+                samples = self.sample_continua(n_samples=n_samples, seed=seed, offset=s, hmean=res[1], hcov=res[2]).cpu().numpy()
             ll, hmean, hcov, cont, unc = (x.cpu().numpy() for x in res)
             for r, path in enumerate(paths):
                 name = os.path.basename(str(path))
                 if not name.endswith(".npz"):
                     name += ".npz"
+                extra = {} if samples is None else {"cont_samples": samples[r]}
                 np.savez(os.path.join(output_dir, name), ll=ll[r].reshape(1, 1), hmean=hmean[r].reshape(self.Nh, 1),
-                         hcov=hcov[r], cont=cont[r], uncertainty=unc[r])
+                         hcov=hcov[r], cont=cont[r], uncertainty=unc[r], **extra)
                 written.append(name)
         return written
 
