@@ -245,6 +245,14 @@ int qfa_omega_func_f32(const float *z, const float *tau0, const float *beta, con
     return hip_status();
 }
 
+// launches whose y extent grows with the batch keep grid.y at or under 65 535 blocks (the portable limit; this runtime
+// accepted more on an MI355X) and stride over the rest
+static constexpr int QFA_GRID_Y_MAX = 65535;
+static unsigned mu_grid_y(int B, int chunk) {
+    const int n = (B + chunk - 1) / chunk;
+    return (unsigned)(n < QFA_GRID_Y_MAX ? n : QFA_GRID_Y_MAX);
+}
+
 static int fill_lyman(int which, double wav0, LymanTable *t) {
     double amp, scale, expo, off;
     switch (which) {
@@ -298,7 +306,8 @@ int qfa_zabs_factor_f32(const float *zabs, int B, int Nb, float tol, float *zq1,
     hipStream_t st = (hipStream_t)stream;
     const int n = B > Nb ? B : Nb;
     k_zfactor_derive<<<(n + 255) / 256, 256, 0, st>>>(zabs, B, Nb, zq1, pix_ratio, nbad);
-    const dim3 grid((unsigned)((Nb + 255) / 256 < 8 ? (Nb + 255) / 256 : 8), (unsigned)((B + 7) / 8));
+    const int gy = (B + 7) / 8 < QFA_GRID_Y_MAX ? (B + 7) / 8 : QFA_GRID_Y_MAX;     // (the kernel strides over the rest)
+    const dim3 grid((unsigned)((Nb + 255) / 256 < 8 ? (Nb + 255) / 256 : 8), (unsigned)gy);
     k_zfactor_check<<<grid, 256, 0, st>>>(zabs, B, Nb, zq1, pix_ratio, tol, nbad);
     return hip_status();
 }
@@ -314,7 +323,7 @@ int qfa_mu_estimate_f64(const float *flux, const float *error, const double *zqs
     hipStream_t st = (hipStream_t)stream;
     (void)hipMemsetAsync(scratch, 0, 2 * (size_t)Npix * sizeof(double), st);
     const int chunk = 64;
-    const dim3 grid((Npix + 255) / 256, (B + chunk - 1) / chunk);
+    const dim3 grid((Npix + 255) / 256, mu_grid_y(B, chunk));
     k_mu_accumulate<<<grid, 256, 0, st>>>(flux, error, zqso, wav, tab, B, Npix, Nb, (size_t)(row_stride ? row_stride : Npix), chunk,
                                           scratch, scratch + Npix);
     k_mu_finish<<<(Npix + 255) / 256, 256, 0, st>>>(scratch, scratch + Npix, Npix, window_len, mu_raw, mu_smooth);
@@ -328,7 +337,7 @@ int qfa_mu_sums_f64(const float *flux, const float *error, const double *zqso, c
     LymanTable tab;
     if (int e = fill_lyman(which, wav0, &tab)) return e;
     const int chunk = 64;
-    const dim3 grid((Npix + 255) / 256, (B + chunk - 1) / chunk);
+    const dim3 grid((Npix + 255) / 256, mu_grid_y(B, chunk));
     k_mu_accumulate<<<grid, 256, 0, (hipStream_t)stream>>>(flux, error, zqso, wav, tab, B, Npix, Nb,
                                                            (size_t)(row_stride ? row_stride : Npix), chunk, scratch, scratch + Npix);
     return hip_status();

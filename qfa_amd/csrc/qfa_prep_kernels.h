@@ -72,22 +72,25 @@ __global__ void k_build_resident(const float *__restrict__ flux, const float *__
     if (i == 0) zq1[s] = (float)(zqso[s] + 1.0);
 }
 
-// mu estimate: per pixel, sums over spectra.  grid.x over pixels, grid.y over chunks of spectra.
+// mu estimate: per pixel, sums over spectra.  grid.x over pixels, grid.y over chunks of spectra (grid-stride: grid.y is
+// clamped to 65 535, a block takes every gridDim.y-th chunk).
 __global__ void k_mu_accumulate(const float *__restrict__ flux, const float *__restrict__ error,
                                 const double *__restrict__ zqso, const double *__restrict__ wav, LymanTable tab, int B,
                                 int Npix, int Nb, size_t in_stride, int chunk, double *__restrict__ num, double *__restrict__ den) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= Npix) return;
-    const int s0 = blockIdx.y * chunk, s1 = min(B, s0 + chunk);
     const double w = wav[i];
     double a = 0.0, c = 0.0;
-    for (int s = s0; s < s1; ++s) {
-        const float f = flux[(size_t)s * in_stride + i], e = error[(size_t)s * in_stride + i];
-        const bool m = (f != -999.f) && (e != -999.f);
-        double up = 1.0;
-        if (i < Nb) up = exp(tau_total_px(tab, (zqso[s] + 1.0) * w, w));
-        if (m) a += (double)f * up;                                         // dataloader.py:110-111
-        c += (f != -999.f) ? 1.0 : 0.0;
+    for (int s0 = blockIdx.y * chunk; s0 < B; s0 += gridDim.y * chunk) {
+        const int s1 = min(B, s0 + chunk);
+        for (int s = s0; s < s1; ++s) {
+            const float f = flux[(size_t)s * in_stride + i], e = error[(size_t)s * in_stride + i];
+            const bool m = (f != -999.f) && (e != -999.f);
+            double up = 1.0;
+            if (i < Nb) up = exp(tau_total_px(tab, (zqso[s] + 1.0) * w, w));
+            if (m) a += (double)f * up;                                     // dataloader.py:110-111
+            c += (f != -999.f) ? 1.0 : 0.0;
+        }
     }
     atomicAdd(num + i, a);
     atomicAdd(den + i, c);

@@ -235,17 +235,18 @@ __global__ void k_zfactor_derive(const float *__restrict__ zabs, int B, int Nb, 
 }
 __global__ __launch_bounds__(256) void k_zfactor_check(const float *__restrict__ zabs, int B, int Nb, const float *__restrict__ zq1,
                                                        const float *__restrict__ ratio, float tol, unsigned *__restrict__ nbad) {
-    // block = 8 spectra x a strip of pixels; 4 consecutive pixels per thread where the row allows 16-byte loads
-    const int s0 = blockIdx.y * 8;
+    // block = groups of 8 spectra x a strip of pixels; grid.y is clamped to 65 535, a block takes every gridDim.y-th group
     unsigned bad = 0u;
-    for (int r = 0; r < 8; ++r) {
-        const int s = s0 + r;
-        if (s >= B) break;
-        const float zq = zq1[s];
-        const float *row = zabs + (size_t)s * Nb;
-        for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < Nb; i += gridDim.x * blockDim.x) {
-            const float a = 1.0f + row[i], d = a - zq * ratio[i];
-            if (!(fabsf(d) <= tol * a)) ++bad;
+    for (int s0 = blockIdx.y * 8; s0 < B; s0 += gridDim.y * 8) {
+        for (int r = 0; r < 8; ++r) {
+            const int s = s0 + r;
+            if (s >= B) break;
+            const float zq = zq1[s];
+            const float *row = zabs + (size_t)s * Nb;
+            for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < Nb; i += gridDim.x * blockDim.x) {
+                const float a = 1.0f + row[i], d = a - zq * ratio[i];
+                if (!(fabsf(d) <= tol * a)) ++bad;
+            }
         }
     }
     for (int o = 32; o >= 1; o >>= 1) bad += __shfl_xor(bad, o);

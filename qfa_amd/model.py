@@ -34,8 +34,10 @@ log2pi = 1.8378770664093453
 default_tau = partial(_utils.tau, which="becker")
 
 PARAM_KEYS = ("F", "Psi", "omega", "tau0", "c0", "beta")
-# default of QFA.auto_factor_zabs (tests/conftest.py turns it off: zabs tensors there are meant to exercise the zabs kernels) and
-# the relative tolerance of the structure test: three float32 roundings of 1 + z (zabs itself, zq1, pix_ratio)
+# default of QFA.auto_factor_zabs (tests/conftest.py turns it off: zabs tensors there are meant to exercise the zabs kernels;
+# tests/test_auto_factor_default.py runs the default) and the relative tolerance of the structure test: three float32 roundings of
+# 1 + z (zabs itself, zq1, pix_ratio).  The factors never serve a call made during a graph capture, a call in deterministic mode
+# or an inference tensor (QFA._auto_zfac).
 AUTO_FACTOR_ZABS = True
 AUTO_FACTOR_TOL = 4e-7
 AUTO_FACTOR_RECHECK = 64
@@ -100,7 +102,11 @@ class QFA(object):
         # tensor object, unchanged (torch's version counter) -- is tested once for the structure the reference's loader gives it,
         # 1 + zabs[s][i] = (1 + z_qso[s]) wav_i / 1215.67 (QFA/dataloader.py:102; qfa_zabs_factor_f32, one pass over it and one
         # host synchronisation), and from then on the factored-z kernels run for it.  A loader that hands out fresh tensors every
-        # step never pays anything; zabs that does not factor within AUTO_FACTOR_TOL keeps the zabs kernels.
+        # step never pays anything; zabs that does not factor within AUTO_FACTOR_TOL keeps the zabs kernels.  Three kinds of call
+        # always read zabs: a call inside a graph capture (the replays read whatever the static tensor then holds, while cached
+        # factors would be the capture-time batch's), a call with deterministic = True (the first call on a tensor and the later
+        # ones must run the same arithmetic) and a zabs made under torch.inference_mode() (no version counter to notice writes).
+        # An explicit zfac, or the one a DeviceDataloader batch carries, is used in all three.
         self.auto_factor_zabs = AUTO_FACTOR_ZABS
         self._zf_seen = {}
 
@@ -217,6 +223,9 @@ class QFA(object):
         if zabs.dtype != f32 or not zabs.is_contiguous() or zabs.dim() != 2 or zabs.shape[1] != self.Nb or zabs.shape[0] < 1 \
                 or zabs.device != self.device:
             return None
+        # (the entry is left as it is: the eager calls around a capture keep their cached pair)
+        if self.deterministic or zabs.is_inference() or torch.cuda.is_current_stream_capturing():
+            return None
         sig = (zabs.data_ptr(), tuple(zabs.shape), zabs._version)
         ent = self._zf_seen.get(id(zabs))
         if ent is None or ent[0]() is not zabs or ent[1] != sig:
@@ -231,8 +240,6 @@ class QFA(object):
         # stale pair could serve (qfa_amd's own writers bump the counter: DeviceDataloader.next_batch(out=...)).
         uses = ent[3] + 1 if len(ent) > 3 else 1
         recheck = isinstance(ent[2], tuple) and uses % AUTO_FACTOR_RECHECK == 0
-        if (ent[2] == "seen" or recheck) and torch.cuda.is_current_stream_capturing():
-            return ent[2] if isinstance(ent[2], tuple) else None          # (no host synchronisation inside a graph capture)
         if ent[2] == "seen" or recheck:
             B = int(zabs.shape[0])
             zq1 = torch.empty(B, dtype=f32, device=self.device)

@@ -610,13 +610,22 @@ def test_pass2_xdl_form_matches_f32_form_and_oracle(dev, npix, nh, B, monkeypatc
         assert rel_l2(ours[ok], ref[ok]) < TOL_G[k], k
 
 
-@pytest.mark.parametrize("npix,nh,B,flags", [(4000, 16, 20000, 0), (2000, 8, 10000, 0), (640, 32, 3000, 0), (200, 12, 70, 0),
-                                            (4000, 16, 30000, 0),                       # (default = k_grads_t from 24 576 spectra on)
-                                            (1913, 13, 2100, _lib.F_PASS2_PIXRES), (200, 12, 70, _lib.F_PASS2_PIXRES),
-                                            (1913, 8, 2100, _lib.F_PASS2_PIXRES)])
-def test_deterministic_mode_is_bit_reproducible(dev, npix, nh, B, flags):
+def _over_auto_factor(cases):
+    """each case with QFA.auto_factor_zabs off (under the case's plain id) and on (id prefixed auto_factor_on-)"""
+    return [pytest.param(*c, auto, id=("auto_factor_on-" if auto else "") + "-".join(str(v) for v in c))
+            for auto in (False, True) for c in cases]
+
+
+@pytest.mark.parametrize("npix,nh,B,flags,auto", _over_auto_factor([
+    (4000, 16, 20000, 0), (2000, 8, 10000, 0), (640, 32, 3000, 0), (200, 12, 70, 0),
+    (4000, 16, 30000, 0),                       # (default = k_grads_t from 24 576 spectra on)
+    (1913, 13, 2100, _lib.F_PASS2_PIXRES), (200, 12, 70, _lib.F_PASS2_PIXRES),
+    (1913, 8, 2100, _lib.F_PASS2_PIXRES)]))
+def test_deterministic_mode_is_bit_reproducible(dev, npix, nh, B, flags, auto):
     """QFA.deterministic = True (qfa_nll_grad_det_f32: per-block slab + fixed-order reducer instead of float32 atomics):
-    repeated runs on the same batch are BIT-identical, and agree with the default (atomic) mode to rounding."""
+    repeated runs on the same batch are BIT-identical, and agree with the default (atomic) mode to rounding.  With
+    QFA.auto_factor_zabs on (the shipped default) the same tensor objects come back every call: deterministic mode must not
+    switch them to the factored-z kernels on the second call."""
     import torch
     from qfa_amd import synthetic
     from tools import parity_sections as PS
@@ -624,12 +633,17 @@ def test_deterministic_mode_is_bit_reproducible(dev, npix, nh, B, flags):
     p, mu = synthetic.mock_parameters(npix, nb, nh, seed=nh)
     batch = synthetic.make_batch_torch(p, mu, wav, nb, B, 1234 + nh, dev, masks=True)
     m = make_model(dev, p, mu)
-    m.flags = flags
+    m.flags, m.auto_factor_zabs = flags, auto
     ref = m.accumulate(*batch).clone()
     m.deterministic = True
     runs = [m.accumulate(*batch).clone() for _ in range(4)]
     for r in runs[1:]:
         assert torch.equal(runs[0], r)
+    if auto:
+        assert m._zf_seen[id(batch[2])][2] == "seen"                 # no structure test ran in deterministic mode
+        m.deterministic = False
+        m.accumulate(*batch)                                         # the same tensor outside it: the default is live
+        assert m._zf_seen[id(batch[2])][2] is not None
     for name, sl in PS.sections(m).items():
         a, r = runs[0][sl].double().cpu().numpy(), ref[sl].double().cpu().numpy()
         if name in ("cnt", "n_blue", "n_spectra"):
@@ -640,20 +654,46 @@ def test_deterministic_mode_is_bit_reproducible(dev, npix, nh, B, flags):
             assert rel_l2(a, r) < 5e-5, (name, rel_l2(a, r))
 
 
-@pytest.mark.parametrize("npix,nh,B", [(4000, 16, 30000), (2000, 8, 12000)])
-def test_default_accumulation_of_a_large_batch_is_bit_reproducible(dev, npix, nh, B):
+@pytest.mark.parametrize("npix,nh,B,auto", _over_auto_factor([(4000, 16, 30000), (2000, 8, 12000)]))
+def test_default_accumulation_of_a_large_batch_is_bit_reproducible(dev, npix, nh, B, auto):
     """From 96 spectra per CU on (N_h <= 8: 36) pass 2 runs in its pixel-resident form (k_grads_t), whose per-range sums leave
     through slab rows and the fixed-order reducer even without a caller's slab: no float atomics anywhere in the step, so the
-    DEFAULT mode is bit-reproducible there, like QFA.deterministic = True is at every size."""
+    DEFAULT mode is bit-reproducible there, like QFA.deterministic = True is at every size.
+    With QFA.auto_factor_zabs on (the shipped default) the first call on a tensor reads zabs and the later ones the factors,
+    which is other arithmetic: calls 2, 3, ... are bit-identical to each other, a fresh model making the same calls reproduces
+    every one of them bit for bit, and call 1 agrees with call 2 to float32 rounding."""
     import torch
     from qfa_amd import synthetic
+    from tools import parity_sections as PS
     wav, nb, nr = synthetic.wavelength_grid(npix)
     p, mu = synthetic.mock_parameters(npix, nb, nh, seed=nh + 3)
-    batch = synthetic.make_batch_torch(p, mu, wav, nb, B, 4321 + nh, dev, masks=True)
+    d, e, z, mk, zq = synthetic.make_batch_torch(p, mu, wav, nb, B, 4321 + nh, dev, masks=True, return_zq=True)
+    if auto:                                                         # 1 + zabs of the reference's loader, rounded once
+        z = ((1.0 + zq.double())[:, None] * torch.tensor(wav[:nb] / synthetic.LYA, device=dev)[None, :] - 1.0).float()
+    batch = (d, e, z, mk)
     m = make_model(dev, p, mu)
-    runs = [m.accumulate(*batch).clone() for _ in range(3)]
-    assert torch.equal(runs[0], runs[1]) and torch.equal(runs[0], runs[2])
-    assert torch.isfinite(runs[0]).all()
+    m.auto_factor_zabs = auto
+    if not auto:
+        runs = [m.accumulate(*batch).clone() for _ in range(3)]
+        assert torch.equal(runs[0], runs[1]) and torch.equal(runs[0], runs[2])
+        assert torch.isfinite(runs[0]).all()
+        return
+    runs = [m.accumulate(*batch).clone() for _ in range(4)]
+    assert isinstance(m._zf_seen[id(z)][2], tuple), "calls 2.. must run the factored-z kernels"
+    assert torch.equal(runs[1], runs[2]) and torch.equal(runs[1], runs[3])
+    assert all(torch.isfinite(r).all() for r in runs)
+    m2 = make_model(dev, p, mu)
+    m2.auto_factor_zabs = True
+    for r in runs:
+        assert torch.equal(m2.accumulate(*batch), r)
+    for name, sl in PS.sections(m).items():
+        a, r = runs[1][sl].double().cpu().numpy(), runs[0][sl].double().cpu().numpy()
+        if name in ("cnt", "n_blue", "n_spectra"):
+            assert np.array_equal(a, r), name
+        elif a.size == 1:
+            assert abs(a[0] - r[0]) <= 2e-4 * abs(r[0]) + 1e-6, (name, a, r)
+        else:
+            assert rel_l2(a, r) < 2e-5, (name, rel_l2(a, r))
 
 
 @pytest.mark.parametrize("npix,nh,B", [(200, 16, 70), (97, 7, 33), (1000, 12, 130), (1913, 8, 50), (33, 3, 17),
@@ -809,11 +849,13 @@ def test_sync_flag_returns_the_calls_own_status(dev):
 
 
 @pytest.mark.parametrize("npix,nh,B,flags", [(1000, 12, 130, 0), (1913, 8, 300, 0), (640, 16, 700, _lib.F_PASS2_PIXRES), (450, 24, 70, 0)])
-def test_auto_factored_zabs_tensor_second_sighting(dev, npix, nh, B, flags):
+def test_auto_factored_zabs_second_sighting_outside_deterministic_mode(dev, npix, nh, B, flags):
     """QFA.auto_factor_zabs (round 5): a plain zabs tensor -- the reference's forward signature, QFA/model.py:74 -- runs on the zabs
     kernels the first time; the SAME live tensor, unchanged, is tested once (qfa_zabs_factor_f32) for the structure of
     QFA/dataloader.py:102 and served by the factored-z kernels from then on: results as the two input forms of one batch agree
-    (sections 2e-5, NLL 5e-6), and the oracle on zabs.  An in-place write makes the tensor new again."""
+    (sections 2e-5, NLL 5e-6), and the oracle on zabs.  An in-place write makes the tensor new again.  Deterministic mode never
+    switches the form (its calls are the bit-exact zabs-kernel reference here); the sightings are default-mode calls, whose first
+    one is the zabs kernels bit for bit in the per-spectrum NLL (pass 1 and the solve: no atomics)."""
     import torch
     from oracle import qfa_oracle as O
     from qfa_amd import synthetic
@@ -824,13 +866,20 @@ def test_auto_factored_zabs_tensor_second_sighting(dev, npix, nh, B, flags):
     m = make_model(dev, p, mu)
     m.flags, m.deterministic, m.auto_factor_zabs = flags, True, True
     bt = batch_t(b, dev)
-    nll1, nll2 = torch.empty(B, device=dev), torch.empty(B, device=dev)
-    acc1 = m.accumulate(*bt, nll=nll1).clone()
-    ent = m._zf_seen[id(bt[2])]
-    assert ent[2] == "seen"                                          # first sighting: the zabs kernels ran
+    nll1, nll2, nll0 = torch.empty(B, device=dev), torch.empty(B, device=dev), torch.empty(B, device=dev)
+    acc1 = m.accumulate(*bt, nll=nll0).clone()
+    assert id(bt[2]) not in m._zf_seen                               # deterministic mode: zabs kernels, nothing recorded
     m.auto_factor_zabs = False
     assert torch.equal(acc1, m.accumulate(*bt).clone())              # ... bit for bit what the switch-off gives
-    m.auto_factor_zabs = True
+    m.auto_factor_zabs, m.deterministic = True, False
+    acc1d = m.accumulate(*bt, nll=nll1).clone()
+    ent = m._zf_seen[id(bt[2])]
+    assert ent[2] == "seen"                                          # first sighting: the zabs kernels ran
+    assert torch.equal(nll1, nll0)                                   # ... bit for bit
+    for name, sl in PS.sections(m).items():
+        a, r = acc1d[sl].double().cpu().numpy(), acc1[sl].double().cpu().numpy()
+        if name in ("cnt", "n_blue", "n_spectra"):
+            assert np.array_equal(a, r), name
     acc2 = m.accumulate(*bt, nll=nll2).clone()
     ent = m._zf_seen[id(bt[2])]
     assert isinstance(ent[2], tuple), "a batch of the reference loader's structure must factor"
@@ -863,11 +912,15 @@ def test_auto_factored_zabs_tensor_second_sighting(dev, npix, nh, B, flags):
         assert np.max(np.abs(a - r)) <= tol * np.max(np.abs(r)), tol
     # an in-place write: torch's version counter moves, the tensor is new again (zabs kernels, bit for bit)
     bt[2].mul_(1.0)
+    nll3 = torch.empty(B, device=dev)
+    m.accumulate(*bt, nll=nll3)
+    assert m._zf_seen[id(bt[2])][2] == "seen" and torch.equal(nll3, nll0)
+    m.deterministic = True
     acc3 = m.accumulate(*bt).clone()
     assert m._zf_seen[id(bt[2])][2] == "seen" and torch.equal(acc3, acc1)
 
 
-def test_auto_factored_zabs_refuses_what_does_not_factor(dev):
+def test_auto_factored_zabs_refuses_what_does_not_factor_in_default_mode(dev):
     """zabs with ONE element moved by 2e-6 (five float32 ulp of 1 + z) does not factor: the zabs kernels keep serving it, bit for
     bit; the C-ABI counts exactly the elements that were moved, and a NaN"""
     import ctypes as C
@@ -880,8 +933,8 @@ def test_auto_factored_zabs_refuses_what_does_not_factor(dev):
     b["zabs"] = b["zabs"].copy()
     b["zabs"][37, 101] = (1.0 + b["zabs"][37, 101]) * (1.0 + 2e-6) - 1.0
     m = make_model(dev, p, mu)
-    m.deterministic = True
-    bt = batch_t(b, dev)
+    m.flags = _lib.F_PASS2_PIXRES                                     # (bit-reproducible in the default mode: no float atomics;
+    bt = batch_t(b, dev)                                              #  deterministic mode would never try to factor)
     ref = m.accumulate(*bt).clone()                                   # (conftest: auto_factor_zabs off)
     m.auto_factor_zabs = True
     a1 = m.accumulate(*bt).clone()
@@ -903,7 +956,7 @@ def test_auto_factored_zabs_refuses_what_does_not_factor(dev):
                                           C.c_void_p(nbad.data_ptr()), _lib.current_stream(dev)) == -1
 
 
-def test_auto_factored_zabs_rechecks_what_was_written_behind_torchs_back(dev, monkeypatch):
+def test_auto_factored_zabs_rechecks_raw_writes_in_default_mode(dev, monkeypatch):
     """A tensor rewritten through raw pointers keeps torch's version counter, so the cached factors would be the OLD batch's: the
     structure test is repeated every AUTO_FACTOR_RECHECK uses (here 3) and refreshes them in place; qfa_amd's own raw writer
     (DeviceDataloader.next_batch(out=...)) bumps the counter itself."""
@@ -918,7 +971,7 @@ def test_auto_factored_zabs_rechecks_what_was_written_behind_torchs_back(dev, mo
     b1 = synthetic.make_batch_numpy(p, mu, wav, nb, B, seed=22)
     b2 = synthetic.make_batch_numpy(p, mu, wav, nb, B, seed=23)
     m = make_model(dev, p, mu)
-    m.deterministic, m.auto_factor_zabs = True, True
+    m.auto_factor_zabs = True
     bt = batch_t(b1, dev)
     for _ in range(2):
         m.accumulate(*bt)
