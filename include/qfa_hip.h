@@ -105,6 +105,20 @@ typedef struct {
 #define QFA_F_ZERO_ACCUM   0x80u /* qfa_nll_grad_*: the library zeroes `accum` itself before it adds to it (inside the first
                                   * kernel of the call: one launch less than a caller-side fill -- the step of a small
                                   * batch is a chain of dependent launches a few microseconds long)                  */
+#define QFA_F_EXACT_GRAD   0x100u /* qfa_nll_grad_*: exact gradients of the reported loss instead of the reference's formulas
+                                  * (opt-in; the default keeps the reference bit for bit).  The reference (QFA/model.py:137-144)
+                                  * multiplies the F term by diag(A) once too often, uses 1 - tau0 (1+z)^beta - c0 with an extra
+                                  * zd factor in the tau0 / c0 / beta terms, and divides every element by its own count.  In this
+                                  * mode, with zd = r^2, r = 1 - c0 - exp(-t), t = tau0 (1+z)^beta, e' = dG omega 2 r (blue pixels):
+                                  *   accF  = -dNLL/dF   (k_solve writes Z = -C^-1 and p = y, so pass 2 runs unchanged;
+                                  *                       the reference's gF_i = wD A^3 f_i - wD A^2 f_i Z - A u p, Z = C^-1 T)
+                                  *   g_tau0 =  sum e' exp(-t) (1+z)^beta      (reference: -sum e (1+z)^beta, e = dG omega zd^2 2 root)
+                                  *   g_beta =  sum e' exp(-t) t ln(1+z)       (reference: -sum e tau0 (1+z)^beta ln(1+z))
+                                  *   g_c0   = -sum e'                         (reference: -sum e)
+                                  *   gPsi, gOmega, NLL: unchanged (already exact)
+                                  * and scalar slot 6 of `accum` gets +B, the way slot 5 counts spectra: the buffer carries
+                                  * its mode through an all-reduce, and qfa_finalize_grads_f32 / qfa_finalize_adam_clip_f32
+                                  * read it there (see qfa_accum_floats).                                            */
 /* (0x10: the one-wave-per-SIMD form k_grads_w of round 3, removed from the library in round 4 -- same results, 5.4 against
  *  2.15 ms at c3; the measurement is kept in profiles/r3_ablation_pass2.txt) */
 
@@ -119,8 +133,14 @@ size_t qfa_workspace_bytes(int B, int Npix, int Nh);
 
 /* number of floats in the packed accumulation buffer used by qfa_nll_grad_f32 and
  * qfa_finalize_grads_f32:  [accF Npix*Nh | sumA Npix | gPsi Npix | gOmega Nb | cnt Npix | 8 scalars]
- * scalars = {g_tau0, g_c0, g_beta, n_spectra_with_blue, sum_nll, n_spectra, 0, 0}.
- * This is the buffer a data-parallel job all-reduces (sum) across ranks once per step. */
+ * scalars = {g_tau0, g_c0, g_beta, n_spectra_with_blue, sum_nll, n_spectra, n_spectra_exact, 0}.
+ * This is the buffer a data-parallel job all-reduces (sum) across ranks once per step.
+ * n_spectra_exact (slot 6) counts the spectra of QFA_F_EXACT_GRAD launches and selects what the finalize calls compute:
+ *   slot 6 = 0        the reference's semantics (every gradient sum / count, 0/0 = NaN);
+ *   slot 6 = slot 5   exact semantics: gF = -accF, every gradient divided by n_spectra (normalize = 0: raw sums), so
+ *                     the step's gradient is that of loss = sum NLL / B; an element no spectrum observes gets 0;
+ *   otherwise         launches of both modes were added into one buffer (e.g. ranks that disagree): NaN in the loss
+ *                     and in every gradient. */
 size_t qfa_accum_floats(int Npix, int Nb, int Nh);
 
 /* Replaces the loop body of QFA.forward (reference QFA/model.py:98-103) and
@@ -167,7 +187,8 @@ int qfa_nll_grad_ex_f32(const qfa_params_t *p, const qfa_batch_t *b, const qfa_t
                         void *slab, size_t slab_bytes, unsigned flags, void *stream, void *const *events);
 
 /* Replaces the normalisation of QFA.forward (reference QFA/model.py:104): elementwise
- * grad = sum / count (0/0 = NaN), loss = sum_nll / n_spectra (model.py:100).  Reads `accum`
+ * grad = sum / count (0/0 = NaN), loss = sum_nll / n_spectra (model.py:100); exact semantics when the buffer's slot 6
+ * says so (QFA_F_EXACT_GRAD, qfa_accum_floats).  Reads `accum`
  * (after the optional all-reduce) and writes gradients with the reference's shapes.
  * normalize = 0 returns the raw sums instead (the per-spectrum gradient of
  * loglikelihood_and_gradient_for_single_spectra when accum holds one spectrum). */

@@ -27,6 +27,7 @@ ABI_VERSION = 4
 F_PASS2_F32, F_PASS2_XDL, F_S3_FAST, F_PREDICT_F32, F_SYNC = 0x1, 0x2, 0x4, 0x8, 0x20
 F_PASS2_PIXRES = 0x40
 F_ZERO_ACCUM = 0x80
+F_EXACT_GRAD = 0x100       # exact gradients of mean NLL (opt-in; QFA.exact_gradients); the buffer carries the mode in slot 6
 
 
 class QFAHipError(RuntimeError):

@@ -102,6 +102,7 @@ def main(argv=None):
     torch.cuda.set_device(device)
     dataloader = load_data(cfg, device)
     model = QFA(dataloader.Nb, dataloader.Nr, cfg.MODEL.NH, device=device, tau=partial(taufunc, which=cfg.MODEL.TAU))
+    model.exact_gradients = bool(cfg.MODEL.EXACT_GRADIENTS)
     if cfg.TYPE == "train":
         logger = logging.getLogger("qfa_amd")
         logger.setLevel(logging.INFO)

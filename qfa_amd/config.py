@@ -46,7 +46,10 @@ DEFAULTS = {                                        # reference QFA/config.py:15
               "REFERENCE_C0_QUIRK": True,
               # not in the reference: predict mode adds N_SAMPLES continua drawn from the posterior to every file
               # (cont_samples, (N_SAMPLES, Npix)); SAMPLE_SEED seeds the counter-based generator (include/qfa_hip.h)
-              "N_SAMPLES": 0, "SAMPLE_SEED": 0},
+              "N_SAMPLES": 0, "SAMPLE_SEED": 0,
+              # not in the reference: train with the exact gradient of the mean NLL instead of the reference's formulas
+              # (QFA.exact_gradients, include/qfa_hip.h QFA_F_EXACT_GRAD); off = the reference's update
+              "EXACT_GRADIENTS": False},
     "TRAIN": {"NEPOCHS": 500, "LEARNING_RATE": 1e-3, "WEIGHT_DECAY": 1e-1, "DECAY_ALPHA": 0.9, "DECAY_STEP": 10,
               "WINDOW_LENGTH_FOR_MU": 16},
 }
@@ -63,7 +66,7 @@ ARG_KEYS = {
 }
 # keys of DEFAULTS the reference does not have (tests/test_cli_config.py pins everything else against
 # tests/golden/g12_config.json, extracted from the reference's config.py / main.py)
-EXTRA_KEYS = ("MODEL.REFERENCE_C0_QUIRK", "MODEL.N_SAMPLES", "MODEL.SAMPLE_SEED")
+EXTRA_KEYS = ("MODEL.REFERENCE_C0_QUIRK", "MODEL.N_SAMPLES", "MODEL.SAMPLE_SEED", "MODEL.EXACT_GRADIENTS")
 
 
 def _set(cfg, dotted, value):

@@ -166,7 +166,9 @@ __device__ unsigned long long qfa_gt_stamps[2 * 16];
 #else
 #define GTS(i) {}
 #endif
-template <int KP, bool HASA, bool ZF, bool IDX>        // IDX: the batch carries row numbers (qfa_batch_t::rows)
+// EXACT: QFA_F_EXACT_GRAD's tau0 / c0 / beta terms.  A template argument here, not a runtime switch: as a uniform runtime select
+// the reference-mode kernel measured +1.5 % at c3 (1.629 -> 1.654 ms); the reference instantiation is the code it was before
+template <int KP, bool HASA, bool ZF, bool IDX, bool EXACT>   // IDX: the batch carries row numbers (qfa_batch_t::rows)
 __global__ __launch_bounds__(512, 2) void k_grads_t(qfa_params_t p, qfa_batch_t bt, qfa_tau_t tau, int B, int Npix, int Nb,
                                                     int Nh, GtPlan gp, const unsigned char *__restrict__ PGT,
                                                     const unsigned char *__restrict__ PST, const float4 *__restrict__ ZS,
@@ -760,17 +762,19 @@ __global__ __launch_bounds__(512, 2) void k_grads_t(qfa_params_t p, qfa_batch_t 
             const float dd = wv_ ? dv[j][r] : 0.f;
             const float sg = sgv[j][r];
             if (BLUE) {
-                float l2 = 0.f, pw, Ab, re;
+                float l2 = 0.f, pw, Ab, re, ex;
                 if (ZF) {                                                                         // qfa_common.h, ZFac
                     pw = zqy[r] * pwi[j];
                     Ab = fast_exp2(fmaf(zqx[r], ti[j], offl[j]));                                 // QFA/model.py:125
-                    re = k.omc0 - fast_exp2(k.k1 * pw);                                           // QFA/utils.py:91
+                    ex = fast_exp2(k.k1 * pw);
+                    re = k.omc0 - ex;                                                             // QFA/utils.py:91
                 } else {
                     l2 = fast_log2(1.0f + zv[j][r]);
                     pw = fast_exp2(k.beta * l2);
                     const float tauv = k.t_amp * fast_exp2(k.t_expo * (l2 + k.t_lscale)) + k.t_off;   // QFA/utils.py:105-141
                     Ab = fast_exp2(-tauv * QFA_LOG2E);                                            // QFA/model.py:125
-                    re = 1.0f - k.c0 - fast_exp2(-k.tau0 * pw * QFA_LOG2E);                       // QFA/utils.py:91
+                    ex = fast_exp2(-k.tau0 * pw * QFA_LOG2E);
+                    re = 1.0f - k.c0 - ex;                                                        // QFA/utils.py:91
                 }
                 if (HASA) Ab = bt.A_blue[(size_t)min(s0 + 4 * g + r, B - 1) * Nb + (unsigned)min(px[j], Nb - 1)];   // custom tau callable
                 const float Av = (ZF && !HASA) ? Ab : (blue[j] ? Ab : 1.f);
@@ -786,14 +790,18 @@ __global__ __launch_bounds__(512, 2) void k_grads_t(qfa_params_t p, qfa_batch_t 
                 gPsi[j] = fmaf(A2, h, gPsi[j]);                             // :139 (x 2)
                 gOm[j] = fmaf(h, zd, gOm[j]);                               // :140 (x 2)
                 const float root = fmaf(-k.tau0, pw, k.omc0);               // :141
-                const float e = h * ozd * zd * root;                        // dG (omega zd) zd 2 root
+                const float er = h * ozd * zd * root;                       // dG (omega zd) zd 2 root
+                // exact: dNLL/dzd = dG omega, dzd/dc0 = -2 re, dzd/dtau0 = 2 re exp(-t) (1+z)^beta (qfa_hip.h); a red pixel's
+                // image has omega = 0
+                const float ee = h * om[j] * re;
+                const float e = EXACT ? ee : er, et = EXACT ? -ee * ex : er;
                 if (ZF) {
-                    const float ep = e * zqy[r];
+                    const float ep = et * zqy[r];
                     e1 += ep;                                               // :142 / pwi[j]
                     e2 = fmaf(ep, zqz[r], e2);                              // :143, the spectrum's part of l2
                 } else {
-                    t_tau0 -= e * pw;                                       // :142
-                    t_beta -= e * (k.tau0 * pw * (l2 * QFA_LN2));           // :143
+                    t_tau0 -= et * pw;                                      // :142
+                    t_beta -= et * (k.tau0 * pw * (l2 * QFA_LN2));          // :143
                 }
                 t_c0 -= e;                                                  // :144
                 cnt[j] += wv_ ? 1 : 0;

@@ -248,7 +248,7 @@ __global__ __launch_bounds__(512, 2) void k_grads_x(qfa_params_t p, qfa_batch_t 
                                                     const float *__restrict__ SOL, const float4 *__restrict__ ZS,
                                                     float *__restrict__ accum,
                                                     float *__restrict__ slab, double *__restrict__ slabS,
-                                                    int slab_stride, Scal64 *__restrict__ sc64) {
+                                                    int slab_stride, Scal64 *__restrict__ sc64, int exact) {
     using C = Cfg<KP>;
     using GX = GXT<KP>;
     __shared__ __attribute__((aligned(16))) unsigned char lds[GX::L_TOTAL];
@@ -550,19 +550,21 @@ __global__ __launch_bounds__(512, 2) void k_grads_x(qfa_params_t p, qfa_batch_t 
                 float dd = wv_ ? cur.d[r][h] : 0.f;
                 const float sg = cur.sg[r][h];
                 if (BLUE) {
-                    float l2, pw, Ab, re;
+                    float l2, pw, Ab, re, ex;
                     if (ZF) {                                                                         // qfa_common.h, ZFac
                         const float4 zq = zsl[4 * g + r];
                         l2 = zq.z + l2i;
                         pw = zq.y * pwi;
                         Ab = fast_exp2(fmaf(zq.x, ti, k.offp));                                       // QFA/model.py:125
-                        re = k.omc0 - fast_exp2(k.k1 * pw);                                           // QFA/utils.py:91
+                        ex = fast_exp2(k.k1 * pw);
+                        re = k.omc0 - ex;                                                             // QFA/utils.py:91
                     } else {
                         l2 = fast_log2(1.0f + cur.z[r][h]);
                         pw = fast_exp2(k.beta * l2);
                         const float tauv = k.t_amp * fast_exp2(k.t_expo * (l2 + k.t_lscale)) + k.t_off;   // QFA/utils.py:105-141
                         Ab = fast_exp2(-tauv * QFA_LOG2E);                                            // QFA/model.py:125
-                        re = 1.0f - k.c0 - fast_exp2(-k.tau0 * pw * QFA_LOG2E);                       // QFA/utils.py:91
+                        ex = fast_exp2(-k.tau0 * pw * QFA_LOG2E);
+                        re = 1.0f - k.c0 - ex;                                                        // QFA/utils.py:91
                     }
                     if (HASA) Ab = abase[offB_of(r) + (unsigned)min(px, Nb - 1)];                     // custom tau callable
                     const float Av = blue ? Ab : 1.f;
@@ -577,9 +579,12 @@ __global__ __launch_bounds__(512, 2) void k_grads_x(qfa_params_t p, qfa_batch_t 
                     gPsi += A2 * dG;                                            // :139
                     gOm += dG * zd;                                             // :140
                     const float root = 1.0f - k.tau0 * pw - k.c0;               // :141
-                    const float e = dG * (om * zd) * zd * 2.0f * root;
-                    t_tau0 -= e * pw;                                           // :142
-                    t_beta -= e * (k.tau0 * pw * (l2 * QFA_LN2));               // :143
+                    const float er = dG * (om * zd) * zd * 2.0f * root;
+                    // exact: dNLL/dzd = dG omega, dzd/dc0 = -2 re, dzd/dtau0 = 2 re exp(-t) (1+z)^beta (qfa_hip.h)
+                    const float ee = dG * om * 2.0f * (blue ? re : 0.f);
+                    const float e = exact ? ee : er, et = exact ? -ee * ex : er;
+                    t_tau0 -= et * pw;                                          // :142
+                    t_beta -= et * (k.tau0 * pw * (l2 * QFA_LN2));              // :143
                     t_c0 -= e;                                                  // :144
                     cnt += wv_ ? 1.f : 0.f;
                     betaR[r] = wDA * Av;

@@ -51,10 +51,14 @@ void qfa_gt_prep_state(int KP, const float *SOL, int B, int Nh, unsigned char *P
 template <int KP>
 static void gt_launch(const qfa_params_t &p, const qfa_batch_t &b, const qfa_tau_t &tau, int B, int Npix, int Nb, int Nh,
                       const GtPlan &g, const unsigned char *PGT, const unsigned char *PST, const float4 *zs, float *accum,
-                      float *slab, double *slabS, int slab_stride, Scal64 *sc64, hipStream_t st) {
+                      float *slab, double *slabS, int slab_stride, Scal64 *sc64, int exact, hipStream_t st) {
     auto go = [&](auto hasa, auto zf, auto ix) {
-        k_grads_t<KP, decltype(hasa)::value, decltype(zf)::value, decltype(ix)::value><<<g.items(), 512, 0, st>>>(
-            p, b, tau, B, Npix, Nb, Nh, g, PGT, PST, zs, accum, slab, slabS, slab_stride, sc64);
+        if (exact)
+            k_grads_t<KP, decltype(hasa)::value, decltype(zf)::value, decltype(ix)::value, true><<<g.items(), 512, 0, st>>>(
+                p, b, tau, B, Npix, Nb, Nh, g, PGT, PST, zs, accum, slab, slabS, slab_stride, sc64);
+        else
+            k_grads_t<KP, decltype(hasa)::value, decltype(zf)::value, decltype(ix)::value, false><<<g.items(), 512, 0, st>>>(
+                p, b, tau, B, Npix, Nb, Nh, g, PGT, PST, zs, accum, slab, slabS, slab_stride, sc64);
     };
     using T = std::true_type;
     using F = std::false_type;
@@ -64,12 +68,12 @@ static void gt_launch(const qfa_params_t &p, const qfa_batch_t &b, const qfa_tau
 }
 void qfa_gt_launch(int KP, const qfa_params_t &p, const qfa_batch_t &b, const qfa_tau_t &tau, int B, int Npix, int Nb, int Nh,
                    int max_ranges, const unsigned char *PGT, const unsigned char *PST, const float *ZS, float *accum,
-                   float *slab, double *slabS, int slab_stride, Scal64 *sc64, hipStream_t st, int *ranges_out) {
+                   float *slab, double *slabS, int slab_stride, Scal64 *sc64, int exact, hipStream_t st, int *ranges_out) {
     const GtPlan g = gt_plan(KP, B, Npix, max_ranges);
     if (ranges_out) *ranges_out = g.R;
     const float4 *zs = reinterpret_cast<const float4 *>(ZS);
-    if (KP == 8) gt_launch<8>(p, b, tau, B, Npix, Nb, Nh, g, PGT, PST, zs, accum, slab, slabS, slab_stride, sc64, st);
-    else gt_launch<16>(p, b, tau, B, Npix, Nb, Nh, g, PGT, PST, zs, accum, slab, slabS, slab_stride, sc64, st);
+    if (KP == 8) gt_launch<8>(p, b, tau, B, Npix, Nb, Nh, g, PGT, PST, zs, accum, slab, slabS, slab_stride, sc64, exact, st);
+    else gt_launch<16>(p, b, tau, B, Npix, Nb, Nh, g, PGT, PST, zs, accum, slab, slabS, slab_stride, sc64, exact, st);
 }
 
 #if QFA_GT_STAMPS

@@ -24,10 +24,11 @@ static void gx_launch(const qfa_params_t &p, const qfa_batch_t &b, const qfa_tau
 #define QFA_WITH_GFORM 0
 #endif
     const bool fast = QFA_WITH_GFORM && (flags & QFA_F_S3_FAST) != 0;
+    const int exact = (flags & QFA_F_EXACT_GRAD) ? 1 : 0;
     if (prep) k_prep_pgx<KP><<<ntiles32, 256, 0, st>>>(p.F, p.Psi, p.omega, ZP, Npix, Nb, Nh, fast ? 0 : 1, PGX);
     auto go = [&](auto hasa, auto terms, auto zf) {
         k_grads_x<KP, decltype(hasa)::value, decltype(terms)::value, decltype(zf)::value><<<wp.items(), 512, 0, st>>>(
-            p, b, tau, B, Npix, Nb, Nh, ntiles32, wp, PGX, SOL, ZS, accum, slab, slabS, slab_stride, sc64);
+            p, b, tau, B, Npix, Nb, Nh, ntiles32, wp, PGX, SOL, ZS, accum, slab, slabS, slab_stride, sc64, exact);
     };
     using T6 = std::integral_constant<int, 6>;
 #if QFA_WITH_GFORM

@@ -27,7 +27,7 @@ void qfa_gt_prep_image(int KP, const qfa_params_t &p, const float *ZP, int Npix,
 void qfa_gt_prep_state(int KP, const float *SOL, int B, int Nh, unsigned char *PST, hipStream_t st);
 void qfa_gt_launch(int KP, const qfa_params_t &p, const qfa_batch_t &b, const qfa_tau_t &tau, int B, int Npix, int Nb, int Nh,
                    int max_ranges, const unsigned char *PGT, const unsigned char *PST, const float *ZS, float *accum,
-                   float *slab, double *slabS, int slab_stride, Scal64 *sc64, hipStream_t st, int *ranges_out);
+                   float *slab, double *slabS, int slab_stride, Scal64 *sc64, int exact, hipStream_t st, int *ranges_out);
 
 // posterior writer for N_h <= 16 on the XDL pipe (qfa_predict_x.h, built in qfa_gx.hip)
 size_t qfa_px_image_bytes(int KP, int ntiles32);
@@ -335,7 +335,8 @@ inline ZTables launch_zfac(const qfa_params_t &p, const qfa_batch_t &b, const qf
 // pass 1 on the XDL pipe (split-bf16 operands, 32-pixel tiles) at every N_h
 template <int KP, bool PREDICT>
 void launch_moments(const qfa_params_t &p, const qfa_batch_t &b, const qfa_tau_t &tau, const float *mu, int B, int Npix,
-                   int Nb, int Nh, const Layout &L, const ZTables &zt, float *ws, hipStream_t st, bool prep = true) {
+                   int Nb, int Nh, const Layout &L, const ZTables &zt, float *ws, hipStream_t st, bool prep = true,
+                   bool exact = false) {
     float *MOM = ws + L.oMOM;
     unsigned char *PFX = reinterpret_cast<unsigned char *>(ws + L.oPFX);
     if (prep) {
@@ -347,6 +348,15 @@ void launch_moments(const qfa_params_t &p, const qfa_batch_t &b, const qfa_tau_t
         k_prep_pfx<KP><<<L.ntiles32, 256, 0, st>>>(p.F, p.Psi, p.omega, PREDICT ? mu : nullptr, zt.ZP, -QFA_LOG2E * tau.offset, Npix, Nb, Nh, PFX);
     }
     constexpr int NW = KP <= 16 ? QFA_P1_NW : 4;      // (L.spb1 = 16 NW spectra per block)
+    // the exact-gradient step's instantiation leaves out the T-side moments where that measured faster (QFA_P1_SKIPT_EXACT_KP)
+    constexpr bool SKIP_EX = !PREDICT && KP >= QFA_P1_SKIPT_EXACT_KP;
+    if (SKIP_EX && exact) {
+        if (zt.ZS)
+            k_moments_x<KP, false, NW, true, SKIP_EX><<<L.wp1.items(), 64 * NW, 0, st>>>(p, b, tau, mu, B, L.Bpad, Npix, Nb, L.ntiles32, L.wp1, PFX, zt.ZS, MOM);
+        else
+            k_moments_x<KP, false, NW, false, SKIP_EX><<<L.wp1.items(), 64 * NW, 0, st>>>(p, b, tau, mu, B, L.Bpad, Npix, Nb, L.ntiles32, L.wp1, PFX, nullptr, MOM);
+        return;
+    }
     if (zt.ZS)
         k_moments_x<KP, PREDICT, NW, true><<<L.wp1.items(), 64 * NW, 0, st>>>(p, b, tau, mu, B, L.Bpad, Npix, Nb, L.ntiles32, L.wp1, PFX, zt.ZS, MOM);
     else
@@ -404,6 +414,9 @@ int run_nll_grad(const qfa_params_t &p, const qfa_batch_t &b, const qfa_tau_t &t
     float *PF = ws + L.oPF, *PFT = ws + L.oPFT, *MOM = ws + L.oMOM, *SOL = ws + L.oSOL, *NBL = ws + L.oNBL;
     float *nllbuf = nll ? nll : ws + L.oNLL;
     const size_t accS = (size_t)Npix * Nh + 3 * (size_t)Npix + Nb;
+    // QFA_F_EXACT_GRAD: k_solve forms Z = -C^-1, p = y; pass 2 sums the exact tau0 / c0 / beta terms; the buffer's slot 6
+    // counts the spectra of such launches (k_reduce_nll, or the solve's last block), and k_finalize* read the mode there
+    const int exact = (flags & QFA_F_EXACT_GRAD) ? 1 : 0;
     auto mark = [&](int i) {
         if (events && events[i]) (void)hipEventRecord((hipEvent_t)events[i], st);
     };
@@ -437,7 +450,7 @@ int run_nll_grad(const qfa_params_t &p, const qfa_batch_t &b, const qfa_tau_t &t
         launch_prep<KP>(p, zt.ZP, Npix, Nb, Nh, L, PF, PFT, st);
     }
     mark(1);
-    launch_moments<KP, false>(p, b, tau, nullptr, B, Npix, Nb, Nh, L, zt, ws, st, !fused);
+    launch_moments<KP, false>(p, b, tau, nullptr, B, Npix, Nb, Nh, L, zt, ws, st, !fused, exact != 0);
     mark(2);
     sum_segments<KP>(MOM, L, B, st);
     constexpr int G = 64 / KP;
@@ -449,7 +462,7 @@ int run_nll_grad(const qfa_params_t &p, const qfa_batch_t &b, const qfa_tau_t &t
     if constexpr (KP == 8 || KP == 16) {
         if (pixres) {
             k_solve<KP, false, true><<<(B + 4 * G - 1) / (4 * G), 256, 0, st>>>(MOM, SOL, nllbuf, NBL, B, Nh, nullptr, nullptr, ticket,
-                                                                               reinterpret_cast<unsigned char *>(ws + L.oPST));
+                                                                               reinterpret_cast<unsigned char *>(ws + L.oPST), nullptr, exact);
             solved = true;
         }
     }
@@ -458,13 +471,14 @@ int run_nll_grad(const qfa_params_t &p, const qfa_batch_t &b, const qfa_tau_t &t
     if constexpr (KP == 8 || KP == 16) {
         if (!solved && fused && B <= 2048) {
             k_solve<KP, false, false, true><<<(B + 4 * G - 1) / (4 * G), 256, 0, st>>>(MOM, SOL, nllbuf, NBL, B, Nh, nullptr, nullptr, ticket,
-                                                                                      nullptr, accum + accS);
+                                                                                      nullptr, accum + accS, exact);
             solved = nll_done = true;
         }
     }
-    if (!solved) k_solve<KP, false><<<(B + 4 * G - 1) / (4 * G), 256, 0, st>>>(MOM, SOL, nllbuf, NBL, B, Nh, nullptr, nullptr, ticket);
+    if (!solved) k_solve<KP, false><<<(B + 4 * G - 1) / (4 * G), 256, 0, st>>>(MOM, SOL, nllbuf, NBL, B, Nh, nullptr, nullptr, ticket,
+                                                                                nullptr, nullptr, exact);
     const int nred = B <= 2048 ? 1 : (B >= 2048 * NRED ? NRED : (B + 2047) / 2048);     // small batches: one block, no hand-over
-    if (!nll_done) k_reduce_nll<<<nred, 256, 0, st>>>(nllbuf, NBL, B, accum + accS, red, ticket);
+    if (!nll_done) k_reduce_nll<<<nred, 256, 0, st>>>(nllbuf, NBL, B, accum + accS, red, ticket, exact);
     mark(3);
     if (pixres) {
         int ranges = 0;
@@ -484,7 +498,7 @@ int run_nll_grad(const qfa_params_t &p, const qfa_batch_t &b, const qfa_tau_t &t
         double *rowsS = reinterpret_cast<double *>(reinterpret_cast<char *>(rowsb) + Dr.oS);
         qfa_gt_launch(KP, p, b, tau, B, Npix, Nb, Nh, maxr, reinterpret_cast<unsigned char *>(ws + L.oPGX),
                       reinterpret_cast<unsigned char *>(ws + L.oPST), reinterpret_cast<const float *>(zt.ZS), accum, rowsb, rowsS,
-                      (int)Dr.stride, sc64, st, &ranges);
+                      (int)Dr.stride, sc64, exact, st, &ranges);
         launch_reduce_slab(rowsb, Dr, B, qfa_gt_items(KP, B, Npix, maxr) * 8, accum, st, ranges);
         mark(4);
         return hip_status(st, flags);
@@ -502,12 +516,18 @@ int run_nll_grad(const qfa_params_t &p, const qfa_batch_t &b, const qfa_tau_t &t
         float *BG = ws + L.oBG, *GG = BG + (size_t)round_up(B, 64) * L.bg_stride;
         unsigned char *IMG = reinterpret_cast<unsigned char *>(ws + L.oPGX);
         k_prep_s12<KP><<<L.ntiles32, 256, 0, st>>>(p.F, p.Psi, p.omega, zt.ZP, Npix, Nb, Nh, IMG);
-        if (b.A_blue)
-            k_s12_x<KP, true, false><<<L.wp2x.items(), 256, 0, st>>>(p, b, tau, B, Npix, Nb, Nh, L.ntiles32, L.wp2x, IMG, SOL, BG, GG, L.bg_stride, accum, slab, slabS, (int)D.stride, sc64, nullptr);
-        else if (zt.ZS)
-            k_s12_x<KP, false, true><<<L.wp2x.items(), 256, 0, st>>>(p, b, tau, B, Npix, Nb, Nh, L.ntiles32, L.wp2x, IMG, SOL, BG, GG, L.bg_stride, accum, slab, slabS, (int)D.stride, sc64, zt.ZS);
-        else
-            k_s12_x<KP, false, false><<<L.wp2x.items(), 256, 0, st>>>(p, b, tau, B, Npix, Nb, Nh, L.ntiles32, L.wp2x, IMG, SOL, BG, GG, L.bg_stride, accum, slab, slabS, (int)D.stride, sc64, nullptr);
+        auto s12 = [&](auto hasa, auto zf, auto ex) {
+            k_s12_x<KP, decltype(hasa)::value, decltype(zf)::value, decltype(ex)::value><<<L.wp2x.items(), 256, 0, st>>>(
+                p, b, tau, B, Npix, Nb, Nh, L.ntiles32, L.wp2x, IMG, SOL, BG, GG, L.bg_stride, accum, slab, slabS, (int)D.stride,
+                sc64, decltype(zf)::value ? zt.ZS : nullptr);
+        };
+        auto s12e = [&](auto hasa, auto zf) {
+            if (exact) s12(hasa, zf, std::true_type{});
+            else s12(hasa, zf, std::false_type{});
+        };
+        if (b.A_blue) s12e(std::true_type{}, std::false_type{});
+        else if (zt.ZS) s12e(std::false_type{}, std::true_type{});
+        else s12e(std::false_type{}, std::false_type{});
         for (int bh = 0; 16 * bh < Nh; ++bh) {
             if (flags & QFA_F_S3_FAST)
                 k_grads_s3<KP, 3><<<L.wp2.items(), 256, 0, st>>>(B, Npix, Nh, L.ntiles, L.wp2, bh, PFT, SOL, BG, GG, L.bg_stride, accum, slab, (int)D.stride);
@@ -518,13 +538,18 @@ int run_nll_grad(const qfa_params_t &p, const qfa_batch_t &b, const qfa_tau_t &t
         mark(4);
         return hip_status(st, flags);
     }
-    auto grads = [&](int bh, float *BG, float *GG) {       // the float32-MFMA form: custom tau table / factored z / zabs
+    auto grads_e = [&](int bh, float *BG, float *GG, auto ex) {   // the float32-MFMA form: custom tau table / factored z / zabs
+        constexpr bool E = decltype(ex)::value;
         if (b.A_blue)
-            k_grads<KP, true, false><<<L.wp2.items(), 256, 0, st>>>(p, b, tau, B, Npix, Nb, Nh, L.ntiles, L.wp2, bh, PFT, SOL, accum, slab, slabS, (int)D.stride, sc64, nullptr, BG, GG, L.bg_stride);
+            k_grads<KP, true, false, E><<<L.wp2.items(), 256, 0, st>>>(p, b, tau, B, Npix, Nb, Nh, L.ntiles, L.wp2, bh, PFT, SOL, accum, slab, slabS, (int)D.stride, sc64, nullptr, BG, GG, L.bg_stride);
         else if (zt.ZS)
-            k_grads<KP, false, true><<<L.wp2.items(), 256, 0, st>>>(p, b, tau, B, Npix, Nb, Nh, L.ntiles, L.wp2, bh, PFT, SOL, accum, slab, slabS, (int)D.stride, sc64, zt.ZS, BG, GG, L.bg_stride);
+            k_grads<KP, false, true, E><<<L.wp2.items(), 256, 0, st>>>(p, b, tau, B, Npix, Nb, Nh, L.ntiles, L.wp2, bh, PFT, SOL, accum, slab, slabS, (int)D.stride, sc64, zt.ZS, BG, GG, L.bg_stride);
         else
-            k_grads<KP, false, false><<<L.wp2.items(), 256, 0, st>>>(p, b, tau, B, Npix, Nb, Nh, L.ntiles, L.wp2, bh, PFT, SOL, accum, slab, slabS, (int)D.stride, sc64, nullptr, BG, GG, L.bg_stride);
+            k_grads<KP, false, false, E><<<L.wp2.items(), 256, 0, st>>>(p, b, tau, B, Npix, Nb, Nh, L.ntiles, L.wp2, bh, PFT, SOL, accum, slab, slabS, (int)D.stride, sc64, nullptr, BG, GG, L.bg_stride);
+    };
+    auto grads = [&](int bh, float *BG, float *GG) {
+        if (exact) grads_e(bh, BG, GG, std::true_type{});
+        else grads_e(bh, BG, GG, std::false_type{});
     };
     if constexpr (KP == 32) {
         // columns 0..15 by k_grads, which also stores beta and gamma; columns 16..31 by the stage-3-only kernel

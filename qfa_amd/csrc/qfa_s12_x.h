@@ -140,7 +140,7 @@ __global__ __launch_bounds__(256) void k_prep_s12(const float *__restrict__ F, c
 // k_s12_x.  One work item = (block of 64 spectra, range of 32-pixel tiles).  slab != NULL: deterministic mode (the
 // per-pixel sums go to row blk of the slab by plain stores, the scalar sums to slabS[item][wave][3]).
 // ------------------------------------------------------------------------------------------------
-template <int KP, bool HASA, bool ZF>
+template <int KP, bool HASA, bool ZF, bool EXACT>   // EXACT: QFA_F_EXACT_GRAD's tau0 / c0 / beta terms (as in k_grads_t)
 __global__ __launch_bounds__(256, 1) void k_s12_x(qfa_params_t p, qfa_batch_t bt, qfa_tau_t tau, int B, int Npix, int Nb,
                                                   int Nh, int ntiles, WorkPlan wp, const unsigned char *__restrict__ IMG,
                                                   const float *__restrict__ SOL, float *__restrict__ BG,
@@ -388,22 +388,28 @@ __global__ __launch_bounds__(256, 1) void k_s12_x(qfa_params_t p, qfa_batch_t bt
             const bool wv_ = inb & sv[r] & (__float_as_int(sg) >= 0);
             const float dd = wv_ ? cur.d[r][h] : 0.f;
             if (BLUE) {
-                float l2, pw, Ab, re;
+                float l2, pw, Ab, re, ex;
                 if (ZF) {                                                                         // qfa_common.h, ZFac
                     l2 = zs[r].l2 + l2iH;
                     pw = zs[r].pw * pwiH;
                     Ab = fast_exp2(fmaf(zs[r].ts, tiH, k.offp));                                  // QFA/model.py:125
-                    re = k.omc0 - fast_exp2(k.k1 * pw);                                           // QFA/utils.py:91
+                    ex = fast_exp2(k.k1 * pw);
+                    re = k.omc0 - ex;                                                             // QFA/utils.py:91
                 } else {
                     l2 = fast_log2(1.0f + cur.z[r][h]);
                     pw = fast_exp2(k.beta * l2);
                     const float tauv = k.t_amp * fast_exp2(k.t_expo * (l2 + k.t_lscale)) + k.t_off;   // QFA/utils.py:105-141
                     Ab = fast_exp2(-tauv * QFA_LOG2E);                                            // QFA/model.py:125
-                    re = 1.0f - k.c0 - fast_exp2(-k.tau0 * pw * QFA_LOG2E);                       // QFA/utils.py:91
+                    ex = fast_exp2(-k.tau0 * pw * QFA_LOG2E);
+                    re = 1.0f - k.c0 - ex;                                                        // QFA/utils.py:91
                 }
                 if (HASA) Ab = bt.A_blue[(size_t)(active ? min(s0 + 4 * g + r, B - 1) : 0) * Nb + min(px, Nb - 1)];
                 const float Av = blue ? Ab : 1.f;
                 const float zd = blue ? re * re : 0.f;
+                // exact mode: exp(-t) enters the tau0 / beta terms through pw at once (one register less across the element:
+                // with ex live the factored instantiation spilled two VGPRs)
+                const float er2 = EXACT ? 2.0f * om * (blue ? re : 0.f) : 0.f;
+                if (EXACT) pw *= ex;
                 const float A2 = Av * Av;
                 const float D = A2 * Psi + om * zd + sg * sg;
                 const float wD = wv_ ? fast_rcp(D) : 0.f;
@@ -414,9 +420,12 @@ __global__ __launch_bounds__(256, 1) void k_s12_x(qfa_params_t p, qfa_batch_t bt
                 gPsi += A2 * dG;                                            // :139
                 gOm += dG * zd;                                             // :140
                 const float root = 1.0f - k.tau0 * pw - k.c0;               // :141
-                const float e = dG * (om * zd) * zd * 2.0f * root;
-                t_tau0 -= e * pw;                                           // :142
-                t_beta -= e * (k.tau0 * pw * (l2 * QFA_LN2));               // :143
+                const float er = dG * (om * zd) * zd * 2.0f * root;
+                // exact: dNLL/dzd = dG omega, dzd/dc0 = -2 re, dzd/dtau0 = 2 re exp(-t) (1+z)^beta (qfa_hip.h); pw = (1+z)^beta exp(-t)
+                const float ee = dG * er2;
+                const float e = EXACT ? ee : er, et = EXACT ? -ee : er;
+                t_tau0 -= et * pw;                                          // :142
+                t_beta -= et * (k.tau0 * pw * (l2 * QFA_LN2));              // :143
                 t_c0 -= e;                                                  // :144
                 cnt += wv_ ? 1.f : 0.f;
                 betaR[r] = wDA * Av;

@@ -4,7 +4,15 @@
 
 // ------------------------------------------------------------------------------------------------
 // k_finalize : grad = sum / count, elementwise, 0/0 = NaN (QFA/model.py:104); loss = sum NLL / B.
+// The buffer's scalar slot 6 selects the semantics (include/qfa_hip.h, QFA_F_EXACT_GRAD): 0 = the reference's (above);
+// = slot 5 (every launch in exact mode) = the gradient of sum NLL / B: gF = -accF, everything divided by B = slot 5;
+// anything else (launches of both modes in one buffer) = NaN in the loss and in every gradient.
 // ------------------------------------------------------------------------------------------------
+enum { GMODE_REF = 0, GMODE_EXACT = 1, GMODE_MIXED = 2 };
+__device__ __forceinline__ int grad_mode(const float *accS) {
+    return accS[6] == 0.f ? GMODE_REF : (accS[6] == accS[5] ? GMODE_EXACT : GMODE_MIXED);
+}
+
 __global__ void k_finalize(const float *__restrict__ accum, const float *__restrict__ F, int Npix, int Nb, int Nh,
                            int normalize, float *__restrict__ gF, float *__restrict__ gPsi, float *__restrict__ gOm,
                            float *__restrict__ gTau0, float *__restrict__ gC0, float *__restrict__ gBeta,
@@ -16,6 +24,22 @@ __global__ void k_finalize(const float *__restrict__ accum, const float *__restr
     const float *accCnt = accOm + Nb;
     const float *accS = accCnt + Npix;
     const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int mode = grad_mode(accS);
+    if (mode != GMODE_REF) {
+        const float nan = __builtin_nanf("");
+        const float ok = mode == GMODE_EXACT ? 1.f : nan;             // (x * NaN = NaN for every x)
+        const float n = normalize ? accS[5] : 1.f;
+        if (idx < (size_t)Npix * Nh) gF[idx] = ok * (-accF[idx] / n);
+        if (idx < (size_t)Npix) gPsi[idx] = ok * (accPsi[idx] / n);
+        if (idx < (size_t)Nb) gOm[idx] = ok * (accOm[idx] / n);
+        if (idx == 0) {
+            *gTau0 = ok * (accS[0] / n);
+            *gC0 = ok * (accS[1] / n);
+            *gBeta = ok * (accS[2] / n);
+            *loss = ok * (normalize ? accS[4] / accS[5] : accS[4]);
+        }
+        return;
+    }
     if (idx < (size_t)Npix * Nh) {
         const int i = (int)(idx / Nh);
         const float v = F[idx] * accA[i] - accF[idx];
@@ -88,7 +112,9 @@ __global__ void k_finalize_adam(AdamMultiArgs a, const float *__restrict__ accum
     const float *accOm = accPsi + Npix;
     const float *accCnt = accOm + Nb;
     const float *accS = accCnt + Npix;
-    if (blockIdx.x == 0 && threadIdx.x == 0) *loss = accS[4] / accS[5];
+    const int mode = grad_mode(accS);                                     // (k_finalize)
+    const float ok = mode == GMODE_MIXED ? __builtin_nanf("") : 1.f;
+    if (blockIdx.x == 0 && threadIdx.x == 0) *loss = mode == GMODE_REF ? accS[4] / accS[5] : ok * (accS[4] / accS[5]);
     int k = 0;
 #pragma unroll
     for (int j = 1; j < 6; ++j)
@@ -97,7 +123,14 @@ __global__ void k_finalize_adam(AdamMultiArgs a, const float *__restrict__ accum
     if (i >= a.t.n[k]) return;
     const float pi = a.t.p[k][i];
     float g;
-    if (k == 0) g = (pi * accA[i / Nh] - accF[i]) / accCnt[i / Nh];        // (p[0] is F itself)
+    if (mode != GMODE_REF) {                                              // exact: the gradient of sum NLL / B
+        if (k == 0) g = -accF[i] / accS[5];
+        else if (k == 1) g = accPsi[i] / accS[5];
+        else if (k == 2) g = accOm[i] / accS[5];
+        else g = accS[k - 3] / accS[5];
+        g *= ok;
+    }
+    else if (k == 0) g = (pi * accA[i / Nh] - accF[i]) / accCnt[i / Nh];   // (p[0] is F itself)
     else if (k == 1) g = accPsi[i] / accCnt[i];
     else if (k == 2) g = accOm[i] / accCnt[i];
     else g = accS[k - 3] / accS[3];

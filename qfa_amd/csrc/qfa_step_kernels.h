@@ -188,7 +188,8 @@ __global__ __launch_bounds__(256, (KP <= 16 && QFA_SOLVE_OCC4) ? 4 : 2) void k_s
                                                float *__restrict__ nll_out, float *__restrict__ nblue_out, int B,
                                                int Nh, float *__restrict__ hmean, float *__restrict__ hcov,
                                                unsigned *__restrict__ ticket = nullptr,
-                                               unsigned char *__restrict__ PST = nullptr, float *__restrict__ scal = nullptr) {
+                                               unsigned char *__restrict__ PST = nullptr, float *__restrict__ scal = nullptr,
+                                               int exact = 0) {
     static_assert(!NLLRED || (!PREDICT && !STATE), "NLLRED: the training step of a small batch");
     using C = Cfg<KP>;
     constexpr int G = 64 / KP;
@@ -298,7 +299,14 @@ __global__ __launch_bounds__(256, (KP <= 16 && QFA_SOLVE_OCC4) ? 4 : 2) void k_s
         return;
     }
     // T column c (= row c); Z row c: Z[c][b] = sum_m Cinv[c][m] T[m][b] (float32 products of the
-    // float64-inverted C^-1: Z is stored in float32 anyway); p_c = b2_c - sum_m T[c][m] y_m
+    // float64-inverted C^-1: Z is stored in float32 anyway); p_c = b2_c - sum_m T[c][m] y_m.
+    // exact (QFA_F_EXACT_GRAD): Z = -C^-1 and p = y, so that pass 2's accF = -dNLL/dF (T and b2 are not read)
+    float Zr[KP];
+    double pc;
+    if (exact) {
+        static_for<KP>([&](auto Bq) { Zr[decltype(Bq)::value] = -(float)Cc[decltype(Bq)::value]; });
+        pc = y;
+    } else {
     float Tc[KP];
     const float *momT = mom;
     if constexpr (VIA_LDS) asm volatile("" : "+v"(momT));          // (keeps these 32 loads behind the elimination: registers)
@@ -307,9 +315,8 @@ __global__ __launch_bounds__(256, (KP <= 16 && QFA_SOLVE_OCC4) ? 4 : 2) void k_s
         const int a = r < c ? r : c, b = r < c ? c : r;
         Tc[r] = momT[C::MOM_T + pair_index(a, b, KP)];
     });
-    float Zr[KP];
     static_for<KP>([&](auto Bq) { Zr[decltype(Bq)::value] = 0.f; });
-    double pc = (double)mom[C::MOM_B2 + c];
+    pc = (double)mom[C::MOM_B2 + c];
     if constexpr (VIA_LDS) {
         // T[m][b] for every lane: the group's copy of T in LDS ([m][b], lane c stores column c = row c), read back four
         // floats at a time; y the same way through the column buffer
@@ -356,6 +363,7 @@ __global__ __launch_bounds__(256, (KP <= 16 && QFA_SOLVE_OCC4) ? 4 : 2) void k_s
             pc -= (double)Tc[m] * group_bcast<KP>(y, m);
         });
     }
+    }
     if (valid) {
         static_for<KP>([&](auto Bq) {
             constexpr int b = decltype(Bq)::value;
@@ -399,6 +407,7 @@ __global__ __launch_bounds__(256, (KP <= 16 && QFA_SOLVE_OCC4) ? 4 : 2) void k_s
             scal[3] += (float)tb;
             scal[4] += (float)ta;
             scal[5] += (float)B;
+            if (exact) scal[6] += (float)B;                      // the buffer's mode (include/qfa_hip.h, QFA_F_EXACT_GRAD)
         }
     }
 }
@@ -412,7 +421,7 @@ __global__ __launch_bounds__(256, (KP <= 16 && QFA_SOLVE_OCC4) ? 4 : 2) void k_s
 constexpr int NRED = 32;
 static __global__ __launch_bounds__(256) void k_reduce_nll(const float *__restrict__ nll, const float *__restrict__ nblue,
                                                            int B, float *__restrict__ scal, double *__restrict__ part,
-                                                           unsigned *__restrict__ ticket) {
+                                                           unsigned *__restrict__ ticket, int exact) {
     __shared__ double sh[2][4];
     __shared__ bool last;
     const int per = (B + (int)gridDim.x - 1) / (int)gridDim.x, s0 = blockIdx.x * per, s1 = min(B, s0 + per);
@@ -445,6 +454,7 @@ static __global__ __launch_bounds__(256) void k_reduce_nll(const float *__restri
             scal[3] += (float)tb;
             scal[4] += (float)ta;
             scal[5] += (float)B;
+            if (exact) scal[6] += (float)B;                       // the buffer's mode (include/qfa_hip.h, QFA_F_EXACT_GRAD)
         }
     }
 }
@@ -478,7 +488,7 @@ struct SpecRegs2 {
 struct PixPar {                  // per-pixel parameters of the lane's pixel: Psi, omega and (factored-z form) ti, pwi, l2i
     float Psi, om, ti, pwi, l2i;
 };
-template <int KP, bool HASA, bool ZF>
+template <int KP, bool HASA, bool ZF, bool EXACT>   // EXACT: QFA_F_EXACT_GRAD's tau0 / c0 / beta terms (as in k_grads_t)
 __global__ __launch_bounds__(256, KP > 16 ? 1 : (KP == 8 ? QFA_G8_OCC : 2)) void k_grads(qfa_params_t p, qfa_batch_t bt, qfa_tau_t tau, int B,
                                                               int Npix, int Nb, int Nh, int ntiles, WorkPlan wp,
                                                               int bhalf, const float *__restrict__ PFT,
@@ -747,6 +757,7 @@ __global__ __launch_bounds__(256, KP > 16 ? 1 : (KP == 8 ? QFA_G8_OCC : 2)) void
             float t_tau0 = 0.f, t_c0 = 0.f, t_beta = 0.f;
             // two elements per chunk (independent dependency chains back to back), two MFMA slots after it
             float dd[4], l2[4], x1[4], x2[4], pw[4], y1[4], y2[4], Av[4], zd[4], A2[4], wD[4], wDA[4], uu[4], dG[4];
+            float rex[4], exv[4];                    // exact mode: 1 - c0 - exp(-t) (0 on red pixels) and exp(-t)
             bool wv_[4];
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
@@ -788,9 +799,12 @@ __global__ __launch_bounds__(256, KP > 16 ? 1 : (KP == 8 ? QFA_G8_OCC : 2)) void
                     for (int r = rp; r < rp + 2; ++r) {           // chunk 2
                         float Ab = fast_exp2(y1[r]);                                   // QFA/model.py:125
                         if (HASA) Ab = abase[offB[r] + min(px, Nb - 1)];               // custom tau callable
-                        const float re = 1.0f - k.c0 - fast_exp2(y2[r]);               // QFA/utils.py:91
+                        const float ex = fast_exp2(y2[r]);
+                        const float re = 1.0f - k.c0 - ex;                             // QFA/utils.py:91
                         Av[r] = blue ? Ab : 1.f;
                         zd[r] = blue ? re * re : 0.f;
+                        rex[r] = blue ? re : 0.f;
+                        exv[r] = ex;
                         pin(Av[r], zd[r]);
                     }
                     slots(2);
@@ -817,9 +831,12 @@ __global__ __launch_bounds__(256, KP > 16 ? 1 : (KP == 8 ? QFA_G8_OCC : 2)) void
 #pragma unroll
                     for (int r = rp; r < rp + 2; ++r) {           // chunk 5
                         const float root = 1.0f - k.tau0 * pw[r] - k.c0;               // :141
-                        const float e = dG[r] * (om * zd[r]) * zd[r] * 2.0f * root;
-                        t_tau0 -= e * pw[r];                                           // :142
-                        t_beta -= e * (k.tau0 * pw[r] * (l2[r] * QFA_LN2));            // :143
+                        const float er = dG[r] * (om * zd[r]) * zd[r] * 2.0f * root;
+                        // exact: dNLL/dzd = dG omega, dzd/dc0 = -2 re, dzd/dtau0 = 2 re exp(-t) (1+z)^beta (qfa_hip.h)
+                        const float ee = dG[r] * om * 2.0f * rex[r];
+                        const float e = EXACT ? ee : er, et = EXACT ? -ee * exv[r] : er;
+                        t_tau0 -= et * pw[r];                                          // :142
+                        t_beta -= et * (k.tau0 * pw[r] * (l2[r] * QFA_LN2));           // :143
                         t_c0 -= e;                                                     // :144
                     }
                     pin(t_tau0, t_beta, t_c0);

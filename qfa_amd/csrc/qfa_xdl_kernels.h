@@ -406,6 +406,9 @@ __device__ __forceinline__ void acc_add(f32x4 &acc, const f32x4 &t) {
 #ifndef QFA_P1_SKIPT_KP
 #define QFA_P1_SKIPT_KP 16     // prediction leaves out the T-side moments from this KP on (8: measured equal to 2.5 % slower, with or without an occupancy cap)
 #endif
+#ifndef QFA_P1_SKIPT_EXACT_KP
+#define QFA_P1_SKIPT_EXACT_KP 8    // the exact-gradient step (QFA_F_EXACT_GRAD) at every N_h: measured faster or equal
+#endif
 #ifndef QFA_P1_PIPE
 #define QFA_P1_PIPE 1          // MFMA phase of pass 1 (N_h <= 16) as an explicit pipeline over the column tiles (mfmas_pipe)
 #endif
@@ -439,7 +442,9 @@ __device__ unsigned long long qfa_p1_stamps[2 * 16];
 #else
 #define P1S(i) {}
 #endif
-template <int KP, bool PREDICT, int NW, bool ZF>      // ZF: factored-z input form (ZS = per-spectrum factors; zabs is not read)
+// ZF: factored-z input form (ZS = per-spectrum factors; zabs is not read).  EXACT: the step of QFA_F_EXACT_GRAD, whose solve
+// reads neither T nor b2
+template <int KP, bool PREDICT, int NW, bool ZF, bool EXACT = false>
 __global__ __launch_bounds__(64 * NW, (KP > 16 || NW == 8) ? 1 : 2) void k_moments_x(qfa_params_t p, qfa_batch_t bt, qfa_tau_t tau,
                                                       const float *__restrict__ mu, int B, int Bpad, int Npix, int Nb,
                                                       int ntiles, WorkPlan wp, const unsigned char *__restrict__ PFX,
@@ -503,7 +508,7 @@ __global__ __launch_bounds__(64 * NW, (KP > 16 || NW == 8) ? 1 : 2) void k_momen
         // the T-side moments (T, b2: weights wD A^3, wD A^2 d) feed the gradients only -- the prediction instantiation
         // (k_solve<KP, true> reads C, b and the scalars) leaves them out: half the MFMAs and two of four splits on a blue tile
         // (N_h <= 8 keeps them: the tile step is VALU-bound there and without them pass 1 measured 2.5 % slower, DESI shape)
-        constexpr bool TSIDE = BLUE && !(PREDICT && KP >= QFA_P1_SKIPT_KP);
+        constexpr bool TSIDE = BLUE && !(PREDICT && KP >= QFA_P1_SKIPT_KP) && !(EXACT && KP >= QFA_P1_SKIPT_EXACT_KP);
         const int n = tb - ta;
         if (n <= 0) return;                                       // block-uniform
 
@@ -1025,7 +1030,7 @@ __global__ __launch_bounds__(64 * NW, (KP > 16 || NW == 8) ? 1 : 2) void k_momen
         __syncthreads();
     };
     run(std::false_type{}, max(t0, nbt), t1);
-    constexpr bool SKIPT = PREDICT && KP >= QFA_P1_SKIPT_KP;
+    constexpr bool SKIPT = (PREDICT && KP >= QFA_P1_SKIPT_KP) || (EXACT && KP >= QFA_P1_SKIPT_EXACT_KP);
     if (!SKIPT) {
 #pragma unroll
         for (int t = 0; t < C::NT; ++t) accT[t] = accC[t];

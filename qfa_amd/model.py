@@ -93,6 +93,11 @@ class QFA(object):
         # (qfa_nll_grad_det_f32): bit-identical sums from run to run, at the price of a (B/64) x accum-sized slab
         # (8..64 rows where pass 2 is pixel-resident -- large batches; there the default has no atomics either)
         self.deterministic = False
+        # exact_gradients=True: the gradient of the loss the step reports, mean NLL over the batch (QFA_F_EXACT_GRAD), instead of
+        # the reference's formulas (QFA/model.py:137-144: an extra diag(A) in the F term, 1 - tau0 (1+z)^beta - c0 and an extra zd
+        # in the tau0 / c0 / beta terms, every element divided by its own count, 0/0 = NaN).  The packed buffer records the mode
+        # (scalar slot 6), so forward / step / update_from_accum / train follow it with no other switch.  Not saved in checkpoints.
+        self.exact_gradients = False
         # kernel-form switches of the *_ex_f32 entry points (_lib.F_*; 0 = defaults): A/B timing, cross-checks in tests/
         self.flags = 0
         # use the factored-z input form when a batch carries it (DeviceDataloader batches, or zfac=...): same results to
@@ -369,13 +374,17 @@ class QFA(object):
         self._dp_checked = False
 
     def check_replicas(self, optimizer=None):
-        """Raise unless every rank holds bit-identical parameters (and Adam state): a collective, call it on all ranks."""
+        """Raise unless every rank holds bit-identical parameters (and Adam state) and the same ``exact_gradients``: a
+        collective, call it on all ranks."""
         from .distributed import agree_on_layout, replicas_in_sync
         agree_on_layout(self._replica_tensors(optimizer), self._dp_group)
         ts = [t for t in self._replica_tensors(optimizer) if t.numel()]
+        # the gradient mode too: ranks that disagree would add both kinds of sums into one buffer (finalize: NaN)
+        ts.append(torch.tensor([1.0 if self.exact_gradients else 0.0], dtype=torch.float64, device=self.device))
         if not replicas_in_sync(ts, self._dp_group):
-            raise _lib.QFAHipError("data-parallel replicas differ (parameters / mu / Adam state): call "
-                                   "sync_replicas(optimizer) after random_init_func / load_* on every rank")
+            raise _lib.QFAHipError("data-parallel replicas differ (parameters / mu / Adam state / exact_gradients): call "
+                                   "sync_replicas(optimizer) after random_init_func / load_* on every rank, and set "
+                                   "exact_gradients alike")
         self._dp_checked = True
 
     def accumulate(self, delta=None, error=None, zabs=None, mask=None, accum=None, nll=None, events=None, zfac=None,
@@ -409,7 +418,8 @@ class QFA(object):
         _lib.check(_lib.lib().qfa_nll_grad_ex_f32(
             C.byref(ps), C.byref(bs), C.byref(self._tau_model), B, self.Npix, self.Nb, self.Nh,
             C.c_void_p(nll.data_ptr()) if nll is not None else None, C.c_void_p(acc.data_ptr()),
-            C.c_void_p(ws.data_ptr()), ws.numel(), slab, slab_bytes, int(self.flags) | zero_flag,
+            C.c_void_p(ws.data_ptr()), ws.numel(), slab, slab_bytes,
+            int(self.flags) | zero_flag | (_lib.F_EXACT_GRAD if self.exact_gradients else 0),
             _lib.current_stream(self.device), evs), "qfa_nll_grad_ex_f32")
         return acc
 
@@ -821,7 +831,8 @@ class StepGraph(object):
     def _key(self):
         # everything the captured launches bake in: scalars passed by value and every buffer address
         m, o = self.model, self.opt
-        return ((o.i, float(o.scheduled_lr), float(o.b1), float(o.b2), float(o.eps), float(o.weight_decay))
+        return ((o.i, float(o.scheduled_lr), float(o.b1), float(o.b2), float(o.eps), float(o.weight_decay),
+                 bool(m.exact_gradients))
                 + tuple(getattr(m, k).data_ptr() for k in PARAM_KEYS)
                 + tuple(o.m[k].data_ptr() for k in PARAM_KEYS) + tuple(o.v[k].data_ptr() for k in PARAM_KEYS)
                 + (tuple(t.data_ptr() for t in (self.rb.delta, self.rb.error, self.rb.mask, self.rb.zq1))
