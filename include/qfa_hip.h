@@ -256,6 +256,37 @@ size_t qfa_continua_workspace_bytes(int Npix, int Nh);
 int qfa_continua_f32(const float *F, const float *mu, const float *h, int64_t R, int Npix, int Nh, float *out,
                      void *workspace, size_t workspace_bytes, void *stream);
 
+/* Closed-form EM update of the factor loadings F (additive to ABI v4).  The reference moves every parameter with Adam
+ * (QFA/model.py:212-214); F is the one group whose M-step has a closed form.  Per batch, at the current parameters, with the
+ * posterior of the latent h of every spectrum s (y_s = C_s^-1 b_s as in qfa_predict_f32's hmean, E_s = C_s^-1 + y_s y_s^T):
+ *   S2_i  = sum_s wD_si A_si^2 E_s           (Nh x Nh, symmetric)         wD = mask / D, a masked pixel contributes an exact 0
+ *   S1_i  = sum_s wD_si A_si delta_si y_s    (Nh)                         whatever delta / error hold under the mask
+ *   cnt_i = sum_s mask_si
+ *   F_i  <- F_i + damping ((S2_i + ridge I)^-1 S1_i - F_i)
+ * S2_i f_i - S1_i is the QFA_F_EXACT_GRAD gradient d(sum_s NLL_s)/df_i: the update's fixed point is that mode's stationary
+ * point.  Psi, omega, tau0, beta, c0 are held fixed (a conditional M-step: with damping = 1, ridge = 0 the update cannot raise
+ * sum_s NLL_s of the batch the statistics were taken on).
+ *
+ * qfa_em_floats: number of floats of the packed statistics  [S2 Npix Nh Nh | S1 Npix Nh | cnt Npix | sum NLL, n_spectra, 0, 0]
+ * (sums only: the buffer a data-parallel job all-reduces); 0 = unsupported shape.  S2 is the full symmetric array, both triangles
+ * bit-equal.  qfa_em_workspace_bytes: scratch of qfa_em_stats_f32 (it contains qfa_workspace_bytes); 0 = unsupported shape.
+ *
+ * qfa_em_stats_f32 ADDS the statistics of the batch into `stats` (QFA_F_ZERO_ACCUM: overwrites instead; QFA_F_SYNC as above;
+ * any other flag: QFA_E_FLAGS) and writes the per-spectrum NLL at the parameters used to `nll` ((B,), may be NULL).  Every input
+ * form of qfa_batch_t.  The sums over the batch leave through rows of the workspace and a fixed-order reducer -- no float
+ * atomics: two calls on the same inputs give the same bits.  The same limit of 2^24 spectra per buffer as qfa_nll_grad_f32.
+ *
+ * qfa_em_update_f_f32 solves the Npix systems in float64 (Cholesky) and writes float32 F_out (Npix, Nh), which may alias F.
+ * A row with cnt_i = 0, a pivot <= 0 or a non-finite solution is copied from F unchanged; *n_skipped (device memory, zeroed by
+ * the call; may be NULL) counts such rows.  ridge >= 0.
+ * Neither call synchronises or allocates (graph-capturable). */
+size_t qfa_em_floats(int Npix, int Nh);
+size_t qfa_em_workspace_bytes(int B, int Npix, int Nh);
+int qfa_em_stats_f32(const qfa_params_t *p, const qfa_batch_t *b, const qfa_tau_t *tau, int B, int Npix, int Nb, int Nh,
+                     float *stats, float *nll, void *workspace, size_t workspace_bytes, unsigned flags, void *stream);
+int qfa_em_update_f_f32(const float *stats, const float *F, int Npix, int Nh, double ridge, double damping, float *F_out,
+                        unsigned *n_skipped, void *stream);
+
 /* Replaces Adam.update (reference QFA/optimizer.py:37-52) followed by the clamp of QFA.clip
  * (QFA/model.py:233-241) for ONE tensor of n elements:
  *   g' = g + wd*p; m = (1-b1) g' + b1 m; v = (1-b2) g'^2 + b2 v;

@@ -120,7 +120,8 @@ def main(argv=None):
             # as main.py:83: the reference re-randomises even after a resume (quirk Q8); a checkpoint of this
             # package that carries the Adam state (QFA.save_checkpoint) continues instead
             model.random_init_func()
-        model.train(optimizer, dataloader, cfg.TRAIN.NEPOCHS, cfg.DATA.OUTPUT_DIR, logger=logger)
+        model.train(optimizer, dataloader, cfg.TRAIN.NEPOCHS, cfg.DATA.OUTPUT_DIR, logger=logger,
+                    f_update=str(cfg.TRAIN.F_UPDATE), em_rho=float(cfg.TRAIN.EM_RHO), em_ridge=float(cfg.TRAIN.EM_RIDGE))
     else:
         print(f"try to predict {len(dataloader)} spectra...")
         print(f"=> Resume from {cfg.MODEL.RESUME}")

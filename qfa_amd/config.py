@@ -51,7 +51,10 @@ DEFAULTS = {                                        # reference QFA/config.py:15
               # (QFA.exact_gradients, include/qfa_hip.h QFA_F_EXACT_GRAD); off = the reference's update
               "EXACT_GRADIENTS": False},
     "TRAIN": {"NEPOCHS": 500, "LEARNING_RATE": 1e-3, "WEIGHT_DECAY": 1e-1, "DECAY_ALPHA": 0.9, "DECAY_STEP": 10,
-              "WINDOW_LENGTH_FOR_MU": 16},
+              "WINDOW_LENGTH_FOR_MU": 16,
+              # not in the reference: "em" = F by its closed-form EM update, Adam for the other parameters (QFA.train
+              # f_update / em_rho / em_ridge); "adam" = the reference's loop
+              "F_UPDATE": "adam", "EM_RHO": 1.0, "EM_RIDGE": 0.0},
 }
 
 # command-line flag -> config key (reference QFA/config.py:92-139)
@@ -66,7 +69,8 @@ ARG_KEYS = {
 }
 # keys of DEFAULTS the reference does not have (tests/test_cli_config.py pins everything else against
 # tests/golden/g12_config.json, extracted from the reference's config.py / main.py)
-EXTRA_KEYS = ("MODEL.REFERENCE_C0_QUIRK", "MODEL.N_SAMPLES", "MODEL.SAMPLE_SEED", "MODEL.EXACT_GRADIENTS")
+EXTRA_KEYS = ("MODEL.REFERENCE_C0_QUIRK", "MODEL.N_SAMPLES", "MODEL.SAMPLE_SEED", "MODEL.EXACT_GRADIENTS",
+              "TRAIN.F_UPDATE", "TRAIN.EM_RHO", "TRAIN.EM_RIDGE")
 
 
 def _set(cfg, dotted, value):

@@ -21,6 +21,22 @@ const double kLymanLam[30] = {1215.6701, 1025.7222, 972.5367, 949.7430, 937.8034
 
 }  // namespace
 
+// the E-step of the EM update of F (qfa_estep.h; called by qfa_em.hip)
+int qfa_estep_check(const qfa_params_t *p, const qfa_batch_t *b, const qfa_tau_t *tau, int B, int Npix, int Nb, int Nh) {
+    if (!p || !b || !tau) return QFA_E_NULL;
+    if (!p->F || !p->Psi || !p->tau0 || !p->c0 || !p->beta || (Nb > 0 && !p->omega)) return QFA_E_NULL;
+    if (int e = check_batch(*b, Npix, Nb)) return e;
+    return check_shape(B, Npix, Nb, Nh);
+}
+
+int qfa_estep(const qfa_params_t &p, const qfa_batch_t &b, const qfa_tau_t &tau, int B, int Npix, int Nb, int Nh, float *nll,
+              float *ws, hipStream_t st, QfaEStep *out) {
+    const qfa_batch_t bb = norm_batch(b, Npix);
+    if (kp_for(Nh) == 8) return run_estep<8>(p, bb, tau, B, Npix, Nb, Nh, nll, ws, st, out);
+    if (kp_for(Nh) == 16) return run_estep<16>(p, bb, tau, B, Npix, Nb, Nh, nll, ws, st, out);
+    return qfa_k32_estep(p, bb, tau, B, Npix, Nb, Nh, nll, ws, st, out);
+}
+
 extern "C" {
 
 #if QFA_P1_STAMPS

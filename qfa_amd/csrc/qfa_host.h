@@ -6,6 +6,7 @@
 #include "qfa_step_kernels.h"
 #include "qfa_xdl_kernels.h"
 #include "qfa_s12_x.h"
+#include "qfa_estep.h"
 
 // pass 2 for N_h <= 16 with every contraction on the XDL pipe (qfa_grads_x.h: KP = 8 or 16, built in qfa_gx.hip)
 size_t qfa_gx_image_bytes(int KP, int ntiles32);
@@ -607,6 +608,32 @@ int run_predict(const qfa_params_t &p, const float *mu, const qfa_batch_t &b, co
     return hip_status(st, flags);
 }
 
+// The E-step of the EM update of F (qfa_em.hip): the training step's images + pass 1 + solve with the existing kernels (the
+// exact-gradient flavour: pass 1 without the T-side moments where that instantiation exists, the solve's record [y | C^-1' | ..]
+// in SOL) -- no pass 2, no continuum writer.  `nll` (B floats, or NULL = the workspace's own row) gets the per-spectrum NLL.
+template <int KP>
+int run_estep(const qfa_params_t &p, const qfa_batch_t &b, const qfa_tau_t &tau, int B, int Npix, int Nb, int Nh, float *nll,
+              float *ws, hipStream_t st, QfaEStep *out) {
+    const Layout L = make_layout_t<KP>(B, Npix);
+    float *MOM = ws + L.oMOM, *SOL = ws + L.oSOL, *NBL = ws + L.oNBL;
+    float *nllbuf = nll ? nll : ws + L.oNLL;
+    const ZTables zt = launch_zfac(p, b, tau, B, Nb, L, ws, st);
+    launch_moments<KP, false>(p, b, tau, nullptr, B, Npix, Nb, Nh, L, zt, ws, st, true, true);
+    sum_segments<KP>(MOM, L, B, st);
+    constexpr int G = 64 / KP;
+    unsigned *ticket = reinterpret_cast<unsigned *>(reinterpret_cast<double *>(ws + L.oRED) + 2 * NRED);
+    k_solve<KP, false><<<(B + 4 * G - 1) / (4 * G), 256, 0, st>>>(MOM, SOL, nllbuf, NBL, B, Nh, nullptr, nullptr, ticket, nullptr,
+                                                                 nullptr, 1);
+    out->SOL = SOL;
+    out->nsol = Cfg<KP>::NSOL;
+    out->KP = KP;
+    out->sol_ci = Cfg<KP>::SOL_CI;
+    out->ZS = zt.ZS;
+    out->ZP = zt.ZP;
+    out->nll = nllbuf;
+    out->batch = b;
+    return hip_status();
+}
 
 }  // namespace
 

@@ -59,6 +59,38 @@ def _resolve_tau(tau):
     raise TypeError("tau must be a name, qfa_amd.utils.tau (partial) or a callable")
 
 
+class EMStats(object):
+    """The packed sufficient statistics of the closed-form update of F (include/qfa_hip.h, qfa_em_floats):
+    ``buf`` = [S2 (Npix, Nh, Nh) | S1 (Npix, Nh) | cnt (Npix,) | sum NLL, n_spectra, 0, 0] -- sums only, which is what data
+    parallelism all-reduces.  ``S2``, ``S1``, ``cnt`` are views of ``buf``; ``loss`` is the (1, 1) mean NLL."""
+
+    def __init__(self, buf, Npix, Nh):
+        self.buf, self.Npix, self.Nh = buf, int(Npix), int(Nh)
+        n2, n1 = self.Npix * self.Nh * self.Nh, self.Npix * self.Nh
+        if buf.numel() != n2 + n1 + self.Npix + 4:
+            raise _lib.QFAHipError(f"EMStats: {buf.numel()} floats, expected {n2 + n1 + self.Npix + 4}")
+        self.S2 = buf[:n2].view(self.Npix, self.Nh, self.Nh)
+        self.S1 = buf[n2:n2 + n1].view(self.Npix, self.Nh)
+        self.cnt = buf[n2 + n1:n2 + n1 + self.Npix]
+        self.tail = buf[n2 + n1 + self.Npix:]
+
+    @property
+    def loss(self):
+        return (self.tail[0] / self.tail[1]).reshape(1, 1)
+
+    def clone(self):
+        return EMStats(self.buf.clone(), self.Npix, self.Nh)
+
+    def blend_(self, other, rho):
+        """self <- (1 - rho) self + rho other, in place (stochastic EM on mini-batches); rho = 1 is replacement, bit for bit."""
+        rho = float(rho)
+        if rho == 1.0:
+            self.buf.copy_(other.buf)
+        else:
+            self.buf.mul_(1.0 - rho).add_(other.buf, alpha=rho)
+        return self
+
+
 class QFA(object):
 
     def __init__(self, Nb: int, Nr: int, Nh: int, device: torch.device,
@@ -114,6 +146,8 @@ class QFA(object):
         # An explicit zfac, or the one a DeviceDataloader batch carries, is used in all three.
         self.auto_factor_zabs = AUTO_FACTOR_ZABS
         self._zf_seen = {}
+        # running statistics of train(f_update="em") (an EMStats, or None); saved by save_checkpoint when present
+        self.em_running = None
 
     # ------------------------------------------------------------------ parameters
     def random_init_func(self) -> None:
@@ -630,6 +664,8 @@ class QFA(object):
             for k in PARAM_KEYS:
                 arrs["adam_m_" + k] = optimizer.m[k].detach().cpu().numpy()
                 arrs["adam_v_" + k] = optimizer.v[k].detach().cpu().numpy()
+        if self.em_running is not None:
+            arrs["em_stats"] = self.em_running.buf.detach().cpu().numpy()
         np.savez(path, **arrs)
 
     def load_checkpoint(self, path, optimizer=None):
@@ -644,6 +680,8 @@ class QFA(object):
         if optimizer is not None and "adam_i" in f.files:
             optimizer.load_state_dict({"i": int(f["adam_i"]), "m": {k: T(f["adam_m_" + k]) for k in PARAM_KEYS},
                                        "v": {k: T(f["adam_v_" + k]) for k in PARAM_KEYS}})
+        if "em_stats" in f.files:
+            self.em_running = EMStats(T(f["em_stats"]), self.Npix, self.Nh)
         if self._dp:
             self.sync_replicas(optimizer)
 
@@ -667,18 +705,123 @@ class QFA(object):
                 setattr(self, k, new[k])
         return loss
 
+    # ------------------------------------------------------------------ closed-form EM update of F
+    def em_statistics(self, delta=None, error=None, zabs=None, mask=None, *, zfac=None, batch=None, stats=None, nll=None):
+        """Sufficient statistics of the closed-form update of F for one (shard of a) batch at the current parameters
+        (qfa_em_stats_f32): S2_i = sum_s wD A^2 (C_s^-1 + y_s y_s^T), S1_i = sum_s wD A delta y_s, cnt_i, sum NLL, B.
+        Returns an ``EMStats``; ``stats`` given: the sums are ADDED to it.  ``nll``: optional (B,) tensor for the per-spectrum
+        NLL.  Input forms, ``auto_factor_zabs`` and graph capture as ``accumulate``; no float atomics in any mode."""
+        ps = self._params_struct()
+        if batch is not None:
+            B = batch.B
+            bs, keep = self._batch_struct_rows(batch)
+        else:
+            B = self._check_batch_shapes(delta, error, zabs, mask)
+            bs, keep = self._batch_struct(delta, error, zabs, mask, zfac)
+        h = _lib.lib()
+        need = h.qfa_em_workspace_bytes(int(B), self.Npix, self.Nh)
+        if need == 0:
+            raise _lib.QFAHipError(f"unsupported shape B={B} Npix={self.Npix} Nh={self.Nh}")
+        ws = self._ws.get("em_ws")
+        if ws is None or ws.numel() < need:
+            ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+            self._ws["em_ws"] = ws
+        flags = 0
+        if stats is None:
+            stats = EMStats(torch.empty(h.qfa_em_floats(self.Npix, self.Nh), dtype=f32, device=self.device), self.Npix, self.Nh)
+            flags = _lib.F_ZERO_ACCUM
+        elif stats.Npix != self.Npix or stats.Nh != self.Nh:
+            raise _lib.QFAHipError(f"stats of shape ({stats.Npix}, {stats.Nh}); the model has ({self.Npix}, {self.Nh})")
+        if nll is not None and (nll.dtype != f32 or nll.numel() != B or not nll.is_contiguous()):
+            raise _lib.QFAHipError(f"nll: expected a contiguous float32 tensor of {B} elements")
+        _lib.check(h.qfa_em_stats_f32(
+            C.byref(ps), C.byref(bs), C.byref(self._tau_model), int(B), self.Npix, self.Nb, self.Nh,
+            _lib.require_device_tensor(stats.buf, f32, "stats"), C.c_void_p(nll.data_ptr()) if nll is not None else None,
+            C.c_void_p(ws.data_ptr()), ws.numel(), flags | (int(self.flags) & _lib.F_SYNC),
+            _lib.current_stream(self.device)), "qfa_em_stats_f32")
+        return stats
+
+    def _em_update(self, stats, ridge=0.0, damping=1.0):
+        """F <- F + damping ((S2 + ridge I)^-1 S1 - F) in place (qfa_em_update_f_f32); the device counter of skipped rows"""
+        self._params_struct()
+        if stats.Npix != self.Npix or stats.Nh != self.Nh:
+            raise _lib.QFAHipError(f"stats of shape ({stats.Npix}, {stats.Nh}); the model has ({self.Npix}, {self.Nh})")
+        nsk = self._ws.get("em_skipped")
+        if nsk is None:
+            nsk = torch.zeros(1, dtype=torch.int32, device=self.device)
+            self._ws["em_skipped"] = nsk
+        fp = _lib.require_device_tensor(self.F, f32, "F")
+        _lib.check(_lib.lib().qfa_em_update_f_f32(
+            _lib.require_device_tensor(stats.buf, f32, "stats"), fp, self.Npix, self.Nh, float(ridge), float(damping), fp,
+            C.c_void_p(nsk.data_ptr()), _lib.current_stream(self.device)), "qfa_em_update_f_f32")
+        return nsk
+
+    def em_update_F(self, stats, ridge=0.0, damping=1.0):
+        """The closed-form M-step of F from ``stats`` (an ``EMStats``), in place on ``self.F``.  Rows no spectrum observes
+        (cnt = 0) and rows whose system is not positive definite stay as they are; returns their number (one host
+        synchronisation; during a graph capture the device counter is returned instead)."""
+        nsk = self._em_update(stats, ridge, damping)
+        if torch.cuda.is_current_stream_capturing():
+            return nsk
+        return int(nsk.item())
+
+    def _em_global(self, delta, error, zabs, mask, zfac=None, batch=None):
+        """statistics of the (global) batch: this rank's sums, all-reduced under data parallelism"""
+        if (batch.B if batch is not None else delta.shape[0]) == 0:
+            if not self._dp:
+                raise _lib.QFAHipError("em_step: empty batch")
+            st = EMStats(torch.zeros(_lib.lib().qfa_em_floats(self.Npix, self.Nh), dtype=f32, device=self.device),
+                         self.Npix, self.Nh)
+        else:
+            st = self.em_statistics(delta, error, zabs, mask, zfac=zfac, batch=batch)
+        if self._dp:
+            from .distributed import all_reduce_accum
+            all_reduce_accum(st.buf, self._dp_group)
+        return st
+
+    def em_step(self, delta=None, error=None, zabs=None, mask=None, *, zfac=None, batch=None, ridge=0.0, damping=1.0):
+        """One EM step of F on a batch: statistics (all-reduced under ``enable_data_parallel``) and the closed-form update, all
+        on the device, no host sync.  Returns the (1, 1) mean NLL at the parameters the statistics were taken with, as
+        ``step`` reports it.  The other parameters stay as they are."""
+        st = self._em_global(delta, error, zabs, mask, zfac, batch)
+        self._em_update(st, ridge, damping)
+        return st.loss
+
+    def _train_step_em(self, optimizer, batch_args, em_rho, em_ridge):
+        """``train(f_update="em")``: Adam + clip for Psi, omega, tau0, beta, c0 (F left out of the tensor list), then, at the
+        parameters after that update, the statistics of the same batch blended into the running ones and the update of F"""
+        loss, grads = self.forward(**batch_args)
+        rest = [k for k in PARAM_KEYS if k != "F"]
+        new = optimizer.update({k: getattr(self, k) for k in rest}, {k: grads[k] for k in rest}, clip=self._clip_table())
+        for k in rest:
+            setattr(self, k, new[k])
+        st = self._em_global(batch_args.get("delta"), batch_args.get("error"), batch_args.get("zabs"), batch_args.get("mask"),
+                             batch=batch_args.get("batch"))
+        if self.em_running is None:
+            self.em_running = st
+        else:
+            self.em_running.blend_(st, em_rho)
+        self._em_update(self.em_running, em_ridge, 1.0)
+        return loss
+
     def step_graph(self, optimizer, batch_size, resident=None):
         """A captured hipGraph of one training step for batches of ``batch_size`` spectra (StepGraph)."""
         return StepGraph(self, optimizer, batch_size, resident=resident)
 
     def train(self, optimizer, dataloader, n_epochs, output_dir="./result", save_interval=5, smooth_interval=5,
-              quiet=False, logger=None, use_graph=False, graph_steps=8):
+              quiet=False, logger=None, use_graph=False, graph_steps=8, f_update="adam", em_rho=1.0, em_ridge=0.0):
         """Training loop with the reference's control flow (reference QFA/model.py:183-231):
         Niter = data_size // batch_size (quirk Q5), optimizer.step() once per epoch (Q4), early
         stop the first time the epoch-mean NLL is negative (Q6), smooth / save cadence.
         ``use_graph``: replay a captured hipGraph of the step for the full-size batches (small batches are
         launch-bound: ~15 launches of a few microseconds each); same arithmetic, parameters updated in place.
-        ``graph_steps``: consecutive steps per replay with a resident loader (StepGraph; the tail of an epoch runs eagerly)."""
+        ``graph_steps``: consecutive steps per replay with a resident loader (StepGraph; the tail of an epoch runs eagerly).
+        ``f_update``: "adam" (default: the reference's loop) or "em": Adam moves Psi, omega, tau0, beta, c0 and F gets its
+        closed-form update from the statistics of the same batch, taken after the Adam update and blended into the running
+        statistics ``self.em_running`` with ``em_rho`` (1.0 = replace), ridge ``em_ridge``; the step runs eagerly (no graph)."""
+        if f_update not in ("adam", "em"):
+            raise ValueError(f"f_update = {f_update!r}: expected 'adam' or 'em'")
+        em = f_update == "em"
         os.makedirs(output_dir, exist_ok=True)
         output_dir = os.path.join(output_dir, "checkpoints")
         os.makedirs(output_dir, exist_ok=True)
@@ -699,7 +842,7 @@ class QFA(object):
         # it depends on mu and tau only); a custom tau callable needs the materialised zabs
         resident = hasattr(dataloader, "next_batch_rows") and self._tau_callable is None and (self.use_factored_z or self.Nb == 0)
         sg = None
-        if use_graph and not self._dp:
+        if use_graph and not self._dp and not em:
             sg = StepGraph(self, optimizer, dataloader.batch_size, resident=dataloader if resident else None,
                            steps=graph_steps if resident else 1)
         # Side effects under data parallelism: the replicas are identical, so ONE rank prints, logs and writes the
@@ -722,7 +865,12 @@ class QFA(object):
             total = torch.zeros((), dtype=torch.float64, device=self.device)
             t0 = time.time()
             while dataloader.have_next_batch():
-                if sg is not None and sg.fits(dataloader):
+                if em and resident:
+                    loss = self._train_step_em(optimizer, {"batch": dataloader.next_batch_rows()}, em_rho, em_ridge)
+                elif em:
+                    d, e, z, m = dataloader.next_batch()
+                    loss = self._train_step_em(optimizer, {"delta": d, "error": e, "zabs": z, "mask": m}, em_rho, em_ridge)
+                elif sg is not None and sg.fits(dataloader):
                     loss = sg.run_next(dataloader)
                 elif resident:
                     loss = self.step(optimizer, batch=dataloader.next_batch_rows())
