@@ -44,11 +44,6 @@ extern "C" int qfa_p1_debug_stamps(unsigned long long *out) {   // diagnostic bu
     return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(qfa_p1_stamps), 16 * sizeof(unsigned long long));
 }
 #endif
-#if QFA_ABL == 7
-int qfa_debug_stamps(unsigned long long *out) {      // diagnostic build only
-    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(qfa_dbg_stamps), 64 * sizeof(unsigned long long));
-}
-#endif
 
 int qfa_abi_version(void) { return QFA_ABI_VERSION; }
 

@@ -47,17 +47,12 @@ struct Cfg {
     // order of the MFMA: KP = 16 v_mfma_f32_16x16x16_bf16 [piece][g][px][a = 4g + j], 3 x 512 bytes; KP = 32
     // v_mfma_f32_16x16x32_bf16 [piece][g][px][a = 8g + j], 3 x 1 KiB) is appended to the tile, and both parts are
     // padded to whole KiB so that the tile moves as 1-KiB LDS-DMA pieces
-#ifndef QFA_XS3_32
-#define QFA_XS3_32 1
-#endif
-    static constexpr bool XS3 = KP == 16 || (KP == 32 && QFA_XS3_32);
+    static constexpr bool XS3 = KP == 16 || KP == 32;
     static constexpr int PFT_MAIN = XS3 ? (NR * 16 + 255) / 256 * 256 : NR * 16;   // floats of the float32 part
-#ifndef QFA_S3_F16
-#define QFA_S3_F16 1       // k_grads_s3 (N_h = 17..32): F Z_s on two float16 pieces per operand, three products per spectrum instead of six
-#endif
-    // (KP = 32, QFA_S3_F16: behind the three bf16 pieces the same F as two float16 pieces of t_px F -- t_px the pixel's power of
-    // two -- and a KiB whose first 16 floats are 1 / t_px: floats 768.., 1024.., 1280..)
-    static constexpr int PFT_FP = XS3 ? (KP == 32 ? (QFA_S3_F16 ? 1536 : 768) : 512) : 0;                // floats
+    // KP = 32: k_grads_s3 takes F Z_s on two float16 pieces per operand, three products per spectrum instead of six.
+    // Behind the three bf16 pieces the tile holds the same F as two float16 pieces of t_px F (t_px: the pixel's power of two)
+    // and a KiB whose first 16 floats are 1 / t_px: floats 768.., 1024.., 1280.. from PFT_MAIN.
+    static constexpr int PFT_FP = XS3 ? (KP == 32 ? 1536 : 512) : 0;                // floats
     static constexpr int PFT_F16H = 768, PFT_F16M = 1024, PFT_F16IT = 1280;      // (floats from PFT_MAIN: the float16 pieces and 1 / t)
     static constexpr int TILE_PFT = PFT_MAIN + PFT_FP;
     // per-spectrum moment record: [C PW][T PW][b FW][b2 FW][qd, ld, n, nblue]
@@ -247,17 +242,9 @@ struct ZPSrc {
 };
 __host__ __device__ inline ZPSrc zp_table(const float4 *ZP, float offp = 0.f) { return ZPSrc{ZP, nullptr, nullptr, 0.f, offp}; }
 
-#ifndef QFA_ABL
-#define QFA_ABL 0          // timing-only ablation builds (build with make -C qfa_amd/csrc B=build/var_x OUT=../libqfa_x.so EXTRA=-DQFA_ABL=n); 0 = product
-#endif
+// (a variant library for an A/B of a build-time switch: make -C qfa_amd/csrc B=build/var_x OUT=../libqfa_x.so EXTRA=-DQFA_...=n)
 __device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) {
-#if QFA_ABL == 1           // no MFMA: keep operands alive, one VALU op instead
-    asm volatile("" ::"v"(a), "v"(b));
-    c[0] += a;
-    return c;
-#else
     return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-#endif
 }
 
 
@@ -296,25 +283,13 @@ __device__ __forceinline__ float sub_bf16_lo(float x, unsigned packed) {
 __device__ __forceinline__ float sub_bf16_hi(float x, unsigned packed) {
     return __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2, packed), __builtin_bit_cast(bf16x2, split_c_hi()), x, false);
 }
-#ifndef QFA_SPLIT_DOT2
-#define QFA_SPLIT_DOT2 1      // 0: residuals by shift / and + v_sub_f32 (11 instead of 7 instructions per pair of values)
-#endif
-// two float32 values -> three packed bf16 pairs with x = h + m + l exactly
+// two float32 values -> three packed bf16 pairs with x = h + m + l exactly (7 instructions per pair of values; the residuals by
+// shift / and + v_sub_f32 take 11)
 __device__ __forceinline__ void split2(float x0, float x1, unsigned &h, unsigned &m, unsigned &l) {
-#if QFA_ABL == 12          // timing only: no split arithmetic
-    h = __float_as_uint(x0); m = __float_as_uint(x1); l = h ^ m;
-    return;
-#endif
     h = cvt_pk_bf16(x0, x1);
-#if QFA_SPLIT_DOT2
     const float r0 = sub_bf16_lo(x0, h), r1 = sub_bf16_hi(x1, h);
     m = cvt_pk_bf16(r0, r1);
     const float s0 = sub_bf16_lo(r0, m), s1 = sub_bf16_hi(r1, m);
-#else
-    const float r0 = x0 - __uint_as_float(h << 16), r1 = x1 - __uint_as_float(h & 0xffff0000u);
-    m = cvt_pk_bf16(r0, r1);
-    const float s0 = r0 - __uint_as_float(m << 16), s1 = r1 - __uint_as_float(m & 0xffff0000u);
-#endif
     l = cvt_pk_bf16(s0, s1);
 }
 // eight float32 values -> three u32x4 of packed bf16 pieces
@@ -327,10 +302,6 @@ __device__ __forceinline__ void split8(const float (&x)[8], u32x4 &h, u32x4 &m, 
     }
 }
 __device__ __forceinline__ f32x4 xdl(const u32x4 &a, const u32x4 &b, f32x4 c) {          // K = 32
-#if QFA_ABL == 11          // timing only: no XDL MFMA
-    asm volatile("" ::"v"(a), "v"(b));
-    return c;
-#endif
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0,
                                                    0, 0);
 }
@@ -386,11 +357,6 @@ __host__ __device__ __forceinline__ float f16_weight_scale(float psi) {
     return ldexpf(1.f, 11 + e);
 }
 __device__ __forceinline__ f32x4 xdl16(const u32x2 &a, const u32x2 &b, f32x4 c) {        // K = 16
-#if QFA_ABL == 13          // timing only: no K = 16 XDL MFMA (stage 3 of pass 2)
-    asm volatile("" ::"v"(a), "v"(b));
-    c[0] += 1.f;
-    return c;
-#endif
     return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(__builtin_bit_cast(s16x4, a), __builtin_bit_cast(s16x4, b), c, 0,
                                                      0, 0);
 }

@@ -16,7 +16,7 @@
 //   * F enters once, at the end: accF[px][b] = sum_a F[px][a] W[px][a][b] + the gamma term, then ONE atomic (or slab
 //     store) per output element and spectra range -- no partial sums in LDS, no flush in the loop.
 // Per (16 spectra x 16 pixels) a wave issues 18 + 35 MFMAs (round 5: two float16 pieces and three products per contraction,
-// qfa_common.h "float16 pieces", qfa_gt_layout.h QFA_GT_F16S1 / QFA_GT_F16S3; 36 + 51 with bf16 pieces), 12 + 19 ds_read_b128 for
+// qfa_common.h "float16 pieces", qfa_gt_layout.h; 36 + 51 with bf16 pieces), 12 + 19 ds_read_b128 for
 // their streamed operands, stage 2 of four elements per lane, one float16 split (beta) and one bf16 split (gamma).
 //
 // Workgroup = 512 threads = 8 waves = 8 tiles (strided over the pixel axis: tile pb + PB w, so that every workgroup
@@ -29,13 +29,8 @@
 // requests in front of the step's barrier (round 5).  Ragged tiles (the last tile of a pixel axis that is no multiple of 16, the
 // tile that straddles the end of the blue side in the zabs form) stage 4-byte pieces through the general path.
 #pragma once
-#ifndef QFA_GT_SETPRIO
-#define QFA_GT_SETPRIO 2   // s_setprio around the MFMA stages of k_grads_t: the wave of a SIMD that is in stage 3 (or 1) issues ahead of its
-                           // partner's VALU stage -- pass 2 at c3 2.24 -> 2.16 ms, DESI shape 1.23 -> 1.19 (levels 1..3 alike; stage 3 carries it)
-#endif
-#ifndef QFA_GT_PRIO_STAGES
-#define QFA_GT_PRIO_STAGES 3   // bit 0: stage 1, bit 1: stage 3
-#endif
+// s_setprio 2 around the MFMA stages 1 and 3 of k_grads_t: the wave of a SIMD that is in stage 3 (or 1) issues ahead of its partner's
+// VALU stage -- pass 2 at c3 2.24 -> 2.16 ms, DESI shape 1.23 -> 1.19 (levels 1..3 alike; stage 3 carries it).
 #include "qfa_common.h"
 #include "qfa_xdl_kernels.h"
 #include "qfa_gt_layout.h"        // GTT, build_state
@@ -65,13 +60,13 @@ __device__ __forceinline__ void prep_pgt_body(int bid, const float *__restrict__
     const int p0 = GT::PXW * (bid / GT::TPW) + bid % GT::TPW;
     auto pixel = [&](int lo) { return p0 + GT::TPW * lo; };
     __shared__ float f[16][KP + 1];
-    __shared__ float tsc[16][3];                                     // F16S1: the pixel's power of two t, 1 / t^2, 1 / t
+    __shared__ float tsc[16][3];                                     // stage 1 (float16 pieces): the pixel's power of two t, 1 / t^2, 1 / t
     for (int i = threadIdx.x; i < 16 * KP; i += 256) {
         const int px = i / KP, a = i % KP;
         f[px][a] = (pixel(px) < Npix && a < Nh) ? F[(size_t)pixel(px) * Nh + a] : 0.f;
     }
     __syncthreads();
-    if (GT::F16S1 && threadIdx.x < 16) {
+    if (threadIdx.x < 16) {
         // t f_a in [2^6, 2^7) for the pixel's largest |f_a|: the pair products t^2 f_a f_b stay below 2^14 (float16: 65 504)
         float mx = 0.f;
         for (int a = 0; a < KP; ++a) mx = fmaxf(mx, fabsf(f[threadIdx.x][a]));
@@ -82,11 +77,11 @@ __device__ __forceinline__ void prep_pgt_body(int bid, const float *__restrict__
         tsc[threadIdx.x][1] = ldexpf(1.f, 2 * (e - 7));
         tsc[threadIdx.x][2] = ldexpf(1.f, e - 7);
     }
-    if (GT::F16S1) __syncthreads();
+    __syncthreads();
     for (int i = threadIdx.x; i < GT::NKQ * 64; i += 256) {
         const int lane = i & 63, ks = i >> 6;
         const int px = lane & 15, g = lane >> 4;
-        const float t1 = GT::F16S1 ? tsc[px][0] : 1.f, t2 = t1 * t1;
+        const float t1 = tsc[px][0], t2 = t1 * t1;
         float v[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
@@ -104,18 +99,10 @@ __device__ __forceinline__ void prep_pgt_body(int bid, const float *__restrict__
             v[j] = x;
         }
         unsigned char *dst = tile + ks * GT::BLK_B + lane * 16;
-        if constexpr (GT::F16S1) {
-            u32x4 ph, pm;
-            split8h(v, ph, pm);
-            *reinterpret_cast<u32x4 *>(dst) = ph;
-            *reinterpret_cast<u32x4 *>(dst + 1024) = pm;
-        } else {
-            u32x4 ph, pm, pl;
-            split8(v, ph, pm, pl);
-            *reinterpret_cast<u32x4 *>(dst) = ph;
-            *reinterpret_cast<u32x4 *>(dst + 1024) = pm;
-            *reinterpret_cast<u32x4 *>(dst + 2048) = pl;
-        }
+        u32x4 ph, pm;
+        split8h(v, ph, pm);
+        *reinterpret_cast<u32x4 *>(dst) = ph;
+        *reinterpret_cast<u32x4 *>(dst + 1024) = pm;
     }
     if (threadIdx.x < 128) {
         const int j = threadIdx.x, px = pixel(j & 15);
@@ -125,8 +112,8 @@ __device__ __forceinline__ void prep_pgt_body(int bid, const float *__restrict__
         else if (j < 80 && ZP.on() && px < Nb) {
             const float4 q = ZP.at(px);
             v = j < 48 ? q.x : (j < 64 ? q.y : q.z);
-        } else if (GT::F16S1 && j >= GT::PAR_IT2 && j < GT::PAR_SBETA) v = tsc[j & 15][j < GT::PAR_IT1 ? 1 : 2];
-        else if (GT::F16S3 && j >= GT::PAR_SBETA) v = f16_weight_scale(px < Npix ? Psi[px] : 1.f);       // beta <= 1 / Psi (qfa_common.h)
+        } else if (j >= GT::PAR_IT2 && j < GT::PAR_SBETA) v = tsc[j & 15][j < GT::PAR_IT1 ? 1 : 2];
+        else if (j >= GT::PAR_SBETA) v = f16_weight_scale(px < Npix ? Psi[px] : 1.f);       // beta <= 1 / Psi (qfa_common.h)
         reinterpret_cast<float *>(tile + GT::OFF_PAR)[j] = v;
     }
     float *fr = reinterpret_cast<float *>(tile + GT::OFF_F);
@@ -217,11 +204,11 @@ __global__ __launch_bounds__(512, 2) void k_grads_t(qfa_params_t p, qfa_batch_t 
 #endif
     // ---- static operands of the wave's tiles
     const unsigned char *tile[TPW];
-    u32x4 IBh[TPW][GT::NKQ], IBm[TPW][GT::NKQ], IBl[TPW][GT::NKQ];
+    u32x4 IBh[TPW][GT::NKQ], IBm[TPW][GT::NKQ];
     float Psi[TPW], om[TPW], ti[TPW], pwi[TPW], l2i[TPW], offl[TPW];
-    float it2[TPW], it1[TPW];                               // F16S1: the inverse powers of two of the lane's pixel (pairs, F)
-    float sbeta[TPW];                                       // F16S3: the power of two of the lane's pixel for beta (<= 2^12 / max beta)
-    f32x4 zfac = {1.f, 1.f, 1.f, 1.f};                      // F16S3: 2^(7 - zk) of the lane's four spectra of the group in stage 1 / 2
+    float it2[TPW], it1[TPW];                               // stage 1 (float16 pieces): the inverse powers of two of the lane's pixel (pairs, F)
+    float sbeta[TPW];                                       // stage 3 (float16 pieces): the power of two of the lane's pixel for beta (<= 2^12 / max beta)
+    f32x4 zfac = {1.f, 1.f, 1.f, 1.f};                      // stage 3 (float16 pieces): 2^(7 - zk) of the lane's four spectra of the group in stage 1 / 2
 #pragma unroll
     for (int j = 0; j < TPW; ++j) {
         tile[j] = PGT + (size_t)(active ? TPW * wt + j : 0) * GT::TILE_B;
@@ -229,12 +216,11 @@ __global__ __launch_bounds__(512, 2) void k_grads_t(qfa_params_t p, qfa_batch_t 
         for (int ks = 0; ks < GT::NKQ; ++ks) {
             IBh[j][ks] = *reinterpret_cast<const u32x4 *>(tile[j] + ks * GT::BLK_B + lane * 16);
             IBm[j][ks] = *reinterpret_cast<const u32x4 *>(tile[j] + ks * GT::BLK_B + 1024 + lane * 16);
-            IBl[j][ks] = GT::F16S1 ? u32x4{0u, 0u, 0u, 0u} : *reinterpret_cast<const u32x4 *>(tile[j] + ks * GT::BLK_B + (GT::S1NP - 1) * 1024 + lane * 16);
         }
         const float *par = reinterpret_cast<const float *>(tile[j] + GT::OFF_PAR);
         Psi[j] = par[lo]; om[j] = par[16 + lo];
-        it2[j] = GT::F16S1 ? par[GT::PAR_IT2 + lo] : 1.f; it1[j] = GT::F16S1 ? par[GT::PAR_IT1 + lo] : 1.f;
-        sbeta[j] = GT::F16S3 ? par[GT::PAR_SBETA + lo] : 1.f;
+        it2[j] = par[GT::PAR_IT2 + lo]; it1[j] = par[GT::PAR_IT1 + lo];
+        sbeta[j] = par[GT::PAR_SBETA + lo];
         ti[j] = ZF ? par[32 + lo] : 0.f; pwi[j] = ZF ? par[48 + lo] : 0.f; l2i[j] = ZF ? par[64 + lo] : 0.f;
         // factored-z form: a red pixel of the tile that holds the boundary has omega = ti = pwi = 0 in its image
         // (prep_pgt_body) and offset 0 here: A = exp2(0) = 1 and omega zd = 0 come out of the blue arithmetic without a select
@@ -249,7 +235,6 @@ __global__ __launch_bounds__(512, 2) void k_grads_t(qfa_params_t p, qfa_batch_t 
 #pragma unroll
         for (int ks = 0; ks < GT::NKQ; ++ks) {
             asm volatile("" ::"v"(IBh[j][ks]), "v"(IBm[j][ks]));
-            if (!GT::F16S1) asm volatile("" ::"v"(IBl[j][ks]));
         }
         asm volatile("" ::"v"(Psi[j]), "v"(om[j]), "v"(ti[j]), "v"(pwi[j]), "v"(l2i[j]), "v"(it2[j]), "v"(it1[j]), "v"(sbeta[j]));
     }
@@ -330,10 +315,7 @@ __global__ __launch_bounds__(512, 2) void k_grads_t(qfa_params_t p, qfa_batch_t 
     // group and wave in the stamps; a scalar instruction outside an MFMA's shadow costs the wave 4 cycles like any other,
     // tools/ubench/issue_mix.hip.)  The first two groups, the partial last group of a batch, ragged / straddling tiles, two
     // tiles per wave and the indexed form keep the general path below.
-#ifndef QFA_GT_RUNPTR
-#define QFA_GT_RUNPTR 1
-#endif
-    constexpr bool RUNP = QFA_GT_RUNPTR && !IDX && TPW == 1 && !QFA_TRACKED_LOADS;
+    constexpr bool RUNP = !IDX && TPW == 1 && !QFA_TRACKED_LOADS;
     struct SpecRun {
         const unsigned char *d, *e, *z, *m;       // group t + 2 of the next stage2 call; e, z, m biased by the LDS offsets of their arrays
     } sr{nullptr, nullptr, nullptr, nullptr};
@@ -368,9 +350,6 @@ __global__ __launch_bounds__(512, 2) void k_grads_t(qfa_params_t p, qfa_batch_t 
     const size_t sr_zinc = zblue ? (size_t)64 * (size_t)(unsigned)Nb : (zfb ? (size_t)256 : (size_t)0);
     auto advance_run = [&]() __attribute__((always_inline)) {
         if (!RUNP) return;
-#ifdef QFA_GT_ABL_L2
-        return;                // timing experiment (wrong results): every group re-reads the rows of group 2 -- the spectra come out of L2
-#endif
         sr.d += (size_t)64 * RS;
         sr.e += (size_t)64 * RS;
         sr.m += (size_t)16 * RS;
@@ -552,9 +531,6 @@ __global__ __launch_bounds__(512, 2) void k_grads_t(qfa_params_t p, qfa_batch_t 
     // ---- the state parts: a contiguous run of 1-KiB pieces per wave.  A request costs the issuing wave ~80 - 100 cycles, and
     // the waves with a blue tile are the critical path of a step (stage 2 of a blue group is 1 200 cycles against 800): the
     // pieces go to the waves with a red tile or none ("duty" waves) when there are at least five of them, else to all eight
-#ifndef QFA_GT_DUTY
-#define QFA_GT_DUTY 1
-#endif
     int nduty = 0, drank = 0;
     bool duty = true;
     {
@@ -566,7 +542,7 @@ __global__ __launch_bounds__(512, 2) void k_grads_t(qfa_params_t p, qfa_batch_t 
             if (w < wv8 && d) ++rk;
             if (d) ++nd;
         }
-        if (QFA_GT_DUTY && nd >= 5) { nduty = nd; drank = rk; duty = !blueTile; }
+        if (nd >= 5) { nduty = nd; drank = rk; duty = !blueTile; }
         else { nduty = GT::NW; drank = wv8; duty = true; }
     }
     const int s1_q = GT::S1_PCS / nduty, s1_r = GT::S1_PCS % nduty, z_q = GT::Z_PCS / nduty, z_r = GT::Z_PCS % nduty;
@@ -630,7 +606,7 @@ __global__ __launch_bounds__(512, 2) void k_grads_t(qfa_params_t p, qfa_batch_t 
 #pragma unroll
     for (int j = 0; j < TPW; ++j) afy[j] = aq[j] = f32x4{0.f, 0.f, 0.f, 0.f};
     auto stage1 = [&](int t, const auto &pt) __attribute__((always_inline)) {
-        if constexpr (QFA_GT_SETPRIO != 0 && (QFA_GT_PRIO_STAGES & 1) != 0) __builtin_amdgcn_s_setprio(QFA_GT_SETPRIO);
+        __builtin_amdgcn_s_setprio(2);
         part_begin(pt);
         const unsigned char *sp = lds + GT::L_S1 + (t & 1) * GT::S1P_B + lane * 16;
 #pragma unroll
@@ -639,15 +615,12 @@ __global__ __launch_bounds__(512, 2) void k_grads_t(qfa_params_t p, qfa_batch_t 
         u32x4 aop[2][NP];
 #pragma unroll
         for (int pc = 0; pc < NP; ++pc) aop[0][pc] = *reinterpret_cast<const u32x4 *>(sp + pc * 1024);
-        // F16S1: the inverse powers of two of the lane's four spectra (Cinv', y), out of the y block's free K slots
+        // stage 1 (float16 pieces): the inverse powers of two of the lane's four spectra (Cinv', y), out of the y block's free K slots
         f32x4 isc[2] = {f32x4{1.f, 1.f, 1.f, 1.f}, f32x4{1.f, 1.f, 1.f, 1.f}};
-        if constexpr (GT::F16S1) {
-            const unsigned char *sq = lds + GT::L_S1 + (t & 1) * GT::S1P_B + GT::S1_SCALES + 32 * g;
-            isc[0] = *reinterpret_cast<const f32x4 *>(sq);          // 1 / scale(Cinv'), 1 / scale(y) of spectra 4 g, 4 g + 1
-            isc[1] = *reinterpret_cast<const f32x4 *>(sq + 16);     // ... of 4 g + 2, 4 g + 3
-            if constexpr (GT::F16S3)
-                zfac = *reinterpret_cast<const f32x4 *>(lds + GT::L_S1 + (t & 1) * GT::S1P_B + GT::S1_ZFAC + 16 * g);
-        }
+        const unsigned char *sq = lds + GT::L_S1 + (t & 1) * GT::S1P_B + GT::S1_SCALES + 32 * g;
+        isc[0] = *reinterpret_cast<const f32x4 *>(sq);          // 1 / scale(Cinv'), 1 / scale(y) of spectra 4 g, 4 g + 1
+        isc[1] = *reinterpret_cast<const f32x4 *>(sq + 16);     // ... of 4 g + 2, 4 g + 3
+        zfac = *reinterpret_cast<const f32x4 *>(lds + GT::L_S1 + (t & 1) * GT::S1P_B + GT::S1_ZFAC + 16 * g);
 #pragma unroll
         for (int ks = 0; ks < GT::NKS; ++ks) {
             if (ks + 1 < GT::NKS) {
@@ -656,30 +629,24 @@ __global__ __launch_bounds__(512, 2) void k_grads_t(qfa_params_t p, qfa_batch_t 
                     aop[(ks + 1) & 1][pc] = *reinterpret_cast<const u32x4 *>(sp + (ks + 1) * GT::BLK_B + pc * 1024);
             }
             piece(pt, ks);
-            if (ks == GT::NKS - 1) piece(pt, GT::NKS);             // (a seventh site: the Z part of the waves 4..7 rides here, QFA_GT_ZS1)
-            const u32x4 &ah = aop[ks & 1][0], &am = aop[ks & 1][1], &al = aop[ks & 1][NP - 1];
+            if (ks == GT::NKS - 1) piece(pt, GT::NKS);             // (a seventh site: the Z part of the waves 4..7 rides here)
+            const u32x4 &ah = aop[ks & 1][0], &am = aop[ks & 1][1];
 #pragma unroll
             for (int j = 0; j < TPW; ++j) {
-                if constexpr (GT::F16S1) {
-                    if (ks < GT::NKQ) aq[j] = xdl3h(ah, am, IBh[j][ks], IBm[j][ks], aq[j]);
-                    else afy[j] = xdl3h(ah, am, IBh[j][GT::NKQ - 1], IBm[j][GT::NKQ - 1], afy[j]);                          // the y block
-                } else {
-                    if (ks < GT::NKQ) aq[j] = xdl6(ah, am, al, IBh[j][ks], IBm[j][ks], IBl[j][ks], aq[j]);
-                    else afy[j] = xdl6(ah, am, al, IBh[j][GT::NKQ - 1], IBm[j][GT::NKQ - 1], IBl[j][GT::NKQ - 1], afy[j]);     // the y block
-                }
+                if (ks < GT::NKQ) aq[j] = xdl3h(ah, am, IBh[j][ks], IBm[j][ks], aq[j]);
+                else afy[j] = xdl3h(ah, am, IBh[j][GT::NKQ - 1], IBm[j][GT::NKQ - 1], afy[j]);                          // the y block
             }
         }
-        if constexpr (GT::F16S1) {             // the powers of two back in: element r <-> spectrum 4 g + r, the lane's pixel
+         // the powers of two back in: element r <-> spectrum 4 g + r, the lane's pixel
 #pragma unroll
-            for (int j = 0; j < TPW; ++j)
+        for (int j = 0; j < TPW; ++j)
 #pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    aq[j][r] = (aq[j][r] * isc[r >> 1][2 * (r & 1)]) * it2[j];          // (one after the other: the PRODUCT of the
-                    afy[j][r] = (afy[j][r] * isc[r >> 1][2 * (r & 1) + 1]) * it1[j];    // two powers may leave the float32 range)
-                }
-        }
+            for (int r = 0; r < 4; ++r) {
+                aq[j][r] = (aq[j][r] * isc[r >> 1][2 * (r & 1)]) * it2[j];          // (one after the other: the PRODUCT of the
+                afy[j][r] = (afy[j][r] * isc[r >> 1][2 * (r & 1) + 1]) * it1[j];    // two powers may leave the float32 range)
+            }
         GTS(5)
-        if constexpr (QFA_GT_SETPRIO != 0 && (QFA_GT_PRIO_STAGES & 1) != 0) __builtin_amdgcn_s_setprio(0);
+        __builtin_amdgcn_s_setprio(0);
     };
     // ---- the lane's 4 TPW elements of group t out of the staging buffer (spectra 4 g + r at the lane's pixels); stage 2 pins
     // sigma and the mask behind its wait: left to itself hipcc reads sigma under a branch on the mask, one LDS round trip after
@@ -807,7 +774,7 @@ __global__ __launch_bounds__(512, 2) void k_grads_t(qfa_params_t p, qfa_batch_t 
                 cnt[j] += wv_ ? 1 : 0;
                 const float bb = wDA * Av;
                 sA[j] += bb * Av;
-                betaR[j][r] = GT::F16S3 ? bb * (sbeta[j] * zfac[r]) : bb;
+                betaR[j][r] = bb * (sbeta[j] * zfac[r]);
                 gamR[j][r] = Av * uu;
             } else {                                                        // red tile: A = 1, zd = 0
                 const float D = Psi[j] + sg * sg;
@@ -816,7 +783,7 @@ __global__ __launch_bounds__(512, 2) void k_grads_t(qfa_params_t p, qfa_batch_t 
                 const float dS = wD - wD * wD * aq[j][r];
                 gPsi[j] += dS - uu * uu;
                 cnt[j] += wv_ ? 1 : 0;
-                betaR[j][r] = GT::F16S3 ? wD * (sbeta[j] * zfac[r]) : wD;
+                betaR[j][r] = wD * (sbeta[j] * zfac[r]);
                 sA[j] += wD;
                 gamR[j][r] = uu;
             }
@@ -853,7 +820,7 @@ __global__ __launch_bounds__(512, 2) void k_grads_t(qfa_params_t p, qfa_batch_t 
     // as a block at the start.  They have the rest of the step to land: every wave waits for everything at the next barrier.
     const int nfull = max(0, min(n, (B >> 4) - g0));         // groups of the range with 16 spectra
     auto stage3 = [&](int t, const auto &pt) __attribute__((always_inline)) {
-        if constexpr (QFA_GT_SETPRIO != 0 && (QFA_GT_PRIO_STAGES & 2) != 0) __builtin_amdgcn_s_setprio(QFA_GT_SETPRIO);
+        __builtin_amdgcn_s_setprio(2);
         const bool run = RUNP && runok && t + 2 < nfull;
         if (t + 2 < n && !run) {
             // (batch order: the rows follow from t -- no LDS read; indexed form: stage 2 (t) read them out of the buffer)
@@ -863,67 +830,46 @@ __global__ __launch_bounds__(512, 2) void k_grads_t(qfa_params_t p, qfa_batch_t 
         if (!RUNP) part_begin(pt);
         const unsigned char *zp = lds + GT::L_Z + (t & 1) * GT::ZP_B + lane * 16;
         // bf16: three MFMAs per column tile ({l | h} x {h | l}, {h | m} x {m | m}, {h | m} x {h | h}: six products, K = 16 spectra x 2
-        // piece slots); float16 (F16S3): two ({h | m} x {h | h} and {h | m} x {m | 0}: three products)
+        // piece slots); float16: two ({h | m} x {h | h} and {h | m} x {m | 0}: three products)
         u32x4 bhl[TPW], bmm[TPW], bhh[TPW];
 #pragma unroll
         for (int j = 0; j < TPW; ++j) {
-            if constexpr (GT::F16S3) {
-                unsigned h01, m01, h23, m23;
-                split2h(betaR[j][0], betaR[j][1], h01, m01);
-                split2h(betaR[j][2], betaR[j][3], h23, m23);
-                bhh[j] = u32x4{h01, h23, h01, h23}; bmm[j] = u32x4{m01, m23, 0u, 0u}; bhl[j] = bhh[j];
-            } else {
-                unsigned h01, m01, l01, h23, m23, l23;
-                split2(betaR[j][0], betaR[j][1], h01, m01, l01);
-                split2(betaR[j][2], betaR[j][3], h23, m23, l23);
-                bhl[j] = u32x4{h01, h23, l01, l23}; bmm[j] = u32x4{m01, m23, m01, m23}; bhh[j] = u32x4{h01, h23, h01, h23};
-            }
+            unsigned h01, m01, h23, m23;
+            split2h(betaR[j][0], betaR[j][1], h01, m01);
+            split2h(betaR[j][2], betaR[j][3], h23, m23);
+            bhh[j] = u32x4{h01, h23, h01, h23}; bmm[j] = u32x4{m01, m23, 0u, 0u}; bhl[j] = bhh[j];
         }
         // The Z operands of column tile a + ZD are requested in front of the MFMAs of tile a, and fences keep it that way (round 5):
         // left to itself hipcc (which schedules this unit for register pressure) asks for tile a + 1 behind the first MFMA of
         // tile a -- 32 cycles in front of its use, an LDS round trip in the open per column tile: 1 670 cycles for 816 of MFMAs.
-#ifndef QFA_GT_ZD
-#define QFA_GT_ZD 3
-#endif
-        constexpr int ZD = QFA_GT_ZD < GT::NWT ? QFA_GT_ZD : GT::NWT, ZR = ZD + 1;
-        constexpr int NZ = GT::F16S3 ? 1 : 2;                                                   // 16-byte operands per column tile
+        constexpr int ZD = 3 < GT::NWT ? 3 : GT::NWT, ZR = ZD + 1;      // column tiles requested ahead
         u32x4 zop[ZR][2];
         auto rdz = [&](int a) __attribute__((always_inline)) {                                   // (a == NWT: the p operands, always two)
             const unsigned char *q = zp + (a < GT::NWT ? a * GT::ZT_B : GT::Z_B);
             zop[a % ZR][0] = *reinterpret_cast<const u32x4 *>(q);
-            if (NZ == 2 || a == GT::NWT) zop[a % ZR][1] = *reinterpret_cast<const u32x4 *>(q + 1024);
+            if (a == GT::NWT) zop[a % ZR][1] = *reinterpret_cast<const u32x4 *>(q + 1024);
         };
 #pragma unroll
         for (int a = 0; a < ZD; ++a) rdz(a);
 #pragma unroll
         for (int a = 0; a < GT::NWT; ++a) {
-#ifndef QFA_GT_ABL
-#define QFA_GT_ABL 0       // timing experiments (wrong results): 1 = stage 3 without its LDS reads, 2 = stage 3 without its DMA pieces
-#endif
-            if (QFA_GT_ABL & 1) { zop[(a + ZD) % ZR][0] = IBh[0][a % GT::NKQ]; zop[(a + ZD) % ZR][1] = IBm[0][a % GT::NKQ]; }
-            else if (a + ZD <= GT::NWT) rdz(a + ZD);
+            if (a + ZD <= GT::NWT) rdz(a + ZD);
             __builtin_amdgcn_sched_barrier(0);
             if constexpr (RUNP) {
-#ifndef QFA_GT_RQS
-#define QFA_GT_RQS 2       // column tiles between two staging requests
-#endif
-                // tiles 0, RQS, 2 RQS, 3 RQS: a request each (the third: blue tiles only); behind them the part's pieces (at most 7)
-                constexpr int RQS = QFA_GT_RQS, P0 = 3 * RQS + 1;
-                static_assert(P0 + 7 <= GT::NWT + (RQS == 1 ? 2 : 0) || RQS == 1, "piece sites");
+                // RQS = 2 column tiles between two staging requests: tiles 0, RQS, 2 RQS, 3 RQS carry a request each (the third: blue
+                // tiles only); behind them the part's pieces (at most 7)
+                constexpr int RQS = 2, P0 = 3 * RQS + 1;
+                static_assert(P0 + 7 <= GT::NWT, "piece sites");
                 if (a < P0) { if (a % RQS == 0 && run && (a / RQS != 2 || blueTile)) stage_req(t & 1, a / RQS); }
-                else if (!(QFA_GT_ABL & 2)) {
+                else {
                     if (a == P0) part_begin(pt);
-                    if (RQS == 1) {
-                        if ((a - P0) % 2 == 0) piece(pt, (a - P0) / 2);
-                        else if (a == GT::NWT - 1) piece(pt, (a - P0 + 1) / 2);
-                    } else if (a - P0 < 7) piece(pt, a - P0);
+                    if (a - P0 < 7) piece(pt, a - P0);
                 }
-            } else if (a % 2 == 0 && !(QFA_GT_ABL & 2)) piece(pt, a / 2);
-            const u32x4 &Z1 = zop[a % ZR][0], &Z2 = zop[a % ZR][NZ - 1];
+            } else if (a % 2 == 0) piece(pt, a / 2);
+            const u32x4 &Z1 = zop[a % ZR][0];
 #pragma unroll
             for (int j = 0; j < TPW; ++j) {
-                if constexpr (GT::F16S3) W[j][a] = xdlh(Z1, bhh[j], xdlh(Z1, bmm[j], W[j][a]));
-                else W[j][a] = xdl(Z2, bhh[j], xdl(Z2, bmm[j], xdl(Z1, bhl[j], W[j][a])));
+                W[j][a] = xdlh(Z1, bhh[j], xdlh(Z1, bmm[j], W[j][a]));
             }
             __builtin_amdgcn_sched_barrier(0);
         }
@@ -937,7 +883,7 @@ __global__ __launch_bounds__(512, 2) void k_grads_t(qfa_params_t p, qfa_batch_t 
             gacc[j] = xdl(P2, ghh, xdl(P2, gmm, xdl(P1, ghl, gacc[j])));                            // sum_s p_s[b] gamma[s][px]
         }
         advance_run();
-        if constexpr (QFA_GT_SETPRIO != 0 && (QFA_GT_PRIO_STAGES & 2) != 0) __builtin_amdgcn_s_setprio(0);
+        __builtin_amdgcn_s_setprio(0);
     };
 
     // ---- the walk: ONE barrier per group, and the two waves of a SIMD (w, w + 4) a stage apart in the same rotation:
@@ -1007,24 +953,14 @@ __global__ __launch_bounds__(512, 2) void k_grads_t(qfa_params_t p, qfa_batch_t 
                 step_barrier();
                 GTS(1)
                 const Part pz{zsrc, zdst, t + 1 < n ? z_req : 0}, ps{ssrc, sdst, t + 2 < n ? s1_req : 0};
-#ifndef QFA_GT_ZS1
-#define QFA_GT_ZS1 1       // waves 4..7: the Z part's pieces between the MFMAs of stage 1 instead of between the elements of stage 2
-#endif
+                // waves 4..7: the Z part's pieces between the MFMAs of stage 1 instead of between the elements of stage 2
                 // (a piece issued in stage 2 -- VALU work, nothing to hide behind -- cost the issuing wave ~100 cycles: stage 2 of a RED
                 // duty wave, one reciprocal per element, took 1 134 cycles with its seven pieces; between MFMAs they are free)
-                if (QFA_GT_ZS1) {
-                    stage2(t, none);
-                    GTS(3)
-                    stage3(t, ps);
-                    GTS(4)
-                    if (t + 1 < n) stage1(t + 1, pz);
-                } else {
-                    stage2(t, pz);
-                    GTS(3)
-                    stage3(t, ps);
-                    GTS(4)
-                    if (t + 1 < n) stage1(t + 1, none);
-                }
+                stage2(t, none);
+                GTS(3)
+                stage3(t, ps);
+                GTS(4)
+                if (t + 1 < n) stage1(t + 1, pz);
                 next();
             }
         }
@@ -1043,9 +979,9 @@ __global__ __launch_bounds__(512, 2) void k_grads_t(qfa_params_t p, qfa_batch_t 
 #pragma unroll
         for (int j = 0; j < TPW; ++j) {
             const float *fr = reinterpret_cast<const float *>(tile[j] + GT::OFF_F) + lo * KP;
-            // F16S3: W holds 2^7 sbeta x the sum (Z as Z 2^zk, beta as beta sbeta 2^(7 - zk)); the gamma term is unscaled
-            const float winv = GT::F16S3 ? 0.0078125f / sbeta[j] : 1.f;          // (a power of two: the quotient is exact)
-            f32x4 acc = GT::F16S3 ? f32x4{0.f, 0.f, 0.f, 0.f} : gacc[j];
+            // stage 3 (float16 pieces): W holds 2^7 sbeta x the sum (Z as Z 2^zk, beta as beta sbeta 2^(7 - zk)); the gamma term is unscaled
+            const float winv = 0.0078125f / sbeta[j];          // (a power of two: the quotient is exact)
+            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
             if constexpr (GT::APT == 1) {
 #pragma unroll
                 for (int a4 = 0; a4 < KP / 4; ++a4) {
@@ -1068,10 +1004,8 @@ __global__ __launch_bounds__(512, 2) void k_grads_t(qfa_params_t p, qfa_batch_t 
 #pragma unroll
                 for (int r = 0; r < 4; ++r) acc[r] += __shfl_xor(acc[r], 32);
             }
-            if constexpr (GT::F16S3) {
 #pragma unroll
-                for (int r = 0; r < 4; ++r) acc[r] = fmaf(acc[r], winv, gacc[j][r]);
-            }
+            for (int r = 0; r < 4; ++r) acc[r] = fmaf(acc[r], winv, gacc[j][r]);
             if (inb[j] && (GT::APT == 1 || g < 2)) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {

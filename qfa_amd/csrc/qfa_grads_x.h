@@ -49,25 +49,21 @@
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
-#ifndef QFA_GX_F16
-#define QFA_GX_F16 1
-#endif
 template <int KP_>
 struct GXT {                                             // KP = 16 (N_h = 9..16) or 8 (N_h <= 8)
     static constexpr int KP = KP_, KK2 = KP * (KP + 1) / 2;
     static constexpr int NKS = 1 + (KK2 + 31) / 32;      // K-steps of stage 1: [y, 0 | pair products, 32 per step]: 6 / 3
-    // Round 5 (QFA_GX_F16): stage 1 on TWO float16 pieces per operand, three products per K-step (qfa_common.h "float16 pieces");
+    // Round 5: stage 1 on TWO float16 pieces per operand, three products per K-step (qfa_common.h "float16 pieces");
     // the image holds t f_a and t^2 f_a f_b, 1 / t and 1 / t^2 of a half's pixels in its parameter KiB (floats 80.., 96..)
-    static constexpr bool F16 = QFA_GX_F16 != 0;
-    static constexpr int NP = F16 ? 2 : 3;               // pieces per K-step
+    static constexpr int NP = 2;                         // pieces per K-step (float16 h, m; A/B against three bf16 pieces: profiles/r5_ab_f16_small.txt)
     static constexpr int KS_B = NP * 1024;
     static constexpr int PAR_IT1 = 80, PAR_IT2 = 96;     // float index in a half's parameter KiB: 1 / t, 1 / t^2 of pixel 2 lo + h
     static constexpr int S1_HALF = NKS * KS_B;           // bytes of the stage-1 image of one 16-pixel half
     static constexpr int HALF_B = S1_HALF + 1024;        // ring slot: + float32 Psi[16], omega[16] of its pixels (19 / 10 KiB)
-    static constexpr int OFF_FP = 2 * HALF_B;            // F as bf16 pieces, A operand of stage 3: [piece][lane][8 a]
+    static constexpr int OFF_FP = 2 * HALF_B;            // F of the tile as float32 rows [pixel 0..31][FROW] (stage 3, W form)
     static constexpr int TILE_B = OFF_FP + 3 * 1024;     // 41 / 23 KiB per 32-pixel tile in global memory
     static constexpr int NCH_HALF = HALF_B / 1024;       // one-KiB DMA pieces per half (+ 3 for the F pieces with h = 1)
-    static constexpr int GROW = 16;                      // floats per row of the transposed gamma slot
+    static constexpr int GROW = 16;                      // (sizes the gamma slot: 32 rows of GROW floats; the W form keeps [half][lane][4])
     static constexpr int FROW = KP + 4;                  // W form: floats per pixel row of the F block (conflict-free b128 reads)
     static constexpr int NG = 4;                         // groups of 16 spectra per workgroup
     static constexpr int SPB = 16 * NG;                  // spectra per workgroup
@@ -90,30 +86,14 @@ struct GXT {                                             // KP = 16 (N_h = 9..16
 };
 static_assert(GXT<16>::L_TOTAL <= 160 * 1024 && GXT<8>::L_TOTAL <= 160 * 1024, "k_grads_x LDS");
 static_assert(32 * GXT<16>::FROW * 4 <= 3072, "F block of the W form fits the F slot");
-__device__ __forceinline__ f32x16 xdl32(const u32x4 &a, const u32x4 &b, f32x16 c) {     // 32x32x16
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0,
-                                                   0);
-}
-// TERMS: bf16 piece products per stage-3 contraction (qfa_common.h): 6 (float32-grade, the default) or 3 (QFA_F_S3_FAST)
-template <int TERMS>
-__device__ __forceinline__ f32x16 xdl32_6(const u32x4 &ah, const u32x4 &am, const u32x4 &al, const u32x4 &bh,
-                                          const u32x4 &bm, const u32x4 &bl, f32x16 c) {
-    c = xdl32(ah, bm, c);           // (first: its operands stay live -- see six_terms in qfa_common.h)
-    if (TERMS == 6) {
-        c = xdl32(al, bh, c);
-        c = xdl32(ah, bl, c);
-    }
-    if (TERMS >= 4) c = xdl32(am, bm, c);
-    c = xdl32(am, bh, c);
-    return xdl32(ah, bh, c);
-}
 
 // ------------------------------------------------------------------------------------------------
 // k_prep_pgx : F, Psi, omega -> the pass-2 image, one block per 32-pixel tile.
 //   half h (h = 0, 1)  [K-step ks][piece][lane (g, lo)][8 k] bf16: B[k = 32 ks + 8 g + j][px = 2 lo + h]
 //                      ks = 0: k < KP -> F[px][k]; ks >= 1: pair q = 32 (ks - 1) + 8 g + j -> F[px][a_q] F[px][b_q]
 //                      then float32 Psi[lo], omega[lo] of the pixels 2 lo + h
-//   stage-3 part       [piece][lane (r, h2)][8 a] bf16: A[px = r][a = 8 h2 + j]
+//   stage-3 part       float32 F[px 0..31][FROW] (wform = 1, what every caller passes; wform = 0 wrote the bf16 pieces of the retired
+//                      G form -- the argument and that arm stay so that the code of k_prep_pgx / k_prep_step is unchanged)
 // ------------------------------------------------------------------------------------------------
 template <int KP>
 __device__ __forceinline__ void prep_pgx_body(int bid, const float *__restrict__ F, const float *__restrict__ Psi,
@@ -129,7 +109,7 @@ __device__ __forceinline__ void prep_pgx_body(int bid, const float *__restrict__
     }
     __syncthreads();
     __shared__ float tsc[32][3];                                  // F16: the pixel's power of two t, 1 / t, 1 / t^2
-    if (GX::F16 && threadIdx.x < 32) {
+    if (threadIdx.x < 32) {
         float mx = 0.f;
         for (int a = 0; a < KP; ++a) mx = fmaxf(mx, fabsf(f[threadIdx.x][a]));
         int e = 7;
@@ -139,11 +119,11 @@ __device__ __forceinline__ void prep_pgx_body(int bid, const float *__restrict__
         tsc[threadIdx.x][1] = ldexpf(1.f, e - 7);
         tsc[threadIdx.x][2] = ldexpf(1.f, 2 * (e - 7));
     }
-    if (GX::F16) __syncthreads();
+    __syncthreads();
     for (int i = threadIdx.x; i < 2 * GX::NKS * 64; i += 256) {
         const int lane = i & 63, ks = (i >> 6) % GX::NKS, h = i / (64 * GX::NKS);
         const int lo = lane & 15, g = lane >> 4, px = 2 * lo + h;
-        const float t1 = GX::F16 ? tsc[px][0] : 1.f, t2 = t1 * t1;
+        const float t1 = tsc[px][0], t2 = t1 * t1;
         float v[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
@@ -163,18 +143,10 @@ __device__ __forceinline__ void prep_pgx_body(int bid, const float *__restrict__
             v[j] = x;
         }
         unsigned char *dst = tile + h * GX::HALF_B + ks * GX::KS_B + lane * 16;
-        if constexpr (GX::F16) {
-            u32x4 ph, pm;
-            split8h(v, ph, pm);
-            *reinterpret_cast<u32x4 *>(dst) = ph;
-            *reinterpret_cast<u32x4 *>(dst + 1024) = pm;
-        } else {
-            u32x4 ph, pm, pl;
-            split8(v, ph, pm, pl);
-            *reinterpret_cast<u32x4 *>(dst) = ph;
-            *reinterpret_cast<u32x4 *>(dst + 1024) = pm;
-            *reinterpret_cast<u32x4 *>(dst + 2048) = pl;
-        }
+        u32x4 ph, pm;
+        split8h(v, ph, pm);
+        *reinterpret_cast<u32x4 *>(dst) = ph;
+        *reinterpret_cast<u32x4 *>(dst + 1024) = pm;
     }
     // Psi, omega of each half's 16 pixels (+ zero padding of the KiB)
     for (int i = threadIdx.x; i < 512; i += 256) {
@@ -187,7 +159,7 @@ __device__ __forceinline__ void prep_pgx_body(int bid, const float *__restrict__
         else if (j < 80 && ZP.on() && px < Nb) {            // factored-z form: ti | pwi | l2i of the half's pixels
             const float4 q = ZP.at(px);
             v = j < 48 ? q.x : (j < 64 ? q.y : q.z);
-        } else if (GX::F16 && j >= GX::PAR_IT1 && j < GX::PAR_IT2 + 16) v = tsc[2 * (j & 15) + h][j < GX::PAR_IT2 ? 1 : 2];
+        } else if (j >= GX::PAR_IT1 && j < GX::PAR_IT2 + 16) v = tsc[2 * (j & 15) + h][j < GX::PAR_IT2 ? 1 : 2];
         po[j] = v;
     }
     if (wform) {       // stage 3 in its W form (role B, TERMS = 6): F of the tile as float32 rows [pixel 0..31][FROW]
@@ -288,21 +260,11 @@ __global__ __launch_bounds__(512, 2) void k_grads_x(qfa_params_t p, qfa_batch_t 
         return t0 + x;
     };
 
-#ifndef QFA_GX_ABL
-#define QFA_GX_ABL 0       // timing-only ablations (wrong results): 1 no spectra staging, 2 no flush, 4 no image DMA,
-#endif                     // 8 the staging re-reads the first tile (cache hits), 16 zabs staged from the delta rows (16-byte aligned),
-                           // 32 flush without its atomics, 64 flush without its LDS reads
-#ifndef QFA_GX_BPRIO
-#define QFA_GX_BPRIO 1        // priority of the role-B waves (0..3; 4 = 1 on red tiles only): 1 or 2 measured -0.05..-0.1 ms at c3
-#endif
-#ifndef QFA_GX_ROLE
-#define QFA_GX_ROLE 0      // register-pressure experiments: 1 = role A only, 2 = role B only
-#endif
-    if (roleA && QFA_GX_ROLE != 2) {
+    if (roleA) {
         // ================================================================ role A: stage 1 + stage 2
         const int lo = lane & 15, g = lane >> 4;
         // A operand of stage 1: spectrum s0 + lo, k = 32 ks + 8 g + j
-        u32x4 S1h[GX::NKS], S1m[GX::NKS], S1l[GX::F16 ? 1 : GX::NKS];
+        u32x4 S1h[GX::NKS], S1m[GX::NKS];
         float is0[4] = {1.f, 1.f, 1.f, 1.f}, is1[4] = {1.f, 1.f, 1.f, 1.f};      // F16: inverse powers of two of the spectra 4 g + r (y | C^-1')
         {
             const bool v = active && (s0 + lo) < B;
@@ -323,29 +285,26 @@ __global__ __launch_bounds__(512, 2) void k_grads_x(qfa_params_t p, qfa_batch_t 
 #pragma unroll
                 for (int j = 0; j < 8; ++j) xs[ks][j] = value(ks, 8 * g + j);
             float sc0 = 1.f, sc1 = 1.f;
-            if constexpr (GX::F16) {
-                float m0 = 0.f, m1 = 0.f;
+            float m0 = 0.f, m1 = 0.f;
 #pragma unroll
-                for (int ks = 0; ks < GX::NKS; ++ks)
+            for (int ks = 0; ks < GX::NKS; ++ks)
 #pragma unroll
-                    for (int j = 0; j < 8; ++j) {
-                        if (ks == 0) m0 = fmaxf(m0, fabsf(xs[ks][j])); else m1 = fmaxf(m1, fabsf(xs[ks][j]));
-                    }
+                for (int j = 0; j < 8; ++j) {
+                    if (ks == 0) m0 = fmaxf(m0, fabsf(xs[ks][j])); else m1 = fmaxf(m1, fabsf(xs[ks][j]));
+                }
 #pragma unroll
-                for (int o = 16; o <= 32; o <<= 1) { m0 = fmaxf(m0, __shfl_xor(m0, o)); m1 = fmaxf(m1, __shfl_xor(m1, o)); }
-                float i0, i1;
-                sc0 = f16_row_scale(m0, i0);
-                sc1 = f16_row_scale(m1, i1);
+            for (int o = 16; o <= 32; o <<= 1) { m0 = fmaxf(m0, __shfl_xor(m0, o)); m1 = fmaxf(m1, __shfl_xor(m1, o)); }
+            float i0, i1;
+            sc0 = f16_row_scale(m0, i0);
+            sc1 = f16_row_scale(m1, i1);
 #pragma unroll
-                for (int r = 0; r < 4; ++r) { is0[r] = __shfl(i0, 4 * g + r); is1[r] = __shfl(i1, 4 * g + r); }
-            }
+            for (int r = 0; r < 4; ++r) { is0[r] = __shfl(i0, 4 * g + r); is1[r] = __shfl(i1, 4 * g + r); }
 #pragma unroll
             for (int ks = 0; ks < GX::NKS; ++ks) {
                 float x[8];
 #pragma unroll
                 for (int j = 0; j < 8; ++j) x[j] = xs[ks][j] * (ks == 0 ? sc0 : sc1);
-                if constexpr (GX::F16) split8h(x, S1h[ks], S1m[ks]);
-                else split8(x, S1h[ks], S1m[ks], S1l[ks]);
+                split8h(x, S1h[ks], S1m[ks]);
             }
         }
         bool sv[4];
@@ -390,12 +349,10 @@ __global__ __launch_bounds__(512, 2) void k_grads_x(qfa_params_t p, qfa_batch_t 
         // there (hits in the vector cache, values unused).  No request reads past the end of a row.
         unsigned char *stg = lds + GX::L_STG + w * 2 * GX::STG_B;
         auto stage_tile = [&](int tg, int par) -> int {
-            if (QFA_GX_ABL & 1) return 8;
-            if (QFA_GX_ABL & 8) tg = t0;
             const bool zblue = !ZF && tg < nbt;                                               // wave-uniform
             const bool fastp = 32 * tg + 31 < Npix, fastz = ZF || !zblue || 32 * tg + 31 < Nb;
             // the third array: zabs rows (Nb apart, Nb long) on a blue tile, else the delta rows again
-            const bool zreal = zblue && !(QFA_GX_ABL & 16);
+            const bool zreal = zblue;
             const float *zb = zreal ? bt.zabs : bt.delta;
             const unsigned zpitch = zreal ? (unsigned)Nb : RS;
             const int zlen = zreal ? Nb : Npix;
@@ -505,24 +462,17 @@ __global__ __launch_bounds__(512, 2) void k_grads_x(qfa_params_t p, qfa_batch_t 
                     for (int pc = 0; pc < NP; ++pc)
                         bq[(ks + 1) & 1][pc] = *reinterpret_cast<const u32x4 *>(bp + (ks + 1) * GX::KS_B + pc * 1024);
                 }
-                const u32x4 &bh = bq[ks & 1][0], &bm = bq[ks & 1][1], &bl = bq[ks & 1][NP - 1];
-                if constexpr (GX::F16) {
-                    if (ks == 0) afy = xdl3h(S1h[ks], S1m[ks], bh, bm, afy);
-                    else aq = xdl3h(S1h[ks], S1m[ks], bh, bm, aq);
-                } else {
-                    constexpr int L0 = GX::F16 ? 0 : 1;
-                    if (ks == 0) afy = xdl6(S1h[ks], S1m[ks], S1l[L0 * ks], bh, bm, bl, afy);
-                    else aq = xdl6(S1h[ks], S1m[ks], S1l[L0 * ks], bh, bm, bl, aq);
-                }
+                const u32x4 &bh = bq[ks & 1][0], &bm = bq[ks & 1][1];
+                if (ks == 0) afy = xdl3h(S1h[ks], S1m[ks], bh, bm, afy);
+                else aq = xdl3h(S1h[ks], S1m[ks], bh, bm, aq);
             }
             const float *po = reinterpret_cast<const float *>(img + GX::S1_HALF);
-            if constexpr (GX::F16) {           // the powers of two back in: element r <-> spectrum 4 g + r, the lane's pixel
-                const float it1 = po[GX::PAR_IT1 + lo], it2 = po[GX::PAR_IT2 + lo];
+       // the powers of two back in: element r <-> spectrum 4 g + r, the lane's pixel
+            const float it1 = po[GX::PAR_IT1 + lo], it2 = po[GX::PAR_IT2 + lo];
 #pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    afy[r] = (afy[r] * is0[r]) * it1;
-                    aq[r] = (aq[r] * is1[r]) * it2;
-                }
+            for (int r = 0; r < 4; ++r) {
+                afy[r] = (afy[r] * is0[r]) * it1;
+                aq[r] = (aq[r] * is1[r]) * it2;
             }
             pp.Psi = po[lo]; pp.om = po[16 + lo];
             pp.ti = pp.pwi = pp.l2i = 0.f;
@@ -604,19 +554,10 @@ __global__ __launch_bounds__(512, 2) void k_grads_x(qfa_params_t p, qfa_batch_t 
                 if (r & 1) __builtin_amdgcn_sched_barrier(0);      // two elements at a time: bounds the live temporaries
             }
             GXS((BLUE ? 0 : 16) + 8 * h + 2)
-            if constexpr (TERMS == 6) {
-                // W form of stage 3 (role B below): beta and gamma of the lane's four spectra stay in THIS lane's layout --
-                // [half h][lane][4 floats], one 16-byte store each
-                *reinterpret_cast<float4 *>(bslot + (h * 64 + lane) * 4) = float4{betaR[0], betaR[1], betaR[2], betaR[3]};
-                *reinterpret_cast<float4 *>(gslot + (h * 64 + lane) * 4) = float4{gamR[0], gamR[1], gamR[2], gamR[3]};
-            } else {
-            // beta[s = 4g + r][pxl = 2 lo + h]
-#pragma unroll
-            for (int r = 0; r < 4; ++r) bslot[(4 * g + r) * 32 + 2 * lo + h] = betaR[r];
-            // gamma transposed: row rho = 16 h + lo, columns s = 4g .. 4g + 3 (one 16-byte store)
-            *reinterpret_cast<float4 *>(gslot + (16 * h + lo) * GX::GROW + 4 * g) =
-                float4{gamR[0], gamR[1], gamR[2], gamR[3]};
-            }
+            // W form of stage 3 (role B below): beta and gamma of the lane's four spectra stay in THIS lane's layout --
+            // [half h][lane][4 floats], one 16-byte store each
+            *reinterpret_cast<float4 *>(bslot + (h * 64 + lane) * 4) = float4{betaR[0], betaR[1], betaR[2], betaR[3]};
+            *reinterpret_cast<float4 *>(gslot + (h * 64 + lane) * 4) = float4{gamR[0], gamR[1], gamR[2], gamR[3]};
             // per-pixel sums over the wave's 16 spectra (lanes lo + 16 g'): two cross-lane adds, one store per pixel
             // (v_permlane16_swap / v_permlane32_swap: three exchanges and three adds leave quantity g's sum over the
             // four 16-lane rows in row g)
@@ -659,8 +600,7 @@ __global__ __launch_bounds__(512, 2) void k_grads_x(qfa_params_t p, qfa_batch_t 
                         if (h != 0) return;
                         // this tile's staged spectra: everything but the requests of tile c + 1 has landed after the wait;
                         // copy out, then the requests for tile c + 2 into the buffer just read
-                        if (QFA_GX_ABL & 1) {}
-                        else if (c + 1 < n && cnt_other == 8) dma_wait<8>();
+                        if (c + 1 < n && cnt_other == 8) dma_wait<8>();
                         else if (c + 1 < n && cnt_other == 6) dma_wait<6>();
                         else if (c + 1 < n && cnt_other == 14) dma_wait<14>();
                         else dma_wait<0>();
@@ -714,81 +654,49 @@ __global__ __launch_bounds__(512, 2) void k_grads_x(qfa_params_t p, qfa_batch_t 
         } else if (!det) {
             scal64_commit(sc64, 0.0, 0.0, 0.0, gridDim.x * (unsigned)GX::NG, accS);
         }
-    } else if (QFA_GX_ROLE != 1) {
+    } else {
         // ================================================================ role B: image DMA, flushes, stage 3
-        constexpr bool WB = TERMS == 6;        // stage 3 in its W form (float32 grade); TERMS == 3: the G form (QFA_F_S3_FAST)
+        static_assert(TERMS == 6, "stage 3 in its W form (float32 grade); the three-product G form of round 2 is retired");
         // ---- W form: accF[px][b] = sum_a F[px][a] W[px][a][b], W = sum_s Z_s[a][b] beta[s][px]
         // as a K = spectrum GEMM per column tile a: A = static Z pieces (row m = b = lane & 15; k = 8 g + j <-> spectrum
         // 4 g + (j & 3), piece slot j >> 2), B = the lane's own four beta values as {h|l}, {m|m}, {h|h}: three INDEPENDENT
         // short chains per column tile instead of six dependent 32x32x16 MFMAs per spectrum pair -- role B alone ran 2.75 ms
         // at c3 in the six-product G form (latency of the dependent chain), against 1.1 ms with three.
         const int loB = lane & 15, gB = lane >> 4;
-        u32x4 ZA1[WB ? KP : 1], ZA2[WB ? KP : 1], PA1 = {0u, 0u, 0u, 0u}, PA2 = {0u, 0u, 0u, 0u};
-        if constexpr (WB) {
-            const float *solr[4];
-            bool vr[4];
+        u32x4 ZA1[KP], ZA2[KP], PA1 = {0u, 0u, 0u, 0u}, PA2 = {0u, 0u, 0u, 0u};
+        const float *solr[4];
+        bool vr[4];
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int sidx = s0 + 4 * gB + r;
-                vr[r] = active && sidx < B && loB < Nh && loB < KP;
-                solr[r] = SOL + (size_t)(vr[r] ? sidx : 0) * C::NSOL;
-            }
+        for (int r = 0; r < 4; ++r) {
+            const int sidx = s0 + 4 * gB + r;
+            vr[r] = active && sidx < B && loB < Nh && loB < KP;
+            solr[r] = SOL + (size_t)(vr[r] ? sidx : 0) * C::NSOL;
+        }
 #pragma unroll
-            for (int a = 0; a < KP; ++a) {
-                float x[4];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) x[r] = vr[r] ? solr[r][C::SOL_Z + a * KP + (loB & (KP - 1))] : 0.f;
-                unsigned h01, m01, l01, h23, m23, l23;
-                split2(x[0], x[1], h01, m01, l01);
-                split2(x[2], x[3], h23, m23, l23);
-                ZA1[a] = u32x4{l01, l23, h01, h23};
-                ZA2[a] = u32x4{h01, h23, m01, m23};
-            }
+        for (int a = 0; a < KP; ++a) {
             float x[4];
 #pragma unroll
-            for (int r = 0; r < 4; ++r) x[r] = vr[r] ? solr[r][C::SOL_P + (loB & (KP - 1))] : 0.f;
+            for (int r = 0; r < 4; ++r) x[r] = vr[r] ? solr[r][C::SOL_Z + a * KP + (loB & (KP - 1))] : 0.f;
             unsigned h01, m01, l01, h23, m23, l23;
             split2(x[0], x[1], h01, m01, l01);
             split2(x[2], x[3], h23, m23, l23);
-            PA1 = u32x4{l01, l23, h01, h23};
-            PA2 = u32x4{h01, h23, m01, m23};
+            ZA1[a] = u32x4{l01, l23, h01, h23};
+            ZA2[a] = u32x4{h01, h23, m01, m23};
         }
-        // ---- G form (TERMS == 3)
-        // One stage-3 MFMA (32 px x 32 columns x K = 16) covers the columns of 32 / KP spectra: a pair at KP = 16, four
-        // spectra at KP = 8 (where only k < 8 carries data).  Column col = (spectrum sc = col / KP, b = col % KP).
-        constexpr int SPM = 32 / KP, NMG = 16 / SPM;       // spectra per MFMA, MFMA groups per wave (8 pairs / 4 fours)
-        const int col = lane & 31, h2 = lane >> 5, b = lane & (KP - 1), sc = col / KP, sp = (lane >> 4) & 1;
+        float x[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) x[r] = vr[r] ? solr[r][C::SOL_P + (loB & (KP - 1))] : 0.f;
+        unsigned h01, m01, l01, h23, m23, l23;
+        split2(x[0], x[1], h01, m01, l01);
+        split2(x[2], x[3], h23, m23, l23);
+        PA1 = u32x4{l01, l23, h01, h23};
+        PA2 = u32x4{h01, h23, m01, m23};
         const int tidB = tid & 255;                        // 0..255 over the four role-B waves
-        // B operands: Z of group m: B[k = a = 8 h2 + j][col = (sc, b)] = Z_{SPM m + sc}[a][b]
-        constexpr int NMGA = WB ? 1 : NMG;
-        u32x4 Zh[NMGA], Zm[NMGA], Zl[NMGA], Ph = {0u, 0u, 0u, 0u}, Pm = Ph, Pl = Ph;
-        if constexpr (!WB) {
-#pragma unroll
-            for (int m = 0; m < NMG; ++m) {
-                const int s = s0 + SPM * m + sc;
-                const bool v = active && s < B && b < Nh;
-                const float *sol = SOL + (size_t)(v ? s : 0) * C::NSOL + C::SOL_Z + b;
-                float x[8];
-#pragma unroll
-                for (int j = 0; j < 8; ++j) x[j] = (v && 8 * h2 + j < KP) ? sol[(8 * h2 + j) * KP] : 0.f;
-                split8(x, Zh[m], Zm[m], Zl[m]);
-            }
-            // gamma term: B[k = s = 8 h2 + j][col] = p_s[b] for col < KP, 0 otherwise
-            float x[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const int s = s0 + 8 * h2 + j;
-                const bool v = active && s < B && col < KP && b < Nh;
-                x[j] = v ? SOL[(size_t)s * C::NSOL + C::SOL_P + b] : 0.f;
-            }
-            split8(x, Ph, Pm, Pl);
-        }
         // LDS-DMA of half-step t = 2 c + h: the stage-1 image + Psi/omega of that half into ring slot h, and with the
         // second half the F pieces of the tile into the F ring; wave w moves the 1-KiB pieces w, w + 4, ...
         // (role A runs stage 1 of half t + 1 during half-step t: the image of half t + 2 is requested at the start of
         // half-step t into the slot half t was read from in half-step t - 1; the F block of tile c with its second half-step)
         auto get_img = [&](int t) {
-            if ((QFA_GX_ABL & 4) && t > 1) return;
             const int c = t >> 1, h = t & 1;
             const unsigned char *sbase = uniform_ptr(PGX + (size_t)tile_of(c) * GX::TILE_B);
             unsigned char *img = lds + GX::L_IMG + h * GX::HALF_B;
@@ -800,7 +708,6 @@ __global__ __launch_bounds__(512, 2) void k_grads_x(qfa_params_t p, qfa_batch_t 
             }
         };
         auto get_F = [&](int c) {
-            if ((QFA_GX_ABL & 4) && c > 0) return;
             const unsigned char *sbase = uniform_ptr(PGX + (size_t)tile_of(c) * GX::TILE_B);
             unsigned char *fp = lds + GX::L_FP + (c & 1) * 3072;
             if (w < 3) glds16a(sbase + GX::OFF_FP + w * 1024, (unsigned)lane * 16u, wave_uniform(lds_addr(fp + w * 1024)));
@@ -817,7 +724,6 @@ __global__ __launch_bounds__(512, 2) void k_grads_x(qfa_params_t p, qfa_batch_t 
         const bool wide = det && (Nh & 3) == 0;
         constexpr int NWIDE = 8 * KP;                      // threads of the 16-byte form: 128 (waves 0, 1) / 64 (wave 0)
         auto flush_F = [&](int tg, int par) {
-            if (QFA_GX_ABL & 2) return;
             const float *pp = reinterpret_cast<const float *>(lds + GX::L_PART + par * GX::NG * GX::PARTF * 4);
             if (wide) {
                 if (tidB >= NWIDE) return;                                            // wave-uniform
@@ -835,10 +741,9 @@ __global__ __launch_bounds__(512, 2) void k_grads_x(qfa_params_t p, qfa_batch_t 
 #pragma unroll
             for (int k4 = 0; k4 < GX::PARTF / 256; ++k4) {
                 const int o = tidB + 256 * k4;
-                float v = (QFA_GX_ABL & 64) ? 1.f : (pp[o] + pp[GX::PARTF + o]) + (pp[2 * GX::PARTF + o] + pp[3 * GX::PARTF + o]);
+                const float v = (pp[o] + pp[GX::PARTF + o]) + (pp[2 * GX::PARTF + o] + pp[3 * GX::PARTF + o]);
                 const int px = 32 * tg + o / KP, bb = o % KP;
                 const bool ok = (bb < Nh) & (px < Npix);
-                if (QFA_GX_ABL & 32) { asm volatile("" ::"v"(v)); continue; }
                 if (det) *(ok ? accF + (size_t)px * Nh + bb : sink) = v;
                 else atomicAdd(accF + (size_t)min(px, Npix - 1) * Nh + bb % Nh, ok ? v : 0.f);
             }
@@ -846,12 +751,10 @@ __global__ __launch_bounds__(512, 2) void k_grads_x(qfa_params_t p, qfa_batch_t 
         // per-pixel sums [sumA | gPsi | gOmega | cnt] of tile tg: thread (which = t >> 5, pxl = t & 31) of 128 -- waves
         // 0 and 1, or waves 2 and 3 when the F sums go out as 16-byte stores (one request per wave and tile then)
         auto flush_P = [&](int tg, int par) {
-            if (QFA_GX_ABL & 2) return;
             if (wide ? tidB < 128 : tidB >= 128) return;                              // wave-uniform (waves 2, 3 / 0, 1)
             const int which = (tidB >> 5) & 3, pxl = tidB & 31;
             const float *q = reinterpret_cast<const float *>(lds + GX::L_PSUM + par * GX::NG * 512) + which * 32 + pxl;
-            float v = (QFA_GX_ABL & 64) ? 1.f : (q[0] + q[128]) + (q[256] + q[384]);
-            if (QFA_GX_ABL & 32) { asm volatile("" ::"v"(v)); return; }
+            const float v = (q[0] + q[128]) + (q[256] + q[384]);
             const int px = 32 * tg + pxl;
             const bool ok = (px < Npix) & ((which != 2) | (px < Nb));
             // (default mode: a red pixel's lane of the gOmega group adds 0 to the pixel's count instead)
@@ -866,118 +769,58 @@ __global__ __launch_bounds__(512, 2) void k_grads_x(qfa_params_t p, qfa_batch_t 
         auto tileB = [&](int c, auto part_tag) {
             constexpr int PART = decltype(part_tag)::value;
             const int par = c & 1;
-            if constexpr (WB) {
-                // half PART of tile c: beta / gamma of the lane's four spectra (pixel 2 lo + PART) as role A left them
-                const float *bsl = reinterpret_cast<const float *>(lds + GX::L_BETA + (par * GX::NG + w) * 2048);
-                const float *gsl = reinterpret_cast<const float *>(lds + GX::L_GAM + (par * GX::NG + w) * 32 * GX::GROW * 4);
-                const float4 b4 = *reinterpret_cast<const float4 *>(bsl + (PART * 64 + lane) * 4);
-                const float4 g4 = *reinterpret_cast<const float4 *>(gsl + (PART * 64 + lane) * 4);
-                const float *frow = reinterpret_cast<const float *>(lds + GX::L_FP + (c & 1) * 3072) + (2 * loB + PART) * GX::FROW;
-                float fa[KP];
+            // half PART of tile c: beta / gamma of the lane's four spectra (pixel 2 lo + PART) as role A left them
+            const float *bsl = reinterpret_cast<const float *>(lds + GX::L_BETA + (par * GX::NG + w) * 2048);
+            const float *gsl = reinterpret_cast<const float *>(lds + GX::L_GAM + (par * GX::NG + w) * 32 * GX::GROW * 4);
+            const float4 b4 = *reinterpret_cast<const float4 *>(bsl + (PART * 64 + lane) * 4);
+            const float4 g4 = *reinterpret_cast<const float4 *>(gsl + (PART * 64 + lane) * 4);
+            const float *frow = reinterpret_cast<const float *>(lds + GX::L_FP + (c & 1) * 3072) + (2 * loB + PART) * GX::FROW;
+            float fa[KP];
 #pragma unroll
-                for (int a4 = 0; a4 < KP / 4; ++a4) {
-                    const float4 f4 = *reinterpret_cast<const float4 *>(frow + 4 * a4);
-                    fa[4 * a4] = f4.x; fa[4 * a4 + 1] = f4.y; fa[4 * a4 + 2] = f4.z; fa[4 * a4 + 3] = f4.w;
-                }
-                unsigned h01, m01, l01, h23, m23, l23;
-                split2(b4.x, b4.y, h01, m01, l01);
-                split2(b4.z, b4.w, h23, m23, l23);
-                const u32x4 bhl = {h01, h23, l01, l23}, bmm = {m01, m23, m01, m23}, bhh = {h01, h23, h01, h23};
-                split2(g4.x, g4.y, h01, m01, l01);
-                split2(g4.z, g4.w, h23, m23, l23);
-                const u32x4 ghl = {h01, h23, l01, l23}, gmm = {m01, m23, m01, m23}, ghh = {h01, h23, h01, h23};
-                const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-                f32x4 acc = xdl(PA2, ghh, xdl(PA2, gmm, xdl(PA1, ghl, zero)));       // sum_s p_s[b] gamma[s][px]
-                // column tiles in chunks of four: twelve MFMAs in flight (independent chains of three), the FMAs of a chunk
-                // behind the MFMAs of the next
-                f32x4 Wc[2][4];
-#pragma unroll
-                for (int ch = 0; ch <= KP / 4; ++ch) {
-                    if (ch < KP / 4) {
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) {
-                            const int a = 4 * ch + j;
-                            Wc[ch & 1][j] = xdl(ZA2[a], bhh, xdl(ZA2[a], bmm, xdl(ZA1[a], bhl, zero)));
-                        }
-                    }
-                    if (ch > 0) {
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) {
-                            const int a = 4 * (ch - 1) + j;
-#pragma unroll
-                            for (int r = 0; r < 4; ++r) acc[r] = fmaf(fa[a], Wc[(ch - 1) & 1][j][r], acc[r]);
-                        }
-                    }
-                }
-                // the lane holds accF[px = 2 lo + PART][b = 4 g + r] of its group: one 16-byte store into the group's slot
-                float *part = reinterpret_cast<float *>(lds + GX::L_PART + (par * GX::NG + w) * GX::PARTF * 4);
-                if (KP == 16 || gB < KP / 4)
-                    *reinterpret_cast<float4 *>(part + (2 * loB + PART) * KP + 4 * gB) = float4{acc[0], acc[1], acc[2], acc[3]};
-                return;
+            for (int a4 = 0; a4 < KP / 4; ++a4) {
+                const float4 f4 = *reinterpret_cast<const float4 *>(frow + 4 * a4);
+                fa[4 * a4] = f4.x; fa[4 * a4 + 1] = f4.y; fa[4 * a4 + 2] = f4.z; fa[4 * a4 + 3] = f4.w;
             }
-            const unsigned char *fp = lds + GX::L_FP + (c & 1) * 3072 + lane * 16;
-            const float *bslot = reinterpret_cast<const float *>(lds + GX::L_BETA + (par * GX::NG + w) * 2048);
-            const float *gslot = reinterpret_cast<const float *>(lds + GX::L_GAM + (par * GX::NG + w) * 32 * GX::GROW * 4);
+            unsigned h01, m01, l01, h23, m23, l23;
+            split2(b4.x, b4.y, h01, m01, l01);
+            split2(b4.z, b4.w, h23, m23, l23);
+            const u32x4 bhl = {h01, h23, l01, l23}, bmm = {m01, m23, m01, m23}, bhh = {h01, h23, h01, h23};
+            split2(g4.x, g4.y, h01, m01, l01);
+            split2(g4.z, g4.w, h23, m23, l23);
+            const u32x4 ghl = {h01, h23, l01, l23}, gmm = {m01, m23, m01, m23}, ghh = {h01, h23, h01, h23};
+            const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+            f32x4 acc = xdl(PA2, ghh, xdl(PA2, gmm, xdl(PA1, ghl, zero)));       // sum_s p_s[b] gamma[s][px]
+            // column tiles in chunks of four: twelve MFMAs in flight (independent chains of three), the FMAs of a chunk
+            // behind the MFMAs of the next
+            f32x4 Wc[2][4];
+#pragma unroll
+            for (int ch = 0; ch <= KP / 4; ++ch) {
+                if (ch < KP / 4) {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const int a = 4 * ch + j;
+                        Wc[ch & 1][j] = xdl(ZA2[a], bhh, xdl(ZA2[a], bmm, xdl(ZA1[a], bhl, zero)));
+                    }
+                }
+                if (ch > 0) {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const int a = 4 * (ch - 1) + j;
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) acc[r] = fmaf(fa[a], Wc[(ch - 1) & 1][j][r], acc[r]);
+                    }
+                }
+            }
+            // the lane holds accF[px = 2 lo + PART][b = 4 g + r] of its group: one 16-byte store into the group's slot
             float *part = reinterpret_cast<float *>(lds + GX::L_PART + (par * GX::NG + w) * GX::PARTF * 4);
-            const u32x4 Fh = *reinterpret_cast<const u32x4 *>(fp), Fm = *reinterpret_cast<const u32x4 *>(fp + 1024),
-                        Fl = *reinterpret_cast<const u32x4 *>(fp + 2048);
-            f32x16 zero;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) zero[i] = 0.f;
-            f32x16 acc = zero;
-            if (PART == 0) {
-                // gamma of pixel pxl = col (row rho = 16 (col & 1) + (col >> 1)), spectra 8 h2 .. 8 h2 + 7
-                const float *grow = gslot + (16 * (col & 1) + (col >> 1)) * GX::GROW + 8 * h2;
-                const float4 g0 = *reinterpret_cast<const float4 *>(grow), g1 = *reinterpret_cast<const float4 *>(grow + 4);
-                const float gx[8] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w};
-                u32x4 Gh, Gm, Gl;
-                split8(gx, Gh, Gm, Gl);
-                acc = xdl32_6<TERMS>(Gh, Gm, Gl, Ph, Pm, Pl, zero);
-            }
-#pragma unroll
-            for (int m = (NMG / 2) * PART; m < (NMG / 2) * (PART + 1); ++m) {
-                const f32x16 G = xdl32_6<TERMS>(Fh, Fm, Fl, Zh[m], Zm[m], Zl[m], zero);
-                const float *brow = bslot + (SPM * m + sc) * 32 + 4 * h2;       // pixels 8 q + 4 h2 + (0..3)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const float4 bq = *reinterpret_cast<const float4 *>(brow + 8 * q);
-                    acc[4 * q + 0] = fmaf(bq.x, G[4 * q + 0], acc[4 * q + 0]);
-                    acc[4 * q + 1] = fmaf(bq.y, G[4 * q + 1], acc[4 * q + 1]);
-                    acc[4 * q + 2] = fmaf(bq.z, G[4 * q + 2], acc[4 * q + 2]);
-                    acc[4 * q + 3] = fmaf(bq.w, G[4 * q + 3], acc[4 * q + 3]);
-                }
-            }
-            // Sum the spectra of the groups (the lanes that share b).  Lanes l and l ^ 16: v_permlane16_swap exchanges
-            // the odd 16-lane rows of acc[i] with the even rows of acc[8 + i], so one add leaves the sums of acc[i] in
-            // the even rows (sp = 0) and those of acc[8 + i] in the odd rows.  KP = 8: also lanes l and l ^ 8 (a rotation
-            // by 8 inside the row, DPP).  Each half of the lanes then stores half the pixel rows:
-            // part[pxl][b], pxl = (ii & 3) + 8 (ii >> 2) + 4 h2 with ii = i + 8 sp
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const auto sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(acc[i]), __float_as_uint(acc[8 + i]), false, false);
-                float v = __uint_as_float(sw[0]) + __uint_as_float(sw[1]);
-                if (KP == 8)
-                    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x128, 0xf, 0xf, false));   // row_ror:8
-                const int pxl0 = (i & 3) + 8 * (i >> 2) + 4 * h2;                 // ii = i; ii = 8 + i adds 16 pixels
-                float *q = part + (pxl0 + 16 * sp) * KP + b;
-                if (KP == 16 || (lane & 8) == 0) {
-                    if (PART == 0) *q = v;
-                    else *q += v;             // (read-add-write: ds_add_f32 cost 2 500 cycles more per tile)
-                }
-            }
+            if (KP == 16 || gB < KP / 4)
+                *reinterpret_cast<float4 *>(part + (2 * loB + PART) * KP + 4 * gB) = float4{acc[0], acc[1], acc[2], acc[3]};
         };
-#if QFA_GX_BPRIO && QFA_GX_BPRIO < 4
-        __builtin_amdgcn_s_setprio(QFA_GX_BPRIO);
-#endif
+        __builtin_amdgcn_s_setprio(1);       // (the role-B waves at priority 1 or 2: measured -0.05..-0.1 ms at c3)
         if (n > 0) get_img(0);
         dma_wait<0>();
         step_barrier();
         for (int c = 0; c < n + 2; ++c) {
-#if QFA_GX_BPRIO == 4
-            // this role is the slower one while role A works on a red tile, and the faster one on a blue tile
-            if (c < n && tile_of(c) < nbt) __builtin_amdgcn_s_setprio(0);
-            else __builtin_amdgcn_s_setprio(1);
-#endif
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
                 const int t = 2 * c + h;
@@ -999,8 +842,7 @@ __global__ __launch_bounds__(512, 2) void k_grads_x(qfa_params_t p, qfa_batch_t 
                     else tileB(c - 1, std::integral_constant<int, 1>{});
                 }
                 GXS(8 * h + 1)
-                if (QFA_GX_ABL & 2) dma_wait<0>();
-                else if (nreq == 3) dma_wait<3>();
+                if (nreq == 3) dma_wait<3>();
                 else if (nreq == 2) dma_wait<2>();
                 else if (nreq == 1) dma_wait<1>();
                 else dma_wait<0>();

@@ -4,17 +4,14 @@
 #pragma once
 #include "qfa_common.h"
 
-#ifndef QFA_GT_F16S1
-#define QFA_GT_F16S1 1     // stage 1 of k_grads_t on TWO float16 pieces per operand and three products (18 MFMAs per group instead of 36;
-                           // qfa_common.h "float16 pieces"): the image carries a power of two per pixel, the state one per spectrum
-#endif
-#ifndef QFA_GT_F16S3
-#define QFA_GT_F16S3 1     // stage 3 of k_grads_t: W += Z beta on TWO float16 pieces per operand, three products in two MFMAs per column tile
-                           // (35 MFMAs per group instead of 51).  beta = A^2 / D <= 1 / Psi of its PIXEL whatever the data (D >= A^2 Psi): the
-                           // image carries the power of two that brings beta below 2^12 and W is a per-pixel sum -- the scale leaves once, when F
-                           // enters.  Z of a spectrum is scaled by 2^7 (by less where its largest element exceeds 128; the factor rides with the
-                           // spectrum's stage-1 scales and multiplies its beta)
-#endif
+// Stage 1 of k_grads_t runs on TWO float16 pieces per operand and three products (18 MFMAs per group instead of 36 with bf16 pieces;
+// qfa_common.h "float16 pieces", A/B in profiles/r5_ab_f16_stage1.txt): the image carries a power of two per pixel, the state one
+// per spectrum.
+// Stage 3: W += Z beta on TWO float16 pieces per operand, three products in two MFMAs per column tile (35 MFMAs per group instead
+// of 51, profiles/r5_ab_f16_stage3.txt).  beta = A^2 / D <= 1 / Psi of its PIXEL whatever the data (D >= A^2 Psi): the image carries
+// the power of two that brings beta below 2^12 and W is a per-pixel sum -- the scale leaves once, when F enters.  Z of a spectrum
+// is scaled by 2^7 (by less where its largest element exceeds 128; the factor rides with the spectrum's stage-1 scales and
+// multiplies its beta).
 template <int KP_>
 struct GTT {
     static constexpr int KP = KP_, KK2 = KP * (KP + 1) / 2;
@@ -26,19 +23,18 @@ struct GTT {
     static constexpr int YOFF = (KK2 % 32 + 7) / 8 * 8;      // 8
     static_assert(KK2 % 32 != 0 && YOFF + KP <= 32, "F / y share the last pair block");
     static constexpr int NKS = NKQ + 1;                      // blocks of the spectrum side (6)
-    static constexpr bool F16S1 = QFA_GT_F16S1 != 0;
-    static constexpr int S1NP = F16S1 ? 2 : 3;               // pieces per K block of stage 1 (float16 h, m | bf16 h, m, l)
+    static constexpr int S1NP = 2;                           // pieces per K block of stage 1 (float16 h, m)
     static constexpr int BLK_B = S1NP * 1024;
     // per 16-pixel tile in global memory (k_prep_pgt)
     static constexpr int IMG_B = NKQ * BLK_B;                // [ks][piece][lane (g, lo)][8 k]: B[k = 32 ks + 8 g + j][px = lo]
-    // float Psi[16] | omega[16] | ti[16] | pwi[16] | l2i[16] | F16S1: 1 / t^2 [16] | 1 / t [16] (t = the pixel's power of two:
+    // float Psi[16] | omega[16] | ti[16] | pwi[16] | l2i[16] | 1 / t^2 [16] | 1 / t [16] (t = the pixel's power of two:
     // the image holds t^2 f_a f_b and t f_a)
     static constexpr int OFF_PAR = IMG_B;
     static constexpr int PAR_IT2 = 80, PAR_IT1 = 96, PAR_SBETA = 112;      // float index in the parameter block: 1 / t^2, 1 / t, s_beta of pixel lo
     static constexpr int OFF_F = IMG_B + 512;                // float F[16 px][KP]
     static constexpr int TILE_B = (OFF_F + 16 * KP * 4 + 1023) / 1024 * 1024;
     // per group of 16 spectra in global memory (k_prep_pst)
-    // F16S1: Cinv' and y of a spectrum are scaled by powers of two of their own; their inverses sit as float32 in the h piece of
+    // stage 1 (float16 pieces): Cinv' and y of a spectrum are scaled by powers of two of their own; their inverses sit as float32 in the h piece of
     // the y block, lanes g = 3 (K slots 24..31, which meet zeros of the image): float 2 s = 1 / scale(Cinv'), 2 s + 1 = 1 / scale(y)
     static constexpr int S1_B = NKS * BLK_B;                 // [block][piece][lane (g, lo = spectrum)][8 k]: A[s][k] of stage 1
     static constexpr int S1_SCALES = NKQ * BLK_B + 48 * 16;  // (byte offset of those 32 floats in the S1 part)
@@ -47,12 +43,10 @@ struct GTT {
     // (row m <-> a = 2 tile + (m >> 3), b = m & 7): half the MFMAs, operand reads and accumulator registers
     static constexpr int APT = 16 / KP;                      // a per tile (1 or 2)
     static constexpr int NWT = KP / APT;                     // tiles (16 or 4)
-    static constexpr bool F16S3 = QFA_GT_F16S3 != 0;
-    static_assert(!F16S3 || F16S1, "the per-spectrum factor of stage 3 lives beside the stage-1 scales");
-    static constexpr int ZT_B = F16S3 ? 1024 : 2048;         // bytes per column tile of the Z part
+    static constexpr int ZT_B = 1024;                        // bytes per column tile of the Z part
     static constexpr int Z_B = NWT * ZT_B;                   // bf16: [tile][operand 1, 2][lane (g, lo = row m)][4 dwords]; float16: [tile][lane][h01 h23 m01 m23]
     static constexpr int ZP_B = Z_B + 2 * 1024;              // + the p operands (gamma term: bf16 pieces, six products)
-    static constexpr int S1_ZFAC = S1_SCALES + 128;          // F16S3: float32 2^(7 - zk) of the 16 spectra (Z is stored as Z 2^zk)
+    static constexpr int S1_ZFAC = S1_SCALES + 128;          // stage 3 (float16 pieces): float32 2^(7 - zk) of the 16 spectra (Z is stored as Z 2^zk)
     static constexpr int STATE_B = S1P_B + ZP_B;
     static constexpr int NW = 8;                             // waves per workgroup
     // A wave owns TPW 16-pixel tiles = PXW pixels; tile j holds the pixels PXW wt + TPW lo + j (lo = the tile's column): a
@@ -88,38 +82,36 @@ template <int KP>
 __device__ __forceinline__ void build_state(const float *rows, int s0, int B, int Nh, unsigned char *__restrict__ st, int tid) {
     using C = Cfg<KP>;
     using GT = GTT<KP>;
-    // F16S1: the powers of two of the group's 16 spectra (16 threads per spectrum look at its Cinv' and y)
-    __shared__ float sc_[16][6];                                         // scale(Cinv'), scale(y), their inverses; F16S3: 2^zk of Z, 2^(7 - zk)
-    if constexpr (GT::F16S1) {
-        __syncthreads();                                                 // (k_solve calls this per group: the previous call's readers)
-        const int s = tid >> 4, sub = tid & 15;
-        const bool v = s0 + s < B;
-        const float *sol = rows + (size_t)(v ? s : 0) * C::NSOL;
-        float mc = 0.f, my = 0.f, mz = 0.f;
-        for (int q = sub; q < GT::KK2; q += 16) mc = fmaxf(mc, fabsf(sol[C::SOL_CI + q]));
-        if (sub < KP) my = fabsf(sol[sub]);
-        if (GT::F16S3) for (int q = sub; q < KP * KP; q += 16) mz = fmaxf(mz, fabsf(sol[C::SOL_Z + q]));
+    // stage 1 (float16 pieces): the powers of two of the group's 16 spectra (16 threads per spectrum look at its Cinv' and y)
+    __shared__ float sc_[16][6];                                         // scale(Cinv'), scale(y), their inverses; stage 3: 2^zk of Z, 2^(7 - zk)
+    __syncthreads();                                                 // (k_solve calls this per group: the previous call's readers)
+    const int s = tid >> 4, sub = tid & 15;
+    const bool v = s0 + s < B;
+    const float *sol = rows + (size_t)(v ? s : 0) * C::NSOL;
+    float mc = 0.f, my = 0.f, mz = 0.f;
+    for (int q = sub; q < GT::KK2; q += 16) mc = fmaxf(mc, fabsf(sol[C::SOL_CI + q]));
+    if (sub < KP) my = fabsf(sol[sub]);
+    for (int q = sub; q < KP * KP; q += 16) mz = fmaxf(mz, fabsf(sol[C::SOL_Z + q]));
 #pragma unroll
-        for (int o = 8; o >= 1; o >>= 1) {
-            mc = fmaxf(mc, __shfl_xor(mc, o)); my = fmaxf(my, __shfl_xor(my, o)); mz = fmaxf(mz, __shfl_xor(mz, o));
-        }
-        if (sub == 0) {
-            float ic, iy;
-            const float c_ = f16_row_scale(v ? mc : 0.f, ic), y_ = f16_row_scale(v ? my : 0.f, iy);
-            sc_[s][0] = c_; sc_[s][1] = y_; sc_[s][2] = ic; sc_[s][3] = iy;
-            // Z 2^zk with zk = 7 while |Z| < 128 (Z = C^-1 T: of order one), less beyond (|Z 2^zk| < 2^14 always)
-            int e = 0;
-            if (v && mz > 0.f && mz < 3.0e38f) (void)frexpf(mz, &e);                  // mz = m 2^e, m in [0.5, 1)
-            const int zk = e > 7 ? (e > 100 ? -86 : 14 - e) : 7;
-            sc_[s][4] = ldexpf(1.f, zk); sc_[s][5] = ldexpf(1.f, 7 - zk);
-        }
-        __syncthreads();
+    for (int o = 8; o >= 1; o >>= 1) {
+        mc = fmaxf(mc, __shfl_xor(mc, o)); my = fmaxf(my, __shfl_xor(my, o)); mz = fmaxf(mz, __shfl_xor(mz, o));
     }
+    if (sub == 0) {
+        float ic, iy;
+        const float c_ = f16_row_scale(v ? mc : 0.f, ic), y_ = f16_row_scale(v ? my : 0.f, iy);
+        sc_[s][0] = c_; sc_[s][1] = y_; sc_[s][2] = ic; sc_[s][3] = iy;
+        // Z 2^zk with zk = 7 while |Z| < 128 (Z = C^-1 T: of order one), less beyond (|Z 2^zk| < 2^14 always)
+        int e = 0;
+        if (v && mz > 0.f && mz < 3.0e38f) (void)frexpf(mz, &e);                  // mz = m 2^e, m in [0.5, 1)
+        const int zk = e > 7 ? (e > 100 ? -86 : 14 - e) : 7;
+        sc_[s][4] = ldexpf(1.f, zk); sc_[s][5] = ldexpf(1.f, 7 - zk);
+    }
+    __syncthreads();
     for (int i = tid; i < GT::NKS * 64; i += 256) {
         const int lane = i & 63, ks = i >> 6, lo = lane & 15, g = lane >> 4;
         const bool v = s0 + lo < B;
         const float *sol = rows + (size_t)(v ? lo : 0) * C::NSOL;
-        const float scl = GT::F16S1 ? sc_[lo][ks < GT::NKQ ? 0 : 1] : 1.f;
+        const float scl = sc_[lo][ks < GT::NKQ ? 0 : 1];
         float x[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
@@ -134,25 +126,17 @@ __device__ __forceinline__ void build_state(const float *rows, int s0, int B, in
             x[j] = val * scl;
         }
         unsigned char *dst = st + ks * GT::BLK_B + lane * 16;
-        if constexpr (GT::F16S1) {
-            u32x4 h, m;
-            split8h(x, h, m);
-            if (ks == GT::NKQ && g == 3) {                               // (zeros so far: the inverse scales of spectra 2 lo, 2 lo + 1)
-                static_assert(GT::YOFF + KP <= 24, "K slots 24..31 of the y block are free");
-                if (lo < 8) h = u32x4{__float_as_uint(sc_[2 * lo][2]), __float_as_uint(sc_[2 * lo][3]),
-                                      __float_as_uint(sc_[2 * lo + 1][2]), __float_as_uint(sc_[2 * lo + 1][3])};
-                else if (GT::F16S3 && lo < 12) h = u32x4{__float_as_uint(sc_[4 * (lo - 8)][5]), __float_as_uint(sc_[4 * (lo - 8) + 1][5]),
-                                                         __float_as_uint(sc_[4 * (lo - 8) + 2][5]), __float_as_uint(sc_[4 * (lo - 8) + 3][5])};
-            }
-            *reinterpret_cast<u32x4 *>(dst) = h;
-            *reinterpret_cast<u32x4 *>(dst + 1024) = m;
-        } else {
-            u32x4 h, m, l;
-            split8(x, h, m, l);
-            *reinterpret_cast<u32x4 *>(dst) = h;
-            *reinterpret_cast<u32x4 *>(dst + 1024) = m;
-            *reinterpret_cast<u32x4 *>(dst + 2048) = l;
+        u32x4 h, m;
+        split8h(x, h, m);
+        if (ks == GT::NKQ && g == 3) {                               // (zeros so far: the inverse scales of spectra 2 lo, 2 lo + 1)
+            static_assert(GT::YOFF + KP <= 24, "K slots 24..31 of the y block are free");
+            if (lo < 8) h = u32x4{__float_as_uint(sc_[2 * lo][2]), __float_as_uint(sc_[2 * lo][3]),
+                                  __float_as_uint(sc_[2 * lo + 1][2]), __float_as_uint(sc_[2 * lo + 1][3])};
+            else if (lo < 12) h = u32x4{__float_as_uint(sc_[4 * (lo - 8)][5]), __float_as_uint(sc_[4 * (lo - 8) + 1][5]),
+                                                     __float_as_uint(sc_[4 * (lo - 8) + 2][5]), __float_as_uint(sc_[4 * (lo - 8) + 3][5])};
         }
+        *reinterpret_cast<u32x4 *>(dst) = h;
+        *reinterpret_cast<u32x4 *>(dst + 1024) = m;
     }
     for (int i = tid; i < (GT::NWT + 1) * 64; i += 256) {
         const int lane = i & 63, wt = i >> 6, lo = lane & 15, g = lane >> 4;      // wt == NWT: the p operands
@@ -163,9 +147,9 @@ __device__ __forceinline__ void build_state(const float *rows, int s0, int B, in
             const bool v = s0 + 4 * g + r < B && bcol < Nh && (wt < GT::NWT || lo < KP);
             const float *sol = rows + (size_t)(v ? 4 * g + r : 0) * C::NSOL;
             x[r] = v ? (wt < GT::NWT ? sol[C::SOL_Z + a * KP + bcol] : sol[C::SOL_P + bcol]) : 0.f;
-            if (GT::F16S3 && wt < GT::NWT) x[r] *= sc_[4 * g + r][4];
+            if (wt < GT::NWT) x[r] *= sc_[4 * g + r][4];
         }
-        if (GT::F16S3 && wt < GT::NWT) {
+        if (wt < GT::NWT) {
             unsigned h01, m01, h23, m23;
             split2h(x[0], x[1], h01, m01);
             split2h(x[2], x[3], h23, m23);

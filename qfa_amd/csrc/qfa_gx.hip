@@ -18,28 +18,13 @@ static void gx_launch(const qfa_params_t &p, const qfa_batch_t &b, const qfa_tau
                       int ntiles32, const WorkPlan &wp, unsigned char *PGX, const float *SOL, const float4 *ZS,
                       const float4 *ZP, float *accum, float *slab, double *slabS, int slab_stride, Scal64 *sc64,
                       unsigned flags, hipStream_t st, bool prep) {
-    // QFA_WITH_GFORM (a variant build, make -C qfa_amd/csrc B=build/var_gform OUT=../libqfa_gform.so EXTRA=-DQFA_WITH_GFORM=1): the three-product G form of stage 3 behind QFA_F_S3_FAST --
-    // round 2's headline form, kept out of the shipped library from round 4 on (the host refuses the flag at N_h <= 16)
-#ifndef QFA_WITH_GFORM
-#define QFA_WITH_GFORM 0
-#endif
-    const bool fast = QFA_WITH_GFORM && (flags & QFA_F_S3_FAST) != 0;
     const int exact = (flags & QFA_F_EXACT_GRAD) ? 1 : 0;
-    if (prep) k_prep_pgx<KP><<<ntiles32, 256, 0, st>>>(p.F, p.Psi, p.omega, ZP, Npix, Nb, Nh, fast ? 0 : 1, PGX);
+    if (prep) k_prep_pgx<KP><<<ntiles32, 256, 0, st>>>(p.F, p.Psi, p.omega, ZP, Npix, Nb, Nh, 1, PGX);
     auto go = [&](auto hasa, auto terms, auto zf) {
         k_grads_x<KP, decltype(hasa)::value, decltype(terms)::value, decltype(zf)::value><<<wp.items(), 512, 0, st>>>(
             p, b, tau, B, Npix, Nb, Nh, ntiles32, wp, PGX, SOL, ZS, accum, slab, slabS, slab_stride, sc64, exact);
     };
     using T6 = std::integral_constant<int, 6>;
-#if QFA_WITH_GFORM
-    using T3 = std::integral_constant<int, 3>;
-    if (fast) {
-        if (b.A_blue) go(std::true_type{}, T3{}, std::false_type{});
-        else if (ZS) go(std::false_type{}, T3{}, std::true_type{});
-        else go(std::false_type{}, T3{}, std::false_type{});
-        return;
-    }
-#endif
     if (b.A_blue) go(std::true_type{}, T6{}, std::false_type{});
     else if (ZS) go(std::false_type{}, T6{}, std::true_type{});
     else go(std::false_type{}, T6{}, std::false_type{});

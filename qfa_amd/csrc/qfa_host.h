@@ -37,18 +37,10 @@ void qfa_px_launch(int KP, const float *F, const float *mu, int B, int Npix, int
 
 namespace {
 
-#ifndef QFA_P1_NW
-#define QFA_P1_NW 4         // waves per workgroup of k_moments_x at N_h <= 16: 4 = two workgroups per CU; 8 = one workgroup per CU, two
-                            // phase-shifted groups sharing the image ring (same results, measured slower: 1.44 against 1.31 ms at c3)
-#endif
-#ifndef QFA_P2_S12
-#define QFA_P2_S12 1        // pass 2 at N_h > 16: 1 = k_s12_x + two k_grads_s3, 0 = k_grads (f32 stage 1) + one k_grads_s3
-#endif
-
 #ifndef QFA_P1_MAX_CHAIN
 #define QFA_P1_MAX_CHAIN 32  // longest accumulation chain of pass 1 at N_h = 17..32, in 32-pixel tiles (make_layout_t).  Round 5: 64 -> 32 --
                              // F gradient of 4 096 c5-shape spectra against the float64 oracle 8.2e-5 -> 4.5e-5 (the chain bias of
-                             // qfa_xdl_kernels.h, QFA_P1_FRESH: N_h <= 16 has fresh accumulators instead), c5 step 5.32 -> 5.41 ms
+                             // qfa_xdl_kernels.h: N_h <= 16 has fresh accumulators per tile instead), c5 step 5.32 -> 5.41 ms
                              // (eight partial records per spectrum instead of four: k_sum_segments + 0.08 ms)
 #endif
 
@@ -130,7 +122,7 @@ struct Layout {
     int KP, NpixPad, ntiles, Bpad;
     int ntiles32;                                      // pass 1 on the XDL pipe walks 32-pixel tiles (N_h <= 16)
     WorkPlan wp1, wp2;                                 // work items of pass 1 / pass 2
-    int spb1;                                          // spectra per block of pass 1's plan (128 for the 8-wave k_moments_x)
+    static constexpr int spb1 = 64;                    // spectra per block of pass 1's plan (four waves of 16: k_moments_x)
     WorkPlan wp2x;                                     // pass 2 on the XDL pipe (k_grads_x: 32-pixel tiles, 1 workgroup per CU)
     WorkPlan wpp;                                      // posterior writer on the XDL pipe (k_predict_x, N_h <= 16)
     size_t oPF, oPFT, oPFX, oPGX, oPXI, oMOM, oSOL, oNLL, oNBL, oRED, oBG, oZS, oZP, oPST, oISLAB, total;   // float offsets
@@ -148,8 +140,8 @@ Layout make_layout_t(int B, int Npix) {
     L.ntiles32 = (Npix + 31) / 32;
     const int NCU = cu_count();
     L.wp2 = plan_work(B, L.ntiles, 4, NCU * (KP == 8 ? QFA_G8_OCC : (KP > 16 ? 1 : 2)));
-    // pass 1 runs on the XDL pipe at every N_h (32-pixel tiles; one workgroup per CU at N_h > 16)
-    L.spb1 = KP <= 16 ? 16 * QFA_P1_NW : 64;
+    // pass 1 runs on the XDL pipe at every N_h (32-pixel tiles; four waves per workgroup, two workgroups per CU at N_h <= 16 -- an
+    // 8-wave workgroup per CU with two phase-shifted groups on one image ring measured 1.44 against 1.31 ms at c3 -- one at N_h > 16)
     // Pass 1 sums C, T, b, b2 of a spectrum over the pixel axis in MFMA accumulators.  The matrix pipe aligns the 32 products
     // of an instruction with the accumulator they are added to and keeps about two bits below the accumulator's last place
     // (tools/ubench/mfma_round.hip: products of 1/16 ulp(C) vanish, of 1/4 ulp survive; the sum itself is rounded to nearest), so
@@ -158,12 +150,9 @@ Layout make_layout_t(int B, int Npix) {
     // (tools/chain_bias.py, c5's shape; 1.8e-6 against 6.3e-7 at c3's 125 tiles), and at N_h = 17..32 the F gradient of
     // 20 000 spectra came out 3.6e-4 from the oracle.  So at N_h = 17..32 no chain is longer than QFA_P1_MAX_CHAIN tiles (the
     // partial records are 4.5 KB per spectrum and segment: 90 MB per segment at c5, against 1.7 ms of pass 1).
-#ifndef QFA_P1_MAX_CHAIN16
-#define QFA_P1_MAX_CHAIN16 0   // experiment (round 5): the same bound at N_h <= 16; 0 = the work plan's own segmentation.  Superseded by
-                               // the fresh accumulators per tile of k_moments_x (QFA_P1_FRESH): profiles/r5_ablation.txt, section 2
-#endif
-    L.wp1 = KP <= 16 ? (QFA_P1_NW == 8 ? plan_work(B, L.ntiles32, 1, NCU, 128) : plan_work(B, L.ntiles32, 1, 2 * NCU, 64, QFA_P1_MAX_CHAIN16))
-                     : plan_work(B, L.ntiles32, 1, NCU, 64, QFA_P1_MAX_CHAIN);
+    // (N_h <= 16 keeps the work plan's own segmentation: the same bound there was superseded by the fresh accumulators per tile of
+    // k_moments_x, profiles/r5_ablation.txt, section 2)
+    L.wp1 = KP <= 16 ? plan_work(B, L.ntiles32, 1, 2 * NCU) : plan_work(B, L.ntiles32, 1, NCU, 64, QFA_P1_MAX_CHAIN);
     size_t o = 0;
     auto take = [&](size_t n) { size_t r = o; o += (n + 63) / 64 * 64; return r; };
     L.oPF = take((size_t)L.ntiles * C::TILE_PF);
@@ -175,7 +164,7 @@ Layout make_layout_t(int B, int Npix) {
     if constexpr (KP == 8 || KP == 16) {
         L.oPGX = take(qfa_gx_image_bytes(KP, L.ntiles32) / 4);
         L.wp2x = plan_work(B, L.ntiles32, 3, NCU, 64);
-    } else if constexpr (QFA_P2_S12 != 0) {            // N_h = 17..32: stages 1 and 2 of pass 2 by k_s12_x (qfa_s12_x.h)
+    } else {                                           // N_h = 17..32: stages 1 and 2 of pass 2 by k_s12_x (qfa_s12_x.h)
         L.oPGX = take((size_t)L.ntiles32 * (S12<KP>::TILE_B / 4));
         L.wp2x = plan_work(B, L.ntiles32, 3, NCU, 64);
     }
@@ -268,8 +257,7 @@ inline int check_shape(int B, int Npix, int Nb, int Nh) {
 //       0.274 / 0.260 at 32 000, 0.83 / 0.62 at 100 000 (k_grads_x<8> / k_grads_t<8>).
 // QFA_F_PASS2_F32 / QFA_F_PASS2_XDL / QFA_F_PASS2_PIXRES in the call's `flags` force one form (A/B timing and the cross-checks of
 // the forms in tests/).
-inline bool pass2_use_xdl(int KP, int B, unsigned flags) {
-    (void)B;
+inline bool pass2_use_xdl(int KP, unsigned flags) {
     if (flags & QFA_F_PASS2_F32) return false;
     return KP == 16 || KP == 8;
 }
@@ -348,7 +336,7 @@ void launch_moments(const qfa_params_t &p, const qfa_batch_t &b, const qfa_tau_t
         }
         k_prep_pfx<KP><<<L.ntiles32, 256, 0, st>>>(p.F, p.Psi, p.omega, PREDICT ? mu : nullptr, zt.ZP, -QFA_LOG2E * tau.offset, Npix, Nb, Nh, PFX);
     }
-    constexpr int NW = KP <= 16 ? QFA_P1_NW : 4;      // (L.spb1 = 16 NW spectra per block)
+    constexpr int NW = 4;                             // (L.spb1 = 16 NW spectra per block)
     // the exact-gradient step's instantiation leaves out the T-side moments where that measured faster (QFA_P1_SKIPT_EXACT_KP)
     constexpr bool SKIP_EX = !PREDICT && KP >= QFA_P1_SKIPT_EXACT_KP;
     if (SKIP_EX && exact) {
@@ -422,11 +410,8 @@ int run_nll_grad(const qfa_params_t &p, const qfa_batch_t &b, const qfa_tau_t &t
         if (events && events[i]) (void)hipEventRecord((hipEvent_t)events[i], st);
     };
     bool pass2_xdl = false;
-    if constexpr (KP == 8 || KP == 16) pass2_xdl = pass2_use_xdl(KP, B, flags);
-#ifndef QFA_WITH_GFORM
-    // the three-product form of stage 3 at N_h <= 16 (the G form of k_grads_x) is not part of the shipped library any more
+    if constexpr (KP == 8 || KP == 16) pass2_xdl = pass2_use_xdl(KP, flags);
     if constexpr (KP <= 16) { if (flags & QFA_F_S3_FAST) return QFA_E_FLAGS; }    // (the three-product form exists at N_h = 17..32 only)
-#endif
     mark(0);
     const bool pixres = pass2_xdl && pass2_use_pixres(KP, B, Npix, flags);             // (its ragged-tile staging wants N_pix >= 4)
     const size_t n_acc = (size_t)Npix * Nh + 3 * (size_t)Npix + Nb + 8;
@@ -512,7 +497,7 @@ int run_nll_grad(const qfa_params_t &p, const qfa_batch_t &b, const qfa_tau_t &t
         mark(4);
         return hip_status(st, flags);
     }
-    if constexpr (KP == 32 && QFA_P2_S12 != 0) {
+    if constexpr (KP == 32) {
         // stages 1 and 2 for every (spectrum, pixel) on the XDL pipe, beta / gamma through HBM, then stage 3 per 16 columns
         float *BG = ws + L.oBG, *GG = BG + (size_t)round_up(B, 64) * L.bg_stride;
         unsigned char *IMG = reinterpret_cast<unsigned char *>(ws + L.oPGX);
@@ -536,35 +521,20 @@ int run_nll_grad(const qfa_params_t &p, const qfa_batch_t &b, const qfa_tau_t &t
                 k_grads_s3<KP, 6><<<L.wp2.items(), 256, 0, st>>>(B, Npix, Nh, L.ntiles, L.wp2, bh, PFT, SOL, BG, GG, L.bg_stride, accum, slab, (int)D.stride);
         }
         if (slab) launch_reduce_slab(slab, D, B, L.wp2x.items() * 4, accum, st);
-        mark(4);
-        return hip_status(st, flags);
-    }
-    auto grads_e = [&](int bh, float *BG, float *GG, auto ex) {   // the float32-MFMA form: custom tau table / factored z / zabs
-        constexpr bool E = decltype(ex)::value;
-        if (b.A_blue)
-            k_grads<KP, true, false, E><<<L.wp2.items(), 256, 0, st>>>(p, b, tau, B, Npix, Nb, Nh, L.ntiles, L.wp2, bh, PFT, SOL, accum, slab, slabS, (int)D.stride, sc64, nullptr, BG, GG, L.bg_stride);
-        else if (zt.ZS)
-            k_grads<KP, false, true, E><<<L.wp2.items(), 256, 0, st>>>(p, b, tau, B, Npix, Nb, Nh, L.ntiles, L.wp2, bh, PFT, SOL, accum, slab, slabS, (int)D.stride, sc64, zt.ZS, BG, GG, L.bg_stride);
-        else
-            k_grads<KP, false, false, E><<<L.wp2.items(), 256, 0, st>>>(p, b, tau, B, Npix, Nb, Nh, L.ntiles, L.wp2, bh, PFT, SOL, accum, slab, slabS, (int)D.stride, sc64, nullptr, BG, GG, L.bg_stride);
-    };
-    auto grads = [&](int bh, float *BG, float *GG) {
-        if (exact) grads_e(bh, BG, GG, std::true_type{});
-        else grads_e(bh, BG, GG, std::false_type{});
-    };
-    if constexpr (KP == 32) {
-        // columns 0..15 by k_grads, which also stores beta and gamma; columns 16..31 by the stage-3-only kernel
-        float *BG = Nh > 16 ? ws + L.oBG : nullptr, *GG = Nh > 16 ? BG + (size_t)round_up(B, 64) * L.bg_stride : nullptr;
-        grads(0, BG, GG);
-        if (Nh > 16)
-            k_grads_s3<KP, 6><<<L.wp2.items(), 256, 0, st>>>(B, Npix, Nh, L.ntiles, L.wp2, 1, PFT, SOL, BG, GG, L.bg_stride, accum, slab, (int)D.stride);
     } else {
-    for (int bh = 0; bh < (KP + 15) / 16; ++bh) {          // one launch per 16 columns of the F gradient
-        if (16 * bh >= Nh) break;
-        grads(bh, nullptr, nullptr);
+        auto grads = [&](auto ex) {   // the float32-MFMA form (QFA_F_PASS2_F32): custom tau table / factored z / zabs
+            constexpr bool E = decltype(ex)::value;
+            if (b.A_blue)
+                k_grads<KP, true, false, E><<<L.wp2.items(), 256, 0, st>>>(p, b, tau, B, Npix, Nb, Nh, L.ntiles, L.wp2, 0, PFT, SOL, accum, slab, slabS, (int)D.stride, sc64, nullptr, nullptr, nullptr, L.bg_stride);
+            else if (zt.ZS)
+                k_grads<KP, false, true, E><<<L.wp2.items(), 256, 0, st>>>(p, b, tau, B, Npix, Nb, Nh, L.ntiles, L.wp2, 0, PFT, SOL, accum, slab, slabS, (int)D.stride, sc64, zt.ZS, nullptr, nullptr, L.bg_stride);
+            else
+                k_grads<KP, false, false, E><<<L.wp2.items(), 256, 0, st>>>(p, b, tau, B, Npix, Nb, Nh, L.ntiles, L.wp2, 0, PFT, SOL, accum, slab, slabS, (int)D.stride, sc64, nullptr, nullptr, nullptr, L.bg_stride);
+        };
+        if (exact) grads(std::true_type{});
+        else grads(std::false_type{});
+        if (slab) launch_reduce_slab(slab, D, B, L.wp2.items() * 4, accum, st);
     }
-    }
-    if (slab) launch_reduce_slab(slab, D, B, L.wp2.items() * 4, accum, st);
     mark(4);
     return hip_status(st, flags);
 }
@@ -578,10 +548,7 @@ int run_predict(const qfa_params_t &p, const float *mu, const qfa_batch_t &b, co
     auto mark = [&](int i) {
         if (events && events[i]) (void)hipEventRecord((hipEvent_t)events[i], st);
     };
-    bool writer_xdl = false;
-    if constexpr (KP <= 16 || QFA_P2_S12 != 0) {
-        writer_xdl = !(flags & QFA_F_PREDICT_F32);               // (the float32-MFMA writer: A/B timing, cross-check)
-    }
+    const bool writer_xdl = !(flags & QFA_F_PREDICT_F32);        // (the float32-MFMA writer: A/B timing, cross-check)
     mark(0);
     const ZTables zt = launch_zfac(p, b, tau, B, Nb, L, ws, st);
     // (PF / PFT: k_predict_out)
@@ -592,7 +559,7 @@ int run_predict(const qfa_params_t &p, const float *mu, const qfa_batch_t &b, co
     constexpr int G = 64 / KP;
     k_solve<KP, true><<<(B + 4 * G - 1) / (4 * G), 256, 0, st>>>(MOM, SOL, ll, nullptr, B, Nh, hmean, hcov);
     mark(2);
-    if constexpr (KP > 16 && QFA_P2_S12 != 0) {
+    if constexpr (KP > 16) {
         if (writer_xdl) {              // the image of k_s12_x with mu in the place of Psi (qfa_s12_x.h)
             unsigned char *IMG = reinterpret_cast<unsigned char *>(ws + L.oPGX);
             k_prep_s12<KP><<<L.ntiles32, 256, 0, st>>>(p.F, mu, p.omega, nullptr, Npix, Nb, Nh, IMG);

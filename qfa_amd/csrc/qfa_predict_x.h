@@ -13,21 +13,17 @@
 #include "qfa_common.h"
 #include "qfa_xdl_kernels.h"
 
-#ifndef QFA_PX_F16
-#define QFA_PX_F16 1
-#endif
 template <int KP>
 struct PX {
     static constexpr int KK2 = KP * (KP + 1) / 2;
     static constexpr int NKS = 1 + (KK2 + 31) / 32;          // K-steps: [hmean, 0 | pair products]; 3 at KP = 8, 6 at 16
-    // Round 5 (QFA_PX_F16): both operands as TWO float16 pieces, three products per K-step (qfa_common.h "float16 pieces").
+    // Round 5: both operands as TWO float16 pieces, three products per K-step (qfa_common.h "float16 pieces").
     // The image holds t f_a and t^2 f_a f_b with t the pixel's power of two; 1 / t and 1 / t^2 sit as float32 in K-step 0's
     // h piece, lanes g = 3 (K slots 24..31: they meet the zeros behind hmean).  [hmean] and [hcov'] of a spectrum get powers
     // of two of their own where the kernel builds its A operand.
-    static constexpr bool F16 = QFA_PX_F16 != 0;
-    static constexpr int NP = F16 ? 2 : 3;                   // pieces per K-step
+    static constexpr int NP = 2;                   // pieces per K-step (float16 h, m; A/B against three bf16 pieces: profiles/r5_ab_f16_writer.txt)
     static constexpr int KS_B = NP * 1024;
-    static_assert(!F16 || KP <= 24, "the scales live in K slots 24..31 of K-step 0");
+    static_assert(KP <= 24, "the scales live in K slots 24..31 of K-step 0");
     static constexpr int S1_HALF = NKS * KS_B;               // bytes of one 16-pixel half: [K-step][piece][lane][8 k]
     static constexpr int TILE_B = 2 * S1_HALF;               // per 32-pixel tile
     static constexpr int NCHUNK = TILE_B / 1024;
@@ -47,7 +43,7 @@ __global__ __launch_bounds__(256) void k_prep_px(const float *__restrict__ F, in
     }
     __syncthreads();
     __shared__ float tsc[32][3];                                  // F16: the pixel's power of two t, 1 / t, 1 / t^2
-    if (X::F16 && threadIdx.x < 32) {
+    if (threadIdx.x < 32) {
         float mx = 0.f;
         for (int a = 0; a < KP; ++a) mx = fmaxf(mx, fabsf(f[threadIdx.x][a]));
         int e = 7;
@@ -57,11 +53,11 @@ __global__ __launch_bounds__(256) void k_prep_px(const float *__restrict__ F, in
         tsc[threadIdx.x][1] = ldexpf(1.f, e - 7);
         tsc[threadIdx.x][2] = ldexpf(1.f, 2 * (e - 7));
     }
-    if (X::F16) __syncthreads();
+    __syncthreads();
     for (int i = threadIdx.x; i < 2 * X::NKS * 64; i += 256) {
         const int lane = i & 63, ks = (i >> 6) % X::NKS, h = i / (64 * X::NKS);
         const int lo = lane & 15, g = lane >> 4, px = 2 * lo + h;
-        const float t1 = X::F16 ? tsc[px][0] : 1.f, t2 = t1 * t1;
+        const float t1 = tsc[px][0], t2 = t1 * t1;
         float v[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
@@ -81,58 +77,32 @@ __global__ __launch_bounds__(256) void k_prep_px(const float *__restrict__ F, in
             v[j] = x;
         }
         unsigned char *dst = tile + h * X::S1_HALF + ks * X::KS_B + lane * 16;
-        if constexpr (X::F16) {
-            u32x4 ph, pm;
-            split8h(v, ph, pm);
-            if (ks == 0 && g == 3) ph = u32x4{__float_as_uint(tsc[px][1]), __float_as_uint(tsc[px][2]), 0u, 0u};
-            *reinterpret_cast<u32x4 *>(dst) = ph;
-            *reinterpret_cast<u32x4 *>(dst + 1024) = pm;
-        } else {
-            u32x4 ph, pm, pl;
-            split8(v, ph, pm, pl);
-            *reinterpret_cast<u32x4 *>(dst) = ph;
-            *reinterpret_cast<u32x4 *>(dst + 1024) = pm;
-            *reinterpret_cast<u32x4 *>(dst + 2048) = pl;
-        }
+        u32x4 ph, pm;
+        split8h(v, ph, pm);
+        if (ks == 0 && g == 3) ph = u32x4{__float_as_uint(tsc[px][1]), __float_as_uint(tsc[px][2]), 0u, 0u};
+        *reinterpret_cast<u32x4 *>(dst) = ph;
+        *reinterpret_cast<u32x4 *>(dst + 1024) = pm;
     }
 }
 
-#ifndef QFA_PX_REALIGN
-#define QFA_PX_REALIGN 1    // N_h <= 8: stores of whole aligned lines when the rows of cont / unc do not start on one
-#endif
-struct __attribute__((packed, aligned(4))) pxf2 { float v[2]; };       // 4-byte aligned 8-byte store
-#ifndef QFA_PX_NT
-#define QFA_PX_NT 1         // cont / unc leave as non-temporal stores (never read back by this call): writer at c3 0.87 - 0.91 -> 0.82 ms, same box
-#endif
-typedef float pxv2 __attribute__((ext_vector_type(2), aligned(4)));
+// cont / unc leave as non-temporal stores (never read back by this call): writer at c3 0.87 - 0.91 -> 0.82 ms, same box
+typedef float pxv2 __attribute__((ext_vector_type(2), aligned(4)));      // 4-byte aligned 8-byte store
 __device__ __forceinline__ void px_store2(float *dst, float a, float b) {
-#if QFA_PX_NT
     __builtin_nontemporal_store(pxv2{a, b}, reinterpret_cast<pxv2 *>(dst));
-#else
-    *reinterpret_cast<pxf2 *>(dst) = pxf2{{a, b}};
-#endif
 }
 
 // One work item = (block of 64 spectra, range of 32-pixel tiles); SOL as k_solve<KP, true> leaves it
 // ([hmean | hcov' with doubled off-diagonals]).
-#ifndef QFA_PX_ABL
-#define QFA_PX_ABL 0        // timing-only ablations of the whole-tile path: 1 no stores, 2 no MFMAs, 4 no image DMA behind the first
-#endif
-#ifndef QFA_PX_OCC2
-#define QFA_PX_OCC2 2       // workgroups per CU of the two-groups-per-wave form
-#endif
-#ifndef QFA_PX_SINGLE_B
-#define QFA_PX_SINGLE_B 1
-#endif
-// host side of the re-aligned store path's condition (see k_predict_x): rows that do not start on a 64-byte boundary
+// host side of the re-aligned store path's condition (see k_predict_x; N_h <= 8: stores of whole aligned lines when the rows of
+// cont / unc do not start on one): rows that do not start on a 64-byte boundary
 inline bool px_realign(int KP, int Npix, const void *cont, const void *unc) {
     const size_t ca = reinterpret_cast<size_t>(cont), ua = reinterpret_cast<size_t>(unc);
-    return KP == 8 && QFA_PX_REALIGN && ((ca ^ ua) & 127) == 0 && ((ca & 63) != 0 || (Npix & 15) != 0);
+    return KP == 8 && ((ca ^ ua) & 127) == 0 && ((ca & 63) != 0 || (Npix & 15) != 0);
 }
 template <int KP, int SPW = 1, bool RA = false>   // SPW: groups of 16 spectra per wave (2: every B-operand read from LDS feeds two
                                                   // MFMA chains); RA: re-aligned stores (N_h <= 8; its own instantiation: 156
                                                   // registers against 92 would cost the aligned shapes their fourth workgroup per CU)
-__global__ __launch_bounds__(256, (KP == 16 && SPW == 1) ? (QFA_PX_SINGLE_B ? 4 : 3) : ((KP == 8 && SPW == 1) ? 4 : QFA_PX_OCC2)) void k_predict_x(const float *__restrict__ mu, int B, int Npix, int ntiles,
+__global__ __launch_bounds__(256, SPW == 1 ? 4 : 2) void k_predict_x(const float *__restrict__ mu, int B, int Npix, int ntiles,
                                                       WorkPlan wp, const unsigned char *__restrict__ PXI,
                                                       const float *__restrict__ SOL, float *__restrict__ cont,
                                                       float *__restrict__ unc) {
@@ -154,9 +124,8 @@ __global__ __launch_bounds__(256, (KP == 16 && SPW == 1) ? (QFA_PX_SINGLE_B ? 4 
     const bool active = s0 < B;
     const int lo = lane & 15, g = lane >> 4;
     // A operand: spectrum s0 + lo, k = 32 ks + 8 g + j  (SPW = 2: a second set for the spectra s0 + 16 + lo)
-    constexpr bool F16 = X::F16;
-    u32x4 S1h[X::NKS], S1m[X::NKS], S1l[F16 ? 1 : X::NKS];
-    u32x4 T1h[SPW == 2 ? X::NKS : 1], T1m[SPW == 2 ? X::NKS : 1], T1l[(SPW == 2 && !F16) ? X::NKS : 1];
+    u32x4 S1h[X::NKS], S1m[X::NKS];
+    u32x4 T1h[SPW == 2 ? X::NKS : 1], T1m[SPW == 2 ? X::NKS : 1];
     // F16: the inverse powers of two of the spectra of the lane's OUTPUT rows (4 g + r): hmean, hcov'
     float ism[SPW][4], isq[SPW][4];
 #pragma unroll
@@ -180,50 +149,35 @@ __global__ __launch_bounds__(256, (KP == 16 && SPW == 1) ? (QFA_PX_SINGLE_B ? 4 
 #pragma unroll
             for (int j = 0; j < 8; ++j) xs[ks][j] = value(ks, j);
         float scm = 1.f, scq = 1.f;
-        if constexpr (F16) {
-            float mm = 0.f, mq = 0.f;
+        float mm = 0.f, mq = 0.f;
 #pragma unroll
-            for (int ks = 0; ks < X::NKS; ++ks)
+        for (int ks = 0; ks < X::NKS; ++ks)
 #pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    if (ks == 0) mm = fmaxf(mm, fabsf(xs[ks][j])); else mq = fmaxf(mq, fabsf(xs[ks][j]));
-                }
+            for (int j = 0; j < 8; ++j) {
+                if (ks == 0) mm = fmaxf(mm, fabsf(xs[ks][j])); else mq = fmaxf(mq, fabsf(xs[ks][j]));
+            }
 #pragma unroll
-            for (int o = 16; o <= 32; o <<= 1) { mm = fmaxf(mm, __shfl_xor(mm, o)); mq = fmaxf(mq, __shfl_xor(mq, o)); }
-            float im, iq;
-            scm = f16_row_scale(mm, im);
-            scq = f16_row_scale(mq, iq);
+        for (int o = 16; o <= 32; o <<= 1) { mm = fmaxf(mm, __shfl_xor(mm, o)); mq = fmaxf(mq, __shfl_xor(mq, o)); }
+        float im, iq;
+        scm = f16_row_scale(mm, im);
+        scq = f16_row_scale(mq, iq);
 #pragma unroll
-            for (int r = 0; r < 4; ++r) { ism[grp][r] = __shfl(im, 4 * g + r); isq[grp][r] = __shfl(iq, 4 * g + r); }
-        } else {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) ism[grp][r] = isq[grp][r] = 1.f;
-        }
+        for (int r = 0; r < 4; ++r) { ism[grp][r] = __shfl(im, 4 * g + r); isq[grp][r] = __shfl(iq, 4 * g + r); }
 #pragma unroll
         for (int ks = 0; ks < X::NKS; ++ks) {
             float x[8];
 #pragma unroll
             for (int j = 0; j < 8; ++j) x[j] = xs[ks][j] * (ks == 0 ? scm : scq);
-            if constexpr (F16) {
-                u32x4 a, b;
-                split8h(x, a, b);
-                if (grp == 0) { S1h[ks] = a; S1m[ks] = b; }
-                else { T1h[SPW == 2 ? ks : 0] = a; T1m[SPW == 2 ? ks : 0] = b; }
-            } else {
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    unsigned a, b, c;
-                    split2(x[2 * q], x[2 * q + 1], a, b, c);
-                    if (grp == 0) { S1h[ks][q] = a; S1m[ks][q] = b; S1l[F16 ? 0 : ks][q] = c; }
-                    else { T1h[SPW == 2 ? ks : 0][q] = a; T1m[SPW == 2 ? ks : 0][q] = b; T1l[(SPW == 2 && !F16) ? ks : 0][q] = c; }
-                }
-            }
+            u32x4 a, b;
+            split8h(x, a, b);
+            if (grp == 0) { S1h[ks] = a; S1m[ks] = b; }
+            else { T1h[SPW == 2 ? ks : 0] = a; T1m[SPW == 2 ? ks : 0] = b; }
         }
     }
     // F16: the lane's pixel of half h of the tile in ring slot `img`: 1 / t, 1 / t^2 (k_prep_px)
     auto pixel_scales = [&](const unsigned char *half) __attribute__((always_inline)) {
         typedef float f32x2t __attribute__((ext_vector_type(2)));
-        return F16 ? *reinterpret_cast<const f32x2t *>(half + (48 + lo) * 16) : f32x2t{1.f, 1.f};
+        return *reinterpret_cast<const f32x2t *>(half + (48 + lo) * 16);
     };
     const bool full_wave = active && s0 + 16 * SPW <= B;
     // mu of the lane's two pixels of tile tg, requested one tile ahead by asm loads IN FRONT of the image DMA of that tile:
@@ -296,22 +250,14 @@ __global__ __launch_bounds__(256, (KP == 16 && SPW == 1) ? (QFA_PX_SINGLE_B ? 4 
             for (int ks = 0; ks < X::NKS; ++ks) {
                 const u32x4 bh = *reinterpret_cast<const u32x4 *>(bp + ks * X::KS_B),
                             bm = *reinterpret_cast<const u32x4 *>(bp + ks * X::KS_B + 1024);
-                if constexpr (F16) {
-                    if (ks == 0) afy = xdl3h(S1h[ks], S1m[ks], bh, bm, afy);
-                    else aq = xdl3h(S1h[ks], S1m[ks], bh, bm, aq);
-                } else {
-                    const u32x4 bl = *reinterpret_cast<const u32x4 *>(bp + ks * X::KS_B + 2048);
-                    if (ks == 0) afy = xdl6(S1h[ks], S1m[ks], S1l[F16 ? 0 : ks], bh, bm, bl, afy);
-                    else aq = xdl6(S1h[ks], S1m[ks], S1l[F16 ? 0 : ks], bh, bm, bl, aq);
-                }
+                if (ks == 0) afy = xdl3h(S1h[ks], S1m[ks], bh, bm, afy);
+                else aq = xdl3h(S1h[ks], S1m[ks], bh, bm, aq);
                 __builtin_amdgcn_sched_barrier(0);           // (four waves per SIMD hide the LDS latency: one B buffer)
             }
-            if constexpr (F16) {
 #pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    afy[r] = (afy[r] * ism[0][r]) * its[0];
-                    aq[r] = (aq[r] * isq[0][r]) * its[1];
-                }
+            for (int r = 0; r < 4; ++r) {
+                afy[r] = (afy[r] * ism[0][r]) * its[0];
+                aq[r] = (aq[r] * isq[0][r]) * its[1];
             }
         };
         for (int c = 0; c < n; ++c) {
@@ -449,7 +395,7 @@ __global__ __launch_bounds__(256, (KP == 16 && SPW == 1) ? (QFA_PX_SINGLE_B ? 4 
         const float mc[2] = {mn0, mn1};
         if (c + 1 < n) {
             load_mu(t0 + c + 1);
-            if (!(QFA_PX_ABL & 4)) get_tile(c + 1);
+            get_tile(c + 1);
         }
         bool counted = false;
         if (active) {
@@ -472,37 +418,21 @@ __global__ __launch_bounds__(256, (KP == 16 && SPW == 1) ? (QFA_PX_SINGLE_B ? 4 
                         for (int pc = 0; pc < NP; ++pc)
                             bq[(ks + 1) & 1][pc] = *reinterpret_cast<const u32x4 *>(bp + (ks + 1) * X::KS_B + pc * 1024);
                     }
-                    const u32x4 &bh = bq[ks & 1][0], &bm = bq[ks & 1][1], &bl = bq[ks & 1][NP - 1];
-                    if (QFA_PX_ABL & 2) {
-                        afy[0] += __uint_as_float(bh[0] ^ bm[1] ^ bl[2]);
-                    } else if constexpr (F16) {
-                        f32x4 &c0 = ks == 0 ? afy : aq, &c1 = ks == 0 ? afy2 : aq2;
-                        if constexpr (SPW == 2) {       // two chains alternating (xdl3h's order)
-                            c0 = xdlh(S1h[ks], bm, c0); c1 = xdlh(T1h[ks], bm, c1);
-                            c0 = xdlh(S1m[ks], bh, c0); c1 = xdlh(T1m[ks], bh, c1);
-                            c0 = xdlh(S1h[ks], bh, c0); c1 = xdlh(T1h[ks], bh, c1);
-                        } else c0 = xdl3h(S1h[ks], S1m[ks], bh, bm, c0);
-                    } else if constexpr (SPW == 2) {    // two chains alternating (six_terms' order)
-                        f32x4 &c0 = ks == 0 ? afy : aq, &c1 = ks == 0 ? afy2 : aq2;
-                        constexpr int kl = F16 ? 0 : ks;
-                        c0 = xdl(S1h[ks], bl, c0); c1 = xdl(T1h[ks], bl, c1);
-                        c0 = xdl(S1l[kl], bh, c0); c1 = xdl(T1l[kl], bh, c1);
-                        c0 = xdl(S1m[ks], bm, c0); c1 = xdl(T1m[ks], bm, c1);
-                        c0 = xdl(S1m[ks], bh, c0); c1 = xdl(T1m[ks], bh, c1);
-                        c0 = xdl(S1h[ks], bm, c0); c1 = xdl(T1h[ks], bm, c1);
-                        c0 = xdl(S1h[ks], bh, c0); c1 = xdl(T1h[ks], bh, c1);
-                    } else if (ks == 0) afy = xdl6(S1h[ks], S1m[ks], S1l[F16 ? 0 : ks], bh, bm, bl, afy);
-                    else aq = xdl6(S1h[ks], S1m[ks], S1l[F16 ? 0 : ks], bh, bm, bl, aq);
+                    const u32x4 &bh = bq[ks & 1][0], &bm = bq[ks & 1][1];
+                    f32x4 &c0 = ks == 0 ? afy : aq, &c1 = ks == 0 ? afy2 : aq2;
+                    if constexpr (SPW == 2) {       // two chains alternating (xdl3h's order)
+                        c0 = xdlh(S1h[ks], bm, c0); c1 = xdlh(T1h[ks], bm, c1);
+                        c0 = xdlh(S1m[ks], bh, c0); c1 = xdlh(T1m[ks], bh, c1);
+                        c0 = xdlh(S1h[ks], bh, c0); c1 = xdlh(T1h[ks], bh, c1);
+                    } else c0 = xdl3h(S1h[ks], S1m[ks], bh, bm, c0);
                 }
-                if constexpr (F16) {
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        afy[r] = (afy[r] * ism[0][r]) * its[0];
-                        aq[r] = (aq[r] * isq[0][r]) * its[1];
-                        if (SPW == 2) {
-                            afy2[r] = (afy2[r] * ism[SPW - 1][r]) * its[0];
-                            aq2[r] = (aq2[r] * isq[SPW - 1][r]) * its[1];
-                        }
+                for (int r = 0; r < 4; ++r) {
+                    afy[r] = (afy[r] * ism[0][r]) * its[0];
+                    aq[r] = (aq[r] * isq[0][r]) * its[1];
+                    if (SPW == 2) {
+                        afy2[r] = (afy2[r] * ism[SPW - 1][r]) * its[0];
+                        aq2[r] = (aq2[r] * isq[SPW - 1][r]) * its[1];
                     }
                 }
                 const float m = mc[h];
@@ -519,11 +449,6 @@ __global__ __launch_bounds__(256, (KP == 16 && SPW == 1) ? (QFA_PX_SINGLE_B ? 4 
             const int px = 32 * tg + 2 * lo;
             if (RA && realign) {
                 counted = realign_store(tg, true, co, un);
-            } else if (QFA_PX_ABL & 1) {
-                float acc_ = 0.f;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) acc_ += co[0][r] + co[1][r] + un[0][r] + un[1][r] + (SPW == 2 ? co2[0][r] + co2[1][r] + un2[0][r] + un2[1][r] : 0.f);
-                if (acc_ == 1.2345e-30f) cont[0] = acc_;
             } else if (full_wave && 32 * tg + 31 < Npix) {          // wave-uniform: exactly 8 SPW store instructions
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {

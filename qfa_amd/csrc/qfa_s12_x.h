@@ -24,25 +24,18 @@
 #include "qfa_common.h"
 #include "qfa_xdl_kernels.h"
 
-#ifndef QFA_S12_ABL
-#define QFA_S12_ABL 0        // timing-only ablations: 1 no beta / gamma stores, 2 no spectra loads (and their share of the waits), 4 no stage 2, 8 staging from cache
-#endif
 typedef float s12_f32x2 __attribute__((ext_vector_type(2)));
-#ifndef QFA_S12_F16
-#define QFA_S12_F16 1
-#endif
 template <int KP>
 struct S12 {
     static constexpr int KK2 = KP * (KP + 1) / 2;
     static constexpr int NKS = 1 + (KK2 + 31) / 32;          // 18 at KP = 32
     static_assert(NKS % 2 == 0, "two quarters of NKS / 2 K-steps");
     static constexpr int NKQ = NKS / 2;                        // K-steps per quarter
-    // Round 5 (QFA_S12_F16): stage 1 on TWO float16 pieces per operand and three products per K-step (qfa_common.h "float16
+    // Round 5: stage 1 on TWO float16 pieces per operand and three products per K-step (qfa_common.h "float16
     // pieces"): 54 MFMAs per 16 spectra x 16 pixels instead of 108.  The image holds t f_a and t^2 f_a f_b (t: the pixel's power of
     // two, 1 / t and 1 / t^2 in the half's parameter KiB, floats 80.. and 96..); [y] and [C^-1'] (the writer: [hmean], [hcov'])
     // of a spectrum get powers of two of their own where the kernels build their A operand.
-    static constexpr bool F16 = QFA_S12_F16 != 0;
-    static constexpr int NP = F16 ? 2 : 3;                     // pieces per K-step
+    static constexpr int NP = 2;                               // pieces per K-step (float16 h, m; A/B against three bf16 pieces: profiles/r5_ab_f16_c5.txt)
     static constexpr int KS_B = NP * 1024;
     static constexpr int PAR_IT1 = 80, PAR_IT2 = 96;           // float index in a half's parameter KiB: 1 / t, 1 / t^2 of pixel 2 lo + h
     static constexpr int Q_B = NKQ * KS_B;                     // bytes of a quarter image (18 KiB; bf16 pieces: 27)
@@ -73,7 +66,7 @@ __global__ __launch_bounds__(256) void k_prep_s12(const float *__restrict__ F, c
     }
     __syncthreads();
     __shared__ float tsc[32][3];                                  // F16: the pixel's power of two t, 1 / t, 1 / t^2
-    if (X::F16 && threadIdx.x < 32) {
+    if (threadIdx.x < 32) {
         float mx = 0.f;
         for (int a = 0; a < KP; ++a) mx = fmaxf(mx, fabsf(f[threadIdx.x][a]));
         int e = 7;
@@ -83,11 +76,11 @@ __global__ __launch_bounds__(256) void k_prep_s12(const float *__restrict__ F, c
         tsc[threadIdx.x][1] = ldexpf(1.f, e - 7);
         tsc[threadIdx.x][2] = ldexpf(1.f, 2 * (e - 7));
     }
-    if (X::F16) __syncthreads();
+    __syncthreads();
     for (int i = threadIdx.x; i < 2 * X::NKS * 64; i += 256) {
         const int lane = i & 63, ks = (i >> 6) % X::NKS, h = i / (64 * X::NKS);
         const int lo = lane & 15, g = lane >> 4, px = 2 * lo + h;
-        const float t1 = X::F16 ? tsc[px][0] : 1.f, t2 = t1 * t1;
+        const float t1 = tsc[px][0], t2 = t1 * t1;
         float v[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
@@ -108,18 +101,10 @@ __global__ __launch_bounds__(256) void k_prep_s12(const float *__restrict__ F, c
         }
         const int qt = ks / X::NKQ, kq = ks % X::NKQ;
         unsigned char *dst = tile + h * X::HALF_B + qt * (X::Q_B + 1024) + kq * X::KS_B + lane * 16;
-        if constexpr (X::F16) {
-            u32x4 ph, pm;
-            split8h(v, ph, pm);
-            *reinterpret_cast<u32x4 *>(dst) = ph;
-            *reinterpret_cast<u32x4 *>(dst + 1024) = pm;
-        } else {
-            u32x4 ph, pm, pl;
-            split8(v, ph, pm, pl);
-            *reinterpret_cast<u32x4 *>(dst) = ph;
-            *reinterpret_cast<u32x4 *>(dst + 1024) = pm;
-            *reinterpret_cast<u32x4 *>(dst + 2048) = pl;
-        }
+        u32x4 ph, pm;
+        split8h(v, ph, pm);
+        *reinterpret_cast<u32x4 *>(dst) = ph;
+        *reinterpret_cast<u32x4 *>(dst + 1024) = pm;
     }
     for (int i = threadIdx.x; i < 512; i += 256) {            // Psi, omega of each half's pixels (+ zero padding of the KiB)
         const int h = i >> 8, j = i & 255;
@@ -131,7 +116,7 @@ __global__ __launch_bounds__(256) void k_prep_s12(const float *__restrict__ F, c
         else if (j < 80 && ZP && px < Nb) {                 // factored-z form: ti | pwi | l2i of the half's pixels
             const float4 q = ZP[px];
             v = j < 48 ? q.x : (j < 64 ? q.y : q.z);
-        } else if (X::F16 && j >= X::PAR_IT1 && j < X::PAR_IT2 + 16) v = tsc[2 * (j & 15) + h][j < X::PAR_IT2 ? 1 : 2];
+        } else if (j >= X::PAR_IT1 && j < X::PAR_IT2 + 16) v = tsc[2 * (j & 15) + h][j < X::PAR_IT2 ? 1 : 2];
         po[j] = v;
     }
 }
@@ -169,7 +154,7 @@ __global__ __launch_bounds__(256, 1) void k_s12_x(qfa_params_t p, qfa_batch_t bt
     for (int i = tid; i < 2 * 4 * 4 * 32; i += 256) (&lpsum[0][0][0][0])[i] = 0.f;      // inactive waves' rows stay 0
 
     // A operand of stage 1: spectrum s0 + lo, k = 32 ks + 8 g + j
-    u32x4 S1h[X::NKS], S1m[X::NKS], S1l[X::F16 ? 1 : X::NKS];
+    u32x4 S1h[X::NKS], S1m[X::NKS];
     float is0[4] = {1.f, 1.f, 1.f, 1.f}, is1[4] = {1.f, 1.f, 1.f, 1.f};      // F16: inverse powers of two of the spectra 4 g + r (y | C^-1')
     {
         const bool v = active && (s0 + lo) < B;
@@ -185,30 +170,27 @@ __global__ __launch_bounds__(256, 1) void k_s12_x(qfa_params_t p, qfa_batch_t bt
             return val;
         };
         float sc0 = 1.f, sc1 = 1.f;                              // powers of two of the spectrum's K-step 0 values / its pair values
-        if constexpr (X::F16) {
-            float m0 = 0.f, m1 = 0.f;
+        float m0 = 0.f, m1 = 0.f;
 #pragma unroll
-            for (int ks = 0; ks < X::NKS; ++ks)
+        for (int ks = 0; ks < X::NKS; ++ks)
 #pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const float a = fabsf(value(ks, 8 * g + j));
-                    if (ks == 0) m0 = fmaxf(m0, a); else m1 = fmaxf(m1, a);
-                }
+            for (int j = 0; j < 8; ++j) {
+                const float a = fabsf(value(ks, 8 * g + j));
+                if (ks == 0) m0 = fmaxf(m0, a); else m1 = fmaxf(m1, a);
+            }
 #pragma unroll
-            for (int o = 16; o <= 32; o <<= 1) { m0 = fmaxf(m0, __shfl_xor(m0, o)); m1 = fmaxf(m1, __shfl_xor(m1, o)); }
-            float i0, i1;
-            sc0 = f16_row_scale(m0, i0);
-            sc1 = f16_row_scale(m1, i1);
+        for (int o = 16; o <= 32; o <<= 1) { m0 = fmaxf(m0, __shfl_xor(m0, o)); m1 = fmaxf(m1, __shfl_xor(m1, o)); }
+        float i0, i1;
+        sc0 = f16_row_scale(m0, i0);
+        sc1 = f16_row_scale(m1, i1);
 #pragma unroll
-            for (int r = 0; r < 4; ++r) { is0[r] = __shfl(i0, 4 * g + r); is1[r] = __shfl(i1, 4 * g + r); }
-        }
+        for (int r = 0; r < 4; ++r) { is0[r] = __shfl(i0, 4 * g + r); is1[r] = __shfl(i1, 4 * g + r); }
 #pragma unroll
         for (int ks = 0; ks < X::NKS; ++ks) {
             float x[8];
 #pragma unroll
             for (int j = 0; j < 8; ++j) x[j] = value(ks, 8 * g + j) * (ks == 0 ? sc0 : sc1);
-            if constexpr (X::F16) split8h(x, S1h[ks], S1m[ks]);
-            else split8(x, S1h[ks], S1m[ks], S1l[ks]);
+            split8h(x, S1h[ks], S1m[ks]);
         }
     }
     bool sv[4];
@@ -237,8 +219,6 @@ __global__ __launch_bounds__(256, 1) void k_s12_x(qfa_params_t p, qfa_batch_t bt
 #pragma unroll
     for (int i = 0; i < 2; ++i) R2[i] = (unsigned)batch_row(bt, (active ? s0 : 0) + (int)slot_row(8 * i + (lane >> 3)));
     auto stage_tile = [&](int tg, int par) -> int {
-        if (QFA_S12_ABL & 2) return 8;
-        if (QFA_S12_ABL & 8) tg = t0;                 // timing only: the staging always re-reads the item's first tile (cache hits)
         const bool zblue = !ZF && tg < nbt;                                               // wave-uniform
         const bool fast = (32 * tg + 31 < Npix) && (!zblue || 32 * tg + 31 < Nb) && !QFA_TRACKED_LOADS;
         // the third array: zabs rows (Nb apart, Nb long) on a blue tile, else the delta rows again
@@ -325,7 +305,7 @@ __global__ __launch_bounds__(256, 1) void k_s12_x(qfa_params_t p, qfa_batch_t bt
             const float *po = reinterpret_cast<const float *>(img + X::Q_B);
             PsiH = po[lo];
             omH = po[16 + lo];
-            if (X::F16) { it1H = po[X::PAR_IT1 + lo]; it2H = po[X::PAR_IT2 + lo]; }
+            it1H = po[X::PAR_IT1 + lo]; it2H = po[X::PAR_IT2 + lo];
             if (ZF) { tiH = po[32 + lo]; pwiH = po[48 + lo]; l2iH = po[64 + lo]; }
         }
         constexpr int NP = X::NP;
@@ -340,33 +320,21 @@ __global__ __launch_bounds__(256, 1) void k_s12_x(qfa_params_t p, qfa_batch_t bt
                     bq[(kq + 1) & 1][pc] = *reinterpret_cast<const u32x4 *>(bp + (kq + 1) * X::KS_B + pc * 1024);
             }
             __builtin_amdgcn_sched_barrier(0);
-            const u32x4 &bh = bq[kq & 1][0], &bm = bq[kq & 1][1], &bl = bq[kq & 1][NP - 1];
+            const u32x4 &bh = bq[kq & 1][0], &bm = bq[kq & 1][1];
             // (ks = NKQ j + kq is a compile-time constant per (j, kq): j is passed as a literal below)
-            if constexpr (X::F16) {
-                if (j == 0) {
-                    if (kq == 0) afy = xdl3h(S1h[0], S1m[0], bh, bm, afy);
-                    else aq = xdl3h(S1h[kq], S1m[kq], bh, bm, aq);
-                } else {
-                    aq = xdl3h(S1h[X::NKQ + kq], S1m[X::NKQ + kq], bh, bm, aq);
-                }
+            if (j == 0) {
+                if (kq == 0) afy = xdl3h(S1h[0], S1m[0], bh, bm, afy);
+                else aq = xdl3h(S1h[kq], S1m[kq], bh, bm, aq);
             } else {
-                constexpr int L0 = X::F16 ? 0 : 1;
-                if (j == 0) {
-                    if (kq == 0) afy = xdl6(S1h[0], S1m[0], S1l[0], bh, bm, bl, afy);
-                    else aq = xdl6(S1h[kq], S1m[kq], S1l[L0 * kq], bh, bm, bl, aq);
-                } else {
-                    aq = xdl6(S1h[X::NKQ + kq], S1m[X::NKQ + kq], S1l[L0 * (X::NKQ + kq)], bh, bm, bl, aq);
-                }
+                aq = xdl3h(S1h[X::NKQ + kq], S1m[X::NKQ + kq], bh, bm, aq);
             }
             __builtin_amdgcn_sched_barrier(0);
         }
-        if constexpr (X::F16) {
-            if (j == 1) {                      // the powers of two back in: element r <-> spectrum 4 g + r, the lane's pixel
+        if (j == 1) {                      // the powers of two back in: element r <-> spectrum 4 g + r, the lane's pixel
 #pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    afy[r] = (afy[r] * is0[r]) * it1H;
-                    aq[r] = (aq[r] * is1[r]) * it2H;
-                }
+            for (int r = 0; r < 4; ++r) {
+                afy[r] = (afy[r] * is0[r]) * it1H;
+                aq[r] = (aq[r] * is1[r]) * it2H;
             }
         }
     };
@@ -443,7 +411,7 @@ __global__ __launch_bounds__(256, 1) void k_s12_x(qfa_params_t p, qfa_batch_t bt
                 gamR[r] = uu;
             }
         }
-        if (active && !(QFA_S12_ABL & 1)) {  // (bg_stride >= 32 ntiles: every pixel of the last tile has its own slot)
+        if (active) {  // (bg_stride >= 32 ntiles: every pixel of the last tile has its own slot)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const size_t o = (size_t)(s0 + 4 * g + r) * bg_stride + px;
@@ -472,7 +440,7 @@ __global__ __launch_bounds__(256, 1) void k_s12_x(qfa_params_t p, qfa_batch_t bt
     // different one per lane, or -- deterministic mode -- stores into the spare floats at the end of the slab row.
     float *sink = (det ? slab + (size_t)blk * (size_t)slab_stride + (slab_stride - 64) : accum) + lane;
     auto flush_P = [&](int tg, int par) {
-        if ((QFA_S12_ABL & 1) || tid >= 128) return;
+        if (tid >= 128) return;
         const int which = tid >> 5, pxl = tid & 31;
         const float v = (lpsum[par][0][which][pxl] + lpsum[par][1][which][pxl]) +
                         (lpsum[par][2][which][pxl] + lpsum[par][3][which][pxl]);
@@ -516,7 +484,7 @@ __global__ __launch_bounds__(256, 1) void k_s12_x(qfa_params_t p, qfa_batch_t bt
                     if (h == 0 && j == 0) {
                         if (c >= 1) {
                             flush_P(tile_of(c - 1), (c - 1) & 1);
-                            rest += (!(QFA_S12_ABL & 1) && tid < 128) ? 1 : 0;
+                            rest += tid < 128 ? 1 : 0;
                         }
                         if (active) {
                             take_tile(c & 1, cur);
@@ -532,10 +500,10 @@ __global__ __launch_bounds__(256, 1) void k_s12_x(qfa_params_t p, qfa_batch_t bt
                     if (active) {
                         if (j == 0) quarter(std::integral_constant<int, 0>{}, lds[u % RING]);
                         else quarter(std::integral_constant<int, 1>{}, lds[u % RING]);
-                        if (j == 1 && !(QFA_S12_ABL & 4)) {
+                        if (j == 1) {
                             if (tg < nbt) stage2(std::true_type{}, tg, h, cur, c & 1);
                             else stage2(std::false_type{}, tg, h, cur, c & 1);
-                            rest += (QFA_S12_ABL & 1) ? 0 : 8;
+                            rest += 8;
                         }
                     }
                     // the DMA of quarter u + 1 (issued at the start of the previous sub-step) must have landed; behind it in
@@ -601,7 +569,7 @@ __global__ __launch_bounds__(256, 1) void k_predict_x32(int B, int Npix, int nti
     const int n = t1 - t0;
     if (n <= 0) return;
 
-    u32x4 S1h[X::NKS], S1m[X::NKS], S1l[X::F16 ? 1 : X::NKS];   // A operand: spectrum s0 + lo, k = 32 ks + 8 g + j
+    u32x4 S1h[X::NKS], S1m[X::NKS];   // A operand: spectrum s0 + lo, k = 32 ks + 8 g + j
     float is0[4] = {1.f, 1.f, 1.f, 1.f}, is1[4] = {1.f, 1.f, 1.f, 1.f};      // F16: inverse powers of two of the spectra 4 g + r (hmean | hcov')
     {
         const bool v = active && (s0 + lo) < B;
@@ -617,30 +585,27 @@ __global__ __launch_bounds__(256, 1) void k_predict_x32(int B, int Npix, int nti
             return val;
         };
         float sc0 = 1.f, sc1 = 1.f;                              // powers of two of the spectrum's K-step 0 values / its pair values
-        if constexpr (X::F16) {
-            float m0 = 0.f, m1 = 0.f;
+        float m0 = 0.f, m1 = 0.f;
 #pragma unroll
-            for (int ks = 0; ks < X::NKS; ++ks)
+        for (int ks = 0; ks < X::NKS; ++ks)
 #pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const float a = fabsf(value(ks, 8 * g + j));
-                    if (ks == 0) m0 = fmaxf(m0, a); else m1 = fmaxf(m1, a);
-                }
+            for (int j = 0; j < 8; ++j) {
+                const float a = fabsf(value(ks, 8 * g + j));
+                if (ks == 0) m0 = fmaxf(m0, a); else m1 = fmaxf(m1, a);
+            }
 #pragma unroll
-            for (int o = 16; o <= 32; o <<= 1) { m0 = fmaxf(m0, __shfl_xor(m0, o)); m1 = fmaxf(m1, __shfl_xor(m1, o)); }
-            float i0, i1;
-            sc0 = f16_row_scale(m0, i0);
-            sc1 = f16_row_scale(m1, i1);
+        for (int o = 16; o <= 32; o <<= 1) { m0 = fmaxf(m0, __shfl_xor(m0, o)); m1 = fmaxf(m1, __shfl_xor(m1, o)); }
+        float i0, i1;
+        sc0 = f16_row_scale(m0, i0);
+        sc1 = f16_row_scale(m1, i1);
 #pragma unroll
-            for (int r = 0; r < 4; ++r) { is0[r] = __shfl(i0, 4 * g + r); is1[r] = __shfl(i1, 4 * g + r); }
-        }
+        for (int r = 0; r < 4; ++r) { is0[r] = __shfl(i0, 4 * g + r); is1[r] = __shfl(i1, 4 * g + r); }
 #pragma unroll
         for (int ks = 0; ks < X::NKS; ++ks) {
             float x[8];
 #pragma unroll
             for (int j = 0; j < 8; ++j) x[j] = value(ks, 8 * g + j) * (ks == 0 ? sc0 : sc1);
-            if constexpr (X::F16) split8h(x, S1h[ks], S1m[ks]);
-            else split8(x, S1h[ks], S1m[ks], S1l[ks]);
+            split8h(x, S1h[ks], S1m[ks]);
         }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // (the operand loads above are the only tracked loads)
@@ -673,7 +638,7 @@ __global__ __launch_bounds__(256, 1) void k_predict_x32(int B, int Npix, int nti
             afy = f32x4{0.f, 0.f, 0.f, 0.f};
             aq = f32x4{0.f, 0.f, 0.f, 0.f};
             muH = reinterpret_cast<const float *>(img + X::Q_B)[lo];
-            if (X::F16) { it1H = reinterpret_cast<const float *>(img + X::Q_B)[X::PAR_IT1 + lo]; it2H = reinterpret_cast<const float *>(img + X::Q_B)[X::PAR_IT2 + lo]; }
+            it1H = reinterpret_cast<const float *>(img + X::Q_B)[X::PAR_IT1 + lo]; it2H = reinterpret_cast<const float *>(img + X::Q_B)[X::PAR_IT2 + lo];
         }
         constexpr int NP = X::NP;
         u32x4 bq[2][NP];
@@ -687,32 +652,20 @@ __global__ __launch_bounds__(256, 1) void k_predict_x32(int B, int Npix, int nti
                     bq[(kq + 1) & 1][pc] = *reinterpret_cast<const u32x4 *>(bp + (kq + 1) * X::KS_B + pc * 1024);
             }
             __builtin_amdgcn_sched_barrier(0);
-            const u32x4 &bh = bq[kq & 1][0], &bm = bq[kq & 1][1], &bl = bq[kq & 1][NP - 1];
-            if constexpr (X::F16) {
-                if (j == 0) {
-                    if (kq == 0) afy = xdl3h(S1h[0], S1m[0], bh, bm, afy);
-                    else aq = xdl3h(S1h[kq], S1m[kq], bh, bm, aq);
-                } else {
-                    aq = xdl3h(S1h[X::NKQ + kq], S1m[X::NKQ + kq], bh, bm, aq);
-                }
+            const u32x4 &bh = bq[kq & 1][0], &bm = bq[kq & 1][1];
+            if (j == 0) {
+                if (kq == 0) afy = xdl3h(S1h[0], S1m[0], bh, bm, afy);
+                else aq = xdl3h(S1h[kq], S1m[kq], bh, bm, aq);
             } else {
-                constexpr int L0 = X::F16 ? 0 : 1;
-                if (j == 0) {
-                    if (kq == 0) afy = xdl6(S1h[0], S1m[0], S1l[0], bh, bm, bl, afy);
-                    else aq = xdl6(S1h[kq], S1m[kq], S1l[L0 * kq], bh, bm, bl, aq);
-                } else {
-                    aq = xdl6(S1h[X::NKQ + kq], S1m[X::NKQ + kq], S1l[L0 * (X::NKQ + kq)], bh, bm, bl, aq);
-                }
+                aq = xdl3h(S1h[X::NKQ + kq], S1m[X::NKQ + kq], bh, bm, aq);
             }
             __builtin_amdgcn_sched_barrier(0);
         }
-        if constexpr (X::F16) {
-            if (j == 1) {                      // the powers of two back in: element r <-> spectrum 4 g + r, the lane's pixel
+        if (j == 1) {                      // the powers of two back in: element r <-> spectrum 4 g + r, the lane's pixel
 #pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    afy[r] = (afy[r] * is0[r]) * it1H;
-                    aq[r] = (aq[r] * is1[r]) * it2H;
-                }
+            for (int r = 0; r < 4; ++r) {
+                afy[r] = (afy[r] * is0[r]) * it1H;
+                aq[r] = (aq[r] * is1[r]) * it2H;
             }
         }
     };
@@ -789,18 +742,12 @@ __global__ __launch_bounds__(256, 1) void k_predict_x32(int B, int Npix, int nti
 // beta / gamma k_s12_x (or k_grads) stored:  accF[px][b] += sum_s beta_{s,px} (F_tile Z_s)[px][b] + sum_s gamma_{s,px} p_s[b].
 // Work items and flush as k_grads (16-pixel tiles, 4 waves = 64 spectra, per-wave LDS slots summed in fixed order);
 // lane (px = lane & 15, g = lane >> 4): rows 4 g + r of the products.  Z_s (K = a = 32) as two bf16 pieces of all 16
-// spectra in 128 registers, TERMS piece products per spectrum (template argument: four by default, three with QFA_F_S3_FAST); 54 MFMAs and 64 FMAs per tile, no transcendental.
+// spectra in 128 registers, TERMS piece products per spectrum (template argument: six by default, on float16 pieces; three with QFA_F_S3_FAST); 54 MFMAs and 64 FMAs per tile, no transcendental.
 // Inputs of a tile arrive by LDS-DMA TWO tiles ahead into the wave's own buffers (ring of 3 x 4 KiB): the beta and gamma
 // tiles of its 16 spectra ([s][16 px] float, 64-byte row segments: one instruction each, and already the layout the
 // beta-scaling reads) and the two F pieces (1 KiB each).  A wave's queue holds those four requests per tile and its one
 // flush request; the wait at the start of a tile leaves the ten youngest in flight.
 // ------------------------------------------------------------------------------------------------
-#ifndef QFA_S3_SETPRIO
-#define QFA_S3_SETPRIO 2     // s_setprio around the products of a tile in k_grads_s3 (c5 pass 2 3.11 / 3.18 -> 3.08 / 3.14 ms, same box)
-#endif
-#ifndef QFA_S3_ABL
-#define QFA_S3_ABL 0         // timing-only ablations of k_grads_s3: 1 no flush, 2 no input DMA, 4 no beta-scaled products (gamma term only)
-#endif
 template <int KP, int TERMS>      // TERMS: bf16 piece products per stage-3 contraction -- 6 (default: float32 grade; the third
                                   // piece of Z is 64 more registers: one workgroup per CU), 4 or 3 (QFA_F_S3_FAST)
 __global__ __launch_bounds__(256, 2) void k_grads_s3(int B, int Npix, int Nh, int ntiles, WorkPlan wp, int bhalf,
@@ -810,11 +757,11 @@ __global__ __launch_bounds__(256, 2) void k_grads_s3(int B, int Npix, int Nh, in
                                                      int slab_stride) {
     static_assert(KP == 32, "k_grads_s3: N_h = 17..32");
     using C = Cfg<KP>;
-    // Round 5 (QFA_S3_F16, TERMS == 6 only): G_s = F_tile Z_s on TWO float16 pieces per operand, three products.  Both operands are
+    // Round 5 (TERMS == 6 only): G_s = F_tile Z_s on TWO float16 pieces per operand, three products.  Both operands are
     // prepared: F t_px (k_prep_pf; 1 / t_px rides as a fifth KiB) and Z_s 2^k of the wave's own spectra (scaled by their largest
     // element below); beta multiplies G in float32 behind the MFMA as before, so nothing here depends on the range of the data.
-    constexpr bool F16 = QFA_S3_F16 != 0 && TERMS == 6;
-    constexpr int RING = 3, BUF_B = TERMS == 6 ? 5120 : 4096;   // per wave and tile: beta 1 KiB | gamma 1 KiB | Fh 1 KiB | Fm 1 KiB (| Fl 1 KiB; F16: 1 / t)
+    constexpr bool F16 = TERMS == 6;
+    constexpr int RING = 3, BUF_B = TERMS == 6 ? 5120 : 4096;   // per wave and tile: beta 1 KiB | gamma 1 KiB | Fh 1 KiB | Fm 1 KiB (| F16: 1 / t)
     constexpr int NREQ = TERMS == 6 ? 5 : 4;                    // input requests per wave and tile
     __shared__ __attribute__((aligned(16))) unsigned char lin[4][RING][BUF_B];
     __shared__ float ldspart[2][4][256];
@@ -831,7 +778,7 @@ __global__ __launch_bounds__(256, 2) void k_grads_s3(int B, int Npix, int Nh, in
     for (int i = tid; i < 2 * 4 * 256; i += 256) (&ldspart[0][0][0])[i] = 0.f;      // inactive waves' slots stay 0
 
     // B operands: Z_s[a = 8g + j][col] of all 16 spectra as two bf16 pieces, p of the spectra 4g + j (gamma term)
-    u32x4 Zh[16], Zm[16], Zl[(TERMS == 6 && !F16) ? 16 : 1];
+    u32x4 Zh[16], Zm[16];
     float iz[16];                                               // F16: 1 / scale of Z_s (wave-uniform)
     u32x2 ph, pm, pl;
     {
@@ -865,7 +812,6 @@ __global__ __launch_bounds__(256, 2) void k_grads_s3(int B, int Npix, int Nh, in
                     split2(zraw[s][2 * q], zraw[s][2 * q + 1], h, m, l);
                     Zh[s][q] = h;
                     Zm[s][q] = m;
-                    if constexpr (TERMS == 6) Zl[F16 ? 0 : s][q] = l;
                 }
             }
         }
@@ -891,7 +837,6 @@ __global__ __launch_bounds__(256, 2) void k_grads_s3(int B, int Npix, int Nh, in
     const float *bgw = uniform_ptr(BG + (size_t)(active ? s0 : 0) * bg_stride);
     const float *ggw = uniform_ptr(GG + (size_t)(active ? s0 : 0) * bg_stride);
     auto get_tile = [&](int c) {
-        if ((QFA_S3_ABL & 2) && c > 0) return;
         const int tg = tile_of(c);
         const unsigned dst = wave_uniform(lds_addr(lin[wv][c % RING]));
         const unsigned o = 4u * ((unsigned)(lane >> 2) * (unsigned)bg_stride + 16u * (unsigned)tg + 4u * (unsigned)(lane & 3));
@@ -905,7 +850,6 @@ __global__ __launch_bounds__(256, 2) void k_grads_s3(int B, int Npix, int Nh, in
         } else {
             glds16a(fg, (unsigned)lane * 16u, dst + 2048);
             glds16a(fg + 256, (unsigned)lane * 16u, dst + 3072);
-            if constexpr (TERMS == 6) glds16a(fg + 512, (unsigned)lane * 16u, dst + 4096);
         }
     };
     auto flush = [&](int tg, const float (*pp)[256]) {
@@ -934,8 +878,6 @@ __global__ __launch_bounds__(256, 2) void k_grads_s3(int B, int Npix, int Nh, in
 
             const u32x4 Fh = *reinterpret_cast<const u32x4 *>(in + 2048 + lane * 16),
                         Fm = *reinterpret_cast<const u32x4 *>(in + 3072 + lane * 16);
-            u32x4 Fl = Fh;
-            if constexpr (TERMS == 6 && !F16) Fl = *reinterpret_cast<const u32x4 *>(in + 4096 + lane * 16);
             float itp[4] = {1.f, 1.f, 1.f, 1.f};                              // F16: 1 / t of the pixels 4 g + r of the tile
             if constexpr (F16) {
                 const float4 q4 = *reinterpret_cast<const float4 *>(in + 4096 + 16 * g);
@@ -943,7 +885,7 @@ __global__ __launch_bounds__(256, 2) void k_grads_s3(int B, int Npix, int Nh, in
             }
 
             float *part = ldspart[pbuf][wv];
-            if constexpr (QFA_S3_SETPRIO != 0) __builtin_amdgcn_s_setprio(QFA_S3_SETPRIO);
+            __builtin_amdgcn_s_setprio(2);          // (around the products of a tile: c5 pass 2 3.11 / 3.18 -> 3.08 / 3.14 ms, same box)
             unsigned h0, m0, l0, h1, m1, l1;
             split2(gam[(4 * g + 0) * 16 + lo], gam[(4 * g + 1) * 16 + lo], h0, m0, l0);
             split2(gam[(4 * g + 2) * 16 + lo], gam[(4 * g + 3) * 16 + lo], h1, m1, l1);
@@ -952,7 +894,7 @@ __global__ __launch_bounds__(256, 2) void k_grads_s3(int B, int Npix, int Nh, in
             f32x4 acc = F16 ? zero : gterm;
             const float4 *brow = reinterpret_cast<const float4 *>(bet) + g;          // beta[s][px = 4g .. 4g + 3]
 #pragma unroll
-            for (int s = 0; s < ((QFA_S3_ABL & 4) ? 0 : 16); ++s) {
+            for (int s = 0; s < 16; ++s) {
                 f32x4 G;
                 if constexpr (F16) {
                     G = xdl3h(Fh, Fm, Zh[s], Zm[s], zero);
@@ -963,8 +905,7 @@ __global__ __launch_bounds__(256, 2) void k_grads_s3(int B, int Npix, int Nh, in
                     acc[2] = fmaf(bq.z * z, G[2], acc[2]);
                     acc[3] = fmaf(bq.w * z, G[3], acc[3]);
                     continue;
-                } else if constexpr (TERMS == 6) G = xdl6(Fh, Fm, Fl, Zh[s], Zm[s], Zl[F16 ? 0 : s], zero);
-                else {
+                } else {
                     G = xdl(Fm, Zh[s], zero);
                     if (TERMS >= 4) G = xdl(Fm, Zm[s], G);
                     G = xdl(Fh, Zm[s], G);
@@ -982,13 +923,12 @@ __global__ __launch_bounds__(256, 2) void k_grads_s3(int B, int Npix, int Nh, in
             }
 #pragma unroll
             for (int rr = 0; rr < 4; ++rr) part[(4 * g + rr) * 16 + lo] = acc[rr];
-            if constexpr (QFA_S3_SETPRIO != 0) __builtin_amdgcn_s_setprio(0);
+            __builtin_amdgcn_s_setprio(0);
         }
         // The wave's inputs of tile c + 1 must have landed before it goes round; behind them in its queue are the
         // flush of tile c - 1 and the requests of tile c + 2, which stay in flight.
-        if (QFA_S3_ABL & 3) dma_wait<0>();
-        else if (c + 1 < n) dma_wait_n((c + 2 < n ? NREQ : 0) + (c >= 1 ? 1 : 0));
+        if (c + 1 < n) dma_wait_n((c + 2 < n ? NREQ : 0) + (c >= 1 ? 1 : 0));
         step_barrier();
-        if (!(QFA_S3_ABL & 1)) flush(tile_of(c), ldspart[pbuf]);          // ldspart[pbuf] is rewritten two tiles later, behind the next barrier
+        flush(tile_of(c), ldspart[pbuf]);          // ldspart[pbuf] is rewritten two tiles later, behind the next barrier
     }
 }

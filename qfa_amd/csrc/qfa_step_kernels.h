@@ -80,27 +80,25 @@ __global__ void k_prep_pf(const float *__restrict__ F, const float *__restrict__
                 split2(v0, v1, h, m, l);
                 fp[q] = h; fp[256 + q] = m; fp[512 + q] = l;
             }
-            if constexpr (QFA_S3_F16 != 0) {
-                // the same row as two float16 pieces of t F (k_grads_s3): t from the row's largest |f| (the four threads of a pixel are
-                // neighbours in a wave), 1 / t in the KiB behind the pieces
-                float mx = 0.f, x[8];
+            // the same row as two float16 pieces of t F (k_grads_s3): t from the row's largest |f| (the four threads of a pixel are
+            // neighbours in a wave), 1 / t in the KiB behind the pieces
+            float mx = 0.f, x[8];
 #pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    x[j] = (live && 8 * g + j < Nh) ? F[(size_t)i * Nh + 8 * g + j] : 0.f;
-                    mx = fmaxf(mx, fabsf(x[j]));
-                }
-                mx = fmaxf(mx, __shfl_xor(mx, 1));
-                mx = fmaxf(mx, __shfl_xor(mx, 2));
-                float it;
-                const float t = f16_row_scale(mx, it);
-#pragma unroll
-                for (int j = 0; j < 8; ++j) x[j] *= t;
-                u32x4 h4, m4;
-                split8h(x, h4, m4);
-#pragma unroll
-                for (int q = 0; q < 4; ++q) { fp[C::PFT_F16H + q] = h4[q]; fp[C::PFT_F16M + q] = m4[q]; }
-                if (g == 0) reinterpret_cast<float *>(PFT + (size_t)(i >> 4) * C::TILE_PFT + C::PFT_MAIN)[C::PFT_F16IT + (i & 15)] = it;
+            for (int j = 0; j < 8; ++j) {
+                x[j] = (live && 8 * g + j < Nh) ? F[(size_t)i * Nh + 8 * g + j] : 0.f;
+                mx = fmaxf(mx, fabsf(x[j]));
             }
+            mx = fmaxf(mx, __shfl_xor(mx, 1));
+            mx = fmaxf(mx, __shfl_xor(mx, 2));
+            float it;
+            const float t = f16_row_scale(mx, it);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) x[j] *= t;
+            u32x4 h4, m4;
+            split8h(x, h4, m4);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) { fp[C::PFT_F16H + q] = h4[q]; fp[C::PFT_F16M + q] = m4[q]; }
+            if (g == 0) reinterpret_cast<float *>(PFT + (size_t)(i >> 4) * C::TILE_PFT + C::PFT_MAIN)[C::PFT_F16IT + (i & 15)] = it;
         }
     } else if constexpr (C::XS3) {
         // F of this pixel as bf16 pieces, A operand of stage 3: [piece][g][px][a = 4g + j], 8 bytes per (g, px)
@@ -176,15 +174,13 @@ static __global__ void k_sum_segments(float4 *__restrict__ mom, const float4 *__
 // pivot column inside the lane group (DPP row broadcast at KP = 16, wavefront shuffles otherwise).  The pivots are the squared Cholesky diagonal, so
 // log det C = sum log(pivot) (finite where the reference's float32 det overflows, QFA/utils.py:54).
 // ------------------------------------------------------------------------------------------------
-#ifndef QFA_SOLVE_OCC4
-#define QFA_SOLVE_OCC4 1      // four waves per SIMD at N_h <= 16 (the state-writing instantiation sat at 130 VGPRs: 126 now, no scratch; c3 solve 0.179 -> 0.163 ms)
-#endif
+// Four waves per SIMD at N_h <= 16 (the state-writing instantiation sat at 130 VGPRs: 126 now, no scratch; c3 solve 0.179 -> 0.163 ms).
 // NLLRED (small batches, training): the block that finishes last also does k_reduce_nll's one-block job -- sum NLL, the number
 // of spectra with a blue pixel and B into the packed buffer's scalars `scal`, float64, the same fixed order (bit-identical) --
 // through the arrival counter ticket[1], which the step's first kernel (k_prep_step) zeroed: one link less in the chain of
 // dependent launches of a small-batch step.
 template <int KP, bool PREDICT, bool STATE = false, bool NLLRED = false>
-__global__ __launch_bounds__(256, (KP <= 16 && QFA_SOLVE_OCC4) ? 4 : 2) void k_solve(const float *__restrict__ MOM, float *__restrict__ SOL,
+__global__ __launch_bounds__(256, KP <= 16 ? 4 : 2) void k_solve(const float *__restrict__ MOM, float *__restrict__ SOL,
                                                float *__restrict__ nll_out, float *__restrict__ nblue_out, int B,
                                                int Nh, float *__restrict__ hmean, float *__restrict__ hcov,
                                                unsigned *__restrict__ ticket = nullptr,
@@ -459,9 +455,6 @@ static __global__ __launch_bounds__(256) void k_reduce_nll(const float *__restri
     }
 }
 
-#if QFA_ABL == 7
-__device__ unsigned long long qfa_dbg_stamps[64];
-#endif
 // ------------------------------------------------------------------------------------------------
 // k_grads (pass 2).  Lane (lo = lane&15, g = lane>>4) owns pixel 16*tile + lo of spectra
 // s0 + 4g + r (r = 0..3):
@@ -489,7 +482,7 @@ struct PixPar {                  // per-pixel parameters of the lane's pixel: Ps
     float Psi, om, ti, pwi, l2i;
 };
 template <int KP, bool HASA, bool ZF, bool EXACT>   // EXACT: QFA_F_EXACT_GRAD's tau0 / c0 / beta terms (as in k_grads_t)
-__global__ __launch_bounds__(256, KP > 16 ? 1 : (KP == 8 ? QFA_G8_OCC : 2)) void k_grads(qfa_params_t p, qfa_batch_t bt, qfa_tau_t tau, int B,
+__global__ __launch_bounds__(256, KP == 8 ? QFA_G8_OCC : 2) void k_grads(qfa_params_t p, qfa_batch_t bt, qfa_tau_t tau, int B,
                                                               int Npix, int Nb, int Nh, int ntiles, WorkPlan wp,
                                                               int bhalf, const float *__restrict__ PFT,
                                                               const float *__restrict__ SOL,
@@ -504,6 +497,10 @@ __global__ __launch_bounds__(256, KP > 16 ? 1 : (KP == 8 ? QFA_G8_OCC : 2)) void
     // scalar sums to slabS[item][wave][3]; k_reduce_slab adds the rows to accum in block order.
     // bhalf: which 16 columns of the F gradient this launch produces (N_h > 16 runs the kernel once per
     // half; the per-pixel and scalar sums are added by the bhalf == 0 launch only)
+    // N_h <= 16 only (QFA_F_PASS2_F32).  The KP = 32 arms below, bhalf and BG / GG / bg_stride (NULL and 0 from every caller) are what
+    // is left of the form that served N_h = 17..32; taking them out reorders instructions of the KP = 16 instantiations, so they wait
+    // for a change that is allowed to touch the kernel's code.
+    static_assert(KP <= 16, "k_grads: N_h <= 16 (N_h = 17..32 runs k_s12_x + k_grads_s3)");
     using C = Cfg<KP>;
     constexpr int KF = KP / 4, KQ = C::KK2 / 4;
     constexpr int NF4 = C::TILE_PFT / 4;
@@ -522,11 +519,6 @@ __global__ __launch_bounds__(256, KP > 16 ? 1 : (KP == 8 ? QFA_G8_OCC : 2)) void
     __shared__ float4 ldsfp[XDMA ? 3 : 1][NP4];                  // F as bf16 pieces (stage-3 A operand, KP = 16)
     __shared__ unsigned ldszl[XDMA ? 4 : 1][XDMA ? 16 * 64 * 2 : 1];   // third bf16 piece of Z (KP = 16), per wave [spectrum][lane][2]
     __shared__ float ldspart[2][4][NPART];
-#if QFA_ABL == 6                                                  // occupancy experiment: one workgroup per CU
-    __shared__ float ldspad[22000];
-    if (B < 0) ldspad[threadIdx.x] = 1.f;
-    if (B < -1) accum[0] = ldspad[threadIdx.x + 1];
-#endif
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wv = wave_uniform(tid >> 6);
@@ -564,7 +556,7 @@ __global__ __launch_bounds__(256, KP > 16 ? 1 : (KP == 8 ? QFA_G8_OCC : 2)) void
     //   ALL 16 spectra as bf16 pieces h, m (registers) and l (LDS); beta is applied to G_s on the VALU.
     constexpr int NZR = XS3 ? 1 : 4, NZA = XS3 ? 1 : KP, NZS = XS3 ? 16 : 1;
     float Zr[NZR][NZA], pr[4];
-    // (KP = 32, THIS kernel's own stage 3 -- the build-time fallback form QFA_P2_S12=0, not k_grads_s3, which issues six products
+    // (KP = 32, THIS kernel's own stage 3 -- not k_grads_s3, which issues six products
     // from round 4 on: K = a = 32 per MFMA, 8 values per lane and piece, the two leading pieces only -- four products, <= 2^-17
     // each; the third piece would take 16 KB of LDS per wave)
     using ZV = std::conditional_t<KP == 32, u32x4, u32x2>;
@@ -639,15 +631,6 @@ __global__ __launch_bounds__(256, KP > 16 ? 1 : (KP == 8 ? QFA_G8_OCC : 2)) void
     float4 tv0, tv1 = {0.f, 0.f, 0.f, 0.f}, tv2 = {0.f, 0.f, 0.f, 0.f}, tvx[TC::NX];
     double s_tau0 = 0.0, s_c0 = 0.0, s_beta = 0.0;   // float32 per tile, float64 across tiles
     int ntile_done = 0;                               // picks the flushing wave, round robin
-#if QFA_ABL == 7      // diagnostic build: where does a tile step spend its cycles (never shipped)
-    unsigned long long st_t[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // [blue 0..6 | red 8..14]
-#define QFA_STAMP(var)                                                                      \
-    __builtin_amdgcn_sched_barrier(0);                                                      \
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(var)::"memory");            \
-    __builtin_amdgcn_sched_barrier(0);
-#else
-#define QFA_STAMP(var)
-#endif
 
     auto run = [&](auto blue_tag, int ta, int tb) {
         constexpr bool BLUE = decltype(blue_tag)::value;
@@ -1014,10 +997,6 @@ __global__ __launch_bounds__(256, KP > 16 ? 1 : (KP == 8 ? QFA_G8_OCC : 2)) void
             const bool more = c + 1 < n;
             const int tg = tile_of(c);
             const int pbuf = c & 1;
-#if QFA_ABL == 7
-            unsigned long long q0 = 0, q1 = 0, q2 = 0, q3 = 0, q4 = 0, q5 = 0, q6 = 0, q7 = 0;
-#endif
-            QFA_STAMP(q0)
             f32x4 afyN = {0.f, 0.f, 0.f, 0.f}, aqN = {0.f, 0.f, 0.f, 0.f};
             PixPar pxpN{0.f, 0.f, 0.f, 0.f, 0.f};
             float betaR[4] = {0.f, 0.f, 0.f, 0.f}, gamR[4] = {0.f, 0.f, 0.f, 0.f};
@@ -1031,21 +1010,14 @@ __global__ __launch_bounds__(256, KP > 16 ? 1 : (KP == 8 ? QFA_G8_OCC : 2)) void
             }
             if (active) {
                 const int cn1 = more ? c + 1 : c;                 // last tile: harmless recomputation
-#if QFA_ABL != 2
                 load_spec(tile_of(cn1), nxt);
-#else
-                nxt = cur;
-#endif
-                QFA_STAMP(q1)
                 region1(tg, cur, afy, aq, pxp, tilebuf(cn1), afyN, aqN, pxpN, betaR, gamR,
                         ldspart[pbuf][wv]);
                 __builtin_amdgcn_sched_barrier(0);
-                QFA_STAMP(q2)
             }
             // parameter tile c+2: issued here so that its latency runs under stage 3
             if (c + 2 < n) get_tile(c + 2);
             if (active) {
-#if QFA_ABL != 5
                 if (BG) {                                  // (uniform; 64-byte segments: 16 pixels of one spectrum)
                     const size_t o = (size_t)(s0 + 4 * g) * bg_stride + 16 * tg + lo;
 #pragma unroll
@@ -1056,30 +1028,12 @@ __global__ __launch_bounds__(256, KP > 16 ? 1 : (KP == 8 ? QFA_G8_OCC : 2)) void
                 }
                 if constexpr (XS3) stage3x(ldsfp[XDMA ? c % 3 : 0], Fgh, Fgm, betaR, gamR, ldspart[pbuf][wv]);
                 else stage3(tilebuf(c), betaR, gamR, ldspart[pbuf][wv]);
-#else
-                asm volatile("" ::"v"(betaR[0]), "v"(betaR[1]), "v"(betaR[2]), "v"(betaR[3]), "v"(gamR[0]), "v"(gamR[1]),
-                             "v"(gamR[2]), "v"(gamR[3]));
-#endif
                 afy = afyN; aq = aqN; pxp = pxpN;
-                QFA_STAMP(q3)
-#if QFA_ABL == 7
-                st_t[(BLUE ? 0 : 8) + 0] += q1 - q0; st_t[(BLUE ? 0 : 8) + 1] += q2 - q1; st_t[(BLUE ? 0 : 8) + 2] += q3 - q2;
-#endif
             }
-            QFA_STAMP(q4)
             if (c + 2 < n) put_tile(c + 2);
-            QFA_STAMP(q5)
             __syncthreads();
-            QFA_STAMP(q6)
             // ldspart[pbuf] is rewritten two tiles later, i.e. after the next barrier
-#if QFA_ABL != 4 && !defined(QFA_NOFLUSH)
             flush(tg, ldspart[pbuf], wv == (ntile_done & 3));
-#endif
-            QFA_STAMP(q7)
-#if QFA_ABL == 7
-            st_t[(BLUE ? 0 : 8) + 3] += q5 - q4; st_t[(BLUE ? 0 : 8) + 4] += q6 - q5; st_t[(BLUE ? 0 : 8) + 5] += q7 - q6;
-            st_t[(BLUE ? 0 : 8) + 6] += 1;
-#endif
             ++ntile_done;
         };
 
@@ -1102,11 +1056,6 @@ __global__ __launch_bounds__(256, KP > 16 ? 1 : (KP == 8 ? QFA_G8_OCC : 2)) void
     run(std::true_type{}, t0, min(t1, nbt));
     run(std::false_type{}, max(t0, nbt), t1);
 
-#if QFA_ABL == 7
-    if (blk == 300 && lane == 0 && wv == 0 && seg < 4) {
-        for (int i = 0; i < 16; ++i) qfa_dbg_stamps[seg * 16 + i] = st_t[i];
-    }
-#endif
     if (!active) {
         if (det && lane == 0 && bhalf == 0) {              // the reducer reads every (item, wave) record
             double *q = slabS + ((size_t)blockIdx.x * 4 + wv) * 3;

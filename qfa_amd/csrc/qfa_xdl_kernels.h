@@ -369,23 +369,6 @@ __device__ __forceinline__ void land(SpecRegsX &r) {
     if (WITHZ) asm volatile("" : "+v"(r.z0), "+v"(r.z1));
 }
 
-#ifndef QFA_P1_EARLY_DMA
-#define QFA_P1_EARLY_DMA 0  // 1: image DMA of tile c + 1 at the START of step c instead of behind the weights (measured: 1.35 against 1.32 ms)
-#endif
-#ifndef QFA_P1_ABL
-#define QFA_P1_ABL 0        // timing-only ablations of k_moments_x (N_h <= 16): 1 no spectra reloads, 2 no MFMAs, 4 no weights, 8 no image DMA
-#endif
-#ifndef QFA_P1_CT_TERMS
-#define QFA_P1_CT_TERMS 6      // experiment: 4 = C and T from the two leading pieces of both operands
-#endif
-__device__ __forceinline__ f32x4 xdl_ct(const u32x4 &ah, const u32x4 &am, const u32x4 &al, const u32x4 &bh,
-                                        const u32x4 &bm, const u32x4 &bl, f32x4 c) {
-    if (QFA_P1_CT_TERMS == 6) return xdl6(ah, am, al, bh, bm, bl, c);
-    c = xdl(am, bm, c);
-    c = xdl(am, bh, c);
-    c = xdl(ah, bm, c);
-    return xdl(ah, bh, c);
-}
 // Fresh accumulators per tile (round 5).  v_mfma_f32_16x16x32_bf16 aligns its 32 products with the accumulator and truncates what
 // lies ~2 bits below its last place: a BIAS per instruction of ~2^-26 of the accumulator.  C, T, b, b2 of a spectrum used to run
 // through ONE accumulator chain over the whole pixel axis -- 125 tiles x 6 products = 750 instructions at c3 -- and the bias added
@@ -395,9 +378,6 @@ __device__ __forceinline__ f32x4 xdl_ct(const u32x4 &ah, const u32x4 &am, const 
 // the running sum by a float32 VALU add (round to nearest, no bias): the chain is six instructions long whatever N_pix is.
 // (N_h = 17..32 keeps its chains, cut at QFA_P1_MAX_CHAIN tiles by the work plan: its accumulators live in the AGPR half of the
 // file and the extra moves collide with the register prefetches.)
-#ifndef QFA_P1_FRESH
-#define QFA_P1_FRESH 1
-#endif
 __device__ __forceinline__ void acc_add(f32x4 &acc, const f32x4 &t) {
     typedef float f32x2p __attribute__((ext_vector_type(2)));            // two v_pk_add_f32 instead of four v_add_f32
     const f32x2p lo = f32x2p{acc[0], acc[1]} + f32x2p{t[0], t[1]}, hi = f32x2p{acc[2], acc[3]} + f32x2p{t[2], t[3]};
@@ -408,22 +388,6 @@ __device__ __forceinline__ void acc_add(f32x4 &acc, const f32x4 &t) {
 #endif
 #ifndef QFA_P1_SKIPT_EXACT_KP
 #define QFA_P1_SKIPT_EXACT_KP 8    // the exact-gradient step (QFA_F_EXACT_GRAD) at every N_h: measured faster or equal
-#endif
-#ifndef QFA_P1_PIPE
-#define QFA_P1_PIPE 1          // MFMA phase of pass 1 (N_h <= 16) as an explicit pipeline over the column tiles (mfmas_pipe)
-#endif
-#ifndef QFA_P1_PIPE_RED
-#define QFA_P1_PIPE_RED 1      // groups requested ahead on a red tile (a group = two column tiles, 12 MFMAs) ...
-#endif
-#ifndef QFA_P1_PIPE_BLUE
-#define QFA_P1_PIPE_BLUE 1     // ... and on a blue tile (a group = one column tile, 12 MFMAs); 2 before the fresh accumulators of round 5
-                               // took eight registers
-#endif
-#ifndef QFA_P1_PIPE_BLUE_ZABS
-#define QFA_P1_PIPE_BLUE_ZABS 0
-#endif
-#ifndef QFA_P1_MULMASK
-#define QFA_P1_MULMASK 1       // pass 1: the pixel mask as a float factor instead of selects / exec-mask branches (weights())
 #endif
 #ifndef QFA_P1_STAMPS
 #define QFA_P1_STAMPS 0    // diagnostic build (tools/p1_stamps.sh): s_memtime shares of the tile steps of one wave of pass 1
@@ -445,14 +409,16 @@ __device__ unsigned long long qfa_p1_stamps[2 * 16];
 // ZF: factored-z input form (ZS = per-spectrum factors; zabs is not read).  EXACT: the step of QFA_F_EXACT_GRAD, whose solve
 // reads neither T nor b2
 template <int KP, bool PREDICT, int NW, bool ZF, bool EXACT = false>
-__global__ __launch_bounds__(64 * NW, (KP > 16 || NW == 8) ? 1 : 2) void k_moments_x(qfa_params_t p, qfa_batch_t bt, qfa_tau_t tau,
+__global__ __launch_bounds__(64 * NW, KP > 16 ? 1 : 2) void k_moments_x(qfa_params_t p, qfa_batch_t bt, qfa_tau_t tau,
                                                       const float *__restrict__ mu, int B, int Bpad, int Npix, int Nb,
                                                       int ntiles, WorkPlan wp, const unsigned char *__restrict__ PFX,
                                                       const float4 *__restrict__ ZS, float *__restrict__ MOM) {
     using C = Cfg<KP>;
     using X = XCfg<KP>;
-    static_assert(NW == 4 || (NW == 8 && X::NSW == 1), "8 waves: the two-group form of N_h <= 16");
-    constexpr int RING = NW == 8 ? 3 : 2;
+    // (four waves, two workgroups per CU at N_h <= 16: one workgroup of 8 waves in two phase-shifted groups on a ring of three image
+    // slots gave the same results and measured slower, 1.44 against 1.31 ms at c3)
+    static_assert(NW == 4, "four waves of 16 spectra share the image ring");
+    constexpr int RING = 2;
     __shared__ __attribute__((aligned(16))) unsigned char lds[RING][X::SLOT_B];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -595,7 +561,6 @@ __global__ __launch_bounds__(64 * NW, (KP > 16 || NW == 8) ? 1 : 2) void k_momen
                 }
             }
             float qd8 = 0.f, ld8 = 0.f;
-#if QFA_P1_MULMASK
             // The mask as a FACTOR (round 4).  `w ? x : 0` per pixel compiles to an exec-mask branch per pixel (saveexec / xor /
             // or, zero-initialising moves: ~100 of the 440 instructions of a red tile step) or to three selects.  Here the
             // mask byte becomes m = 0.0 / 1.0 with ONE instruction (v_cvt_f32_ubyteN; min(., 1) so that any nonzero byte
@@ -676,68 +641,6 @@ __global__ __launch_bounds__(64 * NW, (KP > 16 || NW == 8) ? 1 : 2) void k_momen
             }
             qd += (double)qd8;
             ld += (double)(ld8 * QFA_LN2);
-            return;
-#endif
-            // pixel pair by pixel pair: weights of two pixels, then their bf16 pieces (short live ranges)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                float c2[2], c3[2], cb[2], cb2[2];
-#pragma unroll
-                for (int h2 = 0; h2 < 2; ++h2) {
-                    const int e = 2 * q + h2;
-                    const int px = 32 * tg + 8 * g + e;
-                    const unsigned mb = (cur.m[e >> 2] >> (8 * (e & 3))) & 0xffu;
-                    const bool wv_ = svalid & (mb != 0);
-                    float d = e < 4 ? cur.d0[e & 3] : cur.d1[e & 3];
-                    const float sg = e < 4 ? cur.s0[e & 3] : cur.s1[e & 3];
-                    float D, wD;
-                    if (BLUE) {
-                        const bool blue = px < Nb;
-                        const BlueTerms t = ZF ? blue_terms_zf(zs, ti[e], pwi[e], 0.f, k)
-                                               : blue_terms(e < 4 ? cur.z0[e & 3] : cur.z1[e & 3], k);
-                        float Ab = t.A;
-                        if (abase) Ab = abase[offB + min(px, Nb - 1)];        // custom tau callable (rare path)
-                        const float A = blue ? Ab : 1.f;
-                        const float zdom = blue ? t.zd * om[e] : 0.f;
-                        D = A * A * psi[e] + zdom + sg * sg;
-                        if (PREDICT) d = d - muv[e] * A;                     // QFA/model.py:166
-                        wD = wv_ ? fast_rcp(D) : 0.f;
-                        d = wv_ ? d : 0.f;
-                        const float wDA = wD * A;
-                        c2[h2] = wDA * A;
-                        cb[h2] = wDA * d;
-                        if (TSIDE) cb2[h2] = c2[h2] * d;
-                        if (X::F16) c2[h2] *= swt[e];
-                        if (TSIDE) c3[h2] = c2[h2] * A;
-                        cblue += (wv_ & blue) ? 1.f : 0.f;
-                    } else {                                                 // red side: A = 1, no omega term
-                        D = psi[e] + sg * sg;
-                        if (PREDICT) d = d - muv[e];
-                        wD = wv_ ? fast_rcp(D) : 0.f;
-                        d = wv_ ? d : 0.f;
-                        c2[h2] = X::F16 ? wD * swt[e] : wD;
-                        cb[h2] = wD * d;
-                    }
-                    qd8 += wD * d * d;
-                    ld8 += wv_ ? fast_log(D) : 0.f;
-                    cn += wv_ ? 1.f : 0.f;
-                }
-                unsigned h, m, l;
-                if (X::F16) { split2h(c2[0], c2[1], h, m); w.w1h[q] = h; w.w1m[q] = m; w.w1l[q] = 0u; }
-                else { split2(c2[0], c2[1], h, m, l); w.w1h[q] = h; w.w1m[q] = m; w.w1l[q] = l; }
-                split2(cb[0], cb[1], h, m, l);
-                w.w3h[q] = h; w.w3m[q] = m; w.w3l[q] = l;
-                if (TSIDE) {
-                    if (X::F16) { split2h(c3[0], c3[1], h, m); w.w2h[q] = h; w.w2m[q] = m; w.w2l[q] = 0u; }
-                    else { split2(c3[0], c3[1], h, m, l); w.w2h[q] = h; w.w2m[q] = m; w.w2l[q] = l; }
-                    split2(cb2[0], cb2[1], h, m, l);
-                    w.w4h[q] = h; w.w4m[q] = m; w.w4l[q] = l;
-                }
-                pin(qd8, ld8);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            qd += (double)qd8;
-            ld += (double)ld8;
         };
         // ---- phase 3: per 16-column tile of the image three ds_read_b128, then 6 (red) or 12 (blue) XDL MFMAs.
         // J: the sub-image in `tile` (N_h > 16: column tiles [0, CT1) or [CT1, NCT); else all of them)
@@ -751,13 +654,13 @@ __global__ __launch_bounds__(64 * NW, (KP > 16 || NW == 8) ? 1 : 2) void k_momen
             // (XCfg::F16: the pair column tiles are two float16 pieces -- three products)
             auto ct_terms = [&](const u32x4 &ah, const u32x4 &am, const u32x4 &al, int ct, f32x4 c) __attribute__((always_inline)) {
                 if constexpr (X::F16) return xdl3h(ah, am, rdB(0, ct), rdB(1, ct), c);
-                else return xdl_ct(ah, am, al, rdB(0, ct), rdB(1, ct), rdB(2, ct), c);
+                else return xdl6(ah, am, al, rdB(0, ct), rdB(1, ct), rdB(2, ct), c);
             };
 #pragma unroll
             for (int t = 0; t < C::NFT; ++t) {
                 if (t >= CT0 && t < CTE) {
                     const u32x4 bh = rdB(0, t), bm = rdB(1, t), bl = rdB(2, t);
-                    if (QFA_P1_FRESH && KP <= 16) {
+                    if (KP <= 16) {
                         const f32x4 z = {0.f, 0.f, 0.f, 0.f};
                         acc_add(accb[t], xdl6(w.w3h, w.w3m, w.w3l, bh, bm, bl, z));
                         if (TSIDE) acc_add(accb2[t], xdl6(w.w4h, w.w4m, w.w4l, bh, bm, bl, z));
@@ -770,7 +673,7 @@ __global__ __launch_bounds__(64 * NW, (KP > 16 || NW == 8) ? 1 : 2) void k_momen
 #pragma unroll
             for (int t = 0; t < C::NT; ++t) {
                 if (C::NFT + t >= CT0 && C::NFT + t < CTE) {
-                    if (QFA_P1_FRESH && KP <= 16) {
+                    if (KP <= 16) {
                         const f32x4 z = {0.f, 0.f, 0.f, 0.f};
                         acc_add(accC[t], ct_terms(w.w1h, w.w1m, w.w1l, C::NFT + t, z));
                         if (TSIDE) acc_add(accT[t], ct_terms(w.w2h, w.w2m, w.w2l, C::NFT + t, z));
@@ -792,9 +695,10 @@ __global__ __launch_bounds__(64 * NW, (KP > 16 || NW == 8) ? 1 : 2) void k_momen
             // column tiles in groups of GS whose MFMA chains alternate (a chain of six on one accumulator issues every
             // ~19 cycles, two alternating chains every 16): red tiles pair two column tiles, blue tiles the C-side and
             // the T-side chain of one; PFG groups are requested ahead
-            // (the zabs instantiation -- two more spectra registers sets of 8 -- requests its blue operands one group later: it has no
-            // registers for the two fresh accumulators otherwise)
-            constexpr int NCT = X::NCT, PS = X::pstr(0), GS = TSIDE ? 1 : 2, PFG = TSIDE ? (ZF ? QFA_P1_PIPE_BLUE : QFA_P1_PIPE_BLUE_ZABS) : QFA_P1_PIPE_RED;
+            // (one group ahead on a red tile and on a blue tile of the factored-z form -- two on blue tiles before the fresh accumulators
+            // took eight registers; the zabs instantiation -- two more spectra registers sets of 8 -- requests its blue operands one group
+            // later, none ahead: it has no registers for the two fresh accumulators otherwise)
+            constexpr int NCT = X::NCT, PS = X::pstr(0), GS = TSIDE ? 1 : 2, PFG = (TSIDE && !ZF) ? 0 : 1;
             constexpr int D = GS * (PFG + 1), NG = (NCT + GS - 1) / GS;
             constexpr int NR = (X::NCHUNK + NW - 1) / NW;                        // DMA requests per wave
             constexpr int RPG = (NR + NG - 2) / (NG - 1);                        // ... per group
@@ -809,7 +713,7 @@ __global__ __launch_bounds__(64 * NW, (KP > 16 || NW == 8) ? 1 : 2) void k_momen
                 return t < C::NFT ? (second ? accb2[t] : accb[t]) : (second ? accT[t - C::NFT] : accC[t - C::NFT]);
             };
             // six_terms' order, two chains alternating
-            // (QFA_P1_FRESH: c0 / c1 are the group's two FRESH accumulators tm0 / tm1; their sums join the running sums behind the
+            // (c0 / c1 are the group's two FRESH accumulators tm0 / tm1; their sums join the running sums behind the
             // group's requests -- by then the MFMAs have delivered -- see the loop below)
             f32x4 tm0 = {0.f, 0.f, 0.f, 0.f}, tm1 = {0.f, 0.f, 0.f, 0.f};
             auto six2 = [&](const u32x4 &ah, const u32x4 &am, const u32x4 &al, int q0, f32x4 &c0, const u32x4 &eh,
@@ -852,8 +756,8 @@ __global__ __launch_bounds__(64 * NW, (KP > 16 || NW == 8) ? 1 : 2) void k_momen
                 // the group's two accumulators: (C side, T side) of column tile t on a blue tile, column tiles t and t + 1 on a red one
                 f32x4 &ga0 = acc_of(t, false), &ga1 = TSIDE ? acc_of(t, true) : acc_of(t + 1 < NCT ? t + 1 : t, false);
                 const bool two = TSIDE || t + 1 < NCT;
-                if (QFA_P1_FRESH) tm0 = tm1 = f32x4{0.f, 0.f, 0.f, 0.f};
-                f32x4 &c0 = QFA_P1_FRESH ? tm0 : ga0, &c1 = QFA_P1_FRESH ? tm1 : ga1;
+                tm0 = tm1 = f32x4{0.f, 0.f, 0.f, 0.f};
+                f32x4 &c0 = tm0, &c1 = tm1;
                 if constexpr (X::F16) {
                     static_assert(!X::F16 || C::NFT == 1, "one F tile in front of the pair tiles");
                     if (TSIDE) {
@@ -892,10 +796,8 @@ __global__ __launch_bounds__(64 * NW, (KP > 16 || NW == 8) ? 1 : 2) void k_momen
                     spec_done = true;
                     if (reload) load_spec(tg_spec, cur);
                 }
-                if (QFA_P1_FRESH) {
-                    acc_add(ga0, tm0);
-                    if (two) acc_add(ga1, tm1);
-                }
+                acc_add(ga0, tm0);
+                if (two) acc_add(ga1, tm1);
                 __builtin_amdgcn_sched_barrier(0);
             }
         };
@@ -906,37 +808,26 @@ __global__ __launch_bounds__(64 * NW, (KP > 16 || NW == 8) ? 1 : 2) void k_momen
         // raw barrier waits for the DMA only: vmcnt counts in issue order and the spectra loads come after it.
         auto step = [&](int c, SpecRegsX &cur, int buf) {
             Pieces w;
-            if (QFA_P1_EARLY_DMA && c + 1 < n && !(QFA_P1_ABL & 8)) stage(ta + c + 1, buf ^ 1);
             __builtin_amdgcn_sched_barrier(0);
             P1S(0)
             land<BLUE && !ZF>(cur);
             P1S(1)
-            if (QFA_P1_ABL & 4) {            // timing only: no weights (pieces straight from the spectra registers)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    w.w1h[q] = w.w1m[q] = w.w1l[q] = __float_as_uint(cur.d0[q]);
-                    w.w3h[q] = w.w3m[q] = w.w3l[q] = __float_as_uint(cur.s0[q]);
-                    w.w2h[q] = w.w2m[q] = w.w2l[q] = __float_as_uint(cur.d1[q]);
-                    w.w4h[q] = w.w4m[q] = w.w4l[q] = __float_as_uint(cur.s1[q]);
-                }
-            } else if (active) weights(ta + c, cur, lds[buf] + X::OFF_PSI, w);
+            if (active) weights(ta + c, cur, lds[buf] + X::OFF_PSI, w);
             __builtin_amdgcn_sched_barrier(0);
             P1S(2)
-            const bool reload = active & (c + 2 < n) & !(QFA_P1_ABL & 1);
-            if (QFA_P1_PIPE && KP == 16 && QFA_P1_CT_TERMS == 6 && !QFA_P1_ABL && !QFA_P1_EARLY_DMA) {
+            const bool reload = active & (c + 2 < n);
+            if (KP == 16) {           // the MFMA phase as an explicit pipeline over the column tiles
                 if (active) mfmas_pipe(lds[buf], w, c + 1 < n, ta + c + 1, buf ^ 1, reload, ta + c + 2, cur);
                 else if (c + 1 < n) stage(ta + c + 1, buf ^ 1);
             } else {
-            if (!QFA_P1_EARLY_DMA && c + 1 < n && !(QFA_P1_ABL & 8)) stage(ta + c + 1, buf ^ 1);
-            __builtin_amdgcn_sched_barrier(0);
-            P1S(7)
-            if (reload) load_spec(ta + c + 2, cur);
-            __builtin_amdgcn_sched_barrier(0);
-            P1S(3)
-            if (QFA_P1_ABL & 2) {            // timing only: no MFMAs (the pieces stay live)
-                asm volatile("" ::"v"(w.w1h), "v"(w.w1m), "v"(w.w1l), "v"(w.w3h), "v"(w.w3m), "v"(w.w3l));
-                if (TSIDE) asm volatile("" ::"v"(w.w2h), "v"(w.w2m), "v"(w.w2l), "v"(w.w4h), "v"(w.w4m), "v"(w.w4l));
-            } else if (active) mfmas(lds[buf], w, std::integral_constant<int, 0>{});
+                // (the image DMA of tile c + 1 behind the weights: at the start of the step it measured 1.35 against 1.32 ms)
+                if (c + 1 < n) stage(ta + c + 1, buf ^ 1);
+                __builtin_amdgcn_sched_barrier(0);
+                P1S(7)
+                if (reload) load_spec(ta + c + 2, cur);
+                __builtin_amdgcn_sched_barrier(0);
+                P1S(3)
+                if (active) mfmas(lds[buf], w, std::integral_constant<int, 0>{});
             }
             P1S(4)
             // retire everything up to and including the DMA: it was issued before the 5 (red: 2 delta, 2 sigma,
@@ -976,33 +867,6 @@ __global__ __launch_bounds__(64 * NW, (KP > 16 || NW == 8) ? 1 : 2) void k_momen
             asm volatile("" ::: "memory");
         };
 
-        // NW = 8 (N_h <= 16): ONE workgroup of 8 waves = 128 spectra per CU shares the image ring (half the LDS-DMA per
-        // spectrum), waves w and w + 4 share a SIMD.  Group A (waves 0..3) runs [weights c | MFMAs c] in step c, group B
-        // (waves 4..7) [MFMAs c - 1 | weights c]: the VALU phase of one beside the XDL phase of the other.  B reads image
-        // c - 1 while image c + 1 arrives: ring of 3, the DMA issued at the start of the step (its slot was last read in
-        // step c - 1, by B).
-        const bool grpB = NW == 8 && wv >= 4;                    // wave-uniform
-        Pieces wB;
-        auto step8 = [&](int c, SpecRegsX &cur) {
-            const int slot = c % 3, nslot = (c + 1) % 3, pslot = (c + 2) % 3;
-            if (c + 1 < n) stage(ta + c + 1, nslot);
-            __builtin_amdgcn_sched_barrier(0);
-            land<BLUE && !ZF>(cur);
-            const bool reload = active & (c + 2 < n);
-            // (one weights site and one set of piece registers for both groups)
-            if (grpB && active && c > 0) mfmas(lds[pslot], wB, std::integral_constant<int, 0>{});
-            __builtin_amdgcn_sched_barrier(0);
-            if (active) weights(ta + c, cur, lds[slot] + X::OFF_PSI, wB);
-            __builtin_amdgcn_sched_barrier(0);
-            if (reload) load_spec(ta + c + 2, cur);
-            __builtin_amdgcn_sched_barrier(0);
-            if (!grpB && active) mfmas(lds[slot], wB, std::integral_constant<int, 0>{});
-            if (reload) dma_wait<(BLUE && !ZF) ? 7 : 5>();
-            else dma_wait<0>();
-            wg_barrier();
-            asm volatile("" ::: "memory");
-        };
-
         SpecRegsX ra, rb;
         stage(ta, 0);
         if (active) {
@@ -1011,13 +875,6 @@ __global__ __launch_bounds__(64 * NW, (KP > 16 || NW == 8) ? 1 : 2) void k_momen
         }
         dma_wait<0>();
         __syncthreads();
-        if constexpr (NW == 8) {
-            for (int c = 0; c < n; c += 2) {
-                step8(c, ra);
-                if (c + 1 < n) step8(c + 1, rb);
-            }
-            if (grpB && active) mfmas(lds[(n - 1) % 3], wB, std::integral_constant<int, 0>{});
-        } else
         for (int c = 0; c < n; c += 2) {
             if constexpr (X::NSW == 1) {
                 step(c, ra, 0);

@@ -87,7 +87,7 @@ def test_config3_100k_one_launch_vs_float64_oracle(dev, tmp_path):
     same 100 000 spectra on the host cores (tools/oracle_pool.py, ~40 s).  The normalised F gradient cancels 47x at this size (the data
     are drawn from the model: the expected gradient is zero): with pass 1's moments in ONE MFMA accumulator chain over the pixel axis it
     came out 1.9e-4 from the oracle (4.1e-6 of the cancelling sums); with the fresh accumulators per tile of round 5
-    (qfa_xdl_kernels.h, QFA_P1_FRESH) 6.4e-5 (1.4e-6).  Both input forms."""
+    (qfa_xdl_kernels.h, "Fresh accumulators per tile") 6.4e-5 (1.4e-6).  Both input forms."""
     import torch
     from qfa_amd import QFA, synthetic
     from tools import oracle_pool

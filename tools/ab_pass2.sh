@@ -1,5 +1,5 @@
 #!/bin/bash
-# GPU box: pass-2 time of library variants (tools/build_gt_variant.sh etc.), zabs form and factored-z form, back to back on one box.
+# GPU box: pass-2 time of library variants (make -C qfa_amd/csrc B=build/var_<variant> OUT=../libqfa_<variant>.so EXTRA=-D...), zabs form and factored-z form, back to back on one box.
 # usage: tools/ab_pass2.sh <variant> ...   ("default" = the shipped library; else qfa_amd/libqfa_<variant>.so, same ABI)
 out=${OUT_DIR:-bench_out}; mkdir -p "$out"
 for v in "$@"; do

@@ -1,5 +1,6 @@
 #!/bin/bash
-# GPU box: predict-call times of library variants back to back on one box.  usage: tools/ab_predict.sh <variant> ... ("default" = shipped)
+# GPU box: predict-call times of library variants back to back on one box.  usage: tools/ab_predict.sh <variant> ... ("default" = shipped;
+# a variant: make -C qfa_amd/csrc B=build/var_<variant> OUT=../libqfa_<variant>.so EXTRA=-D...)
 out=${OUT_DIR:-bench_out}; mkdir -p "$out"
 for v in "$@"; do
   if [ "$v" != "default" ]; then L="qfa_amd/libqfa_$v.so"; else L="qfa_amd/libqfa_hip.so"; fi

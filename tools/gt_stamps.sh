@@ -1,6 +1,6 @@
 #!/bin/bash
 # GPU box: s_memtime shares of the walk of waves 0 and 4 of one workgroup of k_grads_t (library variant built with
-# tools/build_gt_variant.sh st -DQFA_GT_STAMPS=1).  usage: tools/gt_stamps.sh <variant name>
+# make -C qfa_amd/csrc B=build/var_st OUT=../libqfa_st.so EXTRA=-DQFA_GT_STAMPS=1).  usage: tools/gt_stamps.sh <variant name>
 cd $GRAFT_REPO_ROOT
 QFA_STAMP_LIB=$PWD/qfa_amd/libqfa_$1.so python - <<'PY'
 import ctypes, sys, os, runpy

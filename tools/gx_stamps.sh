@@ -1,6 +1,6 @@
 #!/bin/bash
 # GPU box: s_memtime shares of one workgroup's tile steps in k_grads_x (library variant built with -DQFA_GX_STAMPS=1:
-# tools/build_gx_variant.sh st -DQFA_GX_STAMPS=1).  usage: tools/gx_stamps.sh <variant name>
+# make -C qfa_amd/csrc B=build/var_st OUT=../libqfa_st.so EXTRA=-DQFA_GX_STAMPS=1).  usage: tools/gx_stamps.sh <variant name>
 cd $GRAFT_REPO_ROOT
 QFA_STAMP_LIB=$PWD/qfa_amd/libqfa_$1.so python - <<'PY'
 import ctypes, sys, os, runpy

@@ -1,6 +1,6 @@
 #!/bin/bash
 # GPU box: s_memtime shares of the tile steps of wave 0 of one workgroup of k_moments_x (library variant built with
-# tools/build_capi_variant.sh p1st -DQFA_P1_STAMPS=1).  usage: tools/p1_stamps.sh <variant name>
+# make -C qfa_amd/csrc B=build/var_p1st OUT=../libqfa_p1st.so EXTRA=-DQFA_P1_STAMPS=1).  usage: tools/p1_stamps.sh <variant name>
 cd $GRAFT_REPO_ROOT
 QFA_STAMP_LIB=$PWD/qfa_amd/libqfa_$1.so python - <<'PY'
 import ctypes, sys, os, runpy
