@@ -256,6 +256,43 @@ size_t qfa_continua_workspace_bytes(int Npix, int Nh);
 int qfa_continua_f32(const float *F, const float *mu, const float *h, int64_t R, int Npix, int Nh, float *out,
                      void *workspace, size_t workspace_bytes, void *stream);
 
+/* Mock spectra and posterior-predictive replicates (additive to ABI v4).  The model is generative -- reference README.md:46-54,
+ *   flux = A (mu + F h + sqrt(Psi) e1) + sqrt(omega zdep) e2 + sigma e3,
+ * with the noise terms of QFA/model.py:125-131 -- but the reference only ever draws continua, one vector at a time in numpy
+ * (nb/generate_mock_continuum.ipynb cell 7).  This call draws whole spectra on the device, under each spectrum's own noise and mask.
+ *
+ * The draw contract.  For spectrum b of a call, r = row0 + b is its global row (int64); for replicate s (0 <= s < S) and pixel p:
+ *   latent     h[b,s,:] is an INPUT, (B, S, Nh) float32: qfa_sample_latent_f32's output.  With hmean = 0, hcov = I that call draws
+ *              from the prior (mock data); with the posterior of qfa_predict_f32 the result is a posterior-predictive replicate;
+ *   noise      the three noise terms are independent Gaussians and are drawn as ONE normal of variance
+ *              D = A^2 Psi + omega zdep + sigma^2   (sigma = b->error; SURVEY App. A step 3, the D of the likelihood kernels);
+ *   normal     e[r,s,p] = z[p & 3] of the Philox4x32-10 / float64 Box-Muller normals above, key = (seed & 0xffffffff, seed >> 32),
+ *              counter = (0x80000000 | (p >> 2), s, r & 0xffffffff, r >> 32): four consecutive pixels share one Philox call.  The
+ *              latent stream's first counter word is 0..7, so bit 31 keeps the two streams disjoint under one seed;
+ *   value      c = mu[p] + sum_j F[p,j] h[b,s,j], the float32 fma chain of qfa_continua_f32 in order of j;
+ *              flux = fma(sqrt(D), e, A c) in float32, A c and sqrt(D) each rounded once.  A and zdep are evaluated the way the
+ *              likelihood kernels evaluate them (the `tau` model; zabs, or the factored zq1 / pix_ratio form, or A_blue for a
+ *              custom tau, which is read in batch order and needs zabs for zdep); on red pixels A = 1, zdep = 0;
+ *   masks      b->mask == NULL: every pixel is used.  A masked pixel gets exactly -999.0f (the loader's sentinel) in every output;
+ *              what `error` holds under the mask (-999, NaN, inf) reaches no output (a select, not a product);
+ *   outputs    flux (B, S, Npix) and delta = flux - fl(mu A) (B, S, Npix) with the same float32 A; either may be NULL, not both;
+ *              contiguous at any 4-byte alignment (rows that start on 16-byte boundaries are stored as whole dwordx4), 64-bit
+ *              indices (B S Npix may pass 2^31).
+ * Consequences: a value depends only on (seed, r, s, p), the parameters and the inputs of its own spectrum -- not on how a data
+ * set is cut into calls, the launch shape or the number of ranks that share the rows; a non-finite h[b,s,:] makes the unmasked
+ * pixels of replicate (b, s) non-finite and touches nothing else.  The call neither synchronises nor allocates (graph-capturable;
+ * a captured graph replays the seed and row0 it was captured with).
+ *
+ * qfa_batch_t: error, mask (may be NULL), zabs | zq1 + pix_ratio | zabs + A_blue, rows / row_stride (the resident form: replicates
+ * of a resident data set need no gather; h and the outputs are in batch order).  b->delta is not read.
+ * workspace: qfa_mock_workspace_bytes (an image of F, mu, Psi, omega and the per-pixel factors of the factored-z form; 0 =
+ * unsupported shape).  Returns QFA_E_NULL for a missing required pointer, QFA_E_SIZE for B < 0, S < 1, Nh outside 1..32, row0 < 0,
+ * Npix < 1, Nb outside 0..Npix or 0 < row_stride < Npix, QFA_E_WORKSPACE; B = 0 does nothing. */
+size_t qfa_mock_workspace_bytes(int Npix, int Nh);
+int qfa_mock_spectra_f32(const qfa_params_t *p, const float *mu, const qfa_batch_t *b, const qfa_tau_t *tau, const float *h,
+                         int B, int S, int Npix, int Nb, int Nh, uint64_t seed, int64_t row0, float *flux, float *delta,
+                         void *workspace, size_t workspace_bytes, void *stream);
+
 /* Closed-form EM update of the factor loadings F (additive to ABI v4).  The reference moves every parameter with Adam
  * (QFA/model.py:212-214); F is the one group whose M-step has a closed form.  Per batch, at the current parameters, with the
  * posterior of the latent h of every spectrum s (y_s = C_s^-1 b_s as in qfa_predict_f32's hmean, E_s = C_s^-1 + y_s y_s^T):

@@ -19,6 +19,7 @@ EXPORTS = (
     "qfa_adam_clip_multi_f32", "qfa_clip_f32", "qfa_smooth_f32", "qfa_tau_f32", "qfa_tauhi_f32", "qfa_omega_func_f32", "qfa_woodbury_f32", "qfa_build_batch_f32", "qfa_mu_estimate_f64",
     "qfa_mu_sums_f64", "qfa_mu_finish_f64", "qfa_build_resident_f32", "qfa_finalize_adam_clip_f32", "qfa_zabs_factor_f32",
     "qfa_sample_latent_f32", "qfa_continua_workspace_bytes", "qfa_continua_f32",
+    "qfa_mock_workspace_bytes", "qfa_mock_spectra_f32",
     "qfa_em_floats", "qfa_em_workspace_bytes", "qfa_em_stats_f32", "qfa_em_update_f_f32",
 )
 
@@ -113,6 +114,9 @@ def lib():
         "qfa_sample_latent_f32": (i, [p, p, i, i, i, C.c_uint64, i64, p, p]),
         "qfa_continua_workspace_bytes": (sz, [i, i]),
         "qfa_continua_f32": (i, [p, p, p, i64, i, i, p, p, sz, p]),
+        "qfa_mock_workspace_bytes": (sz, [i, i]),
+        "qfa_mock_spectra_f32": (i, [C.POINTER(Params), p, C.POINTER(Batch), C.POINTER(TauModel), p, i, i, i, i, i, C.c_uint64, i64,
+                                     p, p, p, sz, p]),
         "qfa_em_floats": (sz, [i, i]),
         "qfa_em_workspace_bytes": (sz, [i, i, i]),
         "qfa_em_stats_f32": (i, [C.POINTER(Params), C.POINTER(Batch), C.POINTER(TauModel), i, i, i, i, p, p, p, sz, C.c_uint, p]),

@@ -128,7 +128,8 @@ def main(argv=None):
         load_model_file(model, cfg.MODEL.RESUME, cfg)         # parameters and mu of the trained model
         ts = time.time()
         model.predict_to_npz(dataloader, os.path.join(cfg.DATA.OUTPUT_DIR, "predict"),
-                             n_samples=int(cfg.MODEL.N_SAMPLES), seed=int(cfg.MODEL.SAMPLE_SEED))
+                             n_samples=int(cfg.MODEL.N_SAMPLES), seed=int(cfg.MODEL.SAMPLE_SEED),
+                             n_replicates=int(cfg.MODEL.N_REPLICATES))
         print(f"Finish predicting {len(dataloader)} spectra in {time.time() - ts} seconds...")
     return 0
 

@@ -47,6 +47,9 @@ DEFAULTS = {                                        # reference QFA/config.py:15
               # not in the reference: predict mode adds N_SAMPLES continua drawn from the posterior to every file
               # (cont_samples, (N_SAMPLES, Npix)); SAMPLE_SEED seeds the counter-based generator (include/qfa_hip.h)
               "N_SAMPLES": 0, "SAMPLE_SEED": 0,
+              # not in the reference: predict mode adds N_REPLICATES posterior-predictive replicates of every spectrum under its
+              # own noise and mask to every file (flux_replicates, (N_REPLICATES, Npix)); same SAMPLE_SEED
+              "N_REPLICATES": 0,
               # not in the reference: train with the exact gradient of the mean NLL instead of the reference's formulas
               # (QFA.exact_gradients, include/qfa_hip.h QFA_F_EXACT_GRAD); off = the reference's update
               "EXACT_GRADIENTS": False},
@@ -69,7 +72,7 @@ ARG_KEYS = {
 }
 # keys of DEFAULTS the reference does not have (tests/test_cli_config.py pins everything else against
 # tests/golden/g12_config.json, extracted from the reference's config.py / main.py)
-EXTRA_KEYS = ("MODEL.REFERENCE_C0_QUIRK", "MODEL.N_SAMPLES", "MODEL.SAMPLE_SEED", "MODEL.EXACT_GRADIENTS",
+EXTRA_KEYS = ("MODEL.REFERENCE_C0_QUIRK", "MODEL.N_SAMPLES", "MODEL.SAMPLE_SEED", "MODEL.N_REPLICATES", "MODEL.EXACT_GRADIENTS",
               "TRAIN.F_UPDATE", "TRAIN.EM_RHO", "TRAIN.EM_RIDGE")
 
 

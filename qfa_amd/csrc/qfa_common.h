@@ -206,12 +206,15 @@ __device__ __forceinline__ const unsigned char *lane_ptr(const void *sbase, unsi
 }
 
 // ZS[s] from zq1[row of s] = 1 + z_qso;  ZP[i] from pix_ratio[i] = wav_i / 1215.67 (blue pixels)
+__device__ __forceinline__ float4 zfac_spec(float zq1, float beta, const qfa_tau_t &tau) {
+    const double l2s = log2((double)zq1);
+    const double ts = -1.4426950408889634 * (double)tau.amp * exp2((double)tau.expo * (l2s + log2((double)tau.scale)));
+    return float4{(float)ts, (float)exp2((double)beta * l2s), (float)l2s, 0.f};
+}
 __device__ __forceinline__ void zfac_spec_body(int s, const float *__restrict__ zq1, const int *__restrict__ rows,
                                                const qfa_params_t &p, const qfa_tau_t &tau, int B, float4 *__restrict__ ZS) {
     if (s >= B) return;
-    const double l2s = log2((double)zq1[rows ? rows[s] : s]);
-    const double ts = -1.4426950408889634 * (double)tau.amp * exp2((double)tau.expo * (l2s + log2((double)tau.scale)));
-    ZS[s] = float4{(float)ts, (float)exp2((double)*p.beta * l2s), (float)l2s, 0.f};
+    ZS[s] = zfac_spec(zq1[rows ? rows[s] : s], *p.beta, tau);
 }
 static __global__ void k_zfac_spec(const float *__restrict__ zq1, const int *__restrict__ rows, qfa_params_t p, qfa_tau_t tau,
                                    int B, float4 *__restrict__ ZS) {

@@ -1,16 +1,19 @@
-// qfa_sample.h -- posterior draws: latent vectors h ~ N(hmean, hcov) and continua mu + F h (include/qfa_hip.h,
-// qfa_sample_latent_f32 / qfa_continua_f32).  Built in qfa_sample.hip.
+// qfa_sample.h -- draws from the model: latent vectors h ~ N(hmean, hcov), continua mu + F h and mock spectra (include/qfa_hip.h,
+// qfa_sample_latent_f32 / qfa_continua_f32 / qfa_mock_spectra_f32).  Built in qfa_sample.hip.
 //
 //   k_sample_image   F (Npix, Nh) row-major -> image (Nh + 1, pad): row j = F[:, j], row Nh = mu  (coalesced per-lane loads)
 //   k_sample_latent  one wave per (spectrum, chunk of samples): float64 Cholesky of hcov in LDS, Philox4x32-10 + Box-Muller
 //                    in registers, h = hmean + C z in float64, rounded once
 //   k_sample_cont    the writer: a lane owns one pixel (its Nh + 1 image values in registers) and walks a run of latent rows;
 //                    the row's h is wave-uniform (scalar loads), one fmaf chain per output, one dword store per lane
+//   k_mock_image, k_mock_spectra   the spectrum writer, described above its kernels at the end of this file
 //
 // The draw contract (what every port must reproduce) is spelled out in include/qfa_hip.h above qfa_sample_latent_f32.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "qfa_common.h"
 
 namespace qfa_sample {
 
@@ -165,6 +168,167 @@ __global__ __launch_bounds__(kWriterThreads) void k_sample_cont(const float *__r
         if (live) *o = acc;
         o += Npix;
         hr += NH;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Mock spectra (include/qfa_hip.h, qfa_mock_spectra_f32):  flux = A c + sqrt(D) e,  c = mu + F h,  D = A^2 Psi + omega zd + sigma^2.
+//
+//   k_mock_image    the image of k_sample_image with two more rows: row j < Nh = F[:, j], Nh = mu, Nh + 1 = Psi, Nh + 2 = omega
+//                   (0 on the red side), rows padded to kMockStrip pixels
+//   k_mock_spectra  a lane owns FOUR consecutive pixels -- one Philox call -- and keeps their Nh + 3 image values in registers; a
+//                   block owns a strip of kMockStrip pixels and walks a run of spectra b, the S replicates of a spectrum
+//                   innermost: A, sqrt(D), mu A and the mask of (b, p) are formed once and serve all S replicates; the latent
+//                   row h[b, s, :] is wave-uniform.  No LDS, no block-level synchronisation: a wave without a pixel leaves.
+//
+// What binds it: per four pixels two float64 Box-Muller pairs (2 log, 2 sqrt, 2 sin, 2 cos) and ten Philox rounds against 16
+// or 32 bytes stored -- the float64 VALU, not HBM: 2.05e11 normals/s (0.82 TB/s of flux) at 4 096 x 1 913, S = 100, where
+// k_sample_cont writes the same bytes 3.9 times faster (profiles/mock_bench.jsonl).
+// ------------------------------------------------------------------------------------------------
+constexpr int kMockThreads = 256;
+constexpr int kMockStrip = 4 * kMockThreads;
+enum { kMockZabs = 0, kMockFactored = 1, kMockABlue = 2 };       // how the blue side's A and zd are formed
+
+__global__ void k_mock_image(const float *__restrict__ F, const float *__restrict__ mu, const float *__restrict__ Psi,
+                             const float *__restrict__ omega, int Npix, int Nb, int Nh, int pad, float *__restrict__ img) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (int64_t)(Nh + 3) * pad) return;
+    const int j = (int)(i / pad), p = (int)(i % pad);
+    float v = 0.f;
+    if (p < Npix) {
+        if (j < Nh) v = F[(int64_t)p * Nh + j];
+        else if (j == Nh) v = mu[p];
+        else if (j == Nh + 1) v = Psi[p];
+        else if (p < Nb) v = omega[p];
+    }
+    img[i] = v;
+}
+
+// four values of pixels p0 .. p0 + 3 of a row (`n` of them exist); `vec`: the row's p0 is 16-byte aligned
+__device__ __forceinline__ void mock_load4(const float *__restrict__ src, int n, bool vec, float fill, float v[4]) {
+    if (vec && n == 4) {
+        const float4 q = *reinterpret_cast<const float4 *>(src);
+        v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[k] = k < n ? src[k] : fill;
+    }
+}
+__device__ __forceinline__ void mock_store4(float *__restrict__ dst, int n, bool vec, const float v[4]) {
+    if (vec && n == 4) {
+        *reinterpret_cast<float4 *>(dst) = float4{v[0], v[1], v[2], v[3]};
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (k < n) dst[k] = v[k];
+    }
+}
+
+// grid (strips * chunks), block x = chunk * strips + strip as in k_sample_cont.  NHM >= Nh (8, 16 or 32): the columns
+// [Nh, NHM) of the image registers and of the latent row are zeros, which leave the fma chain's value as it is.
+template <int NHM>
+__global__ __launch_bounds__(kMockThreads) void k_mock_spectra(qfa_params_t p, qfa_batch_t bt, qfa_tau_t tau, int mode,
+                                                               const float *__restrict__ img, int pad,
+                                                               const float4 *__restrict__ ZP, const float *__restrict__ h, int B,
+                                                               int S, int Npix, int Nb, int Nh, int strips, int rows_per_block,
+                                                               uint32_t k0, uint32_t k1, int64_t row0,
+                                                               float *__restrict__ flux, float *__restrict__ delta) {
+    const int strip = blockIdx.x % strips;
+    const int chunk = blockIdx.x / strips;
+    const int lane = threadIdx.x & 63;
+    if (strip * kMockStrip + 4 * (int)(threadIdx.x & ~63u) >= Npix) return;      // a wave with no pixel of the row
+    const int p0 = strip * kMockStrip + 4 * (int)threadIdx.x;
+    const int n = min(4, max(0, Npix - p0));                                     // pixels of this lane that exist
+    const int nblue = min(4, max(0, Nb - p0));
+    const int b0 = chunk * rows_per_block, b1 = min(B, b0 + rows_per_block);
+    const DevConsts kc = load_consts(p, tau);
+
+    float f[NHM][4], m[4], Psi[4], om[4];
+#pragma unroll
+    for (int j = 0; j < NHM; ++j) {
+        float4 q = {0.f, 0.f, 0.f, 0.f};
+        if (j < Nh) q = *reinterpret_cast<const float4 *>(img + (int64_t)j * pad + p0);      // p0 + 3 < pad, 16-byte aligned
+        f[j][0] = q.x; f[j][1] = q.y; f[j][2] = q.z; f[j][3] = q.w;
+    }
+    {
+        const float4 a = *reinterpret_cast<const float4 *>(img + (int64_t)Nh * pad + p0);
+        const float4 b = *reinterpret_cast<const float4 *>(img + (int64_t)(Nh + 1) * pad + p0);
+        const float4 c = *reinterpret_cast<const float4 *>(img + (int64_t)(Nh + 2) * pad + p0);
+        m[0] = a.x; m[1] = a.y; m[2] = a.z; m[3] = a.w;
+        Psi[0] = b.x; Psi[1] = b.y; Psi[2] = b.z; Psi[3] = b.w;
+        om[0] = c.x; om[1] = c.y; om[2] = c.z; om[3] = c.w;
+    }
+    float4 zp[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) zp[k] = (mode == kMockFactored && k < nblue) ? ZP[p0 + k] : float4{0.f, 0.f, 0.f, 0.f};
+    const uint32_t q = 0x80000000u | (uint32_t)(p0 >> 2);
+    // does the WAVE hold a blue pixel?  Every lane of such a wave forms factors, also one whose own pixels are red or past the row
+    const bool wave_blue = strip * kMockStrip + 4 * (int)(threadIdx.x & ~63u) < Nb;
+
+    // 64 spectra at a time: lane l forms the per-spectrum factors of spectrum g0 + l (factored-z form: k_zfac_spec's float64
+    // arithmetic, once per spectrum and wave), every lane then reads spectrum i's from lane i
+    for (int g0 = b0; g0 < b1; g0 += 64) {
+        float4 zmine = {0.f, 0.f, 0.f, 0.f};
+        if (mode == kMockFactored && wave_blue && g0 + lane < b1)                 // (wave-uniform but for the last term)
+            zmine = zfac_spec(bt.zq1[bt.rows ? bt.rows[g0 + lane] : g0 + lane], kc.beta, tau);
+        const int g1 = min(b1, g0 + 64);
+        for (int b = g0; b < g1; ++b) {
+            const ZFac zs{__shfl(zmine.x, b - g0), __shfl(zmine.y, b - g0), __shfl(zmine.z, b - g0)};
+            const unsigned long long row = batch_row(bt, b);
+            const float *er = bt.error + row * (unsigned long long)bt.row_stride + (unsigned)p0;
+            float sg[4];
+            mock_load4(er, n, (reinterpret_cast<uintptr_t>(er) & 15) == 0, 0.f, sg);
+            bool use[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) use[k] = k < n;
+            if (bt.mask) {
+                const uint8_t *mr = bt.mask + row * (unsigned long long)bt.row_stride + (unsigned)p0;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) use[k] = k < n && mr[k] != 0;
+            }
+            float A[4], sd[4], mA[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                float Ak = 1.f, zd = 0.f;
+                if (k < nblue) {
+                    BlueTerms bl;
+                    if (mode == kMockFactored) {
+                        bl = blue_terms_zf(zs, zp[k].x, zp[k].y, zp[k].z, kc);
+                    } else {
+                        bl = blue_terms(bt.zabs[row * (unsigned long long)Nb + (unsigned)(p0 + k)], kc);
+                        if (mode == kMockABlue) bl.A = bt.A_blue[(size_t)b * Nb + (p0 + k)];
+                    }
+                    Ak = bl.A;
+                    zd = bl.zd;
+                }
+                const float D = Ak * Ak * Psi[k] + om[k] * zd + sg[k] * sg[k];
+                A[k] = Ak;
+                sd[k] = use[k] ? sqrtf(D) : 0.f;             // a select: NaN / inf / -999 under the mask never reach an output
+                mA[k] = __fmul_rn(m[k], Ak);
+            }
+            const uint64_t r = (uint64_t)(row0 + b);
+            const float *hr = h + (int64_t)b * S * Nh;
+            int64_t o = (int64_t)b * S * Npix + p0;
+            for (int s = 0; s < S; ++s, hr += Nh, o += Npix) {
+                float e[4], c[4] = {m[0], m[1], m[2], m[3]};
+                normals4(q, (uint32_t)s, r, k0, k1, e);
+#pragma unroll
+                for (int j = 0; j < NHM; ++j) {
+                    const float hv = j < Nh ? hr[j] : 0.f;            // wave-uniform
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) c[k] = fmaf(f[j][k], hv, c[k]);
+                }
+                float fl[4], dl[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const float v = fmaf(sd[k], e[k], __fmul_rn(A[k], c[k]));
+                    fl[k] = use[k] ? v : -999.0f;
+                    dl[k] = use[k] ? __fsub_rn(v, mA[k]) : -999.0f;
+                }
+                if (flux) mock_store4(flux + o, n, (reinterpret_cast<uintptr_t>(flux + o) & 15) == 0, fl);
+                if (delta) mock_store4(delta + o, n, (reinterpret_cast<uintptr_t>(delta + o) & 15) == 0, dl);
+            }
+        }
     }
 }
 

@@ -8,6 +8,7 @@ here falls back to torch arithmetic when the library or the GPU is missing.
 Additions over the reference (none changes a reference call's result):
   * ``predict`` -- batched ``prediction_for_single_spectra``;
   * ``sample_latent`` / ``continua_from_latent`` / ``sample_continua`` -- posterior draws on the device (include/qfa_hip.h);
+  * ``sample_spectra`` / ``posterior_predictive`` -- mock spectra and posterior-predictive replicates drawn from the model;
   * ``step`` -- forward + Adam + clip without a host sync (what ``train`` and bench.py run);
   * data parallelism: ``enable_data_parallel()`` all-reduces the packed sum/count buffer over
     RCCL once per step before the normalisation (SURVEY.md 8(e));
@@ -215,7 +216,7 @@ class QFA(object):
             setattr(ps, k, _lib.require_device_tensor(t, f32, k).value)
         return ps
 
-    def _batch_struct(self, delta, error, zabs, mask, zfac=None):
+    def _batch_struct(self, delta, error, zabs, mask, zfac=None, allow_no_mask=False):
         """``zfac`` = (zq1 (B,), pix_ratio (Nb,)) float32 device tensors: the factored-z input form of include/qfa_hip.h
         (1 + zabs[s][i] = zq1[s] pix_ratio[i], reference QFA/dataloader.py:102).  Default: the ``zfac`` attribute a
         DeviceDataloader attaches to the zabs tensors it builds; None = the kernels read zabs."""
@@ -224,19 +225,22 @@ class QFA(object):
         if (zfac is None and zabs is not None and self.auto_factor_zabs and self.use_factored_z and self.Nb > 0
                 and self._tau_callable is None):
             zfac = self._auto_zfac(zabs)
-        if mask.dtype != torch.bool:
+        if mask is None and not allow_no_mask:
+            raise _lib.QFAHipError("mask is None: expected a torch.bool tensor (reference model.py:124)")
+        if mask is not None and mask.dtype != torch.bool:            # (None: sample_spectra only -- every pixel is used)
             raise _lib.QFAHipError(f"mask: dtype {mask.dtype}, expected torch.bool (reference model.py:124)")
         bs = _lib.Batch()
         delta = delta if (delta.dtype == f32 and delta.is_contiguous()) else delta.to(f32).contiguous()
         error = error if (error.dtype == f32 and error.is_contiguous()) else error.to(f32).contiguous()
         if zabs is not None:
             zabs = zabs if (zabs.dtype == f32 and zabs.is_contiguous()) else zabs.to(f32).contiguous()
-        mask = mask if mask.is_contiguous() else mask.contiguous()
+        if mask is not None:
+            mask = mask if mask.is_contiguous() else mask.contiguous()
         keep = [delta, error, zabs, mask]
         bs.delta = _lib.require_device_tensor(delta, f32, "delta").value
         bs.error = _lib.require_device_tensor(error, f32, "error").value
         bs.zabs = _lib.require_device_tensor(zabs, f32, "zabs").value if (self.Nb > 0 and zabs is not None) else None
-        bs.mask = _lib.require_device_tensor(mask, torch.bool, "mask").value
+        bs.mask = _lib.require_device_tensor(mask, torch.bool, "mask").value if mask is not None else None
         bs.A_blue = None
         bs.zq1 = None
         bs.pix_ratio = None
@@ -299,7 +303,7 @@ class QFA(object):
         self._zf_seen[id(zabs)] = ent
         return ent[2]
 
-    def _batch_struct_rows(self, rb, raw_flux=False):
+    def _batch_struct_rows(self, rb, raw_flux=False, need_src=True):
         """qfa_batch_t of a ``ResidentBatch`` (qfa_amd/resident.py; ABI v3 rows / row_stride): pointers to the WHOLE resident
         arrays plus the device array of row numbers -- no gather, no copy.  ``raw_flux``: the predict call (delta = raw flux)."""
         if self._tau_callable is not None:
@@ -307,6 +311,8 @@ class QFA(object):
         if rb.Npix != self.Npix or rb.Nb != self.Nb:
             raise _lib.QFAHipError(f"resident batch of shape (.., {rb.Npix}), Nb = {rb.Nb}; the model has ({self.Npix}, {self.Nb})")
         src = rb.flux if raw_flux else rb.delta
+        if not need_src:                                        # (sample_spectra: the call reads neither flux nor delta)
+            src = rb.error
         if src is None:
             raise _lib.QFAHipError("resident batch without " + ("flux" if raw_flux else "delta"))
         N, stride = int(rb.error.shape[0]), int(rb.stride)
@@ -616,12 +622,90 @@ class QFA(object):
         cont = self.continua_from_latent(h, out=out)
         return (cont, h) if return_latent else cont
 
-    def predict_to_npz(self, dataloader, output_dir, batch_size=4096, n_samples=0, seed=0):
+    # ------------------------------------------------------------------ mock spectra
+    def sample_spectra(self, error=None, zabs=None, mask=None, *, n_samples=1, seed=0, offset=0, h=None, hmean=None, hcov=None,
+                       zfac=None, batch=None, out=None, return_delta=False, return_latent=False):
+        """``n_samples`` spectra per row drawn from the model, flux = A (mu + F h) + sqrt(D) e under the row's own ``error`` and
+        ``mask``: (B, S, Npix) float32, masked pixels -999 (qfa_mock_spectra_f32; the draw contract is in include/qfa_hip.h).
+        The latent: ``h`` (B, S, Nh) as it is (``n_samples`` may then stay at its default); else ``hmean`` / ``hcov`` through ``sample_latent`` (a posterior-predictive
+        replicate when they come from ``predict``); else the prior (zeros / identity through ``sample_latent``): mock data.
+        ``offset`` is the global row of spectrum 0: a spectrum's draws depend only on (seed, its global row).  ``mask`` None:
+        every pixel is used.  ``batch``: a ``ResidentBatch`` in the place of error / zabs / mask.  ``out``: the (B, S, Npix)
+        tensor to fill.  ``return_delta`` adds delta = flux - mu A, ``return_latent`` adds h, in that order behind the flux.
+        Bit-identical to calling ``sample_latent`` and the C entry point by hand."""
+        if self.mu is None:
+            raise _lib.QFAHipError("sample_spectra needs model.mu (load_from_npz or train first)")
+        S = int(n_samples)
+        if S < 1:
+            raise _lib.QFAHipError(f"sample_spectra: n_samples = {n_samples}, expected >= 1")
+        if int(offset) < 0:
+            raise _lib.QFAHipError(f"sample_spectra: offset = {offset}, expected >= 0")
+        if not 0 <= int(seed) < 2 ** 64:
+            raise _lib.QFAHipError(f"sample_spectra: seed = {seed}, expected a uint64")
+        if (hmean is None) != (hcov is None):
+            raise _lib.QFAHipError("sample_spectra: pass hmean and hcov together")
+        if h is not None and hmean is not None:
+            raise _lib.QFAHipError("sample_spectra: pass h or hmean / hcov, not both")
+        ps = self._params_struct()
+        if batch is not None:
+            B = batch.B
+            bs, keep = self._batch_struct_rows(batch, need_src=False)
+        else:
+            if not isinstance(error, torch.Tensor) or error.dim() != 2:
+                raise _lib.QFAHipError("sample_spectra: error must be a (B, Npix) tensor")
+            B = self._check_batch_shapes(error, error, zabs, mask if mask is not None else error)
+            bs, keep = self._batch_struct(error, error, zabs, mask, zfac, allow_no_mask=True)
+        bs.delta = None                                         # (not read by the call)
+        dev = self.device
+        if h is None:
+            if hmean is None:
+                hmean = torch.zeros((B, self.Nh), dtype=f32, device=dev)
+                hcov = torch.eye(self.Nh, dtype=f32, device=dev).repeat(B, 1, 1)
+            elif hmean.dim() != 2 or hmean.shape[0] != B:
+                raise _lib.QFAHipError(f"hmean: shape {tuple(hmean.shape)}, expected ({B}, {self.Nh})")
+            h = self.sample_latent(hmean, hcov, S, seed=seed, offset=offset)
+        else:
+            if h.dim() == 3 and S == 1:                         # (n_samples left at its default: h says how many)
+                S = int(h.shape[1])
+            if tuple(h.shape) != (B, S, self.Nh) or S < 1:
+                raise _lib.QFAHipError(f"h: shape {tuple(h.shape)}, expected {(B, S, self.Nh)}")
+        ph = _lib.require_device_tensor(h, f32, "h")
+        if out is None:
+            out = torch.empty((B, S, self.Npix), dtype=f32, device=dev)
+        elif tuple(out.shape) != (B, S, self.Npix):
+            raise _lib.QFAHipError(f"sample_spectra(out=...): expected shape {(B, S, self.Npix)}, got {tuple(out.shape)}")
+        po = _lib.require_device_tensor(out, f32, "out")
+        delta = torch.empty((B, S, self.Npix), dtype=f32, device=dev) if return_delta else None
+        mu = self.mu.to(device=dev, dtype=f32).contiguous()
+        need = _lib.lib().qfa_mock_workspace_bytes(self.Npix, self.Nh)
+        ws = self._ws.get("mock_ws")
+        if ws is None or ws.numel() < need:
+            ws = torch.empty(need, dtype=torch.uint8, device=dev)
+            self._ws["mock_ws"] = ws
+        _lib.check(_lib.lib().qfa_mock_spectra_f32(
+            C.byref(ps), C.c_void_p(mu.data_ptr()), C.byref(bs), C.byref(self._tau_model), ph, B, S, self.Npix, self.Nb, self.Nh,
+            C.c_uint64(int(seed)), int(offset), po, C.c_void_p(delta.data_ptr()) if delta is not None else None,
+            C.c_void_p(ws.data_ptr()), ws.numel(), _lib.current_stream(dev)), "qfa_mock_spectra_f32")
+        res = (out,) + ((delta,) if return_delta else ()) + ((h,) if return_latent else ())
+        return res if len(res) > 1 else out
+
+    def posterior_predictive(self, flux=None, error=None, zabs=None, mask=None, n_samples=1, seed=0, offset=0, *, zfac=None,
+                             batch=None):
+        """``n_samples`` replicates of every observed spectrum under its own posterior, noise and mask: (B, S, Npix) float32.
+        ``predict`` on the inputs, then ``sample_spectra`` with the posterior's hmean / hcov and the observed error and mask --
+        what a posterior-predictive check compares with the data."""
+        _, hmean, hcov, _, _ = self.predict(flux, error, zabs, mask, zfac=zfac, batch=batch)
+        return self.sample_spectra(error, zabs, mask, n_samples=n_samples, seed=seed, offset=offset, hmean=hmean, hcov=hcov,
+                                   zfac=zfac, batch=batch)
+
+    def predict_to_npz(self, dataloader, output_dir, batch_size=4096, n_samples=0, seed=0, n_replicates=0):
         """The predict mode of the reference's main.py:87-98 for a whole dataloader: one
         ``<basename>`` .npz per spectrum with keys ll, hmean, hcov, cont, uncertainty and the
         reference's shapes ((1,1), (Nh,1), (Nh,Nh), (Npix,), (Npix,)); the posterior runs batched.
         ``n_samples`` > 0 adds ``cont_samples`` (S, Npix): continua drawn from the posterior with ``seed``, the global row of a
-        spectrum being its dataloader index (so the files do not depend on ``batch_size``)."""
+        spectrum being its dataloader index (so the files do not depend on ``batch_size``).  ``n_replicates`` > 0 adds
+        ``flux_replicates`` (K, Npix): posterior-predictive replicates of the spectrum under its own error and mask
+        (``sample_spectra``), same ``seed`` and global row."""
         os.makedirs(output_dir, exist_ok=True)
         n = len(dataloader)
         written = []
@@ -631,23 +715,32 @@ class QFA(object):
             if hasattr(dataloader, "rows_batch") and self._tau_callable is None and (self.use_factored_z or self.Nb == 0):
                 rb, paths = dataloader.rows_batch(s, min(s + batch_size, n))
                 res = self.predict(batch=rb)
+                inputs = {"batch": rb}
             elif hasattr(dataloader, "get_rows"):                # one launch for the whole slice
                 f, e, z, m, paths = dataloader.get_rows(s, min(s + batch_size, n))
                 res = self.predict(f, e, z, m)
+                inputs = {"error": e, "zabs": z, "mask": m}
             else:                                                # the reference's per-spectrum contract
                 items = [dataloader[i] for i in range(s, min(s + batch_size, n))]
                 f, e, z, m = (torch.stack([it[j] for it in items]) for j in range(4))
                 paths = [it[4] for it in items]
                 res = self.predict(f, e, z, m)
+                inputs = {"error": e, "zabs": z, "mask": m}
             samples = None
             if n_samples > 0:
                 samples = self.sample_continua(n_samples=n_samples, seed=seed, offset=s, hmean=res[1], hcov=res[2]).cpu().numpy()
+            replicates = None
+            if n_replicates > 0:
+                replicates = self.sample_spectra(n_samples=n_replicates, seed=seed, offset=s, hmean=res[1], hcov=res[2],
+                                                 **inputs).cpu().numpy()
             ll, hmean, hcov, cont, unc = (x.cpu().numpy() for x in res)
             for r, path in enumerate(paths):
                 name = os.path.basename(str(path))
                 if not name.endswith(".npz"):
                     name += ".npz"
                 extra = {} if samples is None else {"cont_samples": samples[r]}
+                if replicates is not None:
+                    extra["flux_replicates"] = replicates[r]
                 np.savez(os.path.join(output_dir, name), ll=ll[r].reshape(1, 1), hmean=hmean[r].reshape(self.Nh, 1),
                          hcov=hcov[r], cont=cont[r], uncertainty=unc[r], **extra)
                 written.append(name)
