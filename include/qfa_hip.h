@@ -324,6 +324,54 @@ int qfa_em_stats_f32(const qfa_params_t *p, const qfa_batch_t *b, const qfa_tau_
 int qfa_em_update_f_f32(const float *stats, const float *F, int Npix, int Nh, double ridge, double damping, float *F_out,
                         unsigned *n_skipped, void *stream);
 
+/* Lyman-alpha forest transmission and its redshift-binned stack (additive to ABI v4).  The reference presents QFA as a continuum
+ * predictor FOR the forest (README.md, the paper's abstract): its users divide the observed flux by the continuum on the blue side,
+ * T = flux / continuum, and stack T in redshift bins for the mean transmission and tau_eff(z) = -ln <T>; the reference itself stops
+ * at the continuum (QFA/model.py:160-180).  This call forms T and its inverse variance for every draw of the latent and adds the
+ * weighted sums of the stack, without ever writing a continuum.
+ *
+ * The contract.  For spectrum b of a call (row r = rows ? rows[b] : b of the input arrays), draw s (0 <= s < S) and blue pixel
+ * p (0 <= p < Nb):
+ *   inputs     b->delta holds the RAW FLUX (as for qfa_predict_f32), b->error the pipeline error sigma, b->mask may be NULL (every
+ *              pixel is used); redshift from b->zabs, or from the factored zq1 + pix_ratio form; rows / row_stride: the resident
+ *              form.  A_blue is ignored; the call uses neither a tau model nor Psi, omega, tau0, beta, c0.
+ *              h (B, S, Nh) float32 in batch order: hmean with S = 1 (the posterior-mean continuum) or qfa_sample_latent_f32's draws.
+ *              unc (B, Npix) in batch order as qfa_predict_f32 writes it, or NULL: the continuum's 1 sigma, meant for S = 1;
+ *   redshift   z = zabs[r, p], or in the factored form z = fma(zq1[r], pix_ratio[p], -1) (one rounding);
+ *   continuum  c = mu[p] + sum_j F[p,j] h[b,s,j], the float32 fma chain of qfa_continua_f32 in order of j;
+ *   values     every operation rounded once, no contraction:  T = flux / c;  den = (T T) u2 + sigma sigma with u2 = unc unc or 0
+ *              (a product, a product and an add);  iv = (c c) / den;
+ *   use        mask != 0 && c > cont_min && isfinite(T) && isfinite(iv) (a NaN c fails the comparison).  What flux or error hold
+ *              under the mask (-999, NaN, inf) reaches no output: selects, not products;
+ *   outputs    trans, ivar (B, S, Nb) float32 in batch order, contiguous at any 4-byte alignment, 64-bit indices; either or both
+ *              may be NULL.  An unused pixel gets exactly 0.0f in both;
+ *   stack      (S, 4, nbin) float64 = [sum w | sum w T | sum w T^2 | n] per draw, or NULL (but not all three outputs NULL);
+ *              w = (double)iv, or 1 with QFA_F_FOREST_UNIT_W; the terms are w, w T and w (T T) in float64, each product rounded
+ *              once.  The sums run over the used pixels with p_lo <= p < p_hi whose bin k = floorf((z - z0) inv_dz) satisfies
+ *              0 <= k < nbin: inv_dz = 1.0f / dz is formed once on the host in float32, the subtraction and the product are each
+ *              rounded once, and the range test is done on the float (a NaN z is not stacked).  The call ADDS to `stack`;
+ *              QFA_F_ZERO_ACCUM overwrites instead;
+ *   sums       sums only -- the buffer a data-parallel job all-reduces.  No float atomics anywhere: every wave adds its pixels to a
+ *              table of its own in a fixed order, the tables leave through rows of the workspace and a fixed-order reducer adds
+ *              the rows to `stack`: two calls on the same inputs give the same bits.  z need not be monotone in p (it is for the
+ *              reference's loader, which is the fast case: a wave's 256 pixels then fall into a few consecutive bins).
+ * qfa_forest_stack_doubles: S 4 nbin, 0 = unsupported (S < 1, nbin outside 1..4096).  qfa_forest_workspace_bytes: the scratch (an
+ * image of F and mu on the blue side and the rows of partial sums); 0 = unsupported shape.
+ * Returns QFA_E_NULL for a missing required pointer; QFA_E_SIZE for B < 0, S < 1, Npix < 1, Nb outside 0..Npix, Nh outside 1..32,
+ * bad bins (dz <= 0 or not finite, z0 not finite, nbin outside 1..4096, not 0 <= p_lo <= p_hi <= Nb) or 0 < row_stride < Npix;
+ * QFA_E_FLAGS for any flag other than QFA_F_ZERO_ACCUM, QFA_F_SYNC, QFA_F_FOREST_UNIT_W; QFA_E_WORKSPACE.  B = 0 or Nb = 0 does
+ * nothing to trans / ivar and, under QFA_F_ZERO_ACCUM, still zeroes `stack`.  Argument checks return before any device work.  The
+ * call neither synchronises nor allocates (graph-capturable). */
+typedef struct { float z0, dz; int nbin; int p_lo, p_hi; } qfa_forest_bins_t;   /* dz > 0, 1 <= nbin <= 4096, 0 <= p_lo <= p_hi <= Nb */
+#define QFA_F_FOREST_UNIT_W 0x200u   /* qfa_forest_f32: stack with w = 1 instead of w = ivar */
+
+size_t qfa_forest_stack_doubles(int S, int nbin);
+size_t qfa_forest_workspace_bytes(int B, int S, int Npix, int Nb, int Nh, int nbin);
+int qfa_forest_f32(const float *F, const float *mu, const qfa_batch_t *b, const float *h, const float *unc,
+                   int B, int S, int Npix, int Nb, int Nh, const qfa_forest_bins_t *bins, float cont_min,
+                   unsigned flags, float *trans, float *ivar, double *stack,
+                   void *workspace, size_t workspace_bytes, void *stream);
+
 /* Replaces Adam.update (reference QFA/optimizer.py:37-52) followed by the clamp of QFA.clip
  * (QFA/model.py:233-241) for ONE tensor of n elements:
  *   g' = g + wd*p; m = (1-b1) g' + b1 m; v = (1-b2) g'^2 + b2 v;

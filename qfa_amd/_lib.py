@@ -21,6 +21,7 @@ EXPORTS = (
     "qfa_sample_latent_f32", "qfa_continua_workspace_bytes", "qfa_continua_f32",
     "qfa_mock_workspace_bytes", "qfa_mock_spectra_f32",
     "qfa_em_floats", "qfa_em_workspace_bytes", "qfa_em_stats_f32", "qfa_em_update_f_f32",
+    "qfa_forest_stack_doubles", "qfa_forest_workspace_bytes", "qfa_forest_f32",
 )
 
 TAU_IDS = {"becker": 0, "fg": 1, "kamble": 2, "mock": 3}
@@ -29,6 +30,7 @@ ABI_VERSION = 4
 F_PASS2_F32, F_PASS2_XDL, F_S3_FAST, F_PREDICT_F32, F_SYNC = 0x1, 0x2, 0x4, 0x8, 0x20
 F_PASS2_PIXRES = 0x40
 F_ZERO_ACCUM = 0x80
+F_FOREST_UNIT_W = 0x200    # qfa_forest_f32: stack with w = 1 instead of w = ivar
 F_EXACT_GRAD = 0x100       # exact gradients of mean NLL (opt-in; QFA.exact_gradients); the buffer carries the mode in slot 6
 
 
@@ -57,6 +59,10 @@ class Batch(C.Structure):
     # qfa_batch_t (ABI v3: rows / row_stride = the resident, indexed input form)
     _fields_ = [(n, C.c_void_p) for n in ("delta", "error", "zabs", "mask", "A_blue", "zq1", "pix_ratio", "rows")] + \
                [("row_stride", C.c_int64)]
+
+
+class ForestBins(C.Structure):      # qfa_forest_bins_t
+    _fields_ = [("z0", C.c_float), ("dz", C.c_float), ("nbin", C.c_int), ("p_lo", C.c_int), ("p_hi", C.c_int)]
 
 
 _lib = None
@@ -121,6 +127,9 @@ def lib():
         "qfa_em_workspace_bytes": (sz, [i, i, i]),
         "qfa_em_stats_f32": (i, [C.POINTER(Params), C.POINTER(Batch), C.POINTER(TauModel), i, i, i, i, p, p, p, sz, C.c_uint, p]),
         "qfa_em_update_f_f32": (i, [p, p, i, i, d, d, p, p, p]),
+        "qfa_forest_stack_doubles": (sz, [i, i]),
+        "qfa_forest_workspace_bytes": (sz, [i, i, i, i, i, i]),
+        "qfa_forest_f32": (i, [p, p, C.POINTER(Batch), p, p, i, i, i, i, i, C.POINTER(ForestBins), f, C.c_uint, p, p, p, p, sz, p]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(h, name, None)

@@ -129,7 +129,15 @@ def main(argv=None):
         ts = time.time()
         model.predict_to_npz(dataloader, os.path.join(cfg.DATA.OUTPUT_DIR, "predict"),
                              n_samples=int(cfg.MODEL.N_SAMPLES), seed=int(cfg.MODEL.SAMPLE_SEED),
-                             n_replicates=int(cfg.MODEL.N_REPLICATES))
+                             n_replicates=int(cfg.MODEL.N_REPLICATES), forest=bool(cfg.MODEL.FOREST))
+        if int(cfg.MODEL.FOREST_NBINS) > 0:
+            import numpy as np
+            st = model.mean_transmission(dataloader, float(cfg.MODEL.FOREST_ZMIN), float(cfg.MODEL.FOREST_ZMAX),
+                                         int(cfg.MODEL.FOREST_NBINS), n_samples=int(cfg.MODEL.N_SAMPLES),
+                                         seed=int(cfg.MODEL.SAMPLE_SEED))
+            np.savez(os.path.join(cfg.DATA.OUTPUT_DIR, "mean_transmission.npz"), z_centers=st.z_centers.cpu().numpy(),
+                     z_edges=st.z_edges.cpu().numpy(), mean=st.mean.cpu().numpy(), var=st.var.cpu().numpy(), n=st.n.cpu().numpy(),
+                     tau_eff=st.tau_eff.cpu().numpy(), sums=st.buf.cpu().numpy())
         print(f"Finish predicting {len(dataloader)} spectra in {time.time() - ts} seconds...")
     return 0
 

@@ -52,7 +52,12 @@ DEFAULTS = {                                        # reference QFA/config.py:15
               "N_REPLICATES": 0,
               # not in the reference: train with the exact gradient of the mean NLL instead of the reference's formulas
               # (QFA.exact_gradients, include/qfa_hip.h QFA_F_EXACT_GRAD); off = the reference's update
-              "EXACT_GRADIENTS": False},
+              "EXACT_GRADIENTS": False,
+              # not in the reference: predict mode adds the forest transmission flux / continuum of the blue side and its inverse
+              # variance to every file (transmission, transmission_ivar, (Nb,)); FOREST_NBINS > 0 also writes
+              # mean_transmission.npz, the stack in FOREST_NBINS bins of [FOREST_ZMIN, FOREST_ZMAX), repeated over N_SAMPLES
+              # posterior draws when that is set (QFA.forest / mean_transmission)
+              "FOREST": False, "FOREST_ZMIN": 0.0, "FOREST_ZMAX": 0.0, "FOREST_NBINS": 0},
     "TRAIN": {"NEPOCHS": 500, "LEARNING_RATE": 1e-3, "WEIGHT_DECAY": 1e-1, "DECAY_ALPHA": 0.9, "DECAY_STEP": 10,
               "WINDOW_LENGTH_FOR_MU": 16,
               # not in the reference: "em" = F by its closed-form EM update, Adam for the other parameters (QFA.train
@@ -73,7 +78,7 @@ ARG_KEYS = {
 # keys of DEFAULTS the reference does not have (tests/test_cli_config.py pins everything else against
 # tests/golden/g12_config.json, extracted from the reference's config.py / main.py)
 EXTRA_KEYS = ("MODEL.REFERENCE_C0_QUIRK", "MODEL.N_SAMPLES", "MODEL.SAMPLE_SEED", "MODEL.N_REPLICATES", "MODEL.EXACT_GRADIENTS",
-              "TRAIN.F_UPDATE", "TRAIN.EM_RHO", "TRAIN.EM_RIDGE")
+              "MODEL.FOREST", "MODEL.FOREST_ZMIN", "MODEL.FOREST_ZMAX", "MODEL.FOREST_NBINS", "TRAIN.F_UPDATE", "TRAIN.EM_RHO", "TRAIN.EM_RIDGE")
 
 
 def _set(cfg, dotted, value):

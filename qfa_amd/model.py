@@ -9,6 +9,8 @@ Additions over the reference (none changes a reference call's result):
   * ``predict`` -- batched ``prediction_for_single_spectra``;
   * ``sample_latent`` / ``continua_from_latent`` / ``sample_continua`` -- posterior draws on the device (include/qfa_hip.h);
   * ``sample_spectra`` / ``posterior_predictive`` -- mock spectra and posterior-predictive replicates drawn from the model;
+  * ``forest`` / ``mean_transmission`` / ``ForestStack`` -- Lyman-alpha forest transmission flux / continuum and its
+    redshift-binned stack, per posterior draw, without writing a continuum (include/qfa_hip.h, qfa_forest_f32);
   * ``step`` -- forward + Adam + clip without a host sync (what ``train`` and bench.py run);
   * data parallelism: ``enable_data_parallel()`` all-reduces the packed sum/count buffer over
     RCCL once per step before the normalisation (SURVEY.md 8(e));
@@ -89,6 +91,97 @@ class EMStats(object):
             self.buf.copy_(other.buf)
         else:
             self.buf.mul_(1.0 - rho).add_(other.buf, alpha=rho)
+        return self
+
+
+class ForestStack(object):
+    """The redshift-binned stack of the forest transmission (include/qfa_hip.h, qfa_forest_f32): ``buf`` = (S, 4, nbin) float64
+    [sum w | sum w T | sum w T^2 | n] per draw of the continuum -- sums only, which is what data parallelism all-reduces --
+    over the bins [z0 + k dz, z0 + (k + 1) dz), z0 and dz as the float32 numbers the kernel bins with."""
+
+    def __init__(self, buf, z0, dz, nbin):
+        self.z0, self.dz, self.nbin = float(np.float32(z0)), float(np.float32(dz)), int(nbin)
+        if buf.dtype != torch.float64 or buf.dim() != 3 or buf.shape[1] != 4 or buf.shape[2] != self.nbin or buf.shape[0] < 1 \
+                or not buf.is_contiguous():
+            raise _lib.QFAHipError(f"ForestStack: buffer {tuple(buf.shape)} {buf.dtype}, expected contiguous float64 (S, 4, {self.nbin})")
+        if not (self.dz > 0.0 and np.isfinite(self.dz) and np.isfinite(self.z0) and 1 <= self.nbin <= 4096):
+            raise _lib.QFAHipError(f"ForestStack: bins z0 = {z0}, dz = {dz}, nbin = {nbin}")
+        self.buf = buf
+
+    @classmethod
+    def zeros(cls, S, z0, dz, nbin, device):
+        return cls(torch.zeros((int(S), 4, int(nbin)), dtype=torch.float64, device=device), z0, dz, nbin)
+
+    @property
+    def S(self):
+        return int(self.buf.shape[0])
+
+    @property
+    def bins(self):
+        return (self.z0, self.dz, self.nbin)
+
+    @property
+    def z_edges(self):
+        return self.z0 + self.dz * torch.arange(self.nbin + 1, dtype=torch.float64, device=self.buf.device)
+
+    @property
+    def z_centers(self):
+        return self.z0 + self.dz * (torch.arange(self.nbin, dtype=torch.float64, device=self.buf.device) + 0.5)
+
+    @property
+    def sum_w(self):
+        return self.buf[:, 0]
+
+    @property
+    def n(self):
+        """(S, nbin) number of pixels stacked"""
+        return self.buf[:, 3]
+
+    @property
+    def mean(self):
+        """(S, nbin) weighted mean transmission sum w T / sum w (NaN in an empty bin)"""
+        return self.buf[:, 1] / self.buf[:, 0]
+
+    @property
+    def var(self):
+        """(S, nbin) weighted variance of T inside the bin, sum w T^2 / sum w - mean^2"""
+        m = self.mean
+        return self.buf[:, 2] / self.buf[:, 0] - m * m
+
+    @property
+    def tau_eff(self):
+        """(S, nbin) effective optical depth -ln <T>"""
+        return -torch.log(self.mean)
+
+    def _draws(self, what):
+        if self.S < 2:
+            raise _lib.QFAHipError(f"ForestStack.{what}: needs more than one draw of the continuum (S = {self.S})")
+        return self.mean
+
+    @property
+    def mean_over_draws(self):
+        """(nbin,) mean of ``mean`` over the S posterior draws of the continuum"""
+        return self._draws("mean_over_draws").mean(0)
+
+    @property
+    def std_over_draws(self):
+        """(nbin,) standard deviation of ``mean`` over the S draws: the continuum posterior's error bar on the stack (the
+        continuum errors of a spectrum's pixels are correlated, which repeating the whole stack per draw carries through)"""
+        return self._draws("std_over_draws").std(0, unbiased=True)
+
+    def clone(self):
+        return ForestStack(self.buf.clone(), self.z0, self.dz, self.nbin)
+
+    def add_(self, other):
+        if other.bins != self.bins or other.S != self.S:
+            raise _lib.QFAHipError(f"ForestStack.add_: bins / draws {other.bins}, {other.S} against {self.bins}, {self.S}")
+        self.buf.add_(other.buf)
+        return self
+
+    def all_reduce(self, group=None):
+        """in-place sum over the process group (every rank calls it; an exhausted rank adds zeros)"""
+        from .distributed import all_reduce_accum
+        all_reduce_accum(self.buf.view(-1), group)
         return self
 
 
@@ -216,13 +309,13 @@ class QFA(object):
             setattr(ps, k, _lib.require_device_tensor(t, f32, k).value)
         return ps
 
-    def _batch_struct(self, delta, error, zabs, mask, zfac=None, allow_no_mask=False):
+    def _batch_struct(self, delta, error, zabs, mask, zfac=None, allow_no_mask=False, auto_factor=True):
         """``zfac`` = (zq1 (B,), pix_ratio (Nb,)) float32 device tensors: the factored-z input form of include/qfa_hip.h
         (1 + zabs[s][i] = zq1[s] pix_ratio[i], reference QFA/dataloader.py:102).  Default: the ``zfac`` attribute a
         DeviceDataloader attaches to the zabs tensors it builds; None = the kernels read zabs."""
         if zfac is None:
             zfac = getattr(zabs, "zfac", None)
-        if (zfac is None and zabs is not None and self.auto_factor_zabs and self.use_factored_z and self.Nb > 0
+        if (zfac is None and zabs is not None and auto_factor and self.auto_factor_zabs and self.use_factored_z and self.Nb > 0
                 and self._tau_callable is None):
             zfac = self._auto_zfac(zabs)
         if mask is None and not allow_no_mask:
@@ -698,14 +791,148 @@ class QFA(object):
         return self.sample_spectra(error, zabs, mask, n_samples=n_samples, seed=seed, offset=offset, hmean=hmean, hcov=hcov,
                                    zfac=zfac, batch=batch)
 
-    def predict_to_npz(self, dataloader, output_dir, batch_size=4096, n_samples=0, seed=0, n_replicates=0):
+    # ------------------------------------------------------------------ forest transmission
+    def forest(self, flux=None, error=None, zabs=None, mask=None, *, h=None, hmean=None, hcov=None, n_samples=0, seed=0, offset=0,
+               unc=None, bins=None, cont_min=0.0, pixel_range=None, unit_weights=False, stack=None, zfac=None, batch=None,
+               return_pixels=True):
+        """Lyman-alpha forest transmission T = flux / continuum on the blue side and its redshift-binned stack, for every draw of
+        the continuum, without writing a continuum (qfa_forest_f32; the contract is in include/qfa_hip.h).
+        The latent: ``h`` (B, S, Nh) as it is; else ``hmean`` alone (or with ``hcov`` and ``n_samples`` = 0): the posterior-mean
+        continuum, S = 1; else ``hmean`` + ``hcov`` + ``n_samples`` > 0 through ``sample_latent`` (``seed``, ``offset`` = the
+        global row of spectrum 0); with none of them ``predict`` runs on the inputs first, and its ``unc`` -- the continuum's
+        1 sigma, which enters ivar -- is passed on when S = 1.  ``bins`` = (z0, dz, nbin) asks for the stack; ``stack``: a
+        ``ForestStack`` to ADD to (its bins are used).  ``pixel_range`` = (p_lo, p_hi) restricts the stacked blue pixels,
+        ``unit_weights`` stacks with w = 1 instead of w = ivar, ``cont_min``: pixels whose continuum is not above it are unused.
+        ``mask`` None: every pixel is used.  A zabs tensor is read as given (never swapped for derived factors: the bins are
+        defined bit for bit by z).  Returns (trans, ivar, stack): (B, S, Nb) float32 each (None with ``return_pixels`` False) and
+        the ``ForestStack`` (None when neither ``bins`` nor ``stack`` was given)."""
+        if self.mu is None:
+            raise _lib.QFAHipError("forest needs model.mu (load_from_npz or train first)")
+        if hcov is not None and hmean is None:
+            raise _lib.QFAHipError("forest: hcov without hmean")
+        if h is not None and hmean is not None:
+            raise _lib.QFAHipError("forest: pass h or hmean / hcov, not both")
+        S = int(n_samples)
+        if S < 0:
+            raise _lib.QFAHipError(f"forest: n_samples = {n_samples}, expected >= 0")
+        if S > 0 and h is None and hmean is not None and hcov is None:
+            raise _lib.QFAHipError("forest: n_samples > 0 needs hcov next to hmean")
+        if bins is None and stack is None and not return_pixels:
+            raise _lib.QFAHipError("forest: nothing asked for (no bins, no stack, return_pixels = False)")
+        dev = self.device
+        self._params_struct()                                   # (F as a contiguous float32 device tensor)
+        if h is None and hmean is None:
+            _, hmean, hcov, _, punc = self.predict(flux, error, zabs, mask, zfac=zfac, batch=batch)
+            if S == 0 and unc is None:
+                unc = punc
+        if batch is not None:
+            B = batch.B
+            bs, keep = self._batch_struct_rows(batch, raw_flux=True)
+        else:
+            if not isinstance(flux, torch.Tensor) or flux.dim() != 2:
+                raise _lib.QFAHipError("forest: flux must be a (B, Npix) tensor")
+            B = self._check_batch_shapes(flux, error, zabs, mask if mask is not None else flux)
+            bs, keep = self._batch_struct(flux, error, zabs, mask, zfac, allow_no_mask=True, auto_factor=False)
+        bs.A_blue = None                                        # (not read by the call)
+        if h is None:
+            if tuple(hmean.shape) != (B, self.Nh):
+                raise _lib.QFAHipError(f"hmean: shape {tuple(hmean.shape)}, expected ({B}, {self.Nh})")
+            if S > 0:
+                h = self.sample_latent(hmean, hcov, S, seed=seed, offset=offset)
+            else:
+                S = 1
+                h = hmean.reshape(B, 1, self.Nh)
+        else:
+            if h.dim() != 3 or h.shape[0] != B or h.shape[2] != self.Nh or h.shape[1] < 1 or (S > 0 and h.shape[1] != S):
+                raise _lib.QFAHipError(f"h: shape {tuple(h.shape)}, expected ({B}, {S if S > 0 else 'S'}, {self.Nh})")
+            S = int(h.shape[1])
+        ph = _lib.require_device_tensor(h, f32, "h")
+        pu = None
+        if unc is not None:
+            if tuple(unc.shape) != (B, self.Npix):
+                raise _lib.QFAHipError(f"unc: shape {tuple(unc.shape)}, expected ({B}, {self.Npix})")
+            pu = _lib.require_device_tensor(unc, f32, "unc")
+        if stack is not None:
+            if not isinstance(stack, ForestStack) or stack.S != S or (bins is not None and ForestStack(stack.buf, *bins).bins != stack.bins):
+                raise _lib.QFAHipError(f"forest(stack=...): expected a ForestStack of {S} draws on the same bins")
+            _lib.require_device_tensor(stack.buf, torch.float64, "stack")
+        elif bins is not None:
+            stack = ForestStack.zeros(S, bins[0], bins[1], bins[2], dev)
+        fb = _lib.ForestBins()
+        fb.z0, fb.dz, fb.nbin = (stack.z0, stack.dz, stack.nbin) if stack is not None else (0.0, 1.0, 1)
+        p_lo, p_hi = (0, self.Nb) if pixel_range is None else (int(pixel_range[0]), int(pixel_range[1]))
+        if not 0 <= p_lo <= p_hi <= self.Nb:
+            raise _lib.QFAHipError(f"forest: pixel_range = {pixel_range}, expected 0 <= p_lo <= p_hi <= {self.Nb}")
+        fb.p_lo, fb.p_hi = p_lo, p_hi
+        trans = ivar = None
+        if return_pixels:
+            trans = torch.empty((B, S, self.Nb), dtype=f32, device=dev)
+            ivar = torch.empty((B, S, self.Nb), dtype=f32, device=dev)
+        mu = self.mu.to(device=dev, dtype=f32).contiguous()
+        need = _lib.lib().qfa_forest_workspace_bytes(B, S, self.Npix, self.Nb, self.Nh, int(fb.nbin))
+        if need == 0:
+            raise _lib.QFAHipError(f"forest: unsupported shape B={B} S={S} Npix={self.Npix} Nb={self.Nb} Nh={self.Nh} nbin={fb.nbin}")
+        ws = self._ws.get("forest_ws")
+        if ws is None or ws.numel() < need:
+            ws = torch.empty(need, dtype=torch.uint8, device=dev)
+            self._ws["forest_ws"] = ws
+        _lib.check(_lib.lib().qfa_forest_f32(
+            _lib.require_device_tensor(self.F, f32, "F"),
+            C.c_void_p(mu.data_ptr()), C.byref(bs), ph, pu, B, S, self.Npix, self.Nb, self.Nh, C.byref(fb), float(cont_min),
+            _lib.F_FOREST_UNIT_W if unit_weights else 0,
+            C.c_void_p(trans.data_ptr()) if trans is not None else None, C.c_void_p(ivar.data_ptr()) if ivar is not None else None,
+            C.c_void_p(stack.buf.data_ptr()) if stack is not None else None,
+            C.c_void_p(ws.data_ptr()), ws.numel(), _lib.current_stream(dev)), "qfa_forest_f32")
+        return trans, ivar, stack
+
+    def _loader_slices(self, dataloader, batch_size):
+        """the slices predict_to_npz walks: (first dataloader index, keyword inputs of predict / forest, paths)"""
+        n = len(dataloader)
+        for s in range(0, n, batch_size):
+            if hasattr(dataloader, "rows_batch") and self._tau_callable is None and (self.use_factored_z or self.Nb == 0):
+                rb, paths = dataloader.rows_batch(s, min(s + batch_size, n))
+                yield s, {"batch": rb}, paths
+            elif hasattr(dataloader, "get_rows"):
+                f, e, z, m, paths = dataloader.get_rows(s, min(s + batch_size, n))
+                yield s, {"flux": f, "error": e, "zabs": z, "mask": m}, paths
+            else:
+                items = [dataloader[i] for i in range(s, min(s + batch_size, n))]
+                f, e, z, m = (torch.stack([it[j] for it in items]) for j in range(4))
+                yield s, {"flux": f, "error": e, "zabs": z, "mask": m}, [it[4] for it in items]
+
+    def mean_transmission(self, dataloader, z_min, z_max, n_bins, n_samples=0, seed=0, batch_size=4096, cont_min=0.0,
+                          pixel_range=None, unit_weights=False):
+        """The stacked forest transmission of a whole dataloader in ``n_bins`` bins of [z_min, z_max): a ``ForestStack`` of S =
+        max(1, n_samples) draws.  ``n_samples`` = 0 stacks the posterior-mean continuum (``predict``'s unc enters the weights);
+        ``n_samples`` > 0 repeats the stack over that many posterior draws of every continuum (``std_over_draws``: the
+        continuum's error bar on the stack).  It walks the loader the way ``predict_to_npz`` does (the resident rows form when
+        the loader has one); the global row of a spectrum is its dataloader index, so the result does not depend on
+        ``batch_size`` beyond the rounding of float64 sums.  Under data parallelism the sums are all-reduced over the model's
+        group: every rank returns the global stack."""
+        n_bins, S = int(n_bins), max(1, int(n_samples))
+        if n_bins < 1 or not float(z_max) > float(z_min):
+            raise _lib.QFAHipError(f"mean_transmission: bins [{z_min}, {z_max}) / {n_bins}")
+        stack = ForestStack.zeros(S, z_min, (float(z_max) - float(z_min)) / n_bins, n_bins, self.device)
+        row0 = int(getattr(dataloader, "_row0", 0))              # (a data-parallel loader: the global index of its first row)
+        for s, inputs, _ in self._loader_slices(dataloader, int(batch_size)):
+            _, hmean, hcov, _, unc = self.predict(**inputs)
+            self.forest(**inputs, hmean=hmean, hcov=hcov, n_samples=int(n_samples), seed=seed, offset=row0 + s,
+                        unc=unc if int(n_samples) == 0 else None, cont_min=cont_min, pixel_range=pixel_range,
+                        unit_weights=unit_weights, stack=stack, return_pixels=False)
+        if self._dp:
+            stack.all_reduce(self._dp_group)
+        return stack
+
+    def predict_to_npz(self, dataloader, output_dir, batch_size=4096, n_samples=0, seed=0, n_replicates=0, forest=False):
         """The predict mode of the reference's main.py:87-98 for a whole dataloader: one
         ``<basename>`` .npz per spectrum with keys ll, hmean, hcov, cont, uncertainty and the
         reference's shapes ((1,1), (Nh,1), (Nh,Nh), (Npix,), (Npix,)); the posterior runs batched.
         ``n_samples`` > 0 adds ``cont_samples`` (S, Npix): continua drawn from the posterior with ``seed``, the global row of a
         spectrum being its dataloader index (so the files do not depend on ``batch_size``).  ``n_replicates`` > 0 adds
         ``flux_replicates`` (K, Npix): posterior-predictive replicates of the spectrum under its own error and mask
-        (``sample_spectra``), same ``seed`` and global row."""
+        (``sample_spectra``), same ``seed`` and global row.  ``forest`` adds ``transmission`` and ``transmission_ivar`` (Nb,):
+        flux over the posterior-mean continuum on the blue side and its inverse variance (``QFA.forest`` with this
+        prediction's hmean and unc)."""
         os.makedirs(output_dir, exist_ok=True)
         n = len(dataloader)
         written = []
@@ -733,6 +960,11 @@ class QFA(object):
             if n_replicates > 0:
                 replicates = self.sample_spectra(n_samples=n_replicates, seed=seed, offset=s, hmean=res[1], hcov=res[2],
                                                  **inputs).cpu().numpy()
+            trans = tivar = None
+            if forest:
+                fin = dict(inputs) if "batch" in inputs else dict(inputs, flux=f)
+                trans, tivar, _ = self.forest(**fin, hmean=res[1], unc=res[4])
+                trans, tivar = trans[:, 0].cpu().numpy(), tivar[:, 0].cpu().numpy()
             ll, hmean, hcov, cont, unc = (x.cpu().numpy() for x in res)
             for r, path in enumerate(paths):
                 name = os.path.basename(str(path))
@@ -741,6 +973,8 @@ class QFA(object):
                 extra = {} if samples is None else {"cont_samples": samples[r]}
                 if replicates is not None:
                     extra["flux_replicates"] = replicates[r]
+                if trans is not None:
+                    extra["transmission"], extra["transmission_ivar"] = trans[r], tivar[r]
                 np.savez(os.path.join(output_dir, name), ll=ll[r].reshape(1, 1), hmean=hmean[r].reshape(self.Nh, 1),
                          hcov=hcov[r], cont=cont[r], uncertainty=unc[r], **extra)
                 written.append(name)
