@@ -372,6 +372,59 @@ int qfa_forest_f32(const float *F, const float *mu, const qfa_batch_t *b, const 
                    unsigned flags, float *trans, float *ivar, double *stack,
                    void *workspace, size_t workspace_bytes, void *stream);
 
+/* The line-of-sight flux power spectrum of forest segments (P1D) and its stack in (k, z) (additive to ABI v4).  The statistic forest
+ * users compute from the transmission: delta_F = T / <T>(z) - 1 on segments of the forest, a Fourier transform per segment, the noise
+ * power subtracted, |delta~(k)|^2 stacked in redshift bins.  The reference stops at the continuum (QFA/model.py:160-180); this call
+ * takes what qfa_forest_f32 writes (trans, ivar) and a mean transmission (the `mean` of qfa_forest_f32's stack) and runs the rest,
+ * per posterior draw of the continuum, without ever writing delta_F.  The rest-frame grid is uniform in log lambda, so pixels are
+ * uniform in velocity and a plain DFT per segment is the estimator; it runs as a float32 matrix product on the matrix pipe, exact
+ * for every segment length.
+ *
+ * The contract.  Row r = b S + s (spectrum b of the call, draw s) of trans / ivar, segment g (0 <= g < nseg) of L = seg_len pixels
+ * p = p_lo + g L + j, 0 <= j < L; M = L / 2 (integer division) modes:
+ *   inputs     trans, ivar (B, S, Nb) float32 exactly as qfa_forest_f32 writes them: an unused pixel has ivar == 0.  Pixels outside
+ *              the segments are not read.  `b` is read for redshift only -- zabs (rows Nb apart), or zq1 + pix_ratio with
+ *              z = fma(zq1[r'], pix_ratio[p], -1) (one rounding), r' = rows ? rows[b] : b; delta, error, mask, A_blue are not read.
+ *              tbar (St, nT) float32, St = 1 (one mean transmission for every draw) or St = S (row s serves draw s), over the bins
+ *              (zT0, dzT, nT): kT = floorf((z - zT0) inv_dzT), qfa_forest_f32's rule (inv_dzT = 1.0f / dzT formed once on the host
+ *              in float32, subtraction and product each rounded once, the range test on the float, a NaN z is in no bin);
+ *   per pixel  used = ivar > 0 && 0 <= kT < nT && tb > 0 with tb = tbar[s or 0][kT] (a NaN tb fails the comparison).  A used
+ *              pixel has d = T / tb - 1 (a division and a subtraction) and v = 1 / (ivar (tb tb)), every operation rounded once,
+ *              no contraction; an unused pixel has d = 0 and v = 0 by selects, not products: a NaN under the mask reaches nothing;
+ *   segment    n_used = the number of used pixels;  N = (sum_j v_j) / L (the sum and the quotient in float64, rounded to float32
+ *              once);  X_m = sum_j d_j (cos(2 pi j m / L) - i sin(2 pi j m / L)) and P_m = (Re^2 + Im^2) / L for m = 1 .. M (mode 0
+ *              is not computed).  Every twiddle is formed from the exact integer (j m) mod L, evaluated in float64 and rounded to
+ *              float32 once; the sums over j are float32 fma chains in order of j (v_mfma_f32_16x16x4_f32); the two squares, their
+ *              sum and the division by L are float32, each rounded once.  The segment is valid when n_used >= min_used;
+ *              zc = z[r', p_lo + g L + L / 2] and kz = floorf((zc - z0) inv_dz) by the same rule;
+ *   outputs    power (B S, nseg, M) and noise (B S, nseg) float32: an invalid segment gets exactly 0 in both;
+ *              stack (S, nz, 2 + 2 M) float64 = [n | sum N | sum P_1..M | sum P^2_1..M] per draw and z-bin, over the valid segments
+ *              with 0 <= kz < nz; the terms are formed in float64 from the float32 P and N, each product rounded once.  The call ADDS
+ *              to `stack`; QFA_F_ZERO_ACCUM overwrites instead.  Any of the three may be NULL, but not all;
+ *   sums       no float atomics anywhere: the per-segment rows leave through the workspace (or through `power` / `noise`), and a
+ *              fixed-order reducer adds them, segment by segment in order of (b, g), onto what `stack` holds: two calls on the same
+ *              inputs give the same bits, and draw s of a call of S draws gets the bits of a call of that draw alone.
+ * qfa_p1d_stack_doubles: S nz (2 + 2 (L / 2)); 0 = unsupported (S < 1, nz outside 1..4096, L outside 1..4096).
+ * qfa_p1d_workspace_bytes(R = B S, ...): the scratch (the twiddle table and the per-segment rows of one launch); 0 = unsupported
+ * shape (R < 0, S < 1, R not a multiple of S, L outside 1..4096, nseg < 1, nseg L > Nb, nz outside 1..4096).
+ * Returns QFA_E_NULL for a missing required pointer (trans, ivar, b, tbar, p, workspace, all three outputs, zabs without the
+ * factored pair, half of the pair); QFA_E_SIZE for B < 0, S < 1, Nb < 1, seg_len outside 1..4096, nseg < 1, p_lo < 0,
+ * p_lo + nseg seg_len > Nb, min_used < 1, bad bins of either kind (dz <= 0 or not finite, z0 not finite, count outside 1..4096),
+ * St other than 1 or S, 0 < row_stride < Nb; QFA_E_FLAGS for any flag other than QFA_F_ZERO_ACCUM, QFA_F_SYNC; QFA_E_WORKSPACE.
+ * B = 0 does nothing, except zeroing `stack` under QFA_F_ZERO_ACCUM.  Argument checks return before any device work.  The call
+ * neither synchronises nor allocates (graph-capturable). */
+typedef struct {
+    float zT0, dzT; int nT, St;                 /* bins and rows of tbar: dzT > 0, 1 <= nT <= 4096, St = 1 or S */
+    int p_lo, seg_len, nseg, min_used;          /* 1 <= seg_len <= 4096, nseg >= 1, p_lo + nseg seg_len <= Nb, min_used >= 1 */
+    float z0, dz; int nz;                       /* bins of the stack: dz > 0, 1 <= nz <= 4096 */
+} qfa_p1d_t;
+
+size_t qfa_p1d_stack_doubles(int S, int nz, int L);
+size_t qfa_p1d_workspace_bytes(int R, int S, int Nb, int L, int nseg, int nz);
+int qfa_p1d_f32(const float *trans, const float *ivar, const qfa_batch_t *b, const float *tbar, int B, int S, int Nb,
+                const qfa_p1d_t *p, unsigned flags, float *power, float *noise, double *stack,
+                void *workspace, size_t workspace_bytes, void *stream);
+
 /* Replaces Adam.update (reference QFA/optimizer.py:37-52) followed by the clamp of QFA.clip
  * (QFA/model.py:233-241) for ONE tensor of n elements:
  *   g' = g + wd*p; m = (1-b1) g' + b1 m; v = (1-b2) g'^2 + b2 v;

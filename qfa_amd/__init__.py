@@ -11,6 +11,7 @@ __version__ = "0.1.0"
 _LAZY = {
     "QFA": ("qfa_amd.model", "QFA"),
     "QFAModel": ("qfa_amd.model", "QFAModel"),
+    "P1DStack": ("qfa_amd.model", "P1DStack"),
     "Adam": ("qfa_amd.optimizer", "Adam"),
     "step_scheduler": ("qfa_amd.optimizer", "step_scheduler"),
 }

@@ -22,6 +22,7 @@ EXPORTS = (
     "qfa_mock_workspace_bytes", "qfa_mock_spectra_f32",
     "qfa_em_floats", "qfa_em_workspace_bytes", "qfa_em_stats_f32", "qfa_em_update_f_f32",
     "qfa_forest_stack_doubles", "qfa_forest_workspace_bytes", "qfa_forest_f32",
+    "qfa_p1d_stack_doubles", "qfa_p1d_workspace_bytes", "qfa_p1d_f32",
 )
 
 TAU_IDS = {"becker": 0, "fg": 1, "kamble": 2, "mock": 3}
@@ -63,6 +64,11 @@ class Batch(C.Structure):
 
 class ForestBins(C.Structure):      # qfa_forest_bins_t
     _fields_ = [("z0", C.c_float), ("dz", C.c_float), ("nbin", C.c_int), ("p_lo", C.c_int), ("p_hi", C.c_int)]
+
+
+class P1DParams(C.Structure):       # qfa_p1d_t
+    _fields_ = [("zT0", C.c_float), ("dzT", C.c_float), ("nT", C.c_int), ("St", C.c_int), ("p_lo", C.c_int), ("seg_len", C.c_int),
+                ("nseg", C.c_int), ("min_used", C.c_int), ("z0", C.c_float), ("dz", C.c_float), ("nz", C.c_int)]
 
 
 _lib = None
@@ -130,6 +136,9 @@ def lib():
         "qfa_forest_stack_doubles": (sz, [i, i]),
         "qfa_forest_workspace_bytes": (sz, [i, i, i, i, i, i]),
         "qfa_forest_f32": (i, [p, p, C.POINTER(Batch), p, p, i, i, i, i, i, C.POINTER(ForestBins), f, C.c_uint, p, p, p, p, sz, p]),
+        "qfa_p1d_stack_doubles": (sz, [i, i, i]),
+        "qfa_p1d_workspace_bytes": (sz, [i, i, i, i, i, i]),
+        "qfa_p1d_f32": (i, [p, p, C.POINTER(Batch), p, i, i, i, C.POINTER(P1DParams), C.c_uint, p, p, p, p, sz, p]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(h, name, None)

@@ -91,6 +91,8 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     cfg = get_config(args)
     assert cfg.TYPE in ("train", "predict"), "TYPE must be in ['train', 'predict']!"
+    if cfg.TYPE == "predict" and int(cfg.MODEL.P1D_SEGMENTS) > 0 and int(cfg.MODEL.FOREST_NBINS) <= 0:
+        raise ValueError("MODEL.P1D_SEGMENTS > 0 needs MODEL.FOREST_NBINS > 0 (the mean transmission the contrast is formed with)")
     os.makedirs(cfg.DATA.OUTPUT_DIR, exist_ok=True)
     with open(os.path.join(cfg.DATA.OUTPUT_DIR, "config.yaml"), "w") as f:
         f.write(cfg.dump())
@@ -138,6 +140,16 @@ def main(argv=None):
             np.savez(os.path.join(cfg.DATA.OUTPUT_DIR, "mean_transmission.npz"), z_centers=st.z_centers.cpu().numpy(),
                      z_edges=st.z_edges.cpu().numpy(), mean=st.mean.cpu().numpy(), var=st.var.cpu().numpy(), n=st.n.cpu().numpy(),
                      tau_eff=st.tau_eff.cpu().numpy(), sums=st.buf.cpu().numpy())
+        if int(cfg.MODEL.P1D_SEGMENTS) > 0:
+            # the contrast is formed with the very stack mean_transmission.npz holds: pixels outside [FOREST_ZMIN, FOREST_ZMAX) are
+            # unused, and a segment that loses too many of them to the edges is left out (P1D_MIN_USED_FRAC)
+            ps = model.flux_power(dataloader, float(cfg.MODEL.FOREST_ZMIN), float(cfg.MODEL.FOREST_ZMAX), int(cfg.MODEL.P1D_NZBINS),
+                                  n_segments=int(cfg.MODEL.P1D_SEGMENTS), min_used_frac=float(cfg.MODEL.P1D_MIN_USED_FRAC),
+                                  tbar=st, n_samples=int(cfg.MODEL.N_SAMPLES), seed=int(cfg.MODEL.SAMPLE_SEED))
+            np.savez(os.path.join(cfg.DATA.OUTPUT_DIR, "flux_power.npz"), k=ps.k.cpu().numpy(), z_centers=ps.z_centers.cpu().numpy(),
+                     z_edges=ps.z_edges.cpu().numpy(), power=ps.power().cpu().numpy(), err=ps.err().cpu().numpy(),
+                     power_raw=ps.power_raw.cpu().numpy(), noise=ps.noise.cpu().numpy(), n=ps.n.cpu().numpy(),
+                     seg_len=ps.L, dv=ps.dv, sums=ps.buf.cpu().numpy())
         print(f"Finish predicting {len(dataloader)} spectra in {time.time() - ts} seconds...")
     return 0
 

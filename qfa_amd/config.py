@@ -57,7 +57,12 @@ DEFAULTS = {                                        # reference QFA/config.py:15
               # variance to every file (transmission, transmission_ivar, (Nb,)); FOREST_NBINS > 0 also writes
               # mean_transmission.npz, the stack in FOREST_NBINS bins of [FOREST_ZMIN, FOREST_ZMAX), repeated over N_SAMPLES
               # posterior draws when that is set (QFA.forest / mean_transmission)
-              "FOREST": False, "FOREST_ZMIN": 0.0, "FOREST_ZMAX": 0.0, "FOREST_NBINS": 0},
+              "FOREST": False, "FOREST_ZMIN": 0.0, "FOREST_ZMAX": 0.0, "FOREST_NBINS": 0,
+              # not in the reference: predict mode with P1D_SEGMENTS > 0 (needs FOREST_NBINS > 0) also writes flux_power.npz, the
+              # 1D flux power spectrum of P1D_SEGMENTS segments of the blue side stacked in P1D_NZBINS bins of [FOREST_ZMIN,
+              # FOREST_ZMAX), per posterior draw when N_SAMPLES is set, the contrast formed with the stack of
+              # mean_transmission.npz; a segment needs P1D_MIN_USED_FRAC of its pixels used (QFA.flux_power)
+              "P1D_SEGMENTS": 0, "P1D_NZBINS": 4, "P1D_MIN_USED_FRAC": 0.75},
     "TRAIN": {"NEPOCHS": 500, "LEARNING_RATE": 1e-3, "WEIGHT_DECAY": 1e-1, "DECAY_ALPHA": 0.9, "DECAY_STEP": 10,
               "WINDOW_LENGTH_FOR_MU": 16,
               # not in the reference: "em" = F by its closed-form EM update, Adam for the other parameters (QFA.train
@@ -78,7 +83,8 @@ ARG_KEYS = {
 # keys of DEFAULTS the reference does not have (tests/test_cli_config.py pins everything else against
 # tests/golden/g12_config.json, extracted from the reference's config.py / main.py)
 EXTRA_KEYS = ("MODEL.REFERENCE_C0_QUIRK", "MODEL.N_SAMPLES", "MODEL.SAMPLE_SEED", "MODEL.N_REPLICATES", "MODEL.EXACT_GRADIENTS",
-              "MODEL.FOREST", "MODEL.FOREST_ZMIN", "MODEL.FOREST_ZMAX", "MODEL.FOREST_NBINS", "TRAIN.F_UPDATE", "TRAIN.EM_RHO", "TRAIN.EM_RIDGE")
+              "MODEL.FOREST", "MODEL.FOREST_ZMIN", "MODEL.FOREST_ZMAX", "MODEL.FOREST_NBINS", "MODEL.P1D_SEGMENTS",
+              "MODEL.P1D_NZBINS", "MODEL.P1D_MIN_USED_FRAC", "TRAIN.F_UPDATE", "TRAIN.EM_RHO", "TRAIN.EM_RIDGE")
 
 
 def _set(cfg, dotted, value):

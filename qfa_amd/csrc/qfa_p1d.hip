@@ -1,0 +1,128 @@
+// qfa_p1d.hip -- C-ABI of the 1D flux power spectrum of forest segments and its (k, z) stack (include/qfa_hip.h:
+// qfa_p1d_stack_doubles, qfa_p1d_workspace_bytes, qfa_p1d_f32): argument checks, the launch plan and the launches.
+// Kernels in qfa_p1d.h.
+#include "qfa_p1d.h"
+#include "../../include/qfa_hip.h"
+
+#include <math.h>
+
+namespace {
+
+using namespace qfa_p1d;
+
+constexpr int kMaxBins = 4096;
+constexpr int kMaxLen = 4096;
+constexpr size_t kRowsTarget = (size_t)64 << 20;   // bytes of per-segment rows (code, noise, power) a launch aims at
+
+// How a call is cut: `Bc` spectra per launch; workspace = [table L float2 | code | noise | power] of one launch from its first
+// 16-byte boundary on.  (The stack does not depend on the cut: k_p1d_reduce continues the sum of the launch before.)
+struct Plan {
+    int M, Bc;
+    size_t segs, bytes;                        // segments of a full launch
+};
+
+bool shape_ok(int R, int S, int Nb, int L, int nseg, int nz) {
+    return R >= 0 && S >= 1 && R % S == 0 && Nb >= 1 && L >= 1 && L <= kMaxLen && nseg >= 1 &&
+           (int64_t)nseg * L <= Nb && nz >= 1 && nz <= kMaxBins;
+}
+
+Plan make_plan(int B, int S, int L, int nseg) {
+    Plan P;
+    P.M = L / 2;
+    const size_t per_b = (size_t)S * nseg * (size_t)(P.M + 2) * 4;
+    size_t bc = kRowsTarget / per_b;
+    if (bc < 1) bc = 1;
+    if (bc > (size_t)(B > 0 ? B : 1)) bc = (size_t)(B > 0 ? B : 1);
+    P.Bc = (int)bc;
+    P.segs = bc * S * nseg;
+    P.bytes = 16 + (size_t)L * sizeof(float2) + P.segs * (size_t)(P.M + 2) * 4;
+    return P;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t qfa_p1d_stack_doubles(int S, int nz, int L) {
+    if (S < 1 || nz < 1 || nz > kMaxBins || L < 1 || L > kMaxLen) return 0;
+    return (size_t)S * nz * (size_t)(2 + 2 * (L / 2));
+}
+
+size_t qfa_p1d_workspace_bytes(int R, int S, int Nb, int L, int nseg, int nz) {
+    if (!shape_ok(R, S, Nb, L, nseg, nz)) return 0;
+    return make_plan(R / S, S, L, nseg).bytes;
+}
+
+int qfa_p1d_f32(const float *trans, const float *ivar, const qfa_batch_t *b, const float *tbar, int B, int S, int Nb,
+                const qfa_p1d_t *p, unsigned flags, float *power, float *noise, double *stack, void *workspace,
+                size_t workspace_bytes, void *stream) {
+    if (!trans || !ivar || !b || !tbar || !p || !workspace || (!power && !noise && !stack)) return QFA_E_NULL;
+    const bool fac = b->zq1 || b->pix_ratio;
+    if (fac && !(b->zq1 && b->pix_ratio)) return QFA_E_NULL;
+    if (!fac && !b->zabs) return QFA_E_NULL;
+    if (B < 0 || S < 1 || Nb < 1 || (int64_t)B * S > INT32_MAX) return QFA_E_SIZE;
+    if (p->seg_len < 1 || p->seg_len > kMaxLen || p->nseg < 1 || p->p_lo < 0 ||
+        (int64_t)p->p_lo + (int64_t)p->nseg * p->seg_len > Nb || p->min_used < 1)
+        return QFA_E_SIZE;
+    if (!(p->dz > 0.f) || !isfinite(p->dz) || !isfinite(p->z0) || p->nz < 1 || p->nz > kMaxBins) return QFA_E_SIZE;
+    if (!(p->dzT > 0.f) || !isfinite(p->dzT) || !isfinite(p->zT0) || p->nT < 1 || p->nT > kMaxBins) return QFA_E_SIZE;
+    if (p->St != 1 && p->St != S) return QFA_E_SIZE;
+    if (b->row_stride != 0 && b->row_stride < (int64_t)Nb) return QFA_E_SIZE;
+    if (flags & ~(QFA_F_ZERO_ACCUM | QFA_F_SYNC)) return QFA_E_FLAGS;
+    const int L = p->seg_len, nseg = p->nseg, nz = p->nz;
+    const Plan P = make_plan(B, S, L, nseg);
+    if (workspace_bytes < P.bytes) return QFA_E_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    const int M = P.M;
+    int zero = (flags & QFA_F_ZERO_ACCUM) ? 1 : 0;
+    if (B == 0) {
+        if (stack && zero) {
+            hipError_t e = hipMemsetAsync(stack, 0, (size_t)S * nz * (size_t)(2 + 2 * M) * sizeof(double), st);
+            if (e != hipSuccess) return (int)e;
+        }
+        return 0;
+    }
+    float2 *tw = (float2 *)(((uintptr_t)workspace + 15) & ~(uintptr_t)15);
+    int *code = (int *)(tw + L);
+    float *nws = (float *)(code + P.segs);
+    float *pws = nws + P.segs;
+    k_p1d_twiddle<<<(unsigned)((L + 255) / 256), 256, 0, st>>>(L, tw);
+    Args a;
+    a.bt = *b;
+    a.trans = trans;
+    a.ivar = ivar;
+    a.tbar = tbar;
+    a.tw = tw;
+    a.S = S; a.St = p->St; a.Nb = Nb; a.L = L; a.M = M; a.nseg = nseg; a.p_lo = p->p_lo; a.min_used = p->min_used;
+    a.nT = p->nT; a.nz = nz; a.factored = fac ? 1 : 0;
+    a.zT0 = p->zT0;
+    a.inv_dzT = 1.0f / p->dzT;
+    a.z0 = p->z0;
+    a.inv_dz = 1.0f / p->dz;
+    const size_t lds = (size_t)kRows * kStride * sizeof(float) + (size_t)L * sizeof(float2);
+    const unsigned gy = (unsigned)((M > 0 ? M : 1) + kModes - 1) / kModes;
+    // without a stack nothing is held between the kernels: one launch writes the caller's arrays
+    const int step = stack ? P.Bc : B;
+    for (int b0 = 0; b0 < B; b0 += step) {
+        a.b0 = b0;
+        a.Bc = B - b0 < step ? B - b0 : step;
+        const size_t first = (size_t)b0 * S * nseg;                               // the launch's first segment
+        a.power = power ? power + first * M : (stack ? pws : nullptr);
+        a.noise = noise ? noise + first : (stack ? nws : nullptr);
+        a.code = stack ? code : nullptr;
+        const size_t segs = (size_t)a.Bc * S * nseg;
+        k_p1d<<<dim3((unsigned)((segs + kRows - 1) / kRows), gy), kThreads, lds, st>>>(a);
+        if (stack) {
+            k_p1d_reduce<<<dim3((unsigned)(S * nz), (unsigned)((M > 0 ? M : 1) + 255) / 256), 256, 0, st>>>(
+                code, a.power, a.noise, a.Bc, S, nseg, M, nz, zero, stack);
+            zero = 0;
+        }
+    }
+    if (flags & QFA_F_SYNC) {
+        hipError_t s = hipStreamSynchronize(st);
+        if (s != hipSuccess) { (void)hipGetLastError(); return (int)s; }
+    }
+    return (int)hipGetLastError();
+}
+
+}  // extern "C"

@@ -11,6 +11,8 @@ Additions over the reference (none changes a reference call's result):
   * ``sample_spectra`` / ``posterior_predictive`` -- mock spectra and posterior-predictive replicates drawn from the model;
   * ``forest`` / ``mean_transmission`` / ``ForestStack`` -- Lyman-alpha forest transmission flux / continuum and its
     redshift-binned stack, per posterior draw, without writing a continuum (include/qfa_hip.h, qfa_forest_f32);
+  * ``p1d`` / ``flux_power`` / ``P1DStack`` -- the 1D flux power spectrum of forest segments and its (k, z) stack, per posterior
+    draw (include/qfa_hip.h, qfa_p1d_f32);
   * ``step`` -- forward + Adam + clip without a host sync (what ``train`` and bench.py run);
   * data parallelism: ``enable_data_parallel()`` all-reduces the packed sum/count buffer over
     RCCL once per step before the normalisation (SURVEY.md 8(e));
@@ -175,6 +177,119 @@ class ForestStack(object):
     def add_(self, other):
         if other.bins != self.bins or other.S != self.S:
             raise _lib.QFAHipError(f"ForestStack.add_: bins / draws {other.bins}, {other.S} against {self.bins}, {self.S}")
+        self.buf.add_(other.buf)
+        return self
+
+    def all_reduce(self, group=None):
+        """in-place sum over the process group (every rank calls it; an exhausted rank adds zeros)"""
+        from .distributed import all_reduce_accum
+        all_reduce_accum(self.buf.view(-1), group)
+        return self
+
+
+class P1DStack(object):
+    """The (k, z) stack of the 1D flux power spectrum (include/qfa_hip.h, qfa_p1d_f32): ``buf`` = (S, nz, 2 + 2M) float64
+    [n | sum N | sum P_1..M | sum P^2_1..M] per draw of the continuum and z-bin -- sums only, which is what data parallelism
+    all-reduces -- over segments of ``L`` pixels ``dv`` km/s wide, M = L // 2 modes k_m = 2 pi m / (L dv); z-bins
+    [z0 + i dz, z0 + (i + 1) dz), z0 and dz as the float32 numbers the kernel bins with."""
+
+    def __init__(self, buf, z0, dz, nz, L, dv=1.0):
+        self.z0, self.dz, self.nz = float(np.float32(z0)), float(np.float32(dz)), int(nz)
+        self.L, self.dv = int(L), float(dv)
+        self.M = self.L // 2
+        if buf.dtype != torch.float64 or buf.dim() != 3 or buf.shape[0] < 1 or buf.shape[1] != self.nz \
+                or buf.shape[2] != 2 + 2 * self.M or not buf.is_contiguous():
+            raise _lib.QFAHipError(f"P1DStack: buffer {tuple(buf.shape)} {buf.dtype}, expected contiguous float64 "
+                                   f"(S, {self.nz}, {2 + 2 * self.M})")
+        if not (self.dz > 0.0 and np.isfinite(self.dz) and np.isfinite(self.z0) and 1 <= self.nz <= 4096 and 1 <= self.L <= 4096
+                and self.dv > 0.0 and np.isfinite(self.dv)):
+            raise _lib.QFAHipError(f"P1DStack: bins z0 = {z0}, dz = {dz}, nz = {nz}, L = {L}, dv = {dv}")
+        self.buf = buf
+
+    @classmethod
+    def zeros(cls, S, z0, dz, nz, L, dv, device):
+        return cls(torch.zeros((int(S), int(nz), 2 + 2 * (int(L) // 2)), dtype=torch.float64, device=device), z0, dz, nz, L, dv)
+
+    @property
+    def S(self):
+        return int(self.buf.shape[0])
+
+    @property
+    def bins(self):
+        return (self.z0, self.dz, self.nz)
+
+    @property
+    def z_edges(self):
+        return self.z0 + self.dz * torch.arange(self.nz + 1, dtype=torch.float64, device=self.buf.device)
+
+    @property
+    def z_centers(self):
+        return self.z0 + self.dz * (torch.arange(self.nz, dtype=torch.float64, device=self.buf.device) + 0.5)
+
+    @property
+    def k(self):
+        """(M,) wavenumbers 2 pi m / (L dv), m = 1 .. M, in s/km"""
+        return 2.0 * np.pi * torch.arange(1, self.M + 1, dtype=torch.float64, device=self.buf.device) / (self.L * self.dv)
+
+    @property
+    def n(self):
+        """(S, nz) number of segments stacked"""
+        return self.buf[:, :, 0]
+
+    @property
+    def noise(self):
+        """(S, nz) mean noise level <N> of the stacked segments, in pixel units (NaN in an empty bin)"""
+        return self.buf[:, :, 1] / self.n
+
+    @property
+    def power_raw(self):
+        """(S, nz, M) mean |delta~_m|^2 / L of the stacked segments, in pixel units, noise included"""
+        return self.buf[:, :, 2:2 + self.M] / self.n[:, :, None]
+
+    def window2(self, resolution_kms):
+        """(M,) W^2(k): the pixel's sinc times a Gaussian of ``resolution_kms`` (1 sigma), squared"""
+        k = self.k
+        return (torch.sinc(k * self.dv / (2.0 * np.pi)) * torch.exp(-0.5 * (k * float(resolution_kms)) ** 2)) ** 2
+
+    def power(self, resolution_kms=None):
+        """(S, nz, M) P1D in km/s: (power_raw - noise) dv, divided by ``window2(resolution_kms)`` when that is given"""
+        P = (self.power_raw - self.noise[:, :, None]) * self.dv
+        return P if resolution_kms is None else P / self.window2(resolution_kms)
+
+    def err(self, resolution_kms=None):
+        """(S, nz, M) standard error of ``power`` from the scatter of the segments: sqrt((<P^2> - <P>^2) / (n - 1)) dv"""
+        m2 = self.buf[:, :, 2 + self.M:] / self.n[:, :, None]
+        var = (m2 - self.power_raw ** 2).clamp_min(0.0) / (self.n[:, :, None] - 1.0)
+        e = torch.sqrt(var) * self.dv
+        e = torch.where(self.n[:, :, None] > 1.0, e, torch.full_like(e, float("nan")))
+        return e if resolution_kms is None else e / self.window2(resolution_kms)
+
+    def _draws(self, what):
+        if self.S < 2:
+            raise _lib.QFAHipError(f"P1DStack.{what}: needs more than one draw of the continuum (S = {self.S})")
+        return self.power()
+
+    @property
+    def mean_over_draws(self):
+        """(nz, M) mean of ``power()`` over the S posterior draws of the continuum"""
+        return self._draws("mean_over_draws").mean(0)
+
+    @property
+    def std_over_draws(self):
+        """(nz, M) standard deviation of ``power()`` over the S draws: the continuum posterior's error bar on P1D"""
+        return self._draws("std_over_draws").std(0, unbiased=True)
+
+    def draws(self, s0, s1):
+        """the stack of draws [s0, s1): a view of the same buffer"""
+        return P1DStack(self.buf[s0:s1], self.z0, self.dz, self.nz, self.L, self.dv)
+
+    def clone(self):
+        return P1DStack(self.buf.clone(), self.z0, self.dz, self.nz, self.L, self.dv)
+
+    def add_(self, other):
+        if other.bins != self.bins or other.S != self.S or other.L != self.L or other.dv != self.dv:
+            raise _lib.QFAHipError(f"P1DStack.add_: bins / draws / segments {other.bins}, {other.S}, {other.L} against "
+                                   f"{self.bins}, {self.S}, {self.L}")
         self.buf.add_(other.buf)
         return self
 
@@ -884,6 +999,148 @@ class QFA(object):
             C.c_void_p(stack.buf.data_ptr()) if stack is not None else None,
             C.c_void_p(ws.data_ptr()), ws.numel(), _lib.current_stream(dev)), "qfa_forest_f32")
         return trans, ivar, stack
+
+    # ------------------------------------------------------------------ 1D flux power spectrum
+    P1D_PAIR_BYTES = 1 << 30    # flux_power: the most the (B, S_chunk, Nb) trans / ivar pair of a slice may take
+
+    def p1d(self, trans, ivar, *, zabs=None, zfac=None, batch=None, tbar, tbar_bins=None, seg_len, n_segments, pixel_start=0,
+            min_used, bins=None, stack=None, return_segments=True, dv=1.0):
+        """The 1D flux power spectrum of forest segments and its (k, z) stack (qfa_p1d_f32; the contract is in include/qfa_hip.h).
+        ``trans``, ``ivar`` (B, S, Nb) as ``forest`` returns them; the redshift of the pixels from ``zabs`` (B, Nb), ``zfac`` =
+        (zq1, pix_ratio) or a resident ``batch``.  ``tbar``: the mean transmission the contrast delta_F = T / tbar - 1 is formed
+        with -- a ``ForestStack`` (its ``mean`` per draw: one row per draw when it has S draws, else its single row for every
+        draw) or a (St, nT) / (nT,) tensor over ``tbar_bins`` = (z0, dz, nT).  Segment g holds the ``seg_len`` pixels from
+        ``pixel_start`` + g ``seg_len`` on and is used when at least ``min_used`` of them are.  ``bins`` = (z0, dz, nz) asks for
+        the stack (``dv``: the pixel width in km/s it reports k and P in); ``stack``: a ``P1DStack`` to ADD to.  Returns
+        (power (B, S, n_segments, M), noise (B, S, n_segments), stack): float32 P_m = |delta~_m|^2 / L for m = 1 .. M = seg_len // 2
+        and the noise level, both in pixel units (None with ``return_segments`` False), and the ``P1DStack`` (or None)."""
+        dev = self.device
+        if not isinstance(trans, torch.Tensor) or trans.dim() != 3 or trans.shape[2] != self.Nb or tuple(ivar.shape) != tuple(trans.shape):
+            raise _lib.QFAHipError(f"p1d: trans / ivar must be (B, S, {self.Nb}) tensors")
+        B, S = int(trans.shape[0]), int(trans.shape[1])
+        L, nseg, p_lo = int(seg_len), int(n_segments), int(pixel_start)
+        if bins is None and stack is None and not return_segments:
+            raise _lib.QFAHipError("p1d: nothing asked for (no bins, no stack, return_segments = False)")
+        if isinstance(tbar, ForestStack):
+            if tbar.S not in (1, S):
+                raise _lib.QFAHipError(f"p1d: tbar has {tbar.S} draws, expected 1 or {S}")
+            tbar_bins, tbar = tbar.bins, tbar.mean
+        if tbar_bins is None:
+            raise _lib.QFAHipError("p1d: a tbar tensor needs tbar_bins = (z0, dz, nT)")
+        tbar = tbar.to(device=dev, dtype=f32).reshape(-1, int(tbar_bins[2])).contiguous()
+        St = int(tbar.shape[0])
+        if St not in (1, S):
+            raise _lib.QFAHipError(f"p1d: tbar has {St} rows, expected 1 or {S}")
+        if batch is not None:
+            if batch.B != B:
+                raise _lib.QFAHipError(f"p1d: resident batch of {batch.B} spectra, trans has {B}")
+            bs, keep = self._batch_struct_rows(batch, need_src=False)
+        else:
+            bs, keep = _lib.Batch(), []
+            bs.row_stride = 0
+            if zfac is None:
+                zfac = getattr(zabs, "zfac", None)              # (what a DeviceDataloader attaches)
+            # _batch_struct's condition, so that p1d bins on the very z `forest` and `mean_transmission` binned on
+            if zfac is not None and not (self._tau_callable is None and self.use_factored_z):
+                if zabs is None:
+                    raise _lib.QFAHipError("zabs is None and no usable zfac = (zq1, pix_ratio) was given")
+                zfac = None
+            if zfac is None and zabs is not None:
+                if tuple(zabs.shape) != (B, self.Nb):
+                    raise _lib.QFAHipError(f"zabs: shape {tuple(zabs.shape)}, expected ({B}, {self.Nb})")
+                zabs = zabs if (zabs.dtype == f32 and zabs.is_contiguous()) else zabs.to(f32).contiguous()
+                keep.append(zabs)
+                bs.zabs = _lib.require_device_tensor(zabs, f32, "zabs").value
+            elif zfac is not None:
+                zq1, ratio = (t if (t.dtype == f32 and t.is_contiguous()) else t.to(f32).contiguous() for t in zfac)
+                if tuple(zq1.shape) != (B,) or tuple(ratio.shape) != (self.Nb,):
+                    raise _lib.QFAHipError(f"zfac shapes {tuple(zq1.shape)}, {tuple(ratio.shape)}: expected ({B},), ({self.Nb},)")
+                keep += [zq1, ratio]
+                bs.zq1 = _lib.require_device_tensor(zq1, f32, "zq1").value
+                bs.pix_ratio = _lib.require_device_tensor(ratio, f32, "pix_ratio").value
+            else:
+                raise _lib.QFAHipError("p1d: pass zabs, zfac = (zq1, pix_ratio) or batch")
+        if stack is not None:
+            if not isinstance(stack, P1DStack) or stack.S != S or stack.L != L or \
+                    (bins is not None and P1DStack(stack.buf, bins[0], bins[1], bins[2], L).bins != stack.bins):
+                raise _lib.QFAHipError(f"p1d(stack=...): expected a P1DStack of {S} draws and segments of {L} pixels on the same bins")
+            _lib.require_device_tensor(stack.buf, torch.float64, "stack")
+        elif bins is not None:
+            stack = P1DStack.zeros(S, bins[0], bins[1], bins[2], L, dv, dev)
+        pp = _lib.P1DParams()
+        pp.zT0, pp.dzT, pp.nT, pp.St = float(np.float32(tbar_bins[0])), float(np.float32(tbar_bins[1])), int(tbar_bins[2]), St
+        pp.p_lo, pp.seg_len, pp.nseg, pp.min_used = p_lo, L, nseg, int(min_used)
+        pp.z0, pp.dz, pp.nz = (stack.z0, stack.dz, stack.nz) if stack is not None else (0.0, 1.0, 1)
+        need = _lib.lib().qfa_p1d_workspace_bytes(B * S, S, self.Nb, L, nseg, int(pp.nz)) if L >= 1 and nseg >= 1 else 0
+        if need == 0:
+            raise _lib.QFAHipError(f"p1d: unsupported shape B={B} S={S} Nb={self.Nb} seg_len={L} n_segments={nseg} nz={pp.nz}")
+        ws = self._ws.get("p1d_ws")
+        if ws is None or ws.numel() < need:
+            ws = torch.empty(need, dtype=torch.uint8, device=dev)
+            self._ws["p1d_ws"] = ws
+        power = noise = None
+        if return_segments:
+            power = torch.empty((B, S, nseg, L // 2), dtype=f32, device=dev)
+            noise = torch.empty((B, S, nseg), dtype=f32, device=dev)
+        _lib.check(_lib.lib().qfa_p1d_f32(
+            _lib.require_device_tensor(trans, f32, "trans"), _lib.require_device_tensor(ivar, f32, "ivar"), C.byref(bs),
+            C.c_void_p(tbar.data_ptr()), B, S, self.Nb, C.byref(pp), 0,
+            C.c_void_p(power.data_ptr()) if power is not None else None, C.c_void_p(noise.data_ptr()) if noise is not None else None,
+            C.c_void_p(stack.buf.data_ptr()) if stack is not None else None,
+            C.c_void_p(ws.data_ptr()), ws.numel(), _lib.current_stream(dev)), "qfa_p1d_f32")
+        return power, noise, stack
+
+    def flux_power(self, dataloader, z_min, z_max, n_zbins, *, n_segments=3, seg_len=None, min_used_frac=0.75, tbar=None,
+                   tbar_nbins=64, n_samples=0, seed=0, batch_size=4096, cont_min=0.0, dv=None):
+        """The 1D flux power spectrum of a whole dataloader: a ``P1DStack`` of S = max(1, n_samples) draws over ``n_zbins`` bins of
+        [z_min, z_max) in the redshift of a segment's central pixel.  The blue side is cut into ``n_segments`` segments of
+        ``seg_len`` pixels (default Nb // n_segments); a segment is used when ``min_used_frac`` of its pixels are.  ``tbar``: the
+        ``ForestStack`` the contrast is formed with; None runs ``mean_transmission`` first, with the same ``n_samples`` / ``seed``
+        and ``tbar_nbins`` bins that cover every pixel of a stacked segment, so that draw s of <T> is the same continuum draw as
+        draw s of T.  Per slice of the loader: ``predict``, ``forest`` and ``p1d``, the draws in chunks that keep the
+        (B, S_chunk, Nb) trans / ivar pair under ``P1D_PAIR_BYTES`` (1 GiB).  ``dv``: the pixel width in km/s, default
+        c ln(lambda_1 / lambda_0) of the loader's ``wav_grid``.  The global row of a spectrum is its dataloader index and the
+        reducer adds segments in order, so the result does not depend on ``batch_size`` beyond the rounding of float64 sums.
+        Under data parallelism the sums are all-reduced over the model's group: every rank returns the global stack."""
+        nseg, nz, S = int(n_segments), int(n_zbins), max(1, int(n_samples))
+        L = int(seg_len) if seg_len is not None else (self.Nb // nseg if nseg > 0 else 0)
+        if nseg < 1 or L < 1 or nseg * L > self.Nb or nz < 1 or not float(z_max) > float(z_min) or not 0.0 < float(min_used_frac) <= 1.0:
+            raise _lib.QFAHipError(f"flux_power: {nseg} segments of {L} pixels on Nb = {self.Nb}, bins [{z_min}, {z_max}) / {nz}, "
+                                   f"min_used_frac = {min_used_frac}")
+        if dv is None:
+            wav = getattr(dataloader, "wav_grid", None)
+            if wav is None or len(wav) < 2:
+                raise _lib.QFAHipError("flux_power: the dataloader has no wav_grid: pass dv (km/s per pixel)")
+            dv = 299792.458 * float(np.log(float(wav[1]) / float(wav[0])))
+        min_used = max(1, int(np.ceil(float(min_used_frac) * L)))
+        if tbar is None:
+            half = float(np.exp(0.5 * (L + 1) * float(dv) / 299792.458))          # (1 + z) over half a segment
+            tbar = self.mean_transmission(dataloader, (1.0 + float(z_min)) / half - 1.0, (1.0 + float(z_max)) * half - 1.0,
+                                          int(tbar_nbins), n_samples=int(n_samples), seed=seed, batch_size=batch_size,
+                                          cont_min=cont_min)
+        if not isinstance(tbar, ForestStack) or tbar.S not in (1, S):
+            raise _lib.QFAHipError(f"flux_power: tbar must be a ForestStack of 1 or {S} draws")
+        tmean = tbar.mean.to(f32)
+        stack = P1DStack.zeros(S, z_min, (float(z_max) - float(z_min)) / nz, nz, L, dv, self.device)
+        row0 = int(getattr(dataloader, "_row0", 0))              # (a data-parallel loader: the global index of its first row)
+        for s, inputs, _ in self._loader_slices(dataloader, int(batch_size)):
+            _, hmean, hcov, _, unc = self.predict(**inputs)
+            B = int(hmean.shape[0])
+            if int(n_samples) > 0:
+                h, unc = self.sample_latent(hmean, hcov, S, seed=seed, offset=row0 + s), None
+            else:
+                h = hmean.reshape(B, 1, self.Nh)
+            Sc = max(1, min(S, self.P1D_PAIR_BYTES // max(1, B * self.Nb * 8)))
+            zin = {"batch": inputs["batch"]} if "batch" in inputs else {"zabs": inputs["zabs"]}
+            for s0 in range(0, S, Sc):
+                s1 = min(S, s0 + Sc)
+                hs = h if (s0 == 0 and s1 == S) else h[:, s0:s1].contiguous()
+                tr, iv, _ = self.forest(**inputs, h=hs, unc=unc, cont_min=cont_min)
+                self.p1d(tr, iv, **zin, tbar=tmean if tbar.S == 1 else tmean[s0:s1], tbar_bins=tbar.bins, seg_len=L,
+                         n_segments=nseg, min_used=min_used, stack=stack.draws(s0, s1), return_segments=False)
+        if self._dp:
+            stack.all_reduce(self._dp_group)
+        return stack
 
     def _loader_slices(self, dataloader, batch_size):
         """the slices predict_to_npz walks: (first dataloader index, keyword inputs of predict / forest, paths)"""
