@@ -432,7 +432,9 @@ int qfa_p1d_f32(const float *trans, const float *ivar, const qfa_batch_t *b, con
  * with i = Adam.i (advanced by Adam.step(), once per epoch in QFA.train).  The hyper-parameters
  * are doubles because the reference holds them as Python floats and rounds (1-b), b^(i+1) etc.
  * to float32 only when they meet a tensor.  m and v are updated in place; pass lo > hi to skip
- * the clamp.  NaN propagates as in torch. */
+ * the clamp.  NaN propagates as in torch.  One departure from the reference's float32: where v/bc2 overflows although v is
+ * finite (|g| beyond ~1e18 while bc2 is small) the root is formed as sqrt(v)/sqrt(bc2), so the element still moves by about
+ * lr as in exact arithmetic; the reference's inf leaves it where it is.  n = 0 does nothing and returns 0. */
 int qfa_adam_clip_f32(const float *p, const float *g, float *m, float *v, float *p_out, size_t n,
                       double lr, double b1, double b2, double eps, double wd, int i,
                       float lo, float hi, void *stream);
@@ -469,7 +471,9 @@ int qfa_clip_f32(const float *x, float *y, size_t n, float lo, float hi, void *s
  * (2*half+1) rows along axis 0 of an (n, cols) array, divisor = in-range sample count. */
 int qfa_smooth_f32(const float *x, float *y, int n, int cols, int half, void *stream);
 
-/* Replace tau(), tauHI(), omega_func() (reference QFA/utils.py:57-92, 149-171), elementwise on n. */
+/* Replace tau(), tauHI(), omega_func() (reference QFA/utils.py:57-92, 149-171), elementwise on n.
+ * For every elementwise entry point (these three, qfa_clip_f32, qfa_smooth_f32, qfa_adam_clip_f32) n = 0 does nothing and
+ * returns 0 whatever the pointers are: an empty torch tensor (N_b = 0) has a NULL data pointer. */
 int qfa_tau_f32(const float *z, float *out, size_t n, const qfa_tau_t *tau, void *stream);
 int qfa_tauhi_f32(const float *z, const float *tau0, const float *beta, float *out, size_t n,
                   void *stream);

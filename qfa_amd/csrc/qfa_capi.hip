@@ -235,23 +235,23 @@ int qfa_smooth_f32(const float *x, float *y, int n, int cols, int half, void *st
 }
 
 int qfa_tau_f32(const float *z, float *out, size_t n, const qfa_tau_t *tau, void *stream) {
+    if (n == 0) return 0;                      // empty tensors (N_b = 0) carry NULL data pointers
     if (!z || !out || !tau) return QFA_E_NULL;
-    if (n == 0) return 0;
     k_tau<<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>(z, out, n, *tau);
     return hip_status();
 }
 
 int qfa_tauhi_f32(const float *z, const float *tau0, const float *beta, float *out, size_t n, void *stream) {
+    if (n == 0) return 0;                      // empty tensors (N_b = 0) carry NULL data pointers
     if (!z || !out || !tau0 || !beta) return QFA_E_NULL;
-    if (n == 0) return 0;
     k_tauhi<<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>(z, tau0, beta, out, n);
     return hip_status();
 }
 
 int qfa_omega_func_f32(const float *z, const float *tau0, const float *beta, const float *c0, float *out, size_t n,
                        void *stream) {
+    if (n == 0) return 0;                      // empty tensors (N_b = 0) carry NULL data pointers
     if (!z || !out || !tau0 || !beta || !c0) return QFA_E_NULL;
-    if (n == 0) return 0;
     k_omega_func<<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>(z, tau0, beta, c0, out, n);
     return hip_status();
 }

@@ -59,20 +59,32 @@ __global__ void k_finalize(const float *__restrict__ accum, const float *__restr
 // ------------------------------------------------------------------------------------------------
 // k_adam_clip : Adam.update + clip for one tensor (QFA/optimizer.py:47-52, QFA/model.py:237-241)
 // ------------------------------------------------------------------------------------------------
+// The update of one element, shared by the three kernels below so that they cannot drift apart (include/qfa_hip.h promises
+// "same arithmetic").  Where v / bc2 overflows float32 although v is finite (|g| beyond ~1e18 early in training) the root is
+// formed as sqrt(v) / sqrt(bc2): the reference's float32 gives inf there and stops moving the element; every other input
+// keeps the reference's operations and roundings.
+__device__ __forceinline__ float adam_clip_update(float pi, float g, float *__restrict__ m, float *__restrict__ v, float lr,
+                                                  float b1, float b2, float omb1, float omb2, float eps, float wd, float bc1,
+                                                  float bc2, float lo, float hi) {
+    const float gi = g + wd * pi;
+    const float mi = omb1 * gi + b1 * *m;
+    const float vi = omb2 * gi * gi + b2 * *v;
+    *m = mi;
+    *v = vi;
+    const float vh = vi / bc2;
+    float root = __fsqrt_rn(vh);
+    if (vh == __builtin_inff() && vi < __builtin_inff()) root = __fsqrt_rn(vi) / __fsqrt_rn(bc2);
+    float q = pi - lr * (mi / bc1) / (root + eps);
+    if (lo <= hi) q = q < lo ? lo : (q > hi ? hi : q);   // NaN stays NaN, like torch.clip
+    return q;
+}
+
 __global__ void k_adam_clip(const float *__restrict__ p, const float *__restrict__ g, float *__restrict__ m,
                             float *__restrict__ v, float *__restrict__ pout, size_t n, float lr, float b1, float b2,
                             float omb1, float omb2, float eps, float wd, float bc1, float bc2, float lo, float hi) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const float pi = p[i];
-    const float gi = g[i] + wd * pi;
-    const float mi = omb1 * gi + b1 * m[i];
-    const float vi = omb2 * gi * gi + b2 * v[i];
-    m[i] = mi;
-    v[i] = vi;
-    float q = pi - lr * (mi / bc1) / (__fsqrt_rn(vi / bc2) + eps);
-    if (lo <= hi) q = q < lo ? lo : (q > hi ? hi : q);   // NaN stays NaN, like torch.clip
-    pout[i] = q;
+    pout[i] = adam_clip_update(p[i], g[i], m + i, v + i, lr, b1, b2, omb1, omb2, eps, wd, bc1, bc2, lo, hi);
 }
 
 // all parameter tensors in one launch: block b works on tensor k with blk0[k] <= b < blk0[k+1]
@@ -88,16 +100,8 @@ __global__ void k_adam_clip_multi(AdamMultiArgs a, float lr, float b1, float b2,
         if (j < a.t.count && blockIdx.x >= a.blk0[j]) k = j;
     const size_t i = (size_t)(blockIdx.x - a.blk0[k]) * blockDim.x + threadIdx.x;
     if (i >= a.t.n[k]) return;
-    const float pi = a.t.p[k][i];
-    const float gi = a.t.g[k][i] + wd * pi;
-    const float mi = omb1 * gi + b1 * a.t.m[k][i];
-    const float vi = omb2 * gi * gi + b2 * a.t.v[k][i];
-    a.t.m[k][i] = mi;
-    a.t.v[k][i] = vi;
-    float q = pi - lr * (mi / bc1) / (__fsqrt_rn(vi / bc2) + eps);
-    const float lo = a.t.lo[k], hi = a.t.hi[k];
-    if (lo <= hi) q = q < lo ? lo : (q > hi ? hi : q);
-    a.t.p_out[k][i] = q;
+    a.t.p_out[k][i] = adam_clip_update(a.t.p[k][i], a.t.g[k][i], a.t.m[k] + i, a.t.v[k] + i, lr, b1, b2, omb1, omb2, eps, wd,
+                                       bc1, bc2, a.t.lo[k], a.t.hi[k]);
 }
 
 // k_finalize + k_adam_clip_multi in ONE launch (the training step never looks at the gradients themselves): block b works on
@@ -134,15 +138,8 @@ __global__ void k_finalize_adam(AdamMultiArgs a, const float *__restrict__ accum
     else if (k == 1) g = accPsi[i] / accCnt[i];
     else if (k == 2) g = accOm[i] / accCnt[i];
     else g = accS[k - 3] / accS[3];
-    const float gi = g + wd * pi;
-    const float mi = omb1 * gi + b1 * a.t.m[k][i];
-    const float vi = omb2 * gi * gi + b2 * a.t.v[k][i];
-    a.t.m[k][i] = mi;
-    a.t.v[k][i] = vi;
-    float q = pi - lr * (mi / bc1) / (__fsqrt_rn(vi / bc2) + eps);
-    const float lo = a.t.lo[k], hi = a.t.hi[k];
-    if (lo <= hi) q = q < lo ? lo : (q > hi ? hi : q);
-    a.t.p_out[k][i] = q;
+    a.t.p_out[k][i] = adam_clip_update(pi, g, a.t.m[k] + i, a.t.v[k] + i, lr, b1, b2, omb1, omb2, eps, wd, bc1, bc2, a.t.lo[k],
+                                       a.t.hi[k]);
 }
 
 __global__ void k_clip(const float *__restrict__ x, float *__restrict__ y, size_t n, float lo, float hi) {
