@@ -425,6 +425,51 @@ int qfa_p1d_f32(const float *trans, const float *ivar, const qfa_batch_t *b, con
                 const qfa_p1d_t *p, unsigned flags, float *power, float *noise, double *stack,
                 void *workspace, size_t workspace_bytes, void *stream);
 
+/* Band powers of the forest's P1D and the covariance matrix between the bands, per posterior draw and z-bin (additive to ABI v4).
+ * qfa_p1d_f32's stack holds a mean and a variance per Fourier mode and nothing between modes; a measurement is reported in
+ * k-bands with the covariance between them, which masks, the window and the continuum make non-diagonal.  This call runs
+ * qfa_p1d_f32's kernels unchanged into the workspace and reduces their rows to bands and to sums of outer products.
+ *
+ * The contract.  trans, ivar, b, tbar, B, S, Nb and p are qfa_p1d_f32's: the per-pixel rule, segment validity and the z-bin kz of a
+ * segment are those of that call, and the P_m and N this call works from have the bits qfa_p1d_f32 writes to `power` / `noise` for
+ * the same inputs.  M = seg_len / 2.
+ *   bands      band (M,) int32 on the device: entry m - 1 is the band of mode m; a value outside 0 .. nband - 1 puts the mode in no
+ *              band.  weight (M,) float32 on the device or NULL (every w_m = 1): the caller folds dv, 1 / n_a and 1 / W^2(k_m) in;
+ *   segment    for a valid segment Q_a = sum_{m : band[m] = a} (double)w_m ((double)P_m - s (double)N), s = subtract_noise: float64,
+ *              the product s N, the difference, the product with w_m and the sum each rounded once, no contraction, the sum in
+ *              order of m from 0; a band without modes has Q_a = 0.  An invalid segment has P = N = 0 and gets exactly 0 in every
+ *              band (finite weights) and adds to nothing;
+ *   outputs    bandpower (B S, nseg, nband) float64; stack (S, nz, 1 + nband + nband^2) float64 = [n | sum Q_a | sum Q_a Q_b,
+ *              row-major, full] per draw and z-bin over the valid segments with 0 <= kz < nz; each product Q_a Q_b rounded once;
+ *              entries (a, b) and (b, a) hold the same bits.  The call ADDS to `stack`; QFA_F_ZERO_ACCUM overwrites.  Either
+ *              output may be NULL, not both;
+ *   sums       no float atomics.  The segments of a draw, in order of (b, g) over the whole call, are cut into chunks of
+ *              qfa_p1d_band_chunk_segments() segments -- a constant of the library, not of the grid or the device.  A chunk's sums
+ *              start from 0 and add its segments in order; they leave through the workspace, and a second kernel adds them in
+ *              chunk order onto what `stack` holds.  The host cuts B into launches on chunk boundaries, so the result does not
+ *              depend on the cut: two calls on the same inputs give the same bits, and draw s of a call of S draws gets the bits
+ *              of a call on that draw alone.
+ * qfa_p1d_band_stack_doubles: S nz (1 + nband + nband^2); 0 = unsupported (S < 1, nz outside 1..4096, nband outside 1..64).
+ * qfa_p1d_band_workspace_bytes(R = B S, ...): qfa_p1d_workspace_bytes' shapes, and nband outside 1..64, give 0.  The rows and the
+ * chunk partials of one launch aim at the cap of qfa_p1d_f32's rows; the least a launch holds is the fewest spectra whose segments
+ * fill whole chunks (chunk / gcd(chunk, nseg)).
+ * Returns every code of qfa_p1d_f32 for the arguments they share; QFA_E_NULL also for q, q->band or both outputs missing;
+ * QFA_E_SIZE also for nband outside 1..64 or subtract_noise outside {0, 1}.  Argument checks return before any device work.  B = 0
+ * does nothing, except zeroing `stack` under QFA_F_ZERO_ACCUM.  The call neither synchronises nor allocates. */
+typedef struct {
+    int nband;              /* 1 .. 64 */
+    const int   *band;      /* device (M,) int32 */
+    const float *weight;    /* device (M,) float32, or NULL = all 1 */
+    int subtract_noise;     /* 0 or 1 */
+} qfa_p1d_band_t;
+
+size_t qfa_p1d_band_stack_doubles(int S, int nz, int nband);
+size_t qfa_p1d_band_workspace_bytes(int R, int S, int Nb, int L, int nseg, int nz, int nband);
+int qfa_p1d_band_chunk_segments(void);
+int qfa_p1d_band_f32(const float *trans, const float *ivar, const qfa_batch_t *b, const float *tbar, int B, int S, int Nb,
+                     const qfa_p1d_t *p, const qfa_p1d_band_t *q, unsigned flags, double *bandpower, double *stack,
+                     void *workspace, size_t workspace_bytes, void *stream);
+
 /* Replaces Adam.update (reference QFA/optimizer.py:37-52) followed by the clamp of QFA.clip
  * (QFA/model.py:233-241) for ONE tensor of n elements:
  *   g' = g + wd*p; m = (1-b1) g' + b1 m; v = (1-b2) g'^2 + b2 v;

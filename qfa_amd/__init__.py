@@ -12,6 +12,7 @@ _LAZY = {
     "QFA": ("qfa_amd.model", "QFA"),
     "QFAModel": ("qfa_amd.model", "QFAModel"),
     "P1DStack": ("qfa_amd.model", "P1DStack"),
+    "P1DBandStack": ("qfa_amd.model", "P1DBandStack"),
     "Adam": ("qfa_amd.optimizer", "Adam"),
     "step_scheduler": ("qfa_amd.optimizer", "step_scheduler"),
 }

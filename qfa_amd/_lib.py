@@ -23,6 +23,7 @@ EXPORTS = (
     "qfa_em_floats", "qfa_em_workspace_bytes", "qfa_em_stats_f32", "qfa_em_update_f_f32",
     "qfa_forest_stack_doubles", "qfa_forest_workspace_bytes", "qfa_forest_f32",
     "qfa_p1d_stack_doubles", "qfa_p1d_workspace_bytes", "qfa_p1d_f32",
+    "qfa_p1d_band_stack_doubles", "qfa_p1d_band_workspace_bytes", "qfa_p1d_band_chunk_segments", "qfa_p1d_band_f32",
 )
 
 TAU_IDS = {"becker": 0, "fg": 1, "kamble": 2, "mock": 3}
@@ -69,6 +70,10 @@ class ForestBins(C.Structure):      # qfa_forest_bins_t
 class P1DParams(C.Structure):       # qfa_p1d_t
     _fields_ = [("zT0", C.c_float), ("dzT", C.c_float), ("nT", C.c_int), ("St", C.c_int), ("p_lo", C.c_int), ("seg_len", C.c_int),
                 ("nseg", C.c_int), ("min_used", C.c_int), ("z0", C.c_float), ("dz", C.c_float), ("nz", C.c_int)]
+
+
+class P1DBandParams(C.Structure):   # qfa_p1d_band_t
+    _fields_ = [("nband", C.c_int), ("band", C.c_void_p), ("weight", C.c_void_p), ("subtract_noise", C.c_int)]
 
 
 _lib = None
@@ -139,6 +144,11 @@ def lib():
         "qfa_p1d_stack_doubles": (sz, [i, i, i]),
         "qfa_p1d_workspace_bytes": (sz, [i, i, i, i, i, i]),
         "qfa_p1d_f32": (i, [p, p, C.POINTER(Batch), p, i, i, i, C.POINTER(P1DParams), C.c_uint, p, p, p, p, sz, p]),
+        "qfa_p1d_band_stack_doubles": (sz, [i, i, i]),
+        "qfa_p1d_band_workspace_bytes": (sz, [i, i, i, i, i, i, i]),
+        "qfa_p1d_band_chunk_segments": (i, []),
+        "qfa_p1d_band_f32": (i, [p, p, C.POINTER(Batch), p, i, i, i, C.POINTER(P1DParams), C.POINTER(P1DBandParams), C.c_uint, p, p,
+                                 p, sz, p]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(h, name, None)

@@ -93,6 +93,10 @@ def main(argv=None):
     assert cfg.TYPE in ("train", "predict"), "TYPE must be in ['train', 'predict']!"
     if cfg.TYPE == "predict" and int(cfg.MODEL.P1D_SEGMENTS) > 0 and int(cfg.MODEL.FOREST_NBINS) <= 0:
         raise ValueError("MODEL.P1D_SEGMENTS > 0 needs MODEL.FOREST_NBINS > 0 (the mean transmission the contrast is formed with)")
+    if cfg.TYPE == "predict" and int(cfg.MODEL.P1D_NBANDS) > 0 and int(cfg.MODEL.P1D_SEGMENTS) <= 0:
+        raise ValueError("MODEL.P1D_NBANDS > 0 needs MODEL.P1D_SEGMENTS > 0 (the segments whose power is binned)")
+    if cfg.TYPE == "predict" and not 0 <= int(cfg.MODEL.P1D_NBANDS) <= 64:
+        raise ValueError("MODEL.P1D_NBANDS must lie in 0 .. 64")
     os.makedirs(cfg.DATA.OUTPUT_DIR, exist_ok=True)
     with open(os.path.join(cfg.DATA.OUTPUT_DIR, "config.yaml"), "w") as f:
         f.write(cfg.dump())
@@ -150,6 +154,17 @@ def main(argv=None):
                      z_edges=ps.z_edges.cpu().numpy(), power=ps.power().cpu().numpy(), err=ps.err().cpu().numpy(),
                      power_raw=ps.power_raw.cpu().numpy(), noise=ps.noise.cpu().numpy(), n=ps.n.cpu().numpy(),
                      seg_len=ps.L, dv=ps.dv, sums=ps.buf.cpu().numpy())
+            if int(cfg.MODEL.P1D_NBANDS) > 0:
+                from .model import P1DBandStack
+                bs = model.band_power(dataloader, float(cfg.MODEL.FOREST_ZMIN), float(cfg.MODEL.FOREST_ZMAX), int(cfg.MODEL.P1D_NZBINS),
+                                      P1DBandStack.linear_k_edges(ps.L, ps.dv, int(cfg.MODEL.P1D_NBANDS)),
+                                      n_segments=int(cfg.MODEL.P1D_SEGMENTS), min_used_frac=float(cfg.MODEL.P1D_MIN_USED_FRAC),
+                                      tbar=st, n_samples=int(cfg.MODEL.N_SAMPLES), seed=int(cfg.MODEL.SAMPLE_SEED))
+                out = dict(k_edges=bs.k_edges.cpu().numpy(), k_centers=bs.k_centers.cpu().numpy(), z_edges=bs.z_edges.cpu().numpy(),
+                           n=bs.n.cpu().numpy(), mean=bs.mean.cpu().numpy(), cov=bs.cov.cpu().numpy())
+                if bs.S > 1:
+                    out["cov_over_draws"] = bs.cov_over_draws.cpu().numpy()
+                np.savez(os.path.join(cfg.DATA.OUTPUT_DIR, "flux_power_bands.npz"), **out)
         print(f"Finish predicting {len(dataloader)} spectra in {time.time() - ts} seconds...")
     return 0
 

@@ -62,7 +62,11 @@ DEFAULTS = {                                        # reference QFA/config.py:15
               # 1D flux power spectrum of P1D_SEGMENTS segments of the blue side stacked in P1D_NZBINS bins of [FOREST_ZMIN,
               # FOREST_ZMAX), per posterior draw when N_SAMPLES is set, the contrast formed with the stack of
               # mean_transmission.npz; a segment needs P1D_MIN_USED_FRAC of its pixels used (QFA.flux_power)
-              "P1D_SEGMENTS": 0, "P1D_NZBINS": 4, "P1D_MIN_USED_FRAC": 0.75},
+              "P1D_SEGMENTS": 0, "P1D_NZBINS": 4, "P1D_MIN_USED_FRAC": 0.75,
+              # not in the reference: P1D_NBANDS > 0 (needs P1D_SEGMENTS > 0) also writes flux_power_bands.npz, the power in
+              # P1D_NBANDS equal bands of k from the fundamental to Nyquist and the covariance matrix between the bands per z-bin,
+              # from the scatter of the segments and, when N_SAMPLES is set, over the posterior draws (QFA.band_power)
+              "P1D_NBANDS": 0},
     "TRAIN": {"NEPOCHS": 500, "LEARNING_RATE": 1e-3, "WEIGHT_DECAY": 1e-1, "DECAY_ALPHA": 0.9, "DECAY_STEP": 10,
               "WINDOW_LENGTH_FOR_MU": 16,
               # not in the reference: "em" = F by its closed-form EM update, Adam for the other parameters (QFA.train
@@ -84,7 +88,7 @@ ARG_KEYS = {
 # tests/golden/g12_config.json, extracted from the reference's config.py / main.py)
 EXTRA_KEYS = ("MODEL.REFERENCE_C0_QUIRK", "MODEL.N_SAMPLES", "MODEL.SAMPLE_SEED", "MODEL.N_REPLICATES", "MODEL.EXACT_GRADIENTS",
               "MODEL.FOREST", "MODEL.FOREST_ZMIN", "MODEL.FOREST_ZMAX", "MODEL.FOREST_NBINS", "MODEL.P1D_SEGMENTS",
-              "MODEL.P1D_NZBINS", "MODEL.P1D_MIN_USED_FRAC", "TRAIN.F_UPDATE", "TRAIN.EM_RHO", "TRAIN.EM_RIDGE")
+              "MODEL.P1D_NZBINS", "MODEL.P1D_MIN_USED_FRAC", "MODEL.P1D_NBANDS", "TRAIN.F_UPDATE", "TRAIN.EM_RHO", "TRAIN.EM_RIDGE")
 
 
 def _set(cfg, dotted, value):

@@ -13,6 +13,8 @@ Additions over the reference (none changes a reference call's result):
     redshift-binned stack, per posterior draw, without writing a continuum (include/qfa_hip.h, qfa_forest_f32);
   * ``p1d`` / ``flux_power`` / ``P1DStack`` -- the 1D flux power spectrum of forest segments and its (k, z) stack, per posterior
     draw (include/qfa_hip.h, qfa_p1d_f32);
+  * ``p1d_bands`` / ``band_power`` / ``P1DBandStack`` -- its band powers and the covariance matrix between the bands per draw and
+    z-bin (include/qfa_hip.h, qfa_p1d_band_f32);
   * ``step`` -- forward + Adam + clip without a host sync (what ``train`` and bench.py run);
   * data parallelism: ``enable_data_parallel()`` all-reduces the packed sum/count buffer over
     RCCL once per step before the normalisation (SURVEY.md 8(e));
@@ -290,6 +292,162 @@ class P1DStack(object):
         if other.bins != self.bins or other.S != self.S or other.L != self.L or other.dv != self.dv:
             raise _lib.QFAHipError(f"P1DStack.add_: bins / draws / segments {other.bins}, {other.S}, {other.L} against "
                                    f"{self.bins}, {self.S}, {self.L}")
+        self.buf.add_(other.buf)
+        return self
+
+    def all_reduce(self, group=None):
+        """in-place sum over the process group (every rank calls it; an exhausted rank adds zeros)"""
+        from .distributed import all_reduce_accum
+        all_reduce_accum(self.buf.view(-1), group)
+        return self
+
+
+class P1DBandStack(object):
+    """The stack of band powers of the 1D flux power spectrum and of their outer products (include/qfa_hip.h, qfa_p1d_band_f32):
+    ``buf`` = (S, nz, 1 + nband + nband^2) float64 [n | sum Q_a | sum Q_a Q_b] per draw of the continuum and z-bin -- sums only,
+    which is what data parallelism all-reduces -- over segments of ``L`` pixels ``dv`` km/s wide.  Band a holds the modes with
+    ``k_edges[a] <= k_m < k_edges[a + 1]``, k_m = 2 pi m / (L dv) in s/km; Q_a is the band's mean power of one segment in km/s
+    (``QFA.p1d_bands`` folds dv, 1 / n_a and the window into the weights).  z-bins as ``P1DStack``'s."""
+
+    def __init__(self, buf, z0, dz, nz, L, dv, k_edges):
+        self.z0, self.dz, self.nz = float(np.float32(z0)), float(np.float32(dz)), int(nz)
+        self.L, self.dv = int(L), float(dv)
+        self.M = self.L // 2
+        self._k_edges = tuple(float(x) for x in np.asarray(k_edges, np.float64).reshape(-1))
+        self.nband = len(self._k_edges) - 1
+        if not (1 <= self.nband <= 64 and np.all(np.isfinite(self._k_edges)) and np.all(np.diff(self._k_edges) > 0.0)):
+            raise _lib.QFAHipError(f"P1DBandStack: k_edges must be 2 .. 65 increasing finite wavenumbers, got {len(self._k_edges)}")
+        if buf.dtype != torch.float64 or buf.dim() != 3 or buf.shape[0] < 1 or buf.shape[1] != self.nz \
+                or buf.shape[2] != 1 + self.nband + self.nband ** 2 or not buf.is_contiguous():
+            raise _lib.QFAHipError(f"P1DBandStack: buffer {tuple(buf.shape)} {buf.dtype}, expected contiguous float64 "
+                                   f"(S, {self.nz}, {1 + self.nband + self.nband ** 2})")
+        if not (self.dz > 0.0 and np.isfinite(self.dz) and np.isfinite(self.z0) and 1 <= self.nz <= 4096 and 1 <= self.L <= 4096
+                and self.dv > 0.0 and np.isfinite(self.dv)):
+            raise _lib.QFAHipError(f"P1DBandStack: bins z0 = {z0}, dz = {dz}, nz = {nz}, L = {L}, dv = {dv}")
+        self.buf = buf
+
+    @classmethod
+    def zeros(cls, S, z0, dz, nz, L, dv, k_edges, device):
+        nband = len(np.asarray(k_edges).reshape(-1)) - 1
+        return cls(torch.zeros((int(S), int(nz), 1 + nband + nband * nband), dtype=torch.float64, device=device), z0, dz, nz, L, dv,
+                   k_edges)
+
+    @staticmethod
+    def linear_k_edges(L, dv, nband):
+        """nband + 1 edges of equal bands from the fundamental to Nyquist: mode m sits at m k_1 inside [k_1 / 2, (M + 1 / 2) k_1)"""
+        return 2.0 * np.pi / (int(L) * float(dv)) * np.linspace(0.5, int(L) // 2 + 0.5, int(nband) + 1)
+
+    @property
+    def S(self):
+        return int(self.buf.shape[0])
+
+    @property
+    def bins(self):
+        return (self.z0, self.dz, self.nz)
+
+    @property
+    def z_edges(self):
+        return self.z0 + self.dz * torch.arange(self.nz + 1, dtype=torch.float64, device=self.buf.device)
+
+    @property
+    def z_centers(self):
+        return self.z0 + self.dz * (torch.arange(self.nz, dtype=torch.float64, device=self.buf.device) + 0.5)
+
+    @property
+    def k_edges(self):
+        """(nband + 1,) band edges in s/km"""
+        return torch.tensor(self._k_edges, dtype=torch.float64, device=self.buf.device)
+
+    def band_map(self):
+        """(band, count): the (M,) int32 band of mode m = 1 .. M (entry m - 1; -1 = in no band) and the (nband,) int64 number of
+        modes per band, as numpy arrays"""
+        k = 2.0 * np.pi * np.arange(1, self.M + 1, dtype=np.float64) / (self.L * self.dv)
+        e = np.asarray(self._k_edges, np.float64)
+        a = np.searchsorted(e, k, side="right") - 1
+        band = np.where((a >= 0) & (a < self.nband), a, -1).astype(np.int32)
+        return band, np.bincount(band[band >= 0], minlength=self.nband).astype(np.int64)
+
+    @property
+    def k_centers(self):
+        """(nband,) mean wavenumber of a band's modes in s/km (NaN for a band without modes)"""
+        band, count = self.band_map()
+        k = 2.0 * np.pi * np.arange(1, self.M + 1, dtype=np.float64) / (self.L * self.dv)
+        tot = np.bincount(band[band >= 0], weights=k[band >= 0], minlength=self.nband)
+        with np.errstate(all="ignore"):
+            c = np.where(count > 0, tot / count, np.nan)
+        return torch.tensor(c, dtype=torch.float64, device=self.buf.device)
+
+    @property
+    def n(self):
+        """(S, nz) number of segments stacked"""
+        return self.buf[:, :, 0]
+
+    @property
+    def mean(self):
+        """(S, nz, nband) mean band power of the stacked segments (NaN in an empty bin)"""
+        return self.buf[:, :, 1:1 + self.nband] / self.n[:, :, None]
+
+    @property
+    def cov(self):
+        """(S, nz, nband, nband) covariance of ``mean`` from the scatter of the segments: (<Q Q^T> - <Q> <Q>^T) / (n - 1); NaN
+        where n < 2"""
+        n = self.n[:, :, None, None]
+        m2 = self.buf[:, :, 1 + self.nband:].reshape(self.S, self.nz, self.nband, self.nband) / n
+        mu = self.mean
+        c = (m2 - mu[:, :, :, None] * mu[:, :, None, :]) / (n - 1.0)
+        return torch.where(n > 1.0, c, torch.full_like(c, float("nan")))
+
+    @property
+    def err(self):
+        """(S, nz, nband) standard error of ``mean``: the root of the diagonal of ``cov``"""
+        return torch.sqrt(torch.diagonal(self.cov, dim1=2, dim2=3).clamp_min(0.0))
+
+    @property
+    def corr(self):
+        """(S, nz, nband, nband) correlation matrix of the bands: cov_ab / sqrt(cov_aa cov_bb)"""
+        c = self.cov
+        d = torch.sqrt(torch.diagonal(c, dim1=2, dim2=3).clamp_min(0.0))
+        return c / (d[:, :, :, None] * d[:, :, None, :])
+
+    def _draws(self, what):
+        if self.S < 2:
+            raise _lib.QFAHipError(f"P1DBandStack.{what}: needs more than one draw of the continuum (S = {self.S})")
+        return self.mean
+
+    @property
+    def mean_over_draws(self):
+        """(nz, nband) mean of ``mean`` over the S posterior draws of the continuum"""
+        return self._draws("mean_over_draws").mean(0)
+
+    @property
+    def cov_over_draws(self):
+        """(nz, nband, nband) covariance of ``mean`` over the S draws: the continuum posterior's covariance of the band powers"""
+        d = self._draws("cov_over_draws")
+        d = d - d.mean(0, keepdim=True)
+        return torch.einsum("sza,szb->zab", d, d) / (self.S - 1.0)
+
+    @property
+    def total_cov(self):
+        """(nz, nband, nband) the mean over the draws of ``cov`` plus ``cov_over_draws``"""
+        return self.cov.mean(0) + self.cov_over_draws
+
+    def _like(self, buf):
+        return P1DBandStack(buf, self.z0, self.dz, self.nz, self.L, self.dv, self._k_edges)
+
+    def draws(self, s0, s1):
+        """the stack of draws [s0, s1): a view of the same buffer"""
+        return self._like(self.buf[s0:s1])
+
+    def clone(self):
+        return self._like(self.buf.clone())
+
+    def same_layout(self, other):
+        return isinstance(other, P1DBandStack) and other.bins == self.bins and other.L == self.L and other.dv == self.dv \
+            and other._k_edges == self._k_edges
+
+    def add_(self, other):
+        if not self.same_layout(other) or other.S != self.S:
+            raise _lib.QFAHipError("P1DBandStack.add_: bins / draws / segments / bands differ")
         self.buf.add_(other.buf)
         return self
 
@@ -1003,37 +1161,26 @@ class QFA(object):
     # ------------------------------------------------------------------ 1D flux power spectrum
     P1D_PAIR_BYTES = 1 << 30    # flux_power: the most the (B, S_chunk, Nb) trans / ivar pair of a slice may take
 
-    def p1d(self, trans, ivar, *, zabs=None, zfac=None, batch=None, tbar, tbar_bins=None, seg_len, n_segments, pixel_start=0,
-            min_used, bins=None, stack=None, return_segments=True, dv=1.0):
-        """The 1D flux power spectrum of forest segments and its (k, z) stack (qfa_p1d_f32; the contract is in include/qfa_hip.h).
-        ``trans``, ``ivar`` (B, S, Nb) as ``forest`` returns them; the redshift of the pixels from ``zabs`` (B, Nb), ``zfac`` =
-        (zq1, pix_ratio) or a resident ``batch``.  ``tbar``: the mean transmission the contrast delta_F = T / tbar - 1 is formed
-        with -- a ``ForestStack`` (its ``mean`` per draw: one row per draw when it has S draws, else its single row for every
-        draw) or a (St, nT) / (nT,) tensor over ``tbar_bins`` = (z0, dz, nT).  Segment g holds the ``seg_len`` pixels from
-        ``pixel_start`` + g ``seg_len`` on and is used when at least ``min_used`` of them are.  ``bins`` = (z0, dz, nz) asks for
-        the stack (``dv``: the pixel width in km/s it reports k and P in); ``stack``: a ``P1DStack`` to ADD to.  Returns
-        (power (B, S, n_segments, M), noise (B, S, n_segments), stack): float32 P_m = |delta~_m|^2 / L for m = 1 .. M = seg_len // 2
-        and the noise level, both in pixel units (None with ``return_segments`` False), and the ``P1DStack`` (or None)."""
+    def _p1d_inputs(self, what, trans, ivar, zabs, zfac, batch, tbar, tbar_bins):
+        """the checks and conversions `p1d` and `p1d_bands` share: (B, S, tbar (St, nT) float32, St, tbar_bins, qfa_batch_t, the
+        tensors it points into)"""
         dev = self.device
         if not isinstance(trans, torch.Tensor) or trans.dim() != 3 or trans.shape[2] != self.Nb or tuple(ivar.shape) != tuple(trans.shape):
-            raise _lib.QFAHipError(f"p1d: trans / ivar must be (B, S, {self.Nb}) tensors")
+            raise _lib.QFAHipError(f"{what}: trans / ivar must be (B, S, {self.Nb}) tensors")
         B, S = int(trans.shape[0]), int(trans.shape[1])
-        L, nseg, p_lo = int(seg_len), int(n_segments), int(pixel_start)
-        if bins is None and stack is None and not return_segments:
-            raise _lib.QFAHipError("p1d: nothing asked for (no bins, no stack, return_segments = False)")
         if isinstance(tbar, ForestStack):
             if tbar.S not in (1, S):
-                raise _lib.QFAHipError(f"p1d: tbar has {tbar.S} draws, expected 1 or {S}")
+                raise _lib.QFAHipError(f"{what}: tbar has {tbar.S} draws, expected 1 or {S}")
             tbar_bins, tbar = tbar.bins, tbar.mean
         if tbar_bins is None:
-            raise _lib.QFAHipError("p1d: a tbar tensor needs tbar_bins = (z0, dz, nT)")
+            raise _lib.QFAHipError(what + ": a tbar tensor needs tbar_bins = (z0, dz, nT)")
         tbar = tbar.to(device=dev, dtype=f32).reshape(-1, int(tbar_bins[2])).contiguous()
         St = int(tbar.shape[0])
         if St not in (1, S):
-            raise _lib.QFAHipError(f"p1d: tbar has {St} rows, expected 1 or {S}")
+            raise _lib.QFAHipError(f"{what}: tbar has {St} rows, expected 1 or {S}")
         if batch is not None:
             if batch.B != B:
-                raise _lib.QFAHipError(f"p1d: resident batch of {batch.B} spectra, trans has {B}")
+                raise _lib.QFAHipError(f"{what}: resident batch of {batch.B} spectra, trans has {B}")
             bs, keep = self._batch_struct_rows(batch, need_src=False)
         else:
             bs, keep = _lib.Batch(), []
@@ -1059,7 +1206,25 @@ class QFA(object):
                 bs.zq1 = _lib.require_device_tensor(zq1, f32, "zq1").value
                 bs.pix_ratio = _lib.require_device_tensor(ratio, f32, "pix_ratio").value
             else:
-                raise _lib.QFAHipError("p1d: pass zabs, zfac = (zq1, pix_ratio) or batch")
+                raise _lib.QFAHipError(what + ": pass zabs, zfac = (zq1, pix_ratio) or batch")
+        return B, S, tbar, St, tbar_bins, bs, keep
+
+    def p1d(self, trans, ivar, *, zabs=None, zfac=None, batch=None, tbar, tbar_bins=None, seg_len, n_segments, pixel_start=0,
+            min_used, bins=None, stack=None, return_segments=True, dv=1.0):
+        """The 1D flux power spectrum of forest segments and its (k, z) stack (qfa_p1d_f32; the contract is in include/qfa_hip.h).
+        ``trans``, ``ivar`` (B, S, Nb) as ``forest`` returns them; the redshift of the pixels from ``zabs`` (B, Nb), ``zfac`` =
+        (zq1, pix_ratio) or a resident ``batch``.  ``tbar``: the mean transmission the contrast delta_F = T / tbar - 1 is formed
+        with -- a ``ForestStack`` (its ``mean`` per draw: one row per draw when it has S draws, else its single row for every
+        draw) or a (St, nT) / (nT,) tensor over ``tbar_bins`` = (z0, dz, nT).  Segment g holds the ``seg_len`` pixels from
+        ``pixel_start`` + g ``seg_len`` on and is used when at least ``min_used`` of them are.  ``bins`` = (z0, dz, nz) asks for
+        the stack (``dv``: the pixel width in km/s it reports k and P in); ``stack``: a ``P1DStack`` to ADD to.  Returns
+        (power (B, S, n_segments, M), noise (B, S, n_segments), stack): float32 P_m = |delta~_m|^2 / L for m = 1 .. M = seg_len // 2
+        and the noise level, both in pixel units (None with ``return_segments`` False), and the ``P1DStack`` (or None)."""
+        dev = self.device
+        if bins is None and stack is None and not return_segments:
+            raise _lib.QFAHipError("p1d: nothing asked for (no bins, no stack, return_segments = False)")
+        B, S, tbar, St, tbar_bins, bs, keep = self._p1d_inputs("p1d", trans, ivar, zabs, zfac, batch, tbar, tbar_bins)
+        L, nseg, p_lo = int(seg_len), int(n_segments), int(pixel_start)
         if stack is not None:
             if not isinstance(stack, P1DStack) or stack.S != S or stack.L != L or \
                     (bins is not None and P1DStack(stack.buf, bins[0], bins[1], bins[2], L).bins != stack.bins):
@@ -1090,6 +1255,78 @@ class QFA(object):
             C.c_void_p(ws.data_ptr()), ws.numel(), _lib.current_stream(dev)), "qfa_p1d_f32")
         return power, noise, stack
 
+    def _p1d_band_tables(self, L, dv, k_edges, resolution_kms):
+        """(band (M,) int32, weight (M,) float32) of qfa_p1d_band_t on the device, built once per (L, dv, k_edges, resolution):
+        weight_m = dv / (n_a W^2(k_m)) with n_a the number of modes of the band of mode m and W^2 = ``P1DStack.window2`` (1 without
+        a resolution), so that Q_a is the mean over the band's modes of the P1D in km/s"""
+        key = (int(L), float(dv), tuple(float(x) for x in np.asarray(k_edges, np.float64).reshape(-1)),
+               None if resolution_kms is None else float(resolution_kms))
+        cache = self.__dict__.setdefault("_p1d_band_cache", {})
+        if key not in cache:
+            ref = P1DBandStack(torch.zeros((1, 1, 1 + (len(key[2]) - 1) + (len(key[2]) - 1) ** 2), dtype=torch.float64), 0.0, 1.0, 1,
+                               L, dv, key[2])
+            band, count = ref.band_map()
+            w = np.full(ref.M, float(dv), np.float64) / np.maximum(count[np.maximum(band, 0)], 1)
+            if resolution_kms is not None:
+                k = 2.0 * np.pi * np.arange(1, ref.M + 1, dtype=np.float64) / (ref.L * ref.dv)
+                w = w / (np.sinc(k * ref.dv / (2.0 * np.pi)) * np.exp(-0.5 * (k * float(resolution_kms)) ** 2)) ** 2
+            w = np.where(band >= 0, w, 0.0).astype(np.float32)
+            if len(cache) >= 16:
+                cache.clear()
+            # (one entry more than the modes: a pointer to an empty tensor would be NULL at L = 1)
+            cache[key] = (torch.tensor(np.append(band, np.int32(-1)), device=self.device),
+                          torch.tensor(np.append(w, np.float32(0.0)), device=self.device))
+        return cache[key]
+
+    def p1d_bands(self, trans, ivar, *, zabs=None, zfac=None, batch=None, tbar, tbar_bins=None, seg_len, n_segments, pixel_start=0,
+                  min_used, bins=None, dv=1.0, k_edges, resolution_kms=None, subtract_noise=True, stack=None,
+                  return_segments=False):
+        """Band powers of the forest's P1D and the stack their covariance matrix comes from (qfa_p1d_band_f32; the contract is in
+        include/qfa_hip.h).  The inputs and keywords of ``p1d``; ``k_edges``: nband + 1 increasing band edges in s/km -- band a
+        holds the modes with k_edges[a] <= 2 pi m / (seg_len dv) < k_edges[a + 1].  Q_a of a segment is the mean over the band's
+        modes of (P_m - N) dv / W^2(k_m): ``subtract_noise`` False keeps the noise in, ``resolution_kms`` divides by
+        ``P1DStack.window2``.  ``bins`` = (z0, dz, nz) asks for the stack, ``stack``: a ``P1DBandStack`` to ADD to.  Returns
+        (bandpower (B, S, n_segments, nband) float64, or None without ``return_segments``; the ``P1DBandStack``, or None)."""
+        dev = self.device
+        if bins is None and stack is None and not return_segments:
+            raise _lib.QFAHipError("p1d_bands: nothing asked for (no bins, no stack, return_segments = False)")
+        B, S, tbar, St, tbar_bins, bs, keep = self._p1d_inputs("p1d_bands", trans, ivar, zabs, zfac, batch, tbar, tbar_bins)
+        L, nseg, p_lo = int(seg_len), int(n_segments), int(pixel_start)
+        if stack is not None:
+            want = P1DBandStack(stack.buf, *(bins if bins is not None else stack.bins), L, stack.dv, k_edges) \
+                if isinstance(stack, P1DBandStack) else None
+            if want is None or stack.S != S or not stack.same_layout(want):
+                raise _lib.QFAHipError(f"p1d_bands(stack=...): expected a P1DBandStack of {S} draws and segments of {L} pixels on the "
+                                       "same bins and bands")
+            _lib.require_device_tensor(stack.buf, torch.float64, "stack")
+            dv = stack.dv
+        elif bins is not None:
+            stack = P1DBandStack.zeros(S, bins[0], bins[1], bins[2], L, dv, k_edges, dev)
+        nband = len(np.asarray(k_edges).reshape(-1)) - 1
+        band, weight = self._p1d_band_tables(L, dv, k_edges, resolution_kms)
+        pp = _lib.P1DParams()
+        pp.zT0, pp.dzT, pp.nT, pp.St = float(np.float32(tbar_bins[0])), float(np.float32(tbar_bins[1])), int(tbar_bins[2]), St
+        pp.p_lo, pp.seg_len, pp.nseg, pp.min_used = p_lo, L, nseg, int(min_used)
+        pp.z0, pp.dz, pp.nz = (stack.z0, stack.dz, stack.nz) if stack is not None else (0.0, 1.0, 1)
+        qq = _lib.P1DBandParams()
+        qq.nband, qq.band, qq.weight, qq.subtract_noise = nband, band.data_ptr(), weight.data_ptr(), 1 if subtract_noise else 0
+        need = _lib.lib().qfa_p1d_band_workspace_bytes(B * S, S, self.Nb, L, nseg, int(pp.nz), nband) if L >= 1 and nseg >= 1 else 0
+        if need == 0:
+            raise _lib.QFAHipError(f"p1d_bands: unsupported shape B={B} S={S} Nb={self.Nb} seg_len={L} n_segments={nseg} nz={pp.nz} "
+                                   f"nband={nband}")
+        ws = self._ws.get("p1d_ws")                               # (shared with p1d: both calls own it only while they run)
+        if ws is None or ws.numel() < need:
+            ws = torch.empty(need, dtype=torch.uint8, device=dev)
+            self._ws["p1d_ws"] = ws
+        bandpower = torch.empty((B, S, nseg, nband), dtype=torch.float64, device=dev) if return_segments else None
+        _lib.check(_lib.lib().qfa_p1d_band_f32(
+            _lib.require_device_tensor(trans, f32, "trans"), _lib.require_device_tensor(ivar, f32, "ivar"), C.byref(bs),
+            C.c_void_p(tbar.data_ptr()), B, S, self.Nb, C.byref(pp), C.byref(qq), 0,
+            C.c_void_p(bandpower.data_ptr()) if bandpower is not None else None,
+            C.c_void_p(stack.buf.data_ptr()) if stack is not None else None,
+            C.c_void_p(ws.data_ptr()), ws.numel(), _lib.current_stream(dev)), "qfa_p1d_band_f32")
+        return bandpower, stack
+
     def flux_power(self, dataloader, z_min, z_max, n_zbins, *, n_segments=3, seg_len=None, min_used_frac=0.75, tbar=None,
                    tbar_nbins=64, n_samples=0, seed=0, batch_size=4096, cont_min=0.0, dv=None):
         """The 1D flux power spectrum of a whole dataloader: a ``P1DStack`` of S = max(1, n_samples) draws over ``n_zbins`` bins of
@@ -1102,15 +1339,34 @@ class QFA(object):
         c ln(lambda_1 / lambda_0) of the loader's ``wav_grid``.  The global row of a spectrum is its dataloader index and the
         reducer adds segments in order, so the result does not depend on ``batch_size`` beyond the rounding of float64 sums.
         Under data parallelism the sums are all-reduced over the model's group: every rank returns the global stack."""
+        return self._power_of_loader("flux_power", dataloader, z_min, z_max, n_zbins, n_segments, seg_len, min_used_frac, tbar,
+                                     tbar_nbins, n_samples, seed, batch_size, cont_min, dv, None)
+
+    def band_power(self, dataloader, z_min, z_max, n_zbins, k_edges, *, n_segments=3, seg_len=None, min_used_frac=0.75, tbar=None,
+                   tbar_nbins=64, n_samples=0, seed=0, batch_size=4096, cont_min=0.0, dv=None, resolution_kms=None,
+                   subtract_noise=True):
+        """The band powers of a whole dataloader and their covariance: a ``P1DBandStack`` of S = max(1, n_samples) draws over
+        ``n_zbins`` bins of [z_min, z_max) and the bands ``k_edges`` (nband + 1 edges in s/km).  Everything else is
+        ``flux_power``'s: the same segments, mean transmission, draws and loop over the loader, with ``p1d_bands`` in the place of
+        ``p1d``.  The sums of a slice are formed in chunks of a fixed number of segments, so the result depends on ``batch_size``
+        only through the rounding of float64 sums.  Under data parallelism the sums are all-reduced over the model's group."""
+        return self._power_of_loader("band_power", dataloader, z_min, z_max, n_zbins, n_segments, seg_len, min_used_frac, tbar,
+                                     tbar_nbins, n_samples, seed, batch_size, cont_min, dv,
+                                     {"k_edges": k_edges, "resolution_kms": resolution_kms, "subtract_noise": subtract_noise})
+
+    def _power_of_loader(self, what, dataloader, z_min, z_max, n_zbins, n_segments, seg_len, min_used_frac, tbar, tbar_nbins,
+                         n_samples, seed, batch_size, cont_min, dv, bands):
+        """the loop `flux_power` (``bands`` None: a ``P1DStack`` through ``p1d``) and `band_power` (``bands``: the keywords of
+        ``p1d_bands``; a ``P1DBandStack``) share"""
         nseg, nz, S = int(n_segments), int(n_zbins), max(1, int(n_samples))
         L = int(seg_len) if seg_len is not None else (self.Nb // nseg if nseg > 0 else 0)
         if nseg < 1 or L < 1 or nseg * L > self.Nb or nz < 1 or not float(z_max) > float(z_min) or not 0.0 < float(min_used_frac) <= 1.0:
-            raise _lib.QFAHipError(f"flux_power: {nseg} segments of {L} pixels on Nb = {self.Nb}, bins [{z_min}, {z_max}) / {nz}, "
+            raise _lib.QFAHipError(f"{what}: {nseg} segments of {L} pixels on Nb = {self.Nb}, bins [{z_min}, {z_max}) / {nz}, "
                                    f"min_used_frac = {min_used_frac}")
         if dv is None:
             wav = getattr(dataloader, "wav_grid", None)
             if wav is None or len(wav) < 2:
-                raise _lib.QFAHipError("flux_power: the dataloader has no wav_grid: pass dv (km/s per pixel)")
+                raise _lib.QFAHipError(what + ": the dataloader has no wav_grid: pass dv (km/s per pixel)")
             dv = 299792.458 * float(np.log(float(wav[1]) / float(wav[0])))
         min_used = max(1, int(np.ceil(float(min_used_frac) * L)))
         if tbar is None:
@@ -1119,9 +1375,12 @@ class QFA(object):
                                           int(tbar_nbins), n_samples=int(n_samples), seed=seed, batch_size=batch_size,
                                           cont_min=cont_min)
         if not isinstance(tbar, ForestStack) or tbar.S not in (1, S):
-            raise _lib.QFAHipError(f"flux_power: tbar must be a ForestStack of 1 or {S} draws")
+            raise _lib.QFAHipError(f"{what}: tbar must be a ForestStack of 1 or {S} draws")
         tmean = tbar.mean.to(f32)
-        stack = P1DStack.zeros(S, z_min, (float(z_max) - float(z_min)) / nz, nz, L, dv, self.device)
+        if bands is None:
+            stack = P1DStack.zeros(S, z_min, (float(z_max) - float(z_min)) / nz, nz, L, dv, self.device)
+        else:
+            stack = P1DBandStack.zeros(S, z_min, (float(z_max) - float(z_min)) / nz, nz, L, dv, bands["k_edges"], self.device)
         row0 = int(getattr(dataloader, "_row0", 0))              # (a data-parallel loader: the global index of its first row)
         for s, inputs, _ in self._loader_slices(dataloader, int(batch_size)):
             _, hmean, hcov, _, unc = self.predict(**inputs)
@@ -1136,8 +1395,12 @@ class QFA(object):
                 s1 = min(S, s0 + Sc)
                 hs = h if (s0 == 0 and s1 == S) else h[:, s0:s1].contiguous()
                 tr, iv, _ = self.forest(**inputs, h=hs, unc=unc, cont_min=cont_min)
-                self.p1d(tr, iv, **zin, tbar=tmean if tbar.S == 1 else tmean[s0:s1], tbar_bins=tbar.bins, seg_len=L,
-                         n_segments=nseg, min_used=min_used, stack=stack.draws(s0, s1), return_segments=False)
+                kw = dict(tbar=tmean if tbar.S == 1 else tmean[s0:s1], tbar_bins=tbar.bins, seg_len=L, n_segments=nseg,
+                          min_used=min_used, stack=stack.draws(s0, s1), return_segments=False)
+                if bands is None:
+                    self.p1d(tr, iv, **zin, **kw)
+                else:
+                    self.p1d_bands(tr, iv, **zin, **kw, **bands)
         if self._dp:
             stack.all_reduce(self._dp_group)
         return stack
