@@ -11,6 +11,7 @@ __version__ = "0.1.0"
 _LAZY = {
     "QFA": ("qfa_amd.model", "QFA"),
     "QFAModel": ("qfa_amd.model", "QFAModel"),
+    "ForestStack": ("qfa_amd.model", "ForestStack"),
     "P1DStack": ("qfa_amd.model", "P1DStack"),
     "P1DBandStack": ("qfa_amd.model", "P1DBandStack"),
     "Adam": ("qfa_amd.optimizer", "Adam"),

@@ -193,6 +193,11 @@ def require_device_tensor(t, dtype, name):
     return C.c_void_p(t.data_ptr())
 
 
+def _ptr(t):
+    """raw pointer of a tensor the caller has checked, NULL for None"""
+    return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
 def current_stream(device):
     import torch
     return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)

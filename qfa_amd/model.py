@@ -9,11 +9,12 @@ Additions over the reference (none changes a reference call's result):
   * ``predict`` -- batched ``prediction_for_single_spectra``;
   * ``sample_latent`` / ``continua_from_latent`` / ``sample_continua`` -- posterior draws on the device (include/qfa_hip.h);
   * ``sample_spectra`` / ``posterior_predictive`` -- mock spectra and posterior-predictive replicates drawn from the model;
-  * ``forest`` / ``mean_transmission`` / ``ForestStack`` -- Lyman-alpha forest transmission flux / continuum and its
+  * the forest statistics, methods of the base class ``ForestStatistics`` (statistics.py) with their result classes in stacks.py:
+    ``forest`` / ``mean_transmission`` / ``ForestStack`` -- Lyman-alpha forest transmission flux / continuum and its
     redshift-binned stack, per posterior draw, without writing a continuum (include/qfa_hip.h, qfa_forest_f32);
-  * ``p1d`` / ``flux_power`` / ``P1DStack`` -- the 1D flux power spectrum of forest segments and its (k, z) stack, per posterior
+    ``p1d`` / ``flux_power`` / ``P1DStack`` -- the 1D flux power spectrum of forest segments and its (k, z) stack, per posterior
     draw (include/qfa_hip.h, qfa_p1d_f32);
-  * ``p1d_bands`` / ``band_power`` / ``P1DBandStack`` -- its band powers and the covariance matrix between the bands per draw and
+    ``p1d_bands`` / ``band_power`` / ``P1DBandStack`` -- its band powers and the covariance matrix between the bands per draw and
     z-bin (include/qfa_hip.h, qfa_p1d_band_f32);
   * ``step`` -- forward + Adam + clip without a host sync (what ``train`` and bench.py run);
   * data parallelism: ``enable_data_parallel()`` all-reduces the packed sum/count buffer over
@@ -35,6 +36,8 @@ import torch
 
 from . import _lib
 from . import utils as _utils
+from .stacks import EMStats, ForestStack, P1DBandStack, P1DStack    # (re-exported)
+from .statistics import ForestStatistics
 
 f32 = torch.float32
 log2pi = 1.8378770664093453
@@ -66,399 +69,7 @@ def _resolve_tau(tau):
     raise TypeError("tau must be a name, qfa_amd.utils.tau (partial) or a callable")
 
 
-class EMStats(object):
-    """The packed sufficient statistics of the closed-form update of F (include/qfa_hip.h, qfa_em_floats):
-    ``buf`` = [S2 (Npix, Nh, Nh) | S1 (Npix, Nh) | cnt (Npix,) | sum NLL, n_spectra, 0, 0] -- sums only, which is what data
-    parallelism all-reduces.  ``S2``, ``S1``, ``cnt`` are views of ``buf``; ``loss`` is the (1, 1) mean NLL."""
-
-    def __init__(self, buf, Npix, Nh):
-        self.buf, self.Npix, self.Nh = buf, int(Npix), int(Nh)
-        n2, n1 = self.Npix * self.Nh * self.Nh, self.Npix * self.Nh
-        if buf.numel() != n2 + n1 + self.Npix + 4:
-            raise _lib.QFAHipError(f"EMStats: {buf.numel()} floats, expected {n2 + n1 + self.Npix + 4}")
-        self.S2 = buf[:n2].view(self.Npix, self.Nh, self.Nh)
-        self.S1 = buf[n2:n2 + n1].view(self.Npix, self.Nh)
-        self.cnt = buf[n2 + n1:n2 + n1 + self.Npix]
-        self.tail = buf[n2 + n1 + self.Npix:]
-
-    @property
-    def loss(self):
-        return (self.tail[0] / self.tail[1]).reshape(1, 1)
-
-    def clone(self):
-        return EMStats(self.buf.clone(), self.Npix, self.Nh)
-
-    def blend_(self, other, rho):
-        """self <- (1 - rho) self + rho other, in place (stochastic EM on mini-batches); rho = 1 is replacement, bit for bit."""
-        rho = float(rho)
-        if rho == 1.0:
-            self.buf.copy_(other.buf)
-        else:
-            self.buf.mul_(1.0 - rho).add_(other.buf, alpha=rho)
-        return self
-
-
-class ForestStack(object):
-    """The redshift-binned stack of the forest transmission (include/qfa_hip.h, qfa_forest_f32): ``buf`` = (S, 4, nbin) float64
-    [sum w | sum w T | sum w T^2 | n] per draw of the continuum -- sums only, which is what data parallelism all-reduces --
-    over the bins [z0 + k dz, z0 + (k + 1) dz), z0 and dz as the float32 numbers the kernel bins with."""
-
-    def __init__(self, buf, z0, dz, nbin):
-        self.z0, self.dz, self.nbin = float(np.float32(z0)), float(np.float32(dz)), int(nbin)
-        if buf.dtype != torch.float64 or buf.dim() != 3 or buf.shape[1] != 4 or buf.shape[2] != self.nbin or buf.shape[0] < 1 \
-                or not buf.is_contiguous():
-            raise _lib.QFAHipError(f"ForestStack: buffer {tuple(buf.shape)} {buf.dtype}, expected contiguous float64 (S, 4, {self.nbin})")
-        if not (self.dz > 0.0 and np.isfinite(self.dz) and np.isfinite(self.z0) and 1 <= self.nbin <= 4096):
-            raise _lib.QFAHipError(f"ForestStack: bins z0 = {z0}, dz = {dz}, nbin = {nbin}")
-        self.buf = buf
-
-    @classmethod
-    def zeros(cls, S, z0, dz, nbin, device):
-        return cls(torch.zeros((int(S), 4, int(nbin)), dtype=torch.float64, device=device), z0, dz, nbin)
-
-    @property
-    def S(self):
-        return int(self.buf.shape[0])
-
-    @property
-    def bins(self):
-        return (self.z0, self.dz, self.nbin)
-
-    @property
-    def z_edges(self):
-        return self.z0 + self.dz * torch.arange(self.nbin + 1, dtype=torch.float64, device=self.buf.device)
-
-    @property
-    def z_centers(self):
-        return self.z0 + self.dz * (torch.arange(self.nbin, dtype=torch.float64, device=self.buf.device) + 0.5)
-
-    @property
-    def sum_w(self):
-        return self.buf[:, 0]
-
-    @property
-    def n(self):
-        """(S, nbin) number of pixels stacked"""
-        return self.buf[:, 3]
-
-    @property
-    def mean(self):
-        """(S, nbin) weighted mean transmission sum w T / sum w (NaN in an empty bin)"""
-        return self.buf[:, 1] / self.buf[:, 0]
-
-    @property
-    def var(self):
-        """(S, nbin) weighted variance of T inside the bin, sum w T^2 / sum w - mean^2"""
-        m = self.mean
-        return self.buf[:, 2] / self.buf[:, 0] - m * m
-
-    @property
-    def tau_eff(self):
-        """(S, nbin) effective optical depth -ln <T>"""
-        return -torch.log(self.mean)
-
-    def _draws(self, what):
-        if self.S < 2:
-            raise _lib.QFAHipError(f"ForestStack.{what}: needs more than one draw of the continuum (S = {self.S})")
-        return self.mean
-
-    @property
-    def mean_over_draws(self):
-        """(nbin,) mean of ``mean`` over the S posterior draws of the continuum"""
-        return self._draws("mean_over_draws").mean(0)
-
-    @property
-    def std_over_draws(self):
-        """(nbin,) standard deviation of ``mean`` over the S draws: the continuum posterior's error bar on the stack (the
-        continuum errors of a spectrum's pixels are correlated, which repeating the whole stack per draw carries through)"""
-        return self._draws("std_over_draws").std(0, unbiased=True)
-
-    def clone(self):
-        return ForestStack(self.buf.clone(), self.z0, self.dz, self.nbin)
-
-    def add_(self, other):
-        if other.bins != self.bins or other.S != self.S:
-            raise _lib.QFAHipError(f"ForestStack.add_: bins / draws {other.bins}, {other.S} against {self.bins}, {self.S}")
-        self.buf.add_(other.buf)
-        return self
-
-    def all_reduce(self, group=None):
-        """in-place sum over the process group (every rank calls it; an exhausted rank adds zeros)"""
-        from .distributed import all_reduce_accum
-        all_reduce_accum(self.buf.view(-1), group)
-        return self
-
-
-class P1DStack(object):
-    """The (k, z) stack of the 1D flux power spectrum (include/qfa_hip.h, qfa_p1d_f32): ``buf`` = (S, nz, 2 + 2M) float64
-    [n | sum N | sum P_1..M | sum P^2_1..M] per draw of the continuum and z-bin -- sums only, which is what data parallelism
-    all-reduces -- over segments of ``L`` pixels ``dv`` km/s wide, M = L // 2 modes k_m = 2 pi m / (L dv); z-bins
-    [z0 + i dz, z0 + (i + 1) dz), z0 and dz as the float32 numbers the kernel bins with."""
-
-    def __init__(self, buf, z0, dz, nz, L, dv=1.0):
-        self.z0, self.dz, self.nz = float(np.float32(z0)), float(np.float32(dz)), int(nz)
-        self.L, self.dv = int(L), float(dv)
-        self.M = self.L // 2
-        if buf.dtype != torch.float64 or buf.dim() != 3 or buf.shape[0] < 1 or buf.shape[1] != self.nz \
-                or buf.shape[2] != 2 + 2 * self.M or not buf.is_contiguous():
-            raise _lib.QFAHipError(f"P1DStack: buffer {tuple(buf.shape)} {buf.dtype}, expected contiguous float64 "
-                                   f"(S, {self.nz}, {2 + 2 * self.M})")
-        if not (self.dz > 0.0 and np.isfinite(self.dz) and np.isfinite(self.z0) and 1 <= self.nz <= 4096 and 1 <= self.L <= 4096
-                and self.dv > 0.0 and np.isfinite(self.dv)):
-            raise _lib.QFAHipError(f"P1DStack: bins z0 = {z0}, dz = {dz}, nz = {nz}, L = {L}, dv = {dv}")
-        self.buf = buf
-
-    @classmethod
-    def zeros(cls, S, z0, dz, nz, L, dv, device):
-        return cls(torch.zeros((int(S), int(nz), 2 + 2 * (int(L) // 2)), dtype=torch.float64, device=device), z0, dz, nz, L, dv)
-
-    @property
-    def S(self):
-        return int(self.buf.shape[0])
-
-    @property
-    def bins(self):
-        return (self.z0, self.dz, self.nz)
-
-    @property
-    def z_edges(self):
-        return self.z0 + self.dz * torch.arange(self.nz + 1, dtype=torch.float64, device=self.buf.device)
-
-    @property
-    def z_centers(self):
-        return self.z0 + self.dz * (torch.arange(self.nz, dtype=torch.float64, device=self.buf.device) + 0.5)
-
-    @property
-    def k(self):
-        """(M,) wavenumbers 2 pi m / (L dv), m = 1 .. M, in s/km"""
-        return 2.0 * np.pi * torch.arange(1, self.M + 1, dtype=torch.float64, device=self.buf.device) / (self.L * self.dv)
-
-    @property
-    def n(self):
-        """(S, nz) number of segments stacked"""
-        return self.buf[:, :, 0]
-
-    @property
-    def noise(self):
-        """(S, nz) mean noise level <N> of the stacked segments, in pixel units (NaN in an empty bin)"""
-        return self.buf[:, :, 1] / self.n
-
-    @property
-    def power_raw(self):
-        """(S, nz, M) mean |delta~_m|^2 / L of the stacked segments, in pixel units, noise included"""
-        return self.buf[:, :, 2:2 + self.M] / self.n[:, :, None]
-
-    def window2(self, resolution_kms):
-        """(M,) W^2(k): the pixel's sinc times a Gaussian of ``resolution_kms`` (1 sigma), squared"""
-        k = self.k
-        return (torch.sinc(k * self.dv / (2.0 * np.pi)) * torch.exp(-0.5 * (k * float(resolution_kms)) ** 2)) ** 2
-
-    def power(self, resolution_kms=None):
-        """(S, nz, M) P1D in km/s: (power_raw - noise) dv, divided by ``window2(resolution_kms)`` when that is given"""
-        P = (self.power_raw - self.noise[:, :, None]) * self.dv
-        return P if resolution_kms is None else P / self.window2(resolution_kms)
-
-    def err(self, resolution_kms=None):
-        """(S, nz, M) standard error of ``power`` from the scatter of the segments: sqrt((<P^2> - <P>^2) / (n - 1)) dv"""
-        m2 = self.buf[:, :, 2 + self.M:] / self.n[:, :, None]
-        var = (m2 - self.power_raw ** 2).clamp_min(0.0) / (self.n[:, :, None] - 1.0)
-        e = torch.sqrt(var) * self.dv
-        e = torch.where(self.n[:, :, None] > 1.0, e, torch.full_like(e, float("nan")))
-        return e if resolution_kms is None else e / self.window2(resolution_kms)
-
-    def _draws(self, what):
-        if self.S < 2:
-            raise _lib.QFAHipError(f"P1DStack.{what}: needs more than one draw of the continuum (S = {self.S})")
-        return self.power()
-
-    @property
-    def mean_over_draws(self):
-        """(nz, M) mean of ``power()`` over the S posterior draws of the continuum"""
-        return self._draws("mean_over_draws").mean(0)
-
-    @property
-    def std_over_draws(self):
-        """(nz, M) standard deviation of ``power()`` over the S draws: the continuum posterior's error bar on P1D"""
-        return self._draws("std_over_draws").std(0, unbiased=True)
-
-    def draws(self, s0, s1):
-        """the stack of draws [s0, s1): a view of the same buffer"""
-        return P1DStack(self.buf[s0:s1], self.z0, self.dz, self.nz, self.L, self.dv)
-
-    def clone(self):
-        return P1DStack(self.buf.clone(), self.z0, self.dz, self.nz, self.L, self.dv)
-
-    def add_(self, other):
-        if other.bins != self.bins or other.S != self.S or other.L != self.L or other.dv != self.dv:
-            raise _lib.QFAHipError(f"P1DStack.add_: bins / draws / segments {other.bins}, {other.S}, {other.L} against "
-                                   f"{self.bins}, {self.S}, {self.L}")
-        self.buf.add_(other.buf)
-        return self
-
-    def all_reduce(self, group=None):
-        """in-place sum over the process group (every rank calls it; an exhausted rank adds zeros)"""
-        from .distributed import all_reduce_accum
-        all_reduce_accum(self.buf.view(-1), group)
-        return self
-
-
-class P1DBandStack(object):
-    """The stack of band powers of the 1D flux power spectrum and of their outer products (include/qfa_hip.h, qfa_p1d_band_f32):
-    ``buf`` = (S, nz, 1 + nband + nband^2) float64 [n | sum Q_a | sum Q_a Q_b] per draw of the continuum and z-bin -- sums only,
-    which is what data parallelism all-reduces -- over segments of ``L`` pixels ``dv`` km/s wide.  Band a holds the modes with
-    ``k_edges[a] <= k_m < k_edges[a + 1]``, k_m = 2 pi m / (L dv) in s/km; Q_a is the band's mean power of one segment in km/s
-    (``QFA.p1d_bands`` folds dv, 1 / n_a and the window into the weights).  z-bins as ``P1DStack``'s."""
-
-    def __init__(self, buf, z0, dz, nz, L, dv, k_edges):
-        self.z0, self.dz, self.nz = float(np.float32(z0)), float(np.float32(dz)), int(nz)
-        self.L, self.dv = int(L), float(dv)
-        self.M = self.L // 2
-        self._k_edges = tuple(float(x) for x in np.asarray(k_edges, np.float64).reshape(-1))
-        self.nband = len(self._k_edges) - 1
-        if not (1 <= self.nband <= 64 and np.all(np.isfinite(self._k_edges)) and np.all(np.diff(self._k_edges) > 0.0)):
-            raise _lib.QFAHipError(f"P1DBandStack: k_edges must be 2 .. 65 increasing finite wavenumbers, got {len(self._k_edges)}")
-        if buf.dtype != torch.float64 or buf.dim() != 3 or buf.shape[0] < 1 or buf.shape[1] != self.nz \
-                or buf.shape[2] != 1 + self.nband + self.nband ** 2 or not buf.is_contiguous():
-            raise _lib.QFAHipError(f"P1DBandStack: buffer {tuple(buf.shape)} {buf.dtype}, expected contiguous float64 "
-                                   f"(S, {self.nz}, {1 + self.nband + self.nband ** 2})")
-        if not (self.dz > 0.0 and np.isfinite(self.dz) and np.isfinite(self.z0) and 1 <= self.nz <= 4096 and 1 <= self.L <= 4096
-                and self.dv > 0.0 and np.isfinite(self.dv)):
-            raise _lib.QFAHipError(f"P1DBandStack: bins z0 = {z0}, dz = {dz}, nz = {nz}, L = {L}, dv = {dv}")
-        self.buf = buf
-
-    @classmethod
-    def zeros(cls, S, z0, dz, nz, L, dv, k_edges, device):
-        nband = len(np.asarray(k_edges).reshape(-1)) - 1
-        return cls(torch.zeros((int(S), int(nz), 1 + nband + nband * nband), dtype=torch.float64, device=device), z0, dz, nz, L, dv,
-                   k_edges)
-
-    @staticmethod
-    def linear_k_edges(L, dv, nband):
-        """nband + 1 edges of equal bands from the fundamental to Nyquist: mode m sits at m k_1 inside [k_1 / 2, (M + 1 / 2) k_1)"""
-        return 2.0 * np.pi / (int(L) * float(dv)) * np.linspace(0.5, int(L) // 2 + 0.5, int(nband) + 1)
-
-    @property
-    def S(self):
-        return int(self.buf.shape[0])
-
-    @property
-    def bins(self):
-        return (self.z0, self.dz, self.nz)
-
-    @property
-    def z_edges(self):
-        return self.z0 + self.dz * torch.arange(self.nz + 1, dtype=torch.float64, device=self.buf.device)
-
-    @property
-    def z_centers(self):
-        return self.z0 + self.dz * (torch.arange(self.nz, dtype=torch.float64, device=self.buf.device) + 0.5)
-
-    @property
-    def k_edges(self):
-        """(nband + 1,) band edges in s/km"""
-        return torch.tensor(self._k_edges, dtype=torch.float64, device=self.buf.device)
-
-    def band_map(self):
-        """(band, count): the (M,) int32 band of mode m = 1 .. M (entry m - 1; -1 = in no band) and the (nband,) int64 number of
-        modes per band, as numpy arrays"""
-        k = 2.0 * np.pi * np.arange(1, self.M + 1, dtype=np.float64) / (self.L * self.dv)
-        e = np.asarray(self._k_edges, np.float64)
-        a = np.searchsorted(e, k, side="right") - 1
-        band = np.where((a >= 0) & (a < self.nband), a, -1).astype(np.int32)
-        return band, np.bincount(band[band >= 0], minlength=self.nband).astype(np.int64)
-
-    @property
-    def k_centers(self):
-        """(nband,) mean wavenumber of a band's modes in s/km (NaN for a band without modes)"""
-        band, count = self.band_map()
-        k = 2.0 * np.pi * np.arange(1, self.M + 1, dtype=np.float64) / (self.L * self.dv)
-        tot = np.bincount(band[band >= 0], weights=k[band >= 0], minlength=self.nband)
-        with np.errstate(all="ignore"):
-            c = np.where(count > 0, tot / count, np.nan)
-        return torch.tensor(c, dtype=torch.float64, device=self.buf.device)
-
-    @property
-    def n(self):
-        """(S, nz) number of segments stacked"""
-        return self.buf[:, :, 0]
-
-    @property
-    def mean(self):
-        """(S, nz, nband) mean band power of the stacked segments (NaN in an empty bin)"""
-        return self.buf[:, :, 1:1 + self.nband] / self.n[:, :, None]
-
-    @property
-    def cov(self):
-        """(S, nz, nband, nband) covariance of ``mean`` from the scatter of the segments: (<Q Q^T> - <Q> <Q>^T) / (n - 1); NaN
-        where n < 2"""
-        n = self.n[:, :, None, None]
-        m2 = self.buf[:, :, 1 + self.nband:].reshape(self.S, self.nz, self.nband, self.nband) / n
-        mu = self.mean
-        c = (m2 - mu[:, :, :, None] * mu[:, :, None, :]) / (n - 1.0)
-        return torch.where(n > 1.0, c, torch.full_like(c, float("nan")))
-
-    @property
-    def err(self):
-        """(S, nz, nband) standard error of ``mean``: the root of the diagonal of ``cov``"""
-        return torch.sqrt(torch.diagonal(self.cov, dim1=2, dim2=3).clamp_min(0.0))
-
-    @property
-    def corr(self):
-        """(S, nz, nband, nband) correlation matrix of the bands: cov_ab / sqrt(cov_aa cov_bb)"""
-        c = self.cov
-        d = torch.sqrt(torch.diagonal(c, dim1=2, dim2=3).clamp_min(0.0))
-        return c / (d[:, :, :, None] * d[:, :, None, :])
-
-    def _draws(self, what):
-        if self.S < 2:
-            raise _lib.QFAHipError(f"P1DBandStack.{what}: needs more than one draw of the continuum (S = {self.S})")
-        return self.mean
-
-    @property
-    def mean_over_draws(self):
-        """(nz, nband) mean of ``mean`` over the S posterior draws of the continuum"""
-        return self._draws("mean_over_draws").mean(0)
-
-    @property
-    def cov_over_draws(self):
-        """(nz, nband, nband) covariance of ``mean`` over the S draws: the continuum posterior's covariance of the band powers"""
-        d = self._draws("cov_over_draws")
-        d = d - d.mean(0, keepdim=True)
-        return torch.einsum("sza,szb->zab", d, d) / (self.S - 1.0)
-
-    @property
-    def total_cov(self):
-        """(nz, nband, nband) the mean over the draws of ``cov`` plus ``cov_over_draws``"""
-        return self.cov.mean(0) + self.cov_over_draws
-
-    def _like(self, buf):
-        return P1DBandStack(buf, self.z0, self.dz, self.nz, self.L, self.dv, self._k_edges)
-
-    def draws(self, s0, s1):
-        """the stack of draws [s0, s1): a view of the same buffer"""
-        return self._like(self.buf[s0:s1])
-
-    def clone(self):
-        return self._like(self.buf.clone())
-
-    def same_layout(self, other):
-        return isinstance(other, P1DBandStack) and other.bins == self.bins and other.L == self.L and other.dv == self.dv \
-            and other._k_edges == self._k_edges
-
-    def add_(self, other):
-        if not self.same_layout(other) or other.S != self.S:
-            raise _lib.QFAHipError("P1DBandStack.add_: bins / draws / segments / bands differ")
-        self.buf.add_(other.buf)
-        return self
-
-    def all_reduce(self, group=None):
-        """in-place sum over the process group (every rank calls it; an exhausted rank adds zeros)"""
-        from .distributed import all_reduce_accum
-        all_reduce_accum(self.buf.view(-1), group)
-        return self
-
-
-class QFA(object):
+class QFA(ForestStatistics):
 
     def __init__(self, Nb: int, Nr: int, Nh: int, device: torch.device,
                  tau: Callable[[torch.Tensor], torch.Tensor] = default_tau,
@@ -484,6 +95,7 @@ class QFA(object):
             self.random_init_func()
         self.mu = None
         self._ws = {}
+        self._p1d_band_cache = {}                       # (_p1d_band_tables)
         self._dp_group = None
         self._dp = False
         self._dp_checked = False
@@ -729,6 +341,13 @@ class QFA(object):
             acc.zero_()
         return acc
 
+    def _scratch(self, key, nbytes):
+        """the uint8 workspace ``self._ws[key]``, grown to hold ``nbytes``"""
+        buf = self._ws.get(key)
+        if buf is None or buf.numel() < nbytes:
+            buf = self._ws[key] = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        return buf
+
     def _check_batch_shapes(self, delta, error, zabs, mask):
         B = delta.shape[0]
         if zabs is None:
@@ -961,11 +580,7 @@ class QFA(object):
             raise _lib.QFAHipError(f"continua_from_latent(out=...): expected shape {shape}, got {tuple(out.shape)}")
         po = _lib.require_device_tensor(out, f32, "out")
         mu = self.mu.to(device=self.device, dtype=f32).contiguous()
-        need = _lib.lib().qfa_continua_workspace_bytes(self.Npix, self.Nh)
-        ws = self._ws.get("cont_ws")
-        if ws is None or ws.numel() < need:
-            ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-            self._ws["cont_ws"] = ws
+        ws = self._scratch("cont_ws", _lib.lib().qfa_continua_workspace_bytes(self.Npix, self.Nh))
         _lib.check(_lib.lib().qfa_continua_f32(
             _lib.require_device_tensor(self.F, f32, "F"), C.c_void_p(mu.data_ptr()), ph, R, self.Npix, self.Nh, po,
             C.c_void_p(ws.data_ptr()), ws.numel(), _lib.current_stream(h.device)), "qfa_continua_f32")
@@ -1043,15 +658,11 @@ class QFA(object):
         po = _lib.require_device_tensor(out, f32, "out")
         delta = torch.empty((B, S, self.Npix), dtype=f32, device=dev) if return_delta else None
         mu = self.mu.to(device=dev, dtype=f32).contiguous()
-        need = _lib.lib().qfa_mock_workspace_bytes(self.Npix, self.Nh)
-        ws = self._ws.get("mock_ws")
-        if ws is None or ws.numel() < need:
-            ws = torch.empty(need, dtype=torch.uint8, device=dev)
-            self._ws["mock_ws"] = ws
+        ws = self._scratch("mock_ws", _lib.lib().qfa_mock_workspace_bytes(self.Npix, self.Nh))
         _lib.check(_lib.lib().qfa_mock_spectra_f32(
             C.byref(ps), C.c_void_p(mu.data_ptr()), C.byref(bs), C.byref(self._tau_model), ph, B, S, self.Npix, self.Nb, self.Nh,
-            C.c_uint64(int(seed)), int(offset), po, C.c_void_p(delta.data_ptr()) if delta is not None else None,
-            C.c_void_p(ws.data_ptr()), ws.numel(), _lib.current_stream(dev)), "qfa_mock_spectra_f32")
+            C.c_uint64(int(seed)), int(offset), po, _lib._ptr(delta), _lib._ptr(ws), ws.numel(), _lib.current_stream(dev)),
+            "qfa_mock_spectra_f32")
         res = (out,) + ((delta,) if return_delta else ()) + ((h,) if return_latent else ())
         return res if len(res) > 1 else out
 
@@ -1064,384 +675,23 @@ class QFA(object):
         return self.sample_spectra(error, zabs, mask, n_samples=n_samples, seed=seed, offset=offset, hmean=hmean, hcov=hcov,
                                    zfac=zfac, batch=batch)
 
-    # ------------------------------------------------------------------ forest transmission
-    def forest(self, flux=None, error=None, zabs=None, mask=None, *, h=None, hmean=None, hcov=None, n_samples=0, seed=0, offset=0,
-               unc=None, bins=None, cont_min=0.0, pixel_range=None, unit_weights=False, stack=None, zfac=None, batch=None,
-               return_pixels=True):
-        """Lyman-alpha forest transmission T = flux / continuum on the blue side and its redshift-binned stack, for every draw of
-        the continuum, without writing a continuum (qfa_forest_f32; the contract is in include/qfa_hip.h).
-        The latent: ``h`` (B, S, Nh) as it is; else ``hmean`` alone (or with ``hcov`` and ``n_samples`` = 0): the posterior-mean
-        continuum, S = 1; else ``hmean`` + ``hcov`` + ``n_samples`` > 0 through ``sample_latent`` (``seed``, ``offset`` = the
-        global row of spectrum 0); with none of them ``predict`` runs on the inputs first, and its ``unc`` -- the continuum's
-        1 sigma, which enters ivar -- is passed on when S = 1.  ``bins`` = (z0, dz, nbin) asks for the stack; ``stack``: a
-        ``ForestStack`` to ADD to (its bins are used).  ``pixel_range`` = (p_lo, p_hi) restricts the stacked blue pixels,
-        ``unit_weights`` stacks with w = 1 instead of w = ivar, ``cont_min``: pixels whose continuum is not above it are unused.
-        ``mask`` None: every pixel is used.  A zabs tensor is read as given (never swapped for derived factors: the bins are
-        defined bit for bit by z).  Returns (trans, ivar, stack): (B, S, Nb) float32 each (None with ``return_pixels`` False) and
-        the ``ForestStack`` (None when neither ``bins`` nor ``stack`` was given)."""
-        if self.mu is None:
-            raise _lib.QFAHipError("forest needs model.mu (load_from_npz or train first)")
-        if hcov is not None and hmean is None:
-            raise _lib.QFAHipError("forest: hcov without hmean")
-        if h is not None and hmean is not None:
-            raise _lib.QFAHipError("forest: pass h or hmean / hcov, not both")
-        S = int(n_samples)
-        if S < 0:
-            raise _lib.QFAHipError(f"forest: n_samples = {n_samples}, expected >= 0")
-        if S > 0 and h is None and hmean is not None and hcov is None:
-            raise _lib.QFAHipError("forest: n_samples > 0 needs hcov next to hmean")
-        if bins is None and stack is None and not return_pixels:
-            raise _lib.QFAHipError("forest: nothing asked for (no bins, no stack, return_pixels = False)")
-        dev = self.device
-        self._params_struct()                                   # (F as a contiguous float32 device tensor)
-        if h is None and hmean is None:
-            _, hmean, hcov, _, punc = self.predict(flux, error, zabs, mask, zfac=zfac, batch=batch)
-            if S == 0 and unc is None:
-                unc = punc
-        if batch is not None:
-            B = batch.B
-            bs, keep = self._batch_struct_rows(batch, raw_flux=True)
-        else:
-            if not isinstance(flux, torch.Tensor) or flux.dim() != 2:
-                raise _lib.QFAHipError("forest: flux must be a (B, Npix) tensor")
-            B = self._check_batch_shapes(flux, error, zabs, mask if mask is not None else flux)
-            bs, keep = self._batch_struct(flux, error, zabs, mask, zfac, allow_no_mask=True, auto_factor=False)
-        bs.A_blue = None                                        # (not read by the call)
-        if h is None:
-            if tuple(hmean.shape) != (B, self.Nh):
-                raise _lib.QFAHipError(f"hmean: shape {tuple(hmean.shape)}, expected ({B}, {self.Nh})")
-            if S > 0:
-                h = self.sample_latent(hmean, hcov, S, seed=seed, offset=offset)
-            else:
-                S = 1
-                h = hmean.reshape(B, 1, self.Nh)
-        else:
-            if h.dim() != 3 or h.shape[0] != B or h.shape[2] != self.Nh or h.shape[1] < 1 or (S > 0 and h.shape[1] != S):
-                raise _lib.QFAHipError(f"h: shape {tuple(h.shape)}, expected ({B}, {S if S > 0 else 'S'}, {self.Nh})")
-            S = int(h.shape[1])
-        ph = _lib.require_device_tensor(h, f32, "h")
-        pu = None
-        if unc is not None:
-            if tuple(unc.shape) != (B, self.Npix):
-                raise _lib.QFAHipError(f"unc: shape {tuple(unc.shape)}, expected ({B}, {self.Npix})")
-            pu = _lib.require_device_tensor(unc, f32, "unc")
-        if stack is not None:
-            if not isinstance(stack, ForestStack) or stack.S != S or (bins is not None and ForestStack(stack.buf, *bins).bins != stack.bins):
-                raise _lib.QFAHipError(f"forest(stack=...): expected a ForestStack of {S} draws on the same bins")
-            _lib.require_device_tensor(stack.buf, torch.float64, "stack")
-        elif bins is not None:
-            stack = ForestStack.zeros(S, bins[0], bins[1], bins[2], dev)
-        fb = _lib.ForestBins()
-        fb.z0, fb.dz, fb.nbin = (stack.z0, stack.dz, stack.nbin) if stack is not None else (0.0, 1.0, 1)
-        p_lo, p_hi = (0, self.Nb) if pixel_range is None else (int(pixel_range[0]), int(pixel_range[1]))
-        if not 0 <= p_lo <= p_hi <= self.Nb:
-            raise _lib.QFAHipError(f"forest: pixel_range = {pixel_range}, expected 0 <= p_lo <= p_hi <= {self.Nb}")
-        fb.p_lo, fb.p_hi = p_lo, p_hi
-        trans = ivar = None
-        if return_pixels:
-            trans = torch.empty((B, S, self.Nb), dtype=f32, device=dev)
-            ivar = torch.empty((B, S, self.Nb), dtype=f32, device=dev)
-        mu = self.mu.to(device=dev, dtype=f32).contiguous()
-        need = _lib.lib().qfa_forest_workspace_bytes(B, S, self.Npix, self.Nb, self.Nh, int(fb.nbin))
-        if need == 0:
-            raise _lib.QFAHipError(f"forest: unsupported shape B={B} S={S} Npix={self.Npix} Nb={self.Nb} Nh={self.Nh} nbin={fb.nbin}")
-        ws = self._ws.get("forest_ws")
-        if ws is None or ws.numel() < need:
-            ws = torch.empty(need, dtype=torch.uint8, device=dev)
-            self._ws["forest_ws"] = ws
-        _lib.check(_lib.lib().qfa_forest_f32(
-            _lib.require_device_tensor(self.F, f32, "F"),
-            C.c_void_p(mu.data_ptr()), C.byref(bs), ph, pu, B, S, self.Npix, self.Nb, self.Nh, C.byref(fb), float(cont_min),
-            _lib.F_FOREST_UNIT_W if unit_weights else 0,
-            C.c_void_p(trans.data_ptr()) if trans is not None else None, C.c_void_p(ivar.data_ptr()) if ivar is not None else None,
-            C.c_void_p(stack.buf.data_ptr()) if stack is not None else None,
-            C.c_void_p(ws.data_ptr()), ws.numel(), _lib.current_stream(dev)), "qfa_forest_f32")
-        return trans, ivar, stack
-
-    # ------------------------------------------------------------------ 1D flux power spectrum
-    P1D_PAIR_BYTES = 1 << 30    # flux_power: the most the (B, S_chunk, Nb) trans / ivar pair of a slice may take
-
-    def _p1d_inputs(self, what, trans, ivar, zabs, zfac, batch, tbar, tbar_bins):
-        """the checks and conversions `p1d` and `p1d_bands` share: (B, S, tbar (St, nT) float32, St, tbar_bins, qfa_batch_t, the
-        tensors it points into)"""
-        dev = self.device
-        if not isinstance(trans, torch.Tensor) or trans.dim() != 3 or trans.shape[2] != self.Nb or tuple(ivar.shape) != tuple(trans.shape):
-            raise _lib.QFAHipError(f"{what}: trans / ivar must be (B, S, {self.Nb}) tensors")
-        B, S = int(trans.shape[0]), int(trans.shape[1])
-        if isinstance(tbar, ForestStack):
-            if tbar.S not in (1, S):
-                raise _lib.QFAHipError(f"{what}: tbar has {tbar.S} draws, expected 1 or {S}")
-            tbar_bins, tbar = tbar.bins, tbar.mean
-        if tbar_bins is None:
-            raise _lib.QFAHipError(what + ": a tbar tensor needs tbar_bins = (z0, dz, nT)")
-        tbar = tbar.to(device=dev, dtype=f32).reshape(-1, int(tbar_bins[2])).contiguous()
-        St = int(tbar.shape[0])
-        if St not in (1, S):
-            raise _lib.QFAHipError(f"{what}: tbar has {St} rows, expected 1 or {S}")
-        if batch is not None:
-            if batch.B != B:
-                raise _lib.QFAHipError(f"{what}: resident batch of {batch.B} spectra, trans has {B}")
-            bs, keep = self._batch_struct_rows(batch, need_src=False)
-        else:
-            bs, keep = _lib.Batch(), []
-            bs.row_stride = 0
-            if zfac is None:
-                zfac = getattr(zabs, "zfac", None)              # (what a DeviceDataloader attaches)
-            # _batch_struct's condition, so that p1d bins on the very z `forest` and `mean_transmission` binned on
-            if zfac is not None and not (self._tau_callable is None and self.use_factored_z):
-                if zabs is None:
-                    raise _lib.QFAHipError("zabs is None and no usable zfac = (zq1, pix_ratio) was given")
-                zfac = None
-            if zfac is None and zabs is not None:
-                if tuple(zabs.shape) != (B, self.Nb):
-                    raise _lib.QFAHipError(f"zabs: shape {tuple(zabs.shape)}, expected ({B}, {self.Nb})")
-                zabs = zabs if (zabs.dtype == f32 and zabs.is_contiguous()) else zabs.to(f32).contiguous()
-                keep.append(zabs)
-                bs.zabs = _lib.require_device_tensor(zabs, f32, "zabs").value
-            elif zfac is not None:
-                zq1, ratio = (t if (t.dtype == f32 and t.is_contiguous()) else t.to(f32).contiguous() for t in zfac)
-                if tuple(zq1.shape) != (B,) or tuple(ratio.shape) != (self.Nb,):
-                    raise _lib.QFAHipError(f"zfac shapes {tuple(zq1.shape)}, {tuple(ratio.shape)}: expected ({B},), ({self.Nb},)")
-                keep += [zq1, ratio]
-                bs.zq1 = _lib.require_device_tensor(zq1, f32, "zq1").value
-                bs.pix_ratio = _lib.require_device_tensor(ratio, f32, "pix_ratio").value
-            else:
-                raise _lib.QFAHipError(what + ": pass zabs, zfac = (zq1, pix_ratio) or batch")
-        return B, S, tbar, St, tbar_bins, bs, keep
-
-    def p1d(self, trans, ivar, *, zabs=None, zfac=None, batch=None, tbar, tbar_bins=None, seg_len, n_segments, pixel_start=0,
-            min_used, bins=None, stack=None, return_segments=True, dv=1.0):
-        """The 1D flux power spectrum of forest segments and its (k, z) stack (qfa_p1d_f32; the contract is in include/qfa_hip.h).
-        ``trans``, ``ivar`` (B, S, Nb) as ``forest`` returns them; the redshift of the pixels from ``zabs`` (B, Nb), ``zfac`` =
-        (zq1, pix_ratio) or a resident ``batch``.  ``tbar``: the mean transmission the contrast delta_F = T / tbar - 1 is formed
-        with -- a ``ForestStack`` (its ``mean`` per draw: one row per draw when it has S draws, else its single row for every
-        draw) or a (St, nT) / (nT,) tensor over ``tbar_bins`` = (z0, dz, nT).  Segment g holds the ``seg_len`` pixels from
-        ``pixel_start`` + g ``seg_len`` on and is used when at least ``min_used`` of them are.  ``bins`` = (z0, dz, nz) asks for
-        the stack (``dv``: the pixel width in km/s it reports k and P in); ``stack``: a ``P1DStack`` to ADD to.  Returns
-        (power (B, S, n_segments, M), noise (B, S, n_segments), stack): float32 P_m = |delta~_m|^2 / L for m = 1 .. M = seg_len // 2
-        and the noise level, both in pixel units (None with ``return_segments`` False), and the ``P1DStack`` (or None)."""
-        dev = self.device
-        if bins is None and stack is None and not return_segments:
-            raise _lib.QFAHipError("p1d: nothing asked for (no bins, no stack, return_segments = False)")
-        B, S, tbar, St, tbar_bins, bs, keep = self._p1d_inputs("p1d", trans, ivar, zabs, zfac, batch, tbar, tbar_bins)
-        L, nseg, p_lo = int(seg_len), int(n_segments), int(pixel_start)
-        if stack is not None:
-            if not isinstance(stack, P1DStack) or stack.S != S or stack.L != L or \
-                    (bins is not None and P1DStack(stack.buf, bins[0], bins[1], bins[2], L).bins != stack.bins):
-                raise _lib.QFAHipError(f"p1d(stack=...): expected a P1DStack of {S} draws and segments of {L} pixels on the same bins")
-            _lib.require_device_tensor(stack.buf, torch.float64, "stack")
-        elif bins is not None:
-            stack = P1DStack.zeros(S, bins[0], bins[1], bins[2], L, dv, dev)
-        pp = _lib.P1DParams()
-        pp.zT0, pp.dzT, pp.nT, pp.St = float(np.float32(tbar_bins[0])), float(np.float32(tbar_bins[1])), int(tbar_bins[2]), St
-        pp.p_lo, pp.seg_len, pp.nseg, pp.min_used = p_lo, L, nseg, int(min_used)
-        pp.z0, pp.dz, pp.nz = (stack.z0, stack.dz, stack.nz) if stack is not None else (0.0, 1.0, 1)
-        need = _lib.lib().qfa_p1d_workspace_bytes(B * S, S, self.Nb, L, nseg, int(pp.nz)) if L >= 1 and nseg >= 1 else 0
-        if need == 0:
-            raise _lib.QFAHipError(f"p1d: unsupported shape B={B} S={S} Nb={self.Nb} seg_len={L} n_segments={nseg} nz={pp.nz}")
-        ws = self._ws.get("p1d_ws")
-        if ws is None or ws.numel() < need:
-            ws = torch.empty(need, dtype=torch.uint8, device=dev)
-            self._ws["p1d_ws"] = ws
-        power = noise = None
-        if return_segments:
-            power = torch.empty((B, S, nseg, L // 2), dtype=f32, device=dev)
-            noise = torch.empty((B, S, nseg), dtype=f32, device=dev)
-        _lib.check(_lib.lib().qfa_p1d_f32(
-            _lib.require_device_tensor(trans, f32, "trans"), _lib.require_device_tensor(ivar, f32, "ivar"), C.byref(bs),
-            C.c_void_p(tbar.data_ptr()), B, S, self.Nb, C.byref(pp), 0,
-            C.c_void_p(power.data_ptr()) if power is not None else None, C.c_void_p(noise.data_ptr()) if noise is not None else None,
-            C.c_void_p(stack.buf.data_ptr()) if stack is not None else None,
-            C.c_void_p(ws.data_ptr()), ws.numel(), _lib.current_stream(dev)), "qfa_p1d_f32")
-        return power, noise, stack
-
-    def _p1d_band_tables(self, L, dv, k_edges, resolution_kms):
-        """(band (M,) int32, weight (M,) float32) of qfa_p1d_band_t on the device, built once per (L, dv, k_edges, resolution):
-        weight_m = dv / (n_a W^2(k_m)) with n_a the number of modes of the band of mode m and W^2 = ``P1DStack.window2`` (1 without
-        a resolution), so that Q_a is the mean over the band's modes of the P1D in km/s"""
-        key = (int(L), float(dv), tuple(float(x) for x in np.asarray(k_edges, np.float64).reshape(-1)),
-               None if resolution_kms is None else float(resolution_kms))
-        cache = self.__dict__.setdefault("_p1d_band_cache", {})
-        if key not in cache:
-            ref = P1DBandStack(torch.zeros((1, 1, 1 + (len(key[2]) - 1) + (len(key[2]) - 1) ** 2), dtype=torch.float64), 0.0, 1.0, 1,
-                               L, dv, key[2])
-            band, count = ref.band_map()
-            w = np.full(ref.M, float(dv), np.float64) / np.maximum(count[np.maximum(band, 0)], 1)
-            if resolution_kms is not None:
-                k = 2.0 * np.pi * np.arange(1, ref.M + 1, dtype=np.float64) / (ref.L * ref.dv)
-                w = w / (np.sinc(k * ref.dv / (2.0 * np.pi)) * np.exp(-0.5 * (k * float(resolution_kms)) ** 2)) ** 2
-            w = np.where(band >= 0, w, 0.0).astype(np.float32)
-            if len(cache) >= 16:
-                cache.clear()
-            # (one entry more than the modes: a pointer to an empty tensor would be NULL at L = 1)
-            cache[key] = (torch.tensor(np.append(band, np.int32(-1)), device=self.device),
-                          torch.tensor(np.append(w, np.float32(0.0)), device=self.device))
-        return cache[key]
-
-    def p1d_bands(self, trans, ivar, *, zabs=None, zfac=None, batch=None, tbar, tbar_bins=None, seg_len, n_segments, pixel_start=0,
-                  min_used, bins=None, dv=1.0, k_edges, resolution_kms=None, subtract_noise=True, stack=None,
-                  return_segments=False):
-        """Band powers of the forest's P1D and the stack their covariance matrix comes from (qfa_p1d_band_f32; the contract is in
-        include/qfa_hip.h).  The inputs and keywords of ``p1d``; ``k_edges``: nband + 1 increasing band edges in s/km -- band a
-        holds the modes with k_edges[a] <= 2 pi m / (seg_len dv) < k_edges[a + 1].  Q_a of a segment is the mean over the band's
-        modes of (P_m - N) dv / W^2(k_m): ``subtract_noise`` False keeps the noise in, ``resolution_kms`` divides by
-        ``P1DStack.window2``.  ``bins`` = (z0, dz, nz) asks for the stack, ``stack``: a ``P1DBandStack`` to ADD to.  Returns
-        (bandpower (B, S, n_segments, nband) float64, or None without ``return_segments``; the ``P1DBandStack``, or None)."""
-        dev = self.device
-        if bins is None and stack is None and not return_segments:
-            raise _lib.QFAHipError("p1d_bands: nothing asked for (no bins, no stack, return_segments = False)")
-        B, S, tbar, St, tbar_bins, bs, keep = self._p1d_inputs("p1d_bands", trans, ivar, zabs, zfac, batch, tbar, tbar_bins)
-        L, nseg, p_lo = int(seg_len), int(n_segments), int(pixel_start)
-        if stack is not None:
-            want = P1DBandStack(stack.buf, *(bins if bins is not None else stack.bins), L, stack.dv, k_edges) \
-                if isinstance(stack, P1DBandStack) else None
-            if want is None or stack.S != S or not stack.same_layout(want):
-                raise _lib.QFAHipError(f"p1d_bands(stack=...): expected a P1DBandStack of {S} draws and segments of {L} pixels on the "
-                                       "same bins and bands")
-            _lib.require_device_tensor(stack.buf, torch.float64, "stack")
-            dv = stack.dv
-        elif bins is not None:
-            stack = P1DBandStack.zeros(S, bins[0], bins[1], bins[2], L, dv, k_edges, dev)
-        nband = len(np.asarray(k_edges).reshape(-1)) - 1
-        band, weight = self._p1d_band_tables(L, dv, k_edges, resolution_kms)
-        pp = _lib.P1DParams()
-        pp.zT0, pp.dzT, pp.nT, pp.St = float(np.float32(tbar_bins[0])), float(np.float32(tbar_bins[1])), int(tbar_bins[2]), St
-        pp.p_lo, pp.seg_len, pp.nseg, pp.min_used = p_lo, L, nseg, int(min_used)
-        pp.z0, pp.dz, pp.nz = (stack.z0, stack.dz, stack.nz) if stack is not None else (0.0, 1.0, 1)
-        qq = _lib.P1DBandParams()
-        qq.nband, qq.band, qq.weight, qq.subtract_noise = nband, band.data_ptr(), weight.data_ptr(), 1 if subtract_noise else 0
-        need = _lib.lib().qfa_p1d_band_workspace_bytes(B * S, S, self.Nb, L, nseg, int(pp.nz), nband) if L >= 1 and nseg >= 1 else 0
-        if need == 0:
-            raise _lib.QFAHipError(f"p1d_bands: unsupported shape B={B} S={S} Nb={self.Nb} seg_len={L} n_segments={nseg} nz={pp.nz} "
-                                   f"nband={nband}")
-        ws = self._ws.get("p1d_ws")                               # (shared with p1d: both calls own it only while they run)
-        if ws is None or ws.numel() < need:
-            ws = torch.empty(need, dtype=torch.uint8, device=dev)
-            self._ws["p1d_ws"] = ws
-        bandpower = torch.empty((B, S, nseg, nband), dtype=torch.float64, device=dev) if return_segments else None
-        _lib.check(_lib.lib().qfa_p1d_band_f32(
-            _lib.require_device_tensor(trans, f32, "trans"), _lib.require_device_tensor(ivar, f32, "ivar"), C.byref(bs),
-            C.c_void_p(tbar.data_ptr()), B, S, self.Nb, C.byref(pp), C.byref(qq), 0,
-            C.c_void_p(bandpower.data_ptr()) if bandpower is not None else None,
-            C.c_void_p(stack.buf.data_ptr()) if stack is not None else None,
-            C.c_void_p(ws.data_ptr()), ws.numel(), _lib.current_stream(dev)), "qfa_p1d_band_f32")
-        return bandpower, stack
-
-    def flux_power(self, dataloader, z_min, z_max, n_zbins, *, n_segments=3, seg_len=None, min_used_frac=0.75, tbar=None,
-                   tbar_nbins=64, n_samples=0, seed=0, batch_size=4096, cont_min=0.0, dv=None):
-        """The 1D flux power spectrum of a whole dataloader: a ``P1DStack`` of S = max(1, n_samples) draws over ``n_zbins`` bins of
-        [z_min, z_max) in the redshift of a segment's central pixel.  The blue side is cut into ``n_segments`` segments of
-        ``seg_len`` pixels (default Nb // n_segments); a segment is used when ``min_used_frac`` of its pixels are.  ``tbar``: the
-        ``ForestStack`` the contrast is formed with; None runs ``mean_transmission`` first, with the same ``n_samples`` / ``seed``
-        and ``tbar_nbins`` bins that cover every pixel of a stacked segment, so that draw s of <T> is the same continuum draw as
-        draw s of T.  Per slice of the loader: ``predict``, ``forest`` and ``p1d``, the draws in chunks that keep the
-        (B, S_chunk, Nb) trans / ivar pair under ``P1D_PAIR_BYTES`` (1 GiB).  ``dv``: the pixel width in km/s, default
-        c ln(lambda_1 / lambda_0) of the loader's ``wav_grid``.  The global row of a spectrum is its dataloader index and the
-        reducer adds segments in order, so the result does not depend on ``batch_size`` beyond the rounding of float64 sums.
-        Under data parallelism the sums are all-reduced over the model's group: every rank returns the global stack."""
-        return self._power_of_loader("flux_power", dataloader, z_min, z_max, n_zbins, n_segments, seg_len, min_used_frac, tbar,
-                                     tbar_nbins, n_samples, seed, batch_size, cont_min, dv, None)
-
-    def band_power(self, dataloader, z_min, z_max, n_zbins, k_edges, *, n_segments=3, seg_len=None, min_used_frac=0.75, tbar=None,
-                   tbar_nbins=64, n_samples=0, seed=0, batch_size=4096, cont_min=0.0, dv=None, resolution_kms=None,
-                   subtract_noise=True):
-        """The band powers of a whole dataloader and their covariance: a ``P1DBandStack`` of S = max(1, n_samples) draws over
-        ``n_zbins`` bins of [z_min, z_max) and the bands ``k_edges`` (nband + 1 edges in s/km).  Everything else is
-        ``flux_power``'s: the same segments, mean transmission, draws and loop over the loader, with ``p1d_bands`` in the place of
-        ``p1d``.  The sums of a slice are formed in chunks of a fixed number of segments, so the result depends on ``batch_size``
-        only through the rounding of float64 sums.  Under data parallelism the sums are all-reduced over the model's group."""
-        return self._power_of_loader("band_power", dataloader, z_min, z_max, n_zbins, n_segments, seg_len, min_used_frac, tbar,
-                                     tbar_nbins, n_samples, seed, batch_size, cont_min, dv,
-                                     {"k_edges": k_edges, "resolution_kms": resolution_kms, "subtract_noise": subtract_noise})
-
-    def _power_of_loader(self, what, dataloader, z_min, z_max, n_zbins, n_segments, seg_len, min_used_frac, tbar, tbar_nbins,
-                         n_samples, seed, batch_size, cont_min, dv, bands):
-        """the loop `flux_power` (``bands`` None: a ``P1DStack`` through ``p1d``) and `band_power` (``bands``: the keywords of
-        ``p1d_bands``; a ``P1DBandStack``) share"""
-        nseg, nz, S = int(n_segments), int(n_zbins), max(1, int(n_samples))
-        L = int(seg_len) if seg_len is not None else (self.Nb // nseg if nseg > 0 else 0)
-        if nseg < 1 or L < 1 or nseg * L > self.Nb or nz < 1 or not float(z_max) > float(z_min) or not 0.0 < float(min_used_frac) <= 1.0:
-            raise _lib.QFAHipError(f"{what}: {nseg} segments of {L} pixels on Nb = {self.Nb}, bins [{z_min}, {z_max}) / {nz}, "
-                                   f"min_used_frac = {min_used_frac}")
-        if dv is None:
-            wav = getattr(dataloader, "wav_grid", None)
-            if wav is None or len(wav) < 2:
-                raise _lib.QFAHipError(what + ": the dataloader has no wav_grid: pass dv (km/s per pixel)")
-            dv = 299792.458 * float(np.log(float(wav[1]) / float(wav[0])))
-        min_used = max(1, int(np.ceil(float(min_used_frac) * L)))
-        if tbar is None:
-            half = float(np.exp(0.5 * (L + 1) * float(dv) / 299792.458))          # (1 + z) over half a segment
-            tbar = self.mean_transmission(dataloader, (1.0 + float(z_min)) / half - 1.0, (1.0 + float(z_max)) * half - 1.0,
-                                          int(tbar_nbins), n_samples=int(n_samples), seed=seed, batch_size=batch_size,
-                                          cont_min=cont_min)
-        if not isinstance(tbar, ForestStack) or tbar.S not in (1, S):
-            raise _lib.QFAHipError(f"{what}: tbar must be a ForestStack of 1 or {S} draws")
-        tmean = tbar.mean.to(f32)
-        if bands is None:
-            stack = P1DStack.zeros(S, z_min, (float(z_max) - float(z_min)) / nz, nz, L, dv, self.device)
-        else:
-            stack = P1DBandStack.zeros(S, z_min, (float(z_max) - float(z_min)) / nz, nz, L, dv, bands["k_edges"], self.device)
-        row0 = int(getattr(dataloader, "_row0", 0))              # (a data-parallel loader: the global index of its first row)
-        for s, inputs, _ in self._loader_slices(dataloader, int(batch_size)):
-            _, hmean, hcov, _, unc = self.predict(**inputs)
-            B = int(hmean.shape[0])
-            if int(n_samples) > 0:
-                h, unc = self.sample_latent(hmean, hcov, S, seed=seed, offset=row0 + s), None
-            else:
-                h = hmean.reshape(B, 1, self.Nh)
-            Sc = max(1, min(S, self.P1D_PAIR_BYTES // max(1, B * self.Nb * 8)))
-            zin = {"batch": inputs["batch"]} if "batch" in inputs else {"zabs": inputs["zabs"]}
-            for s0 in range(0, S, Sc):
-                s1 = min(S, s0 + Sc)
-                hs = h if (s0 == 0 and s1 == S) else h[:, s0:s1].contiguous()
-                tr, iv, _ = self.forest(**inputs, h=hs, unc=unc, cont_min=cont_min)
-                kw = dict(tbar=tmean if tbar.S == 1 else tmean[s0:s1], tbar_bins=tbar.bins, seg_len=L, n_segments=nseg,
-                          min_used=min_used, stack=stack.draws(s0, s1), return_segments=False)
-                if bands is None:
-                    self.p1d(tr, iv, **zin, **kw)
-                else:
-                    self.p1d_bands(tr, iv, **zin, **kw, **bands)
-        if self._dp:
-            stack.all_reduce(self._dp_group)
-        return stack
-
     def _loader_slices(self, dataloader, batch_size):
-        """the slices predict_to_npz walks: (first dataloader index, keyword inputs of predict / forest, paths)"""
+        """the slices predict_to_npz and the forest statistics walk: (first dataloader index, keyword inputs of predict / forest,
+        paths)"""
         n = len(dataloader)
         for s in range(0, n, batch_size):
+            # rows of the resident arrays, no copy (the resident form carries the factors, never zabs: with use_factored_z off or
+            # a custom tau the loader materialises the four tensors)
             if hasattr(dataloader, "rows_batch") and self._tau_callable is None and (self.use_factored_z or self.Nb == 0):
                 rb, paths = dataloader.rows_batch(s, min(s + batch_size, n))
                 yield s, {"batch": rb}, paths
-            elif hasattr(dataloader, "get_rows"):
+            elif hasattr(dataloader, "get_rows"):                # one launch for the whole slice
                 f, e, z, m, paths = dataloader.get_rows(s, min(s + batch_size, n))
                 yield s, {"flux": f, "error": e, "zabs": z, "mask": m}, paths
-            else:
+            else:                                                # the reference's per-spectrum contract
                 items = [dataloader[i] for i in range(s, min(s + batch_size, n))]
                 f, e, z, m = (torch.stack([it[j] for it in items]) for j in range(4))
                 yield s, {"flux": f, "error": e, "zabs": z, "mask": m}, [it[4] for it in items]
-
-    def mean_transmission(self, dataloader, z_min, z_max, n_bins, n_samples=0, seed=0, batch_size=4096, cont_min=0.0,
-                          pixel_range=None, unit_weights=False):
-        """The stacked forest transmission of a whole dataloader in ``n_bins`` bins of [z_min, z_max): a ``ForestStack`` of S =
-        max(1, n_samples) draws.  ``n_samples`` = 0 stacks the posterior-mean continuum (``predict``'s unc enters the weights);
-        ``n_samples`` > 0 repeats the stack over that many posterior draws of every continuum (``std_over_draws``: the
-        continuum's error bar on the stack).  It walks the loader the way ``predict_to_npz`` does (the resident rows form when
-        the loader has one); the global row of a spectrum is its dataloader index, so the result does not depend on
-        ``batch_size`` beyond the rounding of float64 sums.  Under data parallelism the sums are all-reduced over the model's
-        group: every rank returns the global stack."""
-        n_bins, S = int(n_bins), max(1, int(n_samples))
-        if n_bins < 1 or not float(z_max) > float(z_min):
-            raise _lib.QFAHipError(f"mean_transmission: bins [{z_min}, {z_max}) / {n_bins}")
-        stack = ForestStack.zeros(S, z_min, (float(z_max) - float(z_min)) / n_bins, n_bins, self.device)
-        row0 = int(getattr(dataloader, "_row0", 0))              # (a data-parallel loader: the global index of its first row)
-        for s, inputs, _ in self._loader_slices(dataloader, int(batch_size)):
-            _, hmean, hcov, _, unc = self.predict(**inputs)
-            self.forest(**inputs, hmean=hmean, hcov=hcov, n_samples=int(n_samples), seed=seed, offset=row0 + s,
-                        unc=unc if int(n_samples) == 0 else None, cont_min=cont_min, pixel_range=pixel_range,
-                        unit_weights=unit_weights, stack=stack, return_pixels=False)
-        if self._dp:
-            stack.all_reduce(self._dp_group)
-        return stack
 
     def predict_to_npz(self, dataloader, output_dir, batch_size=4096, n_samples=0, seed=0, n_replicates=0, forest=False):
         """The predict mode of the reference's main.py:87-98 for a whole dataloader: one
@@ -1454,36 +704,19 @@ class QFA(object):
         flux over the posterior-mean continuum on the blue side and its inverse variance (``QFA.forest`` with this
         prediction's hmean and unc)."""
         os.makedirs(output_dir, exist_ok=True)
-        n = len(dataloader)
         written = []
-        for s in range(0, n, batch_size):
-            # rows of the resident arrays, no copy (the resident form carries the factors, never zabs: with use_factored_z off or
-            # a custom tau the loader materialises the four tensors)
-            if hasattr(dataloader, "rows_batch") and self._tau_callable is None and (self.use_factored_z or self.Nb == 0):
-                rb, paths = dataloader.rows_batch(s, min(s + batch_size, n))
-                res = self.predict(batch=rb)
-                inputs = {"batch": rb}
-            elif hasattr(dataloader, "get_rows"):                # one launch for the whole slice
-                f, e, z, m, paths = dataloader.get_rows(s, min(s + batch_size, n))
-                res = self.predict(f, e, z, m)
-                inputs = {"error": e, "zabs": z, "mask": m}
-            else:                                                # the reference's per-spectrum contract
-                items = [dataloader[i] for i in range(s, min(s + batch_size, n))]
-                f, e, z, m = (torch.stack([it[j] for it in items]) for j in range(4))
-                paths = [it[4] for it in items]
-                res = self.predict(f, e, z, m)
-                inputs = {"error": e, "zabs": z, "mask": m}
+        for s, inputs, paths in self._loader_slices(dataloader, batch_size):
+            res = self.predict(**inputs)
             samples = None
             if n_samples > 0:
                 samples = self.sample_continua(n_samples=n_samples, seed=seed, offset=s, hmean=res[1], hcov=res[2]).cpu().numpy()
             replicates = None
             if n_replicates > 0:
                 replicates = self.sample_spectra(n_samples=n_replicates, seed=seed, offset=s, hmean=res[1], hcov=res[2],
-                                                 **inputs).cpu().numpy()
+                                                 **{k: v for k, v in inputs.items() if k != "flux"}).cpu().numpy()
             trans = tivar = None
             if forest:
-                fin = dict(inputs) if "batch" in inputs else dict(inputs, flux=f)
-                trans, tivar, _ = self.forest(**fin, hmean=res[1], unc=res[4])
+                trans, tivar, _ = self.forest(**inputs, hmean=res[1], unc=res[4])
                 trans, tivar = trans[:, 0].cpu().numpy(), tivar[:, 0].cpu().numpy()
             ll, hmean, hcov, cont, unc = (x.cpu().numpy() for x in res)
             for r, path in enumerate(paths):
@@ -1569,10 +802,7 @@ class QFA(object):
         need = h.qfa_em_workspace_bytes(int(B), self.Npix, self.Nh)
         if need == 0:
             raise _lib.QFAHipError(f"unsupported shape B={B} Npix={self.Npix} Nh={self.Nh}")
-        ws = self._ws.get("em_ws")
-        if ws is None or ws.numel() < need:
-            ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-            self._ws["em_ws"] = ws
+        ws = self._scratch("em_ws", need)
         flags = 0
         if stats is None:
             stats = EMStats(torch.empty(h.qfa_em_floats(self.Npix, self.Nh), dtype=f32, device=self.device), self.Npix, self.Nh)

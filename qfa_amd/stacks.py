@@ -1,0 +1,359 @@
+"""The result classes of ``QFA``: ``EMStats`` and the three stacks of the forest statistics, ``ForestStack``, ``P1DStack`` and
+``P1DBandStack``.  Views and arithmetic on buffers the kernels filled (include/qfa_hip.h): nothing here calls the library or
+needs a GPU, the classes work on CPU tensors as well.  ``qfa_amd.model`` re-exports the four names."""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from ._lib import QFAHipError
+
+
+class EMStats(object):
+    """The packed sufficient statistics of the closed-form update of F (include/qfa_hip.h, qfa_em_floats):
+    ``buf`` = [S2 (Npix, Nh, Nh) | S1 (Npix, Nh) | cnt (Npix,) | sum NLL, n_spectra, 0, 0] -- sums only, which is what data
+    parallelism all-reduces.  ``S2``, ``S1``, ``cnt`` are views of ``buf``; ``loss`` is the (1, 1) mean NLL."""
+
+    def __init__(self, buf, Npix, Nh):
+        self.buf, self.Npix, self.Nh = buf, int(Npix), int(Nh)
+        n2, n1 = self.Npix * self.Nh * self.Nh, self.Npix * self.Nh
+        if buf.numel() != n2 + n1 + self.Npix + 4:
+            raise QFAHipError(f"EMStats: {buf.numel()} floats, expected {n2 + n1 + self.Npix + 4}")
+        self.S2 = buf[:n2].view(self.Npix, self.Nh, self.Nh)
+        self.S1 = buf[n2:n2 + n1].view(self.Npix, self.Nh)
+        self.cnt = buf[n2 + n1:n2 + n1 + self.Npix]
+        self.tail = buf[n2 + n1 + self.Npix:]
+
+    @property
+    def loss(self):
+        return (self.tail[0] / self.tail[1]).reshape(1, 1)
+
+    def clone(self):
+        return EMStats(self.buf.clone(), self.Npix, self.Nh)
+
+    def blend_(self, other, rho):
+        """self <- (1 - rho) self + rho other, in place (stochastic EM on mini-batches); rho = 1 is replacement, bit for bit."""
+        rho = float(rho)
+        if rho == 1.0:
+            self.buf.copy_(other.buf)
+        else:
+            self.buf.mul_(1.0 - rho).add_(other.buf, alpha=rho)
+        return self
+
+
+def _mode_k(L, dv):
+    """(M,) float64 numpy wavenumbers 2 pi m / (L dv), m = 1 .. M = L // 2, in s/km"""
+    return 2.0 * np.pi * np.arange(1, int(L) // 2 + 1, dtype=np.float64) / (int(L) * float(dv))
+
+
+def _window2(k, dv, resolution_kms):
+    """W^2(k): the pixel's sinc times a Gaussian of ``resolution_kms`` (1 sigma), squared; ``k`` a float64 numpy array or
+    torch tensor, evaluated in its own library"""
+    xp = torch if isinstance(k, torch.Tensor) else np
+    return (xp.sinc(k * dv / (2.0 * np.pi)) * xp.exp(-0.5 * (k * float(resolution_kms)) ** 2)) ** 2
+
+
+def _edges(k_edges):
+    """the checked band edges as a tuple of floats"""
+    e = tuple(float(x) for x in np.asarray(k_edges, np.float64).reshape(-1))
+    if not (2 <= len(e) <= 65 and np.all(np.isfinite(e)) and np.all(np.diff(e) > 0.0)):
+        raise QFAHipError(f"P1DBandStack: k_edges must be 2 .. 65 increasing finite wavenumbers, got {len(e)}")
+    return e
+
+
+def _check_segments(who, L, dv):
+    if not (1 <= int(L) <= 4096 and float(dv) > 0.0 and np.isfinite(float(dv))):
+        raise QFAHipError(f"{who}: segments L = {L}, dv = {dv}")
+
+
+def _band_map(L, dv, k_edges):
+    """(band, count): the (M,) int32 band of mode m = 1 .. M (entry m - 1; -1 = in no band) and the (nband,) int64 number of
+    modes per band, as numpy arrays"""
+    e = np.asarray(k_edges, np.float64)
+    a = np.searchsorted(e, _mode_k(L, dv), side="right") - 1
+    band = np.where((a >= 0) & (a < len(e) - 1), a, -1).astype(np.int32)
+    return band, np.bincount(band[band >= 0], minlength=len(e) - 1).astype(np.int64)
+
+
+class _DrawStack(object):
+    """What the three stacks share: ``buf`` = (S, ...) contiguous float64 sums per draw of the continuum -- sums only, which is
+    what data parallelism all-reduces -- over the z-bins [z0 + i dz, z0 + (i + 1) dz), z0 and dz as the float32 numbers the
+    kernels bin with.  A class adds its layout (``_like``, ``same_layout``) and, where it is not ``mean``, the per-draw quantity
+    the statistics over the draws are taken of (``_per_draw``)."""
+
+    @staticmethod
+    def _round_bins(z0, dz, n):
+        """(z0, dz, n) as ``bins`` reports them: z0 and dz rounded to float32"""
+        return float(np.float32(z0)), float(np.float32(dz)), int(n)
+
+    def __init__(self, buf, z0, dz, n, tail):
+        """``tail``: the shape of ``buf`` behind its first axis"""
+        name = type(self).__name__
+        self.z0, self.dz, self._nbins = self._round_bins(z0, dz, n)
+        if buf.dtype != torch.float64 or buf.dim() != 3 or buf.shape[0] < 1 or tuple(buf.shape[1:]) != tuple(tail) \
+                or not buf.is_contiguous():
+            raise QFAHipError(f"{name}: buffer {tuple(buf.shape)} {buf.dtype}, expected contiguous float64 (S, {tail[0]}, {tail[1]})")
+        if not (self.dz > 0.0 and np.isfinite(self.dz) and np.isfinite(self.z0) and 1 <= self._nbins <= 4096):
+            raise QFAHipError(f"{name}: bins z0 = {z0}, dz = {dz}, n = {n}")
+        self.buf = buf
+
+    @property
+    def S(self):
+        return int(self.buf.shape[0])
+
+    @property
+    def bins(self):
+        return (self.z0, self.dz, self._nbins)
+
+    @property
+    def z_edges(self):
+        return self.z0 + self.dz * torch.arange(self._nbins + 1, dtype=torch.float64, device=self.buf.device)
+
+    @property
+    def z_centers(self):
+        return self.z0 + self.dz * (torch.arange(self._nbins, dtype=torch.float64, device=self.buf.device) + 0.5)
+
+    def _per_draw(self):
+        return self.mean
+
+    def _draws(self, what):
+        if self.S < 2:
+            raise QFAHipError(f"{type(self).__name__}.{what}: needs more than one draw of the continuum (S = {self.S})")
+        return self._per_draw()
+
+    @property
+    def mean_over_draws(self):
+        """mean of the per-draw result (``mean``; ``power()`` of a ``P1DStack``) over the S posterior draws of the continuum"""
+        return self._draws("mean_over_draws").mean(0)
+
+    def draws(self, s0, s1):
+        """the stack of draws [s0, s1): a view of the same buffer"""
+        return self._like(self.buf[s0:s1])
+
+    def clone(self):
+        return self._like(self.buf.clone())
+
+    def same_layout(self, other):
+        return isinstance(other, type(self)) and other.bins == self.bins
+
+    def add_(self, other):
+        if not self.same_layout(other) or other.S != self.S:
+            raise QFAHipError(f"{type(self).__name__}.add_: the other stack's bins / segments / bands / draws differ from "
+                              f"{self.bins}, {self.S}")
+        self.buf.add_(other.buf)
+        return self
+
+    def all_reduce(self, group=None):
+        """in-place sum over the process group (every rank calls it; an exhausted rank adds zeros)"""
+        from .distributed import all_reduce_accum
+        all_reduce_accum(self.buf.view(-1), group)
+        return self
+
+
+class ForestStack(_DrawStack):
+    """The redshift-binned stack of the forest transmission (include/qfa_hip.h, qfa_forest_f32): ``buf`` = (S, 4, nbin) float64
+    [sum w | sum w T | sum w T^2 | n] per draw of the continuum over the bins [z0 + k dz, z0 + (k + 1) dz)."""
+
+    def __init__(self, buf, z0, dz, nbin):
+        super().__init__(buf, z0, dz, nbin, (4, int(nbin)))
+        self.nbin = self._nbins
+
+    @classmethod
+    def zeros(cls, S, z0, dz, nbin, device):
+        return cls(torch.zeros((int(S), 4, int(nbin)), dtype=torch.float64, device=device), z0, dz, nbin)
+
+    def _like(self, buf):
+        return ForestStack(buf, self.z0, self.dz, self.nbin)
+
+    @property
+    def sum_w(self):
+        return self.buf[:, 0]
+
+    @property
+    def n(self):
+        """(S, nbin) number of pixels stacked"""
+        return self.buf[:, 3]
+
+    @property
+    def mean(self):
+        """(S, nbin) weighted mean transmission sum w T / sum w (NaN in an empty bin)"""
+        return self.buf[:, 1] / self.buf[:, 0]
+
+    @property
+    def var(self):
+        """(S, nbin) weighted variance of T inside the bin, sum w T^2 / sum w - mean^2"""
+        m = self.mean
+        return self.buf[:, 2] / self.buf[:, 0] - m * m
+
+    @property
+    def tau_eff(self):
+        """(S, nbin) effective optical depth -ln <T>"""
+        return -torch.log(self.mean)
+
+    @property
+    def std_over_draws(self):
+        """(nbin,) standard deviation of ``mean`` over the S draws: the continuum posterior's error bar on the stack (the
+        continuum errors of a spectrum's pixels are correlated, which repeating the whole stack per draw carries through)"""
+        return self._draws("std_over_draws").std(0, unbiased=True)
+
+
+class _SegmentStack(_DrawStack):
+    """A stack over segments of ``L`` pixels ``dv`` km/s wide, M = L // 2 modes k_m = 2 pi m / (L dv): ``buf`` = (S, nz, width),
+    the number of segments stacked first."""
+
+    def __init__(self, buf, z0, dz, nz, L, dv, width):
+        self.L, self.dv = int(L), float(dv)
+        self.M = self.L // 2
+        super().__init__(buf, z0, dz, nz, (int(nz), width))
+        self.nz = self._nbins
+        _check_segments(type(self).__name__, L, dv)
+
+    @property
+    def n(self):
+        """(S, nz) number of segments stacked"""
+        return self.buf[:, :, 0]
+
+    def same_layout(self, other):
+        return super().same_layout(other) and other.L == self.L and other.dv == self.dv
+
+
+class P1DStack(_SegmentStack):
+    """The (k, z) stack of the 1D flux power spectrum (include/qfa_hip.h, qfa_p1d_f32): ``buf`` = (S, nz, 2 + 2M) float64
+    [n | sum N | sum P_1..M | sum P^2_1..M] per draw of the continuum and z-bin."""
+
+    def __init__(self, buf, z0, dz, nz, L, dv=1.0):
+        super().__init__(buf, z0, dz, nz, L, dv, 2 + 2 * (int(L) // 2))
+
+    @classmethod
+    def zeros(cls, S, z0, dz, nz, L, dv, device):
+        return cls(torch.zeros((int(S), int(nz), 2 + 2 * (int(L) // 2)), dtype=torch.float64, device=device), z0, dz, nz, L, dv)
+
+    def _like(self, buf):
+        return P1DStack(buf, self.z0, self.dz, self.nz, self.L, self.dv)
+
+    @property
+    def k(self):
+        """(M,) wavenumbers 2 pi m / (L dv), m = 1 .. M, in s/km"""
+        return torch.tensor(_mode_k(self.L, self.dv), dtype=torch.float64, device=self.buf.device)
+
+    @property
+    def noise(self):
+        """(S, nz) mean noise level <N> of the stacked segments, in pixel units (NaN in an empty bin)"""
+        return self.buf[:, :, 1] / self.n
+
+    @property
+    def power_raw(self):
+        """(S, nz, M) mean |delta~_m|^2 / L of the stacked segments, in pixel units, noise included"""
+        return self.buf[:, :, 2:2 + self.M] / self.n[:, :, None]
+
+    def window2(self, resolution_kms):
+        """(M,) W^2(k): the pixel's sinc times a Gaussian of ``resolution_kms`` (1 sigma), squared"""
+        return _window2(self.k, self.dv, resolution_kms)
+
+    def power(self, resolution_kms=None):
+        """(S, nz, M) P1D in km/s: (power_raw - noise) dv, divided by ``window2(resolution_kms)`` when that is given"""
+        P = (self.power_raw - self.noise[:, :, None]) * self.dv
+        return P if resolution_kms is None else P / self.window2(resolution_kms)
+
+    def err(self, resolution_kms=None):
+        """(S, nz, M) standard error of ``power`` from the scatter of the segments: sqrt((<P^2> - <P>^2) / (n - 1)) dv"""
+        m2 = self.buf[:, :, 2 + self.M:] / self.n[:, :, None]
+        var = (m2 - self.power_raw ** 2).clamp_min(0.0) / (self.n[:, :, None] - 1.0)
+        e = torch.sqrt(var) * self.dv
+        e = torch.where(self.n[:, :, None] > 1.0, e, torch.full_like(e, float("nan")))
+        return e if resolution_kms is None else e / self.window2(resolution_kms)
+
+    def _per_draw(self):
+        return self.power()
+
+    @property
+    def std_over_draws(self):
+        """(nz, M) standard deviation of ``power()`` over the S draws: the continuum posterior's error bar on P1D"""
+        return self._draws("std_over_draws").std(0, unbiased=True)
+
+
+class P1DBandStack(_SegmentStack):
+    """The stack of band powers of the 1D flux power spectrum and of their outer products (include/qfa_hip.h, qfa_p1d_band_f32):
+    ``buf`` = (S, nz, 1 + nband + nband^2) float64 [n | sum Q_a | sum Q_a Q_b] per draw of the continuum and z-bin.  Band a holds
+    the modes with ``k_edges[a] <= k_m < k_edges[a + 1]``, k_m in s/km; Q_a is the band's mean power of one segment in km/s
+    (``QFA.p1d_bands`` folds dv, 1 / n_a and the window into the weights)."""
+
+    def __init__(self, buf, z0, dz, nz, L, dv, k_edges):
+        self._k_edges = _edges(k_edges)
+        self.nband = len(self._k_edges) - 1
+        super().__init__(buf, z0, dz, nz, L, dv, 1 + self.nband + self.nband ** 2)
+
+    @classmethod
+    def zeros(cls, S, z0, dz, nz, L, dv, k_edges, device):
+        nband = len(_edges(k_edges)) - 1
+        return cls(torch.zeros((int(S), int(nz), 1 + nband + nband * nband), dtype=torch.float64, device=device), z0, dz, nz, L, dv,
+                   k_edges)
+
+    @staticmethod
+    def linear_k_edges(L, dv, nband):
+        """nband + 1 edges of equal bands from the fundamental to Nyquist: mode m sits at m k_1 inside [k_1 / 2, (M + 1 / 2) k_1)"""
+        return 2.0 * np.pi / (int(L) * float(dv)) * np.linspace(0.5, int(L) // 2 + 0.5, int(nband) + 1)
+
+    def _like(self, buf):
+        return P1DBandStack(buf, self.z0, self.dz, self.nz, self.L, self.dv, self._k_edges)
+
+    def same_layout(self, other):
+        return super().same_layout(other) and other._k_edges == self._k_edges
+
+    @property
+    def k_edges(self):
+        """(nband + 1,) band edges in s/km"""
+        return torch.tensor(self._k_edges, dtype=torch.float64, device=self.buf.device)
+
+    def band_map(self):
+        """(band, count): the (M,) int32 band of mode m = 1 .. M (entry m - 1; -1 = in no band) and the (nband,) int64 number of
+        modes per band, as numpy arrays"""
+        return _band_map(self.L, self.dv, self._k_edges)
+
+    @property
+    def k_centers(self):
+        """(nband,) mean wavenumber of a band's modes in s/km (NaN for a band without modes)"""
+        band, count = self.band_map()
+        tot = np.bincount(band[band >= 0], weights=_mode_k(self.L, self.dv)[band >= 0], minlength=self.nband)
+        with np.errstate(all="ignore"):
+            c = np.where(count > 0, tot / count, np.nan)
+        return torch.tensor(c, dtype=torch.float64, device=self.buf.device)
+
+    @property
+    def mean(self):
+        """(S, nz, nband) mean band power of the stacked segments (NaN in an empty bin)"""
+        return self.buf[:, :, 1:1 + self.nband] / self.n[:, :, None]
+
+    @property
+    def cov(self):
+        """(S, nz, nband, nband) covariance of ``mean`` from the scatter of the segments: (<Q Q^T> - <Q> <Q>^T) / (n - 1); NaN
+        where n < 2"""
+        n = self.n[:, :, None, None]
+        m2 = self.buf[:, :, 1 + self.nband:].reshape(self.S, self.nz, self.nband, self.nband) / n
+        mu = self.mean
+        c = (m2 - mu[:, :, :, None] * mu[:, :, None, :]) / (n - 1.0)
+        return torch.where(n > 1.0, c, torch.full_like(c, float("nan")))
+
+    @property
+    def err(self):
+        """(S, nz, nband) standard error of ``mean``: the root of the diagonal of ``cov``"""
+        return torch.sqrt(torch.diagonal(self.cov, dim1=2, dim2=3).clamp_min(0.0))
+
+    @property
+    def corr(self):
+        """(S, nz, nband, nband) correlation matrix of the bands: cov_ab / sqrt(cov_aa cov_bb)"""
+        c = self.cov
+        d = torch.sqrt(torch.diagonal(c, dim1=2, dim2=3).clamp_min(0.0))
+        return c / (d[:, :, :, None] * d[:, :, None, :])
+
+    @property
+    def cov_over_draws(self):
+        """(nz, nband, nband) covariance of ``mean`` over the S draws: the continuum posterior's covariance of the band powers"""
+        d = self._draws("cov_over_draws")
+        d = d - d.mean(0, keepdim=True)
+        return torch.einsum("sza,szb->zab", d, d) / (self.S - 1.0)
+
+    @property
+    def total_cov(self):
+        """(nz, nband, nband) the mean over the draws of ``cov`` plus ``cov_over_draws``"""
+        return self.cov.mean(0) + self.cov_over_draws

@@ -1,0 +1,367 @@
+"""The forest statistics of ``QFA``: transmission and its redshift-binned stack (``forest`` / ``mean_transmission``), the 1D flux
+power spectrum (``p1d`` / ``flux_power``) and its band powers (``p1d_bands`` / ``band_power``).  ``ForestStatistics`` is a plain
+base class of ``qfa_amd.model.QFA`` and uses the model's plumbing (``_batch_struct*``, ``_scratch``, ``predict``, ``sample_latent``,
+``_loader_slices``) as any other method of it does; every call goes through the C-ABI in ``include/qfa_hip.h``."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import QFAHipError, _ptr
+from .stacks import ForestStack, P1DBandStack, P1DStack, _band_map, _check_segments, _edges, _mode_k, _window2
+
+f32 = torch.float32
+
+
+def _p1d_params(tbar_bins, St, p_lo, L, nseg, min_used, stack):
+    """qfa_p1d_t of `p1d` and `p1d_bands`: the bins of tbar, the segments and the z-bins of ``stack`` (None: one unused bin)"""
+    pp = _lib.P1DParams()
+    pp.zT0, pp.dzT, pp.nT = ForestStack._round_bins(tbar_bins[0], tbar_bins[1], tbar_bins[2])
+    pp.St = St
+    pp.p_lo, pp.seg_len, pp.nseg, pp.min_used = p_lo, L, nseg, int(min_used)
+    pp.z0, pp.dz, pp.nz = stack.bins if stack is not None else (0.0, 1.0, 1)
+    return pp
+
+
+class ForestStatistics(object):
+
+    # ------------------------------------------------------------------ forest transmission
+    def forest(self, flux=None, error=None, zabs=None, mask=None, *, h=None, hmean=None, hcov=None, n_samples=0, seed=0, offset=0,
+               unc=None, bins=None, cont_min=0.0, pixel_range=None, unit_weights=False, stack=None, zfac=None, batch=None,
+               return_pixels=True):
+        """Lyman-alpha forest transmission T = flux / continuum on the blue side and its redshift-binned stack, for every draw of
+        the continuum, without writing a continuum (qfa_forest_f32; the contract is in include/qfa_hip.h).
+        The latent: ``h`` (B, S, Nh) as it is; else ``hmean`` alone (or with ``hcov`` and ``n_samples`` = 0): the posterior-mean
+        continuum, S = 1; else ``hmean`` + ``hcov`` + ``n_samples`` > 0 through ``sample_latent`` (``seed``, ``offset`` = the
+        global row of spectrum 0); with none of them ``predict`` runs on the inputs first, and its ``unc`` -- the continuum's
+        1 sigma, which enters ivar -- is passed on when S = 1.  ``bins`` = (z0, dz, nbin) asks for the stack; ``stack``: a
+        ``ForestStack`` to ADD to (its bins are used).  ``pixel_range`` = (p_lo, p_hi) restricts the stacked blue pixels,
+        ``unit_weights`` stacks with w = 1 instead of w = ivar, ``cont_min``: pixels whose continuum is not above it are unused.
+        ``mask`` None: every pixel is used.  A zabs tensor is read as given (never swapped for derived factors: the bins are
+        defined bit for bit by z).  Returns (trans, ivar, stack): (B, S, Nb) float32 each (None with ``return_pixels`` False) and
+        the ``ForestStack`` (None when neither ``bins`` nor ``stack`` was given)."""
+        if self.mu is None:
+            raise QFAHipError("forest needs model.mu (load_from_npz or train first)")
+        if hcov is not None and hmean is None:
+            raise QFAHipError("forest: hcov without hmean")
+        if h is not None and hmean is not None:
+            raise QFAHipError("forest: pass h or hmean / hcov, not both")
+        S = int(n_samples)
+        if S < 0:
+            raise QFAHipError(f"forest: n_samples = {n_samples}, expected >= 0")
+        if S > 0 and h is None and hmean is not None and hcov is None:
+            raise QFAHipError("forest: n_samples > 0 needs hcov next to hmean")
+        if bins is None and stack is None and not return_pixels:
+            raise QFAHipError("forest: nothing asked for (no bins, no stack, return_pixels = False)")
+        dev = self.device
+        self._params_struct()                                   # (F as a contiguous float32 device tensor)
+        if h is None and hmean is None:
+            _, hmean, hcov, _, punc = self.predict(flux, error, zabs, mask, zfac=zfac, batch=batch)
+            if S == 0 and unc is None:
+                unc = punc
+        if batch is not None:
+            B = batch.B
+            bs, keep = self._batch_struct_rows(batch, raw_flux=True)
+        else:
+            if not isinstance(flux, torch.Tensor) or flux.dim() != 2:
+                raise QFAHipError("forest: flux must be a (B, Npix) tensor")
+            B = self._check_batch_shapes(flux, error, zabs, mask if mask is not None else flux)
+            bs, keep = self._batch_struct(flux, error, zabs, mask, zfac, allow_no_mask=True, auto_factor=False)
+        bs.A_blue = None                                        # (not read by the call)
+        if h is None:
+            if tuple(hmean.shape) != (B, self.Nh):
+                raise QFAHipError(f"hmean: shape {tuple(hmean.shape)}, expected ({B}, {self.Nh})")
+            if S > 0:
+                h = self.sample_latent(hmean, hcov, S, seed=seed, offset=offset)
+            else:
+                S = 1
+                h = hmean.reshape(B, 1, self.Nh)
+        else:
+            if h.dim() != 3 or h.shape[0] != B or h.shape[2] != self.Nh or h.shape[1] < 1 or (S > 0 and h.shape[1] != S):
+                raise QFAHipError(f"h: shape {tuple(h.shape)}, expected ({B}, {S if S > 0 else 'S'}, {self.Nh})")
+            S = int(h.shape[1])
+        ph = _lib.require_device_tensor(h, f32, "h")
+        pu = None
+        if unc is not None:
+            if tuple(unc.shape) != (B, self.Npix):
+                raise QFAHipError(f"unc: shape {tuple(unc.shape)}, expected ({B}, {self.Npix})")
+            pu = _lib.require_device_tensor(unc, f32, "unc")
+        if stack is not None:
+            if not isinstance(stack, ForestStack) or stack.S != S or (bins is not None and ForestStack._round_bins(*bins) != stack.bins):
+                raise QFAHipError(f"forest(stack=...): expected a ForestStack of {S} draws on the same bins")
+            _lib.require_device_tensor(stack.buf, torch.float64, "stack")
+        elif bins is not None:
+            stack = ForestStack.zeros(S, bins[0], bins[1], bins[2], dev)
+        fb = _lib.ForestBins()
+        fb.z0, fb.dz, fb.nbin = stack.bins if stack is not None else (0.0, 1.0, 1)
+        p_lo, p_hi = (0, self.Nb) if pixel_range is None else (int(pixel_range[0]), int(pixel_range[1]))
+        if not 0 <= p_lo <= p_hi <= self.Nb:
+            raise QFAHipError(f"forest: pixel_range = {pixel_range}, expected 0 <= p_lo <= p_hi <= {self.Nb}")
+        fb.p_lo, fb.p_hi = p_lo, p_hi
+        trans = ivar = None
+        if return_pixels:
+            trans = torch.empty((B, S, self.Nb), dtype=f32, device=dev)
+            ivar = torch.empty((B, S, self.Nb), dtype=f32, device=dev)
+        mu = self.mu.to(device=dev, dtype=f32).contiguous()
+        need = _lib.lib().qfa_forest_workspace_bytes(B, S, self.Npix, self.Nb, self.Nh, int(fb.nbin))
+        if need == 0:
+            raise QFAHipError(f"forest: unsupported shape B={B} S={S} Npix={self.Npix} Nb={self.Nb} Nh={self.Nh} nbin={fb.nbin}")
+        ws = self._scratch("forest_ws", need)
+        _lib.check(_lib.lib().qfa_forest_f32(
+            _lib.require_device_tensor(self.F, f32, "F"), _ptr(mu), C.byref(bs), ph, pu, B, S, self.Npix, self.Nb, self.Nh,
+            C.byref(fb), float(cont_min), _lib.F_FOREST_UNIT_W if unit_weights else 0, _ptr(trans), _ptr(ivar),
+            _ptr(stack.buf) if stack is not None else None, _ptr(ws), ws.numel(), _lib.current_stream(dev)), "qfa_forest_f32")
+        return trans, ivar, stack
+
+    def mean_transmission(self, dataloader, z_min, z_max, n_bins, n_samples=0, seed=0, batch_size=4096, cont_min=0.0,
+                          pixel_range=None, unit_weights=False):
+        """The stacked forest transmission of a whole dataloader in ``n_bins`` bins of [z_min, z_max): a ``ForestStack`` of S =
+        max(1, n_samples) draws.  ``n_samples`` = 0 stacks the posterior-mean continuum (``predict``'s unc enters the weights);
+        ``n_samples`` > 0 repeats the stack over that many posterior draws of every continuum (``std_over_draws``: the
+        continuum's error bar on the stack).  It walks the loader the way ``predict_to_npz`` does (the resident rows form when
+        the loader has one); the global row of a spectrum is its dataloader index, so the result does not depend on
+        ``batch_size`` beyond the rounding of float64 sums.  Under data parallelism the sums are all-reduced over the model's
+        group: every rank returns the global stack."""
+        n_bins, S = int(n_bins), max(1, int(n_samples))
+        if n_bins < 1 or not float(z_max) > float(z_min):
+            raise QFAHipError(f"mean_transmission: bins [{z_min}, {z_max}) / {n_bins}")
+        stack = ForestStack.zeros(S, z_min, (float(z_max) - float(z_min)) / n_bins, n_bins, self.device)
+        row0 = int(getattr(dataloader, "_row0", 0))              # (a data-parallel loader: the global index of its first row)
+        for s, inputs, _ in self._loader_slices(dataloader, int(batch_size)):
+            _, hmean, hcov, _, unc = self.predict(**inputs)
+            self.forest(**inputs, hmean=hmean, hcov=hcov, n_samples=int(n_samples), seed=seed, offset=row0 + s,
+                        unc=unc if int(n_samples) == 0 else None, cont_min=cont_min, pixel_range=pixel_range,
+                        unit_weights=unit_weights, stack=stack, return_pixels=False)
+        if self._dp:
+            stack.all_reduce(self._dp_group)
+        return stack
+
+    # ------------------------------------------------------------------ 1D flux power spectrum
+    P1D_PAIR_BYTES = 1 << 30    # flux_power: the most the (B, S_chunk, Nb) trans / ivar pair of a slice may take
+
+    def _p1d_inputs(self, what, asked, trans, ivar, zabs, zfac, batch, tbar, tbar_bins):
+        """the checks and conversions `p1d` and `p1d_bands` share: (B, S, tbar (St, nT) float32, St, tbar_bins, qfa_batch_t, the
+        tensors it points into); ``asked``: whether the call has an output at all"""
+        dev = self.device
+        if not asked:
+            raise QFAHipError(what + ": nothing asked for (no bins, no stack, return_segments = False)")
+        if not isinstance(trans, torch.Tensor) or trans.dim() != 3 or trans.shape[2] != self.Nb or tuple(ivar.shape) != tuple(trans.shape):
+            raise QFAHipError(f"{what}: trans / ivar must be (B, S, {self.Nb}) tensors")
+        B, S = int(trans.shape[0]), int(trans.shape[1])
+        if isinstance(tbar, ForestStack):
+            if tbar.S not in (1, S):
+                raise QFAHipError(f"{what}: tbar has {tbar.S} draws, expected 1 or {S}")
+            tbar_bins, tbar = tbar.bins, tbar.mean
+        if tbar_bins is None:
+            raise QFAHipError(what + ": a tbar tensor needs tbar_bins = (z0, dz, nT)")
+        tbar = tbar.to(device=dev, dtype=f32).reshape(-1, int(tbar_bins[2])).contiguous()
+        St = int(tbar.shape[0])
+        if St not in (1, S):
+            raise QFAHipError(f"{what}: tbar has {St} rows, expected 1 or {S}")
+        if batch is not None:
+            if batch.B != B:
+                raise QFAHipError(f"{what}: resident batch of {batch.B} spectra, trans has {B}")
+            bs, keep = self._batch_struct_rows(batch, need_src=False)
+        else:
+            bs, keep = _lib.Batch(), []
+            bs.row_stride = 0
+            if zfac is None:
+                zfac = getattr(zabs, "zfac", None)              # (what a DeviceDataloader attaches)
+            # _batch_struct's condition, so that p1d bins on the very z `forest` and `mean_transmission` binned on
+            if zfac is not None and not (self._tau_callable is None and self.use_factored_z):
+                if zabs is None:
+                    raise QFAHipError("zabs is None and no usable zfac = (zq1, pix_ratio) was given")
+                zfac = None
+            if zfac is None and zabs is not None:
+                if tuple(zabs.shape) != (B, self.Nb):
+                    raise QFAHipError(f"zabs: shape {tuple(zabs.shape)}, expected ({B}, {self.Nb})")
+                zabs = zabs if (zabs.dtype == f32 and zabs.is_contiguous()) else zabs.to(f32).contiguous()
+                keep.append(zabs)
+                bs.zabs = _lib.require_device_tensor(zabs, f32, "zabs").value
+            elif zfac is not None:
+                zq1, ratio = (t if (t.dtype == f32 and t.is_contiguous()) else t.to(f32).contiguous() for t in zfac)
+                if tuple(zq1.shape) != (B,) or tuple(ratio.shape) != (self.Nb,):
+                    raise QFAHipError(f"zfac shapes {tuple(zq1.shape)}, {tuple(ratio.shape)}: expected ({B},), ({self.Nb},)")
+                keep += [zq1, ratio]
+                bs.zq1 = _lib.require_device_tensor(zq1, f32, "zq1").value
+                bs.pix_ratio = _lib.require_device_tensor(ratio, f32, "pix_ratio").value
+            else:
+                raise QFAHipError(what + ": pass zabs, zfac = (zq1, pix_ratio) or batch")
+        return B, S, tbar, St, tbar_bins, bs, keep
+
+    def p1d(self, trans, ivar, *, zabs=None, zfac=None, batch=None, tbar, tbar_bins=None, seg_len, n_segments, pixel_start=0,
+            min_used, bins=None, stack=None, return_segments=True, dv=1.0):
+        """The 1D flux power spectrum of forest segments and its (k, z) stack (qfa_p1d_f32; the contract is in include/qfa_hip.h).
+        ``trans``, ``ivar`` (B, S, Nb) as ``forest`` returns them; the redshift of the pixels from ``zabs`` (B, Nb), ``zfac`` =
+        (zq1, pix_ratio) or a resident ``batch``.  ``tbar``: the mean transmission the contrast delta_F = T / tbar - 1 is formed
+        with -- a ``ForestStack`` (its ``mean`` per draw: one row per draw when it has S draws, else its single row for every
+        draw) or a (St, nT) / (nT,) tensor over ``tbar_bins`` = (z0, dz, nT).  Segment g holds the ``seg_len`` pixels from
+        ``pixel_start`` + g ``seg_len`` on and is used when at least ``min_used`` of them are.  ``bins`` = (z0, dz, nz) asks for
+        the stack (``dv``: the pixel width in km/s it reports k and P in); ``stack``: a ``P1DStack`` to ADD to.  Returns
+        (power (B, S, n_segments, M), noise (B, S, n_segments), stack): float32 P_m = |delta~_m|^2 / L for m = 1 .. M = seg_len // 2
+        and the noise level, both in pixel units (None with ``return_segments`` False), and the ``P1DStack`` (or None)."""
+        dev = self.device
+        B, S, tbar, St, tbar_bins, bs, keep = self._p1d_inputs("p1d", bins is not None or stack is not None or return_segments,
+                                                               trans, ivar, zabs, zfac, batch, tbar, tbar_bins)
+        L, nseg = int(seg_len), int(n_segments)
+        if stack is not None:
+            if not isinstance(stack, P1DStack) or stack.S != S or stack.L != L or \
+                    (bins is not None and P1DStack._round_bins(bins[0], bins[1], bins[2]) != stack.bins):
+                raise QFAHipError(f"p1d(stack=...): expected a P1DStack of {S} draws and segments of {L} pixels on the same bins")
+            _lib.require_device_tensor(stack.buf, torch.float64, "stack")
+        elif bins is not None:
+            stack = P1DStack.zeros(S, bins[0], bins[1], bins[2], L, dv, dev)
+        pp = _p1d_params(tbar_bins, St, int(pixel_start), L, nseg, min_used, stack)
+        need = _lib.lib().qfa_p1d_workspace_bytes(B * S, S, self.Nb, L, nseg, int(pp.nz)) if L >= 1 and nseg >= 1 else 0
+        if need == 0:
+            raise QFAHipError(f"p1d: unsupported shape B={B} S={S} Nb={self.Nb} seg_len={L} n_segments={nseg} nz={pp.nz}")
+        ws = self._scratch("p1d_ws", need)
+        power = noise = None
+        if return_segments:
+            power = torch.empty((B, S, nseg, L // 2), dtype=f32, device=dev)
+            noise = torch.empty((B, S, nseg), dtype=f32, device=dev)
+        _lib.check(_lib.lib().qfa_p1d_f32(
+            _lib.require_device_tensor(trans, f32, "trans"), _lib.require_device_tensor(ivar, f32, "ivar"), C.byref(bs),
+            _ptr(tbar), B, S, self.Nb, C.byref(pp), 0, _ptr(power), _ptr(noise), _ptr(stack.buf) if stack is not None else None,
+            _ptr(ws), ws.numel(), _lib.current_stream(dev)), "qfa_p1d_f32")
+        return power, noise, stack
+
+    def _p1d_band_tables(self, L, dv, k_edges, resolution_kms):
+        """(band (M,) int32, weight (M,) float32) of qfa_p1d_band_t on the device, built once per (L, dv, k_edges, resolution):
+        weight_m = dv / (n_a W^2(k_m)) with n_a the number of modes of the band of mode m and W^2 = ``P1DStack.window2`` (1 without
+        a resolution), so that Q_a is the mean over the band's modes of the P1D in km/s"""
+        key = (int(L), float(dv), _edges(k_edges), None if resolution_kms is None else float(resolution_kms))
+        cache = self._p1d_band_cache
+        if key not in cache:
+            _check_segments("p1d_bands", L, dv)
+            band, count = _band_map(L, dv, key[2])
+            w = np.full(len(band), float(dv), np.float64) / np.maximum(count[np.maximum(band, 0)], 1)
+            if resolution_kms is not None:
+                w = w / _window2(_mode_k(L, dv), float(dv), resolution_kms)
+            w = np.where(band >= 0, w, 0.0).astype(np.float32)
+            if len(cache) >= 16:
+                cache.clear()
+            # (one entry more than the modes: a pointer to an empty tensor would be NULL at L = 1)
+            cache[key] = (torch.tensor(np.append(band, np.int32(-1)), device=self.device),
+                          torch.tensor(np.append(w, np.float32(0.0)), device=self.device))
+        return cache[key]
+
+    def p1d_bands(self, trans, ivar, *, zabs=None, zfac=None, batch=None, tbar, tbar_bins=None, seg_len, n_segments, pixel_start=0,
+                  min_used, bins=None, dv=1.0, k_edges, resolution_kms=None, subtract_noise=True, stack=None,
+                  return_segments=False):
+        """Band powers of the forest's P1D and the stack their covariance matrix comes from (qfa_p1d_band_f32; the contract is in
+        include/qfa_hip.h).  The inputs and keywords of ``p1d``; ``k_edges``: nband + 1 increasing band edges in s/km -- band a
+        holds the modes with k_edges[a] <= 2 pi m / (seg_len dv) < k_edges[a + 1].  Q_a of a segment is the mean over the band's
+        modes of (P_m - N) dv / W^2(k_m): ``subtract_noise`` False keeps the noise in, ``resolution_kms`` divides by
+        ``P1DStack.window2``.  ``bins`` = (z0, dz, nz) asks for the stack, ``stack``: a ``P1DBandStack`` to ADD to.  Returns
+        (bandpower (B, S, n_segments, nband) float64, or None without ``return_segments``; the ``P1DBandStack``, or None)."""
+        dev = self.device
+        B, S, tbar, St, tbar_bins, bs, keep = self._p1d_inputs("p1d_bands", bins is not None or stack is not None or return_segments,
+                                                               trans, ivar, zabs, zfac, batch, tbar, tbar_bins)
+        L, nseg = int(seg_len), int(n_segments)
+        if stack is not None:
+            if not isinstance(stack, P1DBandStack) or stack.S != S or stack.L != L or stack._k_edges != _edges(k_edges) or \
+                    (bins is not None and P1DBandStack._round_bins(*bins) != stack.bins):
+                raise QFAHipError(f"p1d_bands(stack=...): expected a P1DBandStack of {S} draws and segments of {L} pixels on the "
+                                  "same bins and bands")
+            _lib.require_device_tensor(stack.buf, torch.float64, "stack")
+            dv = stack.dv
+        elif bins is not None:
+            stack = P1DBandStack.zeros(S, bins[0], bins[1], bins[2], L, dv, k_edges, dev)
+        nband = len(_edges(k_edges)) - 1
+        band, weight = self._p1d_band_tables(L, dv, k_edges, resolution_kms)
+        pp = _p1d_params(tbar_bins, St, int(pixel_start), L, nseg, min_used, stack)
+        qq = _lib.P1DBandParams()
+        qq.nband, qq.band, qq.weight, qq.subtract_noise = nband, band.data_ptr(), weight.data_ptr(), 1 if subtract_noise else 0
+        need = _lib.lib().qfa_p1d_band_workspace_bytes(B * S, S, self.Nb, L, nseg, int(pp.nz), nband) if L >= 1 and nseg >= 1 else 0
+        if need == 0:
+            raise QFAHipError(f"p1d_bands: unsupported shape B={B} S={S} Nb={self.Nb} seg_len={L} n_segments={nseg} nz={pp.nz} "
+                              f"nband={nband}")
+        ws = self._scratch("p1d_ws", need)                        # (shared with p1d: both calls own it only while they run)
+        bandpower = torch.empty((B, S, nseg, nband), dtype=torch.float64, device=dev) if return_segments else None
+        _lib.check(_lib.lib().qfa_p1d_band_f32(
+            _lib.require_device_tensor(trans, f32, "trans"), _lib.require_device_tensor(ivar, f32, "ivar"), C.byref(bs),
+            _ptr(tbar), B, S, self.Nb, C.byref(pp), C.byref(qq), 0, _ptr(bandpower), _ptr(stack.buf) if stack is not None else None,
+            _ptr(ws), ws.numel(), _lib.current_stream(dev)), "qfa_p1d_band_f32")
+        return bandpower, stack
+
+    def flux_power(self, dataloader, z_min, z_max, n_zbins, *, n_segments=3, seg_len=None, min_used_frac=0.75, tbar=None,
+                   tbar_nbins=64, n_samples=0, seed=0, batch_size=4096, cont_min=0.0, dv=None):
+        """The 1D flux power spectrum of a whole dataloader: a ``P1DStack`` of S = max(1, n_samples) draws over ``n_zbins`` bins of
+        [z_min, z_max) in the redshift of a segment's central pixel.  The blue side is cut into ``n_segments`` segments of
+        ``seg_len`` pixels (default Nb // n_segments); a segment is used when ``min_used_frac`` of its pixels are.  ``tbar``: the
+        ``ForestStack`` the contrast is formed with; None runs ``mean_transmission`` first, with the same ``n_samples`` / ``seed``
+        and ``tbar_nbins`` bins that cover every pixel of a stacked segment, so that draw s of <T> is the same continuum draw as
+        draw s of T.  Per slice of the loader: ``predict``, ``forest`` and ``p1d``, the draws in chunks that keep the
+        (B, S_chunk, Nb) trans / ivar pair under ``P1D_PAIR_BYTES`` (1 GiB).  ``dv``: the pixel width in km/s, default
+        c ln(lambda_1 / lambda_0) of the loader's ``wav_grid``.  The global row of a spectrum is its dataloader index and the
+        reducer adds segments in order, so the result does not depend on ``batch_size`` beyond the rounding of float64 sums.
+        Under data parallelism the sums are all-reduced over the model's group: every rank returns the global stack."""
+        return self._power_of_loader("flux_power", dataloader, z_min, z_max, n_zbins, n_segments, seg_len, min_used_frac, tbar,
+                                     tbar_nbins, n_samples, seed, batch_size, cont_min, dv, None)
+
+    def band_power(self, dataloader, z_min, z_max, n_zbins, k_edges, *, n_segments=3, seg_len=None, min_used_frac=0.75, tbar=None,
+                   tbar_nbins=64, n_samples=0, seed=0, batch_size=4096, cont_min=0.0, dv=None, resolution_kms=None,
+                   subtract_noise=True):
+        """The band powers of a whole dataloader and their covariance: a ``P1DBandStack`` of S = max(1, n_samples) draws over
+        ``n_zbins`` bins of [z_min, z_max) and the bands ``k_edges`` (nband + 1 edges in s/km).  Everything else is
+        ``flux_power``'s: the same segments, mean transmission, draws and loop over the loader, with ``p1d_bands`` in the place of
+        ``p1d``.  The sums of a slice are formed in chunks of a fixed number of segments, so the result depends on ``batch_size``
+        only through the rounding of float64 sums.  Under data parallelism the sums are all-reduced over the model's group."""
+        return self._power_of_loader("band_power", dataloader, z_min, z_max, n_zbins, n_segments, seg_len, min_used_frac, tbar,
+                                     tbar_nbins, n_samples, seed, batch_size, cont_min, dv,
+                                     {"k_edges": k_edges, "resolution_kms": resolution_kms, "subtract_noise": subtract_noise})
+
+    def _power_of_loader(self, what, dataloader, z_min, z_max, n_zbins, n_segments, seg_len, min_used_frac, tbar, tbar_nbins,
+                         n_samples, seed, batch_size, cont_min, dv, bands):
+        """the loop `flux_power` (``bands`` None: a ``P1DStack`` through ``p1d``) and `band_power` (``bands``: the keywords of
+        ``p1d_bands``; a ``P1DBandStack``) share"""
+        nseg, nz, S = int(n_segments), int(n_zbins), max(1, int(n_samples))
+        L = int(seg_len) if seg_len is not None else (self.Nb // nseg if nseg > 0 else 0)
+        if nseg < 1 or L < 1 or nseg * L > self.Nb or nz < 1 or not float(z_max) > float(z_min) or not 0.0 < float(min_used_frac) <= 1.0:
+            raise QFAHipError(f"{what}: {nseg} segments of {L} pixels on Nb = {self.Nb}, bins [{z_min}, {z_max}) / {nz}, "
+                              f"min_used_frac = {min_used_frac}")
+        if dv is None:
+            wav = getattr(dataloader, "wav_grid", None)
+            if wav is None or len(wav) < 2:
+                raise QFAHipError(what + ": the dataloader has no wav_grid: pass dv (km/s per pixel)")
+            dv = 299792.458 * float(np.log(float(wav[1]) / float(wav[0])))
+        min_used = max(1, int(np.ceil(float(min_used_frac) * L)))
+        if tbar is None:
+            half = float(np.exp(0.5 * (L + 1) * float(dv) / 299792.458))          # (1 + z) over half a segment
+            tbar = self.mean_transmission(dataloader, (1.0 + float(z_min)) / half - 1.0, (1.0 + float(z_max)) * half - 1.0,
+                                          int(tbar_nbins), n_samples=int(n_samples), seed=seed, batch_size=batch_size,
+                                          cont_min=cont_min)
+        if not isinstance(tbar, ForestStack) or tbar.S not in (1, S):
+            raise QFAHipError(f"{what}: tbar must be a ForestStack of 1 or {S} draws")
+        tmean = tbar.mean.to(f32)
+        if bands is None:
+            stack = P1DStack.zeros(S, z_min, (float(z_max) - float(z_min)) / nz, nz, L, dv, self.device)
+        else:
+            stack = P1DBandStack.zeros(S, z_min, (float(z_max) - float(z_min)) / nz, nz, L, dv, bands["k_edges"], self.device)
+        row0 = int(getattr(dataloader, "_row0", 0))              # (a data-parallel loader: the global index of its first row)
+        for s, inputs, _ in self._loader_slices(dataloader, int(batch_size)):
+            _, hmean, hcov, _, unc = self.predict(**inputs)
+            B = int(hmean.shape[0])
+            if int(n_samples) > 0:
+                h, unc = self.sample_latent(hmean, hcov, S, seed=seed, offset=row0 + s), None
+            else:
+                h = hmean.reshape(B, 1, self.Nh)
+            Sc = max(1, min(S, self.P1D_PAIR_BYTES // max(1, B * self.Nb * 8)))
+            zin = {"batch": inputs["batch"]} if "batch" in inputs else {"zabs": inputs["zabs"]}
+            for s0 in range(0, S, Sc):
+                s1 = min(S, s0 + Sc)
+                hs = h if (s0 == 0 and s1 == S) else h[:, s0:s1].contiguous()
+                tr, iv, _ = self.forest(**inputs, h=hs, unc=unc, cont_min=cont_min)
+                kw = dict(tbar=tmean if tbar.S == 1 else tmean[s0:s1], tbar_bins=tbar.bins, seg_len=L, n_segments=nseg,
+                          min_used=min_used, stack=stack.draws(s0, s1), return_segments=False)
+                if bands is None:
+                    self.p1d(tr, iv, **zin, **kw)
+                else:
+                    self.p1d_bands(tr, iv, **zin, **kw, **bands)
+        if self._dp:
+            stack.all_reduce(self._dp_group)
+        return stack

@@ -373,3 +373,26 @@ def test_predict_to_npz_reads_the_resident_rows(dev, tmp_path):
     for r in (0, 17, 36):
         got = np.load(tmp_path / names[r])
         assert np.array_equal(got["cont"], cont[r].cpu().numpy()) and np.array_equal(got["ll"].ravel(), ll[r:r + 1].cpu().numpy())
+
+
+def test_predict_to_npz_reads_get_rows_without_factored_z(dev, tmp_path):
+    """use_factored_z off: the resident rows carry the factors, never zabs, so the writer walks the loader's get_rows slices (the
+    last one short); the files equal one predict call on the whole set bit for bit"""
+    import torch
+    dl, p, wav, nb, nr = _mock_loader(dev, 96, 3, 5, 2, seed=12, shuffle=False, mode="predict")
+    from qfa_amd import QFA
+    m = QFA(nb, nr, 3, dev, model_params=p)
+    m.mu = torch.tensor(np.asarray(dl.mu), dtype=torch.float32, device=dev)
+    m.use_factored_z = False
+
+    def refuse(*a, **k):
+        raise AssertionError("predict_to_npz took the resident rows with use_factored_z off")
+    dl.rows_batch = refuse
+    names = m.predict_to_npz(dl, str(tmp_path), batch_size=2)
+    assert len(names) == 5
+    f, e, z, mk, _ = dl.get_rows(0, 5)
+    ll, hm, hc, cont, unc = (x.cpu().numpy() for x in m.predict(f, e, z, mk))
+    for r in range(5):
+        got = np.load(tmp_path / names[r])
+        assert np.array_equal(got["ll"].ravel(), ll[r:r + 1]) and np.array_equal(got["hmean"].ravel(), hm[r])
+        assert np.array_equal(got["hcov"], hc[r]) and np.array_equal(got["cont"], cont[r]) and np.array_equal(got["uncertainty"], unc[r])
