@@ -470,7 +470,50 @@ int qfa_p1d_band_f32(const float *trans, const float *ivar, const qfa_batch_t *b
                      const qfa_p1d_t *p, const qfa_p1d_band_t *q, unsigned flags, double *bandpower, double *stack,
                      void *workspace, size_t workspace_bytes, void *stream);
 
-/* Replaces Adam.update (reference QFA/optimizer.py:37-52) followed by the clamp of QFA.clip
+/* The pair-weighted correlation function of the forest along the line of sight, xi(l), and its (lag, z) stack, per posterior draw
+ * (additive to ABI v4).  Every estimator above is a Fourier one: a masked pixel enters it as d = 0, and the power it reports is
+ * convolved with the mask's window.  The statistic without a window is xi(l) = sum_j w_j w_{j+l} d_j d_{j+l} / sum_j w_j w_{j+l}: a
+ * masked pixel has w = 0 and leaves the numerator and the normaliser alike.  It is the real-space partner of P1D, where metal lines
+ * show as bumps at their velocity separation (SiIII at 2271 km/s), and its scatter over the draws is the continuum's error bar on it.
+ * This call takes qfa_p1d_f32's inputs and writes the pair sums of every segment and their stack, without ever writing delta_F.
+ *
+ * The contract.  trans, ivar, b, tbar, B, S, Nb and p are qfa_p1d_f32's, bit for bit: `used`, d and v of a pixel, n_used, validity
+ * (n_used >= min_used) and the z-bin kz of a segment (at its central pixel p_lo + g L + L / 2) are those of that call, with its rules
+ * on the redshift forms and on NaN under the mask.  L = seg_len, lags l = 0 .. nlag - 1:
+ *   per pixel  float32, every operation rounded once, no contraction:  wv = 1 / (v + sigma2_lss) (an addition and a division);
+ *              w = used && isfinite(wv) ? wv : 0, or with QFA_F_XI_UNIT_W w = used ? 1 : 0, by selects;  x = w d;
+ *   segment    for a valid segment W_l = sum_j w_j w_{j+l}, A_l = sum_j x_j x_{j+l} over j = 0 .. L - 1 - l -- pairs never cross a
+ *              segment edge -- and N0 = sum_j (w_j w_j) v_j, the noise that sits in A_0.  float32 sums (fma chains); their order is
+ *              a function of (L, nlag) alone, never of the grid, B or S;
+ *   outputs    pairs (B S, nseg, 2, nlag) float32 = [W_l | A_l]; noise0 (B S, nseg) float32; an invalid segment gets exactly 0
+ *              everywhere.  stack (S, nz, 2 + 5 nlag) float64 = [n | sum N0 | sum W_l | sum A_l | sum W_l^2 | sum A_l W_l |
+ *              sum A_l^2] per draw and z-bin over the valid segments with 0 <= kz < nz; the three products are formed in float64
+ *              from the float32 rows, each rounded once.  xi_l = sum A_l / sum W_l (sum N0 taken off lag 0), and the last three
+ *              sums give the ratio's error from the scatter of the segments.  The call ADDS to `stack`; QFA_F_ZERO_ACCUM
+ *              overwrites.  Any of the three may be NULL, but not all;
+ *   sums       qfa_p1d_band_f32's: no float atomics; the segments of a draw, in order of (b, g) over the whole call, are cut into
+ *              chunks of qfa_p1d_band_chunk_segments(); a chunk's sums start from 0 and add its segments in order, leave through
+ *              the workspace, and a second kernel adds them in chunk order onto what `stack` holds.  The host cuts B on chunk
+ *              boundaries: two calls on the same inputs give the same bits, and draw s of a call of S draws gets the bits of a
+ *              call on that draw alone.
+ * qfa_xi_stack_doubles: S nz (2 + 5 nlag); 0 = unsupported (S < 1, nz outside 1..4096, nlag outside 1..4096).
+ * qfa_xi_workspace_bytes(R = B S, ...): qfa_p1d_workspace_bytes' shapes, and nlag outside 1..L, give 0.  The rows and the chunk
+ * partials of one launch aim at the cap of qfa_p1d_f32's rows; the least a launch holds is the fewest spectra whose segments fill
+ * whole chunks.
+ * Returns every code of qfa_p1d_f32 for the arguments they share; QFA_E_NULL also for x or all three outputs missing; QFA_E_SIZE
+ * also for nlag outside 1..seg_len or sigma2_lss negative or not finite; QFA_E_FLAGS for any flag other than QFA_F_ZERO_ACCUM,
+ * QFA_F_SYNC, QFA_F_XI_UNIT_W.  Argument checks return before any device work.  B = 0 does nothing, except zeroing `stack` under
+ * QFA_F_ZERO_ACCUM.  The call neither synchronises nor allocates. */
+typedef struct { int nlag; float sigma2_lss; } qfa_xi_t;      /* 1 <= nlag <= seg_len; sigma2_lss >= 0, finite */
+#define QFA_F_XI_UNIT_W 0x400u   /* qfa_xi_f32: w = 1 on a used pixel instead of 1 / (v + sigma2_lss) */
+
+size_t qfa_xi_stack_doubles(int S, int nz, int nlag);
+size_t qfa_xi_workspace_bytes(int R, int S, int Nb, int L, int nseg, int nz, int nlag);
+int qfa_xi_f32(const float *trans, const float *ivar, const qfa_batch_t *b, const float *tbar, int B, int S, int Nb,
+               const qfa_p1d_t *p, const qfa_xi_t *x, unsigned flags, float *pairs, float *noise0, double *stack,
+               void *workspace, size_t workspace_bytes, void *stream);
+
+/* Replaces Adam.update(reference QFA/optimizer.py:37-52) followed by the clamp of QFA.clip
  * (QFA/model.py:233-241) for ONE tensor of n elements:
  *   g' = g + wd*p; m = (1-b1) g' + b1 m; v = (1-b2) g'^2 + b2 v;
  *   p_out = clamp(p - lr * (m/bc1) / (sqrt(v/bc2) + eps), lo, hi),  bc = 1 - b^(i+1),

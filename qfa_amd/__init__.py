@@ -14,6 +14,7 @@ _LAZY = {
     "ForestStack": ("qfa_amd.model", "ForestStack"),
     "P1DStack": ("qfa_amd.model", "P1DStack"),
     "P1DBandStack": ("qfa_amd.model", "P1DBandStack"),
+    "XiStack": ("qfa_amd.model", "XiStack"),
     "Adam": ("qfa_amd.optimizer", "Adam"),
     "step_scheduler": ("qfa_amd.optimizer", "step_scheduler"),
 }

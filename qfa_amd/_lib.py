@@ -24,6 +24,7 @@ EXPORTS = (
     "qfa_forest_stack_doubles", "qfa_forest_workspace_bytes", "qfa_forest_f32",
     "qfa_p1d_stack_doubles", "qfa_p1d_workspace_bytes", "qfa_p1d_f32",
     "qfa_p1d_band_stack_doubles", "qfa_p1d_band_workspace_bytes", "qfa_p1d_band_chunk_segments", "qfa_p1d_band_f32",
+    "qfa_xi_stack_doubles", "qfa_xi_workspace_bytes", "qfa_xi_f32",
 )
 
 TAU_IDS = {"becker": 0, "fg": 1, "kamble": 2, "mock": 3}
@@ -33,6 +34,7 @@ F_PASS2_F32, F_PASS2_XDL, F_S3_FAST, F_PREDICT_F32, F_SYNC = 0x1, 0x2, 0x4, 0x8,
 F_PASS2_PIXRES = 0x40
 F_ZERO_ACCUM = 0x80
 F_FOREST_UNIT_W = 0x200    # qfa_forest_f32: stack with w = 1 instead of w = ivar
+F_XI_UNIT_W = 0x400        # qfa_xi_f32: w = 1 on a used pixel instead of 1 / (v + sigma2_lss)
 F_EXACT_GRAD = 0x100       # exact gradients of mean NLL (opt-in; QFA.exact_gradients); the buffer carries the mode in slot 6
 
 
@@ -74,6 +76,10 @@ class P1DParams(C.Structure):       # qfa_p1d_t
 
 class P1DBandParams(C.Structure):   # qfa_p1d_band_t
     _fields_ = [("nband", C.c_int), ("band", C.c_void_p), ("weight", C.c_void_p), ("subtract_noise", C.c_int)]
+
+
+class XiParams(C.Structure):        # qfa_xi_t
+    _fields_ = [("nlag", C.c_int), ("sigma2_lss", C.c_float)]
 
 
 _lib = None
@@ -149,6 +155,9 @@ def lib():
         "qfa_p1d_band_chunk_segments": (i, []),
         "qfa_p1d_band_f32": (i, [p, p, C.POINTER(Batch), p, i, i, i, C.POINTER(P1DParams), C.POINTER(P1DBandParams), C.c_uint, p, p,
                                  p, sz, p]),
+        "qfa_xi_stack_doubles": (sz, [i, i, i]),
+        "qfa_xi_workspace_bytes": (sz, [i, i, i, i, i, i, i]),
+        "qfa_xi_f32": (i, [p, p, C.POINTER(Batch), p, i, i, i, C.POINTER(P1DParams), C.POINTER(XiParams), C.c_uint, p, p, p, p, sz, p]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(h, name, None)

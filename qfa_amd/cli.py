@@ -97,6 +97,17 @@ def main(argv=None):
         raise ValueError("MODEL.P1D_NBANDS > 0 needs MODEL.P1D_SEGMENTS > 0 (the segments whose power is binned)")
     if cfg.TYPE == "predict" and not 0 <= int(cfg.MODEL.P1D_NBANDS) <= 64:
         raise ValueError("MODEL.P1D_NBANDS must lie in 0 .. 64")
+    if cfg.TYPE == "predict" and int(cfg.MODEL.XI_NLAGS) != 0:
+        if int(cfg.MODEL.XI_NLAGS) < 0 or int(cfg.MODEL.P1D_SEGMENTS) <= 0:
+            raise ValueError("MODEL.XI_NLAGS > 0 needs MODEL.P1D_SEGMENTS > 0 (the segments whose pixel pairs are summed)")
+        import numpy as np
+        from . import io
+        wav = io.wavelength_grid(cfg.DATA.LAMMIN, cfg.DATA.LAMMAX, cfg.DATA.LOGLAM_DELTA)
+        seg_len = int(np.sum(wav < 1215.67)) // int(cfg.MODEL.P1D_SEGMENTS)          # (the dataloader's Nb, flux_power's segments)
+        if int(cfg.MODEL.XI_NLAGS) > seg_len:
+            raise ValueError(f"MODEL.XI_NLAGS = {int(cfg.MODEL.XI_NLAGS)} exceeds the segment length {seg_len}")
+        if not float(cfg.MODEL.XI_SIGMA2_LSS) >= 0.0 or float(cfg.MODEL.XI_SIGMA2_LSS) == float("inf"):
+            raise ValueError("MODEL.XI_SIGMA2_LSS must be finite and >= 0")
     os.makedirs(cfg.DATA.OUTPUT_DIR, exist_ok=True)
     with open(os.path.join(cfg.DATA.OUTPUT_DIR, "config.yaml"), "w") as f:
         f.write(cfg.dump())
@@ -165,6 +176,15 @@ def main(argv=None):
                 if bs.S > 1:
                     out["cov_over_draws"] = bs.cov_over_draws.cpu().numpy()
                 np.savez(os.path.join(cfg.DATA.OUTPUT_DIR, "flux_power_bands.npz"), **out)
+            if int(cfg.MODEL.XI_NLAGS) > 0:
+                xs = model.flux_correlation(dataloader, float(cfg.MODEL.FOREST_ZMIN), float(cfg.MODEL.FOREST_ZMAX),
+                                            int(cfg.MODEL.P1D_NZBINS), int(cfg.MODEL.XI_NLAGS), n_segments=int(cfg.MODEL.P1D_SEGMENTS),
+                                            min_used_frac=float(cfg.MODEL.P1D_MIN_USED_FRAC), tbar=st, n_samples=int(cfg.MODEL.N_SAMPLES),
+                                            seed=int(cfg.MODEL.SAMPLE_SEED), sigma2_lss=float(cfg.MODEL.XI_SIGMA2_LSS))
+                np.savez(os.path.join(cfg.DATA.OUTPUT_DIR, "flux_correlation.npz"), lags_kms=xs.lags_kms.cpu().numpy(),
+                         z_centers=xs.z_centers.cpu().numpy(), z_edges=xs.z_edges.cpu().numpy(), xi=xs.xi().cpu().numpy(),
+                         xi_raw=xs.xi(subtract_noise=False).cpu().numpy(), err=xs.err().cpu().numpy(), n=xs.n.cpu().numpy(),
+                         sum_w=xs.sum_w.cpu().numpy(), seg_len=xs.L, dv=xs.dv, sums=xs.buf.cpu().numpy())
         print(f"Finish predicting {len(dataloader)} spectra in {time.time() - ts} seconds...")
     return 0
 

@@ -66,7 +66,12 @@ DEFAULTS = {                                        # reference QFA/config.py:15
               # not in the reference: P1D_NBANDS > 0 (needs P1D_SEGMENTS > 0) also writes flux_power_bands.npz, the power in
               # P1D_NBANDS equal bands of k from the fundamental to Nyquist and the covariance matrix between the bands per z-bin,
               # from the scatter of the segments and, when N_SAMPLES is set, over the posterior draws (QFA.band_power)
-              "P1D_NBANDS": 0},
+              "P1D_NBANDS": 0,
+              # not in the reference: XI_NLAGS > 0 (needs P1D_SEGMENTS > 0, at most the segment length) also writes
+              # flux_correlation.npz, the pair-weighted correlation function of the same segments at the lags 0 .. XI_NLAGS - 1
+              # pixels per z-bin, which carries no window of the mask; pixels are weighted by 1 / (noise variance + XI_SIGMA2_LSS)
+              # (QFA.flux_correlation)
+              "XI_NLAGS": 0, "XI_SIGMA2_LSS": 0.0},
     "TRAIN": {"NEPOCHS": 500, "LEARNING_RATE": 1e-3, "WEIGHT_DECAY": 1e-1, "DECAY_ALPHA": 0.9, "DECAY_STEP": 10,
               "WINDOW_LENGTH_FOR_MU": 16,
               # not in the reference: "em" = F by its closed-form EM update, Adam for the other parameters (QFA.train
@@ -88,7 +93,7 @@ ARG_KEYS = {
 # tests/golden/g12_config.json, extracted from the reference's config.py / main.py)
 EXTRA_KEYS = ("MODEL.REFERENCE_C0_QUIRK", "MODEL.N_SAMPLES", "MODEL.SAMPLE_SEED", "MODEL.N_REPLICATES", "MODEL.EXACT_GRADIENTS",
               "MODEL.FOREST", "MODEL.FOREST_ZMIN", "MODEL.FOREST_ZMAX", "MODEL.FOREST_NBINS", "MODEL.P1D_SEGMENTS",
-              "MODEL.P1D_NZBINS", "MODEL.P1D_MIN_USED_FRAC", "MODEL.P1D_NBANDS", "TRAIN.F_UPDATE", "TRAIN.EM_RHO", "TRAIN.EM_RIDGE")
+              "MODEL.P1D_NZBINS", "MODEL.P1D_MIN_USED_FRAC", "MODEL.P1D_NBANDS", "MODEL.XI_NLAGS", "MODEL.XI_SIGMA2_LSS", "TRAIN.F_UPDATE", "TRAIN.EM_RHO", "TRAIN.EM_RIDGE")
 
 
 def _set(cfg, dotted, value):

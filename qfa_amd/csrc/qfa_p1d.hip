@@ -1,9 +1,11 @@
 // qfa_p1d.hip -- C-ABI of the 1D flux power spectrum of forest segments and its (k, z) stack (include/qfa_hip.h:
 // qfa_p1d_stack_doubles, qfa_p1d_workspace_bytes, qfa_p1d_f32) and of its band powers and their covariance stack
 // (qfa_p1d_band_stack_doubles, qfa_p1d_band_workspace_bytes, qfa_p1d_band_chunk_segments, qfa_p1d_band_f32): argument checks, the
-// launch plans and the launches.  Kernels in qfa_p1d.h and qfa_p1d_band.h.
+// launch plans and the launches; and of the pair-weighted correlation function of the same segments and its (lag, z) stack
+// (qfa_xi_stack_doubles, qfa_xi_workspace_bytes, qfa_xi_f32).  Kernels in qfa_p1d.h, qfa_p1d_band.h and qfa_xi.h.
 #include "qfa_p1d.h"
 #include "qfa_p1d_band.h"
+#include "qfa_xi.h"
 #include "../../include/qfa_hip.h"
 
 #include <math.h>
@@ -71,7 +73,34 @@ BandPlan make_band_plan(int B, int S, int L, int nseg, int nz, int nband, bool p
     return P;
 }
 
-// the checks qfa_p1d_f32 and qfa_p1d_band_f32 share, in qfa_p1d_f32's order: sizes, then flags
+// The correlation call's cut, the band call's with other rows: launches of `Bc` spectra that end on chunk boundaries, sized so that
+// k_xi's rows (code, N0, [W | A]) and the chunk partials of one launch together aim at kRowsTarget; workspace = [code | N0 | pairs |
+// partials (chunks, S, nz, 2 + 5 nlag) from the next 8-byte boundary] from its first 16-byte boundary on.
+struct XiPlan {
+    int Bc;
+    size_t segs, chunks, bytes;                // segments and chunks (per draw) of a full launch
+};
+
+XiPlan make_xi_plan(int B, int S, int nseg, int nz, int nlag) {
+    namespace xi = qfa_xi;
+    XiPlan P;
+    int g = nseg, r = xi::kChunk;
+    while (r) { const int t = g % r; g = r; r = t; }
+    const size_t unit = (size_t)(xi::kChunk / g);
+    const size_t part_row = (size_t)S * nz * (size_t)(2 + 5 * nlag) * sizeof(double);
+    const size_t per_unit = unit * S * nseg * (size_t)(2 * nlag + 2) * 4 + (unit * nseg / xi::kChunk) * part_row;
+    size_t nu = kRowsTarget / per_unit;
+    if (nu < 1) nu = 1;
+    size_t bc = nu * unit;
+    if (bc > (size_t)(B > 0 ? B : 1)) bc = (size_t)(B > 0 ? B : 1);
+    P.Bc = (int)bc;
+    P.segs = bc * S * nseg;
+    P.chunks = (bc * nseg + xi::kChunk - 1) / xi::kChunk;
+    P.bytes = 16 + P.segs * (size_t)(2 * nlag + 2) * 4 + 8 + P.chunks * part_row;
+    return P;
+}
+
+// the checks qfa_p1d_f32, qfa_p1d_band_f32 and qfa_xi_f32 share, in qfa_p1d_f32's order: sizes, then flags
 int check_sizes(const qfa_batch_t *b, int B, int S, int Nb, const qfa_p1d_t *p) {
     if (B < 0 || S < 1 || Nb < 1 || (int64_t)B * S > INT32_MAX) return QFA_E_SIZE;
     if (p->seg_len < 1 || p->seg_len > kMaxLen || p->nseg < 1 || p->p_lo < 0 ||
@@ -245,6 +274,92 @@ int qfa_p1d_band_f32(const float *trans, const float *ivar, const qfa_batch_t *b
         if (stack) {
             pb::k_p1d_band_reduce<<<dim3((unsigned)(S * nz), (unsigned)((Wf + 255) / 256)), 256, 0, st>>>(part, chunks, S, nz, nband,
                                                                                                          zero, stack);
+            zero = 0;
+        }
+    }
+    if (flags & QFA_F_SYNC) {
+        hipError_t s = hipStreamSynchronize(st);
+        if (s != hipSuccess) { (void)hipGetLastError(); return (int)s; }
+    }
+    return (int)hipGetLastError();
+}
+
+size_t qfa_xi_stack_doubles(int S, int nz, int nlag) {
+    if (S < 1 || nz < 1 || nz > kMaxBins || nlag < 1 || nlag > kMaxLen) return 0;
+    return (size_t)S * nz * (size_t)(2 + 5 * nlag);
+}
+
+size_t qfa_xi_workspace_bytes(int R, int S, int Nb, int L, int nseg, int nz, int nlag) {
+    if (!shape_ok(R, S, Nb, L, nseg, nz) || nlag < 1 || nlag > L) return 0;
+    return make_xi_plan(R / S, S, nseg, nz, nlag).bytes;
+}
+
+int qfa_xi_f32(const float *trans, const float *ivar, const qfa_batch_t *b, const float *tbar, int B, int S, int Nb,
+               const qfa_p1d_t *p, const qfa_xi_t *x, unsigned flags, float *pairs, float *noise0, double *stack, void *workspace,
+               size_t workspace_bytes, void *stream) {
+    namespace xi = qfa_xi;
+    if (!trans || !ivar || !b || !tbar || !p || !workspace || !x || (!pairs && !noise0 && !stack)) return QFA_E_NULL;
+    const bool fac = b->zq1 || b->pix_ratio;
+    if (fac && !(b->zq1 && b->pix_ratio)) return QFA_E_NULL;
+    if (!fac && !b->zabs) return QFA_E_NULL;
+    if (int e = check_sizes(b, B, S, Nb, p)) return e;
+    if (x->nlag < 1 || x->nlag > p->seg_len || !(x->sigma2_lss >= 0.f) || !isfinite(x->sigma2_lss)) return QFA_E_SIZE;
+    if (flags & ~(QFA_F_ZERO_ACCUM | QFA_F_SYNC | QFA_F_XI_UNIT_W)) return QFA_E_FLAGS;
+    const int L = p->seg_len, nseg = p->nseg, nz = p->nz, nlag = x->nlag;
+    const XiPlan P = make_xi_plan(B, S, nseg, nz, nlag);
+    if (workspace_bytes < P.bytes) return QFA_E_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t Wd = (size_t)(2 + 5 * nlag);
+    int zero = (flags & QFA_F_ZERO_ACCUM) ? 1 : 0;
+    if (B == 0) {
+        if (stack && zero) {
+            hipError_t e = hipMemsetAsync(stack, 0, (size_t)S * nz * Wd * sizeof(double), st);
+            if (e != hipSuccess) return (int)e;
+        }
+        return 0;
+    }
+    int *code = (int *)(((uintptr_t)workspace + 15) & ~(uintptr_t)15);
+    float *nws = (float *)(code + P.segs);
+    float *pws = nws + P.segs;
+    double *part = (double *)(((uintptr_t)(pws + P.segs * 2 * (size_t)nlag) + 7) & ~(uintptr_t)7);
+    xi::Args a;
+    a.bt = *b;
+    a.trans = trans;
+    a.ivar = ivar;
+    a.tbar = tbar;
+    a.S = S; a.St = p->St; a.Nb = Nb; a.L = L; a.nlag = nlag; a.nseg = nseg; a.p_lo = p->p_lo; a.min_used = p->min_used;
+    a.nT = p->nT; a.nz = nz; a.factored = fac ? 1 : 0; a.unit_w = (flags & QFA_F_XI_UNIT_W) ? 1 : 0;
+    a.tile = xi::make_tile(L, nlag);
+    a.zT0 = p->zT0;
+    a.inv_dzT = 1.0f / p->dzT;
+    a.z0 = p->z0;
+    a.inv_dz = 1.0f / p->dz;
+    a.sigma2 = x->sigma2_lss;
+    xi::StackArgs sa;
+    sa.code = code;
+    sa.part = part;
+    sa.S = S; sa.nseg = nseg; sa.nlag = nlag; sa.nz = nz;
+    const size_t lds = (size_t)(a.tile.dup ? 4 : 2) * a.tile.Ls * sizeof(float);
+    // without a stack nothing is held between the kernels: one launch writes the caller's arrays
+    const int step = stack ? P.Bc : B;
+    for (int b0 = 0; b0 < B; b0 += step) {                                        // (with a stack every b0 nseg is a multiple of kChunk)
+        a.b0 = b0;
+        a.Bc = B - b0 < step ? B - b0 : step;
+        const size_t first = (size_t)b0 * S * nseg;                               // the launch's first segment
+        a.pairs = pairs ? pairs + first * 2 * (size_t)nlag : (stack ? pws : nullptr);
+        a.noise0 = noise0 ? noise0 + first : (stack ? nws : nullptr);
+        a.code = stack ? code : nullptr;
+        const size_t segs = (size_t)a.Bc * S * nseg;
+        const size_t gx = segs < ((size_t)1 << 20) ? segs : ((size_t)1 << 20);
+        xi::k_xi<<<dim3((unsigned)gx, (unsigned)((segs + gx - 1) / gx)), xi::kThreads, lds, st>>>(a);
+        if (stack) {
+            sa.pairs = a.pairs;
+            sa.noise0 = a.noise0;
+            sa.n = a.Bc * nseg;
+            const int chunks = (sa.n + xi::kChunk - 1) / xi::kChunk;
+            xi::k_xi_stack<<<(unsigned)((size_t)chunks * S), xi::kThreads, 0, st>>>(sa);
+            xi::k_xi_reduce<<<dim3((unsigned)(S * nz), (unsigned)((Wd + 255) / 256)), 256, 0, st>>>(part, chunks, S, nz, nlag, zero,
+                                                                                                   stack);
             zero = 0;
         }
     }

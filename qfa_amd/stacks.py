@@ -1,5 +1,5 @@
-"""The result classes of ``QFA``: ``EMStats`` and the three stacks of the forest statistics, ``ForestStack``, ``P1DStack`` and
-``P1DBandStack``.  Views and arithmetic on buffers the kernels filled (include/qfa_hip.h): nothing here calls the library or
+"""The result classes of ``QFA``: ``EMStats`` and the four stacks of the forest statistics, ``ForestStack``, ``P1DStack``,
+``P1DBandStack`` and ``XiStack``.  Views and arithmetic on buffers the kernels filled (include/qfa_hip.h): nothing here calls the library or
 needs a GPU, the classes work on CPU tensors as well.  ``qfa_amd.model`` re-exports the four names."""
 from __future__ import annotations
 
@@ -357,3 +357,73 @@ class P1DBandStack(_SegmentStack):
     def total_cov(self):
         """(nz, nband, nband) the mean over the draws of ``cov`` plus ``cov_over_draws``"""
         return self.cov.mean(0) + self.cov_over_draws
+
+
+class XiStack(_SegmentStack):
+    """The (lag, z) stack of the pair-weighted line-of-sight correlation function (include/qfa_hip.h, qfa_xi_f32): ``buf`` =
+    (S, nz, 2 + 5 nlag) float64 [n | sum N0 | sum W_l | sum A_l | sum W_l^2 | sum A_l W_l | sum A_l^2] per draw of the continuum and
+    z-bin, over segments of ``L`` pixels ``dv`` km/s wide; W_l and A_l are a segment's sums of w_j w_{j+l} and of
+    w_j w_{j+l} d_j d_{j+l}, N0 the noise in A_0."""
+
+    def __init__(self, buf, z0, dz, nz, L, n_lags, dv=1.0):
+        self.nlag = int(n_lags)
+        if not 1 <= self.nlag <= int(L):
+            raise QFAHipError(f"XiStack: {n_lags} lags on segments of {L} pixels")
+        super().__init__(buf, z0, dz, nz, L, dv, 2 + 5 * self.nlag)
+
+    @classmethod
+    def zeros(cls, S, z0, dz, nz, L, n_lags, dv, device):
+        return cls(torch.zeros((int(S), int(nz), 2 + 5 * int(n_lags)), dtype=torch.float64, device=device), z0, dz, nz, L, n_lags, dv)
+
+    def _like(self, buf):
+        return XiStack(buf, self.z0, self.dz, self.nz, self.L, self.nlag, self.dv)
+
+    def same_layout(self, other):
+        return super().same_layout(other) and other.nlag == self.nlag
+
+    def _part(self, i):
+        return self.buf[:, :, 2 + i * self.nlag:2 + (i + 1) * self.nlag]
+
+    @property
+    def lags_kms(self):
+        """(nlag,) velocity separations l dv in km/s"""
+        return self.dv * torch.arange(self.nlag, dtype=torch.float64, device=self.buf.device)
+
+    @property
+    def noise0(self):
+        """(S, nz) sum N0 of the stacked segments: the noise in sum A_0"""
+        return self.buf[:, :, 1]
+
+    @property
+    def sum_w(self):
+        """(S, nz, nlag) sum W_l: the pair weight behind every lag"""
+        return self._part(0)
+
+    def xi(self, subtract_noise=True):
+        """(S, nz, nlag) xi_l = sum A_l / sum W_l, with sum N0 taken off lag 0 unless ``subtract_noise`` is False; NaN where
+        sum W_l = 0"""
+        A = self._part(1)
+        if subtract_noise:
+            A = A.clone()
+            A[:, :, 0] -= self.noise0
+        W = self.sum_w
+        x = A / W
+        return torch.where(W != 0.0, x, torch.full_like(x, float("nan")))
+
+    def err(self):
+        """(S, nz, nlag) standard error of ``xi(subtract_noise=False)`` from the scatter of the segments, the delta method of a
+        ratio of sums: sqrt((sum A^2 - 2 xi sum A W + xi^2 sum W^2) / (sum W)^2 n / (n - 1)); NaN below two segments.  (The noise
+        taken off lag 0 moves its mean, not, to this order, its scatter.)"""
+        W, x = self.sum_w, self.xi(subtract_noise=False)
+        n = self.n[:, :, None]
+        num = (self._part(4) - 2.0 * x * self._part(3) + x * x * self._part(2)).clamp_min(0.0)
+        e = torch.sqrt(num / (W * W) * n / (n - 1.0))
+        return torch.where((n > 1.0) & (W != 0.0), e, torch.full_like(e, float("nan")))
+
+    def _per_draw(self):
+        return self.xi()
+
+    @property
+    def std_over_draws(self):
+        """(nz, nlag) standard deviation of ``xi()`` over the S draws: the continuum posterior's error bar on xi"""
+        return self._draws("std_over_draws").std(0, unbiased=True)

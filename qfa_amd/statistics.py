@@ -1,5 +1,6 @@
 """The forest statistics of ``QFA``: transmission and its redshift-binned stack (``forest`` / ``mean_transmission``), the 1D flux
-power spectrum (``p1d`` / ``flux_power``) and its band powers (``p1d_bands`` / ``band_power``).  ``ForestStatistics`` is a plain
+power spectrum (``p1d`` / ``flux_power``), its band powers (``p1d_bands`` / ``band_power``) and the line-of-sight correlation function
+(``xi`` / ``flux_correlation``).  ``ForestStatistics`` is a plain
 base class of ``qfa_amd.model.QFA`` and uses the model's plumbing (``_batch_struct*``, ``_scratch``, ``predict``, ``sample_latent``,
 ``_loader_slices``) as any other method of it does; every call goes through the C-ABI in ``include/qfa_hip.h``."""
 from __future__ import annotations
@@ -11,13 +12,13 @@ import torch
 
 from . import _lib
 from ._lib import QFAHipError, _ptr
-from .stacks import ForestStack, P1DBandStack, P1DStack, _band_map, _check_segments, _edges, _mode_k, _window2
+from .stacks import ForestStack, P1DBandStack, P1DStack, XiStack, _band_map, _check_segments, _edges, _mode_k, _window2
 
 f32 = torch.float32
 
 
 def _p1d_params(tbar_bins, St, p_lo, L, nseg, min_used, stack):
-    """qfa_p1d_t of `p1d` and `p1d_bands`: the bins of tbar, the segments and the z-bins of ``stack`` (None: one unused bin)"""
+    """qfa_p1d_t of `p1d`, `p1d_bands` and `xi`: the bins of tbar, the segments and the z-bins of ``stack`` (None: one unused bin)"""
     pp = _lib.P1DParams()
     pp.zT0, pp.dzT, pp.nT = ForestStack._round_bins(tbar_bins[0], tbar_bins[1], tbar_bins[2])
     pp.St = St
@@ -143,7 +144,7 @@ class ForestStatistics(object):
     P1D_PAIR_BYTES = 1 << 30    # flux_power: the most the (B, S_chunk, Nb) trans / ivar pair of a slice may take
 
     def _p1d_inputs(self, what, asked, trans, ivar, zabs, zfac, batch, tbar, tbar_bins):
-        """the checks and conversions `p1d` and `p1d_bands` share: (B, S, tbar (St, nT) float32, St, tbar_bins, qfa_batch_t, the
+        """the checks and conversions `p1d`, `p1d_bands` and `xi` share: (B, S, tbar (St, nT) float32, St, tbar_bins, qfa_batch_t, the
         tensors it points into); ``asked``: whether the call has an output at all"""
         dev = self.device
         if not asked:
@@ -288,6 +289,45 @@ class ForestStatistics(object):
             _ptr(ws), ws.numel(), _lib.current_stream(dev)), "qfa_p1d_band_f32")
         return bandpower, stack
 
+    def xi(self, trans, ivar, *, zabs=None, zfac=None, batch=None, tbar, tbar_bins=None, seg_len, n_segments, pixel_start=0, min_used,
+           n_lags, sigma2_lss=0.0, unit_weights=False, bins=None, stack=None, return_segments=True, dv=1.0):
+        """The pair-weighted correlation function of forest segments along the line of sight and its (lag, z) stack (qfa_xi_f32; the
+        contract is in include/qfa_hip.h).  The inputs and keywords of ``p1d``: the same pixels are used, the same segments valid and
+        binned in z.  Per segment and lag l < ``n_lags`` (<= seg_len): W_l = sum_j w_j w_{j+l} and A_l = sum_j w_j w_{j+l} d_j d_{j+l}
+        with d = T / tbar - 1 and w = 1 / (v + ``sigma2_lss``), v the pixel's noise variance of d (``unit_weights``: w = 1 on every
+        used pixel); an unused pixel has w = 0 and drops out of both, so the ratio carries no window of the mask.  ``bins`` =
+        (z0, dz, nz) asks for the stack (``dv``: the pixel width in km/s it reports the lags in); ``stack``: a ``XiStack`` to ADD
+        to.  Returns (pairs (B, S, n_segments, 2, n_lags) float32 = [W_l | A_l], noise0 (B, S, n_segments) float32 = sum_j w_j^2 v_j,
+        the noise in A_0 -- both None with ``return_segments`` False -- and the ``XiStack`` (or None))."""
+        dev = self.device
+        B, S, tbar, St, tbar_bins, bs, keep = self._p1d_inputs("xi", bins is not None or stack is not None or return_segments,
+                                                               trans, ivar, zabs, zfac, batch, tbar, tbar_bins)
+        L, nseg, nlag, s2 = int(seg_len), int(n_segments), int(n_lags), float(sigma2_lss)
+        if not (L >= 1 and 1 <= nlag <= L and s2 >= 0.0 and np.isfinite(s2)):
+            raise QFAHipError(f"xi: n_lags = {n_lags} on segments of {seg_len} pixels, sigma2_lss = {sigma2_lss}")
+        if stack is not None:
+            if not isinstance(stack, XiStack) or stack.S != S or stack.L != L or stack.nlag != nlag or \
+                    (bins is not None and XiStack._round_bins(bins[0], bins[1], bins[2]) != stack.bins):
+                raise QFAHipError(f"xi(stack=...): expected a XiStack of {S} draws, segments of {L} pixels and {nlag} lags on the same bins")
+            _lib.require_device_tensor(stack.buf, torch.float64, "stack")
+        elif bins is not None:
+            stack = XiStack.zeros(S, bins[0], bins[1], bins[2], L, nlag, dv, dev)
+        pp = _p1d_params(tbar_bins, St, int(pixel_start), L, nseg, min_used, stack)
+        xx = _lib.XiParams(nlag, s2)
+        need = _lib.lib().qfa_xi_workspace_bytes(B * S, S, self.Nb, L, nseg, int(pp.nz), nlag) if nseg >= 1 else 0
+        if need == 0:
+            raise QFAHipError(f"xi: unsupported shape B={B} S={S} Nb={self.Nb} seg_len={L} n_segments={nseg} nz={pp.nz} n_lags={nlag}")
+        ws = self._scratch("p1d_ws", need)                        # (shared with p1d: the calls own it only while they run)
+        pairs = noise0 = None
+        if return_segments:
+            pairs = torch.empty((B, S, nseg, 2, nlag), dtype=f32, device=dev)
+            noise0 = torch.empty((B, S, nseg), dtype=f32, device=dev)
+        _lib.check(_lib.lib().qfa_xi_f32(
+            _lib.require_device_tensor(trans, f32, "trans"), _lib.require_device_tensor(ivar, f32, "ivar"), C.byref(bs),
+            _ptr(tbar), B, S, self.Nb, C.byref(pp), C.byref(xx), _lib.F_XI_UNIT_W if unit_weights else 0, _ptr(pairs), _ptr(noise0),
+            _ptr(stack.buf) if stack is not None else None, _ptr(ws), ws.numel(), _lib.current_stream(dev)), "qfa_xi_f32")
+        return pairs, noise0, stack
+
     def flux_power(self, dataloader, z_min, z_max, n_zbins, *, n_segments=3, seg_len=None, min_used_frac=0.75, tbar=None,
                    tbar_nbins=64, n_samples=0, seed=0, batch_size=4096, cont_min=0.0, dv=None):
         """The 1D flux power spectrum of a whole dataloader: a ``P1DStack`` of S = max(1, n_samples) draws over ``n_zbins`` bins of
@@ -315,10 +355,23 @@ class ForestStatistics(object):
                                      tbar_nbins, n_samples, seed, batch_size, cont_min, dv,
                                      {"k_edges": k_edges, "resolution_kms": resolution_kms, "subtract_noise": subtract_noise})
 
+    def flux_correlation(self, dataloader, z_min, z_max, n_zbins, n_lags, *, n_segments=3, seg_len=None, min_used_frac=0.75, tbar=None,
+                         tbar_nbins=64, n_samples=0, seed=0, batch_size=4096, cont_min=0.0, dv=None, sigma2_lss=0.0,
+                         unit_weights=False):
+        """The line-of-sight correlation function of a whole dataloader: a ``XiStack`` of S = max(1, n_samples) draws over
+        ``n_zbins`` bins of [z_min, z_max) and the lags 0 .. ``n_lags`` - 1 (in pixels; ``XiStack.lags_kms``).  Everything else is
+        ``flux_power``'s: the same segments, mean transmission, draws and loop over the loader, with ``xi`` in the place of ``p1d``
+        (``sigma2_lss``, ``unit_weights``: its weights).  The sums of a slice are formed in chunks of a fixed number of segments, so
+        the result depends on ``batch_size`` only through the rounding of float64 sums.  Under data parallelism the sums are
+        all-reduced over the model's group."""
+        return self._power_of_loader("flux_correlation", dataloader, z_min, z_max, n_zbins, n_segments, seg_len, min_used_frac, tbar,
+                                     tbar_nbins, n_samples, seed, batch_size, cont_min, dv, None,
+                                     {"n_lags": int(n_lags), "sigma2_lss": float(sigma2_lss), "unit_weights": bool(unit_weights)})
+
     def _power_of_loader(self, what, dataloader, z_min, z_max, n_zbins, n_segments, seg_len, min_used_frac, tbar, tbar_nbins,
-                         n_samples, seed, batch_size, cont_min, dv, bands):
-        """the loop `flux_power` (``bands`` None: a ``P1DStack`` through ``p1d``) and `band_power` (``bands``: the keywords of
-        ``p1d_bands``; a ``P1DBandStack``) share"""
+                         n_samples, seed, batch_size, cont_min, dv, bands, lags=None):
+        """the loop `flux_power` (``bands`` and ``lags`` None: a ``P1DStack`` through ``p1d``), `band_power` (``bands``: the keywords
+        of ``p1d_bands``; a ``P1DBandStack``) and `flux_correlation` (``lags``: the keywords of ``xi``; a ``XiStack``) share"""
         nseg, nz, S = int(n_segments), int(n_zbins), max(1, int(n_samples))
         L = int(seg_len) if seg_len is not None else (self.Nb // nseg if nseg > 0 else 0)
         if nseg < 1 or L < 1 or nseg * L > self.Nb or nz < 1 or not float(z_max) > float(z_min) or not 0.0 < float(min_used_frac) <= 1.0:
@@ -329,6 +382,8 @@ class ForestStatistics(object):
             if wav is None or len(wav) < 2:
                 raise QFAHipError(what + ": the dataloader has no wav_grid: pass dv (km/s per pixel)")
             dv = 299792.458 * float(np.log(float(wav[1]) / float(wav[0])))
+        if lags is not None and not 1 <= lags["n_lags"] <= L:
+            raise QFAHipError(f"{what}: n_lags = {lags['n_lags']} on segments of {L} pixels")
         min_used = max(1, int(np.ceil(float(min_used_frac) * L)))
         if tbar is None:
             half = float(np.exp(0.5 * (L + 1) * float(dv) / 299792.458))          # (1 + z) over half a segment
@@ -338,7 +393,9 @@ class ForestStatistics(object):
         if not isinstance(tbar, ForestStack) or tbar.S not in (1, S):
             raise QFAHipError(f"{what}: tbar must be a ForestStack of 1 or {S} draws")
         tmean = tbar.mean.to(f32)
-        if bands is None:
+        if lags is not None:
+            stack = XiStack.zeros(S, z_min, (float(z_max) - float(z_min)) / nz, nz, L, lags["n_lags"], dv, self.device)
+        elif bands is None:
             stack = P1DStack.zeros(S, z_min, (float(z_max) - float(z_min)) / nz, nz, L, dv, self.device)
         else:
             stack = P1DBandStack.zeros(S, z_min, (float(z_max) - float(z_min)) / nz, nz, L, dv, bands["k_edges"], self.device)
@@ -358,7 +415,9 @@ class ForestStatistics(object):
                 tr, iv, _ = self.forest(**inputs, h=hs, unc=unc, cont_min=cont_min)
                 kw = dict(tbar=tmean if tbar.S == 1 else tmean[s0:s1], tbar_bins=tbar.bins, seg_len=L, n_segments=nseg,
                           min_used=min_used, stack=stack.draws(s0, s1), return_segments=False)
-                if bands is None:
+                if lags is not None:
+                    self.xi(tr, iv, **zin, **kw, **lags)
+                elif bands is None:
                     self.p1d(tr, iv, **zin, **kw)
                 else:
                     self.p1d_bands(tr, iv, **zin, **kw, **bands)
