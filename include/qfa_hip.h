@@ -513,6 +513,50 @@ int qfa_xi_f32(const float *trans, const float *ivar, const qfa_batch_t *b, cons
                const qfa_p1d_t *p, const qfa_xi_t *x, unsigned flags, float *pairs, float *noise0, double *stack,
                void *workspace, size_t workspace_bytes, void *stream);
 
+/* The probability distribution of the transmitted flux, P(F), of forest segments and the stack its covariance matrix comes from, per
+ * posterior draw and z-bin (additive to ABI v4).  The one-point statistic reported beside P1D and xi, and the one most sensitive to
+ * the continuum: a continuum placed 2 % low moves the whole F ~ 1 end of the PDF, which is what the scatter over the draws measures.
+ * This call takes qfa_p1d_f32's inputs and counts the pixels of every segment into flux bins; the sums of the counts and of their
+ * outer products per z-bin give the PDF and, with segments as the independent units, the covariance between its bins.
+ *
+ * The contract.  trans, ivar, b, tbar, B, S, Nb and p are qfa_p1d_f32's, bit for bit: `used` of a pixel (ivar > 0 && 0 <= kT < nT &&
+ * tb > 0), n_used, validity of a segment (n_used >= min_used) and its z-bin kz (at the central pixel p_lo + g L + L / 2) are those of
+ * that call, with its rules on the three redshift forms and on NaN under the mask: the PDF is measured on exactly the pixels and
+ * segments of the P1D.  nt flux bins [t0 + a dt, t0 + (a + 1) dt), a = 0 .. nt - 1:
+ *   per pixel  float32, every operation rounded once, no contraction:  x = T, or with QFA_F_PDF_RELATIVE x = T / tb (one division);
+ *              counted = used && ivar >= ivar_min;  fa = floorf((x - t0) inv_dt), a subtraction and a product, inv_dt = 1.0f / dt
+ *              formed once on the host in float32; the range test is on the float, qfa_forest_f32's bin rule: an edge belongs to the
+ *              bin above it.  Without QFA_F_PDF_CLAMP a pixel with fa outside [0, nt) is in no bin; with it fa < 0 goes to bin 0
+ *              and fa >= nt (x = +inf included) to bin nt - 1.  A NaN x is in no bin either way.  Everything is done by selects:
+ *              nothing under the mask reaches an output;
+ *   segment    h_a = the number of counted pixels of bin a; n_cnt = the number of counted pixels, in a bin or not.  An invalid
+ *              segment has h = 0 and n_cnt = 0 and adds to nothing;
+ *   outputs    hist (B S, nseg, nt) int32; stack (S, nz, 2 + nt + nt^2) float64 = [n_seg | sum n_cnt | sum h_a | sum h_a h_b,
+ *              row-major, full] per draw and z-bin over the valid segments with 0 <= kz < nz; entries (a, b) and (b, a) are equal.
+ *              The call ADDS to `stack`; QFA_F_ZERO_ACCUM overwrites.  Either output may be NULL, not both;
+ *   sums       every term is an integer, h_a h_b <= L^2 <= 2^24, so every entry of `stack` is exact while it stays below 2^53 --
+ *              that takes more than 5 10^8 segments in one (draw, z-bin).  The result therefore does not depend on the order of
+ *              addition, on how the host cuts B into launches, on B, S or on how a caller splits its spectra over calls that add
+ *              into one stack; draw s of a call of S draws equals a call on that draw alone.  No atomics all the same: a chunk of
+ *              qfa_p1d_band_chunk_segments() segments leaves its int32 sums through the workspace and a second kernel adds them
+ *              onto what `stack` holds.
+ * qfa_flux_pdf_stack_doubles: S nz (2 + nt + nt^2); 0 = unsupported (S < 1, nz outside 1..4096, nt outside 1..64).
+ * qfa_flux_pdf_workspace_bytes(R = B S, ...): qfa_p1d_workspace_bytes' shapes, and nt outside 1..64, give 0.  The workspace holds the
+ * chunk partials of one launch alone (hist is written directly), aimed at the cap of qfa_p1d_f32's rows, one chunk at the least.
+ * Returns every code of qfa_p1d_f32 for the arguments they share; QFA_E_NULL also for q or both outputs missing; QFA_E_SIZE also for
+ * nt outside 1..64, dt <= 0 or not finite, t0 not finite, ivar_min negative or not finite; QFA_E_FLAGS for any flag other than
+ * QFA_F_ZERO_ACCUM, QFA_F_SYNC, QFA_F_PDF_RELATIVE, QFA_F_PDF_CLAMP.  Argument checks return before any device work.  B = 0 does
+ * nothing, except zeroing `stack` under QFA_F_ZERO_ACCUM.  The call neither synchronises nor allocates. */
+typedef struct { float t0, dt; int nt; float ivar_min; } qfa_pdf_t;   /* dt > 0 finite, t0 finite, 1 <= nt <= 64, ivar_min >= 0 finite */
+#define QFA_F_PDF_RELATIVE 0x800u    /* qfa_flux_pdf_f32: bin x = T / tbar(z) instead of x = T */
+#define QFA_F_PDF_CLAMP    0x1000u   /* qfa_flux_pdf_f32: x below the range counts in bin 0, above it in bin nt - 1 (the convention of the published PDFs) */
+
+size_t qfa_flux_pdf_stack_doubles(int S, int nz, int nt);
+size_t qfa_flux_pdf_workspace_bytes(int R, int S, int Nb, int L, int nseg, int nz, int nt);
+int qfa_flux_pdf_f32(const float *trans, const float *ivar, const qfa_batch_t *b, const float *tbar, int B, int S, int Nb,
+                     const qfa_p1d_t *p, const qfa_pdf_t *q, unsigned flags, int *hist, double *stack,
+                     void *workspace, size_t workspace_bytes, void *stream);
+
 /* Replaces Adam.update(reference QFA/optimizer.py:37-52) followed by the clamp of QFA.clip
  * (QFA/model.py:233-241) for ONE tensor of n elements:
  *   g' = g + wd*p; m = (1-b1) g' + b1 m; v = (1-b2) g'^2 + b2 v;

@@ -15,6 +15,7 @@ _LAZY = {
     "P1DStack": ("qfa_amd.model", "P1DStack"),
     "P1DBandStack": ("qfa_amd.model", "P1DBandStack"),
     "XiStack": ("qfa_amd.model", "XiStack"),
+    "PDFStack": ("qfa_amd.model", "PDFStack"),
     "Adam": ("qfa_amd.optimizer", "Adam"),
     "step_scheduler": ("qfa_amd.optimizer", "step_scheduler"),
 }

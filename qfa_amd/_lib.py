@@ -25,6 +25,7 @@ EXPORTS = (
     "qfa_p1d_stack_doubles", "qfa_p1d_workspace_bytes", "qfa_p1d_f32",
     "qfa_p1d_band_stack_doubles", "qfa_p1d_band_workspace_bytes", "qfa_p1d_band_chunk_segments", "qfa_p1d_band_f32",
     "qfa_xi_stack_doubles", "qfa_xi_workspace_bytes", "qfa_xi_f32",
+    "qfa_flux_pdf_stack_doubles", "qfa_flux_pdf_workspace_bytes", "qfa_flux_pdf_f32",
 )
 
 TAU_IDS = {"becker": 0, "fg": 1, "kamble": 2, "mock": 3}
@@ -35,6 +36,8 @@ F_PASS2_PIXRES = 0x40
 F_ZERO_ACCUM = 0x80
 F_FOREST_UNIT_W = 0x200    # qfa_forest_f32: stack with w = 1 instead of w = ivar
 F_XI_UNIT_W = 0x400        # qfa_xi_f32: w = 1 on a used pixel instead of 1 / (v + sigma2_lss)
+F_PDF_RELATIVE = 0x800     # qfa_flux_pdf_f32: bin x = T / tbar(z) instead of x = T
+F_PDF_CLAMP = 0x1000       # qfa_flux_pdf_f32: x outside the range counts in the first / last bin
 F_EXACT_GRAD = 0x100       # exact gradients of mean NLL (opt-in; QFA.exact_gradients); the buffer carries the mode in slot 6
 
 
@@ -80,6 +83,10 @@ class P1DBandParams(C.Structure):   # qfa_p1d_band_t
 
 class XiParams(C.Structure):        # qfa_xi_t
     _fields_ = [("nlag", C.c_int), ("sigma2_lss", C.c_float)]
+
+
+class PDFParams(C.Structure):       # qfa_pdf_t
+    _fields_ = [("t0", C.c_float), ("dt", C.c_float), ("nt", C.c_int), ("ivar_min", C.c_float)]
 
 
 _lib = None
@@ -158,6 +165,9 @@ def lib():
         "qfa_xi_stack_doubles": (sz, [i, i, i]),
         "qfa_xi_workspace_bytes": (sz, [i, i, i, i, i, i, i]),
         "qfa_xi_f32": (i, [p, p, C.POINTER(Batch), p, i, i, i, C.POINTER(P1DParams), C.POINTER(XiParams), C.c_uint, p, p, p, p, sz, p]),
+        "qfa_flux_pdf_stack_doubles": (sz, [i, i, i]),
+        "qfa_flux_pdf_workspace_bytes": (sz, [i, i, i, i, i, i, i]),
+        "qfa_flux_pdf_f32": (i, [p, p, C.POINTER(Batch), p, i, i, i, C.POINTER(P1DParams), C.POINTER(PDFParams), C.c_uint, p, p, p, sz, p]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(h, name, None)

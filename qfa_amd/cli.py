@@ -108,6 +108,16 @@ def main(argv=None):
             raise ValueError(f"MODEL.XI_NLAGS = {int(cfg.MODEL.XI_NLAGS)} exceeds the segment length {seg_len}")
         if not float(cfg.MODEL.XI_SIGMA2_LSS) >= 0.0 or float(cfg.MODEL.XI_SIGMA2_LSS) == float("inf"):
             raise ValueError("MODEL.XI_SIGMA2_LSS must be finite and >= 0")
+    if cfg.TYPE == "predict" and int(cfg.MODEL.PDF_NBINS) != 0:
+        if not 1 <= int(cfg.MODEL.PDF_NBINS) <= 64:
+            raise ValueError("MODEL.PDF_NBINS must lie in 0 .. 64")
+        if int(cfg.MODEL.P1D_SEGMENTS) <= 0:
+            raise ValueError("MODEL.PDF_NBINS > 0 needs MODEL.P1D_SEGMENTS > 0 (the segments whose pixels are counted)")
+        if not float(cfg.MODEL.PDF_TMAX) > float(cfg.MODEL.PDF_TMIN) or abs(float(cfg.MODEL.PDF_TMAX)) == float("inf") or \
+                abs(float(cfg.MODEL.PDF_TMIN)) == float("inf"):
+            raise ValueError("MODEL.PDF_TMAX must be finite and above MODEL.PDF_TMIN")
+        if not float(cfg.MODEL.PDF_IVAR_MIN) >= 0.0 or float(cfg.MODEL.PDF_IVAR_MIN) == float("inf"):
+            raise ValueError("MODEL.PDF_IVAR_MIN must be finite and >= 0")
     os.makedirs(cfg.DATA.OUTPUT_DIR, exist_ok=True)
     with open(os.path.join(cfg.DATA.OUTPUT_DIR, "config.yaml"), "w") as f:
         f.write(cfg.dump())
@@ -185,6 +195,20 @@ def main(argv=None):
                          z_centers=xs.z_centers.cpu().numpy(), z_edges=xs.z_edges.cpu().numpy(), xi=xs.xi().cpu().numpy(),
                          xi_raw=xs.xi(subtract_noise=False).cpu().numpy(), err=xs.err().cpu().numpy(), n=xs.n.cpu().numpy(),
                          sum_w=xs.sum_w.cpu().numpy(), seg_len=xs.L, dv=xs.dv, sums=xs.buf.cpu().numpy())
+            if int(cfg.MODEL.PDF_NBINS) > 0:
+                fs = model.flux_pdf(dataloader, float(cfg.MODEL.FOREST_ZMIN), float(cfg.MODEL.FOREST_ZMAX), int(cfg.MODEL.P1D_NZBINS),
+                                    int(cfg.MODEL.PDF_NBINS), t_min=float(cfg.MODEL.PDF_TMIN), t_max=float(cfg.MODEL.PDF_TMAX),
+                                    relative=bool(cfg.MODEL.PDF_RELATIVE), clamp=bool(cfg.MODEL.PDF_CLAMP),
+                                    ivar_min=float(cfg.MODEL.PDF_IVAR_MIN), n_segments=int(cfg.MODEL.P1D_SEGMENTS),
+                                    min_used_frac=float(cfg.MODEL.P1D_MIN_USED_FRAC), tbar=st, n_samples=int(cfg.MODEL.N_SAMPLES),
+                                    seed=int(cfg.MODEL.SAMPLE_SEED))
+                out = dict(z=fs.z_centers.cpu().numpy(), t_edges=fs.t_edges.cpu().numpy(), pdf=fs.pdf().cpu().numpy(),
+                           err=fs.err().cpu().numpy(), cov=fs.cov().cpu().numpy(), counts=fs.counts.cpu().numpy(),
+                           n_segments=fs.n_segments.cpu().numpy(), out_of_range=fs.out_of_range().cpu().numpy())
+                if fs.S > 1:
+                    out["std_over_draws"] = fs.std_over_draws.cpu().numpy()
+                    out["total_cov"] = fs.total_cov.cpu().numpy()
+                np.savez(os.path.join(cfg.DATA.OUTPUT_DIR, "flux_pdf.npz"), **out)
         print(f"Finish predicting {len(dataloader)} spectra in {time.time() - ts} seconds...")
     return 0
 

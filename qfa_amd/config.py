@@ -71,7 +71,12 @@ DEFAULTS = {                                        # reference QFA/config.py:15
               # flux_correlation.npz, the pair-weighted correlation function of the same segments at the lags 0 .. XI_NLAGS - 1
               # pixels per z-bin, which carries no window of the mask; pixels are weighted by 1 / (noise variance + XI_SIGMA2_LSS)
               # (QFA.flux_correlation)
-              "XI_NLAGS": 0, "XI_SIGMA2_LSS": 0.0},
+              "XI_NLAGS": 0, "XI_SIGMA2_LSS": 0.0,
+              # not in the reference: PDF_NBINS > 0 (needs P1D_SEGMENTS > 0, at most 64) also writes flux_pdf.npz, the probability
+              # distribution of the transmitted flux of the same segments in PDF_NBINS bins of [PDF_TMIN, PDF_TMAX) per z-bin with
+              # the covariance matrix between the bins; PDF_CLAMP counts pixels outside the range in the first / last bin,
+              # PDF_RELATIVE bins T / <T>(z), PDF_IVAR_MIN leaves out pixels of lower inverse variance (QFA.flux_pdf)
+              "PDF_NBINS": 0, "PDF_TMIN": 0.0, "PDF_TMAX": 1.0, "PDF_CLAMP": True, "PDF_RELATIVE": False, "PDF_IVAR_MIN": 0.0},
     "TRAIN": {"NEPOCHS": 500, "LEARNING_RATE": 1e-3, "WEIGHT_DECAY": 1e-1, "DECAY_ALPHA": 0.9, "DECAY_STEP": 10,
               "WINDOW_LENGTH_FOR_MU": 16,
               # not in the reference: "em" = F by its closed-form EM update, Adam for the other parameters (QFA.train
@@ -93,7 +98,8 @@ ARG_KEYS = {
 # tests/golden/g12_config.json, extracted from the reference's config.py / main.py)
 EXTRA_KEYS = ("MODEL.REFERENCE_C0_QUIRK", "MODEL.N_SAMPLES", "MODEL.SAMPLE_SEED", "MODEL.N_REPLICATES", "MODEL.EXACT_GRADIENTS",
               "MODEL.FOREST", "MODEL.FOREST_ZMIN", "MODEL.FOREST_ZMAX", "MODEL.FOREST_NBINS", "MODEL.P1D_SEGMENTS",
-              "MODEL.P1D_NZBINS", "MODEL.P1D_MIN_USED_FRAC", "MODEL.P1D_NBANDS", "MODEL.XI_NLAGS", "MODEL.XI_SIGMA2_LSS", "TRAIN.F_UPDATE", "TRAIN.EM_RHO", "TRAIN.EM_RIDGE")
+              "MODEL.P1D_NZBINS", "MODEL.P1D_MIN_USED_FRAC", "MODEL.P1D_NBANDS", "MODEL.XI_NLAGS", "MODEL.XI_SIGMA2_LSS", "MODEL.PDF_NBINS",
+              "MODEL.PDF_TMIN", "MODEL.PDF_TMAX", "MODEL.PDF_CLAMP", "MODEL.PDF_RELATIVE", "MODEL.PDF_IVAR_MIN", "TRAIN.F_UPDATE", "TRAIN.EM_RHO", "TRAIN.EM_RIDGE")
 
 
 def _set(cfg, dotted, value):

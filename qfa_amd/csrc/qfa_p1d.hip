@@ -2,10 +2,13 @@
 // qfa_p1d_stack_doubles, qfa_p1d_workspace_bytes, qfa_p1d_f32) and of its band powers and their covariance stack
 // (qfa_p1d_band_stack_doubles, qfa_p1d_band_workspace_bytes, qfa_p1d_band_chunk_segments, qfa_p1d_band_f32): argument checks, the
 // launch plans and the launches; and of the pair-weighted correlation function of the same segments and its (lag, z) stack
-// (qfa_xi_stack_doubles, qfa_xi_workspace_bytes, qfa_xi_f32).  Kernels in qfa_p1d.h, qfa_p1d_band.h and qfa_xi.h.
+// (qfa_xi_stack_doubles, qfa_xi_workspace_bytes, qfa_xi_f32); and of the flux PDF of the same segments and its covariance stack
+// (qfa_flux_pdf_stack_doubles, qfa_flux_pdf_workspace_bytes, qfa_flux_pdf_f32).  Kernels in qfa_p1d.h, qfa_p1d_band.h, qfa_xi.h and
+// qfa_pdf.h.
 #include "qfa_p1d.h"
 #include "qfa_p1d_band.h"
 #include "qfa_xi.h"
+#include "qfa_pdf.h"
 #include "../../include/qfa_hip.h"
 
 #include <math.h>
@@ -100,7 +103,31 @@ XiPlan make_xi_plan(int B, int S, int nseg, int nz, int nlag) {
     return P;
 }
 
-// the checks qfa_p1d_f32, qfa_p1d_band_f32 and qfa_xi_f32 share, in qfa_p1d_f32's order: sizes, then flags
+// The PDF call's cut: nothing but the chunk partials (chunks, S, nz, 2 + nt + nt (nt + 1) / 2) int32 is held between its kernels, from
+// the workspace's first 16-byte boundary on; a launch takes as many chunks as aim at kRowsTarget (at least one).  The sums are
+// integers, so the result does not depend on where the cut falls.
+struct PdfPlan {
+    int Bc, W;
+    size_t chunks, bytes;                      // chunks (per draw) of a full launch
+};
+
+PdfPlan make_pdf_plan(int B, int S, int nseg, int nz, int nt) {
+    namespace pd = qfa_pdf;
+    PdfPlan P;
+    P.W = 2 + nt + nt * (nt + 1) / 2;
+    const size_t part_row = (size_t)S * nz * (size_t)P.W * sizeof(int);
+    size_t nc = kRowsTarget / part_row;
+    if (nc < 1) nc = 1;
+    size_t bc = nc * pd::kChunk / (size_t)nseg;
+    if (bc < 1) bc = 1;
+    if (bc > (size_t)(B > 0 ? B : 1)) bc = (size_t)(B > 0 ? B : 1);
+    P.Bc = (int)bc;
+    P.chunks = (bc * nseg + pd::kChunk - 1) / pd::kChunk;
+    P.bytes = 16 + P.chunks * part_row;
+    return P;
+}
+
+// the checks qfa_p1d_f32, qfa_p1d_band_f32, qfa_xi_f32 and qfa_flux_pdf_f32 share, in qfa_p1d_f32's order: sizes, then flags
 int check_sizes(const qfa_batch_t *b, int B, int S, int Nb, const qfa_p1d_t *p) {
     if (B < 0 || S < 1 || Nb < 1 || (int64_t)B * S > INT32_MAX) return QFA_E_SIZE;
     if (p->seg_len < 1 || p->seg_len > kMaxLen || p->nseg < 1 || p->p_lo < 0 ||
@@ -360,6 +387,83 @@ int qfa_xi_f32(const float *trans, const float *ivar, const qfa_batch_t *b, cons
             xi::k_xi_stack<<<(unsigned)((size_t)chunks * S), xi::kThreads, 0, st>>>(sa);
             xi::k_xi_reduce<<<dim3((unsigned)(S * nz), (unsigned)((Wd + 255) / 256)), 256, 0, st>>>(part, chunks, S, nz, nlag, zero,
                                                                                                    stack);
+            zero = 0;
+        }
+    }
+    if (flags & QFA_F_SYNC) {
+        hipError_t s = hipStreamSynchronize(st);
+        if (s != hipSuccess) { (void)hipGetLastError(); return (int)s; }
+    }
+    return (int)hipGetLastError();
+}
+
+size_t qfa_flux_pdf_stack_doubles(int S, int nz, int nt) {
+    if (S < 1 || nz < 1 || nz > kMaxBins || nt < 1 || nt > qfa_pdf::kMaxBins) return 0;
+    return (size_t)S * nz * (size_t)(2 + nt + nt * nt);
+}
+
+size_t qfa_flux_pdf_workspace_bytes(int R, int S, int Nb, int L, int nseg, int nz, int nt) {
+    if (!shape_ok(R, S, Nb, L, nseg, nz) || nt < 1 || nt > qfa_pdf::kMaxBins) return 0;
+    return make_pdf_plan(R / S, S, nseg, nz, nt).bytes;
+}
+
+int qfa_flux_pdf_f32(const float *trans, const float *ivar, const qfa_batch_t *b, const float *tbar, int B, int S, int Nb,
+                     const qfa_p1d_t *p, const qfa_pdf_t *q, unsigned flags, int *hist, double *stack, void *workspace,
+                     size_t workspace_bytes, void *stream) {
+    namespace pd = qfa_pdf;
+    if (!trans || !ivar || !b || !tbar || !p || !workspace || !q || (!hist && !stack)) return QFA_E_NULL;
+    const bool fac = b->zq1 || b->pix_ratio;
+    if (fac && !(b->zq1 && b->pix_ratio)) return QFA_E_NULL;
+    if (!fac && !b->zabs) return QFA_E_NULL;
+    if (int e = check_sizes(b, B, S, Nb, p)) return e;
+    if (q->nt < 1 || q->nt > pd::kMaxBins || !(q->dt > 0.f) || !isfinite(q->dt) || !isfinite(q->t0) || !(q->ivar_min >= 0.f) ||
+        !isfinite(q->ivar_min))
+        return QFA_E_SIZE;
+    if (flags & ~(QFA_F_ZERO_ACCUM | QFA_F_SYNC | QFA_F_PDF_RELATIVE | QFA_F_PDF_CLAMP)) return QFA_E_FLAGS;
+    const int L = p->seg_len, nseg = p->nseg, nz = p->nz, nt = q->nt;
+    const PdfPlan P = make_pdf_plan(B, S, nseg, nz, nt);
+    if (workspace_bytes < P.bytes) return QFA_E_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t Wf = (size_t)(2 + nt + nt * nt);
+    int zero = (flags & QFA_F_ZERO_ACCUM) ? 1 : 0;
+    if (B == 0) {
+        if (stack && zero) {
+            hipError_t e = hipMemsetAsync(stack, 0, (size_t)S * nz * Wf * sizeof(double), st);
+            if (e != hipSuccess) return (int)e;
+        }
+        return 0;
+    }
+    pd::Args a;
+    a.bt = *b;
+    a.trans = trans;
+    a.ivar = ivar;
+    a.tbar = tbar;
+    a.hist = hist;
+    a.part = stack ? (int *)(((uintptr_t)workspace + 15) & ~(uintptr_t)15) : nullptr;
+    a.S = S; a.St = p->St; a.Nb = Nb; a.L = L; a.nseg = nseg; a.p_lo = p->p_lo; a.min_used = p->min_used;
+    a.nT = p->nT; a.nz = nz; a.factored = fac ? 1 : 0; a.nt = nt;
+    a.relative = (flags & QFA_F_PDF_RELATIVE) ? 1 : 0;
+    a.clamp = (flags & QFA_F_PDF_CLAMP) ? 1 : 0;
+    a.zT0 = p->zT0;
+    a.inv_dzT = 1.0f / p->dzT;
+    a.z0 = p->z0;
+    a.inv_dz = 1.0f / p->dz;
+    a.t0 = q->t0;
+    a.inv_dt = 1.0f / q->dt;
+    a.ivar_min = q->ivar_min;
+    const size_t lds = (size_t)pd::kChunk * (nt + 2) * sizeof(int);
+    // without a stack nothing is held between the kernels: launches as large as the grid allows write the caller's array
+    size_t cap = (((size_t)1 << 30) / (size_t)S) * pd::kChunk / (size_t)nseg;
+    if (cap < 1) cap = 1;
+    const int step = stack ? P.Bc : (int)(cap < (size_t)B ? cap : (size_t)B);
+    for (int b0 = 0; b0 < B; b0 += step) {
+        a.b0 = b0;
+        a.Bc = B - b0 < step ? B - b0 : step;
+        const int chunks = (int)(((size_t)a.Bc * nseg + pd::kChunk - 1) / pd::kChunk);
+        pd::k_pdf<<<(unsigned)((size_t)chunks * S), pd::kThreads, lds, st>>>(a);
+        if (stack) {
+            pd::k_pdf_reduce<<<dim3((unsigned)(S * nz), (unsigned)((Wf + 255) / 256)), 256, 0, st>>>(a.part, chunks, S, nz, nt, zero,
+                                                                                                    stack);
             zero = 0;
         }
     }

@@ -1,6 +1,6 @@
-"""The result classes of ``QFA``: ``EMStats`` and the four stacks of the forest statistics, ``ForestStack``, ``P1DStack``,
-``P1DBandStack`` and ``XiStack``.  Views and arithmetic on buffers the kernels filled (include/qfa_hip.h): nothing here calls the library or
-needs a GPU, the classes work on CPU tensors as well.  ``qfa_amd.model`` re-exports the four names."""
+"""The result classes of ``QFA``: ``EMStats`` and the five stacks of the forest statistics, ``ForestStack``, ``P1DStack``,
+``P1DBandStack``, ``XiStack`` and ``PDFStack``.  Views and arithmetic on buffers the kernels filled (include/qfa_hip.h): nothing here calls the library or
+needs a GPU, the classes work on CPU tensors as well.  ``qfa_amd.model`` re-exports the names."""
 from __future__ import annotations
 
 import numpy as np
@@ -427,3 +427,137 @@ class XiStack(_SegmentStack):
     def std_over_draws(self):
         """(nz, nlag) standard deviation of ``xi()`` over the S draws: the continuum posterior's error bar on xi"""
         return self._draws("std_over_draws").std(0, unbiased=True)
+
+
+class PDFStack(_DrawStack):
+    """The stack of the flux PDF of forest segments and of the outer products of their counts (include/qfa_hip.h,
+    qfa_flux_pdf_f32): ``buf`` = (S, nz, 2 + nt + nt^2) float64 [n_seg | sum n_cnt | sum h_a | sum h_a h_b] per draw of the continuum
+    and z-bin, over segments of ``L`` pixels; h_a is a segment's number of counted pixels in the flux bin
+    [t0 + a dt, t0 + (a + 1) dt), n_cnt its number of counted pixels in a bin or not.  ``relative``: the bins are of T / <T>(z);
+    ``clamp``: pixels outside the range sit in the first / last bin; ``ivar_min``: the least inverse variance of a counted pixel.
+    Every entry is an integer, exact below 2^53: stacks add up exactly, in any order.  t0 and dt are held as the float32 numbers
+    the kernel bins with."""
+
+    def __init__(self, buf, z0, dz, nz, L, t0, dt, n_tbins, relative=False, clamp=False, ivar_min=0.0):
+        self.L, self.nt = int(L), int(n_tbins)
+        self.t0, self.dt = float(np.float32(t0)), float(np.float32(dt))
+        self.relative, self.clamp, self.ivar_min = bool(relative), bool(clamp), float(np.float32(ivar_min))
+        if not (1 <= self.nt <= 64 and self.dt > 0.0 and np.isfinite(self.dt) and np.isfinite(self.t0) and 1 <= self.L <= 4096
+                and self.ivar_min >= 0.0 and np.isfinite(self.ivar_min)):
+            raise QFAHipError(f"PDFStack: {n_tbins} flux bins from {t0} in steps of {dt}, ivar_min = {ivar_min}, segments L = {L}")
+        super().__init__(buf, z0, dz, nz, (int(nz), 2 + self.nt + self.nt ** 2))
+        self.nz = self._nbins
+
+    @classmethod
+    def zeros(cls, S, z0, dz, nz, L, t0, dt, n_tbins, relative=False, clamp=False, ivar_min=0.0, device="cpu"):
+        nt = int(n_tbins)
+        return cls(torch.zeros((int(S), int(nz), 2 + nt + nt * nt), dtype=torch.float64, device=device), z0, dz, nz, L, t0, dt, nt,
+                   relative, clamp, ivar_min)
+
+    def _like(self, buf):
+        return PDFStack(buf, self.z0, self.dz, self.nz, self.L, self.t0, self.dt, self.nt, self.relative, self.clamp, self.ivar_min)
+
+    @property
+    def flux_bins(self):
+        """(t0, dt, nt), t0 and dt as the float32 numbers the kernel bins with"""
+        return (self.t0, self.dt, self.nt)
+
+    def same_layout(self, other):
+        return super().same_layout(other) and other.L == self.L and other.flux_bins == self.flux_bins and \
+            (other.relative, other.clamp, other.ivar_min) == (self.relative, self.clamp, self.ivar_min)
+
+    @property
+    def z_centres(self):
+        return self.z_centers
+
+    @property
+    def t_edges(self):
+        """(nt + 1,) edges of the flux bins"""
+        return self.t0 + self.dt * torch.arange(self.nt + 1, dtype=torch.float64, device=self.buf.device)
+
+    @property
+    def t_centres(self):
+        """(nt,) centres of the flux bins"""
+        return self.t0 + self.dt * (torch.arange(self.nt, dtype=torch.float64, device=self.buf.device) + 0.5)
+
+    @property
+    def n_segments(self):
+        """(S, nz) number of segments stacked"""
+        return self.buf[:, :, 0]
+
+    @property
+    def n_pixels(self):
+        """(S, nz) number of counted pixels of the stacked segments, in a bin or not"""
+        return self.buf[:, :, 1]
+
+    @property
+    def counts(self):
+        """(S, nz, nt) H_a: counted pixels per flux bin"""
+        return self.buf[:, :, 2:2 + self.nt]
+
+    @property
+    def outer(self):
+        """(S, nz, nt, nt) M_ab = sum over the segments of h_a h_b"""
+        return self.buf[:, :, 2 + self.nt:].reshape(self.S, self.nz, self.nt, self.nt)
+
+    def pdf(self):
+        """(S, nz, nt) P_a = H_a / (N dt) with N = sum_a H_a: normalised over the in-range pixels, so that sum_a P_a dt = 1; NaN
+        where N = 0"""
+        H = self.counts
+        N = H.sum(-1, keepdim=True)
+        p = H / (N * self.dt)
+        return torch.where(N > 0.0, p, torch.full_like(p, float("nan")))
+
+    def out_of_range(self):
+        """(S, nz) 1 - N / sum n_cnt: the fraction of counted pixels no bin holds (0 under ``clamp`` unless x is NaN); NaN
+        without pixels"""
+        f = 1.0 - self.counts.sum(-1) / self.n_pixels
+        return torch.where(self.n_pixels > 0.0, f, torch.full_like(f, float("nan")))
+
+    def cov(self):
+        """(S, nz, nt, nt) covariance of ``pdf()``: the delta method of the ratio estimator with segments as the independent units,
+        Cov_ab = n / (n - 1) sum_seg (h_a - r_a m)(h_b - r_b m) / (dt^2 N^2), r_a = H_a / N, m = sum_a h_a of a segment.  It is
+        formed in float64 from the stacked M = sum h h^T as M_ab - r_b sum_c M_ac - r_a sum_c M_bc + r_a r_b sum_cd M_cd.  Its rows
+        sum to zero by construction -- the PDF is normalised, it has nt - 1 degrees of freedom: the matrix is singular and a fit
+        must drop a bin.  NaN below two segments or without pixels."""
+        M, H = self.outer, self.counts
+        N = H.sum(-1)
+        r = H / N[:, :, None]
+        rows = M.sum(-1)                                          # (S, nz, nt) sum_c M_ac: integers, exact
+        tot = rows.sum(-1)
+        ra, rb = r[:, :, :, None], r[:, :, None, :]
+        c = M - rb * rows[:, :, :, None] - ra * rows[:, :, None, :] + ra * rb * tot[:, :, None, None]
+        n = self.n_segments[:, :, None, None]
+        N2 = (N * N)[:, :, None, None]
+        c = n / (n - 1.0) * c / (self.dt * self.dt * N2)
+        return torch.where((n > 1.0) & (N2 > 0.0), c, torch.full_like(c, float("nan")))
+
+    def err(self):
+        """(S, nz, nt) standard error of ``pdf()``: the root of the diagonal of ``cov()``"""
+        return torch.sqrt(torch.diagonal(self.cov(), dim1=2, dim2=3).clamp_min(0.0))
+
+    def corr(self):
+        """(S, nz, nt, nt) correlation matrix of the flux bins: cov_ab / sqrt(cov_aa cov_bb)"""
+        c = self.cov()
+        d = torch.sqrt(torch.diagonal(c, dim1=2, dim2=3))
+        return c / (d[:, :, :, None] * d[:, :, None, :])
+
+    def _per_draw(self):
+        return self.pdf()
+
+    @property
+    def std_over_draws(self):
+        """(nz, nt) standard deviation of ``pdf()`` over the S draws: the continuum posterior's error bar on the PDF"""
+        return self._draws("std_over_draws").std(0, unbiased=True)
+
+    @property
+    def cov_over_draws(self):
+        """(nz, nt, nt) covariance of ``pdf()`` over the S draws: the continuum posterior's covariance of the flux bins"""
+        d = self._draws("cov_over_draws")
+        d = d - d.mean(0, keepdim=True)
+        return torch.einsum("sza,szb->zab", d, d) / (self.S - 1.0)
+
+    @property
+    def total_cov(self):
+        """(nz, nt, nt) the mean over the draws of ``cov()`` plus ``cov_over_draws``"""
+        return self.cov().mean(0) + self.cov_over_draws

@@ -1,6 +1,6 @@
 """The forest statistics of ``QFA``: transmission and its redshift-binned stack (``forest`` / ``mean_transmission``), the 1D flux
-power spectrum (``p1d`` / ``flux_power``), its band powers (``p1d_bands`` / ``band_power``) and the line-of-sight correlation function
-(``xi`` / ``flux_correlation``).  ``ForestStatistics`` is a plain
+power spectrum (``p1d`` / ``flux_power``), its band powers (``p1d_bands`` / ``band_power``), the line-of-sight correlation function
+(``xi`` / ``flux_correlation``) and the flux PDF (``flux_pdf_segments`` / ``flux_pdf``).  ``ForestStatistics`` is a plain
 base class of ``qfa_amd.model.QFA`` and uses the model's plumbing (``_batch_struct*``, ``_scratch``, ``predict``, ``sample_latent``,
 ``_loader_slices``) as any other method of it does; every call goes through the C-ABI in ``include/qfa_hip.h``."""
 from __future__ import annotations
@@ -12,13 +12,13 @@ import torch
 
 from . import _lib
 from ._lib import QFAHipError, _ptr
-from .stacks import ForestStack, P1DBandStack, P1DStack, XiStack, _band_map, _check_segments, _edges, _mode_k, _window2
+from .stacks import ForestStack, P1DBandStack, P1DStack, PDFStack, XiStack, _band_map, _check_segments, _edges, _mode_k, _window2
 
 f32 = torch.float32
 
 
 def _p1d_params(tbar_bins, St, p_lo, L, nseg, min_used, stack):
-    """qfa_p1d_t of `p1d`, `p1d_bands` and `xi`: the bins of tbar, the segments and the z-bins of ``stack`` (None: one unused bin)"""
+    """qfa_p1d_t of `p1d`, `p1d_bands`, `xi` and `flux_pdf_segments`: the bins of tbar, the segments and the z-bins of ``stack`` (None: one unused bin)"""
     pp = _lib.P1DParams()
     pp.zT0, pp.dzT, pp.nT = ForestStack._round_bins(tbar_bins[0], tbar_bins[1], tbar_bins[2])
     pp.St = St
@@ -144,7 +144,7 @@ class ForestStatistics(object):
     P1D_PAIR_BYTES = 1 << 30    # flux_power: the most the (B, S_chunk, Nb) trans / ivar pair of a slice may take
 
     def _p1d_inputs(self, what, asked, trans, ivar, zabs, zfac, batch, tbar, tbar_bins):
-        """the checks and conversions `p1d`, `p1d_bands` and `xi` share: (B, S, tbar (St, nT) float32, St, tbar_bins, qfa_batch_t, the
+        """the checks and conversions `p1d`, `p1d_bands`, `xi` and `flux_pdf_segments` share: (B, S, tbar (St, nT) float32, St, tbar_bins, qfa_batch_t, the
         tensors it points into); ``asked``: whether the call has an output at all"""
         dev = self.device
         if not asked:
@@ -328,6 +328,50 @@ class ForestStatistics(object):
             _ptr(stack.buf) if stack is not None else None, _ptr(ws), ws.numel(), _lib.current_stream(dev)), "qfa_xi_f32")
         return pairs, noise0, stack
 
+    def flux_pdf_segments(self, trans, ivar, *, zabs=None, zfac=None, batch=None, tbar, tbar_bins=None, seg_len, n_segments,
+                          pixel_start=0, min_used, t_min, t_max, n_tbins, relative=False, clamp=False, ivar_min=0.0, bins=None,
+                          stack=None, return_segments=True):
+        """The flux PDF of forest segments and the stack its covariance comes from (qfa_flux_pdf_f32; the contract is in
+        include/qfa_hip.h).  The inputs and keywords of ``p1d``: the same pixels are used, the same segments valid and binned in z.
+        Per segment h_a = the number of counted pixels (used, with ivar >= ``ivar_min``) whose x = T -- or, with ``relative``,
+        x = T / tbar(z) -- falls in flux bin a of the ``n_tbins`` (<= 64) equal bins of [``t_min``, ``t_max``); an edge belongs to
+        the bin above it.  ``clamp`` counts x below the range in the first bin and above it in the last (the convention of the
+        published PDFs); without it such pixels are in no bin.  ``bins`` = (z0, dz, nz) asks for the stack, ``stack``: a
+        ``PDFStack`` to ADD to.  Returns (hist (B, S, n_segments, n_tbins) int32, or None with ``return_segments`` False; the
+        ``PDFStack``, or None).  The counts are integers: the stack is exact, whatever the order and the split of the calls."""
+        dev = self.device
+        B, S, tbar, St, tbar_bins, bs, keep = self._p1d_inputs("flux_pdf_segments", bins is not None or stack is not None or
+                                                               return_segments, trans, ivar, zabs, zfac, batch, tbar, tbar_bins)
+        L, nseg, nt, imin = int(seg_len), int(n_segments), int(n_tbins), float(ivar_min)
+        if not (1 <= nt <= 64 and float(t_max) > float(t_min) and np.isfinite(float(t_min)) and np.isfinite(float(t_max))
+                and imin >= 0.0 and np.isfinite(imin)):
+            raise QFAHipError(f"flux_pdf_segments: {n_tbins} flux bins of [{t_min}, {t_max}), ivar_min = {ivar_min}")
+        t0, dt = float(t_min), (float(t_max) - float(t_min)) / nt
+        if stack is not None:
+            want = PDFStack._round_bins(t0, dt, nt) + (bool(relative), bool(clamp), float(np.float32(imin)))
+            if not isinstance(stack, PDFStack) or stack.S != S or stack.L != L or \
+                    stack.flux_bins + (stack.relative, stack.clamp, stack.ivar_min) != want or \
+                    (bins is not None and PDFStack._round_bins(bins[0], bins[1], bins[2]) != stack.bins):
+                raise QFAHipError(f"flux_pdf_segments(stack=...): expected a PDFStack of {S} draws and segments of {L} pixels on the "
+                                  "same z-bins, flux bins, flags and ivar_min")
+            _lib.require_device_tensor(stack.buf, torch.float64, "stack")
+        elif bins is not None:
+            stack = PDFStack.zeros(S, bins[0], bins[1], bins[2], L, t0, dt, nt, relative, clamp, imin, dev)
+        pp = _p1d_params(tbar_bins, St, int(pixel_start), L, nseg, min_used, stack)
+        qq = _lib.PDFParams(t0, dt, nt, imin)
+        need = _lib.lib().qfa_flux_pdf_workspace_bytes(B * S, S, self.Nb, L, nseg, int(pp.nz), nt) if L >= 1 and nseg >= 1 else 0
+        if need == 0:
+            raise QFAHipError(f"flux_pdf_segments: unsupported shape B={B} S={S} Nb={self.Nb} seg_len={L} n_segments={nseg} "
+                              f"nz={pp.nz} n_tbins={nt}")
+        ws = self._scratch("p1d_ws", need)                        # (shared with p1d: the calls own it only while they run)
+        hist = torch.empty((B, S, nseg, nt), dtype=torch.int32, device=dev) if return_segments else None
+        flags = (_lib.F_PDF_RELATIVE if relative else 0) | (_lib.F_PDF_CLAMP if clamp else 0)
+        _lib.check(_lib.lib().qfa_flux_pdf_f32(
+            _lib.require_device_tensor(trans, f32, "trans"), _lib.require_device_tensor(ivar, f32, "ivar"), C.byref(bs),
+            _ptr(tbar), B, S, self.Nb, C.byref(pp), C.byref(qq), flags, _ptr(hist), _ptr(stack.buf) if stack is not None else None,
+            _ptr(ws), ws.numel(), _lib.current_stream(dev)), "qfa_flux_pdf_f32")
+        return hist, stack
+
     def flux_power(self, dataloader, z_min, z_max, n_zbins, *, n_segments=3, seg_len=None, min_used_frac=0.75, tbar=None,
                    tbar_nbins=64, n_samples=0, seed=0, batch_size=4096, cont_min=0.0, dv=None):
         """The 1D flux power spectrum of a whole dataloader: a ``P1DStack`` of S = max(1, n_samples) draws over ``n_zbins`` bins of
@@ -368,16 +412,34 @@ class ForestStatistics(object):
                                      tbar_nbins, n_samples, seed, batch_size, cont_min, dv, None,
                                      {"n_lags": int(n_lags), "sigma2_lss": float(sigma2_lss), "unit_weights": bool(unit_weights)})
 
+    def flux_pdf(self, dataloader, z_min, z_max, n_zbins, n_tbins=20, *, t_min=0.0, t_max=1.0, relative=False, clamp=True,
+                 ivar_min=0.0, n_segments=3, seg_len=None, min_used_frac=0.75, tbar=None, tbar_nbins=64, n_samples=0, seed=0,
+                 batch_size=4096, cont_min=0.0):
+        """The flux PDF of a whole dataloader and its covariance: a ``PDFStack`` of S = max(1, n_samples) draws over ``n_zbins`` bins
+        of [z_min, z_max) and ``n_tbins`` flux bins of [t_min, t_max) (``relative``, ``clamp``, ``ivar_min``: see
+        ``flux_pdf_segments``).  Everything else is ``flux_power``'s: the same segments, mean transmission, draws and loop over the
+        loader, with ``flux_pdf_segments`` in the place of ``p1d``.  The PDF rides on segments, not on the per-pixel z-bins of
+        ``mean_transmission``, because the segment is the unit its covariance is estimated from.  The sums are integers: the
+        result does not depend on ``batch_size`` at all.  Under data parallelism the sums are all-reduced over the model's group."""
+        pdf = {"t_min": float(t_min), "t_max": float(t_max), "n_tbins": int(n_tbins), "relative": bool(relative), "clamp": bool(clamp),
+               "ivar_min": float(ivar_min)}
+        if not (1 <= pdf["n_tbins"] <= 64 and pdf["t_max"] > pdf["t_min"] and np.isfinite(pdf["t_min"]) and np.isfinite(pdf["t_max"])
+                and pdf["ivar_min"] >= 0.0 and np.isfinite(pdf["ivar_min"])):
+            raise QFAHipError(f"flux_pdf: {n_tbins} flux bins of [{t_min}, {t_max}), ivar_min = {ivar_min}")
+        return self._power_of_loader("flux_pdf", dataloader, z_min, z_max, n_zbins, n_segments, seg_len, min_used_frac, tbar,
+                                     tbar_nbins, n_samples, seed, batch_size, cont_min, None, None, None, pdf)
+
     def _power_of_loader(self, what, dataloader, z_min, z_max, n_zbins, n_segments, seg_len, min_used_frac, tbar, tbar_nbins,
-                         n_samples, seed, batch_size, cont_min, dv, bands, lags=None):
-        """the loop `flux_power` (``bands`` and ``lags`` None: a ``P1DStack`` through ``p1d``), `band_power` (``bands``: the keywords
-        of ``p1d_bands``; a ``P1DBandStack``) and `flux_correlation` (``lags``: the keywords of ``xi``; a ``XiStack``) share"""
+                         n_samples, seed, batch_size, cont_min, dv, bands, lags=None, pdf=None):
+        """the loop `flux_power` (``bands``, ``lags`` and ``pdf`` None: a ``P1DStack`` through ``p1d``), `band_power` (``bands``: the
+        keywords of ``p1d_bands``; a ``P1DBandStack``), `flux_correlation` (``lags``: the keywords of ``xi``; a ``XiStack``) and
+        `flux_pdf` (``pdf``: the keywords of ``flux_pdf_segments``; a ``PDFStack``) share"""
         nseg, nz, S = int(n_segments), int(n_zbins), max(1, int(n_samples))
         L = int(seg_len) if seg_len is not None else (self.Nb // nseg if nseg > 0 else 0)
         if nseg < 1 or L < 1 or nseg * L > self.Nb or nz < 1 or not float(z_max) > float(z_min) or not 0.0 < float(min_used_frac) <= 1.0:
             raise QFAHipError(f"{what}: {nseg} segments of {L} pixels on Nb = {self.Nb}, bins [{z_min}, {z_max}) / {nz}, "
                               f"min_used_frac = {min_used_frac}")
-        if dv is None:
+        if dv is None and not (pdf is not None and tbar is not None):   # (the PDF needs dv for the range of its own <T> alone)
             wav = getattr(dataloader, "wav_grid", None)
             if wav is None or len(wav) < 2:
                 raise QFAHipError(what + ": the dataloader has no wav_grid: pass dv (km/s per pixel)")
@@ -393,7 +455,11 @@ class ForestStatistics(object):
         if not isinstance(tbar, ForestStack) or tbar.S not in (1, S):
             raise QFAHipError(f"{what}: tbar must be a ForestStack of 1 or {S} draws")
         tmean = tbar.mean.to(f32)
-        if lags is not None:
+        if pdf is not None:
+            stack = PDFStack.zeros(S, z_min, (float(z_max) - float(z_min)) / nz, nz, L, pdf["t_min"],
+                                   (pdf["t_max"] - pdf["t_min"]) / pdf["n_tbins"], pdf["n_tbins"], pdf["relative"], pdf["clamp"],
+                                   pdf["ivar_min"], self.device)
+        elif lags is not None:
             stack = XiStack.zeros(S, z_min, (float(z_max) - float(z_min)) / nz, nz, L, lags["n_lags"], dv, self.device)
         elif bands is None:
             stack = P1DStack.zeros(S, z_min, (float(z_max) - float(z_min)) / nz, nz, L, dv, self.device)
@@ -415,7 +481,9 @@ class ForestStatistics(object):
                 tr, iv, _ = self.forest(**inputs, h=hs, unc=unc, cont_min=cont_min)
                 kw = dict(tbar=tmean if tbar.S == 1 else tmean[s0:s1], tbar_bins=tbar.bins, seg_len=L, n_segments=nseg,
                           min_used=min_used, stack=stack.draws(s0, s1), return_segments=False)
-                if lags is not None:
+                if pdf is not None:
+                    self.flux_pdf_segments(tr, iv, **zin, **kw, **pdf)
+                elif lags is not None:
                     self.xi(tr, iv, **zin, **kw, **lags)
                 elif bands is None:
                     self.p1d(tr, iv, **zin, **kw)
