@@ -4,7 +4,7 @@
 //   k_p1d_twiddle  tw[q] = (cos, sin)(2 pi q / L), q < L: evaluated in float64 on the exact integer q, rounded to float32 once
 //   k_p1d          a block owns 16 segments (rows of the product) and kModes consecutive modes.  It walks the L pixels in chunks of
 //                  kKC: (1) every thread forms delta_F = T / <T>(z) - 1 and the noise variance of four pixels of one row from trans /
-//                  ivar / z / tbar and stores the deltas to LDS -- delta_F never reaches memory; pixels past L and rows past the last
+//                  ivar / z / tbar (the pixel rule of qfa_segment.h) and stores the deltas to LDS -- delta_F never reaches memory; pixels past L and rows past the last
 //                  segment are zeros; (2) every wave runs v_mfma_f32_16x16x4_f32 over the chunk: A = 16 rows x 4 pixels of deltas
 //                  from LDS, B = 4 pixels x 16 modes of cos (one accumulator) and of sin (a second one), the twiddle of (pixel j,
 //                  mode m) read from the length-L table in LDS at the exact integer (j m) mod L, carried from one K step to the next
@@ -19,6 +19,7 @@
 #include <stdint.h>
 
 #include "qfa_common.h"
+#include "qfa_segment.h"
 
 namespace qfa_p1d {
 
@@ -41,6 +42,7 @@ struct Args {
     int b0, Bc, S, St, Nb, L, M, nseg, p_lo, min_used, nT, nz, factored;
     float zT0, inv_dzT, z0, inv_dz;
 };
+static_assert(qfa_segment::has_segment_fields<Args>(), "the fields qfa_segment.h reads");
 
 static __global__ void k_p1d_twiddle(int L, float2 *__restrict__ tw) {
     const int q = blockIdx.x * blockDim.x + threadIdx.x;
@@ -54,7 +56,7 @@ static __global__ void k_p1d_twiddle(int L, float2 *__restrict__ tw) {
 __global__ __launch_bounds__(kThreads) void k_p1d(const Args a) {
     extern __shared__ __align__(16) float lds[];                                  // [deltas 16 x kStride | table L x 2]
     __shared__ int s_valid[kRows];
-    const int L = a.L, M = a.M, S = a.S, Nb = a.Nb, nseg = a.nseg;
+    const int L = a.L, M = a.M, S = a.S, nseg = a.nseg;
     float *dl = lds;
     float2 *tw = reinterpret_cast<float2 *>(lds + kRows * kStride);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -72,15 +74,7 @@ __global__ __launch_bounds__(kThreads) void k_p1d(const Args a) {
         s = (int)(rs % S);
         bl = (int)(rs / S);
     }
-    const int b = a.b0 + bl;
-    const unsigned long long zrow = rowok ? batch_row(a.bt, b) : 0ull;
-    const float zq = (rowok && a.factored) ? a.bt.zq1[zrow] : 0.f;
-    const int pseg = a.p_lo + g * L;                                              // the segment's first pixel
-    const float *tr = a.trans + ((int64_t)b * S + s) * Nb + pseg;
-    const float *iv = a.ivar + ((int64_t)b * S + s) * Nb + pseg;
-    const float *tb = a.tbar + (int64_t)(a.St == 1 ? 0 : s) * a.nT;
-    const float *zr = a.factored ? a.bt.pix_ratio + pseg : a.bt.zabs + zrow * (unsigned long long)Nb + (unsigned)pseg;
-    const float fnT = (float)a.nT;
+    const qfa_segment::Segment sg = qfa_segment::locate(a, qfa_segment::tbar_row(a, s), bl, s, g, rowok);
     double vsum = 0.0;
     int nused = 0;
 
@@ -104,17 +98,11 @@ __global__ __launch_bounds__(kThreads) void k_p1d(const Args a) {
             const int j = j0 + pcol + k;
             float d = 0.f;
             if (rowok && j < L) {
-                const float T = tr[j], w = iv[j];
-                const float z = a.factored ? __fmaf_rn(zq, zr[j], -1.0f) : zr[j];
-                const float kf = floorf(__fmul_rn(__fsub_rn(z, a.zT0), a.inv_dzT));
-                float tbv = 0.f;
-                if (kf >= 0.f && kf < fnT) tbv = tb[(int)kf];                     // (a NaN fails both)
-                const bool used = w > 0.f && tbv > 0.f;                          // (a NaN tbar fails the comparison)
-                const float dd = __fsub_rn(__fdiv_rn(T, tbv), 1.0f);
-                const float vv = __fdiv_rn(1.0f, __fmul_rn(w, __fmul_rn(tbv, tbv)));
-                d = used ? dd : 0.f;                                              // selects: nothing under the mask reaches an output
-                vsum = __dadd_rn(vsum, used ? (double)vv : 0.0);
-                nused += used ? 1 : 0;
+                const qfa_segment::Pixel px = qfa_segment::pixel(a, sg, j);
+                const qfa_segment::Contrast c = qfa_segment::contrast(px);
+                d = px.used ? c.d : 0.f;                                          // selects: nothing under the mask reaches an output
+                vsum = __dadd_rn(vsum, px.used ? (double)c.v : 0.0);
+                nused += px.used ? 1 : 0;
             }
             d4[k] = d;
         }
@@ -146,13 +134,7 @@ __global__ __launch_bounds__(kThreads) void k_p1d(const Args a) {
         s_valid[prow] = valid ? 1 : 0;
         if (blockIdx.y == 0 && rowok) {
             if (a.noise) a.noise[q] = valid ? (float)(vsum / (double)L) : 0.f;
-            if (a.code) {
-                const int jc = L / 2;
-                const float zc = a.factored ? __fmaf_rn(zq, zr[jc], -1.0f) : zr[jc];
-                const float kf = floorf(__fmul_rn(__fsub_rn(zc, a.z0), a.inv_dz));
-                const bool in = valid && kf >= 0.f && kf < (float)a.nz;
-                a.code[(int64_t)s * ((int64_t)a.Bc * nseg) + (int64_t)bl * nseg + g] = in ? (int)kf : -1;
-            }
+            if (a.code) a.code[qfa_segment::code_slot(a.Bc, nseg, bl, s, g)] = qfa_segment::segment_code(a, sg, valid);
         }
     }
     __syncthreads();
@@ -204,7 +186,7 @@ static __global__ __launch_bounds__(256) void k_p1d_reduce(const int *__restrict
         while (hit) {                                                             // (wave-uniform) hits in segment order
             const int e = base + __ffsll((long long)hit) - 1;
             hit &= hit - 1;
-            const int64_t seg = ((int64_t)(e / nseg) * S + s) * nseg + e % nseg;
+            const int64_t seg = qfa_segment::chunk_segment(e, s, S, nseg);
             if (mine) {
                 const double p = (double)power[seg * M + mi];
                 aP = __dadd_rn(aP, p);

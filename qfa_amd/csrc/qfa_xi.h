@@ -1,8 +1,8 @@
 // qfa_xi.h -- the pair-weighted line-of-sight correlation function of forest segments and its (lag, z) stack (include/qfa_hip.h,
-// qfa_xi_f32).  Built in qfa_p1d.hip; the per-pixel rule, validity and the z-bin of a segment are k_p1d's (qfa_p1d.h).
+// qfa_xi_f32).  Built in qfa_p1d.hip; the per-pixel rule and the z-bin of a segment are qfa_segment.h's.
 //
 //   k_xi         a block of 256 threads owns one segment.  (1) thread j mod 256 forms w_j and x_j = w_j d_j from trans / ivar / z / tbar
-//                (k_p1d's step 1 and the weight on top of it) and stores them to LDS, zeros behind pixel L - 1; the threads add
+//                (the pixel rule and the weight on top of it) and stores them to LDS, zeros behind pixel L - 1; the threads add
 //                their used pixels and their (w w) v, a butterfly and the four waves in order make n_used and N0.  delta_F never
 //                reaches memory.  (2) a valid segment: thread (t, c) owns the eight lags 8t .. 8t + 7 and the pixels of chunk c,
 //                [c Jc, (c + 1) Jc) below L - 8t (pairs of these lags that start further up fall off the segment).  It walks them in
@@ -15,19 +15,19 @@
 //   k_xi_stack   a block owns one chunk of 64 consecutive segments (in order of (b, g)) of one draw: per z-bin the wave ballots the
 //                chunk's codes (lane i holds segment i), and thread l adds W_l, A_l and their three products (float64, each rounded
 //                once) in segment order from 0; the partial row of (chunk, draw, z-bin) goes to the workspace.
-//   k_xi_reduce  thread per entry of stack (S, nz, 2 + 5 nlag): adds the partials in chunk order onto what `stack` holds (or 0).
+// The stack (S, nz, 2 + 5 nlag) is k_chunk_reduce's (qfa_segment.h) with head = 2 + 5 nlag, n = 0.
 // No atomics, and nothing here depends on the grid: k_p1d_band's decomposition (qfa_p1d_band.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "qfa_common.h"
-#include "qfa_p1d_band.h"
+#include "qfa_segment.h"
 
 namespace qfa_xi {
 
 constexpr int kThreads = 256;
-constexpr int kChunk = qfa_p1d_band::kChunk;    // segments of a reduction chunk (qfa_p1d_band_chunk_segments())
+constexpr int kChunk = qfa_segment::kChunk;     // segments of a reduction chunk (qfa_p1d_band_chunk_segments())
 constexpr int kLags = 8;                        // lags of a thread
 constexpr int kStep = 4;                        // pixels of a step
 constexpr int kPad = 12;                        // zeros behind the segment: the last step reads x[j + 8t + 11], j + 8t <= L - 1
@@ -68,6 +68,7 @@ struct Args {
     Tile tile;
     float zT0, inv_dzT, z0, inv_dz, sigma2;
 };
+static_assert(qfa_segment::has_segment_fields<Args>(), "the fields qfa_segment.h reads");
 
 // grid (gx, gy) with gx gy >= segments of the launch; dynamic LDS: (dup ? 4 : 2) Ls floats.
 // A thread's three reads of x[j + 8t ..] are 32 bytes apart from its neighbour's: the sixteen lanes that ds_read_b128 serves in one
@@ -79,7 +80,7 @@ __global__ __launch_bounds__(kThreads) void k_xi(const Args a) {
     __shared__ __align__(16) float red[kThreads * 2 * kLags];                     // [chunk][lag group][W 8 | A 8]
     __shared__ float s_n0[kThreads / 64];
     __shared__ int s_nu[kThreads / 64];
-    const int L = a.L, nlag = a.nlag, S = a.S, Nb = a.Nb, nseg = a.nseg;
+    const int L = a.L, nlag = a.nlag, S = a.S, nseg = a.nseg;
     const int Lp = a.tile.Lp, Ls = a.tile.Ls, dup = a.tile.dup, ntp = a.tile.ntp, nc = a.tile.nc, Jc = a.tile.Jc;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int64_t nsegs = (int64_t)a.Bc * S * nseg;
@@ -90,15 +91,18 @@ __global__ __launch_bounds__(kThreads) void k_xi(const Args a) {
     const int g = (int)(q % nseg);
     const int64_t rs = q / nseg;
     const int s = (int)(rs % S), bl = (int)(rs / S);
+    // (qfa_segment::locate and code_slot written out, and `used` re-formed from the pixel below: this kernel's code is sensitive to how
+    // these reach the compiler -- profiles/segment_refactor_asm.txt -- and in this form it is the code it was before qfa_segment.h)
     const int b = a.b0 + bl;
     const unsigned long long zrow = batch_row(a.bt, b);
-    const float zq = a.factored ? a.bt.zq1[zrow] : 0.f;
+    qfa_segment::Segment sg;
+    sg.zq = a.factored ? a.bt.zq1[zrow] : 0.f;
     const int pseg = a.p_lo + g * L;                                              // the segment's first pixel
-    const float *tr = a.trans + ((int64_t)b * S + s) * Nb + pseg;
-    const float *iv = a.ivar + ((int64_t)b * S + s) * Nb + pseg;
-    const float *tb = a.tbar + (int64_t)(a.St == 1 ? 0 : s) * a.nT;
-    const float *zr = a.factored ? a.bt.pix_ratio + pseg : a.bt.zabs + zrow * (unsigned long long)Nb + (unsigned)pseg;
-    const float fnT = (float)a.nT;
+    sg.tr = a.trans + ((int64_t)b * S + s) * a.Nb + pseg;
+    sg.iv = a.ivar + ((int64_t)b * S + s) * a.Nb + pseg;
+    sg.tb = a.tbar + (int64_t)(a.St == 1 ? 0 : s) * a.nT;
+    sg.zr = a.factored ? a.bt.pix_ratio + pseg : a.bt.zabs + zrow * (unsigned long long)a.Nb + (unsigned)pseg;
+
 
     // ---- (1) w and x of the segment, once; n_used and N0
     float n0 = 0.f;
@@ -107,16 +111,11 @@ __global__ __launch_bounds__(kThreads) void k_xi(const Args a) {
         float w = 0.f, x = 0.f;
         if (j < L) {
 #pragma clang fp contract(off)
-            const float T = tr[j], wi = iv[j];
-            const float z = a.factored ? __fmaf_rn(zq, zr[j], -1.0f) : zr[j];
-            const float kf = floorf(__fmul_rn(__fsub_rn(z, a.zT0), a.inv_dzT));
-            float tbv = 0.f;
-            if (kf >= 0.f && kf < fnT) tbv = tb[(int)kf];                         // (a NaN fails both)
-            const bool used = wi > 0.f && tbv > 0.f;                              // (a NaN tbar fails the comparison)
-            const float dd = __fsub_rn(__fdiv_rn(T, tbv), 1.0f);
-            const float vv = __fdiv_rn(1.0f, __fmul_rn(wi, __fmul_rn(tbv, tbv)));
-            const float d = used ? dd : 0.f;                                      // selects: nothing under the mask reaches an output
-            const float v = used ? vv : 0.f;
+            const qfa_segment::Pixel px = qfa_segment::pixel(a, sg, j);
+            const qfa_segment::Contrast c = qfa_segment::contrast(px);
+            const bool used = px.ivar > 0.f && px.tbar > 0.f;                     // (qfa_segment::pixel_used, see above)
+            const float d = used ? c.d : 0.f;                                     // selects: nothing under the mask reaches an output
+            const float v = used ? c.v : 0.f;
             const float wv = __fdiv_rn(1.0f, __fadd_rn(v, a.sigma2));
             w = a.unit_w ? (used ? 1.0f : 0.f) : ((used && __builtin_isfinite(wv)) ? wv : 0.f);
             x = __fmul_rn(w, d);
@@ -145,13 +144,7 @@ __global__ __launch_bounds__(kThreads) void k_xi(const Args a) {
     const bool valid = nused >= a.min_used;
     if (tid == 0) {
         if (a.noise0) a.noise0[q] = valid ? n0 : 0.f;
-        if (a.code) {
-            const int jc = L / 2;
-            const float zc = a.factored ? __fmaf_rn(zq, zr[jc], -1.0f) : zr[jc];
-            const float kf = floorf(__fmul_rn(__fsub_rn(zc, a.z0), a.inv_dz));
-            const bool in = valid && kf >= 0.f && kf < (float)a.nz;
-            a.code[(int64_t)s * ((int64_t)a.Bc * nseg) + (int64_t)bl * nseg + g] = in ? (int)kf : -1;
-        }
+        if (a.code) a.code[(int64_t)s * ((int64_t)a.Bc * nseg) + (int64_t)bl * nseg + g] = qfa_segment::segment_code(a, sg, valid);
     }
     if (!a.pairs) return;
     float *out = a.pairs + q * 2 * (int64_t)nlag;
@@ -257,8 +250,7 @@ static __global__ __launch_bounds__(kThreads) void k_xi_stack(const StackArgs a)
             while (hit) {                                                         // (wave-uniform) hits in segment order
                 const int i = __ffsll((long long)hit) - 1;
                 hit &= hit - 1;
-                const int e = e0 + i;
-                const int64_t seg = ((int64_t)(e / nseg) * S + s) * nseg + e % nseg;
+                const int64_t seg = qfa_segment::chunk_segment(e0 + i, s, S, nseg);
                 if (mine) {
                     const double W = (double)a.pairs[seg * 2 * nlag + l], A = (double)a.pairs[seg * 2 * nlag + nlag + l];
                     const double ww = W * W, aw = A * W, aa = A * A;
@@ -284,21 +276,6 @@ static __global__ __launch_bounds__(kThreads) void k_xi_stack(const StackArgs a)
             }
         }
     }
-}
-
-// grid (S nz, ceil((2 + 5 nlag) / 256))
-static __global__ __launch_bounds__(256) void k_xi_reduce(const double *__restrict__ part, int chunks, int S, int nz, int nlag, int zero,
-                                                          double *__restrict__ stack) {
-#pragma clang fp contract(off)
-    const int j = blockIdx.y * 256 + threadIdx.x;
-    const int Wd = 2 + 5 * nlag;
-    if (j >= Wd) return;
-    double *out = stack + (int64_t)blockIdx.x * Wd + j;                           // blockIdx.x = s nz + kz
-    const double *p = part + (int64_t)blockIdx.x * Wd + j;
-    const int64_t stride = (int64_t)S * nz * Wd;
-    double acc = zero ? 0.0 : *out;
-    for (int c = 0; c < chunks; ++c) acc = acc + p[c * stride];
-    *out = acc;
 }
 
 }  // namespace qfa_xi

@@ -5,6 +5,7 @@ base class of ``qfa_amd.model.QFA`` and uses the model's plumbing (``_batch_stru
 ``_loader_slices``) as any other method of it does; every call goes through the C-ABI in ``include/qfa_hip.h``."""
 from __future__ import annotations
 
+import collections
 import ctypes as C
 
 import numpy as np
@@ -15,6 +16,11 @@ from ._lib import QFAHipError, _ptr
 from .stacks import ForestStack, P1DBandStack, P1DStack, PDFStack, XiStack, _band_map, _check_segments, _edges, _mode_k, _window2
 
 f32 = torch.float32
+
+# what `_power_of_loader` needs to know of a statistic: zeros(S, z0, dz, nz, L, dv) makes its stack, ``call`` is its method of a slice
+# with its own ``keywords``, check(L) (or None) returns what is wrong with segments of L pixels, ``needs_dv`` False: dv matters only
+# where <T> is made in the loop's own `mean_transmission`
+_LoaderStat = collections.namedtuple("_LoaderStat", "zeros call keywords check needs_dv", defaults=(None, True))
 
 
 def _p1d_params(tbar_bins, St, p_lo, L, nseg, min_used, stack):
@@ -193,6 +199,37 @@ class ForestStatistics(object):
                 raise QFAHipError(what + ": pass zabs, zfac = (zq1, pix_ratio) or batch")
         return B, S, tbar, St, tbar_bins, bs, keep
 
+    def _segment_call(self, what, name, inp, trans, ivar, L, nseg, pixel_start, min_used, bins, stack, *, cls, same, zeros, expected,
+                      own=None):
+        """what `p1d`, `p1d_bands`, `xi` and `flux_pdf_segments` share behind ``inp`` = `_p1d_inputs`' result: ``stack`` is checked (a
+        ``cls`` of S draws and segments of L pixels on the same bins for which ``same(stack)`` holds, else the error ends in
+        ``expected``) or made by ``zeros()`` when ``bins`` asks for one; ``own(stack)`` -> (the statistic's own size, its note in the
+        error of an unsupported shape, its parameter struct); qfa_p1d_t; the workspace of ``name``_workspace_bytes.  Returns
+        (stack, call): call(flags, *outputs) runs ``name``_f32 with the outputs between the flags and the stack."""
+        B, S, tbar, St, tbar_bins, bs, keep = inp
+        dev = self.device
+        if stack is not None:
+            if not isinstance(stack, cls) or stack.S != S or stack.L != L or not same(stack) or \
+                    (bins is not None and cls._round_bins(bins[0], bins[1], bins[2]) != stack.bins):
+                raise QFAHipError(f"{what}(stack=...): expected a {cls.__name__} of {S} draws{expected}")
+            _lib.require_device_tensor(stack.buf, torch.float64, "stack")
+        elif bins is not None:
+            stack = zeros()
+        size, note, prm = own(stack) if own is not None else ((), "", None)
+        pp = _p1d_params(tbar_bins, St, int(pixel_start), L, nseg, min_used, stack)
+        h = _lib.lib()
+        need = getattr(h, name + "_workspace_bytes")(B * S, S, self.Nb, L, nseg, int(pp.nz), *size) if L >= 1 and nseg >= 1 else 0
+        if need == 0:
+            raise QFAHipError(f"{what}: unsupported shape B={B} S={S} Nb={self.Nb} seg_len={L} n_segments={nseg} nz={pp.nz}{note}")
+        ws = self._scratch("p1d_ws", need)                        # (one for the four calls: they own it only while they run)
+
+        def call(flags, *outputs):
+            _lib.check(getattr(h, name + "_f32")(
+                _lib.require_device_tensor(trans, f32, "trans"), _lib.require_device_tensor(ivar, f32, "ivar"), C.byref(bs),
+                _ptr(tbar), B, S, self.Nb, C.byref(pp), *(() if prm is None else (C.byref(prm),)), flags, *(_ptr(o) for o in outputs),
+                _ptr(stack.buf) if stack is not None else None, _ptr(ws), ws.numel(), _lib.current_stream(dev)), name + "_f32")
+        return stack, call
+
     def p1d(self, trans, ivar, *, zabs=None, zfac=None, batch=None, tbar, tbar_bins=None, seg_len, n_segments, pixel_start=0,
             min_used, bins=None, stack=None, return_segments=True, dv=1.0):
         """The 1D flux power spectrum of forest segments and its (k, z) stack (qfa_p1d_f32; the contract is in include/qfa_hip.h).
@@ -204,30 +241,17 @@ class ForestStatistics(object):
         the stack (``dv``: the pixel width in km/s it reports k and P in); ``stack``: a ``P1DStack`` to ADD to.  Returns
         (power (B, S, n_segments, M), noise (B, S, n_segments), stack): float32 P_m = |delta~_m|^2 / L for m = 1 .. M = seg_len // 2
         and the noise level, both in pixel units (None with ``return_segments`` False), and the ``P1DStack`` (or None)."""
-        dev = self.device
-        B, S, tbar, St, tbar_bins, bs, keep = self._p1d_inputs("p1d", bins is not None or stack is not None or return_segments,
-                                                               trans, ivar, zabs, zfac, batch, tbar, tbar_bins)
-        L, nseg = int(seg_len), int(n_segments)
-        if stack is not None:
-            if not isinstance(stack, P1DStack) or stack.S != S or stack.L != L or \
-                    (bins is not None and P1DStack._round_bins(bins[0], bins[1], bins[2]) != stack.bins):
-                raise QFAHipError(f"p1d(stack=...): expected a P1DStack of {S} draws and segments of {L} pixels on the same bins")
-            _lib.require_device_tensor(stack.buf, torch.float64, "stack")
-        elif bins is not None:
-            stack = P1DStack.zeros(S, bins[0], bins[1], bins[2], L, dv, dev)
-        pp = _p1d_params(tbar_bins, St, int(pixel_start), L, nseg, min_used, stack)
-        need = _lib.lib().qfa_p1d_workspace_bytes(B * S, S, self.Nb, L, nseg, int(pp.nz)) if L >= 1 and nseg >= 1 else 0
-        if need == 0:
-            raise QFAHipError(f"p1d: unsupported shape B={B} S={S} Nb={self.Nb} seg_len={L} n_segments={nseg} nz={pp.nz}")
-        ws = self._scratch("p1d_ws", need)
+        inp = self._p1d_inputs("p1d", bins is not None or stack is not None or return_segments, trans, ivar, zabs, zfac, batch, tbar,
+                               tbar_bins)
+        B, S, L, nseg, dev = inp[0], inp[1], int(seg_len), int(n_segments), self.device
+        stack, call = self._segment_call("p1d", "qfa_p1d", inp, trans, ivar, L, nseg, pixel_start, min_used, bins, stack, cls=P1DStack,
+                                         same=lambda st: True, zeros=lambda: P1DStack.zeros(S, bins[0], bins[1], bins[2], L, dv, dev),
+                                         expected=f" and segments of {L} pixels on the same bins")
         power = noise = None
         if return_segments:
             power = torch.empty((B, S, nseg, L // 2), dtype=f32, device=dev)
             noise = torch.empty((B, S, nseg), dtype=f32, device=dev)
-        _lib.check(_lib.lib().qfa_p1d_f32(
-            _lib.require_device_tensor(trans, f32, "trans"), _lib.require_device_tensor(ivar, f32, "ivar"), C.byref(bs),
-            _ptr(tbar), B, S, self.Nb, C.byref(pp), 0, _ptr(power), _ptr(noise), _ptr(stack.buf) if stack is not None else None,
-            _ptr(ws), ws.numel(), _lib.current_stream(dev)), "qfa_p1d_f32")
+        call(0, power, noise)
         return power, noise, stack
 
     def _p1d_band_tables(self, L, dv, k_edges, resolution_kms):
@@ -259,34 +283,22 @@ class ForestStatistics(object):
         modes of (P_m - N) dv / W^2(k_m): ``subtract_noise`` False keeps the noise in, ``resolution_kms`` divides by
         ``P1DStack.window2``.  ``bins`` = (z0, dz, nz) asks for the stack, ``stack``: a ``P1DBandStack`` to ADD to.  Returns
         (bandpower (B, S, n_segments, nband) float64, or None without ``return_segments``; the ``P1DBandStack``, or None)."""
-        dev = self.device
-        B, S, tbar, St, tbar_bins, bs, keep = self._p1d_inputs("p1d_bands", bins is not None or stack is not None or return_segments,
-                                                               trans, ivar, zabs, zfac, batch, tbar, tbar_bins)
-        L, nseg = int(seg_len), int(n_segments)
-        if stack is not None:
-            if not isinstance(stack, P1DBandStack) or stack.S != S or stack.L != L or stack._k_edges != _edges(k_edges) or \
-                    (bins is not None and P1DBandStack._round_bins(*bins) != stack.bins):
-                raise QFAHipError(f"p1d_bands(stack=...): expected a P1DBandStack of {S} draws and segments of {L} pixels on the "
-                                  "same bins and bands")
-            _lib.require_device_tensor(stack.buf, torch.float64, "stack")
-            dv = stack.dv
-        elif bins is not None:
-            stack = P1DBandStack.zeros(S, bins[0], bins[1], bins[2], L, dv, k_edges, dev)
-        nband = len(_edges(k_edges)) - 1
-        band, weight = self._p1d_band_tables(L, dv, k_edges, resolution_kms)
-        pp = _p1d_params(tbar_bins, St, int(pixel_start), L, nseg, min_used, stack)
-        qq = _lib.P1DBandParams()
-        qq.nband, qq.band, qq.weight, qq.subtract_noise = nband, band.data_ptr(), weight.data_ptr(), 1 if subtract_noise else 0
-        need = _lib.lib().qfa_p1d_band_workspace_bytes(B * S, S, self.Nb, L, nseg, int(pp.nz), nband) if L >= 1 and nseg >= 1 else 0
-        if need == 0:
-            raise QFAHipError(f"p1d_bands: unsupported shape B={B} S={S} Nb={self.Nb} seg_len={L} n_segments={nseg} nz={pp.nz} "
-                              f"nband={nband}")
-        ws = self._scratch("p1d_ws", need)                        # (shared with p1d: both calls own it only while they run)
-        bandpower = torch.empty((B, S, nseg, nband), dtype=torch.float64, device=dev) if return_segments else None
-        _lib.check(_lib.lib().qfa_p1d_band_f32(
-            _lib.require_device_tensor(trans, f32, "trans"), _lib.require_device_tensor(ivar, f32, "ivar"), C.byref(bs),
-            _ptr(tbar), B, S, self.Nb, C.byref(pp), C.byref(qq), 0, _ptr(bandpower), _ptr(stack.buf) if stack is not None else None,
-            _ptr(ws), ws.numel(), _lib.current_stream(dev)), "qfa_p1d_band_f32")
+        inp = self._p1d_inputs("p1d_bands", bins is not None or stack is not None or return_segments, trans, ivar, zabs, zfac, batch, tbar,
+                               tbar_bins)
+        B, S, L, nseg, dev = inp[0], inp[1], int(seg_len), int(n_segments), self.device
+
+        def own(st):
+            nband, qq = len(_edges(k_edges)) - 1, _lib.P1DBandParams()
+            band, weight = self._p1d_band_tables(L, dv if st is None else st.dv, k_edges, resolution_kms)
+            qq.nband, qq.band, qq.weight, qq.subtract_noise = nband, band.data_ptr(), weight.data_ptr(), 1 if subtract_noise else 0
+            return (nband,), f" nband={nband}", qq
+
+        stack, call = self._segment_call("p1d_bands", "qfa_p1d_band", inp, trans, ivar, L, nseg, pixel_start, min_used, bins, stack,
+                                         cls=P1DBandStack, same=lambda st: st._k_edges == _edges(k_edges),
+                                         zeros=lambda: P1DBandStack.zeros(S, bins[0], bins[1], bins[2], L, dv, k_edges, dev),
+                                         expected=f" and segments of {L} pixels on the same bins and bands", own=own)
+        bandpower = torch.empty((B, S, nseg, len(_edges(k_edges)) - 1), dtype=torch.float64, device=dev) if return_segments else None
+        call(0, bandpower)
         return bandpower, stack
 
     def xi(self, trans, ivar, *, zabs=None, zfac=None, batch=None, tbar, tbar_bins=None, seg_len, n_segments, pixel_start=0, min_used,
@@ -299,33 +311,21 @@ class ForestStatistics(object):
         (z0, dz, nz) asks for the stack (``dv``: the pixel width in km/s it reports the lags in); ``stack``: a ``XiStack`` to ADD
         to.  Returns (pairs (B, S, n_segments, 2, n_lags) float32 = [W_l | A_l], noise0 (B, S, n_segments) float32 = sum_j w_j^2 v_j,
         the noise in A_0 -- both None with ``return_segments`` False -- and the ``XiStack`` (or None))."""
-        dev = self.device
-        B, S, tbar, St, tbar_bins, bs, keep = self._p1d_inputs("xi", bins is not None or stack is not None or return_segments,
-                                                               trans, ivar, zabs, zfac, batch, tbar, tbar_bins)
+        inp = self._p1d_inputs("xi", bins is not None or stack is not None or return_segments, trans, ivar, zabs, zfac, batch, tbar, tbar_bins)
+        B, S, dev = inp[0], inp[1], self.device
         L, nseg, nlag, s2 = int(seg_len), int(n_segments), int(n_lags), float(sigma2_lss)
         if not (L >= 1 and 1 <= nlag <= L and s2 >= 0.0 and np.isfinite(s2)):
             raise QFAHipError(f"xi: n_lags = {n_lags} on segments of {seg_len} pixels, sigma2_lss = {sigma2_lss}")
-        if stack is not None:
-            if not isinstance(stack, XiStack) or stack.S != S or stack.L != L or stack.nlag != nlag or \
-                    (bins is not None and XiStack._round_bins(bins[0], bins[1], bins[2]) != stack.bins):
-                raise QFAHipError(f"xi(stack=...): expected a XiStack of {S} draws, segments of {L} pixels and {nlag} lags on the same bins")
-            _lib.require_device_tensor(stack.buf, torch.float64, "stack")
-        elif bins is not None:
-            stack = XiStack.zeros(S, bins[0], bins[1], bins[2], L, nlag, dv, dev)
-        pp = _p1d_params(tbar_bins, St, int(pixel_start), L, nseg, min_used, stack)
-        xx = _lib.XiParams(nlag, s2)
-        need = _lib.lib().qfa_xi_workspace_bytes(B * S, S, self.Nb, L, nseg, int(pp.nz), nlag) if nseg >= 1 else 0
-        if need == 0:
-            raise QFAHipError(f"xi: unsupported shape B={B} S={S} Nb={self.Nb} seg_len={L} n_segments={nseg} nz={pp.nz} n_lags={nlag}")
-        ws = self._scratch("p1d_ws", need)                        # (shared with p1d: the calls own it only while they run)
+        stack, call = self._segment_call("xi", "qfa_xi", inp, trans, ivar, L, nseg, pixel_start, min_used, bins, stack, cls=XiStack,
+                                         same=lambda st: st.nlag == nlag,
+                                         zeros=lambda: XiStack.zeros(S, bins[0], bins[1], bins[2], L, nlag, dv, dev),
+                                         expected=f", segments of {L} pixels and {nlag} lags on the same bins",
+                                         own=lambda st: ((nlag,), f" n_lags={nlag}", _lib.XiParams(nlag, s2)))
         pairs = noise0 = None
         if return_segments:
             pairs = torch.empty((B, S, nseg, 2, nlag), dtype=f32, device=dev)
             noise0 = torch.empty((B, S, nseg), dtype=f32, device=dev)
-        _lib.check(_lib.lib().qfa_xi_f32(
-            _lib.require_device_tensor(trans, f32, "trans"), _lib.require_device_tensor(ivar, f32, "ivar"), C.byref(bs),
-            _ptr(tbar), B, S, self.Nb, C.byref(pp), C.byref(xx), _lib.F_XI_UNIT_W if unit_weights else 0, _ptr(pairs), _ptr(noise0),
-            _ptr(stack.buf) if stack is not None else None, _ptr(ws), ws.numel(), _lib.current_stream(dev)), "qfa_xi_f32")
+        call(_lib.F_XI_UNIT_W if unit_weights else 0, pairs, noise0)
         return pairs, noise0, stack
 
     def flux_pdf_segments(self, trans, ivar, *, zabs=None, zfac=None, batch=None, tbar, tbar_bins=None, seg_len, n_segments,
@@ -339,37 +339,23 @@ class ForestStatistics(object):
         published PDFs); without it such pixels are in no bin.  ``bins`` = (z0, dz, nz) asks for the stack, ``stack``: a
         ``PDFStack`` to ADD to.  Returns (hist (B, S, n_segments, n_tbins) int32, or None with ``return_segments`` False; the
         ``PDFStack``, or None).  The counts are integers: the stack is exact, whatever the order and the split of the calls."""
-        dev = self.device
-        B, S, tbar, St, tbar_bins, bs, keep = self._p1d_inputs("flux_pdf_segments", bins is not None or stack is not None or
-                                                               return_segments, trans, ivar, zabs, zfac, batch, tbar, tbar_bins)
+        inp = self._p1d_inputs("flux_pdf_segments", bins is not None or stack is not None or return_segments, trans, ivar, zabs, zfac,
+                               batch, tbar, tbar_bins)
+        B, S, dev = inp[0], inp[1], self.device
         L, nseg, nt, imin = int(seg_len), int(n_segments), int(n_tbins), float(ivar_min)
         if not (1 <= nt <= 64 and float(t_max) > float(t_min) and np.isfinite(float(t_min)) and np.isfinite(float(t_max))
                 and imin >= 0.0 and np.isfinite(imin)):
             raise QFAHipError(f"flux_pdf_segments: {n_tbins} flux bins of [{t_min}, {t_max}), ivar_min = {ivar_min}")
         t0, dt = float(t_min), (float(t_max) - float(t_min)) / nt
-        if stack is not None:
-            want = PDFStack._round_bins(t0, dt, nt) + (bool(relative), bool(clamp), float(np.float32(imin)))
-            if not isinstance(stack, PDFStack) or stack.S != S or stack.L != L or \
-                    stack.flux_bins + (stack.relative, stack.clamp, stack.ivar_min) != want or \
-                    (bins is not None and PDFStack._round_bins(bins[0], bins[1], bins[2]) != stack.bins):
-                raise QFAHipError(f"flux_pdf_segments(stack=...): expected a PDFStack of {S} draws and segments of {L} pixels on the "
-                                  "same z-bins, flux bins, flags and ivar_min")
-            _lib.require_device_tensor(stack.buf, torch.float64, "stack")
-        elif bins is not None:
-            stack = PDFStack.zeros(S, bins[0], bins[1], bins[2], L, t0, dt, nt, relative, clamp, imin, dev)
-        pp = _p1d_params(tbar_bins, St, int(pixel_start), L, nseg, min_used, stack)
-        qq = _lib.PDFParams(t0, dt, nt, imin)
-        need = _lib.lib().qfa_flux_pdf_workspace_bytes(B * S, S, self.Nb, L, nseg, int(pp.nz), nt) if L >= 1 and nseg >= 1 else 0
-        if need == 0:
-            raise QFAHipError(f"flux_pdf_segments: unsupported shape B={B} S={S} Nb={self.Nb} seg_len={L} n_segments={nseg} "
-                              f"nz={pp.nz} n_tbins={nt}")
-        ws = self._scratch("p1d_ws", need)                        # (shared with p1d: the calls own it only while they run)
+        want = PDFStack._round_bins(t0, dt, nt) + (bool(relative), bool(clamp), float(np.float32(imin)))
+        stack, call = self._segment_call(
+            "flux_pdf_segments", "qfa_flux_pdf", inp, trans, ivar, L, nseg, pixel_start, min_used, bins, stack, cls=PDFStack,
+            same=lambda st: st.flux_bins + (st.relative, st.clamp, st.ivar_min) == want,
+            zeros=lambda: PDFStack.zeros(S, bins[0], bins[1], bins[2], L, t0, dt, nt, relative, clamp, imin, dev),
+            expected=f" and segments of {L} pixels on the same z-bins, flux bins, flags and ivar_min",
+            own=lambda st: ((nt,), f" n_tbins={nt}", _lib.PDFParams(t0, dt, nt, imin)))
         hist = torch.empty((B, S, nseg, nt), dtype=torch.int32, device=dev) if return_segments else None
-        flags = (_lib.F_PDF_RELATIVE if relative else 0) | (_lib.F_PDF_CLAMP if clamp else 0)
-        _lib.check(_lib.lib().qfa_flux_pdf_f32(
-            _lib.require_device_tensor(trans, f32, "trans"), _lib.require_device_tensor(ivar, f32, "ivar"), C.byref(bs),
-            _ptr(tbar), B, S, self.Nb, C.byref(pp), C.byref(qq), flags, _ptr(hist), _ptr(stack.buf) if stack is not None else None,
-            _ptr(ws), ws.numel(), _lib.current_stream(dev)), "qfa_flux_pdf_f32")
+        call((_lib.F_PDF_RELATIVE if relative else 0) | (_lib.F_PDF_CLAMP if clamp else 0), hist)
         return hist, stack
 
     def flux_power(self, dataloader, z_min, z_max, n_zbins, *, n_segments=3, seg_len=None, min_used_frac=0.75, tbar=None,
@@ -385,7 +371,8 @@ class ForestStatistics(object):
         reducer adds segments in order, so the result does not depend on ``batch_size`` beyond the rounding of float64 sums.
         Under data parallelism the sums are all-reduced over the model's group: every rank returns the global stack."""
         return self._power_of_loader("flux_power", dataloader, z_min, z_max, n_zbins, n_segments, seg_len, min_used_frac, tbar,
-                                     tbar_nbins, n_samples, seed, batch_size, cont_min, dv, None)
+                                     tbar_nbins, n_samples, seed, batch_size, cont_min, dv,
+                                     _LoaderStat(lambda *a: P1DStack.zeros(*a, self.device), self.p1d, {}))
 
     def band_power(self, dataloader, z_min, z_max, n_zbins, k_edges, *, n_segments=3, seg_len=None, min_used_frac=0.75, tbar=None,
                    tbar_nbins=64, n_samples=0, seed=0, batch_size=4096, cont_min=0.0, dv=None, resolution_kms=None,
@@ -397,7 +384,8 @@ class ForestStatistics(object):
         only through the rounding of float64 sums.  Under data parallelism the sums are all-reduced over the model's group."""
         return self._power_of_loader("band_power", dataloader, z_min, z_max, n_zbins, n_segments, seg_len, min_used_frac, tbar,
                                      tbar_nbins, n_samples, seed, batch_size, cont_min, dv,
-                                     {"k_edges": k_edges, "resolution_kms": resolution_kms, "subtract_noise": subtract_noise})
+                                     _LoaderStat(lambda *a: P1DBandStack.zeros(*a, k_edges, self.device), self.p1d_bands,
+                                                 {"k_edges": k_edges, "resolution_kms": resolution_kms, "subtract_noise": subtract_noise}))
 
     def flux_correlation(self, dataloader, z_min, z_max, n_zbins, n_lags, *, n_segments=3, seg_len=None, min_used_frac=0.75, tbar=None,
                          tbar_nbins=64, n_samples=0, seed=0, batch_size=4096, cont_min=0.0, dv=None, sigma2_lss=0.0,
@@ -408,9 +396,12 @@ class ForestStatistics(object):
         (``sigma2_lss``, ``unit_weights``: its weights).  The sums of a slice are formed in chunks of a fixed number of segments, so
         the result depends on ``batch_size`` only through the rounding of float64 sums.  Under data parallelism the sums are
         all-reduced over the model's group."""
+        nlag = int(n_lags)
         return self._power_of_loader("flux_correlation", dataloader, z_min, z_max, n_zbins, n_segments, seg_len, min_used_frac, tbar,
-                                     tbar_nbins, n_samples, seed, batch_size, cont_min, dv, None,
-                                     {"n_lags": int(n_lags), "sigma2_lss": float(sigma2_lss), "unit_weights": bool(unit_weights)})
+                                     tbar_nbins, n_samples, seed, batch_size, cont_min, dv,
+                                     _LoaderStat(lambda S, z0, dz, nz, L, dv: XiStack.zeros(S, z0, dz, nz, L, nlag, dv, self.device), self.xi,
+                                                 {"n_lags": nlag, "sigma2_lss": float(sigma2_lss), "unit_weights": bool(unit_weights)},
+                                                 lambda L: None if 1 <= nlag <= L else f"n_lags = {nlag} on segments of {L} pixels"))
 
     def flux_pdf(self, dataloader, z_min, z_max, n_zbins, n_tbins=20, *, t_min=0.0, t_max=1.0, relative=False, clamp=True,
                  ivar_min=0.0, n_segments=3, seg_len=None, min_used_frac=0.75, tbar=None, tbar_nbins=64, n_samples=0, seed=0,
@@ -426,26 +417,28 @@ class ForestStatistics(object):
         if not (1 <= pdf["n_tbins"] <= 64 and pdf["t_max"] > pdf["t_min"] and np.isfinite(pdf["t_min"]) and np.isfinite(pdf["t_max"])
                 and pdf["ivar_min"] >= 0.0 and np.isfinite(pdf["ivar_min"])):
             raise QFAHipError(f"flux_pdf: {n_tbins} flux bins of [{t_min}, {t_max}), ivar_min = {ivar_min}")
+        zeros = lambda S, z0, dz, nz, L, dv: PDFStack.zeros(S, z0, dz, nz, L, pdf["t_min"], (pdf["t_max"] - pdf["t_min"]) / pdf["n_tbins"],
+                                                            pdf["n_tbins"], pdf["relative"], pdf["clamp"], pdf["ivar_min"], self.device)
+        # (dv None: the PDF needs it for the range of its own <T> alone)
         return self._power_of_loader("flux_pdf", dataloader, z_min, z_max, n_zbins, n_segments, seg_len, min_used_frac, tbar,
-                                     tbar_nbins, n_samples, seed, batch_size, cont_min, None, None, None, pdf)
+                                     tbar_nbins, n_samples, seed, batch_size, cont_min, None,
+                                     _LoaderStat(zeros, self.flux_pdf_segments, pdf, needs_dv=False))
 
     def _power_of_loader(self, what, dataloader, z_min, z_max, n_zbins, n_segments, seg_len, min_used_frac, tbar, tbar_nbins,
-                         n_samples, seed, batch_size, cont_min, dv, bands, lags=None, pdf=None):
-        """the loop `flux_power` (``bands``, ``lags`` and ``pdf`` None: a ``P1DStack`` through ``p1d``), `band_power` (``bands``: the
-        keywords of ``p1d_bands``; a ``P1DBandStack``), `flux_correlation` (``lags``: the keywords of ``xi``; a ``XiStack``) and
-        `flux_pdf` (``pdf``: the keywords of ``flux_pdf_segments``; a ``PDFStack``) share"""
+                         n_samples, seed, batch_size, cont_min, dv, stat):
+        """the loop `flux_power`, `band_power`, `flux_correlation` and `flux_pdf` share; ``stat``: the statistic's `_LoaderStat`"""
         nseg, nz, S = int(n_segments), int(n_zbins), max(1, int(n_samples))
         L = int(seg_len) if seg_len is not None else (self.Nb // nseg if nseg > 0 else 0)
         if nseg < 1 or L < 1 or nseg * L > self.Nb or nz < 1 or not float(z_max) > float(z_min) or not 0.0 < float(min_used_frac) <= 1.0:
             raise QFAHipError(f"{what}: {nseg} segments of {L} pixels on Nb = {self.Nb}, bins [{z_min}, {z_max}) / {nz}, "
                               f"min_used_frac = {min_used_frac}")
-        if dv is None and not (pdf is not None and tbar is not None):   # (the PDF needs dv for the range of its own <T> alone)
+        if dv is None and (stat.needs_dv or tbar is None):
             wav = getattr(dataloader, "wav_grid", None)
             if wav is None or len(wav) < 2:
                 raise QFAHipError(what + ": the dataloader has no wav_grid: pass dv (km/s per pixel)")
             dv = 299792.458 * float(np.log(float(wav[1]) / float(wav[0])))
-        if lags is not None and not 1 <= lags["n_lags"] <= L:
-            raise QFAHipError(f"{what}: n_lags = {lags['n_lags']} on segments of {L} pixels")
+        if stat.check is not None and stat.check(L) is not None:
+            raise QFAHipError(f"{what}: {stat.check(L)}")
         min_used = max(1, int(np.ceil(float(min_used_frac) * L)))
         if tbar is None:
             half = float(np.exp(0.5 * (L + 1) * float(dv) / 299792.458))          # (1 + z) over half a segment
@@ -455,16 +448,7 @@ class ForestStatistics(object):
         if not isinstance(tbar, ForestStack) or tbar.S not in (1, S):
             raise QFAHipError(f"{what}: tbar must be a ForestStack of 1 or {S} draws")
         tmean = tbar.mean.to(f32)
-        if pdf is not None:
-            stack = PDFStack.zeros(S, z_min, (float(z_max) - float(z_min)) / nz, nz, L, pdf["t_min"],
-                                   (pdf["t_max"] - pdf["t_min"]) / pdf["n_tbins"], pdf["n_tbins"], pdf["relative"], pdf["clamp"],
-                                   pdf["ivar_min"], self.device)
-        elif lags is not None:
-            stack = XiStack.zeros(S, z_min, (float(z_max) - float(z_min)) / nz, nz, L, lags["n_lags"], dv, self.device)
-        elif bands is None:
-            stack = P1DStack.zeros(S, z_min, (float(z_max) - float(z_min)) / nz, nz, L, dv, self.device)
-        else:
-            stack = P1DBandStack.zeros(S, z_min, (float(z_max) - float(z_min)) / nz, nz, L, dv, bands["k_edges"], self.device)
+        stack = stat.zeros(S, z_min, (float(z_max) - float(z_min)) / nz, nz, L, dv)
         row0 = int(getattr(dataloader, "_row0", 0))              # (a data-parallel loader: the global index of its first row)
         for s, inputs, _ in self._loader_slices(dataloader, int(batch_size)):
             _, hmean, hcov, _, unc = self.predict(**inputs)
@@ -481,14 +465,7 @@ class ForestStatistics(object):
                 tr, iv, _ = self.forest(**inputs, h=hs, unc=unc, cont_min=cont_min)
                 kw = dict(tbar=tmean if tbar.S == 1 else tmean[s0:s1], tbar_bins=tbar.bins, seg_len=L, n_segments=nseg,
                           min_used=min_used, stack=stack.draws(s0, s1), return_segments=False)
-                if pdf is not None:
-                    self.flux_pdf_segments(tr, iv, **zin, **kw, **pdf)
-                elif lags is not None:
-                    self.xi(tr, iv, **zin, **kw, **lags)
-                elif bands is None:
-                    self.p1d(tr, iv, **zin, **kw)
-                else:
-                    self.p1d_bands(tr, iv, **zin, **kw, **bands)
+                stat.call(tr, iv, **zin, **kw, **stat.keywords)
         if self._dp:
             stack.all_reduce(self._dp_group)
         return stack
