@@ -158,7 +158,7 @@ int qfa_nll_grad_f32(const qfa_params_t *p, const qfa_batch_t *b, const qfa_tau_
                      void *stream);
 
 /* Same call with stage timing for benchmarks: `events` is NULL or an array of 5 hipEvent_t
- * (entries may be NULL) recorded on `stream` at {start, after PF-image build, after pass 1
+ * (entries may be NULL) recorded on `stream` at {start, after the parameter-image build, after pass 1
  * (moments), after the k x k solve, after pass 2 (gradients)}. */
 int qfa_nll_grad_events_f32(const qfa_params_t *p, const qfa_batch_t *b, const qfa_tau_t *tau,
                             int B, int Npix, int Nb, int Nh,

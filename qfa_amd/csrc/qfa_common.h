@@ -7,9 +7,13 @@
 //   wD  = mask / D
 //   C   = I + sum_i wD A^2 f_i f_i^T,  T = sum_i wD A^3 f_i f_i^T   (k x k, symmetric)
 //   b   = sum_i wD A delta f_i,        b2 = sum_i wD A^2 delta f_i
-// The k(k+1)/2 distinct products f_a f_b of every pixel are tabulated once per step in the
-// "PF image" (row i = [f_i | P_i], P_i[pair(a,b)] = f_ia f_ib), so that C/T/b/b2 of 16 spectra
-// are plain GEMMs against it and map onto v_mfma_f32_16x16x4_f32.
+// The k(k+1)/2 distinct products f_a f_b of every pixel are tabulated once per step in a parameter image (per pixel
+// [f_i | P_i], P_i[pair(a,b)] = f_ia f_ib, then Psi, omega), so that C/T/b/b2 of 16 spectra are plain GEMMs against it:
+//   PFX  pass 1 (k_moments_x, qfa_xdl_kernels.h): 32-pixel tiles of split-bf16 / float16 pieces for the XDL pipe, every N_h;
+//   PFT  tile-major float32 image of 16-pixel tiles (Cfg below; k_prep_pft): the B operand of v_mfma_f32_16x16x4_f32 in the
+//        float32-MFMA forms k_grads and k_predict_out (N_h <= 16, the tests' cross-check forms), and the source of the F pieces
+//        of k_grads_s3 (N_h = 17..32).
+// (The default pass 2 and posterior writer build images of their own: qfa_grads_x.h, qfa_gt_layout.h, qfa_s12_x.h, qfa_predict_x.h.)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -27,25 +31,19 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 template <int KP>
 struct Cfg {
-    static constexpr int FW = KP < 16 ? 16 : KP;       // width of the F part of a PF row
+    static constexpr int FW = KP < 16 ? 16 : KP;       // width of the b / b2 parts of a moment record (and of PFX's F columns)
     static constexpr int KK2 = KP * (KP + 1) / 2;       // distinct pairs (a <= b)
     static constexpr int NT = (KK2 + 15) / 16;          // 16-column tiles of the pair part
     static constexpr int PW = NT * 16;                  // padded pair width
     static constexpr int NFT = FW / 16;                 // 16-column tiles of the F part
-    // PF image (pass 1): row i = [f_i (FW) | f_ia f_ib (PW) | Psi_i, omega_i, 0, 0].  The stride is
-    // 4 mod 8 floats so that the B-operand read of lane (j, col) at row 4j+e hits 32 distinct
-    // LDS banks per half-wave (4*NCPL = 16 mod 32).
-    static constexpr int PF_PSI = FW + PW;
-    static constexpr int NCPL = FW + PW + 4;
-    static constexpr int TILE_PF = 16 * NCPL;           // floats per 16-pixel tile (contiguous)
-    // PFT image (pass 2), tile-major: tile t = [row c][16 px]; rows [0,KP) = F^T, [KP,KP+KK2) =
+    // PFT image, tile-major: tile t = [row c][16 px]; rows [0,KP) = F^T, [KP,KP+KK2) =
     // pair products, then Psi, omega, the per-pixel factors ti, pwi, l2i of the factored-z input form (ZP of this
     // header; zeros otherwise), zero padding to a multiple of 4 rows.
     static constexpr int PFT_PSI = KP + KK2;
     static constexpr int NR = (KP + KK2 + 5 + 3) / 4 * 4;    // (+ ti, pwi, l2i of the factored-z form behind Psi, omega)
-    // N_h > 8: stage 3 of k_grads runs on the XDL pipe; its A operand (F of the tile as three bf16 pieces in the lane
-    // order of the MFMA: KP = 16 v_mfma_f32_16x16x16_bf16 [piece][g][px][a = 4g + j], 3 x 512 bytes; KP = 32
-    // v_mfma_f32_16x16x32_bf16 [piece][g][px][a = 8g + j], 3 x 1 KiB) is appended to the tile, and both parts are
+    // N_h > 8: stage 3 (k_grads at KP = 16, k_grads_s3 at KP = 32) runs on the XDL pipe; its A operand (F of the tile as three
+    // bf16 pieces in the lane order of the MFMA: KP = 16 v_mfma_f32_16x16x16_bf16 [piece][g][px][a = 4g + j], 3 x 512 bytes;
+    // KP = 32 v_mfma_f32_16x16x32_bf16 [piece][g][px][a = 8g + j], 3 x 1 KiB) is appended to the tile, and both parts are
     // padded to whole KiB so that the tile moves as 1-KiB LDS-DMA pieces
     static constexpr bool XS3 = KP == 16 || KP == 32;
     static constexpr int PFT_MAIN = XS3 ? (NR * 16 + 255) / 256 * 256 : NR * 16;   // floats of the float32 part

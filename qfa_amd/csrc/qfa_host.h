@@ -118,6 +118,34 @@ inline WorkPlan plan_work(int B, int ntiles, int pro, int slots, int spb = 64, i
     return best;
 }
 
+// deterministic mode: slab = [nblk rows of det_row_stride floats | scalar sums: (max items) x 4 waves x 3 doubles |
+//                             float64 partial sums of the reducer: det_chunks x NF]
+// A row holds the NF = Npix Nh + 3 Npix + Nb sums of one block of 64 spectra, padded to a multiple of 4 floats (16-byte
+// stores), plus 64 floats that lanes outside the arrays write to (every lane of a flushing wave stores: the counted
+// wait in k_grads_x needs a constant number of requests per wave).
+inline size_t det_rows_floats(int Npix, int Nb, int Nh) { return (size_t)Npix * Nh + 3 * (size_t)Npix + Nb; }
+inline size_t det_row_stride(int Npix, int Nb, int Nh) { return (det_rows_floats(Npix, Nb, Nh) + 3) / 4 * 4 + 64; }
+inline size_t det_rows(int B) { return (size_t)((B + 63) / 64); }
+constexpr int DET_CHUNK_ROWS = QFA_DET_CHUNK_ROWS;   // rows summed by one thread of the reducer's first stage
+inline size_t det_chunks(int B) { return (det_rows(B) + DET_CHUNK_ROWS - 1) / DET_CHUNK_ROWS; }
+struct DetLayout {
+    size_t NF, stride, oS, oPart, bytes;      // offsets in bytes
+};
+// The rows of the pixel-resident pass 2 (k_grads_t) where they live in the workspace (no caller's slab): one slab row per range of
+// spectra | scalar records, 8 waves x 3 doubles per item | float64 partial sums of the reducer.  make_layout_t sizes Layout::oISLAB
+// from it and run_nll_grad addresses the region by it.  (`bytes` is the size of the whole region, with the slack both places always
+// left behind the parts; the reducer's chunks are DET_CHUNK_ROWS rows, as launch_reduce_slab cuts them.)
+inline DetLayout pixres_rows_layout(int KP, int B, int Npix, int Nb, int Nh, int max_ranges) {
+    const size_t rows = (size_t)qfa_gt_ranges(KP, B, Npix, max_ranges), items8 = 8 * (size_t)qfa_gt_items(KP, B, Npix, max_ranges);
+    DetLayout D;
+    D.NF = det_rows_floats(Npix, Nb, Nh);
+    D.stride = det_row_stride(Npix, Nb, Nh);
+    D.oS = (rows * D.stride * sizeof(float) + 15) / 16 * 16;
+    D.oPart = D.oS + (items8 * 3 * sizeof(double) + 15) / 16 * 16;
+    D.bytes = (rows * D.stride + (items8 * 3 * 2 + 8) + 2 * ((rows + DET_CHUNK_ROWS - 1) / DET_CHUNK_ROWS) * D.NF + 16) * sizeof(float);
+    return D;
+}
+
 struct Layout {
     int KP, NpixPad, ntiles, Bpad;
     int ntiles32;                                      // pass 1 on the XDL pipe walks 32-pixel tiles (N_h <= 16)
@@ -125,7 +153,7 @@ struct Layout {
     static constexpr int spb1 = 64;                    // spectra per block of pass 1's plan (four waves of 16: k_moments_x)
     WorkPlan wp2x;                                     // pass 2 on the XDL pipe (k_grads_x: 32-pixel tiles, 1 workgroup per CU)
     WorkPlan wpp;                                      // posterior writer on the XDL pipe (k_predict_x, N_h <= 16)
-    size_t oPF, oPFT, oPFX, oPGX, oPXI, oMOM, oSOL, oNLL, oNBL, oRED, oBG, oZS, oZP, oPST, oISLAB, total;   // float offsets
+    size_t oPFT, oPFX, oPGX, oPXI, oMOM, oSOL, oNLL, oNBL, oRED, oBG, oZS, oZP, oPST, oISLAB, total;   // float offsets
     int bg_stride;                                     // beta / gamma hand-over of pass 2 at N_h = 17..32 ([2][Bpad][NpixPad])
 };
 
@@ -155,9 +183,7 @@ Layout make_layout_t(int B, int Npix) {
     L.wp1 = KP <= 16 ? plan_work(B, L.ntiles32, 1, 2 * NCU) : plan_work(B, L.ntiles32, 1, NCU, 64, QFA_P1_MAX_CHAIN);
     size_t o = 0;
     auto take = [&](size_t n) { size_t r = o; o += (n + 63) / 64 * 64; return r; };
-    L.oPF = take((size_t)L.ntiles * C::TILE_PF);
     L.oPFT = take((size_t)L.ntiles * C::TILE_PFT);
-    L.oPFX = 0;
     L.oPFX = take((size_t)L.ntiles32 * (XCfg<KP>::TILE_B / 4) + 2 * (C::FW + C::PW));      // + the column maxima (pfx_colmax)
     L.oPGX = 0;
     L.wp2x = WorkPlan{0, 0, 1, 0};
@@ -187,13 +213,9 @@ Layout make_layout_t(int B, int Npix) {
     if constexpr (KP == 8 || KP == 16) L.oPST = take(qfa_gt_state_bytes(KP, B) / 4);
     // pixel-resident pass 2 without a caller's slab: its per-range sums go through rows of the workspace and the fixed-order
     // reducer as well (no atomics: the default accumulation of a large batch is bit-reproducible too).  Sized for N_b = N_pix,
-    // N_h = KP: rows | scalar records | float64 partial sums of the reducer
+    // N_h = KP
     L.oISLAB = 0;
-    if constexpr (KP == 8 || KP == 16) {
-        const size_t rows = (size_t)qfa_gt_ranges(KP, B, Npix, 1 << 30), items8 = 8 * (size_t)qfa_gt_items(KP, B, Npix, 1 << 30);
-        const size_t nf = (size_t)Npix * KP + 4 * (size_t)Npix, stride = (nf + 3) / 4 * 4 + 64;
-        L.oISLAB = take(rows * stride + (items8 * 3 * 2 + 8) + 2 * ((rows + 31) / 32) * nf + 16);
-    }
+    if constexpr (KP == 8 || KP == 16) L.oISLAB = take(pixres_rows_layout(KP, B, Npix, Npix, KP, 1 << 30).bytes / sizeof(float));
     L.oBG = 0;
     L.bg_stride = round_up(Npix, 32);
     if constexpr (KP == 32) L.oBG = take(2 * (size_t)round_up(B, 64) * L.bg_stride);
@@ -241,8 +263,8 @@ inline int check_shape(int B, int Npix, int Nb, int Nh) {
     return 0;
 }
 
-// Which form of pass 2 runs at N_h <= 16 (KP = 8 or 16).  Three forms: k_grads (float32-MFMA stage 1; the only one for
-// N_h = 17..32), the two-role all-XDL k_grads_x, the pixel-resident all-XDL k_grads_t.  Defaults from measurements on MI355X
+// Which form of pass 2 runs at N_h <= 16 (KP = 8 or 16).  Three forms: k_grads (float32-MFMA stage 1), the two-role all-XDL k_grads_x,
+// the pixel-resident all-XDL k_grads_t.  Defaults from measurements on MI355X
 // (tools/time_pass2.py: pass 1 + solve + pass 2 per call, ms; profiles/r3_ablation_pass2.txt):
 //   k_grads never: k_grads_x is as fast or faster at every batch size measured, N_h = 8: 0.072 / 0.083 at 500 spectra x 2000 px,
 //     0.104 / 0.117 at 2 000, 0.192 / 0.220 at 8 000, 2.82 / 3.25 at 40 000 x 9243 (the one exception, 10 000 x 2000 --
@@ -287,12 +309,28 @@ inline int hip_status(hipStream_t st = nullptr, unsigned flags = 0) {
     return e == hipSuccess ? 0 : (int)e;
 }
 
+// the tile-major float32 image PFT: k_grads and k_predict_out (N_h <= 16), k_grads_s3 (N_h = 17..32)
 template <int KP>
-void launch_prep(const qfa_params_t &p, const float4 *ZP, int Npix, int Nb, int Nh, const Layout &L, float *PF, float *PFT,
-                 hipStream_t st) {
+void launch_prep_pft(const qfa_params_t &p, const float4 *ZP, int Npix, int Nb, int Nh, const Layout &L, float *PFT, hipStream_t st) {
     dim3 blk(64, 4);
-    k_prep_pf<KP><<<(L.NpixPad + 3) / 4, blk, 0, st>>>(p.F, p.Psi, p.omega, ZP, Npix, Nb, Nh, L.NpixPad, PF, PFT);
+    k_prep_pft<KP><<<(L.NpixPad + 3) / 4, blk, 0, st>>>(p.F, p.Psi, p.omega, ZP, Npix, Nb, Nh, L.NpixPad, PFT);
 }
+
+// k_solve: KP lanes per spectrum, four waves per block
+template <int KP>
+inline unsigned solve_blocks(int B) {
+    constexpr int G = 64 / KP;
+    return (unsigned)((B + 4 * G - 1) / (4 * G));
+}
+
+// the caller's stage events (bench.py's stamps; entries may be NULL), recorded on the call's stream
+struct EventMarks {
+    void *const *events;
+    hipStream_t st;
+    void operator()(int i) const {
+        if (events && events[i]) (void)hipEventRecord((hipEvent_t)events[i], st);
+    }
+};
 
 // MOM[seg 0] += MOM[seg 1..] for the rows of the segmented blocks of pass 1
 template <int KP>
@@ -352,19 +390,6 @@ void launch_moments(const qfa_params_t &p, const qfa_batch_t &b, const qfa_tau_t
         k_moments_x<KP, PREDICT, NW, false><<<L.wp1.items(), 64 * NW, 0, st>>>(p, b, tau, mu, B, L.Bpad, Npix, Nb, L.ntiles32, L.wp1, PFX, nullptr, MOM);
 }
 
-// deterministic mode: slab = [nblk rows of det_row_stride floats | scalar sums: (max items) x 4 waves x 3 doubles |
-//                             float64 partial sums of the reducer: det_chunks x NF]
-// A row holds the NF = Npix Nh + 3 Npix + Nb sums of one block of 64 spectra, padded to a multiple of 4 floats (16-byte
-// stores), plus 64 floats that lanes outside the arrays write to (every lane of a flushing wave stores: the counted
-// wait in k_grads_x needs a constant number of requests per wave).
-inline size_t det_rows_floats(int Npix, int Nb, int Nh) { return (size_t)Npix * Nh + 3 * (size_t)Npix + Nb; }
-inline size_t det_row_stride(int Npix, int Nb, int Nh) { return (det_rows_floats(Npix, Nb, Nh) + 3) / 4 * 4 + 64; }
-inline size_t det_rows(int B) { return (size_t)((B + 63) / 64); }
-constexpr int DET_CHUNK_ROWS = QFA_DET_CHUNK_ROWS;   // rows summed by one thread of the reducer's first stage
-inline size_t det_chunks(int B) { return (det_rows(B) + DET_CHUNK_ROWS - 1) / DET_CHUNK_ROWS; }
-struct DetLayout {
-    size_t NF, stride, oS, oPart, bytes;      // offsets in bytes
-};
 inline DetLayout det_layout(int B, int Npix, int Nb, int Nh) {
     const Layout L = make_layout(B, Npix, Nh);
     size_t items = (size_t)(L.wp2.items() > L.wp2x.items() ? L.wp2.items() : L.wp2x.items());
@@ -400,15 +425,13 @@ int run_nll_grad(const qfa_params_t &p, const qfa_batch_t &b, const qfa_tau_t &t
     DetLayout D{};
     if (slab) D = det_layout(B, Npix, Nb, Nh);
     double *slabS = slab ? reinterpret_cast<double *>(reinterpret_cast<char *>(slab) + D.oS) : nullptr;
-    float *PF = ws + L.oPF, *PFT = ws + L.oPFT, *MOM = ws + L.oMOM, *SOL = ws + L.oSOL, *NBL = ws + L.oNBL;
+    float *PFT = ws + L.oPFT, *MOM = ws + L.oMOM, *SOL = ws + L.oSOL, *NBL = ws + L.oNBL;
     float *nllbuf = nll ? nll : ws + L.oNLL;
     const size_t accS = (size_t)Npix * Nh + 3 * (size_t)Npix + Nb;
     // QFA_F_EXACT_GRAD: k_solve forms Z = -C^-1, p = y; pass 2 sums the exact tau0 / c0 / beta terms; the buffer's slot 6
     // counts the spectra of such launches (k_reduce_nll, or the solve's last block), and k_finalize* read the mode there
     const int exact = (flags & QFA_F_EXACT_GRAD) ? 1 : 0;
-    auto mark = [&](int i) {
-        if (events && events[i]) (void)hipEventRecord((hipEvent_t)events[i], st);
-    };
+    const EventMarks mark{events, st};
     bool pass2_xdl = false;
     if constexpr (KP == 8 || KP == 16) pass2_xdl = pass2_use_xdl(KP, flags);
     if constexpr (KP <= 16) { if (flags & QFA_F_S3_FAST) return QFA_E_FLAGS; }    // (the three-product form exists at N_h = 17..32 only)
@@ -432,14 +455,12 @@ int run_nll_grad(const qfa_params_t &p, const qfa_batch_t &b, const qfa_tau_t &t
     if (!fused) {
         if (flags & QFA_F_ZERO_ACCUM) (void)hipMemsetAsync(accum, 0, n_acc * sizeof(float), st);
         zt = launch_zfac(p, b, tau, B, Nb, L, ws, st);
-        // the float32 images PF / PFT serve k_grads (and the N_h = 17..32 kernels)
-        launch_prep<KP>(p, zt.ZP, Npix, Nb, Nh, L, PF, PFT, st);
+        launch_prep_pft<KP>(p, zt.ZP, Npix, Nb, Nh, L, PFT, st);
     }
     mark(1);
     launch_moments<KP, false>(p, b, tau, nullptr, B, Npix, Nb, Nh, L, zt, ws, st, !fused, exact != 0);
     mark(2);
     sum_segments<KP>(MOM, L, B, st);
-    constexpr int G = 64 / KP;
     double *red = reinterpret_cast<double *>(ws + L.oRED);
     unsigned *ticket = reinterpret_cast<unsigned *>(red + 2 * NRED);
     Scal64 *sc64 = reinterpret_cast<Scal64 *>(ticket + 2);      // (zeroed by k_solve, like the ticket)
@@ -447,7 +468,7 @@ int run_nll_grad(const qfa_params_t &p, const qfa_batch_t &b, const qfa_tau_t &t
     bool solved = false;
     if constexpr (KP == 8 || KP == 16) {
         if (pixres) {
-            k_solve<KP, false, true><<<(B + 4 * G - 1) / (4 * G), 256, 0, st>>>(MOM, SOL, nllbuf, NBL, B, Nh, nullptr, nullptr, ticket,
+            k_solve<KP, false, true><<<solve_blocks<KP>(B), 256, 0, st>>>(MOM, SOL, nllbuf, NBL, B, Nh, nullptr, nullptr, ticket,
                                                                                reinterpret_cast<unsigned char *>(ws + L.oPST), nullptr, exact);
             solved = true;
         }
@@ -456,12 +477,12 @@ int run_nll_grad(const qfa_params_t &p, const qfa_batch_t &b, const qfa_tau_t &t
     bool nll_done = false;
     if constexpr (KP == 8 || KP == 16) {
         if (!solved && fused && B <= 2048) {
-            k_solve<KP, false, false, true><<<(B + 4 * G - 1) / (4 * G), 256, 0, st>>>(MOM, SOL, nllbuf, NBL, B, Nh, nullptr, nullptr, ticket,
+            k_solve<KP, false, false, true><<<solve_blocks<KP>(B), 256, 0, st>>>(MOM, SOL, nllbuf, NBL, B, Nh, nullptr, nullptr, ticket,
                                                                                       nullptr, accum + accS, exact);
             solved = nll_done = true;
         }
     }
-    if (!solved) k_solve<KP, false><<<(B + 4 * G - 1) / (4 * G), 256, 0, st>>>(MOM, SOL, nllbuf, NBL, B, Nh, nullptr, nullptr, ticket,
+    if (!solved) k_solve<KP, false><<<solve_blocks<KP>(B), 256, 0, st>>>(MOM, SOL, nllbuf, NBL, B, Nh, nullptr, nullptr, ticket,
                                                                                 nullptr, nullptr, exact);
     const int nred = B <= 2048 ? 1 : (B >= 2048 * NRED ? NRED : (B + 2047) / 2048);     // small batches: one block, no hand-over
     if (!nll_done) k_reduce_nll<<<nred, 256, 0, st>>>(nllbuf, NBL, B, accum + accS, red, ticket, exact);
@@ -473,13 +494,8 @@ int run_nll_grad(const qfa_params_t &p, const qfa_batch_t &b, const qfa_tau_t &t
         DetLayout Dr = D;
         const int maxr = slab ? (int)det_rows(B) : (1 << 30);
         if (!slab) {
-            const size_t rows = (size_t)qfa_gt_ranges(KP, B, Npix, maxr), items8 = 8 * (size_t)qfa_gt_items(KP, B, Npix, maxr);
             rowsb = ws + L.oISLAB;
-            Dr.NF = det_rows_floats(Npix, Nb, Nh);
-            Dr.stride = det_row_stride(Npix, Nb, Nh);
-            Dr.oS = (rows * Dr.stride * sizeof(float) + 15) / 16 * 16;
-            Dr.oPart = Dr.oS + (items8 * 3 * sizeof(double) + 15) / 16 * 16;
-            Dr.bytes = 0;
+            Dr = pixres_rows_layout(KP, B, Npix, Nb, Nh, maxr);
         }
         double *rowsS = reinterpret_cast<double *>(reinterpret_cast<char *>(rowsb) + Dr.oS);
         qfa_gt_launch(KP, p, b, tau, B, Npix, Nb, Nh, maxr, reinterpret_cast<unsigned char *>(ws + L.oPGX),
@@ -522,14 +538,14 @@ int run_nll_grad(const qfa_params_t &p, const qfa_batch_t &b, const qfa_tau_t &t
         }
         if (slab) launch_reduce_slab(slab, D, B, L.wp2x.items() * 4, accum, st);
     } else {
-        auto grads = [&](auto ex) {   // the float32-MFMA form (QFA_F_PASS2_F32): custom tau table / factored z / zabs
+        auto grads = [&](auto ex) {   // the float32-MFMA form (QFA_F_PASS2_F32, N_h <= 16): custom tau table / factored z / zabs
             constexpr bool E = decltype(ex)::value;
             if (b.A_blue)
-                k_grads<KP, true, false, E><<<L.wp2.items(), 256, 0, st>>>(p, b, tau, B, Npix, Nb, Nh, L.ntiles, L.wp2, 0, PFT, SOL, accum, slab, slabS, (int)D.stride, sc64, nullptr, nullptr, nullptr, L.bg_stride);
+                k_grads<KP, true, false, E><<<L.wp2.items(), 256, 0, st>>>(p, b, tau, B, Npix, Nb, Nh, L.ntiles, L.wp2, PFT, SOL, accum, slab, slabS, (int)D.stride, sc64, nullptr);
             else if (zt.ZS)
-                k_grads<KP, false, true, E><<<L.wp2.items(), 256, 0, st>>>(p, b, tau, B, Npix, Nb, Nh, L.ntiles, L.wp2, 0, PFT, SOL, accum, slab, slabS, (int)D.stride, sc64, zt.ZS, nullptr, nullptr, L.bg_stride);
+                k_grads<KP, false, true, E><<<L.wp2.items(), 256, 0, st>>>(p, b, tau, B, Npix, Nb, Nh, L.ntiles, L.wp2, PFT, SOL, accum, slab, slabS, (int)D.stride, sc64, zt.ZS);
             else
-                k_grads<KP, false, false, E><<<L.wp2.items(), 256, 0, st>>>(p, b, tau, B, Npix, Nb, Nh, L.ntiles, L.wp2, 0, PFT, SOL, accum, slab, slabS, (int)D.stride, sc64, nullptr, nullptr, nullptr, L.bg_stride);
+                k_grads<KP, false, false, E><<<L.wp2.items(), 256, 0, st>>>(p, b, tau, B, Npix, Nb, Nh, L.ntiles, L.wp2, PFT, SOL, accum, slab, slabS, (int)D.stride, sc64, nullptr);
         };
         if (exact) grads(std::true_type{});
         else grads(std::false_type{});
@@ -544,20 +560,16 @@ int run_predict(const qfa_params_t &p, const float *mu, const qfa_batch_t &b, co
                 int Nb, int Nh, float *ll, float *hmean, float *hcov, float *cont, float *unc, float *ws,
                 hipStream_t st, void *const *events, unsigned flags) {
     const Layout L = make_layout_t<KP>(B, Npix);
-    float *PF = ws + L.oPF, *PFT = ws + L.oPFT, *MOM = ws + L.oMOM, *SOL = ws + L.oSOL;
-    auto mark = [&](int i) {
-        if (events && events[i]) (void)hipEventRecord((hipEvent_t)events[i], st);
-    };
+    float *PFT = ws + L.oPFT, *MOM = ws + L.oMOM, *SOL = ws + L.oSOL;
+    const EventMarks mark{events, st};
     const bool writer_xdl = !(flags & QFA_F_PREDICT_F32);        // (the float32-MFMA writer: A/B timing, cross-check)
     mark(0);
     const ZTables zt = launch_zfac(p, b, tau, B, Nb, L, ws, st);
-    // (PF / PFT: k_predict_out)
-    if (!writer_xdl) launch_prep<KP>(p, nullptr, Npix, Nb, Nh, L, PF, PFT, st);
+    if (!writer_xdl) launch_prep_pft<KP>(p, nullptr, Npix, Nb, Nh, L, PFT, st);      // (k_predict_out)
     launch_moments<KP, true>(p, b, tau, mu, B, Npix, Nb, Nh, L, zt, ws, st);
     mark(1);
     sum_segments<KP>(MOM, L, B, st);
-    constexpr int G = 64 / KP;
-    k_solve<KP, true><<<(B + 4 * G - 1) / (4 * G), 256, 0, st>>>(MOM, SOL, ll, nullptr, B, Nh, hmean, hcov);
+    k_solve<KP, true><<<solve_blocks<KP>(B), 256, 0, st>>>(MOM, SOL, ll, nullptr, B, Nh, hmean, hcov);
     mark(2);
     if constexpr (KP > 16) {
         if (writer_xdl) {              // the image of k_s12_x with mu in the place of Psi (qfa_s12_x.h)
@@ -587,9 +599,8 @@ int run_estep(const qfa_params_t &p, const qfa_batch_t &b, const qfa_tau_t &tau,
     const ZTables zt = launch_zfac(p, b, tau, B, Nb, L, ws, st);
     launch_moments<KP, false>(p, b, tau, nullptr, B, Npix, Nb, Nh, L, zt, ws, st, true, true);
     sum_segments<KP>(MOM, L, B, st);
-    constexpr int G = 64 / KP;
     unsigned *ticket = reinterpret_cast<unsigned *>(reinterpret_cast<double *>(ws + L.oRED) + 2 * NRED);
-    k_solve<KP, false><<<(B + 4 * G - 1) / (4 * G), 256, 0, st>>>(MOM, SOL, nllbuf, NBL, B, Nh, nullptr, nullptr, ticket, nullptr,
+    k_solve<KP, false><<<solve_blocks<KP>(B), 256, 0, st>>>(MOM, SOL, nllbuf, NBL, B, Nh, nullptr, nullptr, ticket, nullptr,
                                                                  nullptr, 1);
     out->SOL = SOL;
     out->nsol = Cfg<KP>::NSOL;

@@ -758,7 +758,7 @@ __global__ __launch_bounds__(256, 2) void k_grads_s3(int B, int Npix, int Nh, in
     static_assert(KP == 32, "k_grads_s3: N_h = 17..32");
     using C = Cfg<KP>;
     // Round 5 (TERMS == 6 only): G_s = F_tile Z_s on TWO float16 pieces per operand, three products.  Both operands are
-    // prepared: F t_px (k_prep_pf; 1 / t_px rides as a fifth KiB) and Z_s 2^k of the wave's own spectra (scaled by their largest
+    // prepared: F t_px (k_prep_pft; 1 / t_px rides as a fifth KiB) and Z_s 2^k of the wave's own spectra (scaled by their largest
     // element below); beta multiplies G in float32 behind the MFMA as before, so nothing here depends on the range of the data.
     constexpr bool F16 = TERMS == 6;
     constexpr int RING = 3, BUF_B = TERMS == 6 ? 5120 : 4096;   // per wave and tile: beta 1 KiB | gamma 1 KiB | Fh 1 KiB | Fm 1 KiB (| F16: 1 / t)

@@ -1,13 +1,14 @@
 // qfa_step_kernels.h -- the hot kernels of one QFA training / prediction step on CDNA4 (gfx950).
 //
-//   k_prep_pf      F, Psi, omega -> PF image (pass 1 B operand, f32 form) and tile-major PFT image (pass 2)
-//   k_moments      pass 1, f32 form (N_h > 16): C, T, b, b2 + scalar sums of 16 spectra per wave on
-//                  v_mfma_f32_16x16x4_f32 (N_h <= 16 runs k_moments_x of qfa_xdl_kernels.h on the bf16 XDL pipe)
+//   k_prep_pft     F, Psi, omega -> tile-major float32 image PFT (k_grads, k_predict_out; k_grads_s3 of qfa_s12_x.h)
 //   k_solve        k x k Gauss-Jordan in fp64 on KP lanes per spectrum (DPP / readlane broadcasts)
 //   k_reduce_nll   sum NLL / spectrum counts (fp64, fixed order)
-//   k_grads        pass 2: u, diag(Sigma^-1), Psi/omega/scalar sums (stage 1 on the f32 MFMA), F-gradient
-//                  contraction (stage 3: XDL pipe with split-bf16 static operands at N_h = 16, f32 MFMA otherwise)
-//   k_predict_out  cont = F hmean + mu, unc = sqrt(f^T hcov f)
+//   k_grads        pass 2 in its float32-MFMA form, N_h <= 16 (QFA_F_PASS2_F32: the cross-check form of the tests): u,
+//                  diag(Sigma^-1), Psi/omega/scalar sums (stage 1 on the f32 MFMA), F-gradient contraction (stage 3: XDL pipe
+//                  with split-bf16 static operands at N_h = 9..16, f32 MFMA at N_h <= 8)
+//   k_predict_out  cont = F hmean + mu, unc = sqrt(f^T hcov f) (QFA_F_PREDICT_F32)
+// (Pass 1 is k_moments_x of qfa_xdl_kernels.h at every N_h; the default pass 2 is k_grads_x / k_grads_t at N_h <= 16 and
+// k_s12_x + k_grads_s3 at N_h = 17..32.)
 //
 // Both passes share one structure: a 256-thread workgroup = 4 waves = 4 x 16 spectra walks a segment of the
 // pixel axis in tiles (16 pixels; 32 in k_moments_x); the tile of the parameter image every wave needs is staged
@@ -23,43 +24,30 @@
 
 // ------------------------------------------------------------------------------------------------
 template <int KP>
-__global__ void k_prep_pf(const float *__restrict__ F, const float *__restrict__ Psi,
-                          const float *__restrict__ omega, const float4 *__restrict__ ZP, int Npix, int Nb, int Nh,
-                          int NpixPad, float *__restrict__ PF, float *__restrict__ PFT) {
+__global__ void k_prep_pft(const float *__restrict__ F, const float *__restrict__ Psi,
+                           const float *__restrict__ omega, const float4 *__restrict__ ZP, int Npix, int Nb, int Nh,
+                           int NpixPad, float *__restrict__ PFT) {
     using C = Cfg<KP>;
-    const int i = blockIdx.x * blockDim.y + threadIdx.y;   // pixel row
+    const int i = blockIdx.x * blockDim.y + threadIdx.y;   // pixel
     if (i >= NpixPad) return;
     const bool live = i < Npix;
     float *pft = PFT + (size_t)(i >> 4) * C::TILE_PFT + (i & 15);
-    for (int c = threadIdx.x; c < C::NCPL; c += blockDim.x) {
+    // rows of the tile (Cfg): F^T, pair products, Psi, omega, the per-pixel factors of the factored-z form, zero padding
+    for (int r = threadIdx.x; r < C::NR; r += blockDim.x) {
         float v = 0.f;
-        int rt = -1;                       // row in the PFT tile
-        if (c < C::FW) {
-            if (live && c < Nh) v = F[(size_t)i * Nh + c];
-            if (c < KP) rt = c;
-        } else if (c < C::PF_PSI) {
-            const int pidx = c - C::FW;
-            if (pidx < C::KK2) {
-                int a = 0;
-                while (a + 1 < KP && pair_index(a + 1, a + 1, KP) <= pidx) ++a;
-                const int b = a + (pidx - pair_index(a, a, KP));
-                if (live && b < Nh) v = F[(size_t)i * Nh + a] * F[(size_t)i * Nh + b];
-                rt = KP + pidx;
-            }
-        } else if (c == C::PF_PSI) {
+        if (r < KP) {
+            if (live && r < Nh) v = F[(size_t)i * Nh + r];
+        } else if (r < C::PFT_PSI) {
+            const int pidx = r - KP;
+            int a = 0;
+            while (a + 1 < KP && pair_index(a + 1, a + 1, KP) <= pidx) ++a;
+            const int b = a + (pidx - pair_index(a, a, KP));
+            if (live && b < Nh) v = F[(size_t)i * Nh + a] * F[(size_t)i * Nh + b];
+        } else if (r == C::PFT_PSI) {
             if (live) v = Psi[i];
-            rt = C::PFT_PSI;
-        } else if (c == C::PF_PSI + 1) {
+        } else if (r == C::PFT_PSI + 1) {
             if (i < Nb) v = omega[i];
-            rt = C::PFT_PSI + 1;
-        }
-        PF[(size_t)i * C::NCPL + c] = v;
-        if (rt >= 0) pft[rt * 16] = v;
-    }
-    // the per-pixel factors of the factored-z form, then zero padding rows of the PFT tile
-    for (int r = C::PFT_PSI + 2 + threadIdx.x; r < C::NR; r += blockDim.x) {
-        float v = 0.f;
-        if (ZP && i < Nb && r < C::PFT_PSI + 5) {
+        } else if (ZP && i < Nb && r < C::PFT_PSI + 5) {
             const float4 q = ZP[i];
             v = r == C::PFT_PSI + 2 ? q.x : (r == C::PFT_PSI + 3 ? q.y : q.z);
         }
@@ -118,36 +106,6 @@ __global__ void k_prep_pf(const float *__restrict__ F, const float *__restrict__
         }
     }
 }
-
-// copy one contiguous tile (NF4 float4) global -> registers -> LDS with all 256 threads.  The first
-// three staging registers are named locals of the kernel (an array or a struct captured by the nested
-// lambdas ended up in scratch for N = 3); tiles of N_h > 16 continue in a local array.
-template <int NF4>
-struct TileCopy {
-    static constexpr int N = (NF4 + 255) / 256;
-    static constexpr int NX = N > 3 ? N - 3 : 1;
-    static __device__ __forceinline__ bool in(int i, int idx) { return 256 * i + 255 < NF4 || idx < NF4; }
-    static __device__ __forceinline__ float4 ld(const float4 *__restrict__ src, int i, int tid) {
-        return src[in(i, tid + 256 * i) ? tid + 256 * i : NF4 - 1];
-    }
-    static __device__ __forceinline__ void load(const float4 *__restrict__ src, int tid, float4 &v0, float4 &v1,
-                                                float4 &v2, float4 (&vx)[NX]) {
-        v0 = ld(src, 0, tid);
-        if (N > 1) v1 = ld(src, 1, tid);
-        if (N > 2) v2 = ld(src, 2, tid);
-#pragma unroll
-        for (int i = 3; i < N; ++i) vx[i - 3] = ld(src, i, tid);
-    }
-    static __device__ __forceinline__ void store(float4 *dst, int tid, const float4 &v0, const float4 &v1,
-                                                 const float4 &v2, const float4 (&vx)[NX]) {
-        if (in(0, tid)) dst[tid] = v0;
-        if (N > 1 && in(1, tid + 256)) dst[tid + 256] = v1;
-        if (N > 2 && in(2, tid + 512)) dst[tid + 512] = v2;
-#pragma unroll
-        for (int i = 3; i < N; ++i)
-            if (in(i, tid + 256 * i)) dst[tid + 256 * i] = vx[i - 3];
-    }
-};
 
 // (Round 1's float32-MFMA pass 1, k_moments, left the library in round 4: k_moments_x (qfa_xdl_kernels.h) runs pass 1 on
 // the XDL pipe at every N_h -- 1.25 against 2.24 ms at c3, 1.9 against 3.2 ms at c5.)
@@ -456,7 +414,8 @@ static __global__ __launch_bounds__(256) void k_reduce_nll(const float *__restri
 }
 
 // ------------------------------------------------------------------------------------------------
-// k_grads (pass 2).  Lane (lo = lane&15, g = lane>>4) owns pixel 16*tile + lo of spectra
+// k_grads (pass 2, float32-MFMA form: N_h <= 16 under QFA_F_PASS2_F32; N_h = 17..32 runs k_s12_x + k_grads_s3).
+// Lane (lo = lane&15, g = lane>>4) owns pixel 16*tile + lo of spectra
 // s0 + 4g + r (r = 0..3):
 //   stage 1  [f^T y | f^T C^-1 f] (16 spectra x 16 px) = [y | Cinv'] (registers, A operand) x PFT tile
 //            (LDS, B operand) -> C/D layout col = px, row = 4g + r: the lane's own four elements
@@ -484,40 +443,30 @@ struct PixPar {                  // per-pixel parameters of the lane's pixel: Ps
 template <int KP, bool HASA, bool ZF, bool EXACT>   // EXACT: QFA_F_EXACT_GRAD's tau0 / c0 / beta terms (as in k_grads_t)
 __global__ __launch_bounds__(256, KP == 8 ? QFA_G8_OCC : 2) void k_grads(qfa_params_t p, qfa_batch_t bt, qfa_tau_t tau, int B,
                                                               int Npix, int Nb, int Nh, int ntiles, WorkPlan wp,
-                                                              int bhalf, const float *__restrict__ PFT,
+                                                              const float *__restrict__ PFT,
                                                               const float *__restrict__ SOL,
                                                               float *__restrict__ accum, float *__restrict__ slab,
                                                               double *__restrict__ slabS, int slab_stride,
-                                                              Scal64 *__restrict__ sc64, const float4 *__restrict__ ZS,
-                                                              float *__restrict__ BG = nullptr,
-                                                              float *__restrict__ GG = nullptr, int bg_stride = 0) {
-    // BG != NULL (KP = 32): beta = wD A^2 and gamma = A u of every (spectrum, pixel) are also stored, [Bpad][bg_stride]
-    // each, for k_grads_s3, which produces the second 16 columns of the F gradient from them: stages 1 and 2 run once.
+                                                              Scal64 *__restrict__ sc64, const float4 *__restrict__ ZS) {
     // slab != NULL: deterministic mode -- the block's tile partials go to row blk of the slab (plain stores), its
     // scalar sums to slabS[item][wave][3]; k_reduce_slab adds the rows to accum in block order.
-    // bhalf: which 16 columns of the F gradient this launch produces (N_h > 16 runs the kernel once per
-    // half; the per-pixel and scalar sums are added by the bhalf == 0 launch only)
-    // N_h <= 16 only (QFA_F_PASS2_F32).  The KP = 32 arms below, bhalf and BG / GG / bg_stride (NULL and 0 from every caller) are what
-    // is left of the form that served N_h = 17..32; taking them out reorders instructions of the KP = 16 instantiations, so they wait
-    // for a change that is allowed to touch the kernel's code.
-    static_assert(KP <= 16, "k_grads: N_h <= 16 (N_h = 17..32 runs k_s12_x + k_grads_s3)");
+    static_assert(KP == 8 || KP == 16, "k_grads: N_h <= 16 (N_h = 17..32 runs k_s12_x + k_grads_s3)");
     using C = Cfg<KP>;
     constexpr int KF = KP / 4, KQ = C::KK2 / 4;
     constexpr int NF4 = C::TILE_PFT / 4;
     constexpr int NPART = 512;      // per wave and tile: aG [px][16] (256) + 4 per-pixel sums x 64 lanes
-    constexpr bool XS3 = C::XS3;
-    // ring of 3 parameter tiles; with stage 3 on the XDL pipe only the F pieces of a tile are read in its own step
-    // (the float32 part is consumed one step earlier by stage 1), so the float32 part needs two slots only
-    // KP = 32: stage 3 on the XDL pipe as well, but the float32 part of the tile keeps travelling through the staging
-    // registers into a ring of 3 (XDMA = false) and every lane reads its two 16-byte F pieces of the tile straight
-    // from the image in global memory (L2) at the start of the step.  (Through LDS -- by LDS-DMA into a ring, or
-    // staged with the rest of the tile -- they arrived wrong at this size; not understood, the parity tests caught it.)
-    constexpr bool XDMA = XS3 && KP == 16;
-    constexpr int NM4 = C::PFT_MAIN / 4, NP4 = XDMA ? C::PFT_FP / 4 : 1, RING_M = XDMA ? 2 : 3;
+    // KP = 16: stage 3 on the XDL pipe (the F pieces behind the tile's float32 part), the tile by LDS-DMA; KP = 8: stage 3 on the
+    // float32 MFMA, the tile through one staging register per thread
+    constexpr bool XS3 = KP == 16;
+    // ring of 3 parameter tiles; with stage 3 on the XDL pipe only the F pieces of a tile are read in its own step (the float32
+    // part is consumed one step earlier, by stage 1 in region 1 of that step, and the tile's last step re-reads its own slot), so
+    // the float32 part needs two slots only.  The one read that does not fit that pattern, stage 1 of a range's first tile in the
+    // prologue, ends at a barrier of its own before step 0 may overwrite the slot
+    constexpr int NM4 = C::PFT_MAIN / 4, NP4 = XS3 ? C::PFT_FP / 4 : 1, RING_M = XS3 ? 2 : 3;
     constexpr int NCH_MAIN = C::PFT_MAIN / 256, NCH = C::TILE_PFT / 256;   // 1-KiB LDS-DMA pieces (XDL form)
     __shared__ float4 lds4[RING_M][XS3 ? NM4 : NF4];
-    __shared__ float4 ldsfp[XDMA ? 3 : 1][NP4];                  // F as bf16 pieces (stage-3 A operand, KP = 16)
-    __shared__ unsigned ldszl[XDMA ? 4 : 1][XDMA ? 16 * 64 * 2 : 1];   // third bf16 piece of Z (KP = 16), per wave [spectrum][lane][2]
+    __shared__ float4 ldsfp[XS3 ? 3 : 1][NP4];                  // F as bf16 pieces (stage-3 A operand, KP = 16)
+    __shared__ unsigned ldszl[XS3 ? 4 : 1][XS3 ? 16 * 64 * 2 : 1];   // third bf16 piece of Z (KP = 16), per wave [spectrum][lane][2]
     __shared__ float ldspart[2][4][NPART];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -551,17 +500,12 @@ __global__ __launch_bounds__(256, KP == 8 ? QFA_G8_OCC : 2) void k_grads(qfa_par
         for (int t = 0; t < KQ; ++t) qA[t] = v ? sol[C::SOL_CI + 4 * t + g] : 0.f;
     }
     // B operands of stage 3, column b = lo.
-    //   f32 MFMA form (N_h > 16): Z of the lane's own spectra s0+4g+r, K = (spectrum, a).
-    //   XDL form: G_s = F_tile Z_s per spectrum (both operands static), K = a: the lane holds Z_s[a = 4g+j][b] of
+    //   f32 MFMA form (KP = 8): Z of the lane's own spectra s0+4g+r, K = (spectrum, a).
+    //   XDL form (KP = 16): G_s = F_tile Z_s per spectrum (both operands static), K = a: the lane holds Z_s[a = 4g+j][b] of
     //   ALL 16 spectra as bf16 pieces h, m (registers) and l (LDS); beta is applied to G_s on the VALU.
     constexpr int NZR = XS3 ? 1 : 4, NZA = XS3 ? 1 : KP, NZS = XS3 ? 16 : 1;
     float Zr[NZR][NZA], pr[4];
-    // (KP = 32, THIS kernel's own stage 3 -- not k_grads_s3, which issues six products
-    // from round 4 on: K = a = 32 per MFMA, 8 values per lane and piece, the two leading pieces only -- four products, <= 2^-17
-    // each; the third piece would take 16 KB of LDS per wave)
-    using ZV = std::conditional_t<KP == 32, u32x4, u32x2>;
-    constexpr int NZJ = KP == 32 ? 8 : 4;              // values of Z per lane and spectrum
-    ZV Zh[NZS], Zm[NZS];
+    u32x2 Zh[NZS], Zm[NZS];
     u32x2 ph = {0u, 0u}, pm = {0u, 0u}, pl = {0u, 0u};
     bool sv[4];
     unsigned rowi[4];                             // rows of the lane's four spectra in the batch arrays (qfa_common.h, batch_row); the
@@ -570,51 +514,39 @@ __global__ __launch_bounds__(256, KP == 8 ? QFA_G8_OCC : 2) void k_grads(qfa_par
     for (int r = 0; r < 4; ++r) {
         const int srel = 4 * g + r;
         sv[r] = active && (s0 + srel) < B;
-        const int col = 16 * bhalf + lo;
-        const bool v = sv[r] && col < KP;
+        const bool v = sv[r] && lo < KP;
         const float *sol = SOL + (size_t)(v ? s0 + srel : 0) * C::NSOL;
         if constexpr (!XS3) {
 #pragma unroll
-            for (int a = 0; a < KP; ++a) Zr[r][a] = v ? sol[C::SOL_Z + a * KP + col] : 0.f;
+            for (int a = 0; a < KP; ++a) Zr[r][a] = v ? sol[C::SOL_Z + a * KP + lo] : 0.f;
         }
-        pr[r] = v ? sol[C::SOL_P + col] : 0.f;
+        pr[r] = v ? sol[C::SOL_P + lo] : 0.f;
         const int sc = active ? min(srel, B - 1 - s0) : 0;
         rowi[r] = (unsigned)batch_row(bt, (active ? s0 : 0) + sc);
         offB[r] = sc * Nb;                          // (A_blue: batch order)
     }
     if constexpr (XS3) {
-        unsigned *zl = ldszl[KP == 16 ? wv : 0];
+        unsigned *zl = ldszl[wv];
         // all 64 loads first (the LDS stores below otherwise serialise them: load 4, wait, split, store, ...)
-        float zraw[16][NZJ];
-        const int zcol = 16 * bhalf + lo;
+        float zraw[16][4];
 #pragma unroll
         for (int s = 0; s < 16; ++s) {
-            const bool v = active && (s0 + s) < B && zcol < KP;
-            const float *sol = SOL + (size_t)(v ? s0 + s : 0) * C::NSOL + C::SOL_Z + zcol;
+            const bool v = active && (s0 + s) < B;
+            const float *sol = SOL + (size_t)(v ? s0 + s : 0) * C::NSOL + C::SOL_Z + lo;
 #pragma unroll
-            for (int j = 0; j < NZJ; ++j) zraw[s][j] = (v && NZJ * g + j < KP) ? sol[(NZJ * g + j) * KP] : 0.f;
+            for (int j = 0; j < 4; ++j) zraw[s][j] = v ? sol[(4 * g + j) * KP] : 0.f;
         }
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int s = 0; s < 16; ++s) {
             const float *z = zraw[s];
-            if constexpr (KP == 32) {
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    unsigned h, m, l;
-                    split2(z[2 * q], z[2 * q + 1], h, m, l);
-                    Zh[s][q] = h;
-                    Zm[s][q] = m;
-                }
-            } else {
-                unsigned h0, m0, l0, h1, m1, l1;
-                split2(z[0], z[1], h0, m0, l0);
-                split2(z[2], z[3], h1, m1, l1);
-                Zh[s] = u32x2{h0, h1};
-                Zm[s] = u32x2{m0, m1};
-                zl[(s * 64 + lane) * 2] = l0;
-                zl[(s * 64 + lane) * 2 + 1] = l1;
-            }
+            unsigned h0, m0, l0, h1, m1, l1;
+            split2(z[0], z[1], h0, m0, l0);
+            split2(z[2], z[3], h1, m1, l1);
+            Zh[s] = u32x2{h0, h1};
+            Zm[s] = u32x2{m0, m1};
+            zl[(s * 64 + lane) * 2] = l0;
+            zl[(s * 64 + lane) * 2 + 1] = l1;
         }
         // p of the spectra 4g+j as the B operand of the gamma term (K = spectrum)
         unsigned h0, m0, l0, h1, m1, l1;
@@ -627,8 +559,8 @@ __global__ __launch_bounds__(256, KP == 8 ? QFA_G8_OCC : 2) void k_grads(qfa_par
 #pragma unroll
     for (int r = 0; r < 4; ++r) zs[r] = zfac_load(ZS, s0 + 4 * g + r, ZF && sv[r]);
     const float4 *PFT4 = reinterpret_cast<const float4 *>(PFT);
-    using TC = TileCopy<XS3 ? NM4 : NF4>;       // (XDL stage 3: the F pieces at the end of the tile are not staged)
-    float4 tv0, tv1 = {0.f, 0.f, 0.f, 0.f}, tv2 = {0.f, 0.f, 0.f, 0.f}, tvx[TC::NX];
+    static_assert(XS3 || NF4 <= 256, "KP = 8: one staging register per thread holds the tile");
+    float4 tv = {0.f, 0.f, 0.f, 0.f};
     double s_tau0 = 0.0, s_c0 = 0.0, s_beta = 0.0;   // float32 per tile, float64 across tiles
     int ntile_done = 0;                               // picks the flushing wave, round robin
 
@@ -716,11 +648,10 @@ __global__ __launch_bounds__(256, KP == 8 ? QFA_G8_OCC : 2) void k_grads(qfa_par
                 else if (t < NK1 && (t & 1)) a1 = mfma4(qA[t < NK1 ? t - KF : 0], bop[t & 7], a1);
                 else if (t < NK1) a2 = mfma4(qA[t < NK1 ? t - KF : 0], bop[t & 7], a2);
             };
-            constexpr int SF = (NK1 + 39) / 40;      // MFMAs per slot (1 up to N_h = 16, 4 at N_h = 32)
             int slot_no = 0;
             auto slots = [&](int nslot) {            // nslot MFMA slots, then fence
 #pragma unroll
-                for (int i = 0; i < nslot * SF; ++i) {
+                for (int i = 0; i < nslot; ++i) {
                     rd(slot_no + AHEAD);
                     mf(slot_no);
                     ++slot_no;
@@ -863,7 +794,7 @@ __global__ __launch_bounds__(256, KP == 8 ? QFA_G8_OCC : 2) void k_grads(qfa_par
                     slots(8);
                 }
             }
-            static_assert(NK1 <= 40 * SF && AHEAD < 8, "stage 1 has more K-steps than MFMA slots");
+            static_assert(NK1 <= 40 && AHEAD < 8, "stage 1 has more K-steps than MFMA slots");
             if (BLUE) {
                 s_tau0 += (double)t_tau0;
                 s_c0 += (double)t_c0;
@@ -905,31 +836,22 @@ __global__ __launch_bounds__(256, KP == 8 ? QFA_G8_OCC : 2) void k_grads(qfa_par
         // static operands), then accF[px][b] += beta_{s,px} G_s[px][b] on the VALU; beta reaches the lane that
         // holds rows px = 4g..4g+3 of G through the wave's LDS slot.  The gamma term sum_s gamma_{s,px} p_s[b] is
         // one more product with K = spectrum (gamma split in the loop: 4 values per lane).
-        auto stage3x = [&](const float4 *fpt, const ZV &Fgh, const ZV &Fgm, const float (&betaR)[4], const float (&gamR)[4],
-                           float *part) {
+        auto stage3x = [&](const float4 *fpt, const float (&betaR)[4], const float (&gamR)[4], float *part) {
             if constexpr (XS3) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) part[(4 * g + r) * 16 + lo] = betaR[r];
-                const ZV *fp = reinterpret_cast<const ZV *>(fpt) + lane;
-                const ZV Fh = XDMA ? fp[0] : Fgh, Fm = XDMA ? fp[64] : Fgm;
+                const u32x2 *fp = reinterpret_cast<const u32x2 *>(fpt) + lane;
+                const u32x2 Fh = fp[0], Fm = fp[64];
                 unsigned h0, m0, l0, h1, m1, l1;
                 split2(gamR[0], gamR[1], h0, m0, l0);
                 split2(gamR[2], gamR[3], h1, m1, l1);
                 const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
                 f32x4 acc = xdl16_6(u32x2{h0, h1}, u32x2{m0, m1}, u32x2{l0, l1}, ph, pm, pl, zero);
-                const u32x2 *zl = reinterpret_cast<const u32x2 *>(ldszl[KP == 16 ? wv : 0]) + lane;
+                const u32x2 *zl = reinterpret_cast<const u32x2 *>(ldszl[wv]) + lane;
                 const float4 *brow = reinterpret_cast<const float4 *>(part) + g;
 #pragma unroll
                 for (int s = 0; s < 16; ++s) {
-                    f32x4 G;
-                    if constexpr (KP == 32) {
-                        G = xdl(Fm, Zm[s], zero);
-                        G = xdl(Fm, Zh[s], G);
-                        G = xdl(Fh, Zm[s], G);
-                        G = xdl(Fh, Zh[s], G);
-                    } else {
-                        G = xdl16_6(Fh, Fm, fp[128], Zh[s], Zm[s], zl[s * 64], zero);
-                    }
+                    const f32x4 G = xdl16_6(Fh, Fm, fp[128], Zh[s], Zm[s], zl[s * 64], zero);
                     const float4 bq = brow[s * 4];
                     acc[0] = fmaf(bq.x, G[0], acc[0]);
                     acc[1] = fmaf(bq.y, G[1], acc[1]);
@@ -950,10 +872,10 @@ __global__ __launch_bounds__(256, KP == 8 ? QFA_G8_OCC : 2) void k_grads(qfa_par
             {
                 const int idx = lane + 64 * wv;
                 const float v = (pp[0][idx] + pp[1][idx]) + (pp[2][idx] + pp[3][idx]);
-                const int px = base + (idx >> 4), b = 16 * bhalf + (idx & 15);
+                const int px = base + (idx >> 4), b = idx & 15;
                 if ((b < Nh) & (px < Npix)) add_to(accF + (size_t)px * Nh + b, v);
             }
-            if (extra & (bhalf == 0)) {
+            if (extra) {
                 const int which = lane >> 4, px = base + (lane & 15);
                 float v = 0.f;
 #pragma unroll
@@ -969,9 +891,9 @@ __global__ __launch_bounds__(256, KP == 8 ? QFA_G8_OCC : 2) void k_grads(qfa_par
         };
         auto tilebuf = [&](int c) { return reinterpret_cast<const float *>(lds4[c % RING_M]); };
         // parameter tile c -> LDS.  XDL form: LDS-DMA, wave w moves the 1-KiB pieces w, w+4, ... (no staging
-        // registers; the tile barrier retires them).  f32 form: through the staging registers (get / put).
+        // registers; the tile barrier retires them).  KP = 8: through the staging register tv (get / put).
         auto get_tile = [&](int c) {
-            if constexpr (XDMA) {
+            if constexpr (XS3) {
                 const unsigned char *src = reinterpret_cast<const unsigned char *>(PFT4 + (size_t)tile_of(c) * NF4) + lane * 16;
 #pragma unroll
                 for (int i = 0; i < (NCH + 3) / 4; ++i) {
@@ -980,11 +902,13 @@ __global__ __launch_bounds__(256, KP == 8 ? QFA_G8_OCC : 2) void k_grads(qfa_par
                     else if (ch < NCH) glds16(src + ch * 1024, reinterpret_cast<unsigned char *>(ldsfp[c % 3]) + (ch - NCH_MAIN) * 1024);
                 }
             } else {
-                TC::load(PFT4 + (size_t)tile_of(c) * NF4, tid, tv0, tv1, tv2, tvx);
+                tv = PFT4[(size_t)tile_of(c) * NF4 + min(tid, NF4 - 1)];
             }
         };
         auto put_tile = [&](int c) {
-            if constexpr (!XDMA) TC::store(lds4[c % RING_M], tid, tv0, tv1, tv2, tvx);
+            if constexpr (!XS3) {
+                if (tid < NF4) lds4[c % RING_M][tid] = tv;
+            }
         };
 
         // Software pipeline over tiles (one barrier per tile, ring of 3 parameter tiles):
@@ -1000,14 +924,6 @@ __global__ __launch_bounds__(256, KP == 8 ? QFA_G8_OCC : 2) void k_grads(qfa_par
             f32x4 afyN = {0.f, 0.f, 0.f, 0.f}, aqN = {0.f, 0.f, 0.f, 0.f};
             PixPar pxpN{0.f, 0.f, 0.f, 0.f, 0.f};
             float betaR[4] = {0.f, 0.f, 0.f, 0.f}, gamR[4] = {0.f, 0.f, 0.f, 0.f};
-            ZV Fgh = {}, Fgm = {};
-            if constexpr (XS3 && !XDMA) {      // KP = 32: the lane's F pieces of this tile straight from the tile image (L2)
-                if (active) {
-                    const ZV *fg = reinterpret_cast<const ZV *>(PFT + (size_t)tg * C::TILE_PFT + C::PFT_MAIN) + lane;
-                    Fgh = fg[0];
-                    Fgm = fg[64];
-                }
-            }
             if (active) {
                 const int cn1 = more ? c + 1 : c;                 // last tile: harmless recomputation
                 load_spec(tile_of(cn1), nxt);
@@ -1018,15 +934,7 @@ __global__ __launch_bounds__(256, KP == 8 ? QFA_G8_OCC : 2) void k_grads(qfa_par
             // parameter tile c+2: issued here so that its latency runs under stage 3
             if (c + 2 < n) get_tile(c + 2);
             if (active) {
-                if (BG) {                                  // (uniform; 64-byte segments: 16 pixels of one spectrum)
-                    const size_t o = (size_t)(s0 + 4 * g) * bg_stride + 16 * tg + lo;
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        BG[o + (size_t)r * bg_stride] = betaR[r];
-                        GG[o + (size_t)r * bg_stride] = gamR[r];
-                    }
-                }
-                if constexpr (XS3) stage3x(ldsfp[XDMA ? c % 3 : 0], Fgh, Fgm, betaR, gamR, ldspart[pbuf][wv]);
+                if constexpr (XS3) stage3x(ldsfp[c % 3], betaR, gamR, ldspart[pbuf][wv]);
                 else stage3(tilebuf(c), betaR, gamR, ldspart[pbuf][wv]);
                 afy = afyN; aq = aqN; pxp = pxpN;
             }
@@ -1047,6 +955,9 @@ __global__ __launch_bounds__(256, KP == 8 ? QFA_G8_OCC : 2) void k_grads(qfa_par
         if (active) load_spec(tile_of(0), ra);
         __syncthreads();
         if (active) stage1(tilebuf(0), afy, aq, pxp);
+        // KP = 16: step 0 brings tile 2 into slot 0 of the two-slot ring, and a wave without spectra gets there at once: every
+        // wave has to be done with this read of tile 0 first
+        if constexpr (XS3) __syncthreads();
         for (int c = 0; c < n; c += 2) {
             step(c, ra, rb);
             if (c + 1 < n) step(c + 1, rb, ra);
@@ -1057,10 +968,10 @@ __global__ __launch_bounds__(256, KP == 8 ? QFA_G8_OCC : 2) void k_grads(qfa_par
     run(std::false_type{}, max(t0, nbt), t1);
 
     if (!active) {
-        if (det && lane == 0 && bhalf == 0) {              // the reducer reads every (item, wave) record
+        if (det && lane == 0) {                            // the reducer reads every (item, wave) record
             double *q = slabS + ((size_t)blockIdx.x * 4 + wv) * 3;
             q[0] = 0.0; q[1] = 0.0; q[2] = 0.0;
-        } else if (!det && bhalf == 0) {
+        } else if (!det) {
             scal64_commit(sc64, 0.0, 0.0, 0.0, gridDim.x * 4u, accS);
         }
         return;
@@ -1070,7 +981,7 @@ __global__ __launch_bounds__(256, KP == 8 ? QFA_G8_OCC : 2) void k_grads(qfa_par
         s_c0 += __shfl_xor(s_c0, o);
         s_beta += __shfl_xor(s_beta, o);
     }
-    if (lane == 0 && bhalf == 0) {
+    if (lane == 0) {
         if (det) {
             double *q = slabS + ((size_t)blockIdx.x * 4 + wv) * 3;
             q[0] = s_tau0; q[1] = s_c0; q[2] = s_beta;

@@ -420,7 +420,7 @@ class QFA(ForestStatistics):
                    batch=None):
         """Raw sums of one (shard of a) batch into the packed buffer; no normalisation.
         ``events``: optional list of 5 recorded torch.cuda.Event(enable_timing=True) that the library
-        re-records at {start, PF image, pass 1, solve, pass 2} on the current stream (bench.py).
+        re-records at {start, parameter images, pass 1, solve, pass 2} on the current stream (bench.py).
         ``batch``: a ``ResidentBatch`` in the place of the four tensors (the resident, indexed input form)."""
         ps = self._params_struct()
         if batch is not None:

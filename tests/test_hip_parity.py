@@ -365,12 +365,17 @@ def test_custom_tau_callable_goes_through_A_blue(dev, shipped, grid):
     assert abs(l3.item() - ol3) / abs(ol3) < TOL_NLL
 
 
-@pytest.mark.parametrize("npix,nh,B", [(200, 12, 70), (1000, 16, 40), (97, 8, 33)])
-def test_custom_tau_on_the_xdl_pass2(dev, npix, nh, B, monkeypatch):
+@pytest.mark.parametrize("npix,nh,B,exact", [
+    pytest.param(200, 12, 70, False, id="200-12-70"), pytest.param(1000, 16, 40, False, id="1000-16-40"),
+    pytest.param(97, 8, 33, False, id="97-8-33"),
+    # exact-gradient mode: the two k_grads instantiations (KP = 16 / 8, A_blue, exact terms) no other test reaches
+    pytest.param(200, 12, 70, True, id="200-12-70-exact"), pytest.param(97, 8, 33, True, id="97-8-33-exact")])
+def test_custom_tau_on_the_xdl_pass2(dev, npix, nh, B, exact, monkeypatch):
     """The A_blue input (a user tau callable) through k_grads_x (HASA instantiation; N_h = 8 forced onto it), ragged
     shapes: section by section against k_grads on the SAME A_blue, and the vector gradients against the built-in becker
     tau (the callable IS becker; the three scalar gradients are sums of cancelling terms that amplify the difference
-    between torch's pow / exp and the kernel's exp2 / log2, so they are compared on the same-input pair only)."""
+    between torch's pow / exp and the kernel's exp2 / log2, so they are compared on the same-input pair only).
+    ``exact``: the same with QFA.exact_gradients on both models."""
     from qfa_amd import synthetic
     from tools import parity_sections as PS
     wav, nb, nr = synthetic.wavelength_grid(npix)
@@ -378,6 +383,7 @@ def test_custom_tau_on_the_xdl_pass2(dev, npix, nh, B, monkeypatch):
     b = synthetic.make_batch_numpy(p, mu, wav, nb, B, seed=npix + 1)
     m1 = make_model(dev, p, mu)
     m2 = make_model(dev, p, mu, tau=lambda z: 0.751 * ((1 + z) / 4.5) ** 2.90 - 0.132)
+    m1.exact_gradients = m2.exact_gradients = exact
     bt = batch_t(b, dev)
     m2.flags = _lib.F_PASS2_PIXRES                           # (N_h = 9..16: k_grads_t's HASA instantiation)
     acc_t = m2.accumulate(*bt).clone()
