@@ -557,6 +557,51 @@ int qfa_flux_pdf_f32(const float *trans, const float *ivar, const qfa_batch_t *b
                      const qfa_p1d_t *p, const qfa_pdf_t *q, unsigned flags, int *hist, double *stack,
                      void *workspace, size_t workspace_bytes, void *stream);
 
+/* The variance function of the forest: the moments of delta_F in bins of the pipeline's noise variance v and of redshift, per
+ * posterior draw (additive to ABI v4).  qfa_xi_f32 weights a pixel by 1 / (v + sigma2_lss) and qfa_p1d_f32 subtracts a noise level
+ * made of v: both rest on v being right and on a number, sigma2_lss, that nothing above produces.  The standard answer of the Lya
+ * pipelines is to measure var(delta_F) in bins of v and z and to fit var = eta v + sigma2_lss (+ eps / v): eta corrects the
+ * pipeline's noise, sigma2_lss is the intrinsic variance of the forest, and the scatter of the fit over the draws is the continuum's
+ * error bar on both.  This call takes qfa_p1d_f32's inputs and writes the five sums per bin the fit needs, without ever writing
+ * delta_F; the fit itself is a closed form on the stack (qfa_amd.stacks.VarianceStack.fit).
+ *
+ * The contract.  trans, ivar, b, tbar, B, S, Nb and p are qfa_p1d_f32's, bit for bit: `used`, d and v of a pixel, n_used, validity
+ * (n_used >= min_used) and the z-bin kz of a segment (at its central pixel p_lo + g L + L / 2) are those of that call, with its rules
+ * on the redshift forms and on NaN under the mask.  nv = n_oct << sub variance bins, 2^sub per octave from 2^e_lo on:
+ *   bin rule   on bits, no logarithm: with u the int32 bit pattern of the float32 v, c = (u >> (23 - sub)) - ((e_lo + 127) << sub)
+ *              (an arithmetic shift).  Bin c covers 2^(e_lo + (c >> sub)) [1 + m / 2^sub, 1 + (m + 1) / 2^sub), m = c & (2^sub - 1):
+ *              an edge belongs to the bin above it.  Zero, denormal, negative, inf and NaN v have c outside [0, nv) by construction;
+ *   per pixel  counted = used && the segment is valid && 0 <= c < nv && fabsf(d) <= d_max (false for a NaN d; d_max = FLT_MAX cuts
+ *              the non-finite d alone).  Its terms in float64: (double)v, (double)d, d2 = (double)d (double)d (exact) and d4 = d2 d2
+ *              (rounded once); no contraction.  Everything is done by selects: nothing under the mask reaches an output;
+ *   segment    moments (B S, nseg, 5, nv) float64 = [n_a | sum v | sum d | sum d^2 | sum d^4] over the counted pixels of bin a.  The
+ *              order of the additions is a fixed function of the segment's data and of (L, nv): never of the grid, of B, S or of
+ *              how a batch is cut.  An invalid segment gets exactly 0 everywhere;
+ *   outputs    stack (S, nz, 2 + 5 nv) float64 = [n_seg | n_used | n_a | sum v_a | sum d_a | sum d^2_a | sum d^4_a] per draw and
+ *              z-bin over the valid segments with 0 <= kz < nz; n_used = the used pixels of those segments, so that n_used - sum_a
+ *              n_a is what fell outside the bins or the cut.  The call ADDS to `stack`; QFA_F_ZERO_ACCUM overwrites.  Either output
+ *              may be NULL, not both;
+ *   sums       qfa_xi_f32's: no atomics; the segments of a draw, in order of (b, g) over the whole call, are cut into chunks of
+ *              qfa_p1d_band_chunk_segments(); a chunk's sums start from 0 and add its segments in order, leave through the
+ *              workspace, and a second kernel adds them in chunk order onto what `stack` holds.  The host cuts B on chunk
+ *              boundaries: two calls on the same inputs give the same bits, and draw s of a call of S draws gets the bits of a
+ *              call on that draw alone.
+ * qfa_variance_stack_doubles: S nz (2 + 5 nv); 0 = unsupported (S < 1, nz outside 1..4096, nv outside 1..64).
+ * qfa_variance_workspace_bytes(R = B S, ...): qfa_p1d_workspace_bytes' shapes, and nv outside 1..64, give 0.  The rows
+ * (segment, 1 + 5 nv) float64 and the chunk partials of one launch aim at the cap of qfa_p1d_f32's rows; the least a launch holds
+ * is the fewest spectra whose segments fill whole chunks.
+ * Returns every code of qfa_p1d_f32 for the arguments they share; QFA_E_NULL also for q or both outputs missing; QFA_E_SIZE also
+ * for sub outside 0..4, n_oct < 1, n_oct << sub above 64, e_lo < -126, e_lo + n_oct > 127, d_max <= 0 or NaN; QFA_E_FLAGS for any
+ * flag other than QFA_F_ZERO_ACCUM, QFA_F_SYNC.  Argument checks return before any device work.  B = 0 does nothing, except zeroing
+ * `stack` under QFA_F_ZERO_ACCUM.  The call neither synchronises nor allocates. */
+typedef struct { int e_lo, n_oct, sub; float d_max; } qfa_var_t;   /* 0 <= sub <= 4, 1 <= n_oct << sub <= 64, -126 <= e_lo, e_lo + n_oct <= 127, d_max > 0 */
+
+size_t qfa_variance_stack_doubles(int S, int nz, int nv);
+size_t qfa_variance_workspace_bytes(int R, int S, int Nb, int L, int nseg, int nz, int nv);
+int qfa_variance_f32(const float *trans, const float *ivar, const qfa_batch_t *b, const float *tbar, int B, int S, int Nb,
+                     const qfa_p1d_t *p, const qfa_var_t *q, unsigned flags, double *moments, double *stack,
+                     void *workspace, size_t workspace_bytes, void *stream);
+
 /* Replaces Adam.update(reference QFA/optimizer.py:37-52) followed by the clamp of QFA.clip
  * (QFA/model.py:233-241) for ONE tensor of n elements:
  *   g' = g + wd*p; m = (1-b1) g' + b1 m; v = (1-b2) g'^2 + b2 v;

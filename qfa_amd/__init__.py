@@ -16,6 +16,7 @@ _LAZY = {
     "P1DBandStack": ("qfa_amd.model", "P1DBandStack"),
     "XiStack": ("qfa_amd.model", "XiStack"),
     "PDFStack": ("qfa_amd.model", "PDFStack"),
+    "VarianceStack": ("qfa_amd.model", "VarianceStack"),
     "Adam": ("qfa_amd.optimizer", "Adam"),
     "step_scheduler": ("qfa_amd.optimizer", "step_scheduler"),
 }

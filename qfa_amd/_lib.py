@@ -26,6 +26,7 @@ EXPORTS = (
     "qfa_p1d_band_stack_doubles", "qfa_p1d_band_workspace_bytes", "qfa_p1d_band_chunk_segments", "qfa_p1d_band_f32",
     "qfa_xi_stack_doubles", "qfa_xi_workspace_bytes", "qfa_xi_f32",
     "qfa_flux_pdf_stack_doubles", "qfa_flux_pdf_workspace_bytes", "qfa_flux_pdf_f32",
+    "qfa_variance_stack_doubles", "qfa_variance_workspace_bytes", "qfa_variance_f32",
 )
 
 TAU_IDS = {"becker": 0, "fg": 1, "kamble": 2, "mock": 3}
@@ -87,6 +88,10 @@ class XiParams(C.Structure):        # qfa_xi_t
 
 class PDFParams(C.Structure):       # qfa_pdf_t
     _fields_ = [("t0", C.c_float), ("dt", C.c_float), ("nt", C.c_int), ("ivar_min", C.c_float)]
+
+
+class VarParams(C.Structure):       # qfa_var_t
+    _fields_ = [("e_lo", C.c_int), ("n_oct", C.c_int), ("sub", C.c_int), ("d_max", C.c_float)]
 
 
 _lib = None
@@ -168,6 +173,9 @@ def lib():
         "qfa_flux_pdf_stack_doubles": (sz, [i, i, i]),
         "qfa_flux_pdf_workspace_bytes": (sz, [i, i, i, i, i, i, i]),
         "qfa_flux_pdf_f32": (i, [p, p, C.POINTER(Batch), p, i, i, i, C.POINTER(P1DParams), C.POINTER(PDFParams), C.c_uint, p, p, p, sz, p]),
+        "qfa_variance_stack_doubles": (sz, [i, i, i]),
+        "qfa_variance_workspace_bytes": (sz, [i, i, i, i, i, i, i]),
+        "qfa_variance_f32": (i, [p, p, C.POINTER(Batch), p, i, i, i, C.POINTER(P1DParams), C.POINTER(VarParams), C.c_uint, p, p, p, sz, p]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(h, name, None)

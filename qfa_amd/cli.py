@@ -118,6 +118,20 @@ def main(argv=None):
             raise ValueError("MODEL.PDF_TMAX must be finite and above MODEL.PDF_TMIN")
         if not float(cfg.MODEL.PDF_IVAR_MIN) >= 0.0 or float(cfg.MODEL.PDF_IVAR_MIN) == float("inf"):
             raise ValueError("MODEL.PDF_IVAR_MIN must be finite and >= 0")
+    if cfg.TYPE == "predict" and int(cfg.MODEL.VAR_NOCT) != 0:
+        noct, elo, sub = int(cfg.MODEL.VAR_NOCT), int(cfg.MODEL.VAR_ELO), int(cfg.MODEL.VAR_SUB)
+        if not 0 <= sub <= 4:
+            raise ValueError("MODEL.VAR_SUB must lie in 0 .. 4")
+        if not 1 <= noct << sub <= 64:
+            raise ValueError("MODEL.VAR_NOCT << MODEL.VAR_SUB must lie in 1 .. 64 (0 = off)")
+        if int(cfg.MODEL.P1D_SEGMENTS) <= 0:
+            raise ValueError("MODEL.VAR_NOCT > 0 needs MODEL.P1D_SEGMENTS > 0 (the segments whose pixels are binned)")
+        if elo < -126 or elo + noct > 127:
+            raise ValueError("MODEL.VAR_ELO must be >= -126 and MODEL.VAR_ELO + MODEL.VAR_NOCT <= 127")
+        if not float(cfg.MODEL.VAR_DMAX) >= 0.0 or float(cfg.MODEL.VAR_DMAX) == float("inf"):
+            raise ValueError("MODEL.VAR_DMAX must be finite and >= 0 (0 = no cut)")
+        if int(cfg.MODEL.VAR_MIN_COUNT) < 1:
+            raise ValueError("MODEL.VAR_MIN_COUNT must be >= 1")
     os.makedirs(cfg.DATA.OUTPUT_DIR, exist_ok=True)
     with open(os.path.join(cfg.DATA.OUTPUT_DIR, "config.yaml"), "w") as f:
         f.write(cfg.dump())
@@ -209,6 +223,24 @@ def main(argv=None):
                     out["std_over_draws"] = fs.std_over_draws.cpu().numpy()
                     out["total_cov"] = fs.total_cov.cpu().numpy()
                 np.savez(os.path.join(cfg.DATA.OUTPUT_DIR, "flux_pdf.npz"), **out)
+            if int(cfg.MODEL.VAR_NOCT) > 0:
+                vs = model.variance_function(dataloader, float(cfg.MODEL.FOREST_ZMIN), float(cfg.MODEL.FOREST_ZMAX), int(cfg.MODEL.P1D_NZBINS),
+                                             e_lo=int(cfg.MODEL.VAR_ELO), n_oct=int(cfg.MODEL.VAR_NOCT), sub=int(cfg.MODEL.VAR_SUB),
+                                             d_max=float(cfg.MODEL.VAR_DMAX) if float(cfg.MODEL.VAR_DMAX) > 0.0 else None,
+                                             n_segments=int(cfg.MODEL.P1D_SEGMENTS), min_used_frac=float(cfg.MODEL.P1D_MIN_USED_FRAC),
+                                             tbar=st, n_samples=int(cfg.MODEL.N_SAMPLES), seed=int(cfg.MODEL.SAMPLE_SEED))
+                ft = vs.fit(min_count=int(cfg.MODEL.VAR_MIN_COUNT))
+                out = dict(z=vs.z_centers.cpu().numpy(), z_edges=vs.z_edges.cpu().numpy(), v_edges=vs.v_edges.cpu().numpy(),
+                           v_mean=vs.v_mean.cpu().numpy(), var_delta=vs.var_delta.cpu().numpy(), var_err=vs.var_err.cpu().numpy(),
+                           mean_delta=vs.mean_delta.cpu().numpy(), counts=vs.counts.cpu().numpy(),
+                           n_segments=vs.n_segments.cpu().numpy(), n_pixels=vs.n_pixels.cpu().numpy(),
+                           out_of_range=vs.out_of_range().cpu().numpy(), seg_len=vs.L, sums=vs.buf.cpu().numpy(),
+                           eta=ft.eta.cpu().numpy(), sigma2_lss=ft.sigma2_lss.cpu().numpy(), cov=ft.cov.cpu().numpy(),
+                           chi2=ft.chi2.cpu().numpy(), ndof=ft.ndof.cpu().numpy(), n_bins=ft.n_bins.cpu().numpy())
+                if vs.S > 1:
+                    out["eta_std_over_draws"], out["sigma2_lss_std_over_draws"] = (
+                        t.cpu().numpy() for t in vs.std_over_draws(min_count=int(cfg.MODEL.VAR_MIN_COUNT)))
+                np.savez(os.path.join(cfg.DATA.OUTPUT_DIR, "variance_function.npz"), **out)
         print(f"Finish predicting {len(dataloader)} spectra in {time.time() - ts} seconds...")
     return 0
 

@@ -76,7 +76,12 @@ DEFAULTS = {                                        # reference QFA/config.py:15
               # distribution of the transmitted flux of the same segments in PDF_NBINS bins of [PDF_TMIN, PDF_TMAX) per z-bin with
               # the covariance matrix between the bins; PDF_CLAMP counts pixels outside the range in the first / last bin,
               # PDF_RELATIVE bins T / <T>(z), PDF_IVAR_MIN leaves out pixels of lower inverse variance (QFA.flux_pdf)
-              "PDF_NBINS": 0, "PDF_TMIN": 0.0, "PDF_TMAX": 1.0, "PDF_CLAMP": True, "PDF_RELATIVE": False, "PDF_IVAR_MIN": 0.0},
+              "PDF_NBINS": 0, "PDF_TMIN": 0.0, "PDF_TMAX": 1.0, "PDF_CLAMP": True, "PDF_RELATIVE": False, "PDF_IVAR_MIN": 0.0,
+              # not in the reference: VAR_NOCT > 0 (needs P1D_SEGMENTS > 0) also writes variance_function.npz, the variance of delta_F
+              # of the same segments in VAR_NOCT octaves of the pipeline's noise variance from 2^VAR_ELO on, 2^VAR_SUB bins per octave
+              # (at most 64 bins), per z-bin, and the fit var = eta v + sigma2_lss on the bins of at least VAR_MIN_COUNT pixels;
+              # VAR_DMAX > 0 leaves out pixels with |delta_F| above it (QFA.variance_function)
+              "VAR_NOCT": 0, "VAR_ELO": -12, "VAR_SUB": 1, "VAR_DMAX": 0.0, "VAR_MIN_COUNT": 100},
     "TRAIN": {"NEPOCHS": 500, "LEARNING_RATE": 1e-3, "WEIGHT_DECAY": 1e-1, "DECAY_ALPHA": 0.9, "DECAY_STEP": 10,
               "WINDOW_LENGTH_FOR_MU": 16,
               # not in the reference: "em" = F by its closed-form EM update, Adam for the other parameters (QFA.train
@@ -99,7 +104,8 @@ ARG_KEYS = {
 EXTRA_KEYS = ("MODEL.REFERENCE_C0_QUIRK", "MODEL.N_SAMPLES", "MODEL.SAMPLE_SEED", "MODEL.N_REPLICATES", "MODEL.EXACT_GRADIENTS",
               "MODEL.FOREST", "MODEL.FOREST_ZMIN", "MODEL.FOREST_ZMAX", "MODEL.FOREST_NBINS", "MODEL.P1D_SEGMENTS",
               "MODEL.P1D_NZBINS", "MODEL.P1D_MIN_USED_FRAC", "MODEL.P1D_NBANDS", "MODEL.XI_NLAGS", "MODEL.XI_SIGMA2_LSS", "MODEL.PDF_NBINS",
-              "MODEL.PDF_TMIN", "MODEL.PDF_TMAX", "MODEL.PDF_CLAMP", "MODEL.PDF_RELATIVE", "MODEL.PDF_IVAR_MIN", "TRAIN.F_UPDATE", "TRAIN.EM_RHO", "TRAIN.EM_RIDGE")
+              "MODEL.PDF_TMIN", "MODEL.PDF_TMAX", "MODEL.PDF_CLAMP", "MODEL.PDF_RELATIVE", "MODEL.PDF_IVAR_MIN", "MODEL.VAR_NOCT", "MODEL.VAR_ELO",
+              "MODEL.VAR_SUB", "MODEL.VAR_DMAX", "MODEL.VAR_MIN_COUNT", "TRAIN.F_UPDATE", "TRAIN.EM_RHO", "TRAIN.EM_RIDGE")
 
 
 def _set(cfg, dotted, value):

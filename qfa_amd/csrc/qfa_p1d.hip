@@ -3,12 +3,14 @@
 // (qfa_p1d_band_stack_doubles, qfa_p1d_band_workspace_bytes, qfa_p1d_band_chunk_segments, qfa_p1d_band_f32): argument checks, the
 // launch plans and the launches; and of the pair-weighted correlation function of the same segments and its (lag, z) stack
 // (qfa_xi_stack_doubles, qfa_xi_workspace_bytes, qfa_xi_f32); and of the flux PDF of the same segments and its covariance stack
-// (qfa_flux_pdf_stack_doubles, qfa_flux_pdf_workspace_bytes, qfa_flux_pdf_f32).  Kernels in qfa_p1d.h, qfa_p1d_band.h, qfa_xi.h and
-// qfa_pdf.h.
+// (qfa_flux_pdf_stack_doubles, qfa_flux_pdf_workspace_bytes, qfa_flux_pdf_f32); and of the variance function of the same segments
+// and its (v-bin, z) stack (qfa_variance_stack_doubles, qfa_variance_workspace_bytes, qfa_variance_f32).  Kernels in qfa_p1d.h,
+// qfa_p1d_band.h, qfa_xi.h, qfa_pdf.h and qfa_variance.h.
 #include "qfa_p1d.h"
 #include "qfa_p1d_band.h"
 #include "qfa_xi.h"
 #include "qfa_pdf.h"
+#include "qfa_variance.h"
 #include "../../include/qfa_hip.h"
 
 #include <math.h>
@@ -108,7 +110,14 @@ PdfPlan make_pdf_plan(int B, int S, int nseg, int nz, int nt) {
     return P;
 }
 
-// The checks the four calls share behind their own NULL checks, in qfa_p1d_f32's order: the redshift form (`fac`: zq1 x pix_ratio),
+// the variance call: workspace = [code | rows (segments, 1 + 5 nv) from the next 8-byte boundary | partials (chunks, S, nz, 2 + 5 nv)]
+// from its first 16-byte boundary on
+ChunkPlan make_var_plan(int B, int S, int nseg, int nz, int nv) {
+    return make_chunk_plan(B, S, nseg, 4 + (size_t)(1 + 5 * nv) * sizeof(double), (size_t)S * nz * (size_t)(2 + 5 * nv) * sizeof(double),
+                           16 + 8 + 8);
+}
+
+// The checks the five calls share behind their own NULL checks, in qfa_p1d_f32's order: the redshift form (`fac`: zq1 x pix_ratio),
 // then the sizes.  The statistic's own sizes and the flags follow in the caller.
 int check_call(const qfa_batch_t *b, int B, int S, int Nb, const qfa_p1d_t *p, bool &fac) {
     fac = b->zq1 || b->pix_ratio;
@@ -125,7 +134,7 @@ int check_call(const qfa_batch_t *b, int B, int S, int Nb, const qfa_p1d_t *p, b
     return 0;
 }
 
-// the fields the Args of k_p1d, k_xi and k_pdf share (qfa_segment.h)
+// the fields the Args of k_p1d, k_xi, k_pdf and k_var share (qfa_segment.h)
 template <typename A>
 void seg_args(A &a, const float *trans, const float *ivar, const qfa_batch_t *b, const float *tbar, int S, int Nb, const qfa_p1d_t *p,
               bool fac) {
@@ -394,6 +403,63 @@ int qfa_flux_pdf_f32(const float *trans, const float *ivar, const qfa_batch_t *b
         const int chunks = (int)(((size_t)a.Bc * nseg + kChunk - 1) / kChunk);
         pd::k_pdf<<<(unsigned)((size_t)chunks * S), pd::kThreads, lds, st>>>(a);
         if (stack) chunk_reduce(a.part, chunks, S, nz, 2 + nt, nt, zero, stack, st);
+    });
+}
+
+size_t qfa_variance_stack_doubles(int S, int nz, int nv) {
+    if (S < 1 || nz < 1 || nz > kMaxBins || nv < 1 || nv > qfa_variance::kMaxBins) return 0;
+    return (size_t)S * nz * (size_t)(2 + 5 * nv);
+}
+
+size_t qfa_variance_workspace_bytes(int R, int S, int Nb, int L, int nseg, int nz, int nv) {
+    if (!shape_ok(R, S, Nb, L, nseg, nz) || nv < 1 || nv > qfa_variance::kMaxBins) return 0;
+    return make_var_plan(R / S, S, nseg, nz, nv).bytes;
+}
+
+int qfa_variance_f32(const float *trans, const float *ivar, const qfa_batch_t *b, const float *tbar, int B, int S, int Nb,
+                     const qfa_p1d_t *p, const qfa_var_t *q, unsigned flags, double *moments, double *stack, void *workspace,
+                     size_t workspace_bytes, void *stream) {
+    namespace vf = qfa_variance;
+    if (!trans || !ivar || !b || !tbar || !p || !workspace || !q || (!moments && !stack)) return QFA_E_NULL;
+    bool fac;
+    if (int e = check_call(b, B, S, Nb, p, fac)) return e;
+    if (q->sub < 0 || q->sub > 4 || q->n_oct < 1 || q->n_oct > vf::kMaxBins || (q->n_oct << q->sub) > vf::kMaxBins || q->e_lo < -126 ||
+        (int64_t)q->e_lo + q->n_oct > 127 || !(q->d_max > 0.f))
+        return QFA_E_SIZE;
+    if (flags & ~(QFA_F_ZERO_ACCUM | QFA_F_SYNC)) return QFA_E_FLAGS;
+    const int nseg = p->nseg, nz = p->nz, nv = q->n_oct << q->sub;
+    const ChunkPlan P = make_var_plan(B, S, nseg, nz, nv);
+    if (workspace_bytes < P.bytes) return QFA_E_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t W = 1 + 5 * (size_t)nv;
+    int *code = aligned<int>(workspace, 16);
+    double *rows = aligned<double>(code + P.segs, 8);
+    double *part = rows + P.segs * W;
+    vf::Args a;
+    seg_args(a, trans, ivar, b, tbar, S, Nb, p, fac);
+    a.moments = moments;
+    a.nv = nv;
+    a.shift = 23 - q->sub;
+    a.c0 = (q->e_lo + 127) << q->sub;
+    a.d_max = q->d_max;
+    vf::StackArgs sa;
+    sa.rows = rows;
+    sa.code = code;
+    sa.part = part;
+    sa.S = S; sa.nseg = nseg; sa.nv = nv; sa.nz = nz;
+    // without a stack nothing is held between the kernels: one launch writes the caller's array
+    // (with a stack every b0 nseg is a multiple of kChunk)
+    return run_call(a, B, stack ? P.Bc : B, flags, stack, qfa_variance_stack_doubles(S, nz, nv), st, [&](int zero) {
+        a.rows = stack ? rows : nullptr;
+        a.code = stack ? code : nullptr;
+        const size_t segs = (size_t)a.Bc * S * nseg;
+        const size_t gx = segs < ((size_t)1 << 20) ? segs : ((size_t)1 << 20);
+        vf::k_var<<<dim3((unsigned)gx, (unsigned)((segs + gx - 1) / gx)), vf::kThreads, 0, st>>>(a);
+        if (!stack) return;
+        sa.n = a.Bc * nseg;
+        const int chunks = (sa.n + kChunk - 1) / kChunk;
+        vf::k_var_stack<<<(unsigned)((size_t)chunks * S), vf::kThreads, 0, st>>>(sa);
+        chunk_reduce(part, chunks, S, nz, 2 + 5 * nv, 0, zero, stack, st);
     });
 }
 

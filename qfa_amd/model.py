@@ -20,6 +20,8 @@ Additions over the reference (none changes a reference call's result):
     sight and its (lag, z) stack, which carries no window of the mask (include/qfa_hip.h, qfa_xi_f32);
     ``flux_pdf_segments`` / ``flux_pdf`` / ``PDFStack`` -- the probability distribution of the transmitted flux of the same segments
     and the covariance matrix between its flux bins per draw and z-bin (include/qfa_hip.h, qfa_flux_pdf_f32);
+    ``variance_segments`` / ``variance_function`` / ``VarianceStack`` -- the variance of delta_F of the same segments in bins of the
+    pipeline's noise variance and of z, and the fit of eta and sigma2_lss on it (include/qfa_hip.h, qfa_variance_f32);
   * ``step`` -- forward + Adam + clip without a host sync (what ``train`` and bench.py run);
   * data parallelism: ``enable_data_parallel()`` all-reduces the packed sum/count buffer over
     RCCL once per step before the normalisation (SURVEY.md 8(e));
@@ -40,7 +42,7 @@ import torch
 
 from . import _lib
 from . import utils as _utils
-from .stacks import EMStats, ForestStack, P1DBandStack, P1DStack, PDFStack, XiStack    # (re-exported)
+from .stacks import EMStats, ForestStack, P1DBandStack, P1DStack, PDFStack, VarianceStack, XiStack    # (re-exported)
 from .statistics import ForestStatistics
 
 f32 = torch.float32

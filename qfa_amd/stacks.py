@@ -1,7 +1,9 @@
-"""The result classes of ``QFA``: ``EMStats`` and the five stacks of the forest statistics, ``ForestStack``, ``P1DStack``,
-``P1DBandStack``, ``XiStack`` and ``PDFStack``.  Views and arithmetic on buffers the kernels filled (include/qfa_hip.h): nothing here calls the library or
+"""The result classes of ``QFA``: ``EMStats`` and the six stacks of the forest statistics, ``ForestStack``, ``P1DStack``,
+``P1DBandStack``, ``XiStack``, ``PDFStack`` and ``VarianceStack``.  Views and arithmetic on buffers the kernels filled (include/qfa_hip.h): nothing here calls the library or
 needs a GPU, the classes work on CPU tensors as well.  ``qfa_amd.model`` re-exports the names."""
 from __future__ import annotations
+
+import collections
 
 import numpy as np
 import torch
@@ -561,3 +563,163 @@ class PDFStack(_DrawStack):
     def total_cov(self):
         """(nz, nt, nt) the mean over the draws of ``cov()`` plus ``cov_over_draws``"""
         return self.cov().mean(0) + self.cov_over_draws
+
+
+# what ``VarianceStack.fit`` returns: (S, nz) tensors, ``cov`` (S, nz, P, P) in the order (eta, sigma2_lss[, eps]); ``eps`` None
+# without the third term
+VarianceFit = collections.namedtuple("VarianceFit", "eta sigma2_lss eps cov chi2 ndof n_bins")
+
+
+def _sym_inverse(N):
+    """(inverse, determinant) of (..., P, P) symmetric matrices, P = 2 or 3, by cofactors: elementwise arithmetic only"""
+    P = N.shape[-1]
+    if P == 2:
+        a, b, d = N[..., 0, 0], N[..., 0, 1], N[..., 1, 1]
+        det = a * d - b * b
+        inv = torch.stack([torch.stack([d, -b], -1), torch.stack([-b, a], -1)], -2)
+        return inv / det[..., None, None], det
+    a, b, c, d, e, f = N[..., 0, 0], N[..., 0, 1], N[..., 0, 2], N[..., 1, 1], N[..., 1, 2], N[..., 2, 2]
+    A, B, Cc = d * f - e * e, c * e - b * f, b * e - c * d
+    D, E, F = a * f - c * c, b * c - a * e, a * d - b * b
+    det = a * A + b * B + c * Cc
+    inv = torch.stack([torch.stack([A, B, Cc], -1), torch.stack([B, D, E], -1), torch.stack([Cc, E, F], -1)], -2)
+    return inv / det[..., None, None], det
+
+
+class VarianceStack(_SegmentStack):
+    """The (v-bin, z) stack of the variance function of the forest (include/qfa_hip.h, qfa_variance_f32): ``buf`` =
+    (S, nz, 2 + 5 nv) float64 [n_seg | n_used | n_a | sum v_a | sum d_a | sum d^2_a | sum d^4_a] per draw of the continuum and z-bin,
+    over segments of ``L`` pixels; d = delta_F of a pixel, v the pipeline's noise variance of d.  The nv = ``n_oct`` << ``sub`` bins of
+    v are defined on the bits of the float32 v, 2^sub per octave from 2^``e_lo`` on (``v_edges``); a pixel with |d| > ``d_max``
+    (float32; None = the largest finite float32, which cuts the non-finite d alone) is left out.  ``fit`` turns the stack into
+    eta(z) and sigma2_lss(z) of var(d) = eta v + sigma2_lss."""
+
+    FLT_MAX = float(np.finfo(np.float32).max)
+
+    def __init__(self, buf, z0, dz, nz, L, e_lo, n_oct, sub=1, d_max=None):
+        self.e_lo, self.n_oct, self.sub = int(e_lo), int(n_oct), int(sub)
+        with np.errstate(over="ignore"):
+            self.d_max = self.FLT_MAX if d_max is None else float(np.float32(d_max))
+        if not (0 <= self.sub <= 4 and self.n_oct >= 1 and 1 <= (self.n_oct << self.sub) <= 64 and self.e_lo >= -126
+                and self.e_lo + self.n_oct <= 127 and self.d_max > 0.0):
+            raise QFAHipError(f"VarianceStack: e_lo = {e_lo}, n_oct = {n_oct}, sub = {sub}, d_max = {d_max}")
+        self.nv = self.n_oct << self.sub
+        super().__init__(buf, z0, dz, nz, L, 1.0, 2 + 5 * self.nv)
+
+    @classmethod
+    def zeros(cls, S, z0, dz, nz, L, e_lo, n_oct, sub=1, d_max=None, device="cpu"):
+        nv = max(0, int(n_oct)) << max(0, min(4, int(sub)))
+        return cls(torch.zeros((int(S), int(nz), 2 + 5 * nv), dtype=torch.float64, device=device), z0, dz, nz, L, e_lo, n_oct, sub, d_max)
+
+    def _like(self, buf):
+        return VarianceStack(buf, self.z0, self.dz, self.nz, self.L, self.e_lo, self.n_oct, self.sub, self.d_max)
+
+    @property
+    def var_bins(self):
+        """(e_lo, n_oct, sub, d_max), d_max as the float32 number the kernel cuts with"""
+        return (self.e_lo, self.n_oct, self.sub, self.d_max)
+
+    def same_layout(self, other):
+        return super().same_layout(other) and other.var_bins == self.var_bins
+
+    def _part(self, i):
+        return self.buf[:, :, 2 + i * self.nv:2 + (i + 1) * self.nv]
+
+    @property
+    def v_edges(self):
+        """(nv + 1,) edges of the variance bins, exact: 2^(e_lo + (c >> sub)) (1 + (c & (2^sub - 1)) / 2^sub), c = 0 .. nv; an edge
+        belongs to the bin above it"""
+        c = np.arange(self.nv + 1)
+        e = np.ldexp(1.0 + (c & ((1 << self.sub) - 1)) / float(1 << self.sub), self.e_lo + (c >> self.sub))
+        return torch.tensor(e, dtype=torch.float64, device=self.buf.device)
+
+    @property
+    def n_segments(self):
+        """(S, nz) number of segments stacked"""
+        return self.buf[:, :, 0]
+
+    @property
+    def n_pixels(self):
+        """(S, nz) number of used pixels of the stacked segments, in a bin or not"""
+        return self.buf[:, :, 1]
+
+    @property
+    def counts(self):
+        """(S, nz, nv) n_a: counted pixels per variance bin"""
+        return self._part(0)
+
+    def out_of_range(self):
+        """(S, nz) 1 - sum_a n_a / n_used: the fraction of used pixels that no bin holds or the cut on |d| removed; NaN without
+        pixels"""
+        f = 1.0 - self.counts.sum(-1) / self.n_pixels
+        return torch.where(self.n_pixels > 0.0, f, torch.full_like(f, float("nan")))
+
+    @property
+    def v_mean(self):
+        """(S, nz, nv) mean pipeline variance <v> of a bin's pixels (NaN in an empty bin)"""
+        return self._part(1) / self.counts
+
+    @property
+    def mean_delta(self):
+        """(S, nz, nv) <d> of a bin's pixels"""
+        return self._part(2) / self.counts
+
+    @property
+    def var_delta(self):
+        """(S, nz, nv) the variance function <d^2> - <d>^2 of a bin's pixels (NaN in an empty bin)"""
+        m = self.mean_delta
+        return self._part(3) / self.counts - m * m
+
+    @property
+    def var_err(self):
+        """(S, nz, nv) standard error of ``var_delta`` from the fourth moment: sqrt((<d^4> - <d^2>^2) / n_a)"""
+        n = self.counts
+        m2 = self._part(3) / n
+        return torch.sqrt(((self._part(4) / n - m2 * m2) / n).clamp_min(0.0))
+
+    def fit(self, min_count=100, epsilon=False):
+        """The weighted least squares fit var_delta = eta v_mean + sigma2_lss (+ eps / v_mean with ``epsilon``) per draw and z-bin,
+        in closed form in float64 on the stack's device: over the bins with n_a >= ``min_count`` and var_err > 0, weights
+        1 / var_err^2.  The normal matrix is scaled to a unit diagonal and inverted by cofactors.  Returns a ``VarianceFit`` of
+        (S, nz) tensors: ``eta``, ``sigma2_lss``, ``eps`` (None without ``epsilon``), ``cov`` (S, nz, P, P) of the P parameters in that
+        order, ``chi2``, ``ndof`` = n_bins - P and ``n_bins``, the usable bins.  A cell with fewer usable bins than parameters, or
+        whose scaled normal matrix has a determinant below 64 x 2^-52 (singular), gets NaN.  ``sigma2_lss`` is the number
+        ``QFA.xi`` / ``QFA.flux_correlation`` take as their one scalar ``sigma2_lss``."""
+        P = 3 if epsilon else 2
+        x, y, e = self.v_mean, self.var_delta, self.var_err
+        ok = (self.counts >= float(min_count)) & (e > 0.0) & torch.isfinite(e) & torch.isfinite(y) & (x > 0.0)
+        zero, one = torch.zeros_like(x), torch.ones_like(x)
+        w = torch.where(ok, 1.0 / torch.where(ok, e * e, one), zero)
+        xs, ys = torch.where(ok, x, one), torch.where(ok, y, zero)
+        cols = [xs, one] + ([1.0 / xs] if epsilon else [])
+        f = torch.stack(cols, -1)                                 # (S, nz, nv, P)
+        N = torch.einsum("szc,szcp,szcq->szpq", w, f, f)
+        r = torch.einsum("szc,szcp,szc->szp", w, f, ys)
+        n_bins = ok.sum(-1).to(torch.float64)
+        sc = torch.sqrt(torch.diagonal(N, dim1=2, dim2=3))        # (S, nz, P)
+        good = (n_bins >= P) & (sc > 0.0).all(-1)
+        sc = torch.where(good[..., None], sc, torch.ones_like(sc))
+        eye = torch.eye(P, dtype=torch.float64, device=self.buf.device).expand_as(N)
+        Ns = torch.where(good[..., None, None], N / (sc[..., :, None] * sc[..., None, :]), eye)
+        inv, det = _sym_inverse(Ns)
+        good = good & (det > 64.0 * 2.0 ** -52)
+        par = torch.einsum("szpq,szq->szp", inv, r / sc) / sc
+        cov = inv / (sc[..., :, None] * sc[..., None, :])
+        res = ys - torch.einsum("szcp,szp->szc", f, par)
+        chi2 = (w * res * res).sum(-1)
+        nan = torch.full_like(n_bins, float("nan"))
+        par = torch.where(good[..., None], par, nan[..., None])
+        cov = torch.where(good[..., None, None], cov, nan[..., None, None])
+        chi2 = torch.where(good, chi2, nan)
+        return VarianceFit(par[..., 0], par[..., 1], par[..., 2] if epsilon else None, cov, chi2, n_bins - P, n_bins)
+
+    def _per_draw(self):
+        return self.var_delta
+
+    def std_over_draws(self, min_count=100):
+        """((nz,), (nz,)) standard deviation of ``fit(min_count)``'s eta and sigma2_lss over the S draws: the continuum posterior's
+        error bar on both"""
+        if self.S < 2:
+            raise QFAHipError(f"VarianceStack.std_over_draws: needs more than one draw of the continuum (S = {self.S})")
+        ft = self.fit(min_count=min_count)
+        return ft.eta.std(0, unbiased=True), ft.sigma2_lss.std(0, unbiased=True)

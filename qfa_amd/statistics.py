@@ -1,6 +1,7 @@
 """The forest statistics of ``QFA``: transmission and its redshift-binned stack (``forest`` / ``mean_transmission``), the 1D flux
 power spectrum (``p1d`` / ``flux_power``), its band powers (``p1d_bands`` / ``band_power``), the line-of-sight correlation function
-(``xi`` / ``flux_correlation``) and the flux PDF (``flux_pdf_segments`` / ``flux_pdf``).  ``ForestStatistics`` is a plain
+(``xi`` / ``flux_correlation``), the flux PDF (``flux_pdf_segments`` / ``flux_pdf``) and the variance function
+(``variance_segments`` / ``variance_function``).  ``ForestStatistics`` is a plain
 base class of ``qfa_amd.model.QFA`` and uses the model's plumbing (``_batch_struct*``, ``_scratch``, ``predict``, ``sample_latent``,
 ``_loader_slices``) as any other method of it does; every call goes through the C-ABI in ``include/qfa_hip.h``."""
 from __future__ import annotations
@@ -13,7 +14,7 @@ import torch
 
 from . import _lib
 from ._lib import QFAHipError, _ptr
-from .stacks import ForestStack, P1DBandStack, P1DStack, PDFStack, XiStack, _band_map, _check_segments, _edges, _mode_k, _window2
+from .stacks import ForestStack, P1DBandStack, P1DStack, PDFStack, VarianceStack, XiStack, _band_map, _check_segments, _edges, _mode_k, _window2
 
 f32 = torch.float32
 
@@ -358,6 +359,34 @@ class ForestStatistics(object):
         call((_lib.F_PDF_RELATIVE if relative else 0) | (_lib.F_PDF_CLAMP if clamp else 0), hist)
         return hist, stack
 
+    def variance_segments(self, trans, ivar, *, zabs=None, zfac=None, batch=None, tbar, tbar_bins=None, seg_len, n_segments,
+                          pixel_start=0, min_used, e_lo, n_oct, sub=1, d_max=None, bins=None, stack=None, return_segments=False):
+        """The moments of delta_F of forest segments in bins of the pipeline's noise variance, and their (v-bin, z) stack
+        (qfa_variance_f32; the contract is in include/qfa_hip.h).  The inputs and keywords of ``p1d``: the same pixels are used, the
+        same segments valid and binned in z.  The nv = ``n_oct`` << ``sub`` (<= 64) bins of v = 1 / (ivar tbar^2) are defined on the
+        bits of the float32 v: 2^sub bins per octave from 2^``e_lo`` on (``VarianceStack.v_edges``).  A used pixel of a valid segment
+        is counted when its v falls in a bin and |d| <= ``d_max`` (None: only non-finite d are cut).  ``bins`` = (z0, dz, nz) asks for
+        the stack, ``stack``: a ``VarianceStack`` to ADD to.  Returns (moments (B, S, n_segments, 5, nv) float64 = [n_a | sum v |
+        sum d | sum d^2 | sum d^4], or None without ``return_segments``; the ``VarianceStack``, or None)."""
+        inp = self._p1d_inputs("variance_segments", bins is not None or stack is not None or return_segments, trans, ivar, zabs, zfac,
+                               batch, tbar, tbar_bins)
+        B, S, dev = inp[0], inp[1], self.device
+        L, nseg = int(seg_len), int(n_segments)
+        try:
+            want = VarianceStack.zeros(1, 0.0, 1.0, 1, max(1, min(L, 4096)), e_lo, n_oct, sub, d_max).var_bins
+        except QFAHipError:
+            raise QFAHipError(f"variance_segments: e_lo = {e_lo}, n_oct = {n_oct}, sub = {sub}, d_max = {d_max}") from None
+        nv = want[1] << want[2]
+        stack, call = self._segment_call(
+            "variance_segments", "qfa_variance", inp, trans, ivar, L, nseg, pixel_start, min_used, bins, stack, cls=VarianceStack,
+            same=lambda st: st.var_bins == want,
+            zeros=lambda: VarianceStack.zeros(S, bins[0], bins[1], bins[2], L, e_lo, n_oct, sub, d_max, dev),
+            expected=f" and segments of {L} pixels on the same z-bins, variance bins and d_max",
+            own=lambda st: ((nv,), f" nv={nv}", _lib.VarParams(want[0], want[1], want[2], want[3])))
+        moments = torch.empty((B, S, nseg, 5, nv), dtype=torch.float64, device=dev) if return_segments else None
+        call(0, moments)
+        return moments, stack
+
     def flux_power(self, dataloader, z_min, z_max, n_zbins, *, n_segments=3, seg_len=None, min_used_frac=0.75, tbar=None,
                    tbar_nbins=64, n_samples=0, seed=0, batch_size=4096, cont_min=0.0, dv=None):
         """The 1D flux power spectrum of a whole dataloader: a ``P1DStack`` of S = max(1, n_samples) draws over ``n_zbins`` bins of
@@ -423,6 +452,28 @@ class ForestStatistics(object):
         return self._power_of_loader("flux_pdf", dataloader, z_min, z_max, n_zbins, n_segments, seg_len, min_used_frac, tbar,
                                      tbar_nbins, n_samples, seed, batch_size, cont_min, None,
                                      _LoaderStat(zeros, self.flux_pdf_segments, pdf, needs_dv=False))
+
+    def variance_function(self, dataloader, z_min, z_max, n_zbins, *, e_lo=-12, n_oct=14, sub=1, d_max=None, n_segments=3, seg_len=None,
+                          min_used_frac=0.75, tbar=None, tbar_nbins=64, n_samples=0, seed=0, batch_size=4096, cont_min=0.0):
+        """The variance function of a whole dataloader: a ``VarianceStack`` of S = max(1, n_samples) draws over ``n_zbins`` bins of
+        [z_min, z_max) and ``n_oct`` << ``sub`` bins of the pipeline's noise variance from 2^``e_lo`` on (``d_max``: see
+        ``variance_segments``).  Everything else is ``flux_power``'s: the same segments, mean transmission, draws and loop over the
+        loader, with ``variance_segments`` in the place of ``p1d``.  ``VarianceStack.fit()`` then gives eta(z), the correction to
+        the pipeline's noise, and sigma2_lss(z), the intrinsic variance of the forest: ``fit().sigma2_lss`` is the number
+        ``flux_correlation(sigma2_lss=...)`` and ``xi`` take -- as ONE scalar per call (of the z-bin of interest, or a mean over
+        the bins); ``std_over_draws`` is the continuum's error bar on both.  The sums of a slice are formed in chunks of a fixed
+        number of segments, so the result depends on ``batch_size`` only through the rounding of float64 sums.  Under data
+        parallelism the sums are all-reduced over the model's group."""
+        var = {"e_lo": int(e_lo), "n_oct": int(n_oct), "sub": int(sub), "d_max": d_max}
+        try:
+            VarianceStack.zeros(1, 0.0, 1.0, 1, 1, **var)
+        except QFAHipError:
+            raise QFAHipError(f"variance_function: e_lo = {e_lo}, n_oct = {n_oct}, sub = {sub}, d_max = {d_max}") from None
+        zeros = lambda S, z0, dz, nz, L, dv: VarianceStack.zeros(S, z0, dz, nz, L, device=self.device, **var)
+        # (dv None: the variance function needs it for the range of its own <T> alone)
+        return self._power_of_loader("variance_function", dataloader, z_min, z_max, n_zbins, n_segments, seg_len, min_used_frac, tbar,
+                                     tbar_nbins, n_samples, seed, batch_size, cont_min, None,
+                                     _LoaderStat(zeros, self.variance_segments, var, needs_dv=False))
 
     def _power_of_loader(self, what, dataloader, z_min, z_max, n_zbins, n_segments, seg_len, min_used_frac, tbar, tbar_nbins,
                          n_samples, seed, batch_size, cont_min, dv, stat):
