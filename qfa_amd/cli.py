@@ -86,8 +86,18 @@ def load_model_file(model, path, cfg, optimizer=None):
     return False
 
 
+def refuse(message, check, *args, **kw):
+    """the command line's ValueError for what a stack's own parameter check (qfa_amd/stacks.py) refuses: the bounds are written there"""
+    from ._lib import QFAHipError
+    try:
+        check(*args, **kw)
+    except QFAHipError:
+        raise ValueError(message) from None
+
+
 def main(argv=None):
     from .config import get_config
+    from .stacks import P1DBandStack, PDFStack, VarianceStack, XiStack, _edges
     args = build_parser().parse_args(argv)
     cfg = get_config(args)
     assert cfg.TYPE in ("train", "predict"), "TYPE must be in ['train', 'predict']!"
@@ -95,42 +105,36 @@ def main(argv=None):
         raise ValueError("MODEL.P1D_SEGMENTS > 0 needs MODEL.FOREST_NBINS > 0 (the mean transmission the contrast is formed with)")
     if cfg.TYPE == "predict" and int(cfg.MODEL.P1D_NBANDS) > 0 and int(cfg.MODEL.P1D_SEGMENTS) <= 0:
         raise ValueError("MODEL.P1D_NBANDS > 0 needs MODEL.P1D_SEGMENTS > 0 (the segments whose power is binned)")
-    if cfg.TYPE == "predict" and not 0 <= int(cfg.MODEL.P1D_NBANDS) <= 64:
-        raise ValueError("MODEL.P1D_NBANDS must lie in 0 .. 64")
-    if cfg.TYPE == "predict" and int(cfg.MODEL.XI_NLAGS) != 0:
-        if int(cfg.MODEL.XI_NLAGS) < 0 or int(cfg.MODEL.P1D_SEGMENTS) <= 0:
+    M = cfg.MODEL
+    if cfg.TYPE == "predict" and int(M.P1D_NBANDS) != 0:
+        refuse("MODEL.P1D_NBANDS must lie in 0 .. 64", _edges, range(int(M.P1D_NBANDS) + 1))
+    if cfg.TYPE == "predict" and int(M.XI_NLAGS) != 0:
+        if int(M.XI_NLAGS) < 0 or int(M.P1D_SEGMENTS) <= 0:
             raise ValueError("MODEL.XI_NLAGS > 0 needs MODEL.P1D_SEGMENTS > 0 (the segments whose pixel pairs are summed)")
         import numpy as np
         from . import io
         wav = io.wavelength_grid(cfg.DATA.LAMMIN, cfg.DATA.LAMMAX, cfg.DATA.LOGLAM_DELTA)
-        seg_len = int(np.sum(wav < 1215.67)) // int(cfg.MODEL.P1D_SEGMENTS)          # (the dataloader's Nb, flux_power's segments)
-        if int(cfg.MODEL.XI_NLAGS) > seg_len:
-            raise ValueError(f"MODEL.XI_NLAGS = {int(cfg.MODEL.XI_NLAGS)} exceeds the segment length {seg_len}")
-        if not float(cfg.MODEL.XI_SIGMA2_LSS) >= 0.0 or float(cfg.MODEL.XI_SIGMA2_LSS) == float("inf"):
+        seg_len = int(np.sum(wav < 1215.67)) // int(M.P1D_SEGMENTS)                  # (the dataloader's Nb, flux_power's segments)
+        refuse(f"MODEL.XI_NLAGS = {int(M.XI_NLAGS)} exceeds the segment length {seg_len}", XiStack.lag_params, seg_len, M.XI_NLAGS)
+        if not float(M.XI_SIGMA2_LSS) >= 0.0 or float(M.XI_SIGMA2_LSS) == float("inf"):
             raise ValueError("MODEL.XI_SIGMA2_LSS must be finite and >= 0")
-    if cfg.TYPE == "predict" and int(cfg.MODEL.PDF_NBINS) != 0:
-        if not 1 <= int(cfg.MODEL.PDF_NBINS) <= 64:
-            raise ValueError("MODEL.PDF_NBINS must lie in 0 .. 64")
-        if int(cfg.MODEL.P1D_SEGMENTS) <= 0:
+    if cfg.TYPE == "predict" and int(M.PDF_NBINS) != 0:
+        refuse("MODEL.PDF_NBINS must lie in 0 .. 64", PDFStack.flux_params, 0.0, 1.0, M.PDF_NBINS)
+        if int(M.P1D_SEGMENTS) <= 0:
             raise ValueError("MODEL.PDF_NBINS > 0 needs MODEL.P1D_SEGMENTS > 0 (the segments whose pixels are counted)")
-        if not float(cfg.MODEL.PDF_TMAX) > float(cfg.MODEL.PDF_TMIN) or abs(float(cfg.MODEL.PDF_TMAX)) == float("inf") or \
-                abs(float(cfg.MODEL.PDF_TMIN)) == float("inf"):
-            raise ValueError("MODEL.PDF_TMAX must be finite and above MODEL.PDF_TMIN")
-        if not float(cfg.MODEL.PDF_IVAR_MIN) >= 0.0 or float(cfg.MODEL.PDF_IVAR_MIN) == float("inf"):
-            raise ValueError("MODEL.PDF_IVAR_MIN must be finite and >= 0")
-    if cfg.TYPE == "predict" and int(cfg.MODEL.VAR_NOCT) != 0:
-        noct, elo, sub = int(cfg.MODEL.VAR_NOCT), int(cfg.MODEL.VAR_ELO), int(cfg.MODEL.VAR_SUB)
-        if not 0 <= sub <= 4:
-            raise ValueError("MODEL.VAR_SUB must lie in 0 .. 4")
-        if not 1 <= noct << sub <= 64:
-            raise ValueError("MODEL.VAR_NOCT << MODEL.VAR_SUB must lie in 1 .. 64 (0 = off)")
-        if int(cfg.MODEL.P1D_SEGMENTS) <= 0:
+        refuse("MODEL.PDF_TMAX must be finite and above MODEL.PDF_TMIN", PDFStack.flux_params, M.PDF_TMIN,
+               (float(M.PDF_TMAX) - float(M.PDF_TMIN)) / int(M.PDF_NBINS), M.PDF_NBINS)
+        refuse("MODEL.PDF_IVAR_MIN must be finite and >= 0", PDFStack.flux_params, 0.0, 1.0, 1, ivar_min=M.PDF_IVAR_MIN)
+    if cfg.TYPE == "predict" and int(M.VAR_NOCT) != 0:
+        refuse("MODEL.VAR_SUB must lie in 0 .. 4", VarianceStack.var_params, 0, 1, M.VAR_SUB)
+        refuse("MODEL.VAR_NOCT << MODEL.VAR_SUB must lie in 1 .. 64 (0 = off)", VarianceStack.var_params, 0, M.VAR_NOCT, M.VAR_SUB)
+        if int(M.P1D_SEGMENTS) <= 0:
             raise ValueError("MODEL.VAR_NOCT > 0 needs MODEL.P1D_SEGMENTS > 0 (the segments whose pixels are binned)")
-        if elo < -126 or elo + noct > 127:
-            raise ValueError("MODEL.VAR_ELO must be >= -126 and MODEL.VAR_ELO + MODEL.VAR_NOCT <= 127")
-        if not float(cfg.MODEL.VAR_DMAX) >= 0.0 or float(cfg.MODEL.VAR_DMAX) == float("inf"):
+        refuse("MODEL.VAR_ELO must be >= -126 and MODEL.VAR_ELO + MODEL.VAR_NOCT <= 127", VarianceStack.var_params, M.VAR_ELO, M.VAR_NOCT,
+               M.VAR_SUB)
+        if not float(M.VAR_DMAX) >= 0.0 or float(M.VAR_DMAX) == float("inf"):
             raise ValueError("MODEL.VAR_DMAX must be finite and >= 0 (0 = no cut)")
-        if int(cfg.MODEL.VAR_MIN_COUNT) < 1:
+        if int(M.VAR_MIN_COUNT) < 1:
             raise ValueError("MODEL.VAR_MIN_COUNT must be >= 1")
     os.makedirs(cfg.DATA.OUTPUT_DIR, exist_ok=True)
     with open(os.path.join(cfg.DATA.OUTPUT_DIR, "config.yaml"), "w") as f:
@@ -171,76 +175,34 @@ def main(argv=None):
         model.predict_to_npz(dataloader, os.path.join(cfg.DATA.OUTPUT_DIR, "predict"),
                              n_samples=int(cfg.MODEL.N_SAMPLES), seed=int(cfg.MODEL.SAMPLE_SEED),
                              n_replicates=int(cfg.MODEL.N_REPLICATES), forest=bool(cfg.MODEL.FOREST))
-        if int(cfg.MODEL.FOREST_NBINS) > 0:
+        if int(M.FOREST_NBINS) > 0:
             import numpy as np
-            st = model.mean_transmission(dataloader, float(cfg.MODEL.FOREST_ZMIN), float(cfg.MODEL.FOREST_ZMAX),
-                                         int(cfg.MODEL.FOREST_NBINS), n_samples=int(cfg.MODEL.N_SAMPLES),
-                                         seed=int(cfg.MODEL.SAMPLE_SEED))
-            np.savez(os.path.join(cfg.DATA.OUTPUT_DIR, "mean_transmission.npz"), z_centers=st.z_centers.cpu().numpy(),
-                     z_edges=st.z_edges.cpu().numpy(), mean=st.mean.cpu().numpy(), var=st.var.cpu().numpy(), n=st.n.cpu().numpy(),
-                     tau_eff=st.tau_eff.cpu().numpy(), sums=st.buf.cpu().numpy())
-        if int(cfg.MODEL.P1D_SEGMENTS) > 0:
+            save = lambda name, stack, **kw: np.savez(os.path.join(cfg.DATA.OUTPUT_DIR, name), **stack.arrays(**kw))
+            draws = dict(n_samples=int(M.N_SAMPLES), seed=int(M.SAMPLE_SEED))
+            st = model.mean_transmission(dataloader, float(M.FOREST_ZMIN), float(M.FOREST_ZMAX), int(M.FOREST_NBINS), **draws)
+            save("mean_transmission.npz", st)
+        if int(M.P1D_SEGMENTS) > 0:
             # the contrast is formed with the very stack mean_transmission.npz holds: pixels outside [FOREST_ZMIN, FOREST_ZMAX) are
             # unused, and a segment that loses too many of them to the edges is left out (P1D_MIN_USED_FRAC)
-            ps = model.flux_power(dataloader, float(cfg.MODEL.FOREST_ZMIN), float(cfg.MODEL.FOREST_ZMAX), int(cfg.MODEL.P1D_NZBINS),
-                                  n_segments=int(cfg.MODEL.P1D_SEGMENTS), min_used_frac=float(cfg.MODEL.P1D_MIN_USED_FRAC),
-                                  tbar=st, n_samples=int(cfg.MODEL.N_SAMPLES), seed=int(cfg.MODEL.SAMPLE_SEED))
-            np.savez(os.path.join(cfg.DATA.OUTPUT_DIR, "flux_power.npz"), k=ps.k.cpu().numpy(), z_centers=ps.z_centers.cpu().numpy(),
-                     z_edges=ps.z_edges.cpu().numpy(), power=ps.power().cpu().numpy(), err=ps.err().cpu().numpy(),
-                     power_raw=ps.power_raw.cpu().numpy(), noise=ps.noise.cpu().numpy(), n=ps.n.cpu().numpy(),
-                     seg_len=ps.L, dv=ps.dv, sums=ps.buf.cpu().numpy())
-            if int(cfg.MODEL.P1D_NBANDS) > 0:
-                from .model import P1DBandStack
-                bs = model.band_power(dataloader, float(cfg.MODEL.FOREST_ZMIN), float(cfg.MODEL.FOREST_ZMAX), int(cfg.MODEL.P1D_NZBINS),
-                                      P1DBandStack.linear_k_edges(ps.L, ps.dv, int(cfg.MODEL.P1D_NBANDS)),
-                                      n_segments=int(cfg.MODEL.P1D_SEGMENTS), min_used_frac=float(cfg.MODEL.P1D_MIN_USED_FRAC),
-                                      tbar=st, n_samples=int(cfg.MODEL.N_SAMPLES), seed=int(cfg.MODEL.SAMPLE_SEED))
-                out = dict(k_edges=bs.k_edges.cpu().numpy(), k_centers=bs.k_centers.cpu().numpy(), z_edges=bs.z_edges.cpu().numpy(),
-                           n=bs.n.cpu().numpy(), mean=bs.mean.cpu().numpy(), cov=bs.cov.cpu().numpy())
-                if bs.S > 1:
-                    out["cov_over_draws"] = bs.cov_over_draws.cpu().numpy()
-                np.savez(os.path.join(cfg.DATA.OUTPUT_DIR, "flux_power_bands.npz"), **out)
-            if int(cfg.MODEL.XI_NLAGS) > 0:
-                xs = model.flux_correlation(dataloader, float(cfg.MODEL.FOREST_ZMIN), float(cfg.MODEL.FOREST_ZMAX),
-                                            int(cfg.MODEL.P1D_NZBINS), int(cfg.MODEL.XI_NLAGS), n_segments=int(cfg.MODEL.P1D_SEGMENTS),
-                                            min_used_frac=float(cfg.MODEL.P1D_MIN_USED_FRAC), tbar=st, n_samples=int(cfg.MODEL.N_SAMPLES),
-                                            seed=int(cfg.MODEL.SAMPLE_SEED), sigma2_lss=float(cfg.MODEL.XI_SIGMA2_LSS))
-                np.savez(os.path.join(cfg.DATA.OUTPUT_DIR, "flux_correlation.npz"), lags_kms=xs.lags_kms.cpu().numpy(),
-                         z_centers=xs.z_centers.cpu().numpy(), z_edges=xs.z_edges.cpu().numpy(), xi=xs.xi().cpu().numpy(),
-                         xi_raw=xs.xi(subtract_noise=False).cpu().numpy(), err=xs.err().cpu().numpy(), n=xs.n.cpu().numpy(),
-                         sum_w=xs.sum_w.cpu().numpy(), seg_len=xs.L, dv=xs.dv, sums=xs.buf.cpu().numpy())
-            if int(cfg.MODEL.PDF_NBINS) > 0:
-                fs = model.flux_pdf(dataloader, float(cfg.MODEL.FOREST_ZMIN), float(cfg.MODEL.FOREST_ZMAX), int(cfg.MODEL.P1D_NZBINS),
-                                    int(cfg.MODEL.PDF_NBINS), t_min=float(cfg.MODEL.PDF_TMIN), t_max=float(cfg.MODEL.PDF_TMAX),
-                                    relative=bool(cfg.MODEL.PDF_RELATIVE), clamp=bool(cfg.MODEL.PDF_CLAMP),
-                                    ivar_min=float(cfg.MODEL.PDF_IVAR_MIN), n_segments=int(cfg.MODEL.P1D_SEGMENTS),
-                                    min_used_frac=float(cfg.MODEL.P1D_MIN_USED_FRAC), tbar=st, n_samples=int(cfg.MODEL.N_SAMPLES),
-                                    seed=int(cfg.MODEL.SAMPLE_SEED))
-                out = dict(z=fs.z_centers.cpu().numpy(), t_edges=fs.t_edges.cpu().numpy(), pdf=fs.pdf().cpu().numpy(),
-                           err=fs.err().cpu().numpy(), cov=fs.cov().cpu().numpy(), counts=fs.counts.cpu().numpy(),
-                           n_segments=fs.n_segments.cpu().numpy(), out_of_range=fs.out_of_range().cpu().numpy())
-                if fs.S > 1:
-                    out["std_over_draws"] = fs.std_over_draws.cpu().numpy()
-                    out["total_cov"] = fs.total_cov.cpu().numpy()
-                np.savez(os.path.join(cfg.DATA.OUTPUT_DIR, "flux_pdf.npz"), **out)
-            if int(cfg.MODEL.VAR_NOCT) > 0:
-                vs = model.variance_function(dataloader, float(cfg.MODEL.FOREST_ZMIN), float(cfg.MODEL.FOREST_ZMAX), int(cfg.MODEL.P1D_NZBINS),
-                                             e_lo=int(cfg.MODEL.VAR_ELO), n_oct=int(cfg.MODEL.VAR_NOCT), sub=int(cfg.MODEL.VAR_SUB),
-                                             d_max=float(cfg.MODEL.VAR_DMAX) if float(cfg.MODEL.VAR_DMAX) > 0.0 else None,
-                                             n_segments=int(cfg.MODEL.P1D_SEGMENTS), min_used_frac=float(cfg.MODEL.P1D_MIN_USED_FRAC),
-                                             tbar=st, n_samples=int(cfg.MODEL.N_SAMPLES), seed=int(cfg.MODEL.SAMPLE_SEED))
-                ft = vs.fit(min_count=int(cfg.MODEL.VAR_MIN_COUNT))
-                out = dict(z=vs.z_centers.cpu().numpy(), z_edges=vs.z_edges.cpu().numpy(), v_edges=vs.v_edges.cpu().numpy(),
-                           v_mean=vs.v_mean.cpu().numpy(), var_delta=vs.var_delta.cpu().numpy(), var_err=vs.var_err.cpu().numpy(),
-                           mean_delta=vs.mean_delta.cpu().numpy(), counts=vs.counts.cpu().numpy(),
-                           n_segments=vs.n_segments.cpu().numpy(), n_pixels=vs.n_pixels.cpu().numpy(),
-                           out_of_range=vs.out_of_range().cpu().numpy(), seg_len=vs.L, sums=vs.buf.cpu().numpy(),
-                           eta=ft.eta.cpu().numpy(), sigma2_lss=ft.sigma2_lss.cpu().numpy(), cov=ft.cov.cpu().numpy(),
-                           chi2=ft.chi2.cpu().numpy(), ndof=ft.ndof.cpu().numpy(), n_bins=ft.n_bins.cpu().numpy())
-                if vs.S > 1:
-                    out["eta_std_over_draws"], out["sigma2_lss_std_over_draws"] = (
-                        t.cpu().numpy() for t in vs.std_over_draws(min_count=int(cfg.MODEL.VAR_MIN_COUNT)))
-                np.savez(os.path.join(cfg.DATA.OUTPUT_DIR, "variance_function.npz"), **out)
+            shared = dict(n_segments=int(M.P1D_SEGMENTS), min_used_frac=float(M.P1D_MIN_USED_FRAC), tbar=st, **draws)
+            done = []                                           # (flux_power's stack first: the bands lie on its segments and dv)
+            # (config switch, loader method, its own keywords, arrays()'s keywords, file): one row per statistic
+            for switch, method, own, export, name in (
+                    (M.P1D_SEGMENTS, model.flux_power, dict, {}, "flux_power.npz"),
+                    (M.P1D_NBANDS, model.band_power,
+                     lambda: dict(k_edges=P1DBandStack.linear_k_edges(done[0].L, done[0].dv, int(M.P1D_NBANDS))), {}, "flux_power_bands.npz"),
+                    (M.XI_NLAGS, model.flux_correlation, lambda: dict(n_lags=int(M.XI_NLAGS), sigma2_lss=float(M.XI_SIGMA2_LSS)), {},
+                     "flux_correlation.npz"),
+                    (M.PDF_NBINS, model.flux_pdf,
+                     lambda: dict(n_tbins=int(M.PDF_NBINS), t_min=float(M.PDF_TMIN), t_max=float(M.PDF_TMAX), relative=bool(M.PDF_RELATIVE),
+                                  clamp=bool(M.PDF_CLAMP), ivar_min=float(M.PDF_IVAR_MIN)), {}, "flux_pdf.npz"),
+                    (M.VAR_NOCT, model.variance_function,
+                     lambda: dict(e_lo=int(M.VAR_ELO), n_oct=int(M.VAR_NOCT), sub=int(M.VAR_SUB),
+                                  d_max=float(M.VAR_DMAX) if float(M.VAR_DMAX) > 0.0 else None),
+                     dict(min_count=int(M.VAR_MIN_COUNT)), "variance_function.npz")):
+                if int(switch) > 0:
+                    done.append(method(dataloader, float(M.FOREST_ZMIN), float(M.FOREST_ZMAX), int(M.P1D_NZBINS), **own(), **shared))
+                    save(name, done[-1], **export)
         print(f"Finish predicting {len(dataloader)} spectra in {time.time() - ts} seconds...")
     return 0
 

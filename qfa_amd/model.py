@@ -200,38 +200,34 @@ class QFA(ForestStatistics):
             setattr(ps, k, _lib.require_device_tensor(t, f32, k).value)
         return ps
 
-    def _batch_struct(self, delta, error, zabs, mask, zfac=None, allow_no_mask=False, auto_factor=True):
-        """``zfac`` = (zq1 (B,), pix_ratio (Nb,)) float32 device tensors: the factored-z input form of include/qfa_hip.h
-        (1 + zabs[s][i] = zq1[s] pix_ratio[i], reference QFA/dataloader.py:102).  Default: the ``zfac`` attribute a
-        DeviceDataloader attaches to the zabs tensors it builds; None = the kernels read zabs."""
+    def _redshift_form(self, bs, keep, B, zabs, zfac=None, auto_factor=False, also_zabs=False):
+        """The one rule for the redshift of the blue pixels of a qfa_batch_t: fills ``bs.zabs`` / ``bs.zq1`` / ``bs.pix_ratio`` for ``B``
+        spectra, appends the float32 contiguous tensors they point into to ``keep`` and returns the converted zabs (or None).
+        ``zfac`` = (zq1 (B,), pix_ratio (Nb,)): the factored-z input form of include/qfa_hip.h (1 + zabs[s][i] = zq1[s] pix_ratio[i],
+        reference QFA/dataloader.py:102); default: the ``zfac`` attribute a DeviceDataloader attaches to the zabs tensors it builds.
+        The pair is used when the model reads factored z at all (``use_factored_z``, no custom tau callable); else, or without one, the
+        kernels read zabs.  ``auto_factor``: a plain zabs may be swapped for factors derived from it (`_auto_zfac`) -- off for the
+        forest statistics, whose bins are defined bit for bit by z.  ``also_zabs``: zabs is passed on next to the pair (the training
+        and prediction calls; the statistics pass one form only)."""
         if zfac is None:
             zfac = getattr(zabs, "zfac", None)
-        if (zfac is None and zabs is not None and auto_factor and self.auto_factor_zabs and self.use_factored_z and self.Nb > 0
-                and self._tau_callable is None):
+        usable = self.Nb > 0 and self._tau_callable is None and self.use_factored_z
+        if zfac is None and zabs is not None and auto_factor and self.auto_factor_zabs and usable:
             zfac = self._auto_zfac(zabs)
-        if mask is None and not allow_no_mask:
-            raise _lib.QFAHipError("mask is None: expected a torch.bool tensor (reference model.py:124)")
-        if mask is not None and mask.dtype != torch.bool:            # (None: sample_spectra only -- every pixel is used)
-            raise _lib.QFAHipError(f"mask: dtype {mask.dtype}, expected torch.bool (reference model.py:124)")
-        bs = _lib.Batch()
-        delta = delta if (delta.dtype == f32 and delta.is_contiguous()) else delta.to(f32).contiguous()
-        error = error if (error.dtype == f32 and error.is_contiguous()) else error.to(f32).contiguous()
-        if zabs is not None:
+        if not usable:
+            zfac = None
+        bs.zabs = bs.zq1 = bs.pix_ratio = None
+        if zabs is not None and (zfac is None or also_zabs):
+            if zfac is None and tuple(zabs.shape) != (B, self.Nb):
+                raise _lib.QFAHipError(f"zabs: shape {tuple(zabs.shape)}, expected ({B}, {self.Nb})")
             zabs = zabs if (zabs.dtype == f32 and zabs.is_contiguous()) else zabs.to(f32).contiguous()
-        if mask is not None:
-            mask = mask if mask.is_contiguous() else mask.contiguous()
-        keep = [delta, error, zabs, mask]
-        bs.delta = _lib.require_device_tensor(delta, f32, "delta").value
-        bs.error = _lib.require_device_tensor(error, f32, "error").value
-        bs.zabs = _lib.require_device_tensor(zabs, f32, "zabs").value if (self.Nb > 0 and zabs is not None) else None
-        bs.mask = _lib.require_device_tensor(mask, torch.bool, "mask").value if mask is not None else None
-        bs.A_blue = None
-        bs.zq1 = None
-        bs.pix_ratio = None
-        if zfac is not None and self.Nb > 0 and self._tau_callable is None and self.use_factored_z:
+            keep.append(zabs)
+            if self.Nb > 0:
+                bs.zabs = _lib.require_device_tensor(zabs, f32, "zabs").value
+        if zfac is not None:
             zq1, ratio = zfac
-            if tuple(zq1.shape) != (delta.shape[0],) or tuple(ratio.shape) != (self.Nb,):
-                raise _lib.QFAHipError(f"zfac shapes {tuple(zq1.shape)}, {tuple(ratio.shape)}: expected ({delta.shape[0]},), ({self.Nb},)")
+            if tuple(zq1.shape) != (B,) or tuple(ratio.shape) != (self.Nb,):
+                raise _lib.QFAHipError(f"zfac shapes {tuple(zq1.shape)}, {tuple(ratio.shape)}: expected ({B},), ({self.Nb},)")
             zq1 = zq1 if (zq1.dtype == f32 and zq1.is_contiguous()) else zq1.to(f32).contiguous()
             ratio = ratio if (ratio.dtype == f32 and ratio.is_contiguous()) else ratio.to(f32).contiguous()
             keep += [zq1, ratio]
@@ -239,6 +235,25 @@ class QFA(ForestStatistics):
             bs.pix_ratio = _lib.require_device_tensor(ratio, f32, "pix_ratio").value
         elif zabs is None and self.Nb > 0:
             raise _lib.QFAHipError("zabs is None and no usable zfac = (zq1, pix_ratio) was given")
+        return zabs
+
+    def _batch_struct(self, delta, error, zabs, mask, zfac=None, allow_no_mask=False, auto_factor=True):
+        """qfa_batch_t of the 4-tensor form and the tensors it points into; the redshift by `_redshift_form`"""
+        if mask is None and not allow_no_mask:
+            raise _lib.QFAHipError("mask is None: expected a torch.bool tensor (reference model.py:124)")
+        if mask is not None and mask.dtype != torch.bool:            # (None: sample_spectra only -- every pixel is used)
+            raise _lib.QFAHipError(f"mask: dtype {mask.dtype}, expected torch.bool (reference model.py:124)")
+        bs = _lib.Batch()
+        delta = delta if (delta.dtype == f32 and delta.is_contiguous()) else delta.to(f32).contiguous()
+        error = error if (error.dtype == f32 and error.is_contiguous()) else error.to(f32).contiguous()
+        if mask is not None:
+            mask = mask if mask.is_contiguous() else mask.contiguous()
+        keep = [delta, error, mask]
+        bs.delta = _lib.require_device_tensor(delta, f32, "delta").value
+        bs.error = _lib.require_device_tensor(error, f32, "error").value
+        bs.mask = _lib.require_device_tensor(mask, torch.bool, "mask").value if mask is not None else None
+        bs.A_blue = None
+        zabs = self._redshift_form(bs, keep, delta.shape[0], zabs, zfac, auto_factor=auto_factor, also_zabs=True)
         if self._tau_callable is not None and self.Nb > 0:
             a = torch.exp(-1. * self._tau_callable(zabs)).to(f32).contiguous()   # user code (model.py:125)
             keep.append(a)

@@ -55,8 +55,14 @@ def _window2(k, dv, resolution_kms):
     return (xp.sinc(k * dv / (2.0 * np.pi)) * xp.exp(-0.5 * (k * float(resolution_kms)) ** 2)) ** 2
 
 
+def _f32(x):
+    """x as the float32 number a kernel reads (an overflow is inf, quietly: the checks see it)"""
+    with np.errstate(over="ignore"):
+        return float(np.float32(x))
+
+
 def _edges(k_edges):
-    """the checked band edges as a tuple of floats"""
+    """the checked band edges as a tuple of floats: the band stack's parameter rule"""
     e = tuple(float(x) for x in np.asarray(k_edges, np.float64).reshape(-1))
     if not (2 <= len(e) <= 65 and np.all(np.isfinite(e)) and np.all(np.diff(e) > 0.0)):
         raise QFAHipError(f"P1DBandStack: k_edges must be 2 .. 65 increasing finite wavenumbers, got {len(e)}")
@@ -78,10 +84,12 @@ def _band_map(L, dv, k_edges):
 
 
 class _DrawStack(object):
-    """What the three stacks share: ``buf`` = (S, ...) contiguous float64 sums per draw of the continuum -- sums only, which is
+    """What the six stacks share: ``buf`` = (S, ...) contiguous float64 sums per draw of the continuum -- sums only, which is
     what data parallelism all-reduces -- over the z-bins [z0 + i dz, z0 + (i + 1) dz), z0 and dz as the float32 numbers the
     kernels bin with.  A class adds its layout (``_like``, ``same_layout``) and, where it is not ``mean``, the per-draw quantity
-    the statistics over the draws are taken of (``_per_draw``)."""
+    the statistics over the draws are taken of (``_per_draw``), its parameter rule -- a static check that returns the parameters as the
+    kernels will see them and raises ``QFAHipError``, the one place in Python where the bounds of the C checks are written -- and
+    ``arrays()``, what the command line writes of it."""
 
     @staticmethod
     def _round_bins(z0, dz, n):
@@ -114,6 +122,10 @@ class _DrawStack(object):
     @property
     def z_centers(self):
         return self.z0 + self.dz * (torch.arange(self._nbins, dtype=torch.float64, device=self.buf.device) + 0.5)
+
+    def _export(self, **named):
+        """``arrays()``: tensors as numpy arrays on the host, scalars as they are"""
+        return {k: v.cpu().numpy() if isinstance(v, torch.Tensor) else v for k, v in named.items()}
 
     def _per_draw(self):
         return self.mean
@@ -198,6 +210,11 @@ class ForestStack(_DrawStack):
         continuum errors of a spectrum's pixels are correlated, which repeating the whole stack per draw carries through)"""
         return self._draws("std_over_draws").std(0, unbiased=True)
 
+    def arrays(self):
+        """what mean_transmission.npz holds"""
+        return self._export(z_centers=self.z_centers, z_edges=self.z_edges, mean=self.mean, var=self.var, n=self.n, tau_eff=self.tau_eff,
+                            sums=self.buf)
+
 
 class _SegmentStack(_DrawStack):
     """A stack over segments of ``L`` pixels ``dv`` km/s wide, M = L // 2 modes k_m = 2 pi m / (L dv): ``buf`` = (S, nz, width),
@@ -272,6 +289,11 @@ class P1DStack(_SegmentStack):
     def std_over_draws(self):
         """(nz, M) standard deviation of ``power()`` over the S draws: the continuum posterior's error bar on P1D"""
         return self._draws("std_over_draws").std(0, unbiased=True)
+
+    def arrays(self):
+        """what flux_power.npz holds"""
+        return self._export(k=self.k, z_centers=self.z_centers, z_edges=self.z_edges, power=self.power(), err=self.err(),
+                            power_raw=self.power_raw, noise=self.noise, n=self.n, seg_len=self.L, dv=self.dv, sums=self.buf)
 
 
 class P1DBandStack(_SegmentStack):
@@ -360,6 +382,12 @@ class P1DBandStack(_SegmentStack):
         """(nz, nband, nband) the mean over the draws of ``cov`` plus ``cov_over_draws``"""
         return self.cov.mean(0) + self.cov_over_draws
 
+    def arrays(self):
+        """what flux_power_bands.npz holds; ``cov_over_draws`` with more than one draw"""
+        over = {"cov_over_draws": self.cov_over_draws} if self.S > 1 else {}
+        return self._export(k_edges=self.k_edges, k_centers=self.k_centers, z_edges=self.z_edges, n=self.n, mean=self.mean, cov=self.cov,
+                            **over)
+
 
 class XiStack(_SegmentStack):
     """The (lag, z) stack of the pair-weighted line-of-sight correlation function (include/qfa_hip.h, qfa_xi_f32): ``buf`` =
@@ -367,15 +395,21 @@ class XiStack(_SegmentStack):
     z-bin, over segments of ``L`` pixels ``dv`` km/s wide; W_l and A_l are a segment's sums of w_j w_{j+l} and of
     w_j w_{j+l} d_j d_{j+l}, N0 the noise in A_0."""
 
-    def __init__(self, buf, z0, dz, nz, L, n_lags, dv=1.0):
-        self.nlag = int(n_lags)
-        if not 1 <= self.nlag <= int(L):
+    @staticmethod
+    def lag_params(L, n_lags):
+        """the checked number of lags on segments of ``L`` pixels"""
+        if not 1 <= int(n_lags) <= int(L):
             raise QFAHipError(f"XiStack: {n_lags} lags on segments of {L} pixels")
+        return int(n_lags)
+
+    def __init__(self, buf, z0, dz, nz, L, n_lags, dv=1.0):
+        self.nlag = self.lag_params(L, n_lags)
         super().__init__(buf, z0, dz, nz, L, dv, 2 + 5 * self.nlag)
 
     @classmethod
     def zeros(cls, S, z0, dz, nz, L, n_lags, dv, device):
-        return cls(torch.zeros((int(S), int(nz), 2 + 5 * int(n_lags)), dtype=torch.float64, device=device), z0, dz, nz, L, n_lags, dv)
+        nlag = cls.lag_params(L, n_lags)
+        return cls(torch.zeros((int(S), int(nz), 2 + 5 * nlag), dtype=torch.float64, device=device), z0, dz, nz, L, nlag, dv)
 
     def _like(self, buf):
         return XiStack(buf, self.z0, self.dz, self.nz, self.L, self.nlag, self.dv)
@@ -430,6 +464,12 @@ class XiStack(_SegmentStack):
         """(nz, nlag) standard deviation of ``xi()`` over the S draws: the continuum posterior's error bar on xi"""
         return self._draws("std_over_draws").std(0, unbiased=True)
 
+    def arrays(self):
+        """what flux_correlation.npz holds"""
+        return self._export(lags_kms=self.lags_kms, z_centers=self.z_centers, z_edges=self.z_edges, xi=self.xi(),
+                            xi_raw=self.xi(subtract_noise=False), err=self.err(), n=self.n, sum_w=self.sum_w, seg_len=self.L, dv=self.dv,
+                            sums=self.buf)
+
 
 class PDFStack(_DrawStack):
     """The stack of the flux PDF of forest segments and of the outer products of their counts (include/qfa_hip.h,
@@ -440,19 +480,24 @@ class PDFStack(_DrawStack):
     Every entry is an integer, exact below 2^53: stacks add up exactly, in any order.  t0 and dt are held as the float32 numbers
     the kernel bins with."""
 
+    @staticmethod
+    def flux_params(t0, dt, n_tbins, relative=False, clamp=False, ivar_min=0.0):
+        """(t0, dt, nt, relative, clamp, ivar_min) checked, t0, dt and ivar_min as the float32 numbers the kernel reads"""
+        p = (_f32(t0), _f32(dt), int(n_tbins), bool(relative), bool(clamp), _f32(ivar_min))
+        if not (1 <= p[2] <= 64 and p[1] > 0.0 and np.isfinite(p[1]) and np.isfinite(p[0]) and p[5] >= 0.0 and np.isfinite(p[5])):
+            raise QFAHipError(f"PDFStack: {n_tbins} flux bins from {t0} in steps of {dt}, ivar_min = {ivar_min}")
+        return p
+
     def __init__(self, buf, z0, dz, nz, L, t0, dt, n_tbins, relative=False, clamp=False, ivar_min=0.0):
-        self.L, self.nt = int(L), int(n_tbins)
-        self.t0, self.dt = float(np.float32(t0)), float(np.float32(dt))
-        self.relative, self.clamp, self.ivar_min = bool(relative), bool(clamp), float(np.float32(ivar_min))
-        if not (1 <= self.nt <= 64 and self.dt > 0.0 and np.isfinite(self.dt) and np.isfinite(self.t0) and 1 <= self.L <= 4096
-                and self.ivar_min >= 0.0 and np.isfinite(self.ivar_min)):
-            raise QFAHipError(f"PDFStack: {n_tbins} flux bins from {t0} in steps of {dt}, ivar_min = {ivar_min}, segments L = {L}")
+        self.t0, self.dt, self.nt, self.relative, self.clamp, self.ivar_min = self.flux_params(t0, dt, n_tbins, relative, clamp, ivar_min)
+        self.L = int(L)
+        _check_segments("PDFStack", L, 1.0)
         super().__init__(buf, z0, dz, nz, (int(nz), 2 + self.nt + self.nt ** 2))
         self.nz = self._nbins
 
     @classmethod
     def zeros(cls, S, z0, dz, nz, L, t0, dt, n_tbins, relative=False, clamp=False, ivar_min=0.0, device="cpu"):
-        nt = int(n_tbins)
+        nt = cls.flux_params(t0, dt, n_tbins, relative, clamp, ivar_min)[2]
         return cls(torch.zeros((int(S), int(nz), 2 + nt + nt * nt), dtype=torch.float64, device=device), z0, dz, nz, L, t0, dt, nt,
                    relative, clamp, ivar_min)
 
@@ -564,6 +609,12 @@ class PDFStack(_DrawStack):
         """(nz, nt, nt) the mean over the draws of ``cov()`` plus ``cov_over_draws``"""
         return self.cov().mean(0) + self.cov_over_draws
 
+    def arrays(self):
+        """what flux_pdf.npz holds; ``std_over_draws`` and ``total_cov`` with more than one draw"""
+        over = {"std_over_draws": self.std_over_draws, "total_cov": self.total_cov} if self.S > 1 else {}
+        return self._export(z=self.z_centers, t_edges=self.t_edges, pdf=self.pdf(), err=self.err(), cov=self.cov(), counts=self.counts,
+                            n_segments=self.n_segments, out_of_range=self.out_of_range(), **over)
+
 
 # what ``VarianceStack.fit`` returns: (S, nz) tensors, ``cov`` (S, nz, P, P) in the order (eta, sigma2_lss[, eps]); ``eps`` None
 # without the third term
@@ -596,19 +647,23 @@ class VarianceStack(_SegmentStack):
 
     FLT_MAX = float(np.finfo(np.float32).max)
 
-    def __init__(self, buf, z0, dz, nz, L, e_lo, n_oct, sub=1, d_max=None):
-        self.e_lo, self.n_oct, self.sub = int(e_lo), int(n_oct), int(sub)
-        with np.errstate(over="ignore"):
-            self.d_max = self.FLT_MAX if d_max is None else float(np.float32(d_max))
-        if not (0 <= self.sub <= 4 and self.n_oct >= 1 and 1 <= (self.n_oct << self.sub) <= 64 and self.e_lo >= -126
-                and self.e_lo + self.n_oct <= 127 and self.d_max > 0.0):
+    @classmethod
+    def var_params(cls, e_lo, n_oct, sub=1, d_max=None):
+        """(e_lo, n_oct, sub, d_max) checked -- what ``var_bins`` reports --, d_max as the float32 number the kernel cuts with"""
+        p = (int(e_lo), int(n_oct), int(sub), cls.FLT_MAX if d_max is None else _f32(d_max))
+        if not (0 <= p[2] <= 4 and p[1] >= 1 and 1 <= (p[1] << p[2]) <= 64 and p[0] >= -126 and p[0] + p[1] <= 127 and p[3] > 0.0):
             raise QFAHipError(f"VarianceStack: e_lo = {e_lo}, n_oct = {n_oct}, sub = {sub}, d_max = {d_max}")
+        return p
+
+    def __init__(self, buf, z0, dz, nz, L, e_lo, n_oct, sub=1, d_max=None):
+        self.e_lo, self.n_oct, self.sub, self.d_max = self.var_params(e_lo, n_oct, sub, d_max)
         self.nv = self.n_oct << self.sub
         super().__init__(buf, z0, dz, nz, L, 1.0, 2 + 5 * self.nv)
 
     @classmethod
     def zeros(cls, S, z0, dz, nz, L, e_lo, n_oct, sub=1, d_max=None, device="cpu"):
-        nv = max(0, int(n_oct)) << max(0, min(4, int(sub)))
+        p = cls.var_params(e_lo, n_oct, sub, d_max)
+        nv = p[1] << p[2]
         return cls(torch.zeros((int(S), int(nz), 2 + 5 * nv), dtype=torch.float64, device=device), z0, dz, nz, L, e_lo, n_oct, sub, d_max)
 
     def _like(self, buf):
@@ -723,3 +778,12 @@ class VarianceStack(_SegmentStack):
             raise QFAHipError(f"VarianceStack.std_over_draws: needs more than one draw of the continuum (S = {self.S})")
         ft = self.fit(min_count=min_count)
         return ft.eta.std(0, unbiased=True), ft.sigma2_lss.std(0, unbiased=True)
+
+    def arrays(self, min_count=100):
+        """what variance_function.npz holds: the stack, ``fit(min_count)`` and, with more than one draw, ``std_over_draws(min_count)``"""
+        ft = self.fit(min_count=min_count)
+        over = dict(zip(("eta_std_over_draws", "sigma2_lss_std_over_draws"), self.std_over_draws(min_count))) if self.S > 1 else {}
+        return self._export(z=self.z_centers, z_edges=self.z_edges, v_edges=self.v_edges, v_mean=self.v_mean, var_delta=self.var_delta,
+                            var_err=self.var_err, mean_delta=self.mean_delta, counts=self.counts, n_segments=self.n_segments,
+                            n_pixels=self.n_pixels, out_of_range=self.out_of_range(), seg_len=self.L, sums=self.buf, eta=ft.eta,
+                            sigma2_lss=ft.sigma2_lss, cov=ft.cov, chi2=ft.chi2, ndof=ft.ndof, n_bins=ft.n_bins, **over)

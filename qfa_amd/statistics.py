@@ -18,14 +18,14 @@ from .stacks import ForestStack, P1DBandStack, P1DStack, PDFStack, VarianceStack
 
 f32 = torch.float32
 
-# what `_power_of_loader` needs to know of a statistic: zeros(S, z0, dz, nz, L, dv) makes its stack, ``call`` is its method of a slice
-# with its own ``keywords``, check(L) (or None) returns what is wrong with segments of L pixels, ``needs_dv`` False: dv matters only
-# where <T> is made in the loop's own `mean_transmission`
-_LoaderStat = collections.namedtuple("_LoaderStat", "zeros call keywords check needs_dv", defaults=(None, True))
+# what `_power_of_loader` needs to know of a statistic: zeros(S, z0, dz, nz, L, dv) makes its stack -- and with it checks the
+# statistic's parameters, before the first slice --, ``call`` is its method of a slice with its own ``keywords``, ``needs_dv`` False: dv
+# matters only where <T> is made in the loop's own `mean_transmission`
+_LoaderStat = collections.namedtuple("_LoaderStat", "zeros call keywords needs_dv", defaults=(True,))
 
 
 def _p1d_params(tbar_bins, St, p_lo, L, nseg, min_used, stack):
-    """qfa_p1d_t of `p1d`, `p1d_bands`, `xi` and `flux_pdf_segments`: the bins of tbar, the segments and the z-bins of ``stack`` (None: one unused bin)"""
+    """qfa_p1d_t of `p1d`, `p1d_bands`, `xi`, `flux_pdf_segments` and `variance_segments`: the bins of tbar, the segments and the z-bins of ``stack`` (None: one unused bin)"""
     pp = _lib.P1DParams()
     pp.zT0, pp.dzT, pp.nT = ForestStack._round_bins(tbar_bins[0], tbar_bins[1], tbar_bins[2])
     pp.St = St
@@ -151,8 +151,8 @@ class ForestStatistics(object):
     P1D_PAIR_BYTES = 1 << 30    # flux_power: the most the (B, S_chunk, Nb) trans / ivar pair of a slice may take
 
     def _p1d_inputs(self, what, asked, trans, ivar, zabs, zfac, batch, tbar, tbar_bins):
-        """the checks and conversions `p1d`, `p1d_bands`, `xi` and `flux_pdf_segments` share: (B, S, tbar (St, nT) float32, St, tbar_bins, qfa_batch_t, the
-        tensors it points into); ``asked``: whether the call has an output at all"""
+        """the checks and conversions `p1d`, `p1d_bands`, `xi`, `flux_pdf_segments` and `variance_segments` share: (B, S, tbar (St, nT)
+        float32, St, tbar_bins, qfa_batch_t, the tensors it points into); ``asked``: whether the call has an output at all"""
         dev = self.device
         if not asked:
             raise QFAHipError(what + ": nothing asked for (no bins, no stack, return_segments = False)")
@@ -174,35 +174,17 @@ class ForestStatistics(object):
                 raise QFAHipError(f"{what}: resident batch of {batch.B} spectra, trans has {B}")
             bs, keep = self._batch_struct_rows(batch, need_src=False)
         else:
+            if zabs is None and zfac is None:
+                raise QFAHipError(what + ": pass zabs, zfac = (zq1, pix_ratio) or batch")
             bs, keep = _lib.Batch(), []
             bs.row_stride = 0
-            if zfac is None:
-                zfac = getattr(zabs, "zfac", None)              # (what a DeviceDataloader attaches)
-            # _batch_struct's condition, so that p1d bins on the very z `forest` and `mean_transmission` binned on
-            if zfac is not None and not (self._tau_callable is None and self.use_factored_z):
-                if zabs is None:
-                    raise QFAHipError("zabs is None and no usable zfac = (zq1, pix_ratio) was given")
-                zfac = None
-            if zfac is None and zabs is not None:
-                if tuple(zabs.shape) != (B, self.Nb):
-                    raise QFAHipError(f"zabs: shape {tuple(zabs.shape)}, expected ({B}, {self.Nb})")
-                zabs = zabs if (zabs.dtype == f32 and zabs.is_contiguous()) else zabs.to(f32).contiguous()
-                keep.append(zabs)
-                bs.zabs = _lib.require_device_tensor(zabs, f32, "zabs").value
-            elif zfac is not None:
-                zq1, ratio = (t if (t.dtype == f32 and t.is_contiguous()) else t.to(f32).contiguous() for t in zfac)
-                if tuple(zq1.shape) != (B,) or tuple(ratio.shape) != (self.Nb,):
-                    raise QFAHipError(f"zfac shapes {tuple(zq1.shape)}, {tuple(ratio.shape)}: expected ({B},), ({self.Nb},)")
-                keep += [zq1, ratio]
-                bs.zq1 = _lib.require_device_tensor(zq1, f32, "zq1").value
-                bs.pix_ratio = _lib.require_device_tensor(ratio, f32, "pix_ratio").value
-            else:
-                raise QFAHipError(what + ": pass zabs, zfac = (zq1, pix_ratio) or batch")
+            # `_batch_struct`'s rule, so that p1d bins on the very z `forest` and `mean_transmission` binned on
+            self._redshift_form(bs, keep, B, zabs, zfac)
         return B, S, tbar, St, tbar_bins, bs, keep
 
     def _segment_call(self, what, name, inp, trans, ivar, L, nseg, pixel_start, min_used, bins, stack, *, cls, same, zeros, expected,
                       own=None):
-        """what `p1d`, `p1d_bands`, `xi` and `flux_pdf_segments` share behind ``inp`` = `_p1d_inputs`' result: ``stack`` is checked (a
+        """what `p1d`, `p1d_bands`, `xi`, `flux_pdf_segments` and `variance_segments` share behind ``inp`` = `_p1d_inputs`' result: ``stack`` is checked (a
         ``cls`` of S draws and segments of L pixels on the same bins for which ``same(stack)`` holds, else the error ends in
         ``expected``) or made by ``zeros()`` when ``bins`` asks for one; ``own(stack)`` -> (the statistic's own size, its note in the
         error of an unsupported shape, its parameter struct); qfa_p1d_t; the workspace of ``name``_workspace_bytes.  Returns
@@ -222,7 +204,7 @@ class ForestStatistics(object):
         need = getattr(h, name + "_workspace_bytes")(B * S, S, self.Nb, L, nseg, int(pp.nz), *size) if L >= 1 and nseg >= 1 else 0
         if need == 0:
             raise QFAHipError(f"{what}: unsupported shape B={B} S={S} Nb={self.Nb} seg_len={L} n_segments={nseg} nz={pp.nz}{note}")
-        ws = self._scratch("p1d_ws", need)                        # (one for the four calls: they own it only while they run)
+        ws = self._scratch("p1d_ws", need)                        # (one for the five calls: they own it only while they run)
 
         def call(flags, *outputs):
             _lib.check(getattr(h, name + "_f32")(
@@ -314,9 +296,10 @@ class ForestStatistics(object):
         the noise in A_0 -- both None with ``return_segments`` False -- and the ``XiStack`` (or None))."""
         inp = self._p1d_inputs("xi", bins is not None or stack is not None or return_segments, trans, ivar, zabs, zfac, batch, tbar, tbar_bins)
         B, S, dev = inp[0], inp[1], self.device
-        L, nseg, nlag, s2 = int(seg_len), int(n_segments), int(n_lags), float(sigma2_lss)
-        if not (L >= 1 and 1 <= nlag <= L and s2 >= 0.0 and np.isfinite(s2)):
-            raise QFAHipError(f"xi: n_lags = {n_lags} on segments of {seg_len} pixels, sigma2_lss = {sigma2_lss}")
+        L, nseg, s2 = int(seg_len), int(n_segments), float(sigma2_lss)
+        nlag = XiStack.lag_params(L, n_lags)
+        if not (s2 >= 0.0 and np.isfinite(s2)):
+            raise QFAHipError(f"xi: sigma2_lss = {sigma2_lss}")
         stack, call = self._segment_call("xi", "qfa_xi", inp, trans, ivar, L, nseg, pixel_start, min_used, bins, stack, cls=XiStack,
                                          same=lambda st: st.nlag == nlag,
                                          zeros=lambda: XiStack.zeros(S, bins[0], bins[1], bins[2], L, nlag, dv, dev),
@@ -328,6 +311,11 @@ class ForestStatistics(object):
             noise0 = torch.empty((B, S, nseg), dtype=f32, device=dev)
         call(_lib.F_XI_UNIT_W if unit_weights else 0, pairs, noise0)
         return pairs, noise0, stack
+
+    @staticmethod
+    def _flux_params(t_min, t_max, n_tbins, relative, clamp, ivar_min):
+        """`PDFStack.flux_params` of ``n_tbins`` equal bins of [t_min, t_max): an empty or unbounded range has no valid step"""
+        return PDFStack.flux_params(t_min, (float(t_max) - float(t_min)) / max(1, int(n_tbins)), n_tbins, relative, clamp, ivar_min)
 
     def flux_pdf_segments(self, trans, ivar, *, zabs=None, zfac=None, batch=None, tbar, tbar_bins=None, seg_len, n_segments,
                           pixel_start=0, min_used, t_min, t_max, n_tbins, relative=False, clamp=False, ivar_min=0.0, bins=None,
@@ -343,16 +331,13 @@ class ForestStatistics(object):
         inp = self._p1d_inputs("flux_pdf_segments", bins is not None or stack is not None or return_segments, trans, ivar, zabs, zfac,
                                batch, tbar, tbar_bins)
         B, S, dev = inp[0], inp[1], self.device
-        L, nseg, nt, imin = int(seg_len), int(n_segments), int(n_tbins), float(ivar_min)
-        if not (1 <= nt <= 64 and float(t_max) > float(t_min) and np.isfinite(float(t_min)) and np.isfinite(float(t_max))
-                and imin >= 0.0 and np.isfinite(imin)):
-            raise QFAHipError(f"flux_pdf_segments: {n_tbins} flux bins of [{t_min}, {t_max}), ivar_min = {ivar_min}")
-        t0, dt = float(t_min), (float(t_max) - float(t_min)) / nt
-        want = PDFStack._round_bins(t0, dt, nt) + (bool(relative), bool(clamp), float(np.float32(imin)))
+        L, nseg = int(seg_len), int(n_segments)
+        want = self._flux_params(t_min, t_max, n_tbins, relative, clamp, ivar_min)
+        t0, dt, nt, _, _, imin = want
         stack, call = self._segment_call(
             "flux_pdf_segments", "qfa_flux_pdf", inp, trans, ivar, L, nseg, pixel_start, min_used, bins, stack, cls=PDFStack,
             same=lambda st: st.flux_bins + (st.relative, st.clamp, st.ivar_min) == want,
-            zeros=lambda: PDFStack.zeros(S, bins[0], bins[1], bins[2], L, t0, dt, nt, relative, clamp, imin, dev),
+            zeros=lambda: PDFStack.zeros(S, bins[0], bins[1], bins[2], L, *want, dev),
             expected=f" and segments of {L} pixels on the same z-bins, flux bins, flags and ivar_min",
             own=lambda st: ((nt,), f" n_tbins={nt}", _lib.PDFParams(t0, dt, nt, imin)))
         hist = torch.empty((B, S, nseg, nt), dtype=torch.int32, device=dev) if return_segments else None
@@ -372,17 +357,14 @@ class ForestStatistics(object):
                                batch, tbar, tbar_bins)
         B, S, dev = inp[0], inp[1], self.device
         L, nseg = int(seg_len), int(n_segments)
-        try:
-            want = VarianceStack.zeros(1, 0.0, 1.0, 1, max(1, min(L, 4096)), e_lo, n_oct, sub, d_max).var_bins
-        except QFAHipError:
-            raise QFAHipError(f"variance_segments: e_lo = {e_lo}, n_oct = {n_oct}, sub = {sub}, d_max = {d_max}") from None
+        want = VarianceStack.var_params(e_lo, n_oct, sub, d_max)
         nv = want[1] << want[2]
         stack, call = self._segment_call(
             "variance_segments", "qfa_variance", inp, trans, ivar, L, nseg, pixel_start, min_used, bins, stack, cls=VarianceStack,
             same=lambda st: st.var_bins == want,
-            zeros=lambda: VarianceStack.zeros(S, bins[0], bins[1], bins[2], L, e_lo, n_oct, sub, d_max, dev),
+            zeros=lambda: VarianceStack.zeros(S, bins[0], bins[1], bins[2], L, *want, dev),
             expected=f" and segments of {L} pixels on the same z-bins, variance bins and d_max",
-            own=lambda st: ((nv,), f" nv={nv}", _lib.VarParams(want[0], want[1], want[2], want[3])))
+            own=lambda st: ((nv,), f" nv={nv}", _lib.VarParams(*want)))
         moments = torch.empty((B, S, nseg, 5, nv), dtype=torch.float64, device=dev) if return_segments else None
         call(0, moments)
         return moments, stack
@@ -425,12 +407,10 @@ class ForestStatistics(object):
         (``sigma2_lss``, ``unit_weights``: its weights).  The sums of a slice are formed in chunks of a fixed number of segments, so
         the result depends on ``batch_size`` only through the rounding of float64 sums.  Under data parallelism the sums are
         all-reduced over the model's group."""
-        nlag = int(n_lags)
         return self._power_of_loader("flux_correlation", dataloader, z_min, z_max, n_zbins, n_segments, seg_len, min_used_frac, tbar,
                                      tbar_nbins, n_samples, seed, batch_size, cont_min, dv,
-                                     _LoaderStat(lambda S, z0, dz, nz, L, dv: XiStack.zeros(S, z0, dz, nz, L, nlag, dv, self.device), self.xi,
-                                                 {"n_lags": nlag, "sigma2_lss": float(sigma2_lss), "unit_weights": bool(unit_weights)},
-                                                 lambda L: None if 1 <= nlag <= L else f"n_lags = {nlag} on segments of {L} pixels"))
+                                     _LoaderStat(lambda S, z0, dz, nz, L, dv: XiStack.zeros(S, z0, dz, nz, L, n_lags, dv, self.device), self.xi,
+                                                 {"n_lags": int(n_lags), "sigma2_lss": float(sigma2_lss), "unit_weights": bool(unit_weights)}))
 
     def flux_pdf(self, dataloader, z_min, z_max, n_zbins, n_tbins=20, *, t_min=0.0, t_max=1.0, relative=False, clamp=True,
                  ivar_min=0.0, n_segments=3, seg_len=None, min_used_frac=0.75, tbar=None, tbar_nbins=64, n_samples=0, seed=0,
@@ -443,11 +423,8 @@ class ForestStatistics(object):
         result does not depend on ``batch_size`` at all.  Under data parallelism the sums are all-reduced over the model's group."""
         pdf = {"t_min": float(t_min), "t_max": float(t_max), "n_tbins": int(n_tbins), "relative": bool(relative), "clamp": bool(clamp),
                "ivar_min": float(ivar_min)}
-        if not (1 <= pdf["n_tbins"] <= 64 and pdf["t_max"] > pdf["t_min"] and np.isfinite(pdf["t_min"]) and np.isfinite(pdf["t_max"])
-                and pdf["ivar_min"] >= 0.0 and np.isfinite(pdf["ivar_min"])):
-            raise QFAHipError(f"flux_pdf: {n_tbins} flux bins of [{t_min}, {t_max}), ivar_min = {ivar_min}")
-        zeros = lambda S, z0, dz, nz, L, dv: PDFStack.zeros(S, z0, dz, nz, L, pdf["t_min"], (pdf["t_max"] - pdf["t_min"]) / pdf["n_tbins"],
-                                                            pdf["n_tbins"], pdf["relative"], pdf["clamp"], pdf["ivar_min"], self.device)
+        want = self._flux_params(**pdf)
+        zeros = lambda S, z0, dz, nz, L, dv: PDFStack.zeros(S, z0, dz, nz, L, *want, self.device)
         # (dv None: the PDF needs it for the range of its own <T> alone)
         return self._power_of_loader("flux_pdf", dataloader, z_min, z_max, n_zbins, n_segments, seg_len, min_used_frac, tbar,
                                      tbar_nbins, n_samples, seed, batch_size, cont_min, None,
@@ -465,10 +442,7 @@ class ForestStatistics(object):
         number of segments, so the result depends on ``batch_size`` only through the rounding of float64 sums.  Under data
         parallelism the sums are all-reduced over the model's group."""
         var = {"e_lo": int(e_lo), "n_oct": int(n_oct), "sub": int(sub), "d_max": d_max}
-        try:
-            VarianceStack.zeros(1, 0.0, 1.0, 1, 1, **var)
-        except QFAHipError:
-            raise QFAHipError(f"variance_function: e_lo = {e_lo}, n_oct = {n_oct}, sub = {sub}, d_max = {d_max}") from None
+        VarianceStack.var_params(**var)
         zeros = lambda S, z0, dz, nz, L, dv: VarianceStack.zeros(S, z0, dz, nz, L, device=self.device, **var)
         # (dv None: the variance function needs it for the range of its own <T> alone)
         return self._power_of_loader("variance_function", dataloader, z_min, z_max, n_zbins, n_segments, seg_len, min_used_frac, tbar,
@@ -477,7 +451,7 @@ class ForestStatistics(object):
 
     def _power_of_loader(self, what, dataloader, z_min, z_max, n_zbins, n_segments, seg_len, min_used_frac, tbar, tbar_nbins,
                          n_samples, seed, batch_size, cont_min, dv, stat):
-        """the loop `flux_power`, `band_power`, `flux_correlation` and `flux_pdf` share; ``stat``: the statistic's `_LoaderStat`"""
+        """the loop `flux_power`, `band_power`, `flux_correlation`, `flux_pdf` and `variance_function` share; ``stat``: the statistic's `_LoaderStat`"""
         nseg, nz, S = int(n_segments), int(n_zbins), max(1, int(n_samples))
         L = int(seg_len) if seg_len is not None else (self.Nb // nseg if nseg > 0 else 0)
         if nseg < 1 or L < 1 or nseg * L > self.Nb or nz < 1 or not float(z_max) > float(z_min) or not 0.0 < float(min_used_frac) <= 1.0:
@@ -488,8 +462,7 @@ class ForestStatistics(object):
             if wav is None or len(wav) < 2:
                 raise QFAHipError(what + ": the dataloader has no wav_grid: pass dv (km/s per pixel)")
             dv = 299792.458 * float(np.log(float(wav[1]) / float(wav[0])))
-        if stat.check is not None and stat.check(L) is not None:
-            raise QFAHipError(f"{what}: {stat.check(L)}")
+        stack = stat.zeros(S, z_min, (float(z_max) - float(z_min)) / nz, nz, L, dv)
         min_used = max(1, int(np.ceil(float(min_used_frac) * L)))
         if tbar is None:
             half = float(np.exp(0.5 * (L + 1) * float(dv) / 299792.458))          # (1 + z) over half a segment
@@ -499,7 +472,6 @@ class ForestStatistics(object):
         if not isinstance(tbar, ForestStack) or tbar.S not in (1, S):
             raise QFAHipError(f"{what}: tbar must be a ForestStack of 1 or {S} draws")
         tmean = tbar.mean.to(f32)
-        stack = stat.zeros(S, z_min, (float(z_max) - float(z_min)) / nz, nz, L, dv)
         row0 = int(getattr(dataloader, "_row0", 0))              # (a data-parallel loader: the global index of its first row)
         for s, inputs, _ in self._loader_slices(dataloader, int(batch_size)):
             _, hmean, hcov, _, unc = self.predict(**inputs)

@@ -13,29 +13,16 @@ import pytest
 
 import _flux_pdf_ref as R
 import _p1d_ref as RP
-from test_forest import T, make_model
-from test_p1d import TB_BINS, forest_case
+from _segment_harness import (F_ZERO, TB_BINS, T, call_segment, case_shape, cli_predict_case, dev, forest_case,  # noqa: F401 (dev: the fixture)
+                              loader_case, make_model, redshift_forms, refusals)
 
 pytestmark = pytest.mark.gpu
-F_ZERO, F_REL, F_CLAMP = 0x80, 0x800, 0x1000
+F_REL, F_CLAMP = 0x800, 0x1000
 BINS = (1.6, 0.45, 4)
 T_LO, T_HI = 0.2, 1.4                                         # the geometry's T leaves pixels on both sides of it
 # (rows, L, nseg, p_lo, nt): the 64-pixel walk at L = 63 / 64 / 65 via the neighbours, lane nt - 1 at nt = 64, a chunk not filled
 CASES = [(1, 1, 1, 0, 1), (3, 2, 2, 1, 2), (17, 37, 3, 5, 20), (33, 64, 2, 0, 63), (33, 65, 2, 0, 64), (16, 240, 3, 0, 20),
          (5, 667, 1, 3, 21), (2, 4096, 1, 0, 64)]
-
-
-@pytest.fixture(scope="module")
-def dev():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    return torch.device("cuda:0")
-
-
-def case_shape(rows, L, nseg, p_lo):
-    """B, S, nb, min_used and the seed of a row of CASES: tests/test_p1d.py's rule"""
-    S = 3 if rows % 3 == 0 and rows > 3 else 1
-    return rows // S, S, p_lo + nseg * L + 3, max(1, int(np.ceil(0.78 * L))), 1000 + L
 
 
 def median_ivar(ivar):
@@ -44,36 +31,13 @@ def median_ivar(ivar):
     return float(np.median(pos)) if pos.size else 0.0
 
 
-def call_pdf(dev, trans, ivar, tbar, prm, pdf, *, zabs=None, zq1=None, ratio=None, rows=None, flags=F_ZERO, outs="hs", stack=None,
-             expect=0, ws_bytes=None):
+def call_pdf(dev, trans, ivar, tbar, prm, pdf, **kw):
     """qfa_flux_pdf_f32 by hand on device tensors; prm = (p_lo, L, nseg, min_used, (z0, dz, nz)), pdf = (t0, dt, nt, ivar_min).
-    Returns hist, stack (numpy).  Fresh outputs hold the sentinels -7 and 3.0"""
-    import torch
+    Returns hist, stack (numpy)"""
     from qfa_amd import _lib
-    lib = _lib.lib()
-    B, S, Nb = trans.shape
-    p_lo, L, nseg, min_used, bins = prm
-    tb = T(tbar, dev).reshape(-1, TB_BINS[2]).contiguous()
-    ptr = lambda t: None if t is None else t.data_ptr()
-    bs = _lib.Batch()
-    bs.zabs, bs.zq1, bs.pix_ratio, bs.rows, bs.row_stride = ptr(zabs), ptr(zq1), ptr(ratio), ptr(rows), 0
-    pp = _lib.P1DParams(TB_BINS[0], TB_BINS[1], TB_BINS[2], int(tb.shape[0]), p_lo, L, nseg, min_used, bins[0], bins[1], bins[2])
-    qq = _lib.PDFParams(*pdf)
     nt = max(1, min(64, int(pdf[2])))
-    hist = torch.full((B, S, nseg, nt), -7, dtype=torch.int32, device=dev) if "h" in outs else None
-    if stack is None and "s" in outs:
-        stack = torch.full((S, bins[2], 2 + nt + nt * nt), 3.0, dtype=torch.float64, device=dev)
-    need = lib.qfa_flux_pdf_workspace_bytes(B * S, S, Nb, L, nseg, bins[2], int(pdf[2]))
-    if expect == 0:
-        assert need > 0
-    need = max(need, 1 << 16) if ws_bytes is None else ws_bytes
-    ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
-    st = lib.qfa_flux_pdf_f32(C.c_void_p(trans.data_ptr()), C.c_void_p(ivar.data_ptr()), C.byref(bs), C.c_void_p(tb.data_ptr()), B, S,
-                              Nb, C.byref(pp), C.byref(qq), flags, C.c_void_p(ptr(hist)), C.c_void_p(ptr(stack)),
-                              C.c_void_p(ws.data_ptr()), need, _lib.current_stream(dev))
-    torch.cuda.synchronize()
-    assert st == expect, st
-    return tuple(None if x is None else x.cpu().numpy() for x in (hist, stack))
+    return call_segment("qfa_flux_pdf", dev, trans, ivar, tbar, prm, _lib.PDFParams(*pdf), (("h", (nt,), "int32"),), size=(int(pdf[2]),),
+                        stack_width=2 + nt + nt * nt, **kw)
 
 
 def check_exact(hist, stack, ref, nt, what):
@@ -125,15 +89,9 @@ def test_redshift_forms_equal_the_port(dev, rows, L, nseg, p_lo, nt):
     g, m, tr, iv, tbar = forest_case(dev, B, S, nb, seed=seed)
     prm = (p_lo, L, nseg, min_used, BINS)
     t0, dt = np.float32(T_LO), np.float32((T_HI - T_LO) / nt)
-    zf = RP.z_factored(g["zq1"], g["ratio"])                                          # the float32 z the factored form computes
+    zf, forms = redshift_forms(dev, g, B, nb)
     ref = R.flux_pdf(tr.cpu().numpy(), iv.cpu().numpy(), zf, tbar, TB_BINS, p_lo, L, nseg, min_used, BINS, t0, dt, nt, True, True)
     assert_not_vacuous(ref, rows, L, nt, True, False, "forms")
-    N = B + 4
-    rws = np.random.default_rng(3).permutation(N)[:B].astype(np.int32)
-    zres, zq = np.full((N, nb), np.nan, np.float32), np.full(N, np.nan, np.float32)
-    zres[rws], zq[rws] = zf, g["zq1"]
-    forms = (dict(zabs=T(zf, dev)), dict(zq1=T(g["zq1"], dev), ratio=T(g["ratio"], dev)), dict(zabs=T(zres, dev), rows=T(rws, dev)),
-             dict(zq1=T(zq, dev), ratio=T(g["ratio"], dev), rows=T(rws, dev)))
     for kw in forms:
         hist, stack = call_pdf(dev, tr, iv, tbar, prm, (t0, dt, nt, 0.0), flags=F_ZERO | F_REL | F_CLAMP, **kw)
         check_exact(hist, stack, ref, nt, sorted(kw))
@@ -235,12 +193,7 @@ def test_every_refusal_returns_its_code_and_touches_nothing(dev):
     prm = (0, L, nseg, 10, BINS)
     pdf = (0.0, 0.1, nt, 0.0)
 
-    def refused(code, **kw):
-        args = dict(prm=prm, pdf=pdf, flags=F_ZERO, outs="hs", zabs=z)
-        args.update(kw)
-        h, s = call_pdf(dev, tr, iv, tbar, args.pop("prm"), args.pop("pdf"), expect=code, **args)
-        assert (h is None or (h == -7).all()) and (s is None or (s == 3.0).all()), kw
-
+    refused = refusals(lambda **kw: call_pdf(dev, tr, iv, tbar, **kw), prm=prm, pdf=pdf, flags=F_ZERO, outs="hs", zabs=z)
     refused(-1, outs="")                                                              # both outputs missing
     refused(-1, zabs=None)                                                            # no redshift at all
     refused(-1, zabs=None, zq1=T(g["zq1"], dev))                                      # half of the factored pair
@@ -281,8 +234,7 @@ def call_ws(B, S, nb, L, nseg, nt):
 # ------------------------------------------------------------------------------------------------------------ end to end
 def test_flux_pdf_of_a_loader(dev):
     import torch
-    from test_p1d import _loader_case
-    m, mk, wav = _loader_case(dev)
+    m, mk, wav = loader_case(dev)
     kw = dict(n_segments=2, seg_len=24, min_used_frac=0.75, tbar_nbins=8, seed=6, t_min=0.0, t_max=1.2)
     for S in (0, 3):
         a = m.flux_pdf(mk(96), 1.8, 3.4, 3, 12, n_samples=S, batch_size=96, **kw)
@@ -343,28 +295,13 @@ def test_cli_predict_writes_flux_pdf_npz(dev, tmp_path):
     """predict mode with MODEL.PDF_NBINS: flux_pdf.npz next to flux_power.npz with the documented keys and shapes; its counts are
     the in-range counted pixels the port finds on the same loader"""
     import torch
-    from qfa_amd import cli, io, synthetic
+    from qfa_amd import cli
     from qfa_amd.dataloader import DeviceDataloader
     from qfa_amd.model import ForestStack
-    lam = dict(LAMMIN=1030.0, LAMMAX=1600.0, LOGLAM_DELTA=2e-3)
-    wav = io.wavelength_grid(lam["LAMMIN"], lam["LAMMAX"], lam["LOGLAM_DELTA"])
-    npix, nb, n = len(wav), int(np.sum(wav < 1215.67)), 24
-    p, mu = synthetic.mock_parameters(npix, nb, 4, seed=9)
-    b = synthetic.make_batch_numpy(p, mu, wav, nb, n, seed=91, masks=False)
-    data = tmp_path / "data"
-    data.mkdir()
-    names = [f"spec-{i:02d}.npz" for i in range(n)]
-    for i, name in enumerate(names):
-        np.savez(data / name, flux=b["flux"][i].astype(np.float64), error=b["error"][i].astype(np.float64), z=b["zqso"][i])
-    (tmp_path / "pred.csv").write_text("file\n" + "\n".join(names) + "\n")
-    m = make_model(dev, {"p": p, "mu": mu}, nb, npix - nb, 4)
-    m.save_to_npz(str(tmp_path), "model.npz")
+    c = cli_predict_case(dev, tmp_path)
+    wav, npix, nb, b, names, p, mu = c.wav, c.npix, c.nb, c.b, c.names, c.p, c.mu
     out = tmp_path / "out"
-    argv = ["--type", "predict", "--data_dir", str(data), "--catalog", str(tmp_path / "pred.csv"), "--output_dir", str(out),
-            "--opts", "MODEL.NH", "4", "MODEL.RESUME", str(tmp_path / "model.npz"), "MODEL.REFERENCE_C0_QUIRK", "False",
-            "DATA.LOGLAM_DELTA", "2e-3", "MODEL.FOREST_ZMIN", "1.6", "MODEL.FOREST_ZMAX", "3.6", "MODEL.FOREST_NBINS", "10",
-            "MODEL.N_SAMPLES", "2", "MODEL.P1D_SEGMENTS", "2", "MODEL.P1D_NZBINS", "3", "MODEL.P1D_MIN_USED_FRAC", "0.6",
-            "MODEL.PDF_NBINS", "12", "MODEL.PDF_TMAX", "1.2", "MODEL.PDF_CLAMP", "False"]
+    argv = c.argv(out, "MODEL.N_SAMPLES", "2", "MODEL.PDF_NBINS", "12", "MODEL.PDF_TMAX", "1.2", "MODEL.PDF_CLAMP", "False")
     assert cli.main(argv) == 0
     f, fp, t = np.load(out / "flux_pdf.npz"), np.load(out / "flux_power.npz"), np.load(out / "mean_transmission.npz")
     assert set(f.files) == {"z", "t_edges", "pdf", "err", "cov", "counts", "n_segments", "out_of_range", "std_over_draws", "total_cov"}

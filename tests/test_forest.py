@@ -15,55 +15,12 @@ import numpy as np
 import pytest
 
 import _forest_ref as R
+from _segment_harness import T, dev, geometry, make_model  # noqa: F401 (dev: the fixture)
 from conftest import GOLDEN, REPO
 
 pytestmark = pytest.mark.gpu
 U64 = 2.0 ** -53
 CONT_MIN = 0.05
-
-
-@pytest.fixture(scope="module")
-def dev():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    return torch.device("cuda:0")
-
-
-def T(x, dev):
-    import torch
-    x = np.asarray(x)
-    if x.dtype == bool:
-        return torch.tensor(x, dtype=torch.bool, device=dev)
-    if x.dtype == np.int32:
-        return torch.tensor(x, dtype=torch.int32, device=dev)
-    return torch.tensor(x, dtype=torch.float32, device=dev)
-
-
-def geometry(npix, nb, nh, B, S, seed, masks=True):
-    """mu ~ 1, small F, h ~ N(0, 1): c stays in [0.5, 2]; z = zq1 ratio - 1 with zq1 in [3, 4.5], ratio log-spaced 1030 .. 1215 A"""
-    rng = np.random.default_rng(seed)
-    p = {"F": (rng.uniform(-1, 1, (npix, nh)) * 0.1 / np.sqrt(nh)).astype(np.float32),
-         "Psi": np.full(npix, 0.01, np.float32), "omega": np.full(nb, 0.1, np.float32),
-         "tau0": np.float32(0.02), "c0": np.float32(0.3), "beta": np.float32(2.0)}
-    mu = (1.0 + 0.1 * np.sin(np.arange(npix) / 7.0)).astype(np.float32)
-    ratio = (10 ** np.linspace(np.log10(1030.0), np.log10(1215.0), nb) / 1215.67).astype(np.float32)
-    zq1 = rng.uniform(3.0, 4.5, B).astype(np.float32)
-    zfac = R.z_factored(zq1, ratio)                                  # what the factored form bins with
-    zabs = (zq1.astype(np.float64)[:, None] * ratio.astype(np.float64)[None, :] - 1.0 + rng.normal(0, 1e-4, (B, nb))).astype(np.float32)
-    h = np.clip(rng.normal(0, 1, (B, S, nh)), -3, 3).astype(np.float32)
-    error = rng.uniform(0.01, 0.1, (B, npix)).astype(np.float32)
-    flux = (rng.uniform(0.0, 1.0, (B, npix)) * mu[None, :] + error * rng.normal(0, 1, (B, npix))).astype(np.float32)
-    unc = rng.uniform(0.01, 0.05, (B, npix)).astype(np.float32)
-    mask = rng.random((B, npix)) > 0.2 if masks else None
-    return {"p": p, "mu": mu, "ratio": ratio, "zq1": zq1, "zfac": zfac, "zabs": zabs, "h": h, "error": error, "flux": flux,
-            "unc": unc, "mask": mask}
-
-
-def make_model(dev, g, nb, nr, nh):
-    from qfa_amd import QFA
-    m = QFA(nb, nr, nh, dev, model_params=g["p"])
-    m.mu = T(g["mu"], dev)
-    return m
 
 
 def call_c(m, flux, error, h, bins, *, zabs=None, mask=None, zq1=None, ratio=None, rows=None, row_stride=0, unc=None,

@@ -5,7 +5,6 @@ Bars (derived in tests/_p1d_ref.py): per mode |dP_m| <= (2 |X_m| e + e^2) / L + 
 (L + 4) u N; the valid / invalid pattern is exact, the port working on the very trans / ivar the GPU read.  Stack: N 2^-53 sum
 |terms| per entry against float64 sums of the GPU's own power / noise, counts exact.  The inputs are the transmission and inverse
 variance QFA.forest writes for tests/test_forest.py's `geometry` (continuum in [0.5, 2], 20 % masks)."""
-import ctypes as C
 import os
 import sys
 
@@ -14,56 +13,11 @@ import pytest
 
 import _p1d_ref as R
 from conftest import REPO
-from test_forest import T, geometry, make_model
+from _segment_harness import (TB_BINS, T, call_p1d as call_c, cli_predict_case, dev, forest_case, loader_case,  # noqa: F401 (dev: the fixture)
+                              make_model, redshift_forms, tbar_range, two_ranks)
 
 pytestmark = pytest.mark.gpu
 U64 = 2.0 ** -53
-TB_BINS = (1.5, 0.125, 17)                                    # z of `geometry` lies in [1.54, 3.5]
-
-
-@pytest.fixture(scope="module")
-def dev():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    return torch.device("cuda:0")
-
-
-def forest_case(dev, B, S, nb, seed, nh=4):
-    """trans / ivar (B, S, nb) as qfa_forest_f32 writes them, on the device and as numpy, with the geometry they came from"""
-    npix = nb + 20
-    g = geometry(npix, nb, nh, B, S, seed)
-    m = make_model(dev, g, nb, npix - nb, nh)
-    tr, iv, _ = m.forest(T(g["flux"], dev), T(g["error"], dev), T(g["zabs"], dev), T(g["mask"], dev), h=T(g["h"], dev), cont_min=0.05)
-    tbar = np.random.default_rng(seed + 1).uniform(0.3, 0.9, (S, TB_BINS[2])).astype(np.float32)
-    return g, m, tr, iv, tbar
-
-
-def call_c(dev, trans, ivar, tbar, prm, *, zabs=None, zq1=None, ratio=None, rows=None, flags=0x80, outs="pns", stack=None):
-    """qfa_p1d_f32 by hand on device tensors; prm = (p_lo, L, nseg, min_used, (z0, dz, nz)).  Returns power, noise, stack (numpy)"""
-    import torch
-    from qfa_amd import _lib
-    lib = _lib.lib()
-    B, S, Nb = trans.shape
-    p_lo, L, nseg, min_used, bins = prm
-    tb = T(tbar, dev).reshape(-1, TB_BINS[2]).contiguous()
-    ptr = lambda t: None if t is None else t.data_ptr()
-    bs = _lib.Batch()
-    bs.zabs, bs.zq1, bs.pix_ratio, bs.rows, bs.row_stride = ptr(zabs), ptr(zq1), ptr(ratio), ptr(rows), 0
-    pp = _lib.P1DParams(TB_BINS[0], TB_BINS[1], TB_BINS[2], int(tb.shape[0]), p_lo, L, nseg, min_used, bins[0], bins[1], bins[2])
-    M = L // 2
-    power = torch.full((B, S, nseg, M), -7.0, dtype=torch.float32, device=dev) if "p" in outs else None
-    noise = torch.full((B, S, nseg), -7.0, dtype=torch.float32, device=dev) if "n" in outs else None
-    if stack is None and "s" in outs:
-        stack = torch.full((S, bins[2], 2 + 2 * M), 3.0, dtype=torch.float64, device=dev)
-    need = lib.qfa_p1d_workspace_bytes(B * S, S, Nb, L, nseg, bins[2])
-    assert need > 0
-    ws = torch.empty(need, dtype=torch.uint8, device=dev)
-    st = lib.qfa_p1d_f32(C.c_void_p(trans.data_ptr()), C.c_void_p(ivar.data_ptr()), C.byref(bs), C.c_void_p(tb.data_ptr()), B, S, Nb,
-                         C.byref(pp), flags, C.c_void_p(ptr(power)), C.c_void_p(ptr(noise)), C.c_void_p(ptr(stack)),
-                         C.c_void_p(ws.data_ptr()), need, _lib.current_stream(dev))
-    torch.cuda.synchronize()
-    assert st == 0, st
-    return tuple(None if x is None else x.cpu().numpy() for x in (power, noise, stack))
 
 
 def check_segments(power, noise, ref, L, what):
@@ -112,19 +66,9 @@ def test_redshift_forms_give_identical_bits(dev):
     B, S, nb, L, nseg, p_lo = 9, 2, 80, 37, 2, 4
     g, m, tr, iv, tbar = forest_case(dev, B, S, nb, seed=21)
     prm = (p_lo, L, nseg, 25, (1.6, 0.45, 4))
-    zf = R.z_factored(g["zq1"], g["ratio"])                                           # the float32 z the factored form computes
-    a = call_c(dev, tr, iv, tbar, prm, zabs=T(zf, dev))
-    b = call_c(dev, tr, iv, tbar, prm, zq1=T(g["zq1"], dev), ratio=T(g["ratio"], dev))
-    N = B + 4
-    rows = np.random.default_rng(3).permutation(N)[:B].astype(np.int32)
-    zres = np.full((N, nb), np.nan, np.float32)
-    zres[rows] = zf
-    c = call_c(dev, tr, iv, tbar, prm, zabs=T(zres, dev), rows=T(rows, dev))
-    zq = np.full(N, np.nan, np.float32)
-    zq[rows] = g["zq1"]
-    d = call_c(dev, tr, iv, tbar, prm, zq1=T(zq, dev), ratio=T(g["ratio"], dev), rows=T(rows, dev))
+    a, *others = (call_c(dev, tr, iv, tbar, prm, **kw) for kw in redshift_forms(dev, g, B, nb)[1])
     assert a[2][:, :, 0].sum() > 0
-    for other in (b, c, d):
+    for other in others:
         for x, y in zip(a, other):
             assert np.array_equal(x, y)
 
@@ -242,24 +186,9 @@ def test_injected_cosine(dev):
     assert (noise[:, 0, 0] == np.float32(1.0) / np.float32(25.0)).all()
 
 
-def _loader_case(dev, **dl_kw):
-    from qfa_amd import synthetic
-    from qfa_amd.dataloader import DeviceDataloader
-    npix, nb, nh, B = 96, 48, 4, 96
-    wav = 10 ** (np.log10(synthetic.LYA) + (np.arange(npix) - nb + 0.5) * 1.2e-3)
-    assert int(np.sum(wav < synthetic.LYA)) == nb
-    p, mu = synthetic.mock_parameters(npix, nb, nh, seed=3)
-    b = synthetic.make_batch_numpy(p, mu, wav, nb, B, seed=33, masks=False)
-    dead = np.random.default_rng(4).random((B, npix)) < 0.1
-    flux, err = np.where(dead, np.float32(-999.0), b["flux"]), np.where(dead, np.float32(-999.0), b["error"])
-    m = make_model(dev, {"p": p, "mu": mu}, nb, npix - nb, nh)
-    mk = lambda bs: DeviceDataloader(flux, err, b["zqso"], wav, batch_size=bs, device=dev, shuffle=False, **dl_kw)
-    return m, mk, wav
-
-
 def test_flux_power_of_a_loader(dev):
     import torch
-    m, mk, wav = _loader_case(dev)
+    m, mk, wav = loader_case(dev)
     kw = dict(n_segments=2, seg_len=24, min_used_frac=0.75, tbar_nbins=8, seed=6)
     for S in (0, 4):
         a = m.flux_power(mk(96), 1.8, 3.4, 3, n_samples=S, batch_size=96, **kw)
@@ -293,11 +222,6 @@ def test_flux_power_of_a_loader(dev):
 FP_KW = dict(n_segments=2, seg_len=24, min_used_frac=0.75, tbar_nbins=8, n_samples=2, seed=6, batch_size=40)
 
 
-def _tbar_range(dv):
-    half = float(np.exp(0.5 * 25 * dv / 299792.458))                                  # flux_power's own: half a segment of 24
-    return (1.0 + 1.8) / half - 1.0, (1.0 + 3.4) * half - 1.0
-
-
 def _worker_flux_power(rank, world, port, q):
     import torch
     import torch.distributed as dist
@@ -305,10 +229,10 @@ def _worker_flux_power(rank, world, port, q):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     dist.init_process_group("gloo", rank=rank, world_size=world)
     dev = torch.device("cuda:0")
-    m, mk, wav = _loader_case(dev, rank=rank, world=world)
+    m, mk, wav = loader_case(dev, rank=rank, world=world)
     m.enable_data_parallel()
     ps = m.flux_power(mk(40), 1.8, 3.4, 3, **FP_KW)                                   # its own <T>, all-reduced, then its own sums
-    tb = m.mean_transmission(mk(40), *_tbar_range(ps.dv), 8, n_samples=2, seed=6, batch_size=40)
+    tb = m.mean_transmission(mk(40), *tbar_range(ps.dv), 8, n_samples=2, seed=6, batch_size=40)
     if rank == 0:
         q.put(np.concatenate([ps.buf.cpu().numpy().ravel(), tb.buf.cpu().numpy().ravel()]))
     dist.destroy_process_group()
@@ -319,22 +243,13 @@ def test_two_ranks_all_reduce_to_the_single_process_stack(dev):
     mean transmission is handed over, so that both sides form the contrast with the same float32 <T>: the stacks are then sums of
     the same terms in another grouping"""
     import torch
-    import torch.multiprocessing as mp
     from qfa_amd.model import ForestStack
-    from test_data_parallel import _collect
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = 31500 + os.getpid() % 2000
-    procs = [ctx.Process(target=_worker_flux_power, args=(r, 2, port, q)) for r in range(2)]
-    [pr.start() for pr in procs]
-    got = _collect(procs, q, 300)
-    [pr.join(60) for pr in procs]
-    assert all(pr.exitcode == 0 for pr in procs)
-    m, mk, wav = _loader_case(dev)
+    got = two_ranks(_worker_flux_power, 31500)
+    m, mk, wav = loader_case(dev)
     dv = 299792.458 * float(np.log(wav[1] / wav[0]))
     n1 = 2 * 3 * (2 + 2 * 12)
     two, tbuf = got[:n1].reshape(2, 3, 26), got[n1:].reshape(2, 4, 8)
-    z_lo, z_hi = _tbar_range(dv)
+    z_lo, z_hi = tbar_range(dv)
     tb = ForestStack(torch.tensor(tbuf, device=dev), z_lo, (z_hi - z_lo) / 8, 8)
     one = m.flux_power(mk(40), 1.8, 3.4, 3, tbar=tb, **FP_KW).buf.cpu().numpy()
     assert np.array_equal(two[:, :, 0], one[:, :, 0]) and one[:, :, 0].sum() > 40
@@ -344,26 +259,12 @@ def test_two_ranks_all_reduce_to_the_single_process_stack(dev):
 def test_cli_predict_writes_flux_power_npz(dev, tmp_path):
     """predict mode with MODEL.P1D_SEGMENTS: flux_power.npz next to mean_transmission.npz, formed with that file's stack"""
     import torch
-    from qfa_amd import cli, io, synthetic
+    from qfa_amd import cli
     from qfa_amd.model import ForestStack
-    lam = dict(LAMMIN=1030.0, LAMMAX=1600.0, LOGLAM_DELTA=2e-3)
-    wav = io.wavelength_grid(lam["LAMMIN"], lam["LAMMAX"], lam["LOGLAM_DELTA"])
-    npix, nb, n = len(wav), int(np.sum(wav < 1215.67)), 24
-    p, mu = synthetic.mock_parameters(npix, nb, 4, seed=9)
-    b = synthetic.make_batch_numpy(p, mu, wav, nb, n, seed=91, masks=False)
-    data = tmp_path / "data"
-    data.mkdir()
-    names = [f"spec-{i:02d}.npz" for i in range(n)]
-    for i, name in enumerate(names):
-        np.savez(data / name, flux=b["flux"][i].astype(np.float64), error=b["error"][i].astype(np.float64), z=b["zqso"][i])
-    (tmp_path / "pred.csv").write_text("file\n" + "\n".join(names) + "\n")
-    m = make_model(dev, {"p": p, "mu": mu}, nb, npix - nb, 4)
-    m.save_to_npz(str(tmp_path), "model.npz")
+    c = cli_predict_case(dev, tmp_path)
+    wav, npix, nb, b, names, p, mu = c.wav, c.npix, c.nb, c.b, c.names, c.p, c.mu
     out = tmp_path / "out"
-    argv = ["--type", "predict", "--data_dir", str(data), "--catalog", str(tmp_path / "pred.csv"), "--output_dir", str(out),
-            "--opts", "MODEL.NH", "4", "MODEL.RESUME", str(tmp_path / "model.npz"), "MODEL.REFERENCE_C0_QUIRK", "False",
-            "DATA.LOGLAM_DELTA", "2e-3", "MODEL.FOREST_ZMIN", "1.6", "MODEL.FOREST_ZMAX", "3.6", "MODEL.FOREST_NBINS", "10",
-            "MODEL.N_SAMPLES", "2", "MODEL.P1D_SEGMENTS", "2", "MODEL.P1D_NZBINS", "3", "MODEL.P1D_MIN_USED_FRAC", "0.6"]
+    argv = c.argv(out, "MODEL.N_SAMPLES", "2")
     assert cli.main(argv) == 0
     f, t = np.load(out / "flux_power.npz"), np.load(out / "mean_transmission.npz")
     L = nb // 2

@@ -5,7 +5,6 @@ a second DFT.
 Bars (derived in tests/_p1d_band_ref.py): Q_a within (n_a + 2) 2^-53 sum_m |w_m| (|P_m| + |N|); sum Q_a and sum Q_a Q_b within
 (n + 3) 2^-53 sum |terms| plus the propagated bar of Q; counts, zeros of invalid segments and the symmetry of the matrix exact.
 Inputs: tests/test_p1d.py's forest_case (20 % masks), NaN put under every unused pixel."""
-import ctypes as C
 import os
 import sys
 
@@ -15,19 +14,11 @@ import pytest
 import _p1d_band_ref as RB
 import _p1d_ref as R
 from conftest import REPO
-from test_forest import T
-from test_p1d import TB_BINS, _loader_case, call_c, forest_case
+from _segment_harness import (F_SYNC as SYNC, F_ZERO as ZERO, TB_BINS, T, call_p1d as call_c, call_segment, cli_predict_case, dev,  # noqa: F401 (dev: the fixture)
+                              forest_case, loader_case, redshift_forms, tbar_range, two_ranks)
 
 pytestmark = pytest.mark.gpu
 U64 = 2.0 ** -53
-ZERO, SYNC = 0x80, 0x20
-
-
-@pytest.fixture(scope="module")
-def dev():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    return torch.device("cuda:0")
 
 
 def masked_case(dev, B, S, nb, seed):
@@ -38,38 +29,18 @@ def masked_case(dev, B, S, nb, seed):
     return g, m, tr, iv, tbar
 
 
-def call_band(dev, trans, ivar, tbar, prm, band, weight, sub, *, zabs=None, zq1=None, ratio=None, rows=None, flags=ZERO | SYNC,
-              outs="bs", stack=None, nrows=None):
+def call_band(dev, trans, ivar, tbar, prm, band, weight, sub, *, flags=ZERO | SYNC, **kw):
     """qfa_p1d_band_f32 by hand; prm = (p_lo, L, nseg, min_used, (z0, dz, nz)); band (M,) ints, weight (M,) or None.  Returns
     (bandpower, stack) as numpy"""
     import torch
     from qfa_amd import _lib
-    lib = _lib.lib()
-    B, S, Nb = trans.shape
-    B = B if nrows is None else nrows
-    p_lo, L, nseg, min_used, bins = prm
     nband = int(max(np.max(band, initial=0), 0)) + 1 if not isinstance(band, tuple) else band[1]
     band = band[0] if isinstance(band, tuple) else band
-    tb = T(tbar, dev).reshape(-1, TB_BINS[2]).contiguous()
-    ptr = lambda t: None if t is None else t.data_ptr()
-    bs = _lib.Batch()
-    bs.zabs, bs.zq1, bs.pix_ratio, bs.rows, bs.row_stride = ptr(zabs), ptr(zq1), ptr(ratio), ptr(rows), 0
-    pp = _lib.P1DParams(TB_BINS[0], TB_BINS[1], TB_BINS[2], int(tb.shape[0]), p_lo, L, nseg, min_used, bins[0], bins[1], bins[2])
     bd = torch.tensor(np.append(np.asarray(band, np.int32), np.int32(-1)), device=dev)          # (never empty: L = 1 has M = 0)
     wd = None if weight is None else torch.tensor(np.append(np.asarray(weight, np.float32), np.float32(0)), device=dev)
-    qq = _lib.P1DBandParams(nband, bd.data_ptr(), ptr(wd), sub)
-    bp = torch.full((B, S, nseg, nband), -7.0, dtype=torch.float64, device=dev) if "b" in outs else None
-    if stack is None and "s" in outs:
-        stack = torch.full((S, bins[2], 1 + nband + nband * nband), 3.0, dtype=torch.float64, device=dev)
-    need = lib.qfa_p1d_band_workspace_bytes(B * S, S, Nb, L, nseg, bins[2], nband)
-    assert need > 0
-    ws = torch.empty(need, dtype=torch.uint8, device=dev)
-    st = lib.qfa_p1d_band_f32(C.c_void_p(trans.data_ptr()), C.c_void_p(ivar.data_ptr()), C.byref(bs), C.c_void_p(tb.data_ptr()), B, S, Nb,
-                              C.byref(pp), C.byref(qq), flags, C.c_void_p(ptr(bp)), C.c_void_p(ptr(stack)),
-                              C.c_void_p(ws.data_ptr()), need, _lib.current_stream(dev))
-    torch.cuda.synchronize()
-    assert st == 0, st
-    return tuple(None if x is None else x.cpu().numpy() for x in (bp, stack))
+    qq = _lib.P1DBandParams(nband, bd.data_ptr(), None if wd is None else wd.data_ptr(), sub)
+    return call_segment("qfa_p1d_band", dev, trans, ivar, tbar, prm, qq, (("b", (nband,), "float64"),), size=(nband,),
+                        stack_width=1 + nband + nband * nband, flags=flags, **kw)
 
 
 def reference(dev, g, tr, iv, tbar, prm, band, nband, weight, sub):
@@ -170,16 +141,9 @@ def test_redshift_forms_give_identical_bits(dev):
     g, m, tr, iv, tbar = masked_case(dev, B, S, nb, seed=21)
     prm = (p_lo, L, nseg, 25, (1.6, 0.45, 4))
     band = band_for(L, 5)
-    zf = R.z_factored(g["zq1"], g["ratio"])
-    a = call_band(dev, tr, iv, tbar, prm, band, None, 1, zabs=T(zf, dev))
-    b = call_band(dev, tr, iv, tbar, prm, band, None, 1, zq1=T(g["zq1"], dev), ratio=T(g["ratio"], dev))
-    N = B + 4
-    rows = np.random.default_rng(3).permutation(N)[:B].astype(np.int32)
-    zres = np.full((N, nb), np.nan, np.float32)
-    zres[rows] = zf
-    c = call_band(dev, tr, iv, tbar, prm, band, None, 1, zabs=T(zres, dev), rows=T(rows, dev))
+    a, *others = (call_band(dev, tr, iv, tbar, prm, band, None, 1, **kw) for kw in redshift_forms(dev, g, B, nb)[1][:3])
     assert a[1][:, :, 0].sum() > 0
-    for other in (b, c):
+    for other in others:
         for x, y in zip(a, other):
             assert np.array_equal(x, y)
 
@@ -249,7 +213,7 @@ def test_band_power_of_a_loader(dev):
     """band_power against the port on the concatenated batches (p1d on the whole loader in one call gives P and N), two batch sizes
     within the float64 summation bar, and flux_power's bits untouched by the shared loop"""
     import torch
-    m, mk, wav = _loader_case(dev)
+    m, mk, wav = loader_case(dev)
     dv = 299792.458 * float(np.log(wav[1] / wav[0]))
     edges = _edges(dv)
     for S in (0, 3):
@@ -311,11 +275,10 @@ def _worker_band_power(rank, world, port, q):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     dist.init_process_group("gloo", rank=rank, world_size=world)
     dev = torch.device("cuda:0")
-    m, mk, wav = _loader_case(dev, rank=rank, world=world)
+    m, mk, wav = loader_case(dev, rank=rank, world=world)
     m.enable_data_parallel()
     dv = 299792.458 * float(np.log(wav[1] / wav[0]))
-    from test_p1d import _tbar_range
-    tb = m.mean_transmission(mk(40), *_tbar_range(dv), 8, n_samples=2, seed=6, batch_size=40)
+    tb = m.mean_transmission(mk(40), *tbar_range(dv), 8, n_samples=2, seed=6, batch_size=40)
     ps = m.band_power(mk(40), 1.8, 3.4, 3, _edges(dv), tbar=tb, **DP_KW)
     if rank == 0:
         q.put(np.concatenate([ps.buf.cpu().numpy().ravel(), tb.buf.cpu().numpy().ravel()]))
@@ -326,23 +289,13 @@ def test_two_ranks_all_reduce_to_the_single_process_stack(dev):
     """band_power on two ranks against one process, both forming the contrast with the same all-reduced <T>: the stacks are sums
     of the same terms in another grouping"""
     import torch
-    import torch.multiprocessing as mp
     from qfa_amd.model import ForestStack
-    from test_data_parallel import _collect
-    from test_p1d import _tbar_range
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = 33500 + os.getpid() % 2000
-    procs = [ctx.Process(target=_worker_band_power, args=(r, 2, port, q)) for r in range(2)]
-    [pr.start() for pr in procs]
-    got = _collect(procs, q, 300)
-    [pr.join(60) for pr in procs]
-    assert all(pr.exitcode == 0 for pr in procs)
-    m, mk, wav = _loader_case(dev)
+    got = two_ranks(_worker_band_power, 33500)
+    m, mk, wav = loader_case(dev)
     dv = 299792.458 * float(np.log(wav[1] / wav[0]))
     n1 = 2 * 3 * 21
     two, tbuf = got[:n1].reshape(2, 3, 21), got[n1:].reshape(2, 4, 8)
-    z_lo, z_hi = _tbar_range(dv)
+    z_lo, z_hi = tbar_range(dv)
     tb = ForestStack(torch.tensor(tbuf, device=dev), z_lo, (z_hi - z_lo) / 8, 8)
     one = m.band_power(mk(40), 1.8, 3.4, 3, _edges(dv), tbar=tb, **DP_KW).buf.cpu().numpy()
     assert np.array_equal(two[:, :, 0], one[:, :, 0]) and one[:, :, 0].sum() > 40
@@ -353,27 +306,10 @@ def test_two_ranks_all_reduce_to_the_single_process_stack(dev):
 
 
 def test_cli_predict_writes_flux_power_bands_npz(dev, tmp_path):
-    from qfa_amd import cli, io, synthetic
-    from test_forest import make_model
-    lam = dict(LAMMIN=1030.0, LAMMAX=1600.0, LOGLAM_DELTA=2e-3)
-    wav = io.wavelength_grid(lam["LAMMIN"], lam["LAMMAX"], lam["LOGLAM_DELTA"])
-    npix, nb, n = len(wav), int(np.sum(wav < 1215.67)), 24
-    p, mu = synthetic.mock_parameters(npix, nb, 4, seed=9)
-    b = synthetic.make_batch_numpy(p, mu, wav, nb, n, seed=91, masks=False)
-    data = tmp_path / "data"
-    data.mkdir()
-    names = [f"spec-{i:02d}.npz" for i in range(n)]
-    for i, name in enumerate(names):
-        np.savez(data / name, flux=b["flux"][i].astype(np.float64), error=b["error"][i].astype(np.float64), z=b["zqso"][i])
-    (tmp_path / "pred.csv").write_text("file\n" + "\n".join(names) + "\n")
-    m = make_model(dev, {"p": p, "mu": mu}, nb, npix - nb, 4)
-    m.save_to_npz(str(tmp_path), "model.npz")
+    from qfa_amd import cli
+    c = cli_predict_case(dev, tmp_path)
     for S, out in ((2, tmp_path / "out2"), (0, tmp_path / "out0")):
-        argv = ["--type", "predict", "--data_dir", str(data), "--catalog", str(tmp_path / "pred.csv"), "--output_dir", str(out),
-                "--opts", "MODEL.NH", "4", "MODEL.RESUME", str(tmp_path / "model.npz"), "MODEL.REFERENCE_C0_QUIRK", "False",
-                "DATA.LOGLAM_DELTA", "2e-3", "MODEL.FOREST_ZMIN", "1.6", "MODEL.FOREST_ZMAX", "3.6", "MODEL.FOREST_NBINS", "10",
-                "MODEL.N_SAMPLES", str(S), "MODEL.P1D_SEGMENTS", "2", "MODEL.P1D_NZBINS", "3", "MODEL.P1D_MIN_USED_FRAC", "0.6",
-                "MODEL.P1D_NBANDS", "5"]
+        argv = c.argv(out, "MODEL.N_SAMPLES", str(S), "MODEL.P1D_NBANDS", "5")
         assert cli.main(argv) == 0
         f, old = np.load(out / "flux_power_bands.npz"), np.load(out / "flux_power.npz")
         keys = {"k_edges", "k_centers", "z_edges", "n", "mean", "cov"} | ({"cov_over_draws"} if S > 1 else set())

@@ -5,18 +5,14 @@ The port works on the very trans / ivar the GPU read.  Every count (n_a, n_seg, 
 within (terms) 2^-52 sum |term| of the port -- the bound on any order of summation derived in the port's docstring, not a measured
 tolerance.  The inputs are those of tests/test_p1d.py: the transmission and inverse variance QFA.forest writes for
 tests/test_forest.py's `geometry` (continuum in [0.5, 2], 20 % masks)."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 import _p1d_ref as RP
 import _variance_ref as R
-from test_forest import T
-from test_p1d import TB_BINS, forest_case
+from _segment_harness import F_SYNC, F_ZERO, TB_BINS, T, call_segment, case_shape, dev, forest_case, loader_case, redshift_forms, refusals  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-F_ZERO, F_SYNC = 0x80, 0x20
 BINS = (1.6, 0.45, 4)
 # (rows, L, nseg, p_lo): one wave's walk at L = 63 / 64 / 65, the block's at 240 (one trip, 16 idle lanes), 667 and 4096 (three and
 # sixteen trips), rows that leave the only chunk of 64 unfilled (17 x 3 = 51, 11 x 2 = 22, 16 x 3 = 48 segments per draw; more than one
@@ -27,50 +23,14 @@ CASES = [(1, 1, 1, 0), (3, 2, 2, 1), (17, 37, 3, 5), (33, 63, 2, 0), (33, 64, 2,
 VBINS = [(1, 0), (3, 1), (4, 4)]
 
 
-@pytest.fixture(scope="module")
-def dev():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    return torch.device("cuda:0")
-
-
-def case_shape(rows, L, nseg, p_lo):
-    """B, S, nb, min_used and the seed of a row of CASES: tests/test_p1d.py's rule"""
-    S = 3 if rows % 3 == 0 and rows > 3 else 1
-    return rows // S, S, p_lo + nseg * L + 3, max(1, int(np.ceil(0.78 * L))), 1000 + L
-
-
-def call_var(dev, trans, ivar, tbar, prm, var, *, zabs=None, zq1=None, ratio=None, rows=None, flags=F_ZERO, outs="ms", stack=None,
-             expect=0, ws_bytes=None):
+def call_var(dev, trans, ivar, tbar, prm, var, **kw):
     """qfa_variance_f32 by hand on device tensors; prm = (p_lo, L, nseg, min_used, (z0, dz, nz)), var = (e_lo, n_oct, sub, d_max).
-    Returns moments, stack (numpy).  Fresh outputs hold the sentinels -7 and 3.0"""
-    import torch
+    Returns moments, stack (numpy)"""
     from qfa_amd import _lib
-    lib = _lib.lib()
-    B, S, Nb = trans.shape
-    p_lo, L, nseg, min_used, bins = prm
-    tb = T(tbar, dev).reshape(-1, TB_BINS[2]).contiguous()
-    ptr = lambda t: None if t is None else t.data_ptr()
-    bs = _lib.Batch()
-    bs.zabs, bs.zq1, bs.pix_ratio, bs.rows, bs.row_stride = ptr(zabs), ptr(zq1), ptr(ratio), ptr(rows), 0
-    pp = _lib.P1DParams(TB_BINS[0], TB_BINS[1], TB_BINS[2], int(tb.shape[0]), p_lo, L, nseg, min_used, bins[0], bins[1], bins[2])
-    qq = _lib.VarParams(*var)
     nv = var[1] << var[2] if 0 <= var[2] <= 4 and 1 <= var[1] <= 64 else 1
     nv = max(1, min(64, nv))
-    mom = torch.full((B, S, nseg, 5, nv), -7.0, dtype=torch.float64, device=dev) if "m" in outs else None
-    if stack is None and "s" in outs:
-        stack = torch.full((S, bins[2], 2 + 5 * nv), 3.0, dtype=torch.float64, device=dev)
-    need = lib.qfa_variance_workspace_bytes(B * S, S, Nb, L, nseg, bins[2], nv)
-    if expect == 0:
-        assert need > 0
-    need = need if ws_bytes is None else ws_bytes
-    ws = torch.empty(max(need, 1 << 16), dtype=torch.uint8, device=dev)
-    st = lib.qfa_variance_f32(C.c_void_p(trans.data_ptr()), C.c_void_p(ivar.data_ptr()), C.byref(bs), C.c_void_p(tb.data_ptr()), B, S,
-                              Nb, C.byref(pp), C.byref(qq), flags, C.c_void_p(ptr(mom)), C.c_void_p(ptr(stack)),
-                              C.c_void_p(ws.data_ptr()), need, _lib.current_stream(dev))
-    torch.cuda.synchronize()
-    assert st == expect, st
-    return tuple(None if x is None else x.cpu().numpy() for x in (mom, stack))
+    return call_segment("qfa_variance", dev, trans, ivar, tbar, prm, _lib.VarParams(*var), (("m", (5, nv), "float64"),), size=(nv,),
+                        stack_width=2 + 5 * nv, **kw)
 
 
 def check(mom, stack, ref, what, extra_stack_bar=0.0):
@@ -134,15 +94,9 @@ def test_redshift_forms_against_the_port(dev, rows, L, nseg, p_lo):
     B, S, nb, min_used, seed = case_shape(rows, L, nseg, p_lo)
     g, m, tr, iv, tbar = forest_case(dev, B, S, nb, seed=seed)
     prm = (p_lo, L, nseg, min_used, BINS)
-    zf = RP.z_factored(g["zq1"], g["ratio"])                                          # the float32 z the factored form computes
+    zf, forms = redshift_forms(dev, g, B, nb)
     ref, var = reference(zf, tr.cpu().numpy(), iv.cpu().numpy(), tbar, prm, 3, 1)
     assert_not_vacuous(ref, rows, L, ref["nv"], "forms")
-    N = B + 4
-    rws = np.random.default_rng(3).permutation(N)[:B].astype(np.int32)
-    zres, zq = np.full((N, nb), np.nan, np.float32), np.full(N, np.nan, np.float32)
-    zres[rws], zq[rws] = zf, g["zq1"]
-    forms = (dict(zabs=T(zf, dev)), dict(zq1=T(g["zq1"], dev), ratio=T(g["ratio"], dev)), dict(zabs=T(zres, dev), rows=T(rws, dev)),
-             dict(zq1=T(zq, dev), ratio=T(g["ratio"], dev), rows=T(rws, dev)))
     first = None
     for kw in forms:
         mom, stack = call_var(dev, tr, iv, tbar, prm, var, **kw)
@@ -215,12 +169,7 @@ def test_every_refusal_returns_its_code_and_touches_nothing(dev):
     prm = (0, L, nseg, 10, BINS)
     var = (-8, 8, 1, R.FLT_MAX)
 
-    def refused(code, **kw):
-        args = dict(prm=prm, var=var, flags=F_ZERO, outs="ms", zabs=z)
-        args.update(kw)
-        mo, s = call_var(dev, tr, iv, tbar, args.pop("prm"), args.pop("var"), expect=code, **args)
-        assert (mo is None or (mo == -7.0).all()) and (s is None or (s == 3.0).all()), kw
-
+    refused = refusals(lambda **kw: call_var(dev, tr, iv, tbar, **kw), prm=prm, var=var, flags=F_ZERO, outs="ms", zabs=z)
     refused(-1, outs="")                                                              # both outputs missing
     refused(-1, zabs=None)                                                            # no redshift at all
     nan = float("nan")
@@ -242,8 +191,7 @@ def test_variance_function_of_a_loader(dev):
     tensor, factored and resident forms"""
     import torch
     from qfa_amd._lib import QFAHipError
-    from test_p1d import _loader_case
-    m, mk, wav = _loader_case(dev)
+    m, mk, wav = loader_case(dev)
     kw = dict(n_segments=2, seg_len=24, min_used_frac=0.75, tbar_nbins=8, seed=6)
     dl = mk(96)
     dv = 299792.458 * float(np.log(wav[1] / wav[0]))

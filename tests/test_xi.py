@@ -15,52 +15,20 @@ import pytest
 
 import _p1d_ref as RP
 import _xi_ref as R
-from test_forest import T, make_model
-from test_p1d import TB_BINS, forest_case
-from test_p1d import call_c as call_p1d
+from _segment_harness import (F_ZERO, TB_BINS, T, call_p1d, call_segment, case_shape, cli_predict_case, dev,  # noqa: F401 (dev: the fixture)
+                              forest_case, loader_case, redshift_forms, refusals)
 
 pytestmark = pytest.mark.gpu
 U64 = 2.0 ** -53
-F_ZERO, F_UNIT = 0x80, 0x400
+F_UNIT = 0x400
 
 
-@pytest.fixture(scope="module")
-def dev():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    return torch.device("cuda:0")
-
-
-def call_x(dev, trans, ivar, tbar, prm, nlag, *, sigma2=0.0, zabs=None, zq1=None, ratio=None, rows=None, flags=F_ZERO, outs="pns",
-           stack=None, expect=0):
+def call_x(dev, trans, ivar, tbar, prm, nlag, *, sigma2=0.0, **kw):
     """qfa_xi_f32 by hand on device tensors; prm = (p_lo, L, nseg, min_used, (z0, dz, nz)).  Returns pairs, noise0, stack (numpy)"""
-    import torch
     from qfa_amd import _lib
-    lib = _lib.lib()
-    B, S, Nb = trans.shape
-    p_lo, L, nseg, min_used, bins = prm
-    tb = T(tbar, dev).reshape(-1, TB_BINS[2]).contiguous()
-    ptr = lambda t: None if t is None else t.data_ptr()
-    bs = _lib.Batch()
-    bs.zabs, bs.zq1, bs.pix_ratio, bs.rows, bs.row_stride = ptr(zabs), ptr(zq1), ptr(ratio), ptr(rows), 0
-    pp = _lib.P1DParams(TB_BINS[0], TB_BINS[1], TB_BINS[2], int(tb.shape[0]), p_lo, L, nseg, min_used, bins[0], bins[1], bins[2])
-    xx = _lib.XiParams(nlag, sigma2)
     nl = max(1, nlag)
-    pairs = torch.full((B, S, nseg, 2, nl), -7.0, dtype=torch.float32, device=dev) if "p" in outs else None
-    noise0 = torch.full((B, S, nseg), -7.0, dtype=torch.float32, device=dev) if "n" in outs else None
-    if stack is None and "s" in outs:
-        stack = torch.full((S, bins[2], 2 + 5 * nl), 3.0, dtype=torch.float64, device=dev)
-    need = lib.qfa_xi_workspace_bytes(B * S, S, Nb, L, nseg, bins[2], nlag)
-    if expect == 0:
-        assert need > 0
-    need = max(need, 1 << 16)
-    ws = torch.empty(need, dtype=torch.uint8, device=dev)
-    st = lib.qfa_xi_f32(C.c_void_p(trans.data_ptr()), C.c_void_p(ivar.data_ptr()), C.byref(bs), C.c_void_p(tb.data_ptr()), B, S, Nb,
-                        C.byref(pp), C.byref(xx), flags, C.c_void_p(ptr(pairs)), C.c_void_p(ptr(noise0)), C.c_void_p(ptr(stack)),
-                        C.c_void_p(ws.data_ptr()), need, _lib.current_stream(dev))
-    torch.cuda.synchronize()
-    assert st == expect, st
-    return tuple(None if x is None else x.cpu().numpy() for x in (pairs, noise0, stack))
+    return call_segment("qfa_xi", dev, trans, ivar, tbar, prm, _lib.XiParams(nlag, sigma2), (("p", (2, nl), "float32"), ("n", (), "float32")),
+                        size=(nlag,), stack_width=2 + 5 * nl, **kw)
 
 
 def check_segments(pairs, noise0, ref, L, what):
@@ -96,12 +64,6 @@ def check_stack(got, pairs, noise0, ref, nz, what):
 CASES = [(1, 1, 1, 0, 1), (3, 2, 2, 1, 2), (17, 37, 3, 5, 37), (33, 64, 2, 0, 17), (16, 240, 3, 0, 120), (5, 667, 1, 3, 256),
          (4, 130, 1, 0, 63), (4, 130, 1, 0, 64), (4, 130, 1, 0, 65), (2, 4096, 1, 0, 5)]
 BINS = (1.6, 0.45, 4)
-
-
-def case_shape(rows, L, nseg, p_lo):
-    """B, S, nb, min_used and the seed of a row of CASES: tests/test_p1d.py's rule"""
-    S = 3 if rows % 3 == 0 and rows > 3 else 1
-    return rows // S, S, p_lo + nseg * L + 3, max(1, int(np.ceil(0.78 * L))), 1000 + L
 
 
 @pytest.mark.parametrize("rows,L,nseg,p_lo,nlag", CASES)
@@ -155,19 +117,9 @@ def test_redshift_forms_give_identical_bits(dev):
     B, S, nb, L, nseg, p_lo, nlag = 9, 2, 80, 37, 2, 4, 20
     g, m, tr, iv, tbar = forest_case(dev, B, S, nb, seed=21)
     prm = (p_lo, L, nseg, 25, BINS)
-    zf = RP.z_factored(g["zq1"], g["ratio"])                                         # the float32 z the factored form computes
-    a = call_x(dev, tr, iv, tbar, prm, nlag, zabs=T(zf, dev))
-    b = call_x(dev, tr, iv, tbar, prm, nlag, zq1=T(g["zq1"], dev), ratio=T(g["ratio"], dev))
-    N = B + 4
-    rows = np.random.default_rng(3).permutation(N)[:B].astype(np.int32)
-    zres = np.full((N, nb), np.nan, np.float32)
-    zres[rows] = zf
-    c = call_x(dev, tr, iv, tbar, prm, nlag, zabs=T(zres, dev), rows=T(rows, dev))
-    zq = np.full(N, np.nan, np.float32)
-    zq[rows] = g["zq1"]
-    d = call_x(dev, tr, iv, tbar, prm, nlag, zq1=T(zq, dev), ratio=T(g["ratio"], dev), rows=T(rows, dev))
+    a, *others = (call_x(dev, tr, iv, tbar, prm, nlag, **kw) for kw in redshift_forms(dev, g, B, nb)[1])
     assert a[2][:, :, 0].sum() > 0
-    for other in (b, c, d):
+    for other in others:
         for x, y in zip(a, other):
             assert np.array_equal(x, y)
 
@@ -229,13 +181,7 @@ def test_every_refusal_returns_its_code_and_touches_nothing(dev):
     z = T(g["zabs"], dev)
     prm = (0, L, nseg, 10, BINS)
 
-    def refused(code, **kw):
-        args = dict(prm=prm, nlag=nlag, sigma2=0.0, flags=F_ZERO, outs="pns", zabs=z)
-        args.update(kw)
-        p, n, s = call_x(dev, tr, iv, tbar, args.pop("prm"), args.pop("nlag"), expect=code, **args)
-        for x, fill in ((p, -7.0), (n, -7.0), (s, 3.0)):
-            assert x is None or (x == fill).all(), kw
-
+    refused = refusals(lambda **kw: call_x(dev, tr, iv, tbar, **kw), prm=prm, nlag=nlag, sigma2=0.0, flags=F_ZERO, outs="pns", zabs=z)
     refused(-1, outs="")                                                              # all three outputs missing
     refused(-1, zabs=None)                                                            # no redshift at all
     refused(-1, zabs=None, zq1=T(g["zq1"], dev))                                      # half of the factored pair
@@ -270,11 +216,6 @@ def test_every_refusal_returns_its_code_and_touches_nothing(dev):
 
 
 # ------------------------------------------------------------------------------------------------------------ end to end
-def _loader_case(dev):
-    from test_p1d import _loader_case as lc
-    return lc(dev)
-
-
 def sum_abs_bound(buf, nlag):
     """an upper bound of sum |terms| behind every entry of a stack (S, nz, 2 + 5 nlag), from the stack itself: the entries whose
     terms are >= 0 are their own; sum |A_l| <= sqrt(n sum A_l^2) and sum |A_l W_l| <= sqrt(sum A_l^2 sum W_l^2) (Cauchy-Schwarz)"""
@@ -288,7 +229,7 @@ def sum_abs_bound(buf, nlag):
 
 def test_flux_correlation_of_a_loader(dev):
     import torch
-    m, mk, wav = _loader_case(dev)
+    m, mk, wav = loader_case(dev)
     kw = dict(n_segments=2, seg_len=24, min_used_frac=0.75, tbar_nbins=8, seed=6, sigma2_lss=0.05)
     for S in (0, 3):
         a = m.flux_correlation(mk(96), 1.8, 3.4, 3, 10, n_samples=S, batch_size=96, **kw)
@@ -316,28 +257,13 @@ def test_flux_correlation_of_a_loader(dev):
 
 def test_cli_predict_writes_flux_correlation_npz(dev, tmp_path):
     """predict mode with MODEL.XI_NLAGS: flux_correlation.npz next to flux_power.npz, with the documented keys"""
-    from qfa_amd import cli, io, synthetic
-    lam = dict(LAMMIN=1030.0, LAMMAX=1600.0, LOGLAM_DELTA=2e-3)
-    wav = io.wavelength_grid(lam["LAMMIN"], lam["LAMMAX"], lam["LOGLAM_DELTA"])
-    npix, nb, n = len(wav), int(np.sum(wav < 1215.67)), 24
-    p, mu = synthetic.mock_parameters(npix, nb, 4, seed=9)
-    b = synthetic.make_batch_numpy(p, mu, wav, nb, n, seed=91, masks=False)
-    data = tmp_path / "data"
-    data.mkdir()
-    names = [f"spec-{i:02d}.npz" for i in range(n)]
-    for i, name in enumerate(names):
-        np.savez(data / name, flux=b["flux"][i].astype(np.float64), error=b["error"][i].astype(np.float64), z=b["zqso"][i])
-    (tmp_path / "pred.csv").write_text("file\n" + "\n".join(names) + "\n")
-    m = make_model(dev, {"p": p, "mu": mu}, nb, npix - nb, 4)
-    m.save_to_npz(str(tmp_path), "model.npz")
+    from qfa_amd import cli
+    c = cli_predict_case(dev, tmp_path)
+    wav, nb = c.wav, c.nb
     out = tmp_path / "out"
     L = nb // 2
     nlag = min(12, L)
-    argv = ["--type", "predict", "--data_dir", str(data), "--catalog", str(tmp_path / "pred.csv"), "--output_dir", str(out),
-            "--opts", "MODEL.NH", "4", "MODEL.RESUME", str(tmp_path / "model.npz"), "MODEL.REFERENCE_C0_QUIRK", "False",
-            "DATA.LOGLAM_DELTA", "2e-3", "MODEL.FOREST_ZMIN", "1.6", "MODEL.FOREST_ZMAX", "3.6", "MODEL.FOREST_NBINS", "10",
-            "MODEL.N_SAMPLES", "2", "MODEL.P1D_SEGMENTS", "2", "MODEL.P1D_NZBINS", "3", "MODEL.P1D_MIN_USED_FRAC", "0.6",
-            "MODEL.XI_NLAGS", str(nlag), "MODEL.XI_SIGMA2_LSS", "0.02"]
+    argv = c.argv(out, "MODEL.N_SAMPLES", "2", "MODEL.XI_NLAGS", str(nlag), "MODEL.XI_SIGMA2_LSS", "0.02")
     assert cli.main(argv) == 0
     f, fp = np.load(out / "flux_correlation.npz"), np.load(out / "flux_power.npz")
     assert set(f.files) == {"lags_kms", "z_centers", "z_edges", "xi", "xi_raw", "err", "n", "sum_w", "seg_len", "dv", "sums"}

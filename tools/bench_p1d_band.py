@@ -11,19 +11,16 @@ warm-up call, and (b) - (a), what the band reduction adds to the call.
 
     python tools/bench_p1d_band.py [--shapes B:Nb:nseg:S ...] [--iters 7] [--nz 8] [--nband 35] [--out profiles/p1d_band_bench.jsonl]"""
 import argparse
-import json
 import os
 import sys
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
-sys.path.insert(0, os.path.join(REPO, "tools"))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+from _segment_bench import REPO, inputs, ms, time_ms, write  # noqa: E402
 
 
 def main():
-    import numpy as np
     import torch
-    from bench_p1d import time_ms
     from qfa_amd import QFA
     from qfa_amd.model import P1DBandStack, P1DStack
     ap = argparse.ArgumentParser()
@@ -34,27 +31,16 @@ def main():
     ap.add_argument("--out", default=os.path.join(REPO, "profiles", "p1d_band_bench.jsonl"))
     a = ap.parse_args()
     dev = torch.device("cuda:0")
-    lines = []
     for spec in a.shapes:
-        B, nb, nseg, S = (int(x) for x in spec.split(":"))
-        L, nT, nz, nband, dv = nb // nseg, 64, a.nz, a.nband, 69.0
-        M = L // 2
-        min_used = int(np.ceil(0.75 * L))
+        c = inputs(spec, a.nz, dev)
+        B, nb, nseg, S, L, nz, min_used, trans, ivar, tbar = c.B, c.nb, c.nseg, c.S, c.L, c.nz, c.min_used, c.trans, c.ivar, c.tbar
+        okz, row, z0, dz = c.okz, c.row, c.z0, c.dz
+        nband, dv, M = a.nband, 69.0, L // 2
         m = QFA(nb, 8, 4, dev)
-        torch.manual_seed(0)
-        trans = torch.rand((B, S, nb), device=dev) * 1.2
-        ivar = 10.0 + 90.0 * torch.rand((B, S, nb), device=dev)
-        ivar.mul_(torch.rand((B, S, nb), device=dev) > 0.2)               # 20 % unused pixels: segments on both sides of min_used
-        zq1 = (3.0 + 1.5 * torch.rand(B, device=dev)).contiguous()
-        ratio = torch.tensor((10 ** np.linspace(np.log10(1030.0), np.log10(1215.0), nb) / 1215.67).astype(np.float32), device=dev)
-        zabs = (zq1[:, None] * ratio[None, :] - 1.0).contiguous()
-        zT0, dzT = np.float32(1.5), np.float32(2.1 / nT)
-        z0, dz = np.float32(1.6), np.float32(1.8 / nz)
-        tbar = (0.3 + 0.6 * torch.rand((S, nT), device=dev)).contiguous()
         edges = P1DBandStack.linear_k_edges(L, dv, nband)
         stack = P1DStack.zeros(S, z0, dz, nz, L, dv, dev)
         bstack = P1DBandStack.zeros(S, z0, dz, nz, L, dv, edges, dev)
-        kw = dict(zabs=zabs, tbar=tbar, tbar_bins=(zT0, dzT, nT), seg_len=L, n_segments=nseg, min_used=min_used)
+        kw = c.kw
 
         def p1d_stack():
             stack.buf.zero_()
@@ -69,10 +55,6 @@ def main():
         idx = torch.arange(M, device=dev)
         A[idx, band[:M].long().clamp_min(0)] = torch.where(band[:M] >= 0, weight[:M].double(), torch.zeros((), dtype=torch.float64, device=dev))
         est = torch.zeros_like(bstack.buf)
-        zc = zabs[:, torch.arange(nseg, device=dev) * L + L // 2]
-        kz = torch.floor((zc - z0) * (np.float32(1.0) / dz)).long()
-        okz = (kz >= 0) & (kz < nz)
-        row = torch.arange(S, device=dev)[None, :, None] * nz + kz.clamp(0, nz - 1)[:, None, :]     # (B, S, nseg)
 
         def eager():
             est.zero_()
@@ -90,20 +72,15 @@ def main():
         scale = est.abs().amax(-1, keepdim=True).clamp_min(1e-300)
         rel = float(((bstack.buf - est).abs() / scale).max())
         rec = {"shape": {"B": B, "Nb": nb, "nseg": nseg, "L": L, "S": S, "nz": nz, "nband": nband, "min_used": min_used},
-               "p1d_stack_ms": {"median": t_a[0], "min": t_a[1], "max": t_a[2]},
-               "band_stack_ms": {"median": t_b[0], "min": t_b[1], "max": t_b[2]},
-               "eager_ms": {"median": t_c[0], "min": t_c[1], "max": t_c[2]},
+               "p1d_stack_ms": ms(t_a),
+               "band_stack_ms": ms(t_b),
+               "eager_ms": ms(t_c),
                "band_minus_p1d_ms": t_b[0] - t_a[0], "band_minus_p1d_over_p1d": (t_b[0] - t_a[0]) / t_a[0],
                "eager_over_band": t_c[0] / t_b[0], "max_diff_of_stacks_over_row_max": rel, "iters": a.iters,
                "device": torch.cuda.get_device_name(0)}
-        print(json.dumps(rec), flush=True)
-        lines.append(json.dumps(rec))
-        del trans, ivar, tbar, stack, bstack, est
+        write(a.out, rec)
+        del c, trans, ivar, tbar, stack, bstack, est
         torch.cuda.empty_cache()
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "a") as f:
-        for ln in lines:
-            f.write(ln + "\n")
 
 
 if __name__ == "__main__":

@@ -9,21 +9,15 @@ take at 4 TB/s that the fused call reaches.
     python tools/bench_variance.py [--shapes B:Nb:nseg:S ...] [--iters 7] [--nz 8] [--e_lo -12] [--n_oct 14] [--sub 1]
                                    [--out profiles/variance_bench.jsonl]"""
 import argparse
-import json
 import os
 import sys
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
-sys.path.insert(0, os.path.join(REPO, "tools"))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-from bench_p1d import time_ms  # noqa: E402
-
-HBM_BYTES_PER_S = 4.0e12                                     # what the project's streaming kernels reach (DESIGN.md)
+from _segment_bench import REPO, floor_ms, inputs, ms, time_ms, write  # noqa: E402
 
 
 def main():
-    import numpy as np
     import torch
     from qfa_amd import QFA
     from qfa_amd.model import VarianceStack
@@ -39,30 +33,13 @@ def main():
     dev = torch.device("cuda:0")
     nv, c0 = a.n_oct << a.sub, (a.e_lo + 127) << a.sub
     for spec in a.shapes:
-        B, nb, nseg, S = (int(x) for x in spec.split(":"))
-        L, nT, nz = nb // nseg, 64, a.nz
-        min_used = int(np.ceil(0.75 * L))
+        c = inputs(spec, a.nz, dev, trans_lo=-0.05, ivar_of=lambda u: torch.exp(u * 6.0))
+        B, nb, nseg, S, L, nz, min_used, trans, ivar, tbar = c.B, c.nb, c.nseg, c.S, c.L, c.nz, c.min_used, c.trans, c.ivar, c.tbar
+        kT, okT, okz, row, z0, dz = c.kT, c.okT, c.okz, c.row, c.z0, c.dz
+        # (ivar over 2.6 decades: v spreads over some 9 octaves)
         m = QFA(nb, 8, 8 if nb < 1000 else 16, dev)
-        torch.manual_seed(0)
-        trans = torch.rand((B, S, nb), device=dev) * 1.2 - 0.05
-        ivar = torch.exp(torch.rand((B, S, nb), device=dev) * 6.0)       # ivar over 2.6 decades: v spreads over some 9 octaves
-        ivar.mul_(torch.rand((B, S, nb), device=dev) > 0.2)               # 20 % unused pixels: segments on both sides of min_used
-        zq1 = (3.0 + 1.5 * torch.rand(B, device=dev)).contiguous()
-        ratio = torch.tensor((10 ** np.linspace(np.log10(1030.0), np.log10(1215.0), nb) / 1215.67).astype(np.float32), device=dev)
-        zabs = (zq1[:, None] * ratio[None, :] - 1.0).contiguous()
-        zT0, dzT = np.float32(1.5), np.float32(2.1 / nT)
-        z0, dz = np.float32(1.6), np.float32(1.8 / nz)
-        tbar = (0.3 + 0.6 * torch.rand((S, nT), device=dev)).contiguous()
-        kT = torch.floor((zabs - zT0) * (np.float32(1.0) / dzT)).long()
-        okT = (kT >= 0) & (kT < nT)
-        kT.clamp_(0, nT - 1)
-        zc = zabs[:, torch.arange(nseg, device=dev) * L + L // 2]
-        kz = torch.floor((zc - z0) * (np.float32(1.0) / dz)).long()
-        okz = (kz >= 0) & (kz < nz)
-        row = torch.arange(S, device=dev)[None, :, None] * nz + kz.clamp(0, nz - 1)[:, None, :]     # (B, S, nseg)
         stack = VarianceStack.zeros(S, z0, dz, nz, L, a.e_lo, a.n_oct, a.sub, None, dev)
-        kw = dict(zabs=zabs, tbar=tbar, tbar_bins=(zT0, dzT, nT), seg_len=L, n_segments=nseg, min_used=min_used, e_lo=a.e_lo,
-                  n_oct=a.n_oct, sub=a.sub)
+        kw = dict(c.kw, e_lo=a.e_lo, n_oct=a.n_oct, sub=a.sub)
 
         def fused_stack():
             stack.buf.zero_()
@@ -111,22 +88,18 @@ def main():
         counts_equal = bool(torch.equal(got[0], sums[0]))
         assert abs(got[0].sum().item() - sums[0].sum().item()) <= 1e-6 * sums[0].sum().item(), "the counted pixels differ"
         assert torch.allclose(got.reshape(5, S * nz, nv).sum(-1), sums.reshape(5, S * nz, nv).sum(-1), rtol=1e-5, atol=0.0), "the sums differ"
-        floor_ms = nsegs * L * 8 / HBM_BYTES_PER_S * 1e3
         rec = {"shape": {"B": B, "Nb": nb, "nseg": nseg, "L": L, "S": S, "nz": nz, "nv": nv, "e_lo": a.e_lo, "sub": a.sub,
                          "min_used": min_used},
-               "fused_stack_ms": {"median": t_stack[0], "min": t_stack[1], "max": t_stack[2]},
-               "fused_stack_and_moments_ms": {"median": t_all[0], "min": t_all[1], "max": t_all[2]},
-               "eager_ms": {"median": t_eager[0], "min": t_eager[1], "max": t_eager[2]},
+               "fused_stack_ms": ms(t_stack),
+               "fused_stack_and_moments_ms": ms(t_all),
+               "eager_ms": ms(t_eager),
                "eager_over_fused_stack": t_eager[0] / t_stack[0], "eager_over_fused_all": t_eager[0] / t_all[0],
                "counts_equal": counts_equal, "counted_fraction": float(sums[0].sum().item() / max(1.0, head[:, 1].sum().item())),
                "occupied_bins": int((sums[0].reshape(S * nz, nv).sum(0) > 0).sum().item()),
-               "bytes_read": nsegs * L * 8, "floor_ms_at_4TBs": floor_ms,
-               "fraction_of_floor": floor_ms / t_stack[0], "iters": a.iters, "device": torch.cuda.get_device_name(0)}
-        print(json.dumps(rec), flush=True)
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "a") as f:                                        # (line by line: a later shape may not fit the device)
-            f.write(json.dumps(rec) + "\n")
-        del stack, head, sums, trans, ivar, tbar
+               "bytes_read": nsegs * L * 8, "floor_ms_at_4TBs": floor_ms(nsegs, L),
+               "fraction_of_floor": floor_ms(nsegs, L) / t_stack[0], "iters": a.iters, "device": torch.cuda.get_device_name(0)}
+        write(a.out, rec)
+        del c, stack, head, sums, trans, ivar, tbar
         torch.cuda.empty_cache()
 
 

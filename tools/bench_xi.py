@@ -8,19 +8,15 @@ algorithmic flops and the rate they give.
 
     python tools/bench_xi.py [--shapes B:Nb:nseg:S ...] [--iters 7] [--nz 8] [--out profiles/xi_bench.jsonl]"""
 import argparse
-import json
 import os
 import sys
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
-sys.path.insert(0, os.path.join(REPO, "tools"))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-from bench_p1d import time_ms  # noqa: E402
+from _segment_bench import REPO, inputs, ms, time_ms, write  # noqa: E402
 
 
 def main():
-    import numpy as np
     import torch
     from qfa_amd import QFA
     from qfa_amd.model import XiStack
@@ -34,31 +30,13 @@ def main():
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     for spec in a.shapes:
-        B, nb, nseg, S = (int(x) for x in spec.split(":"))
-        L, nT, nz = nb // nseg, 64, a.nz
-        min_used = int(np.ceil(0.75 * L))
+        c = inputs(spec, a.nz, dev)
+        B, nb, nseg, S, L, nz, min_used, trans, ivar, tbar = c.B, c.nb, c.nseg, c.S, c.L, c.nz, c.min_used, c.trans, c.ivar, c.tbar
+        kT, okT, okz, row, z0, dz = c.kT, c.okT, c.okz, c.row, c.z0, c.dz
         m = QFA(nb, 8, 4, dev)
-        torch.manual_seed(0)
-        trans = torch.rand((B, S, nb), device=dev) * 1.2
-        ivar = 10.0 + 90.0 * torch.rand((B, S, nb), device=dev)
-        ivar.mul_(torch.rand((B, S, nb), device=dev) > 0.2)               # 20 % unused pixels: segments on both sides of min_used
-        zq1 = (3.0 + 1.5 * torch.rand(B, device=dev)).contiguous()
-        ratio = torch.tensor((10 ** np.linspace(np.log10(1030.0), np.log10(1215.0), nb) / 1215.67).astype(np.float32), device=dev)
-        zabs = (zq1[:, None] * ratio[None, :] - 1.0).contiguous()
-        zT0, dzT = np.float32(1.5), np.float32(2.1 / nT)
-        z0, dz = np.float32(1.6), np.float32(1.8 / nz)
-        tbar = (0.3 + 0.6 * torch.rand((S, nT), device=dev)).contiguous()
-        kT = torch.floor((zabs - zT0) * (np.float32(1.0) / dzT)).long()
-        okT = (kT >= 0) & (kT < nT)
-        kT.clamp_(0, nT - 1)
-        zc = zabs[:, torch.arange(nseg, device=dev) * L + L // 2]
-        kz = torch.floor((zc - z0) * (np.float32(1.0) / dz)).long()
-        okz = (kz >= 0) & (kz < nz)
-        row = torch.arange(S, device=dev)[None, :, None] * nz + kz.clamp(0, nz - 1)[:, None, :]     # (B, S, nseg)
         for nlag in sorted({min(64, L), L // 2}):
             stack = XiStack.zeros(S, z0, dz, nz, L, nlag, 69.0, dev)
-            kw = dict(zabs=zabs, tbar=tbar, tbar_bins=(zT0, dzT, nT), seg_len=L, n_segments=nseg, min_used=min_used, n_lags=nlag,
-                      sigma2_lss=a.sigma2)
+            kw = dict(c.kw, n_lags=nlag, sigma2_lss=a.sigma2)
 
             def fused_stack():
                 stack.buf.zero_()
@@ -98,8 +76,8 @@ def main():
             eager_bytes = nsegs * (12 * 4 * L + 2 * 8 * (L + 1) + 2 * 4 * 2 * L + 2 * 8 * (2 + 5 * nlag))
             t_stack, t_all = time_ms(fused_stack, a.iters), time_ms(fused_all, a.iters)
             rec = {"shape": {"B": B, "Nb": nb, "nseg": nseg, "L": L, "S": S, "nz": nz, "nlag": nlag, "min_used": min_used},
-                   "fused_stack_ms": {"median": t_stack[0], "min": t_stack[1], "max": t_stack[2]},
-                   "fused_stack_and_segments_ms": {"median": t_all[0], "min": t_all[1], "max": t_all[2]}}
+                   "fused_stack_ms": ms(t_stack),
+                   "fused_stack_and_segments_ms": ms(t_all)}
             if eager_bytes <= a.eager_bytes:
                 t_eager = time_ms(eager, a.iters)
                 fused_stack()
@@ -110,7 +88,7 @@ def main():
                 scale = torch.cat([stack.buf[:, :, :2].abs()] + [stack.buf[:, :, 2 + i * nlag:2 + (i + 1) * nlag].abs().amax(-1, keepdim=True)
                                                                  .expand(-1, -1, nlag) for i in range(5)], -1)
                 rel = float(((stack.buf - est).abs() / scale.clamp_min(1e-300))[scale > 0].max())
-                rec.update({"eager_ms": {"median": t_eager[0], "min": t_eager[1], "max": t_eager[2]},
+                rec.update({"eager_ms": ms(t_eager),
                             "eager_over_fused_stack": t_eager[0] / t_stack[0], "eager_over_fused_all": t_eager[0] / t_all[0],
                             "max_diff_of_stacks_over_lag0": rel})
             else:
@@ -120,13 +98,10 @@ def main():
             flops = nsegs * 2 * 2 * nlag * (L - (nlag - 1) / 2.0)
             rec.update({"algorithmic_flops": flops, "fused_stack_TFLOPs": flops / t_stack[0] * 1e-9, "iters": a.iters,
                         "device": torch.cuda.get_device_name(0)})
-            print(json.dumps(rec), flush=True)
-            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-            with open(a.out, "a") as f:                                        # (line by line: a later shape may not fit the device)
-                f.write(json.dumps(rec) + "\n")
+            write(a.out, rec)
             del stack, est
             torch.cuda.empty_cache()
-        del trans, ivar, tbar
+        del c, trans, ivar, tbar
         torch.cuda.empty_cache()
 
 
