@@ -19,22 +19,63 @@ const double kLymanLam[30] = {1215.6701, 1025.7222, 972.5367, 949.7430, 937.8034
                               914.5762,  914.2861,  914.0385, 913.8256, 913.6411, 913.4803, 913.3391, 913.2146,
                               913.1042,  913.0059,  912.9179, 912.8389, 912.7676, 912.7032};
 
+// the four models of the mean optical depth: tau(z) = (amp ((1 + z) scale)^expo + off) x the series line's coefficient
+struct TauModel { double amp, scale, expo, off; };
+const TauModel *tau_model(int which) {
+    static const TauModel becker{0.751, 1.0 / 4.5, 2.90, -0.132}, fg{0.0018, 1.0, 3.92, 0.0}, kamble{5.54e-3, 1.0, 3.182, 0.0},
+        mock{0.2231435513142097, 1.0 / 3.25, 3.2, 0.0};
+    switch (which) {
+        case QFA_TAU_BECKER: return &becker;
+        case QFA_TAU_FG: return &fg;
+        case QFA_TAU_KAMBLE: return &kamble;
+        case QFA_TAU_MOCK: return &mock;
+        default: return nullptr;
+    }
+}
+double lyman_coeff(int i) { return kLymanLam[i] * kLymanF[i] / (kLymanLam[0] * kLymanF[0]); }
+
+// The checks every call on a batch shares, in the order that decides the returned code: the pointers (`other`: the call's own are
+// all there), the parameters, the batch, the shape, the workspace (workspace_bytes NULL: the caller checks a workspace of its own).
+int check_call(const qfa_params_t *p, const qfa_batch_t *b, const qfa_tau_t *tau, bool other, int B, int Npix, int Nb, int Nh,
+               const size_t *workspace_bytes) {
+    if (!p || !b || !tau || !other) return QFA_E_NULL;
+    if (!p->F || !p->Psi || !p->tau0 || !p->c0 || !p->beta || (Nb > 0 && !p->omega)) return QFA_E_NULL;
+    if (int e = check_batch(*b, Npix, Nb)) return e;
+    if (int e = check_shape(B, Npix, Nb, Nh)) return e;
+    if (workspace_bytes && *workspace_bytes < make_layout(B, Npix, Nh).total * sizeof(float)) return QFA_E_WORKSPACE;
+    return 0;
+}
+
+// N_h -> the instantiation of the step's host code: KP = 8 and 16 here, the N_h = 17..32 build in qfa_k32.hip
+template <class R8, class R16, class R32>
+int by_kp(int Nh, R8 run8, R16 run16, R32 run32) {
+    switch (kp_for(Nh)) {
+        case 8: return run8();
+        case 16: return run16();
+        default: return run32();
+    }
+}
+
+// The bias corrections of Adam's step i.  The reference mixes Python floats (double) with float32 tensors: every scalar is
+// formed in double and rounded to float32 once, exactly where torch would round it.
+struct AdamBias { float bc1, bc2; };
+AdamBias adam_bias(double b1, double b2, int i) {
+    return AdamBias{(float)(1.0 - pow(b1, (double)(i + 1))), (float)(1.0 - pow(b2, (double)(i + 1)))};
+}
+
 }  // namespace
 
 // the E-step of the EM update of F (qfa_estep.h; called by qfa_em.hip)
 int qfa_estep_check(const qfa_params_t *p, const qfa_batch_t *b, const qfa_tau_t *tau, int B, int Npix, int Nb, int Nh) {
-    if (!p || !b || !tau) return QFA_E_NULL;
-    if (!p->F || !p->Psi || !p->tau0 || !p->c0 || !p->beta || (Nb > 0 && !p->omega)) return QFA_E_NULL;
-    if (int e = check_batch(*b, Npix, Nb)) return e;
-    return check_shape(B, Npix, Nb, Nh);
+    return check_call(p, b, tau, true, B, Npix, Nb, Nh, nullptr);
 }
 
 int qfa_estep(const qfa_params_t &p, const qfa_batch_t &b, const qfa_tau_t &tau, int B, int Npix, int Nb, int Nh, float *nll,
               float *ws, hipStream_t st, QfaEStep *out) {
     const qfa_batch_t bb = norm_batch(b, Npix);
-    if (kp_for(Nh) == 8) return run_estep<8>(p, bb, tau, B, Npix, Nb, Nh, nll, ws, st, out);
-    if (kp_for(Nh) == 16) return run_estep<16>(p, bb, tau, B, Npix, Nb, Nh, nll, ws, st, out);
-    return qfa_k32_estep(p, bb, tau, B, Npix, Nb, Nh, nll, ws, st, out);
+    return by_kp(Nh, [&] { return run_estep<8>(p, bb, tau, B, Npix, Nb, Nh, nll, ws, st, out); },
+                 [&] { return run_estep<16>(p, bb, tau, B, Npix, Nb, Nh, nll, ws, st, out); },
+                 [&] { return qfa_k32_estep(p, bb, tau, B, Npix, Nb, Nh, nll, ws, st, out); });
 }
 
 extern "C" {
@@ -50,19 +91,13 @@ int qfa_abi_version(void) { return QFA_ABI_VERSION; }
 int qfa_tau_model(int which, int series, qfa_tau_t *out) {
     if (!out) return QFA_E_NULL;
     if (series < 1 || series > 30) return QFA_E_TAU;
-    const double coeff = kLymanLam[series - 1] * kLymanF[series - 1] / (kLymanLam[0] * kLymanF[0]);
-    double amp, scale, expo, off;
-    switch (which) {
-        case QFA_TAU_BECKER: amp = 0.751; scale = 1.0 / 4.5; expo = 2.90; off = -0.132; break;
-        case QFA_TAU_FG: amp = 0.0018; scale = 1.0; expo = 3.92; off = 0.0; break;
-        case QFA_TAU_KAMBLE: amp = 5.54e-3; scale = 1.0; expo = 3.182; off = 0.0; break;
-        case QFA_TAU_MOCK: amp = 0.2231435513142097; scale = 1.0 / 3.25; expo = 3.2; off = 0.0; break;
-        default: return QFA_E_TAU;
-    }
-    out->amp = (float)(amp * coeff);
-    out->scale = (float)scale;
-    out->expo = (float)expo;
-    out->offset = (float)(off * coeff);
+    const TauModel *m = tau_model(which);
+    if (!m) return QFA_E_TAU;
+    const double coeff = lyman_coeff(series - 1);
+    out->amp = (float)(m->amp * coeff);
+    out->scale = (float)m->scale;
+    out->expo = (float)m->expo;
+    out->offset = (float)(m->off * coeff);
     return 0;
 }
 
@@ -106,18 +141,14 @@ int qfa_nll_grad_det_f32(const qfa_params_t *p, const qfa_batch_t *b, const qfa_
 int qfa_nll_grad_ex_f32(const qfa_params_t *p, const qfa_batch_t *b, const qfa_tau_t *tau, int B, int Npix, int Nb,
                         int Nh, float *nll, float *accum, void *workspace, size_t workspace_bytes, void *slab,
                         size_t slab_bytes, unsigned flags, void *stream, void *const *events) {
-    if (!p || !b || !tau || !accum || !workspace) return QFA_E_NULL;
-    if (!p->F || !p->Psi || !p->tau0 || !p->c0 || !p->beta || (Nb > 0 && !p->omega)) return QFA_E_NULL;
-    if (int e = check_batch(*b, Npix, Nb)) return e;
-    if (int e = check_shape(B, Npix, Nb, Nh)) return e;
-    if (workspace_bytes < qfa_workspace_bytes(B, Npix, Nh)) return QFA_E_WORKSPACE;
+    if (int e = check_call(p, b, tau, accum && workspace, B, Npix, Nb, Nh, &workspace_bytes)) return e;
     if (slab && slab_bytes < det_slab_bytes(B, Npix, Nb, Nh)) return QFA_E_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     float *ws = (float *)workspace;
     const qfa_batch_t bb = norm_batch(*b, Npix);
-    if (kp_for(Nh) == 8) return run_nll_grad<8>(*p, bb, *tau, B, Npix, Nb, Nh, nll, accum, ws, st, events, slab, flags);
-    if (kp_for(Nh) == 16) return run_nll_grad<16>(*p, bb, *tau, B, Npix, Nb, Nh, nll, accum, ws, st, events, slab, flags);
-    return qfa_k32_nll_grad(*p, bb, *tau, B, Npix, Nb, Nh, nll, accum, ws, st, events, slab, flags);
+    return by_kp(Nh, [&] { return run_nll_grad<8>(*p, bb, *tau, B, Npix, Nb, Nh, nll, accum, ws, st, events, slab, flags); },
+                 [&] { return run_nll_grad<16>(*p, bb, *tau, B, Npix, Nb, Nh, nll, accum, ws, st, events, slab, flags); },
+                 [&] { return qfa_k32_nll_grad(*p, bb, *tau, B, Npix, Nb, Nh, nll, accum, ws, st, events, slab, flags); });
 }
 
 int qfa_finalize_grads_f32(const float *accum, const float *F, int Npix, int Nb, int Nh, int normalize, float *gF,
@@ -148,17 +179,13 @@ int qfa_predict_events_f32(const qfa_params_t *p, const float *mu, const qfa_bat
 int qfa_predict_ex_f32(const qfa_params_t *p, const float *mu, const qfa_batch_t *b, const qfa_tau_t *tau, int B,
                        int Npix, int Nb, int Nh, float *ll, float *hmean, float *hcov, float *cont, float *unc,
                        void *workspace, size_t workspace_bytes, unsigned flags, void *stream, void *const *events) {
-    if (!p || !b || !tau || !mu || !ll || !hmean || !hcov || !cont || !unc || !workspace) return QFA_E_NULL;
-    if (!p->F || !p->Psi || !p->tau0 || !p->c0 || !p->beta || (Nb > 0 && !p->omega)) return QFA_E_NULL;
-    if (int e = check_batch(*b, Npix, Nb)) return e;
-    if (int e = check_shape(B, Npix, Nb, Nh)) return e;
-    if (workspace_bytes < qfa_workspace_bytes(B, Npix, Nh)) return QFA_E_WORKSPACE;
+    if (int e = check_call(p, b, tau, mu && ll && hmean && hcov && cont && unc && workspace, B, Npix, Nb, Nh, &workspace_bytes)) return e;
     hipStream_t st = (hipStream_t)stream;
     float *ws = (float *)workspace;
     const qfa_batch_t bb = norm_batch(*b, Npix);
-    if (kp_for(Nh) == 8) return run_predict<8>(*p, mu, bb, *tau, B, Npix, Nb, Nh, ll, hmean, hcov, cont, unc, ws, st, events, flags);
-    if (kp_for(Nh) == 16) return run_predict<16>(*p, mu, bb, *tau, B, Npix, Nb, Nh, ll, hmean, hcov, cont, unc, ws, st, events, flags);
-    return qfa_k32_predict(*p, mu, bb, *tau, B, Npix, Nb, Nh, ll, hmean, hcov, cont, unc, ws, st, events, flags);
+    return by_kp(Nh, [&] { return run_predict<8>(*p, mu, bb, *tau, B, Npix, Nb, Nh, ll, hmean, hcov, cont, unc, ws, st, events, flags); },
+                 [&] { return run_predict<16>(*p, mu, bb, *tau, B, Npix, Nb, Nh, ll, hmean, hcov, cont, unc, ws, st, events, flags); },
+                 [&] { return qfa_k32_predict(*p, mu, bb, *tau, B, Npix, Nb, Nh, ll, hmean, hcov, cont, unc, ws, st, events, flags); });
 }
 
 int qfa_adam_clip_f32(const float *p, const float *g, float *m, float *v, float *p_out, size_t n, double lr, double b1,
@@ -166,12 +193,10 @@ int qfa_adam_clip_f32(const float *p, const float *g, float *m, float *v, float 
     if (n == 0) return 0;
     if (!p || !g || !m || !v || !p_out) return QFA_E_NULL;
     if (i < 0) return QFA_E_SIZE;
-    // The reference mixes Python floats (double) with float32 tensors: every scalar below is
-    // formed in double and rounded to float32 once, exactly where torch would round it.
-    const float bc1 = (float)(1.0 - pow(b1, (double)(i + 1))), bc2 = (float)(1.0 - pow(b2, (double)(i + 1)));
+    const AdamBias bc = adam_bias(b1, b2, i);
     k_adam_clip<<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>(
         p, g, m, v, p_out, n, (float)lr, (float)b1, (float)b2, (float)(1.0 - b1), (float)(1.0 - b2), (float)eps,
-        (float)wd, bc1, bc2, lo, hi);
+        (float)wd, bc.bc1, bc.bc2, lo, hi);
     return hip_status();
 }
 
@@ -190,9 +215,9 @@ int qfa_adam_clip_multi_f32(const qfa_adam_multi_t *t, double lr, double b1, dou
     }
     for (int k = t->count; k <= QFA_ADAM_MAX; ++k) a.blk0[k] = nblk;
     if (nblk == 0) return 0;
-    const float bc1 = (float)(1.0 - pow(b1, (double)(i + 1))), bc2 = (float)(1.0 - pow(b2, (double)(i + 1)));
+    const AdamBias bc = adam_bias(b1, b2, i);
     k_adam_clip_multi<<<nblk, 256, 0, (hipStream_t)stream>>>(a, (float)lr, (float)b1, (float)b2, (float)(1.0 - b1),
-                                                             (float)(1.0 - b2), (float)eps, (float)wd, bc1, bc2);
+                                                             (float)(1.0 - b2), (float)eps, (float)wd, bc.bc1, bc.bc2);
     return hip_status();
 }
 
@@ -212,9 +237,9 @@ int qfa_finalize_adam_clip_f32(const float *accum, int Npix, int Nb, int Nh, con
         nblk += (unsigned)((t->n[k] + 255) / 256);
     }
     for (int k = 6; k <= QFA_ADAM_MAX; ++k) a.blk0[k] = nblk;
-    const float bc1 = (float)(1.0 - pow(b1, (double)(i + 1))), bc2 = (float)(1.0 - pow(b2, (double)(i + 1)));
+    const AdamBias bc = adam_bias(b1, b2, i);
     k_finalize_adam<<<nblk, 256, 0, (hipStream_t)stream>>>(a, accum, Npix, Nb, Nh, loss, (float)lr, (float)b1, (float)b2,
-                                                           (float)(1.0 - b1), (float)(1.0 - b2), (float)eps, (float)wd, bc1, bc2);
+                                                           (float)(1.0 - b1), (float)(1.0 - b2), (float)eps, (float)wd, bc.bc1, bc.bc2);
     return hip_status();
 }
 
@@ -265,19 +290,13 @@ static unsigned mu_grid_y(int B, int chunk) {
 }
 
 static int fill_lyman(int which, double wav0, LymanTable *t) {
-    double amp, scale, expo, off;
-    switch (which) {
-        case QFA_TAU_BECKER: amp = 0.751; scale = 1.0 / 4.5; expo = 2.90; off = -0.132; break;
-        case QFA_TAU_FG: amp = 0.0018; scale = 1.0; expo = 3.92; off = 0.0; break;
-        case QFA_TAU_KAMBLE: amp = 5.54e-3; scale = 1.0; expo = 3.182; off = 0.0; break;
-        case QFA_TAU_MOCK: amp = 0.2231435513142097; scale = 1.0 / 3.25; expo = 3.2; off = 0.0; break;
-        default: return QFA_E_TAU;
-    }
-    t->amp = amp; t->scale = scale; t->expo = expo; t->offset = off;
+    const TauModel *m = tau_model(which);
+    if (!m) return QFA_E_TAU;
+    t->amp = m->amp; t->scale = m->scale; t->expo = m->expo; t->offset = m->off;
     t->level = 0;
     for (int i = 0; i < 30; ++i) {
         t->lam[i] = kLymanLam[i];
-        t->coeff[i] = kLymanLam[i] * kLymanF[i] / (kLymanLam[0] * kLymanF[0]);
+        t->coeff[i] = lyman_coeff(i);
         if (wav0 < kLymanLam[i]) t->level = i + 1;        // lambdas decrease (QFA/utils.py:186-192)
     }
     return t->level == 0 ? QFA_E_SIZE : 0;

@@ -48,7 +48,8 @@ struct GtPlan {
 };
 
 // ------------------------------------------------------------------------------------------------
-// k_prep_pgt : F, Psi, omega (+ the per-pixel factors of the factored-z form) -> the image of every 16-pixel tile
+// prep_pgt_body : F, Psi, omega (+ the per-pixel factors of the factored-z form) -> the image of one 16-pixel tile (a block range of
+// k_prep_step, qfa_gx.hip).  The state images of the groups of spectra are written by k_solve (template argument STATE: build_state).
 // ------------------------------------------------------------------------------------------------
 template <int KP>
 __device__ __forceinline__ void prep_pgt_body(int bid, const float *__restrict__ F, const float *__restrict__ Psi,
@@ -118,22 +119,6 @@ __device__ __forceinline__ void prep_pgt_body(int bid, const float *__restrict__
     }
     float *fr = reinterpret_cast<float *>(tile + GT::OFF_F);
     for (int i = threadIdx.x; i < 16 * KP; i += 256) fr[i] = f[i / KP][i % KP];
-}
-template <int KP>
-__global__ __launch_bounds__(256) void k_prep_pgt(const float *__restrict__ F, const float *__restrict__ Psi,
-                                                  const float *__restrict__ omega, const float4 *__restrict__ ZP,
-                                                  int Npix, int Nb, int Nh, unsigned char *__restrict__ PGT) {
-    prep_pgt_body<KP>(blockIdx.x, F, Psi, omega, zp_table(ZP), Npix, Nb, Nh, PGT);
-}
-
-// ------------------------------------------------------------------------------------------------
-// k_prep_pst : the state images from the float32 record SOL (one block per group).  The training step does not launch it:
-// k_solve builds the images itself (qfa_step_kernels.h, template argument STATE); this kernel serves tools and tests.
-// ------------------------------------------------------------------------------------------------
-template <int KP>
-__global__ __launch_bounds__(256) void k_prep_pst(const float *__restrict__ SOL, int B, int Nh, unsigned char *__restrict__ PST) {
-    build_state<KP>(SOL + (size_t)16 * blockIdx.x * Cfg<KP>::NSOL, 16 * blockIdx.x, B, Nh, PST + (size_t)blockIdx.x * GTT<KP>::STATE_B,
-                    threadIdx.x);
 }
 
 #ifndef QFA_GT_STAMPS

@@ -6,7 +6,7 @@
 //   * stage 3 (F-gradient contraction) ran as 102 K = 16 bf16 MFMAs: the 16x16x16 form keeps the XDL pipe at half rate.
 // Here both are six-term split-bf16 products (qfa_common.h) at the pipe's full rate:
 //   stage 1  v_mfma_f32_16x16x32_bf16: A = [y | Cinv'] of 16 spectra (static, split once per work item, 72 VGPRs),
-//            B = the tile image [F^T | pair products] (static per step, split once by k_prep_pgx), 36 MFMAs / 16 px;
+//            B = the tile image [F^T | pair products] (static per step, split once by prep_pgx_body), 36 MFMAs / 16 px;
 //   stage 3  v_mfma_f32_32x32x16_bf16: per PAIR of spectra G = F_tile (32 px x 16 a) x [Z_s | Z_s'] (16 a x 32), both
 //            static; beta is applied to G on the VALU; the gamma term is one more product with K = spectrum.
 //            48 + 6 MFMAs of 32 cycles per 32 px (was 204 x 16).
@@ -88,17 +88,16 @@ static_assert(GXT<16>::L_TOTAL <= 160 * 1024 && GXT<8>::L_TOTAL <= 160 * 1024, "
 static_assert(32 * GXT<16>::FROW * 4 <= 3072, "F block of the W form fits the F slot");
 
 // ------------------------------------------------------------------------------------------------
-// k_prep_pgx : F, Psi, omega -> the pass-2 image, one block per 32-pixel tile.
+// prep_pgx_body : F, Psi, omega -> the pass-2 image, one block per 32-pixel tile (a block range of k_prep_step, qfa_gx.hip).
 //   half h (h = 0, 1)  [K-step ks][piece][lane (g, lo)][8 k] bf16: B[k = 32 ks + 8 g + j][px = 2 lo + h]
 //                      ks = 0: k < KP -> F[px][k]; ks >= 1: pair q = 32 (ks - 1) + 8 g + j -> F[px][a_q] F[px][b_q]
 //                      then float32 Psi[lo], omega[lo] of the pixels 2 lo + h
-//   stage-3 part       float32 F[px 0..31][FROW] (wform = 1, what every caller passes; wform = 0 wrote the bf16 pieces of the retired
-//                      G form -- the argument and that arm stay so that the code of k_prep_pgx / k_prep_step is unchanged)
+//   stage-3 part       float32 F[px 0..31][FROW] (stage 3 in its W form)
 // ------------------------------------------------------------------------------------------------
 template <int KP>
 __device__ __forceinline__ void prep_pgx_body(int bid, const float *__restrict__ F, const float *__restrict__ Psi,
                                               const float *__restrict__ omega, const ZPSrc &ZP, int Npix, int Nb, int Nh,
-                                              int wform, unsigned char *__restrict__ PGX) {
+                                              unsigned char *__restrict__ PGX) {
     using GX = GXT<KP>;
     unsigned char *tile = PGX + (size_t)bid * GX::TILE_B;
     const int p0 = 32 * bid;
@@ -162,30 +161,12 @@ __device__ __forceinline__ void prep_pgx_body(int bid, const float *__restrict__
         } else if (j >= GX::PAR_IT1 && j < GX::PAR_IT2 + 16) v = tsc[2 * (j & 15) + h][j < GX::PAR_IT2 ? 1 : 2];
         po[j] = v;
     }
-    if (wform) {       // stage 3 in its W form (role B, TERMS = 6): F of the tile as float32 rows [pixel 0..31][FROW]
-        float *fr = reinterpret_cast<float *>(tile + GX::OFF_FP);
-        for (int i = threadIdx.x; i < 32 * GX::FROW; i += 256) {
-            const int px = i / GX::FROW, a = i % GX::FROW;
-            fr[i] = a < KP ? f[px][a] : 0.f;
-        }
-    } else if (threadIdx.x < 64) {
-        const int lane = threadIdx.x, r = lane & 31, h2 = lane >> 5;
-        float v[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = f[r][8 * h2 + j];
-        u32x4 ph, pm, pl;
-        split8(v, ph, pm, pl);
-        unsigned char *dst = tile + GX::OFF_FP + lane * 16;
-        *reinterpret_cast<u32x4 *>(dst) = ph;
-        *reinterpret_cast<u32x4 *>(dst + 1024) = pm;
-        *reinterpret_cast<u32x4 *>(dst + 2048) = pl;
+    // stage 3 in its W form (role B): F of the tile as float32 rows [pixel 0..31][FROW]
+    float *fr = reinterpret_cast<float *>(tile + GX::OFF_FP);
+    for (int i = threadIdx.x; i < 32 * GX::FROW; i += 256) {
+        const int px = i / GX::FROW, a = i % GX::FROW;
+        fr[i] = a < KP ? f[px][a] : 0.f;
     }
-}
-template <int KP>
-__global__ __launch_bounds__(256) void k_prep_pgx(const float *__restrict__ F, const float *__restrict__ Psi,
-                                                  const float *__restrict__ omega, const float4 *__restrict__ ZP,
-                                                  int Npix, int Nb, int Nh, int wform, unsigned char *__restrict__ PGX) {
-    prep_pgx_body<KP>(blockIdx.x, F, Psi, omega, zp_table(ZP), Npix, Nb, Nh, wform, PGX);
 }
 
 struct SpecA {                       // role A: one lane's 4 spectra x 2 pixels of a tile (sigma < 0: masked pixel)
@@ -213,7 +194,7 @@ __device__ unsigned long long qfa_gx_stamps[2 * 32];
 #else
 #define GXS(i) {}
 #endif
-template <int KP, bool HASA, int TERMS, bool ZF>
+template <int KP, bool HASA, bool ZF>
 __global__ __launch_bounds__(512, 2) void k_grads_x(qfa_params_t p, qfa_batch_t bt, qfa_tau_t tau, int B, int Npix, int Nb,
                                                     int Nh, int ntiles, WorkPlan wp,
                                                     const unsigned char *__restrict__ PGX,
@@ -656,7 +637,6 @@ __global__ __launch_bounds__(512, 2) void k_grads_x(qfa_params_t p, qfa_batch_t 
         }
     } else {
         // ================================================================ role B: image DMA, flushes, stage 3
-        static_assert(TERMS == 6, "stage 3 in its W form (float32 grade); the three-product G form of round 2 is retired");
         // ---- W form: accF[px][b] = sum_a F[px][a] W[px][a][b], W = sum_s Z_s[a][b] beta[s][px]
         // as a K = spectrum GEMM per column tile a: A = static Z pieces (row m = b = lane & 15; k = 8 g + j <-> spectrum
         // 4 g + (j & 3), piece slot j >> 2), B = the lane's own four beta values as {h|l}, {m|m}, {h|h}: three INDEPENDENT

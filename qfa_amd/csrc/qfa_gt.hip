@@ -37,17 +37,6 @@ static GtPlan gt_plan(int KP, int B, int Npix, int max_ranges) {
 }
 int qfa_gt_items(int KP, int B, int Npix, int max_ranges) { return gt_plan(KP, B, Npix, max_ranges).items(); }
 int qfa_gt_ranges(int KP, int B, int Npix, int max_ranges) { return gt_plan(KP, B, Npix, max_ranges).R; }
-// the per-tile images (beside the other parameter images of the call) and the per-group operand images (behind the solve)
-void qfa_gt_prep_image(int KP, const qfa_params_t &p, const float *ZP, int Npix, int Nb, int Nh, unsigned char *PGT, hipStream_t st) {
-    const float4 *zp = reinterpret_cast<const float4 *>(ZP);
-    // (one block per 16-pixel tile: TPW per wave tile)
-    if (KP == 8) k_prep_pgt<8><<<(Npix + GTT<8>::PXW - 1) / GTT<8>::PXW * GTT<8>::TPW, 256, 0, st>>>(p.F, p.Psi, p.omega, zp, Npix, Nb, Nh, PGT);
-    else k_prep_pgt<16><<<(Npix + GTT<16>::PXW - 1) / GTT<16>::PXW * GTT<16>::TPW, 256, 0, st>>>(p.F, p.Psi, p.omega, zp, Npix, Nb, Nh, PGT);
-}
-void qfa_gt_prep_state(int KP, const float *SOL, int B, int Nh, unsigned char *PST, hipStream_t st) {
-    if (KP == 8) k_prep_pst<8><<<(B + 15) / 16, 256, 0, st>>>(SOL, B, Nh, PST);
-    else k_prep_pst<16><<<(B + 15) / 16, 256, 0, st>>>(SOL, B, Nh, PST);
-}
 template <int KP>
 static void gt_launch(const qfa_params_t &p, const qfa_batch_t &b, const qfa_tau_t &tau, int B, int Npix, int Nb, int Nh,
                       const GtPlan &g, const unsigned char *PGT, const unsigned char *PST, const float4 *zs, float *accum,
@@ -68,9 +57,8 @@ static void gt_launch(const qfa_params_t &p, const qfa_batch_t &b, const qfa_tau
 }
 void qfa_gt_launch(int KP, const qfa_params_t &p, const qfa_batch_t &b, const qfa_tau_t &tau, int B, int Npix, int Nb, int Nh,
                    int max_ranges, const unsigned char *PGT, const unsigned char *PST, const float *ZS, float *accum,
-                   float *slab, double *slabS, int slab_stride, Scal64 *sc64, int exact, hipStream_t st, int *ranges_out) {
-    const GtPlan g = gt_plan(KP, B, Npix, max_ranges);
-    if (ranges_out) *ranges_out = g.R;
+                   float *slab, double *slabS, int slab_stride, Scal64 *sc64, int exact, hipStream_t st) {
+    const GtPlan g = gt_plan(KP, B, Npix, max_ranges);        // (g.R rows leave: qfa_gt_ranges)
     const float4 *zs = reinterpret_cast<const float4 *>(ZS);
     if (KP == 8) gt_launch<8>(p, b, tau, B, Npix, Nb, Nh, g, PGT, PST, zs, accum, slab, slabS, slab_stride, sc64, exact, st);
     else gt_launch<16>(p, b, tau, B, Npix, Nb, Nh, g, PGT, PST, zs, accum, slab, slabS, slab_stride, sc64, exact, st);

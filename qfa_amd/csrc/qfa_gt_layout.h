@@ -1,6 +1,6 @@
 // qfa_gt_layout.h -- the pixel-resident form of pass 2 (qfa_grads_t.h): sizes of its images and LDS rings, and the builder of
 // the per-group operand images ("state"), which runs at the end of k_solve (qfa_step_kernels.h) on the solve's output
-// while it is still in LDS -- or as a kernel of its own (k_prep_pst) on the float32 record SOL.
+// while it is still in LDS.
 #pragma once
 #include "qfa_common.h"
 
@@ -25,7 +25,7 @@ struct GTT {
     static constexpr int NKS = NKQ + 1;                      // blocks of the spectrum side (6)
     static constexpr int S1NP = 2;                           // pieces per K block of stage 1 (float16 h, m)
     static constexpr int BLK_B = S1NP * 1024;
-    // per 16-pixel tile in global memory (k_prep_pgt)
+    // per 16-pixel tile in global memory (prep_pgt_body)
     static constexpr int IMG_B = NKQ * BLK_B;                // [ks][piece][lane (g, lo)][8 k]: B[k = 32 ks + 8 g + j][px = lo]
     // float Psi[16] | omega[16] | ti[16] | pwi[16] | l2i[16] | 1 / t^2 [16] | 1 / t [16] (t = the pixel's power of two:
     // the image holds t^2 f_a f_b and t f_a)
@@ -33,7 +33,7 @@ struct GTT {
     static constexpr int PAR_IT2 = 80, PAR_IT1 = 96, PAR_SBETA = 112;      // float index in the parameter block: 1 / t^2, 1 / t, s_beta of pixel lo
     static constexpr int OFF_F = IMG_B + 512;                // float F[16 px][KP]
     static constexpr int TILE_B = (OFF_F + 16 * KP * 4 + 1023) / 1024 * 1024;
-    // per group of 16 spectra in global memory (k_prep_pst)
+    // per group of 16 spectra in global memory (build_state)
     // stage 1 (float16 pieces): Cinv' and y of a spectrum are scaled by powers of two of their own; their inverses sit as float32 in the h piece of
     // the y block, lanes g = 3 (K slots 24..31, which meet zeros of the image): float 2 s = 1 / scale(Cinv'), 2 s + 1 = 1 / scale(y)
     static constexpr int S1_B = NKS * BLK_B;                 // [block][piece][lane (g, lo = spectrum)][8 k]: A[s][k] of stage 1

@@ -12,37 +12,33 @@ size_t qfa_gx_image_bytes(int KP, int ntiles32) {            // the largest of t
     return (size_t)ntiles32 * std::max(t, x);
 }
 
-// pass 2, two-role form (qfa_grads_x.h)
+// pass 2, two-role form (qfa_grads_x.h); its image is built by k_prep_step below
 template <int KP>
 static void gx_launch(const qfa_params_t &p, const qfa_batch_t &b, const qfa_tau_t &tau, int B, int Npix, int Nb, int Nh,
-                      int ntiles32, const WorkPlan &wp, unsigned char *PGX, const float *SOL, const float4 *ZS,
-                      const float4 *ZP, float *accum, float *slab, double *slabS, int slab_stride, Scal64 *sc64,
-                      unsigned flags, hipStream_t st, bool prep) {
+                      int ntiles32, const WorkPlan &wp, unsigned char *PGX, const float *SOL, const float4 *ZS, float *accum,
+                      float *slab, double *slabS, int slab_stride, Scal64 *sc64, unsigned flags, hipStream_t st) {
     const int exact = (flags & QFA_F_EXACT_GRAD) ? 1 : 0;
-    if (prep) k_prep_pgx<KP><<<ntiles32, 256, 0, st>>>(p.F, p.Psi, p.omega, ZP, Npix, Nb, Nh, 1, PGX);
-    auto go = [&](auto hasa, auto terms, auto zf) {
-        k_grads_x<KP, decltype(hasa)::value, decltype(terms)::value, decltype(zf)::value><<<wp.items(), 512, 0, st>>>(
+    auto go = [&](auto hasa, auto zf) {
+        k_grads_x<KP, decltype(hasa)::value, decltype(zf)::value><<<wp.items(), 512, 0, st>>>(
             p, b, tau, B, Npix, Nb, Nh, ntiles32, wp, PGX, SOL, ZS, accum, slab, slabS, slab_stride, sc64, exact);
     };
-    using T6 = std::integral_constant<int, 6>;
-    if (b.A_blue) go(std::true_type{}, T6{}, std::false_type{});
-    else if (ZS) go(std::false_type{}, T6{}, std::true_type{});
-    else go(std::false_type{}, T6{}, std::false_type{});
+    if (b.A_blue) go(std::true_type{}, std::false_type{});
+    else if (ZS) go(std::false_type{}, std::true_type{});
+    else go(std::false_type{}, std::false_type{});
 }
 void qfa_gx_launch(int KP, const qfa_params_t &p, const qfa_batch_t &b, const qfa_tau_t &tau, int B, int Npix, int Nb, int Nh,
-                   int ntiles32, const WorkPlan &wp, unsigned char *PGX, const float *SOL, const float *ZS, const float *ZP,
-                   float *accum, float *slab, double *slabS, int slab_stride, Scal64 *sc64, unsigned flags, hipStream_t st,
-                   bool prep) {
-    const float4 *zs = reinterpret_cast<const float4 *>(ZS), *zp = reinterpret_cast<const float4 *>(ZP);
-    if (KP == 8) gx_launch<8>(p, b, tau, B, Npix, Nb, Nh, ntiles32, wp, PGX, SOL, zs, zp, accum, slab, slabS, slab_stride, sc64, flags, st, prep);
-    else gx_launch<16>(p, b, tau, B, Npix, Nb, Nh, ntiles32, wp, PGX, SOL, zs, zp, accum, slab, slabS, slab_stride, sc64, flags, st, prep);
+                   int ntiles32, const WorkPlan &wp, unsigned char *PGX, const float *SOL, const float *ZS, float *accum,
+                   float *slab, double *slabS, int slab_stride, Scal64 *sc64, unsigned flags, hipStream_t st) {
+    const float4 *zs = reinterpret_cast<const float4 *>(ZS);
+    if (KP == 8) gx_launch<8>(p, b, tau, B, Npix, Nb, Nh, ntiles32, wp, PGX, SOL, zs, accum, slab, slabS, slab_stride, sc64, flags, st);
+    else gx_launch<16>(p, b, tau, B, Npix, Nb, Nh, ntiles32, wp, PGX, SOL, zs, accum, slab, slabS, slab_stride, sc64, flags, st);
 }
 
 // ---- everything a training step derives from the parameters before pass 1, in ONE launch (N_h <= 16): the pass-1 image,
 // the pass-2 image of the form that will run, the per-spectrum factors of the factored-z form, and (QFA_F_ZERO_ACCUM) the
 // zeroing of the packed buffer.  The step of a small batch -- the reference's default is 500 spectra -- is a chain of a dozen
 // dependent kernels of 3 - 30 us with ~3 us of dispatch latency between any two: five of them were these preparations
-// (k_zfac_spec, k_zfac_pix, k_prep_pfx, k_prep_pgx / k_prep_pgt, torch's fill).  Block ranges: [pfx tiles | pass-2 tiles |
+// (k_zfac_spec, k_zfac_pix, k_prep_pfx, a kernel of its own for the pass-2 image, torch's fill).  Block ranges: [pfx tiles | pass-2 tiles |
 // 256 spectra each | 1024 floats of accum each]; the per-pixel factors are computed where they are needed (ZPSrc).
 template <int KP, bool PIXRES>
 __global__ __launch_bounds__(256) void k_prep_step(qfa_params_t p, qfa_tau_t tau, const float *__restrict__ zq1,
@@ -57,7 +53,7 @@ __global__ __launch_bounds__(256) void k_prep_step(qfa_params_t p, qfa_tau_t tau
     if (b < n_pfx) prep_pfx_body<KP>(b, n_pfx, p.F, p.Psi, p.omega, nullptr, zp, Npix, Nb, Nh, PFX);
     else if (b < n_pfx + n_p2) {
         if constexpr (PIXRES) prep_pgt_body<KP>(b - n_pfx, p.F, p.Psi, p.omega, zp, Npix, Nb, Nh, P2);
-        else prep_pgx_body<KP>(b - n_pfx, p.F, p.Psi, p.omega, zp, Npix, Nb, Nh, 1, P2);
+        else prep_pgx_body<KP>(b - n_pfx, p.F, p.Psi, p.omega, zp, Npix, Nb, Nh, P2);
     } else if (b < n_pfx + n_p2 + n_zs) zfac_spec_body((b - n_pfx - n_p2) * 256 + (int)threadIdx.x, zq1, rows, p, tau, B, ZS);
     else {
         const size_t i0 = (size_t)(b - n_pfx - n_p2 - n_zs) * 1024 + threadIdx.x;

@@ -11,9 +11,8 @@
 // pass 2 for N_h <= 16 with every contraction on the XDL pipe (qfa_grads_x.h: KP = 8 or 16, built in qfa_gx.hip)
 size_t qfa_gx_image_bytes(int KP, int ntiles32);
 void qfa_gx_launch(int KP, const qfa_params_t &p, const qfa_batch_t &b, const qfa_tau_t &tau, int B, int Npix, int Nb, int Nh,
-                   int ntiles32, const WorkPlan &wp, unsigned char *PGX, const float *SOL, const float *ZS, const float *ZP,
-                   float *accum, float *slab, double *slabS, int slab_stride, Scal64 *sc64, unsigned flags, hipStream_t st,
-                   bool prep = true);
+                   int ntiles32, const WorkPlan &wp, unsigned char *PGX, const float *SOL, const float *ZS, float *accum,
+                   float *slab, double *slabS, int slab_stride, Scal64 *sc64, unsigned flags, hipStream_t st);
 // everything a training step derives from the parameters before pass 1, in one launch (N_h <= 16; qfa_gx.hip, k_prep_step)
 void qfa_prep_step_launch(int KP, bool pixres, const qfa_params_t &p, const qfa_batch_t &b, const qfa_tau_t &tau, int B, int Npix,
                           int Nb, int Nh, int ntiles32, unsigned char *PFX, unsigned char *P2, float *ZS, float *zero,
@@ -24,11 +23,9 @@ struct GtPlan;
 size_t qfa_gt_state_bytes(int KP, int B);
 int qfa_gt_items(int KP, int B, int Npix, int max_ranges);
 int qfa_gt_ranges(int KP, int B, int Npix, int max_ranges);
-void qfa_gt_prep_image(int KP, const qfa_params_t &p, const float *ZP, int Npix, int Nb, int Nh, unsigned char *PGT, hipStream_t st);
-void qfa_gt_prep_state(int KP, const float *SOL, int B, int Nh, unsigned char *PST, hipStream_t st);
 void qfa_gt_launch(int KP, const qfa_params_t &p, const qfa_batch_t &b, const qfa_tau_t &tau, int B, int Npix, int Nb, int Nh,
                    int max_ranges, const unsigned char *PGT, const unsigned char *PST, const float *ZS, float *accum,
-                   float *slab, double *slabS, int slab_stride, Scal64 *sc64, int exact, hipStream_t st, int *ranges_out);
+                   float *slab, double *slabS, int slab_stride, Scal64 *sc64, int exact, hipStream_t st);
 
 // posterior writer for N_h <= 16 on the XDL pipe (qfa_predict_x.h, built in qfa_gx.hip)
 size_t qfa_px_image_bytes(int KP, int ntiles32);
@@ -131,18 +128,24 @@ inline size_t det_chunks(int B) { return (det_rows(B) + DET_CHUNK_ROWS - 1) / DE
 struct DetLayout {
     size_t NF, stride, oS, oPart, bytes;      // offsets in bytes
 };
-// The rows of the pixel-resident pass 2 (k_grads_t) where they live in the workspace (no caller's slab): one slab row per range of
-// spectra | scalar records, 8 waves x 3 doubles per item | float64 partial sums of the reducer.  make_layout_t sizes Layout::oISLAB
-// from it and run_nll_grad addresses the region by it.  (`bytes` is the size of the whole region, with the slack both places always
-// left behind the parts; the reducer's chunks are DET_CHUNK_ROWS rows, as launch_reduce_slab cuts them.)
-inline DetLayout pixres_rows_layout(int KP, int B, int Npix, int Nb, int Nh, int max_ranges) {
-    const size_t rows = (size_t)qfa_gt_ranges(KP, B, Npix, max_ranges), items8 = 8 * (size_t)qfa_gt_items(KP, B, Npix, max_ranges);
+// The region the fixed-order reducer works on: `rows` slab rows | scalar records, 3 doubles per item-wave | float64 partial sums of
+// the reducer, `chunks` x NF (the parts start on 16-byte boundaries)
+inline DetLayout rows_region(size_t rows, size_t itemwaves, size_t chunks, size_t NF, size_t stride) {
     DetLayout D;
-    D.NF = det_rows_floats(Npix, Nb, Nh);
-    D.stride = det_row_stride(Npix, Nb, Nh);
-    D.oS = (rows * D.stride * sizeof(float) + 15) / 16 * 16;
-    D.oPart = D.oS + (items8 * 3 * sizeof(double) + 15) / 16 * 16;
-    D.bytes = (rows * D.stride + (items8 * 3 * 2 + 8) + 2 * ((rows + DET_CHUNK_ROWS - 1) / DET_CHUNK_ROWS) * D.NF + 16) * sizeof(float);
+    D.NF = NF;
+    D.stride = stride;
+    D.oS = (rows * stride * sizeof(float) + 15) / 16 * 16;
+    D.oPart = D.oS + (itemwaves * 3 * sizeof(double) + 15) / 16 * 16;
+    D.bytes = D.oPart + chunks * NF * sizeof(double);
+    return D;
+}
+// The rows of the pixel-resident pass 2 (k_grads_t) where they live in the workspace (no caller's slab): one slab row per range of
+// spectra, 8 waves per item.  make_layout_t sizes Layout::oISLAB from it and plan_step addresses the region by it.  (The reducer's
+// chunks are DET_CHUNK_ROWS rows, as launch_reduce_slab cuts them.)
+inline DetLayout pixres_rows_layout(size_t rows, size_t itemwaves, int Npix, int Nb, int Nh) {
+    DetLayout D = rows_region(rows, itemwaves, (rows + DET_CHUNK_ROWS - 1) / DET_CHUNK_ROWS, det_rows_floats(Npix, Nb, Nh),
+                              det_row_stride(Npix, Nb, Nh));
+    D.bytes += 24 * sizeof(float);     // the slack this region has always had behind its parts (the workspace sizes are pinned)
     return D;
 }
 
@@ -215,7 +218,8 @@ Layout make_layout_t(int B, int Npix) {
     // reducer as well (no atomics: the default accumulation of a large batch is bit-reproducible too).  Sized for N_b = N_pix,
     // N_h = KP
     L.oISLAB = 0;
-    if constexpr (KP == 8 || KP == 16) L.oISLAB = take(pixres_rows_layout(KP, B, Npix, Npix, KP, 1 << 30).bytes / sizeof(float));
+    if constexpr (KP == 8 || KP == 16)
+        L.oISLAB = take(pixres_rows_layout(qfa_gt_ranges(KP, B, Npix, 1 << 30), 8 * (size_t)qfa_gt_items(KP, B, Npix, 1 << 30), Npix, Npix, KP).bytes / sizeof(float));
     L.oBG = 0;
     L.bg_stride = round_up(Npix, 32);
     if constexpr (KP == 32) L.oBG = take(2 * (size_t)round_up(B, 64) * L.bg_stride);
@@ -270,7 +274,7 @@ inline int check_shape(int B, int Npix, int Nb, int Nh) {
 //     0.104 / 0.117 at 2 000, 0.192 / 0.220 at 8 000, 2.82 / 3.25 at 40 000 x 9243 (the one exception, 10 000 x 2000 --
 //     157 blocks on 256 CUs, 0.281 / 0.258 -- goes to k_grads_t); N_h = 16: 2.5 - 2.6 against 3.2 ms at c3;
 //   k_grads_t once the batch gives every workgroup a walk long enough to pay for its prologue and epilogue (the figures of ROUND 3 --
-//     superseded for N_pix >= 1024 by the round-5 sweep quoted in pass2_use_pixres below):
+//     superseded for N_pix >= 1024 by the round-5 sweep quoted in pass2_form below):
 //     N_h = 9..16 from 96 spectra per CU (24 576) on: N_pix = 4000: 0.146 / 0.166 at 1 000 spectra, 0.42 / 0.44 at 8 000,
 //       1.43 / 1.35 at 32 000, 4.31 / 3.98 at 100 000 (k_grads_x / k_grads_t); N_pix = 640: 0.161 / 0.183 at 8 000, 1.085 / 0.971 at 100 000;
 //     N_h <= 8 (a wave owns two 16-pixel tiles there) from 96 spectra per CU on, and from 36 per CU (9 216) on for N_pix >= 1024:
@@ -279,24 +283,22 @@ inline int check_shape(int B, int Npix, int Nb, int Nh) {
 //       0.274 / 0.260 at 32 000, 0.83 / 0.62 at 100 000 (k_grads_x<8> / k_grads_t<8>).
 // QFA_F_PASS2_F32 / QFA_F_PASS2_XDL / QFA_F_PASS2_PIXRES in the call's `flags` force one form (A/B timing and the cross-checks of
 // the forms in tests/).
-inline bool pass2_use_xdl(int KP, unsigned flags) {
-    if (flags & QFA_F_PASS2_F32) return false;
-    return KP == 16 || KP == 8;
-}
-inline bool pass2_use_pixres(int KP, int B, int Npix, unsigned flags) {
-    if ((KP != 16 && KP != 8) || Npix < 16 || (flags & (QFA_F_PASS2_F32 | QFA_F_S3_FAST))) return false;
-    if (flags & QFA_F_PASS2_PIXRES) return true;
-    if (flags & QFA_F_PASS2_XDL) return false;
-    const int ncu = cu_count();
-    if (B >= 96 * ncu) return true;
+enum class Pass2 { F32, XDL, PIXRES, S12 };       // k_grads | k_grads_x | k_grads_t | k_s12_x + k_grads_s3 (N_h = 17..32)
+inline Pass2 pass2_form(int KP, int B, int Npix, unsigned flags) {
+    if (KP > 16) return Pass2::S12;
+    if (flags & QFA_F_PASS2_F32) return Pass2::F32;
+    if (Npix < 16) return Pass2::XDL;                  // (k_grads_t's ragged-tile staging wants N_pix >= 4)
+    if (flags & QFA_F_PASS2_PIXRES) return Pass2::PIXRES;
+    if (flags & QFA_F_PASS2_XDL) return Pass2::XDL;
+    if (B >= 96 * cu_count()) return Pass2::PIXRES;
     // Round 5, after the float16 stages (18 + 35 MFMAs per group instead of 36 + 51) and the reworked walk: the pixel-resident form
     // wins from a few hundred spectra on wherever the pixel axis gives every CU work (tools/pass2_crossover.sh,
     // profiles/r5_pass2_crossover.txt; step k_grads_x / k_grads_t in ms): N_h = 16, N_pix = 4000: 0.102 / 0.096 at 128 spectra,
     // 0.127 / 0.109 at 500, 0.206 / 0.149 at 2 000, 0.51 / 0.30 at 8 000; N_h = 8, N_pix = 2000: 0.080 / 0.088 at 256, 0.086 / 0.085
     // at 500, 0.095 / 0.083 at 1 000, 0.195 / 0.134 at 8 000; N_pix = 9243: 0.106 / 0.102 at 256, 0.182 / 0.148 at 1 000.
     // (Short pixel axes keep the rule of round 3: 96 spectra per CU.)
-    if (Npix < 1024) return false;
-    return KP == 16 ? B >= 128 : B >= 512;
+    if (Npix < 1024) return Pass2::XDL;
+    return (KP == 16 ? B >= 128 : B >= 512) ? Pass2::PIXRES : Pass2::XDL;
 }
 
 // launch errors of the calls just made; with QFA_F_SYNC also the asynchronous ones (the stream is drained first)
@@ -350,9 +352,10 @@ void sum_segments(float *MOM, const Layout &L, int B, hipStream_t st) {
 struct ZTables {
     const float4 *ZS, *ZP;
 };
+inline bool has_zfac(const qfa_batch_t &b, int Nb) { return b.zq1 && b.pix_ratio && Nb > 0; }
 inline ZTables launch_zfac(const qfa_params_t &p, const qfa_batch_t &b, const qfa_tau_t &tau, int B, int Nb, const Layout &L,
                            float *ws, hipStream_t st) {
-    if (!(b.zq1 && b.pix_ratio) || Nb <= 0) return ZTables{nullptr, nullptr};
+    if (!has_zfac(b, Nb)) return ZTables{nullptr, nullptr};
     float4 *ZS = reinterpret_cast<float4 *>(ws + L.oZS), *ZP = reinterpret_cast<float4 *>(ws + L.oZP);
     k_zfac_spec<<<(B + 255) / 256, 256, 0, st>>>(b.zq1, b.rows, p, tau, B, ZS);
     k_zfac_pix<<<(Nb + 255) / 256, 256, 0, st>>>(b.pix_ratio, p, tau, Nb, ZP);
@@ -390,169 +393,190 @@ void launch_moments(const qfa_params_t &p, const qfa_batch_t &b, const qfa_tau_t
         k_moments_x<KP, PREDICT, NW, false><<<L.wp1.items(), 64 * NW, 0, st>>>(p, b, tau, mu, B, L.Bpad, Npix, Nb, L.ntiles32, L.wp1, PFX, nullptr, MOM);
 }
 
-inline DetLayout det_layout(int B, int Npix, int Nb, int Nh) {
-    const Layout L = make_layout(B, Npix, Nh);
+inline DetLayout det_layout(const Layout &L, int B, int Npix, int Nb, int Nh) {
     size_t items = (size_t)(L.wp2.items() > L.wp2x.items() ? L.wp2.items() : L.wp2x.items());
     if (L.KP == 16 || L.KP == 8) items = std::max(items, 2 * (size_t)qfa_gt_items(L.KP, B, Npix, (int)det_rows(B)));   // (8 waves per item there)
-    DetLayout D;
-    D.NF = det_rows_floats(Npix, Nb, Nh);
-    D.stride = det_row_stride(Npix, Nb, Nh);
-    D.oS = (det_rows(B) * D.stride * sizeof(float) + 15) / 16 * 16;
-    D.oPart = D.oS + (items * 4 * 3 * sizeof(double) + 15) / 16 * 16;
-    D.bytes = D.oPart + det_chunks(B) * D.NF * sizeof(double);
-    return D;
+    return rows_region(det_rows(B), 4 * items, det_chunks(B), det_rows_floats(Npix, Nb, Nh), det_row_stride(Npix, Nb, Nh));
 }
-inline size_t det_slab_bytes(int B, int Npix, int Nb, int Nh) { return det_layout(B, Npix, Nb, Nh).bytes; }
+inline size_t det_slab_bytes(int B, int Npix, int Nb, int Nh) { return det_layout(make_layout(B, Npix, Nh), B, Npix, Nb, Nh).bytes; }
 
-// the fixed-order reduction of the slab into the packed buffer: rows in chunks of DET_CHUNK_ROWS (float64 partials,
+// the fixed-order reduction of `rows` slab rows into the packed buffer: rows in chunks of DET_CHUNK_ROWS (float64 partials,
 // rows in order), then the chunks in order
-inline void launch_reduce_slab(const float *slab, const DetLayout &D, int B, int nitemwaves, float *accum, hipStream_t st,
-                               int rows = -1) {
+inline void launch_reduce_slab(const float *slab, const DetLayout &D, int rows, int nitemwaves, float *accum, hipStream_t st) {
     const double *slabS = reinterpret_cast<const double *>(reinterpret_cast<const char *>(slab) + D.oS);
     double *part = reinterpret_cast<double *>(const_cast<char *>(reinterpret_cast<const char *>(slab)) + D.oPart);
-    // rows written by the launch: one per block of 64 spectra, or (pixel-resident pass 2) one per range of spectra
-    const int nblk = rows >= 0 ? rows : (int)det_rows(B), nch = (nblk + DET_CHUNK_ROWS - 1) / DET_CHUNK_ROWS;
+    const int nch = (rows + DET_CHUNK_ROWS - 1) / DET_CHUNK_ROWS;
     const unsigned gx = (unsigned)((D.NF + 255) / 256);
-    k_reduce_slab_rows<<<dim3(gx, (unsigned)nch), 256, 0, st>>>(slab, nblk, D.NF, D.stride, part);
+    k_reduce_slab_rows<<<dim3(gx, (unsigned)nch), 256, 0, st>>>(slab, rows, D.NF, D.stride, part);
     k_reduce_slab_fin<<<gx, 256, 0, st>>>(part, slabS, nch, nitemwaves, D.NF, accum);
 }
 
+// What a training step launches, decided once from the shape, the flags and whether the caller brought a slab.
+enum class Solve { RECORD, STATE, NLLRED };   // k_solve writes: the float32 record SOL | the operand images k_grads_t streams | SOL, and
+                                              // its last block sums the NLL of a small batch (no k_reduce_nll)
+struct StepPlan {
+    int err;               // QFA_E_FLAGS: the call asks for a form that does not exist at this N_h
+    Pass2 pass2;
+    Solve solve;
+    bool prep_step;        // the preparations are ONE launch (k_prep_step: both passes on the XDL pipe, N_h <= 16); else memset,
+                           // k_zfac_*, k_prep_pft, and k_prep_pfx in front of pass 1
+    int nred;              // blocks of k_reduce_nll; 0: the solve summed the NLL itself
+    // the fixed-order reducer behind pass 2 (rows == 0: pass 2 adds to the packed buffer itself)
+    bool rows_in_ws;       // the rows live in the workspace (Layout::oISLAB), not in a caller's slab
+    int max_ranges;        // pixel-resident pass 2: at most that many ranges of spectra (= rows)
+    int rows, itemwaves;   // rows written, scalar records written (waves per work item x items)
+    DetLayout D;           // of the region the rows live in (all zero without one)
+};
+inline StepPlan plan_step(const Layout &L, int B, int Npix, int Nb, int Nh, unsigned flags, bool slab) {
+    StepPlan P{};
+    if (L.KP <= 16 && (flags & QFA_F_S3_FAST)) {      // (the three-product form exists at N_h = 17..32 only)
+        P.err = QFA_E_FLAGS;
+        return P;
+    }
+    P.pass2 = pass2_form(L.KP, B, Npix, flags);
+    P.prep_step = P.pass2 == Pass2::XDL || P.pass2 == Pass2::PIXRES;
+    // (pixel-resident pass 2: the solve writes the operand images that form streams instead of the float32 record SOL;
+    // small batches -- one block of k_reduce_nll -- on the two-role form: the solve's last block sums the NLL itself)
+    P.solve = P.pass2 == Pass2::PIXRES ? Solve::STATE : (P.pass2 == Pass2::XDL && B <= 2048 ? Solve::NLLRED : Solve::RECORD);
+    P.nred = P.solve == Solve::NLLRED ? 0 : (B <= 2048 ? 1 : (B >= 2048 * NRED ? NRED : (B + 2047) / 2048));   // small batches: one block, no hand-over
+    if (slab) P.D = det_layout(L, B, Npix, Nb, Nh);
+    if (P.pass2 == Pass2::PIXRES) {
+        // the sums of a range leave as one slab row: the caller's slab (deterministic mode), else rows of the workspace
+        P.rows_in_ws = !slab;
+        P.max_ranges = slab ? (int)det_rows(B) : (1 << 30);
+        P.rows = qfa_gt_ranges(L.KP, B, Npix, P.max_ranges);
+        P.itemwaves = 8 * qfa_gt_items(L.KP, B, Npix, P.max_ranges);
+        if (!slab) P.D = pixres_rows_layout(P.rows, P.itemwaves, Npix, Nb, Nh);
+    } else if (slab) {
+        P.rows = (int)det_rows(B);
+        P.itemwaves = 4 * (P.pass2 == Pass2::F32 ? L.wp2.items() : L.wp2x.items());
+    }
+    return P;
+}
+
+// pass 2 in its float32-MFMA form (QFA_F_PASS2_F32, N_h <= 16): custom tau table / factored z / zabs
+template <int KP>
+void launch_grads_f32(const qfa_params_t &p, const qfa_batch_t &b, const qfa_tau_t &tau, int B, int Npix, int Nb, int Nh, const Layout &L,
+                      const float4 *ZS, const float *PFT, const float *SOL, float *accum, float *slab, double *slabS, int slab_stride,
+                      Scal64 *sc64, int exact, hipStream_t st) {
+    auto grads = [&](auto ex) {
+        constexpr bool E = decltype(ex)::value;
+        if (b.A_blue)
+            k_grads<KP, true, false, E><<<L.wp2.items(), 256, 0, st>>>(p, b, tau, B, Npix, Nb, Nh, L.ntiles, L.wp2, PFT, SOL, accum, slab, slabS, slab_stride, sc64, nullptr);
+        else if (ZS)
+            k_grads<KP, false, true, E><<<L.wp2.items(), 256, 0, st>>>(p, b, tau, B, Npix, Nb, Nh, L.ntiles, L.wp2, PFT, SOL, accum, slab, slabS, slab_stride, sc64, ZS);
+        else
+            k_grads<KP, false, false, E><<<L.wp2.items(), 256, 0, st>>>(p, b, tau, B, Npix, Nb, Nh, L.ntiles, L.wp2, PFT, SOL, accum, slab, slabS, slab_stride, sc64, nullptr);
+    };
+    if (exact) grads(std::true_type{});
+    else grads(std::false_type{});
+}
+
+// pass 2 at N_h = 17..32: stages 1 and 2 for every (spectrum, pixel) on the XDL pipe, beta / gamma through HBM, then stage 3 per
+// 16 columns
+template <int KP>
+void launch_s12_s3(const qfa_params_t &p, const qfa_batch_t &b, const qfa_tau_t &tau, int B, int Npix, int Nb, int Nh, const Layout &L,
+                   const ZTables &zt, float *ws, float *accum, float *slab, double *slabS, int slab_stride, Scal64 *sc64, int exact,
+                   bool s3_fast, hipStream_t st) {
+    const float *PFT = ws + L.oPFT, *SOL = ws + L.oSOL;
+    float *BG = ws + L.oBG, *GG = BG + (size_t)round_up(B, 64) * L.bg_stride;
+    unsigned char *IMG = reinterpret_cast<unsigned char *>(ws + L.oPGX);
+    k_prep_s12<KP><<<L.ntiles32, 256, 0, st>>>(p.F, p.Psi, p.omega, zt.ZP, Npix, Nb, Nh, IMG);
+    auto s12 = [&](auto hasa, auto zf, auto ex) {
+        k_s12_x<KP, decltype(hasa)::value, decltype(zf)::value, decltype(ex)::value><<<L.wp2x.items(), 256, 0, st>>>(
+            p, b, tau, B, Npix, Nb, Nh, L.ntiles32, L.wp2x, IMG, SOL, BG, GG, L.bg_stride, accum, slab, slabS, slab_stride,
+            sc64, decltype(zf)::value ? zt.ZS : nullptr);
+    };
+    auto s12e = [&](auto hasa, auto zf) {
+        if (exact) s12(hasa, zf, std::true_type{});
+        else s12(hasa, zf, std::false_type{});
+    };
+    if (b.A_blue) s12e(std::true_type{}, std::false_type{});
+    else if (zt.ZS) s12e(std::false_type{}, std::true_type{});
+    else s12e(std::false_type{}, std::false_type{});
+    for (int bh = 0; 16 * bh < Nh; ++bh) {
+        if (s3_fast)
+            k_grads_s3<KP, 3><<<L.wp2.items(), 256, 0, st>>>(B, Npix, Nh, L.ntiles, L.wp2, bh, PFT, SOL, BG, GG, L.bg_stride, accum, slab, slab_stride);
+        else
+            k_grads_s3<KP, 6><<<L.wp2.items(), 256, 0, st>>>(B, Npix, Nh, L.ntiles, L.wp2, bh, PFT, SOL, BG, GG, L.bg_stride, accum, slab, slab_stride);
+    }
+}
+
+// The training step: plan, preparations, pass 1, solve, NLL sum, pass 2, fixed-order reduction.  The stage events 0..4 stand in
+// front of the preparations, pass 1, the segment sum, pass 2, and behind everything.
 template <int KP>
 int run_nll_grad(const qfa_params_t &p, const qfa_batch_t &b, const qfa_tau_t &tau, int B, int Npix, int Nb, int Nh,
                  float *nll, float *accum, float *ws, hipStream_t st, void *const *events, void *slabv, unsigned flags) {
     const Layout L = make_layout_t<KP>(B, Npix);
-    float *slab = reinterpret_cast<float *>(slabv);
-    DetLayout D{};
-    if (slab) D = det_layout(B, Npix, Nb, Nh);
-    double *slabS = slab ? reinterpret_cast<double *>(reinterpret_cast<char *>(slab) + D.oS) : nullptr;
-    float *PFT = ws + L.oPFT, *MOM = ws + L.oMOM, *SOL = ws + L.oSOL, *NBL = ws + L.oNBL;
-    float *nllbuf = nll ? nll : ws + L.oNLL;
-    const size_t accS = (size_t)Npix * Nh + 3 * (size_t)Npix + Nb;
-    // QFA_F_EXACT_GRAD: k_solve forms Z = -C^-1, p = y; pass 2 sums the exact tau0 / c0 / beta terms; the buffer's slot 6
-    // counts the spectra of such launches (k_reduce_nll, or the solve's last block), and k_finalize* read the mode there
-    const int exact = (flags & QFA_F_EXACT_GRAD) ? 1 : 0;
-    const EventMarks mark{events, st};
-    bool pass2_xdl = false;
-    if constexpr (KP == 8 || KP == 16) pass2_xdl = pass2_use_xdl(KP, flags);
-    if constexpr (KP <= 16) { if (flags & QFA_F_S3_FAST) return QFA_E_FLAGS; }    // (the three-product form exists at N_h = 17..32 only)
-    mark(0);
-    const bool pixres = pass2_xdl && pass2_use_pixres(KP, B, Npix, flags);             // (its ragged-tile staging wants N_pix >= 4)
-    const size_t n_acc = (size_t)Npix * Nh + 3 * (size_t)Npix + Nb + 8;
-    ZTables zt{nullptr, nullptr};
-    bool fused = false;
-    if constexpr (KP == 8 || KP == 16) {
-        // both passes on the XDL pipe: ONE launch builds the two images and the per-spectrum factors (and zeroes accum)
-        if (pass2_xdl) {
-            fused = true;
-            const bool zf = b.zq1 && b.pix_ratio && Nb > 0;
-            if (zf) zt.ZS = reinterpret_cast<float4 *>(ws + L.oZS);
-            qfa_prep_step_launch(KP, pixres, p, b, tau, B, Npix, Nb, Nh, L.ntiles32, reinterpret_cast<unsigned char *>(ws + L.oPFX),
-                                 reinterpret_cast<unsigned char *>(ws + L.oPGX), zf ? ws + L.oZS : nullptr,
-                                 (flags & QFA_F_ZERO_ACCUM) ? accum : nullptr, n_acc, st,
-                                 reinterpret_cast<unsigned *>(reinterpret_cast<double *>(ws + L.oRED) + 2 * NRED) + 1);
+    const StepPlan P = plan_step(L, B, Npix, Nb, Nh, flags, slabv != nullptr);
+    if (P.err == 0) {
+        float *PFT = ws + L.oPFT, *MOM = ws + L.oMOM, *SOL = ws + L.oSOL, *NBL = ws + L.oNBL;
+        float *nllbuf = nll ? nll : ws + L.oNLL;
+        unsigned char *P2 = reinterpret_cast<unsigned char *>(ws + L.oPGX), *PST = reinterpret_cast<unsigned char *>(ws + L.oPST);
+        // the rows of the fixed-order reducer and their scalar records (NULL: pass 2 adds to the packed buffer with atomics)
+        float *rows = P.rows_in_ws ? ws + L.oISLAB : reinterpret_cast<float *>(slabv);
+        double *rowsS = rows ? reinterpret_cast<double *>(reinterpret_cast<char *>(rows) + P.D.oS) : nullptr;
+        const size_t accS = det_rows_floats(Npix, Nb, Nh), n_acc = accS + 8;
+        double *red = reinterpret_cast<double *>(ws + L.oRED);
+        unsigned *ticket = reinterpret_cast<unsigned *>(red + 2 * NRED);
+        Scal64 *sc64 = reinterpret_cast<Scal64 *>(ticket + 2);      // (zeroed by k_solve, like the ticket)
+        // QFA_F_EXACT_GRAD: k_solve forms Z = -C^-1, p = y; pass 2 sums the exact tau0 / c0 / beta terms; the buffer's slot 6
+        // counts the spectra of such launches (k_reduce_nll, or the solve's last block), and k_finalize* read the mode there
+        const int exact = (flags & QFA_F_EXACT_GRAD) ? 1 : 0;
+        const EventMarks mark{events, st};
+        mark(0);
+        ZTables zt{nullptr, nullptr};
+        if (P.prep_step) {
+            // ONE launch builds the two images and the per-spectrum factors, zeroes accum and the solve's arrival counter ticket[1]
+            if (has_zfac(b, Nb)) zt.ZS = reinterpret_cast<float4 *>(ws + L.oZS);
+            qfa_prep_step_launch(KP, P.pass2 == Pass2::PIXRES, p, b, tau, B, Npix, Nb, Nh, L.ntiles32,
+                                 reinterpret_cast<unsigned char *>(ws + L.oPFX), P2, zt.ZS ? ws + L.oZS : nullptr,
+                                 (flags & QFA_F_ZERO_ACCUM) ? accum : nullptr, n_acc, st, ticket + 1);
+        } else {
+            if (flags & QFA_F_ZERO_ACCUM) (void)hipMemsetAsync(accum, 0, n_acc * sizeof(float), st);
+            zt = launch_zfac(p, b, tau, B, Nb, L, ws, st);
+            launch_prep_pft<KP>(p, zt.ZP, Npix, Nb, Nh, L, PFT, st);
         }
-    }
-    if (!fused) {
-        if (flags & QFA_F_ZERO_ACCUM) (void)hipMemsetAsync(accum, 0, n_acc * sizeof(float), st);
-        zt = launch_zfac(p, b, tau, B, Nb, L, ws, st);
-        launch_prep_pft<KP>(p, zt.ZP, Npix, Nb, Nh, L, PFT, st);
-    }
-    mark(1);
-    launch_moments<KP, false>(p, b, tau, nullptr, B, Npix, Nb, Nh, L, zt, ws, st, !fused, exact != 0);
-    mark(2);
-    sum_segments<KP>(MOM, L, B, st);
-    double *red = reinterpret_cast<double *>(ws + L.oRED);
-    unsigned *ticket = reinterpret_cast<unsigned *>(red + 2 * NRED);
-    Scal64 *sc64 = reinterpret_cast<Scal64 *>(ticket + 2);      // (zeroed by k_solve, like the ticket)
-    // (pixel-resident pass 2: the solve writes the operand images that form streams instead of the float32 record SOL)
-    bool solved = false;
-    if constexpr (KP == 8 || KP == 16) {
-        if (pixres) {
-            k_solve<KP, false, true><<<solve_blocks<KP>(B), 256, 0, st>>>(MOM, SOL, nllbuf, NBL, B, Nh, nullptr, nullptr, ticket,
-                                                                               reinterpret_cast<unsigned char *>(ws + L.oPST), nullptr, exact);
-            solved = true;
+        mark(1);
+        launch_moments<KP, false>(p, b, tau, nullptr, B, Npix, Nb, Nh, L, zt, ws, st, !P.prep_step, exact != 0);
+        mark(2);
+        sum_segments<KP>(MOM, L, B, st);
+        switch (P.solve) {
+            case Solve::RECORD:
+                k_solve<KP, false><<<solve_blocks<KP>(B), 256, 0, st>>>(MOM, SOL, nllbuf, NBL, B, Nh, nullptr, nullptr, ticket, nullptr, nullptr, exact);
+                break;
+            case Solve::STATE:
+                if constexpr (KP <= 16)
+                    k_solve<KP, false, true><<<solve_blocks<KP>(B), 256, 0, st>>>(MOM, SOL, nllbuf, NBL, B, Nh, nullptr, nullptr, ticket, PST, nullptr, exact);
+                break;
+            case Solve::NLLRED:
+                if constexpr (KP <= 16)
+                    k_solve<KP, false, false, true><<<solve_blocks<KP>(B), 256, 0, st>>>(MOM, SOL, nllbuf, NBL, B, Nh, nullptr, nullptr, ticket, nullptr, accum + accS, exact);
+                break;
         }
-    }
-    // small batches (one block of k_reduce_nll): the solve's last block sums the NLL itself (ticket[1]: zeroed by k_prep_step)
-    bool nll_done = false;
-    if constexpr (KP == 8 || KP == 16) {
-        if (!solved && fused && B <= 2048) {
-            k_solve<KP, false, false, true><<<solve_blocks<KP>(B), 256, 0, st>>>(MOM, SOL, nllbuf, NBL, B, Nh, nullptr, nullptr, ticket,
-                                                                                      nullptr, accum + accS, exact);
-            solved = nll_done = true;
+        if (P.nred) k_reduce_nll<<<P.nred, 256, 0, st>>>(nllbuf, NBL, B, accum + accS, red, ticket, exact);
+        mark(3);
+        const float *ZS = reinterpret_cast<const float *>(zt.ZS);
+        switch (P.pass2) {
+            case Pass2::F32:
+                if constexpr (KP <= 16)
+                    launch_grads_f32<KP>(p, b, tau, B, Npix, Nb, Nh, L, zt.ZS, PFT, SOL, accum, rows, rowsS, (int)P.D.stride, sc64, exact, st);
+                break;
+            case Pass2::XDL:
+                qfa_gx_launch(KP, p, b, tau, B, Npix, Nb, Nh, L.ntiles32, L.wp2x, P2, SOL, ZS, accum, rows, rowsS, (int)P.D.stride, sc64, flags, st);
+                break;
+            case Pass2::PIXRES:
+                qfa_gt_launch(KP, p, b, tau, B, Npix, Nb, Nh, P.max_ranges, P2, PST, ZS, accum, rows, rowsS, (int)P.D.stride, sc64, exact, st);
+                break;
+            case Pass2::S12:
+                if constexpr (KP > 16)
+                    launch_s12_s3<KP>(p, b, tau, B, Npix, Nb, Nh, L, zt, ws, accum, rows, rowsS, (int)P.D.stride, sc64, exact, (flags & QFA_F_S3_FAST) != 0, st);
+                break;
         }
-    }
-    if (!solved) k_solve<KP, false><<<solve_blocks<KP>(B), 256, 0, st>>>(MOM, SOL, nllbuf, NBL, B, Nh, nullptr, nullptr, ticket,
-                                                                                nullptr, nullptr, exact);
-    const int nred = B <= 2048 ? 1 : (B >= 2048 * NRED ? NRED : (B + 2047) / 2048);     // small batches: one block, no hand-over
-    if (!nll_done) k_reduce_nll<<<nred, 256, 0, st>>>(nllbuf, NBL, B, accum + accS, red, ticket, exact);
-    mark(3);
-    if (pixres) {
-        int ranges = 0;
-        // the sums of a range leave as one slab row: the caller's slab (deterministic mode), else rows of the workspace
-        float *rowsb = slab;
-        DetLayout Dr = D;
-        const int maxr = slab ? (int)det_rows(B) : (1 << 30);
-        if (!slab) {
-            rowsb = ws + L.oISLAB;
-            Dr = pixres_rows_layout(KP, B, Npix, Nb, Nh, maxr);
-        }
-        double *rowsS = reinterpret_cast<double *>(reinterpret_cast<char *>(rowsb) + Dr.oS);
-        qfa_gt_launch(KP, p, b, tau, B, Npix, Nb, Nh, maxr, reinterpret_cast<unsigned char *>(ws + L.oPGX),
-                      reinterpret_cast<unsigned char *>(ws + L.oPST), reinterpret_cast<const float *>(zt.ZS), accum, rowsb, rowsS,
-                      (int)Dr.stride, sc64, exact, st, &ranges);
-        launch_reduce_slab(rowsb, Dr, B, qfa_gt_items(KP, B, Npix, maxr) * 8, accum, st, ranges);
+        if (P.rows) launch_reduce_slab(rows, P.D, P.rows, P.itemwaves, accum, st);
         mark(4);
-        return hip_status(st, flags);
     }
-    if (pass2_xdl) {
-        qfa_gx_launch(KP, p, b, tau, B, Npix, Nb, Nh, L.ntiles32, L.wp2x, reinterpret_cast<unsigned char *>(ws + L.oPGX), SOL,
-                      reinterpret_cast<const float *>(zt.ZS), reinterpret_cast<const float *>(zt.ZP), accum, slab, slabS,
-                      (int)D.stride, sc64, flags, st, !fused);
-        if (slab) launch_reduce_slab(slab, D, B, L.wp2x.items() * 4, accum, st);
-        mark(4);
-        return hip_status(st, flags);
-    }
-    if constexpr (KP == 32) {
-        // stages 1 and 2 for every (spectrum, pixel) on the XDL pipe, beta / gamma through HBM, then stage 3 per 16 columns
-        float *BG = ws + L.oBG, *GG = BG + (size_t)round_up(B, 64) * L.bg_stride;
-        unsigned char *IMG = reinterpret_cast<unsigned char *>(ws + L.oPGX);
-        k_prep_s12<KP><<<L.ntiles32, 256, 0, st>>>(p.F, p.Psi, p.omega, zt.ZP, Npix, Nb, Nh, IMG);
-        auto s12 = [&](auto hasa, auto zf, auto ex) {
-            k_s12_x<KP, decltype(hasa)::value, decltype(zf)::value, decltype(ex)::value><<<L.wp2x.items(), 256, 0, st>>>(
-                p, b, tau, B, Npix, Nb, Nh, L.ntiles32, L.wp2x, IMG, SOL, BG, GG, L.bg_stride, accum, slab, slabS, (int)D.stride,
-                sc64, decltype(zf)::value ? zt.ZS : nullptr);
-        };
-        auto s12e = [&](auto hasa, auto zf) {
-            if (exact) s12(hasa, zf, std::true_type{});
-            else s12(hasa, zf, std::false_type{});
-        };
-        if (b.A_blue) s12e(std::true_type{}, std::false_type{});
-        else if (zt.ZS) s12e(std::false_type{}, std::true_type{});
-        else s12e(std::false_type{}, std::false_type{});
-        for (int bh = 0; 16 * bh < Nh; ++bh) {
-            if (flags & QFA_F_S3_FAST)
-                k_grads_s3<KP, 3><<<L.wp2.items(), 256, 0, st>>>(B, Npix, Nh, L.ntiles, L.wp2, bh, PFT, SOL, BG, GG, L.bg_stride, accum, slab, (int)D.stride);
-            else
-                k_grads_s3<KP, 6><<<L.wp2.items(), 256, 0, st>>>(B, Npix, Nh, L.ntiles, L.wp2, bh, PFT, SOL, BG, GG, L.bg_stride, accum, slab, (int)D.stride);
-        }
-        if (slab) launch_reduce_slab(slab, D, B, L.wp2x.items() * 4, accum, st);
-    } else {
-        auto grads = [&](auto ex) {   // the float32-MFMA form (QFA_F_PASS2_F32, N_h <= 16): custom tau table / factored z / zabs
-            constexpr bool E = decltype(ex)::value;
-            if (b.A_blue)
-                k_grads<KP, true, false, E><<<L.wp2.items(), 256, 0, st>>>(p, b, tau, B, Npix, Nb, Nh, L.ntiles, L.wp2, PFT, SOL, accum, slab, slabS, (int)D.stride, sc64, nullptr);
-            else if (zt.ZS)
-                k_grads<KP, false, true, E><<<L.wp2.items(), 256, 0, st>>>(p, b, tau, B, Npix, Nb, Nh, L.ntiles, L.wp2, PFT, SOL, accum, slab, slabS, (int)D.stride, sc64, zt.ZS);
-            else
-                k_grads<KP, false, false, E><<<L.wp2.items(), 256, 0, st>>>(p, b, tau, B, Npix, Nb, Nh, L.ntiles, L.wp2, PFT, SOL, accum, slab, slabS, (int)D.stride, sc64, nullptr);
-        };
-        if (exact) grads(std::true_type{});
-        else grads(std::false_type{});
-        if (slab) launch_reduce_slab(slab, D, B, L.wp2.items() * 4, accum, st);
-    }
-    mark(4);
-    return hip_status(st, flags);
+    return P.err ? P.err : hip_status(st, flags);
 }
 
 template <int KP>

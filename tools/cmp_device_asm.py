@@ -1,10 +1,18 @@
 #!/usr/bin/env python3
-"""tools/cmp_device_asm.py PARENT_BUILD_DIR RESULT_BUILD_DIR [--strip-comments]: compare the device assembly (-save-temps, build/*-hip-amdgcn-*.s)
-of two builds kernel by kernel; profiles/retired_switches_asm_identity.txt was made with it."""
+"""tools/cmp_device_asm.py PARENT_BUILD_DIR RESULT_BUILD_DIR [--strip-comments] [--rename REGEX=REPLACEMENT ...]: compare the device
+assembly (-save-temps, build/*-hip-amdgcn-*.s) of two builds kernel by kernel; profiles/retired_switches_asm_identity.txt was made with it.
+--rename rewrites symbols of the PARENT before the comparison (a kernel that lost a template argument keeps its body under a new mangled
+name); the old -> new names it produced are printed."""
 import re, sys, glob, os
-STRIP = len(sys.argv) > 3 and sys.argv[3] == '--strip-comments'
-def load(path):
+STRIP = '--strip-comments' in sys.argv[3:]
+RENAMES = [tuple(sys.argv[i + 1].split('=', 1)) for i, a in enumerate(sys.argv) if a == '--rename']
+renamed = {}
+def load(path, parent=False):
     t = re.sub(r'__hip_cuid_[0-9a-f]+', '__hip_cuid_X', open(path).read())
+    for pat, rep in (RENAMES if parent else []):
+        for m in re.finditer(r'[\w$.]*(?:' + pat + r')[\w$.]*', t):
+            renamed.setdefault(m.group(0), re.sub(pat, rep, m.group(0)))
+        t = re.sub(pat, rep, t)
     if STRIP:
         # assembler comments (hipcc writes the names of the IR blocks there: they count the blocks of arms that were never
         # emitted) and the ordinal of the function inside the file in its local labels (.LBB12_3, .Lfunc_end12, .Ltmp..)
@@ -43,7 +51,7 @@ for pa in sorted(glob.glob(os.path.join(sys.argv[1], '*-hip-amdgcn-amd-amdhsa-gf
     name = os.path.basename(pa)
     ra = os.path.join(sys.argv[2], name)
     if not os.path.exists(ra): print(name, 'MISSING in result'); ok = False; continue
-    a, b = load(pa), load(ra)
+    a, b = load(pa, True), load(ra)
     short = name.split('-hip-')[0]
     if a == b:
         print(f'{short}: identical ({len(a.splitlines())} lines)'); continue
@@ -59,4 +67,5 @@ for pa in sorted(glob.glob(os.path.join(sys.argv[1], '*-hip-amdgcn-amd-amdhsa-gf
     for k in diff: print('   BODY DIFFERS:', k); ok = False
     for k in mdiff: print('   METADATA DIFFERS:', k); ok = False
     if pa_ != pb_ and not removed: ok = False
+for old in sorted(k for k in renamed if k.startswith('_Z') and '.' not in k): print('renamed:', old, '->', renamed[old])
 sys.exit(0 if ok else 1)

@@ -11,7 +11,7 @@ for line in open(summary):
         names.append(name)
         cur = name.split("<")[0]
         targs = [a.strip() for a in name[name.find("<") + 1:name.rfind(">")].split(",")] if "<" in name else []
-        # the factored-z instantiations are kept apart: template argument ZF = the last one of k_grads_x<KP, HASA, TERMS, ZF> and
+        # the factored-z instantiations are kept apart: template argument ZF = the last one of k_grads_x<KP, HASA, ZF> and
         # k_moments_x<KP, PREDICT, NW, ZF>, the third of k_grads_t<KP, HASA, ZF, IDX>
         zf = (cur in ("k_grads_x", "k_moments_x") and targs and targs[-1] == "true") or (cur in ("k_grads_t", "k_s12_x", "k_grads") and len(targs) >= 3 and targs[2] == "true")
         if zf:
@@ -29,9 +29,6 @@ res = {"config": cfg, "B": B,
        "kernels_measured": names,
        "method": "rocprofv3 --pmc, separate passes (FETCH_SIZE | WRITE_SIZE | TCC_EA0_RDREQ*); "
        "bytes = 2*FETCH_SIZE*1024 + WRITE_SIZE*1024; check: TCC_EA0_RDREQ_128B*128"}
-# (k_prep_pst: the operand images of the pixel-resident pass 2, written behind the solve and counted with it)
-if "k_prep_pst" in vals and "k_solve" in vals:
-    for c in vals["k_prep_pst"]: vals["k_solve"][c] = vals["k_solve"].get(c, 0) + vals["k_prep_pst"][c]
 for k in ("k_grads", "k_grads_x", "k_grads_t", "k_moments", "k_solve", "k_grads_x_zfac", "k_grads_t_zfac", "k_moments_x_zfac"):
     v = vals.get(k, {})
     if k == "k_moments" and "k_moments_x" in vals:      # pass 1 on the XDL pipe (N_h <= 16)
