@@ -516,6 +516,9 @@ __global__ __launch_bounds__(512, 2) void k_grads_t(qfa_params_t p, qfa_batch_t 
     // ---- the state parts: a contiguous run of 1-KiB pieces per wave.  A request costs the issuing wave ~80 - 100 cycles, and
     // the waves with a blue tile are the critical path of a step (stage 2 of a blue group is 1 200 cycles against 800): the
     // pieces go to the waves with a red tile or none ("duty" waves) when there are at least five of them, else to all eight
+    // (MIN_DUTY is also what bounds a wave's run of a part, PartZ / PartS below: a part is never dealt to fewer waves)
+    constexpr int MIN_DUTY = 5;
+    static_assert(MIN_DUTY <= GT::NW, "the parts go to MIN_DUTY duty waves or to all NW");
     int nduty = 0, drank = 0;
     bool duty = true;
     {
@@ -527,7 +530,7 @@ __global__ __launch_bounds__(512, 2) void k_grads_t(qfa_params_t p, qfa_batch_t 
             if (w < wv8 && d) ++rk;
             if (d) ++nd;
         }
-        if (nd >= 5) { nduty = nd; drank = rk; duty = !blueTile; }
+        if (nd >= MIN_DUTY) { nduty = nd; drank = rk; duty = !blueTile; }
         else { nduty = GT::NW; drank = wv8; duty = true; }
     }
     const int s1_q = GT::S1_PCS / nduty, s1_r = GT::S1_PCS % nduty, z_q = GT::Z_PCS / nduty, z_r = GT::Z_PCS % nduty;
@@ -560,19 +563,23 @@ __global__ __launch_bounds__(512, 2) void k_grads_t(qfa_params_t p, qfa_batch_t 
         unsigned dst;                  // LDS byte address of the run, biased the same way
         int cnt;
     };
+    // A wave's run of a part is at most MAX pieces (the parts go to MIN_DUTY waves or more, above): the piece sites of a stage beyond
+    // MAX -- three of the seven of the Z part, four of the S1 part's at KP = 16 -- hold no code (each was a test and a branch)
+    struct PartZ : Part { enum { MAX = (GT::Z_PCS + MIN_DUTY - 1) / MIN_DUTY }; };
+    struct PartS : Part { enum { MAX = (GT::S1_PCS + MIN_DUTY - 1) / MIN_DUTY }; };
     struct NoPart {};
     constexpr unsigned PBIAS = QFA_TRACKED_LOADS ? 0u : 4096u;
     const unsigned lane16 = (unsigned)lane * 16u;
     auto part_begin = [&](const auto &pt) __attribute__((always_inline)) {
-        if constexpr (std::is_same_v<std::decay_t<decltype(pt)>, Part>) {
+        if constexpr (std::is_base_of_v<Part, std::decay_t<decltype(pt)>>) {
 #if !QFA_TRACKED_LOADS
             asm volatile("s_mov_b32 m0, %0\n\ts_nop 0" ::"s"(pt.dst));
 #endif
         }
     };
     auto piece = [&](const auto &pt, int j) __attribute__((always_inline)) {
-        if constexpr (std::is_same_v<std::decay_t<decltype(pt)>, Part>) {
-            if (j < pt.cnt) {
+        if constexpr (std::is_base_of_v<Part, std::decay_t<decltype(pt)>>) {
+            if (j < std::decay_t<decltype(pt)>::MAX && j < pt.cnt) {
 #if QFA_TRACKED_LOADS
                 glds16a(pt.src + 1024 * j, lane16, pt.dst + 1024 * j);
 #else
@@ -583,17 +590,19 @@ __global__ __launch_bounds__(512, 2) void k_grads_t(qfa_params_t p, qfa_batch_t 
             }
         }
     };
-    static_assert((GT::Z_PCS + 4) / 5 <= 8 && (GT::S1_PCS + 4) / 5 <= 8, "a wave's run of a part: at most eight pieces (immediate offsets)");
+    static_assert(PartZ::MAX <= 8 && PartS::MAX <= 8, "a wave's run of a part: at most eight pieces (immediate offsets)");
 
     // ---- stage 1 of group t (its results wait in afy / aq for stage 2, one half-step later); the operands of a K block are
     // read once for the wave's TPW tiles
     f32x4 afy[TPW], aq[TPW];
 #pragma unroll
     for (int j = 0; j < TPW; ++j) afy[j] = aq[j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    auto stage1 = [&](int t, const auto &pt) __attribute__((always_inline)) {
+    // (par: the ring slot, t & 1 of the group -- a literal in the unrolled walk, where every address below is then an immediate
+    // offset off one per-lane base)
+    auto stage1 = [&](int par, const auto &pt) __attribute__((always_inline)) {
         __builtin_amdgcn_s_setprio(2);
         part_begin(pt);
-        const unsigned char *sp = lds + GT::L_S1 + (t & 1) * GT::S1P_B + lane * 16;
+        const unsigned char *sp = lds + GT::L_S1 + par * GT::S1P_B + lane * 16;
 #pragma unroll
         for (int j = 0; j < TPW; ++j) afy[j] = aq[j] = f32x4{0.f, 0.f, 0.f, 0.f};
         constexpr int NP = GT::S1NP;
@@ -602,10 +611,10 @@ __global__ __launch_bounds__(512, 2) void k_grads_t(qfa_params_t p, qfa_batch_t 
         for (int pc = 0; pc < NP; ++pc) aop[0][pc] = *reinterpret_cast<const u32x4 *>(sp + pc * 1024);
         // stage 1 (float16 pieces): the inverse powers of two of the lane's four spectra (Cinv', y), out of the y block's free K slots
         f32x4 isc[2] = {f32x4{1.f, 1.f, 1.f, 1.f}, f32x4{1.f, 1.f, 1.f, 1.f}};
-        const unsigned char *sq = lds + GT::L_S1 + (t & 1) * GT::S1P_B + GT::S1_SCALES + 32 * g;
+        const unsigned char *sq = lds + GT::L_S1 + par * GT::S1P_B + GT::S1_SCALES + 32 * g;
         isc[0] = *reinterpret_cast<const f32x4 *>(sq);          // 1 / scale(Cinv'), 1 / scale(y) of spectra 4 g, 4 g + 1
         isc[1] = *reinterpret_cast<const f32x4 *>(sq + 16);     // ... of 4 g + 2, 4 g + 3
-        zfac = *reinterpret_cast<const f32x4 *>(lds + GT::L_S1 + (t & 1) * GT::S1P_B + GT::S1_ZFAC + 16 * g);
+        zfac = *reinterpret_cast<const f32x4 *>(lds + GT::L_S1 + par * GT::S1P_B + GT::S1_ZFAC + 16 * g);
 #pragma unroll
         for (int ks = 0; ks < GT::NKS; ++ks) {
             if (ks + 1 < GT::NKS) {
@@ -644,8 +653,8 @@ __global__ __launch_bounds__(512, 2) void k_grads_t(qfa_params_t p, qfa_batch_t 
     for (int j = 0; j < TPW; ++j)
 #pragma unroll
         for (int r = 0; r < 4; ++r) { dv[j][r] = sgv[j][r] = zv[j][r] = 0.f; mk[j][r] = 0u; }
-    auto take = [&](int t) __attribute__((always_inline)) {
-        const unsigned char *sb = stg + (t & 1) * GT::STG_B;
+    auto take = [&](int par) __attribute__((always_inline)) {
+        const unsigned char *sb = stg + par * GT::STG_B;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int q = (4 * g + r) ^ (g & 1);
@@ -669,20 +678,23 @@ __global__ __launch_bounds__(512, 2) void k_grads_t(qfa_params_t p, qfa_batch_t 
         }
     };
     // ---- stage 2 of group t
-    auto stage2_t = [&](auto blue_tag, int t, const auto &pt) __attribute__((always_inline)) {
+    // FULL (full_tag): a group of 16 spectra of the batch on a tile inside the pixel axis -- the walk's steady state (below): the
+    // spectrum and the pixel of every element exist, an element counts when its mask does
+    auto stage2_t = [&](auto blue_tag, auto full_tag, int t, int par, const auto &pt) __attribute__((always_inline)) {
         constexpr bool BLUE = decltype(blue_tag)::value;       // (the tile has blue pixels: wave-uniform, one branch per stage)
+        constexpr bool FULL = decltype(full_tag)::value;
         const int s0 = 16 * (g0 + t);
-        take(t);
+        take(par);
         float zqx[4] = {0.f, 0.f, 0.f, 0.f}, zqy[4] = {0.f, 0.f, 0.f, 0.f}, zqz[4] = {0.f, 0.f, 0.f, 0.f};
         if (ZF && BLUE) {      // (the factors of the lane's four spectra)
-            const unsigned char *sb = stg + (t & 1) * GT::STG_B;
+            const unsigned char *sb = stg + par * GT::STG_B;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const float4 q = reinterpret_cast<const float4 *>(sb + 2 * GT::STG_ARR)[4 * g + r];
                 zqx[r] = q.x; zqy[r] = q.y; zqz[r] = q.z;
             }
         }
-        if (IDX && t + 2 < n) ri_next = read_rows(t + 2, t & 1, std::false_type{});      // (for stage 3's requests)
+        if (IDX && t + 2 < n) ri_next = read_rows(t + 2, par, std::false_type{});        // (for stage 3's requests)
         bool wvm[TPW][4];                                        // element counts: mask & spectrum < B & pixel < Npix (lane masks)
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       // staging buffer read: it may be overwritten now
 #pragma unroll
@@ -693,7 +705,7 @@ __global__ __launch_bounds__(512, 2) void k_grads_t(qfa_params_t p, qfa_batch_t 
 #pragma unroll
         for (int j = 0; j < TPW; ++j)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) wvm[j][r] = inb[j] & (s0 + 4 * g + r < B) & (mk[j][r] != 0u);
+            for (int r = 0; r < 4; ++r) wvm[j][r] = FULL ? mk[j][r] != 0u : (inb[j] & (s0 + 4 * g + r < B) & (mk[j][r] != 0u));
         GTS(6)
         part_begin(pt);
         piece(pt, 0);
@@ -793,9 +805,9 @@ __global__ __launch_bounds__(512, 2) void k_grads_t(qfa_params_t p, qfa_batch_t 
             d_beta += (double)t_beta;
         }
     };
-    auto stage2 = [&](int t, const auto &pt) __attribute__((always_inline)) {       // (the prologue's call)
-        if (blueTile) stage2_t(std::true_type{}, t, pt);
-        else stage2_t(std::false_type{}, t, pt);
+    auto stage2 = [&](auto full_tag, int t, int par, const auto &pt) __attribute__((always_inline)) {
+        if (blueTile) stage2_t(std::true_type{}, full_tag, t, par, pt);
+        else stage2_t(std::false_type{}, full_tag, t, par, pt);
     };
 
     // ---- stage 3 of group t: W[a] += Z pieces x the lane's own beta pieces (K = spectrum), the gamma term likewise; the Z
@@ -804,16 +816,22 @@ __global__ __launch_bounds__(512, 2) void k_grads_t(qfa_params_t p, qfa_batch_t 
     // form one request per column tile in front of the part's pieces, every other form (the first two groups are the prologue's)
     // as a block at the start.  They have the rest of the step to land: every wave waits for everything at the next barrier.
     const int nfull = max(0, min(n, (B >> 4) - g0));         // groups of the range with 16 spectra
-    auto stage3 = [&](int t, const auto &pt) __attribute__((always_inline)) {
+    // MODE (mode_tag): 0 = any step; 1 = group t + 2 belongs to the range (its requests are unconditional); 2 = and it is a full
+    // group on a wave with running pointers (runok): one request per site, no general-path code in the stage
+    auto stage3 = [&](auto mode_tag, int t, int par, const auto &pt) __attribute__((always_inline)) {
+        constexpr int MODE = decltype(mode_tag)::value;
+        static_assert(MODE != 2 || RUNP, "running pointers");
         __builtin_amdgcn_s_setprio(2);
-        const bool run = RUNP && runok && t + 2 < nfull;
-        if (t + 2 < n && !run) {
-            // (batch order: the rows follow from t -- no LDS read; indexed form: stage 2 (t) read them out of the buffer)
-            const RowIdx ri = IDX ? ri_next : read_rows(t + 2, t & 1, std::false_type{});
-            stage_spectra(t + 2, t & 1, ri, std::false_type{});
+        const bool run = MODE == 2 || (RUNP && runok && t + 2 < nfull);
+        if constexpr (MODE != 2) {
+            if ((MODE == 1 || t + 2 < n) && !run) {
+                // (batch order: the rows follow from t -- no LDS read; indexed form: stage 2 (t) read them out of the buffer)
+                const RowIdx ri = IDX ? ri_next : read_rows(t + 2, par, std::false_type{});
+                stage_spectra(t + 2, par, ri, std::false_type{});
+            }
         }
         if (!RUNP) part_begin(pt);
-        const unsigned char *zp = lds + GT::L_Z + (t & 1) * GT::ZP_B + lane * 16;
+        const unsigned char *zp = lds + GT::L_Z + par * GT::ZP_B + lane * 16;
         // bf16: three MFMAs per column tile ({l | h} x {h | l}, {h | m} x {m | m}, {h | m} x {h | h}: six products, K = 16 spectra x 2
         // piece slots); float16: two ({h | m} x {h | h} and {h | m} x {m | 0}: three products)
         u32x4 bhl[TPW], bmm[TPW], bhh[TPW];
@@ -845,7 +863,7 @@ __global__ __launch_bounds__(512, 2) void k_grads_t(qfa_params_t p, qfa_batch_t 
                 // tiles only); behind them the part's pieces (at most 7)
                 constexpr int RQS = 2, P0 = 3 * RQS + 1;
                 static_assert(P0 + 7 <= GT::NWT, "piece sites");
-                if (a < P0) { if (a % RQS == 0 && run && (a / RQS != 2 || blueTile)) stage_req(t & 1, a / RQS); }
+                if (a < P0) { if (a % RQS == 0 && run && (a / RQS != 2 || blueTile)) stage_req(par, a / RQS); }
                 else {
                     if (a == P0) part_begin(pt);
                     if (a - P0 < 7) piece(pt, a - P0);
@@ -899,7 +917,7 @@ __global__ __launch_bounds__(512, 2) void k_grads_t(qfa_params_t p, qfa_batch_t 
     const NoPart none{};
     if (active && n > 0) {
         stage1(0, none);
-        if (lead) stage2(0, none);
+        if (lead) stage2(std::false_type{}, 0, 0, none);
     }
     // The parts' source pointers and ring slots run along the walk: the Z part of group t + 1 goes to slot (t + 1) & 1, the S1
     // part of group t + 2 to slot t & 1.  (One walk for every kind of wave: instantiated per (blue, duty) -- six loops -- hipcc
@@ -915,37 +933,90 @@ __global__ __launch_bounds__(512, 2) void k_grads_t(qfa_params_t p, qfa_batch_t 
             zsrc += GT::STATE_B; ssrc += GT::STATE_B;
             zdst = 2 * zd0 + GT::ZP_B - zdst; sdst = 2 * sd0 + GT::S1P_B - sdst;
         };
+        // The steady state, two groups (an even and an odd ring slot) per iteration: the steps t < nst, in which the groups t + 1
+        // and t + 2 belong to the range -- every part has its full count, no stage is conditional -- and, with running pointers
+        // (RUNP, a wave with runok), t + 2 is a full group as well: the stages run in their FULL / MODE 2 form, which holds no
+        // general-path code, and the slot of every LDS address is a literal.  What is left of the range (its last two or three
+        // groups, the partial last group of a batch; every step of a ragged or straddling tile) takes the general step
+        // behind it, which starts at an even t: zdst / sdst stand where they stood at t = 0.
+        constexpr int SMODE = RUNP ? 2 : 1;
+        using SFull = std::integral_constant<bool, RUNP>;
+        using SMode = std::integral_constant<int, SMODE>;
+        const int nst = (RUNP ? (runok ? max(0, nfull - 2) : 0) : max(0, n - 2)) & ~1;
+        const unsigned zdst_s[2] = {zd0 + GT::ZP_B, zd0}, sdst_s[2] = {sd0, sd0 + GT::S1P_B};      // slot of Z(t + 1), S1(t + 2) at step parity 0, 1
+        auto steady_lead = [&](int t, int par) __attribute__((always_inline)) {
+            dma_wait<0>();
+            GTS(0)
+            step_barrier();
+            GTS(1)
+            const PartZ pz{{zsrc, zdst_s[par], z_req}};
+            const PartS ps{{ssrc, sdst_s[par], s1_req}};
+            stage3(SMode{}, t, par, pz);
+            GTS(4)
+            stage1(par ^ 1, ps);
+            stage2(SFull{}, t + 1, par ^ 1, none);
+            GTS(3)
+            zsrc += GT::STATE_B; ssrc += GT::STATE_B;
+        };
+        auto steady_rear = [&](int t, int par) __attribute__((always_inline)) {
+            dma_wait<0>();
+            GTS(0)
+            step_barrier();
+            GTS(1)
+            const PartZ pz{{zsrc, zdst_s[par], z_req}};
+            const PartS ps{{ssrc, sdst_s[par], s1_req}};
+            stage2(SFull{}, t, par, none);
+            GTS(3)
+            stage3(SMode{}, t, par, ps);
+            GTS(4)
+            stage1(par ^ 1, pz);
+            zsrc += GT::STATE_B; ssrc += GT::STATE_B;
+        };
+        using Any = std::false_type;
+        using AnyMode = std::integral_constant<int, 0>;
         if (lead) {
-            for (int t = 0; t < n; ++t) {
+            int t = 0;
+            for (; t < nst; t += 2) {
+                steady_lead(t, 0);
+                steady_lead(t + 1, 1);
+            }
+            for (; t < n; ++t) {
                 dma_wait<0>();       // (round 5: the staging requests sit in stage 3, the first stage of the step -- nothing is left in flight)
                 GTS(0)
                 step_barrier();
                 GTS(1)
-                const Part pz{zsrc, zdst, t + 1 < n ? z_req : 0}, ps{ssrc, sdst, t + 2 < n ? s1_req : 0};
-                stage3(t, pz);
+                const PartZ pz{{zsrc, zdst, t + 1 < n ? z_req : 0}};
+                const PartS ps{{ssrc, sdst, t + 2 < n ? s1_req : 0}};
+                stage3(AnyMode{}, t, t & 1, pz);
                 GTS(4)
                 if (t + 1 < n) {
-                    stage1(t + 1, ps);
-                    stage2(t + 1, none);
+                    stage1((t + 1) & 1, ps);
+                    stage2(Any{}, t + 1, (t + 1) & 1, none);
                     GTS(3)
                 }
                 next();
             }
         } else {
-            for (int t = 0; t < n; ++t) {
+            int t = 0;
+            for (; t < nst; t += 2) {
+                steady_rear(t, 0);
+                steady_rear(t + 1, 1);
+            }
+            for (; t < n; ++t) {
                 dma_wait<0>();
                 GTS(0)
                 step_barrier();
                 GTS(1)
-                const Part pz{zsrc, zdst, t + 1 < n ? z_req : 0}, ps{ssrc, sdst, t + 2 < n ? s1_req : 0};
+                const PartZ pz{{zsrc, zdst, t + 1 < n ? z_req : 0}};
+                const PartS ps{{ssrc, sdst, t + 2 < n ? s1_req : 0}};
                 // waves 4..7: the Z part's pieces between the MFMAs of stage 1 instead of between the elements of stage 2
                 // (a piece issued in stage 2 -- VALU work, nothing to hide behind -- cost the issuing wave ~100 cycles: stage 2 of a RED
                 // duty wave, one reciprocal per element, took 1 134 cycles with its seven pieces; between MFMAs they are free)
-                stage2(t, none);
+                stage2(Any{}, t, t & 1, none);
                 GTS(3)
-                stage3(t, ps);
+                stage3(AnyMode{}, t, t & 1, ps);
                 GTS(4)
-                if (t + 1 < n) stage1(t + 1, pz);
+                if (t + 1 < n) stage1((t + 1) & 1, pz);
                 next();
             }
         }
