@@ -602,6 +602,66 @@ int qfa_variance_f32(const float *trans, const float *ivar, const qfa_batch_t *b
                      const qfa_p1d_t *p, const qfa_var_t *q, unsigned flags, double *moments, double *stack,
                      void *workspace, size_t workspace_bytes, void *stream);
 
+/* Observed-frame spectra onto the common rest-frame grid: rebin, normalise, S/N and the catalogue's counts (additive to ABI v4).
+ * Every other entry point assumes the reference's contract -- "all spectra should have same wavelength grid", "spectra are
+ * preprocessed as in the paper" (reference QFA/dataloader.py:21-24): rest frame, the common log-lambda grid, normalised at 1280 A,
+ * -999 sentinels, and a catalogue whose `snr` and `num_mask` columns exist (QFA/dataloader.py:49).  The reference ships no such step.
+ * This call takes spectra as a survey delivers them and writes the two (N, Npix) float32 arrays the loaders accept, and the
+ * catalogue's columns.
+ *
+ * The contract.  N spectra, ragged: spectrum i owns the input pixels offsets[i] .. offsets[i + 1] - 1 (n of them) of
+ *   inputs     wave (float64, observed-frame pixel centres in Angstrom, strictly increasing inside a spectrum), flux (float32),
+ *              ivar (float32), bad (uint8, or NULL), offsets (int64, N + 1, non-decreasing, every n <= max_n_in: the CALLER checks
+ *              these, the arrays live on the device), zqso (float64, N).  Input pixel j is usable when ivar_j > 0 and finite,
+ *              flux_j is finite and bad_j == 0 (NULL: every bad_j = 0);  u_j = ivar_j if usable, else 0.  What an unusable pixel
+ *              holds in flux (NaN, inf) reaches no sum: selects, not products.
+ *              out_edges (float64, Npix + 1, rest frame, increasing: the caller checks) and wav_grid (float64, Npix, the pixel
+ *              centres the windows below are tested on) come from the host, so both sides of every comparison share their bits;
+ *   geometry   all in float64.  Input edges (n >= 2):  e_j = 0.5 (w_{j-1} + w_j) for 0 < j < n,  e_0 = w_0 - (e_1 - w_0),
+ *              e_n = w_{n-1} + (w_{n-1} - e_{n-1}) -- additions, subtractions and halvings only, which no fused contraction can
+ *              change.  Output edges in the observed frame E_k = out_edges[k] (1 + z) (one product, 1 + z one addition);
+ *              width(k) = E_{k+1} - E_k;  overlap(j, k) = max(0, min(e_{j+1}, E_{k+1}) - max(e_j, E_k)).  A spectrum with n < 2, or
+ *              whose 1 + z is not a positive finite number, covers nothing;
+ *   rebin      per output pixel k, float64, every operation rounded once, no contraction, the sums in input-pixel order:
+ *                c_jk = overlap(j, k) / width(k)              W = sum_j c_jk u_j              coverage_k = sum_{j usable} c_jk
+ *                flux_k = (sum_j (c_jk u_j) f_j) / W          ivar_k = (W W) / sum_j c_jk (c_jk u_j)
+ *              ivar_k is the inverse variance of that weighted mean for independent input pixels.  Pixel k is VALID iff
+ *              coverage_k >= min_coverage and W > 0;
+ *   norm       norm = (sum_k ivar_k flux_k) / (sum_k ivar_k) over the valid pixels with norm_lo <= wav_grid[k] < norm_hi, of the
+ *              unrounded flux_k ("normalized at rest-frame wavelength 1280 A", reference nb/predict.ipynb).  The spectrum is OK
+ *              iff that window holds at least norm_min_pixels valid pixels and norm > 0 and finite;
+ *   outputs    flux_out[i, k] = float32(flux_k / norm), error_out[i, k] = float32(1 / (sqrt(ivar_k) norm)); exactly -999.0f in both
+ *              for an invalid pixel and for EVERY pixel of a spectrum that is not ok -- the reference's sentinels: the mask is
+ *              (flux != -999) & (error != -999) as everywhere else.  (N, Npix) contiguous, written once, 64-bit indices;
+ *   record     per spectrum, whether ok or not, from the valid flags of the rebin, in two arrays: record_f64 (N, 2) = [norm | snr],
+ *              record_i32 (N, 5) = [n_valid | n_lead | n_trail | num_mask | ok].  snr = the mean of
+ *              flux_k sqrt(ivar_k) over the valid pixels with snr_lo <= wav_grid[k] < snr_hi, NaN if there are none;  n_valid;
+ *              n_lead / n_trail = the length of the invalid run that touches the blue / red end (Npix in both when nothing is
+ *              valid);  num_mask = the number of maximal runs of invalid pixels that touch neither end, the catalogue's "masked
+ *              regions" (reference main.py:33) -- a leading run is what the spectrograph's blue limit leaves at low z: reported,
+ *              but no masked region;  ok (0 / 1).  The five integers are int32 and exact;
+ *   sums       float64 in one fixed order (per thread in order of k, a butterfly over the wave, the waves in order), no atomics.  A
+ *              spectrum's outputs depend on that spectrum alone -- not on N, on how a data set is cut into calls, or on the number
+ *              of ranks that share it -- and two calls on the same inputs give the same bits.
+ * qfa_preprocess_workspace_bytes: the scratch (one byte per output pixel: its window flags); 0 = unsupported shape (N < 0, Npix
+ * outside 1..16 384, max_n_in outside 0..32 768).
+ * Returns QFA_E_NULL for q == NULL; QFA_E_SIZE for N < 0, Npix outside 1..16 384, max_n_in outside 0..32 768, min_coverage not in
+ * (0, 1], a window that is empty (lo >= hi) or not finite, norm_min_pixels < 1; then N = 0 does nothing and returns 0; QFA_E_NULL
+ * for any other missing pointer (bad may be NULL; wave, flux, ivar may be NULL when max_n_in = 0); QFA_E_WORKSPACE.  Argument checks
+ * return before any device work.  The call neither synchronises nor allocates (graph-capturable). */
+typedef struct {
+    double min_coverage;        /* in (0, 1] */
+    double norm_lo, norm_hi;    /* rest-frame Angstrom, lo < hi */
+    double snr_lo, snr_hi;
+    int norm_min_pixels;        /* >= 1 */
+} qfa_preprocess_t;
+
+size_t qfa_preprocess_workspace_bytes(int N, int Npix, int max_n_in);
+int qfa_preprocess_f32(const double *wave, const float *flux, const float *ivar, const uint8_t *bad, const int64_t *offsets,
+                       const double *zqso, int N, int max_n_in, const double *out_edges, const double *wav_grid, int Npix,
+                       const qfa_preprocess_t *q, float *flux_out, float *error_out, double *record_f64,
+                       int32_t *record_i32, void *workspace, size_t workspace_bytes, void *stream);
+
 /* Replaces Adam.update(reference QFA/optimizer.py:37-52) followed by the clamp of QFA.clip
  * (QFA/model.py:233-241) for ONE tensor of n elements:
  *   g' = g + wd*p; m = (1-b1) g' + b1 m; v = (1-b2) g'^2 + b2 v;

@@ -19,6 +19,10 @@ _LAZY = {
     "VarianceStack": ("qfa_amd.model", "VarianceStack"),
     "Adam": ("qfa_amd.optimizer", "Adam"),
     "step_scheduler": ("qfa_amd.optimizer", "step_scheduler"),
+    # (the function has its module's name: once qfa_amd.preprocess is imported this attribute is the module, which is callable
+    #  and calls the function -- qfa_amd/preprocess.py, _CallableModule)
+    "preprocess": ("qfa_amd.preprocess", "preprocess"),
+    "Preprocessed": ("qfa_amd.preprocess", "Preprocessed"),
 }
 
 

@@ -27,6 +27,7 @@ EXPORTS = (
     "qfa_xi_stack_doubles", "qfa_xi_workspace_bytes", "qfa_xi_f32",
     "qfa_flux_pdf_stack_doubles", "qfa_flux_pdf_workspace_bytes", "qfa_flux_pdf_f32",
     "qfa_variance_stack_doubles", "qfa_variance_workspace_bytes", "qfa_variance_f32",
+    "qfa_preprocess_workspace_bytes", "qfa_preprocess_f32",
 )
 
 TAU_IDS = {"becker": 0, "fg": 1, "kamble": 2, "mock": 3}
@@ -92,6 +93,11 @@ class PDFParams(C.Structure):       # qfa_pdf_t
 
 class VarParams(C.Structure):       # qfa_var_t
     _fields_ = [("e_lo", C.c_int), ("n_oct", C.c_int), ("sub", C.c_int), ("d_max", C.c_float)]
+
+
+class PreprocessParams(C.Structure):   # qfa_preprocess_t
+    _fields_ = [("min_coverage", C.c_double), ("norm_lo", C.c_double), ("norm_hi", C.c_double), ("snr_lo", C.c_double),
+                ("snr_hi", C.c_double), ("norm_min_pixels", C.c_int)]
 
 
 _lib = None
@@ -176,6 +182,8 @@ def lib():
         "qfa_variance_stack_doubles": (sz, [i, i, i]),
         "qfa_variance_workspace_bytes": (sz, [i, i, i, i, i, i, i]),
         "qfa_variance_f32": (i, [p, p, C.POINTER(Batch), p, i, i, i, C.POINTER(P1DParams), C.POINTER(VarParams), C.c_uint, p, p, p, sz, p]),
+        "qfa_preprocess_workspace_bytes": (sz, [i, i, i]),
+        "qfa_preprocess_f32": (i, [p, p, p, p, p, p, i, i, p, p, i, C.POINTER(PreprocessParams), p, p, p, p, p, sz, p]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(h, name, None)

@@ -153,6 +153,61 @@ class DeviceDataloader(object):
                                                         num_mask, nprocs, output_dir, prefix)
         return cls(flux, error, zqso, wav_grid, batch_size, device, paths=plist, **kw)
 
+    @classmethod
+    def from_observed(cls, wave, flux, ivar, offsets, zqso, wav_grid, batch_size, device, bad=None, names=None,
+                      snr_min=-np.inf, snr_max=np.inf, z_min=-np.inf, z_max=np.inf, num_mask=np.inf, preprocess_kw=None, **kw):
+        """Observed-frame spectra (the ragged form of ``qfa_amd.preprocess.preprocess``: observed wavelength, flux, inverse
+        variance, pixel flags, z) to resident training storage without a host round trip: ``preprocess`` on the device,
+        ``Preprocessed.select`` (the reference's catalogue criteria, QFA/dataloader.py:49), and the constructor on the device
+        tensors.  ``names`` (N) become ``pathlist``; without them it holds the input row numbers.
+        Data parallel (``rank`` / ``world`` in ``kw``): every rank is handed the whole input and preprocesses the spectra
+        ``shard_bounds`` gives it; the selected counts are all-reduced, and since the selection of a shard need not have the size
+        of the loader's shard of the selected set, the rows a rank lacks -- spectra next to its shard -- are preprocessed in a
+        second, small call (a spectrum's result depends on that spectrum alone: the same bits on whichever rank)."""
+        from .preprocess import preprocess
+        pk = dict(preprocess_kw or {})
+        off = (offsets.detach().cpu().numpy() if isinstance(offsets, torch.Tensor) else np.asarray(offsets)).astype(np.int64)
+        n = len(off) - 1
+        names = np.asarray(names) if names is not None else np.arange(n)
+        crit = dict(snr_min=snr_min, snr_max=snr_max, z_min=z_min, z_max=z_max, num_mask=num_mask)
+
+        def run(rows_lo, rows_hi):
+            a, b = int(off[rows_lo]), int(off[rows_hi])
+            return preprocess(wave[a:b], flux[a:b], ivar[a:b], off[rows_lo:rows_hi + 1] - a, zqso[rows_lo:rows_hi], wav_grid,
+                              bad=None if bad is None else bad[a:b], device=device, **pk)
+
+        def rows_of(pre, idx):
+            idx_d = torch.as_tensor(idx, device=pre.flux.device)
+            return pre.flux[idx_d], pre.error[idx_d], pre.zqso[idx_d]
+
+        world, rank = int(kw.get("world", 1)), int(kw.get("rank", 0))
+        if world <= 1:
+            pre = run(0, n)
+            sel = pre.select(**crit)
+            f, e, zq = rows_of(pre, sel)
+            return cls(f, e, zq, wav_grid, batch_size, device, paths=names[sel], **kw)
+        from .distributed import all_reduce_, shard_bounds
+        lo, hi = shard_bounds(n, rank, world)
+        pre = run(lo, hi)
+        sel = pre.select(**crit)
+        keep = torch.zeros(n, dtype=torch.int32, device=torch.device(device))      # which input rows the ranks selected
+        keep[torch.as_tensor(sel + lo, device=keep.device)] = 1
+        all_reduce_(keep, kw.get("group"))
+        chosen = np.nonzero(keep.cpu().numpy())[0]                                  # the selected set, in input order
+        glo, ghi = shard_bounds(len(chosen), rank, world)
+        mine = chosen[glo:ghi]                                                      # this rank's rows of the selected set
+        have = (mine >= lo) & (mine < hi)
+        parts = [rows_of(pre, mine[have] - lo)]
+        before, after = mine[mine < lo], mine[mine >= hi]
+        for extra, first in ((before, True), (after, False)):
+            if len(extra):
+                p2 = run(int(extra[0]), int(extra[-1]) + 1)
+                part = rows_of(p2, extra - int(extra[0]))
+                parts = [part] + parts if first else parts + [part]
+        f, e, zq = (torch.cat([p[c] for p in parts]) for c in range(3))
+        kw.update(sharded_input=True, global_size=len(chosen))
+        return cls(f, e, zq, wav_grid, batch_size, device, paths=names[mine], **kw)
+
     # ------------------------------------------------------------------ mu
     def _estimate_mu(self, window):
         """reference QFA/dataloader.py:109-111; under data parallelism the per-pixel sums of the shards are

@@ -48,6 +48,37 @@ def read_spectra(paths, nprocs=1):
     return flux, error, zqso, np.array([d[3] for d in data])
 
 
+def read_observed_spectrum(path):
+    """wave, flux, ivar, bad, z of one observed-frame file: keys ``wave`` (Angstrom) or ``loglam`` (log10 Angstrom, the SDSS
+    column), ``flux``, ``ivar``, optional ``and_mask`` (non-zero = a flagged pixel), ``z``"""
+    with np.load(path) as f:
+        wave = np.asarray(f["wave"], dtype=np.float64) if "wave" in f.files else 10.0 ** np.asarray(f["loglam"], dtype=np.float64)
+        flux, ivar = np.asarray(f["flux"], dtype=np.float32), np.asarray(f["ivar"], dtype=np.float32)
+        bad = (np.asarray(f["and_mask"]) != 0) if "and_mask" in f.files else np.zeros(len(wave), dtype=bool)
+        z = float(f["z"])
+    if not (wave.ndim == 1 and wave.shape == flux.shape == ivar.shape == bad.shape):
+        raise ValueError(f"{path}: wave / flux / ivar / and_mask must be 1-d arrays of one length")
+    return wave, flux, ivar, bad.view(np.uint8), z
+
+
+def read_observed_npz(paths, nprocs=1):
+    """Observed-frame spectra as ``qfa_amd.preprocess.preprocess`` takes them: the ragged, concatenated form
+    (wave f64, flux f32, ivar f32, bad u8, offsets i64 (N + 1), zqso f64 (N)) of the per-spectrum files, in the order of ``paths``.
+    (No FITS reader: the survey's tables are converted to .npz by whoever has astropy.)"""
+    paths = list(paths)
+    if not paths:
+        raise ValueError("no spectrum files given")
+    if nprocs and nprocs > 1:
+        with ThreadPoolExecutor(max_workers=int(nprocs)) as ex:
+            data = list(ex.map(read_observed_spectrum, paths))
+    else:
+        data = [read_observed_spectrum(p) for p in paths]
+    offsets = np.concatenate([[0], np.cumsum([len(d[0]) for d in data])]).astype(np.int64)
+    cat = lambda i, dt: np.concatenate([d[i] for d in data]).astype(dt, copy=False)
+    return cat(0, np.float64), cat(1, np.float32), cat(2, np.float32), cat(3, np.uint8), offsets, \
+        np.array([d[4] for d in data], dtype=np.float64)
+
+
 def select_from_catalog(catalog, num, snr_min, snr_max, z_min, z_max, num_mask, output_dir=None, prefix="train"):
     """File names drawn from a catalogue csv with columns file, snr, z, num_mask
     (reference QFA/dataloader.py:48-55): the rows inside the S/N, redshift and masked-pixel limits,
