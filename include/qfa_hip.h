@@ -662,6 +662,56 @@ int qfa_preprocess_f32(const double *wave, const float *flux, const float *ivar,
                        const qfa_preprocess_t *q, float *flux_out, float *error_out, double *record_f64,
                        int32_t *record_i32, void *workspace, size_t workspace_bytes, void *stream);
 
+/* The sightline bootstrap of the segment statistics (additive to ABI v4).  The five calls above take their error bars from the scatter
+ * of segments, but the segments of one quasar share a continuum, a noise model and a large-scale mode, and nothing but the band stack
+ * gives a covariance between modes, lags, flux bins or z-bins.  The published measurements resample quasars.  These calls do that on
+ * the per-segment rows the statistics already write (power, pairs, hist, bandpower, moments): R Poisson-bootstrap replicates of the
+ * sums of the rows per draw and z-bin, from which qfa_amd.stacks.BootstrapStack forms the estimates and their covariance.
+ *
+ * qfa_segment_codes_f32 writes codes (B S, nseg) int32: entry (b S + s, g) is the z-bin kz of segment g of draw s of spectrum b when
+ * the segment is valid and 0 <= kz < nz, else -1.  trans, ivar, b, tbar, B, S, Nb and p are qfa_p1d_f32's, bit for bit: `used` of a
+ * pixel, n_used, validity (n_used >= min_used) and the z-bin (at the central pixel p_lo + g L + L / 2) are those of that call -- the
+ * same device functions -- with its rules on the redshift forms and on NaN under the mask.  Returns every code of qfa_p1d_f32 for the
+ * arguments they share (QFA_E_NULL also for codes, QFA_E_SIZE also for B S nseg above 2^31 - 1); checks return before any device work; B = 0 does nothing.
+ *
+ * The weight (the contract every port must reproduce).  Replicate r (0 <= r < R) gives the spectrum of global row g = row_offset + b
+ * (int64) the weight w(seed, g, r) ~ Poisson(1), the same for all its segments and draws:
+ *   generator  Philox4x32-10 as above, key = (seed & 0xffffffff, seed >> 32),
+ *              counter = (0x40000000 | (r >> 2), 0, g & 0xffffffff, g >> 32) -> words x0..x3.  Bit 30 is set and bit 31 clear: disjoint
+ *              from the latent stream (first word 0..7) and the mock stream (bit 31 set) under one seed;
+ *   word       u = x[r & 3]: four consecutive replicates share one Philox call;
+ *   weight     w = the number of thresholds T_k <= u, T_k = floor(2^32 sum_{i <= k} e^-1 / i!), k = 0 .. 12:
+ *              0x5e2d58d8 0xbc5ab1b1 0xeb715e1d 0xfb239797 0xff1025f5 0xffd90f3b 0xfffa8b71 0xffff540c 0xffffed1f 0xfffffe21
+ *              0xffffffd4 0xfffffffc 0xffffffff  (w <= 13).  Integer arithmetic only: identical on every device and in numpy.
+ * The weight depends on (seed, g, r) alone -- not on the cut of a data set into calls, on the draw s, on R or on the rank.
+ *
+ * qfa_bootstrap_f64.  rows (B S, nseg, W) of row_type QFA_ROW_F32 / QFA_ROW_F64 / QFA_ROW_I32 -- row (b S + s, g) is segment g of draw s
+ * of spectrum b, as the statistics write them; codes (B S, nseg) as qfa_segment_codes_f32 writes them (any value outside 0 .. nz - 1
+ * puts the segment in no bin: its row is never read, NaN or inf in it reach nothing).
+ *   output     boot (S, R, nz, 1 + W) float64 = [sum w | sum w x_0 .. x_{W-1}] over the segments of draw s with code kz.  The call ADDS
+ *              to `boot`; QFA_F_ZERO_ACCUM overwrites instead;
+ *   sums       x is converted to float64 (exact) and every term enters as fma(w, x, sum): w x is never rounded on its own (for
+ *              float32 and int32 rows it is exact anyway, w <= 13), so the only roundings are those of the float64 additions --
+ *              n_terms 2^-52 sum w |x| bounds the distance to the sum in any order.  Every element of boot is ONE chain of additions in order of (b, g) that starts from what `boot` holds
+ *              (qfa_p1d_f32's rule: chunks of one segment): no atomics, two runs give the same bits, and calls on consecutive
+ *              pieces of a batch -- the later ones adding, row_offset advanced -- give the bits of one call.  Replicate r does not
+ *              depend on R, draw s not on S.  Sums over pieces added in another order (ranks, an all-reduce) differ by the rounding
+ *              of float64 sums; int32 rows give integers, exact below 2^53 in any order.
+ * qfa_bootstrap_workspace_bytes(n_spectra = B, ...): 0 = unsupported shape (B < 0, S < 1, nseg < 1, W or nz outside 1..4096, R outside
+ * 1..65 536, B S nseg or S nz ceil((1 + W) / 4) above 2^31 - 1).  Nothing is held between kernels: the size of a supported shape is a
+ * token 16 bytes.
+ * Returns QFA_E_NULL for boot or ws missing; QFA_E_SIZE for an unsupported shape, row_offset < 0 or an unknown row_type; QFA_E_FLAGS
+ * for any flag other than QFA_F_ZERO_ACCUM, QFA_F_SYNC; QFA_E_WORKSPACE; then QFA_E_NULL for rows or codes missing when B > 0.  B = 0
+ * does nothing, except zeroing `boot` under QFA_F_ZERO_ACCUM.  Argument checks return before any device work.  Neither call
+ * synchronises or allocates (graph-capturable). */
+enum { QFA_ROW_F32 = 0, QFA_ROW_F64 = 1, QFA_ROW_I32 = 2 };
+
+int qfa_segment_codes_f32(const float *trans, const float *ivar, const qfa_batch_t *b, const float *tbar, int B, int S, int Nb,
+                          const qfa_p1d_t *p, int32_t *codes, void *stream);
+size_t qfa_bootstrap_workspace_bytes(int n_spectra, int S, int nseg, int W, int nz, int R);
+int qfa_bootstrap_f64(const void *rows, int row_type, const int32_t *codes, int B, int S, int nseg, int W, int nz, int R, uint64_t seed,
+                      int64_t row_offset, unsigned flags, double *boot, void *ws, size_t ws_bytes, void *stream);
+
 /* Replaces Adam.update(reference QFA/optimizer.py:37-52) followed by the clamp of QFA.clip
  * (QFA/model.py:233-241) for ONE tensor of n elements:
  *   g' = g + wd*p; m = (1-b1) g' + b1 m; v = (1-b2) g'^2 + b2 v;

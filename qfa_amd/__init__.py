@@ -17,6 +17,7 @@ _LAZY = {
     "XiStack": ("qfa_amd.model", "XiStack"),
     "PDFStack": ("qfa_amd.model", "PDFStack"),
     "VarianceStack": ("qfa_amd.model", "VarianceStack"),
+    "BootstrapStack": ("qfa_amd.model", "BootstrapStack"),
     "Adam": ("qfa_amd.optimizer", "Adam"),
     "step_scheduler": ("qfa_amd.optimizer", "step_scheduler"),
     # (the function has its module's name: once qfa_amd.preprocess is imported this attribute is the module, which is callable

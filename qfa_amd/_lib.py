@@ -28,6 +28,7 @@ EXPORTS = (
     "qfa_flux_pdf_stack_doubles", "qfa_flux_pdf_workspace_bytes", "qfa_flux_pdf_f32",
     "qfa_variance_stack_doubles", "qfa_variance_workspace_bytes", "qfa_variance_f32",
     "qfa_preprocess_workspace_bytes", "qfa_preprocess_f32",
+    "qfa_segment_codes_f32", "qfa_bootstrap_workspace_bytes", "qfa_bootstrap_f64",
 )
 
 TAU_IDS = {"becker": 0, "fg": 1, "kamble": 2, "mock": 3}
@@ -40,6 +41,7 @@ F_FOREST_UNIT_W = 0x200    # qfa_forest_f32: stack with w = 1 instead of w = iva
 F_XI_UNIT_W = 0x400        # qfa_xi_f32: w = 1 on a used pixel instead of 1 / (v + sigma2_lss)
 F_PDF_RELATIVE = 0x800     # qfa_flux_pdf_f32: bin x = T / tbar(z) instead of x = T
 F_PDF_CLAMP = 0x1000       # qfa_flux_pdf_f32: x outside the range counts in the first / last bin
+ROW_TYPES = {"float32": 0, "float64": 1, "int32": 2}    # qfa_bootstrap_f64: QFA_ROW_* by the name of the rows' dtype
 F_EXACT_GRAD = 0x100       # exact gradients of mean NLL (opt-in; QFA.exact_gradients); the buffer carries the mode in slot 6
 
 
@@ -184,6 +186,9 @@ def lib():
         "qfa_variance_f32": (i, [p, p, C.POINTER(Batch), p, i, i, i, C.POINTER(P1DParams), C.POINTER(VarParams), C.c_uint, p, p, p, sz, p]),
         "qfa_preprocess_workspace_bytes": (sz, [i, i, i]),
         "qfa_preprocess_f32": (i, [p, p, p, p, p, p, i, i, p, p, i, C.POINTER(PreprocessParams), p, p, p, p, p, sz, p]),
+        "qfa_segment_codes_f32": (i, [p, p, C.POINTER(Batch), p, i, i, i, C.POINTER(P1DParams), p, p]),
+        "qfa_bootstrap_workspace_bytes": (sz, [i, i, i, i, i, i]),
+        "qfa_bootstrap_f64": (i, [p, i, p, i, i, i, i, i, i, C.c_uint64, i64, C.c_uint, p, p, sz, p]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(h, name, None)

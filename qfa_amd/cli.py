@@ -136,6 +136,8 @@ def main(argv=None):
             raise ValueError("MODEL.VAR_DMAX must be finite and >= 0 (0 = no cut)")
         if int(M.VAR_MIN_COUNT) < 1:
             raise ValueError("MODEL.VAR_MIN_COUNT must be >= 1")
+    if cfg.TYPE == "predict" and not 0 <= int(M.BOOT_N) <= 65536:
+        raise ValueError("MODEL.BOOT_N must lie in 0 .. 65536 (0 = off)")
     os.makedirs(cfg.DATA.OUTPUT_DIR, exist_ok=True)
     with open(os.path.join(cfg.DATA.OUTPUT_DIR, "config.yaml"), "w") as f:
         f.write(cfg.dump())
@@ -186,21 +188,27 @@ def main(argv=None):
             # unused, and a segment that loses too many of them to the edges is left out (P1D_MIN_USED_FRAC)
             shared = dict(n_segments=int(M.P1D_SEGMENTS), min_used_frac=float(M.P1D_MIN_USED_FRAC), tbar=st, **draws)
             done = []                                           # (flux_power's stack first: the bands lie on its segments and dv)
-            # (config switch, loader method, its own keywords, arrays()'s keywords, file): one row per statistic
-            for switch, method, own, export, name in (
-                    (M.P1D_SEGMENTS, model.flux_power, dict, {}, "flux_power.npz"),
-                    (M.P1D_NBANDS, model.band_power,
+            # (config switch, loader method, its name in QFA.bootstrap, its own keywords, arrays()'s keywords, file): one row per statistic
+            for switch, method, boot, own, export, name in (
+                    (M.P1D_SEGMENTS, model.flux_power, "p1d", dict, {}, "flux_power.npz"),
+                    (M.P1D_NBANDS, model.band_power, "bands",
                      lambda: dict(k_edges=P1DBandStack.linear_k_edges(done[0].L, done[0].dv, int(M.P1D_NBANDS))), {}, "flux_power_bands.npz"),
-                    (M.XI_NLAGS, model.flux_correlation, lambda: dict(n_lags=int(M.XI_NLAGS), sigma2_lss=float(M.XI_SIGMA2_LSS)), {},
+                    (M.XI_NLAGS, model.flux_correlation, "xi", lambda: dict(n_lags=int(M.XI_NLAGS), sigma2_lss=float(M.XI_SIGMA2_LSS)), {},
                      "flux_correlation.npz"),
-                    (M.PDF_NBINS, model.flux_pdf,
+                    (M.PDF_NBINS, model.flux_pdf, "pdf",
                      lambda: dict(n_tbins=int(M.PDF_NBINS), t_min=float(M.PDF_TMIN), t_max=float(M.PDF_TMAX), relative=bool(M.PDF_RELATIVE),
                                   clamp=bool(M.PDF_CLAMP), ivar_min=float(M.PDF_IVAR_MIN)), {}, "flux_pdf.npz"),
-                    (M.VAR_NOCT, model.variance_function,
+                    (M.VAR_NOCT, model.variance_function, "variance",
                      lambda: dict(e_lo=int(M.VAR_ELO), n_oct=int(M.VAR_NOCT), sub=int(M.VAR_SUB),
                                   d_max=float(M.VAR_DMAX) if float(M.VAR_DMAX) > 0.0 else None),
                      dict(min_count=int(M.VAR_MIN_COUNT)), "variance_function.npz")):
-                if int(switch) > 0:
+                if int(switch) > 0 and int(M.BOOT_N) > 0:
+                    stack, bt = model.bootstrap(dataloader, boot, float(M.FOREST_ZMIN), float(M.FOREST_ZMAX), int(M.P1D_NZBINS),
+                                                int(M.BOOT_N), boot_seed=int(M.BOOT_SEED), **own(), **shared)
+                    done.append(stack)
+                    save(name, stack, **export)
+                    save(name[:-4] + "_bootstrap.npz", bt)
+                elif int(switch) > 0:
                     done.append(method(dataloader, float(M.FOREST_ZMIN), float(M.FOREST_ZMAX), int(M.P1D_NZBINS), **own(), **shared))
                     save(name, done[-1], **export)
         print(f"Finish predicting {len(dataloader)} spectra in {time.time() - ts} seconds...")

@@ -81,7 +81,11 @@ DEFAULTS = {                                        # reference QFA/config.py:15
               # of the same segments in VAR_NOCT octaves of the pipeline's noise variance from 2^VAR_ELO on, 2^VAR_SUB bins per octave
               # (at most 64 bins), per z-bin, and the fit var = eta v + sigma2_lss on the bins of at least VAR_MIN_COUNT pixels;
               # VAR_DMAX > 0 leaves out pixels with |delta_F| above it (QFA.variance_function)
-              "VAR_NOCT": 0, "VAR_ELO": -12, "VAR_SUB": 1, "VAR_DMAX": 0.0, "VAR_MIN_COUNT": 100},
+              "VAR_NOCT": 0, "VAR_ELO": -12, "VAR_SUB": 1, "VAR_DMAX": 0.0, "VAR_MIN_COUNT": 100,
+              # not in the reference: BOOT_N > 0 makes every segment statistic predict mode writes (flux_power, flux_power_bands,
+              # flux_correlation, flux_pdf, variance_function) also write <its file stem>_bootstrap.npz: its estimate in BOOT_N Poisson
+              # bootstrap replicates over quasars and their covariance matrix per z-bin; BOOT_SEED seeds the weights (QFA.bootstrap)
+              "BOOT_N": 0, "BOOT_SEED": 0},
     "TRAIN": {"NEPOCHS": 500, "LEARNING_RATE": 1e-3, "WEIGHT_DECAY": 1e-1, "DECAY_ALPHA": 0.9, "DECAY_STEP": 10,
               "WINDOW_LENGTH_FOR_MU": 16,
               # not in the reference: "em" = F by its closed-form EM update, Adam for the other parameters (QFA.train
@@ -105,7 +109,7 @@ EXTRA_KEYS = ("MODEL.REFERENCE_C0_QUIRK", "MODEL.N_SAMPLES", "MODEL.SAMPLE_SEED"
               "MODEL.FOREST", "MODEL.FOREST_ZMIN", "MODEL.FOREST_ZMAX", "MODEL.FOREST_NBINS", "MODEL.P1D_SEGMENTS",
               "MODEL.P1D_NZBINS", "MODEL.P1D_MIN_USED_FRAC", "MODEL.P1D_NBANDS", "MODEL.XI_NLAGS", "MODEL.XI_SIGMA2_LSS", "MODEL.PDF_NBINS",
               "MODEL.PDF_TMIN", "MODEL.PDF_TMAX", "MODEL.PDF_CLAMP", "MODEL.PDF_RELATIVE", "MODEL.PDF_IVAR_MIN", "MODEL.VAR_NOCT", "MODEL.VAR_ELO",
-              "MODEL.VAR_SUB", "MODEL.VAR_DMAX", "MODEL.VAR_MIN_COUNT", "TRAIN.F_UPDATE", "TRAIN.EM_RHO", "TRAIN.EM_RIDGE")
+              "MODEL.VAR_SUB", "MODEL.VAR_DMAX", "MODEL.VAR_MIN_COUNT", "MODEL.BOOT_N", "MODEL.BOOT_SEED", "TRAIN.F_UPDATE", "TRAIN.EM_RHO", "TRAIN.EM_RIDGE")
 
 
 def _set(cfg, dotted, value):

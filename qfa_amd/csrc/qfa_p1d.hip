@@ -4,13 +4,15 @@
 // launch plans and the launches; and of the pair-weighted correlation function of the same segments and its (lag, z) stack
 // (qfa_xi_stack_doubles, qfa_xi_workspace_bytes, qfa_xi_f32); and of the flux PDF of the same segments and its covariance stack
 // (qfa_flux_pdf_stack_doubles, qfa_flux_pdf_workspace_bytes, qfa_flux_pdf_f32); and of the variance function of the same segments
-// and its (v-bin, z) stack (qfa_variance_stack_doubles, qfa_variance_workspace_bytes, qfa_variance_f32).  Kernels in qfa_p1d.h,
-// qfa_p1d_band.h, qfa_xi.h, qfa_pdf.h and qfa_variance.h.
+// and its (v-bin, z) stack (qfa_variance_stack_doubles, qfa_variance_workspace_bytes, qfa_variance_f32); and of the z-bin codes of
+// the same segments (qfa_segment_codes_f32, what the sightline bootstrap of qfa_bootstrap.hip sorts its rows by).  Kernels in qfa_p1d.h,
+// qfa_p1d_band.h, qfa_xi.h, qfa_pdf.h, qfa_variance.h and qfa_bootstrap.h.
 #include "qfa_p1d.h"
 #include "qfa_p1d_band.h"
 #include "qfa_xi.h"
 #include "qfa_pdf.h"
 #include "qfa_variance.h"
+#include "qfa_bootstrap.h"
 #include "../../include/qfa_hip.h"
 
 #include <math.h>
@@ -461,6 +463,24 @@ int qfa_variance_f32(const float *trans, const float *ivar, const qfa_batch_t *b
         vf::k_var_stack<<<(unsigned)((size_t)chunks * S), vf::kThreads, 0, st>>>(sa);
         chunk_reduce(part, chunks, S, nz, 2 + 5 * nv, 0, zero, stack, st);
     });
+}
+
+int qfa_segment_codes_f32(const float *trans, const float *ivar, const qfa_batch_t *b, const float *tbar, int B, int S, int Nb,
+                          const qfa_p1d_t *p, int32_t *codes, void *stream) {
+    namespace bt = qfa_bootstrap;
+    if (!trans || !ivar || !b || !tbar || !p || !codes) return QFA_E_NULL;
+    bool fac;
+    if (int e = check_call(b, B, S, Nb, p, fac)) return e;
+    if ((int64_t)B * S * p->nseg > INT32_MAX) return QFA_E_SIZE;
+    if (B == 0) return 0;
+    bt::CodeArgs a;
+    seg_args(a, trans, ivar, b, tbar, S, Nb, p, fac);
+    a.Bc = B;
+    a.codes = codes;
+    const size_t segs = (size_t)B * S * p->nseg;
+    constexpr size_t per = bt::kCodeThreads / 64;
+    bt::k_segment_codes<<<(unsigned)((segs + per - 1) / per), bt::kCodeThreads, 0, (hipStream_t)stream>>>(a);
+    return (int)hipGetLastError();
 }
 
 }  // extern "C"

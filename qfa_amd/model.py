@@ -42,7 +42,7 @@ import torch
 
 from . import _lib
 from . import utils as _utils
-from .stacks import EMStats, ForestStack, P1DBandStack, P1DStack, PDFStack, VarianceStack, XiStack    # (re-exported)
+from .stacks import BootstrapStack, EMStats, ForestStack, P1DBandStack, P1DStack, PDFStack, VarianceStack, XiStack    # (re-exported)
 from .statistics import ForestStatistics
 
 f32 = torch.float32

@@ -1,5 +1,5 @@
-"""The result classes of ``QFA``: ``EMStats`` and the six stacks of the forest statistics, ``ForestStack``, ``P1DStack``,
-``P1DBandStack``, ``XiStack``, ``PDFStack`` and ``VarianceStack``.  Views and arithmetic on buffers the kernels filled (include/qfa_hip.h): nothing here calls the library or
+"""The result classes of ``QFA``: ``EMStats``, the six stacks of the forest statistics, ``ForestStack``, ``P1DStack``,
+``P1DBandStack``, ``XiStack``, ``PDFStack`` and ``VarianceStack``, and ``BootstrapStack``, the sightline bootstrap of the segment ones.  Views and arithmetic on buffers the kernels filled (include/qfa_hip.h): nothing here calls the library or
 needs a GPU, the classes work on CPU tensors as well.  ``qfa_amd.model`` re-exports the names."""
 from __future__ import annotations
 
@@ -295,6 +295,11 @@ class P1DStack(_SegmentStack):
         return self._export(k=self.k, z_centers=self.z_centers, z_edges=self.z_edges, power=self.power(), err=self.err(),
                             power_raw=self.power_raw, noise=self.noise, n=self.n, seg_len=self.L, dv=self.dv, sums=self.buf)
 
+    @staticmethod
+    def bootstrap_estimate(sums, dv=1.0):
+        """``power()`` of bootstrap sums (..., 2 + M) = [sum w | sum w N | sum w P_1..M] of the rows [noise | power]: (..., M)"""
+        return (sums[..., 2:] - sums[..., 1:2]) / sums[..., 0:1] * float(dv)
+
 
 class P1DBandStack(_SegmentStack):
     """The stack of band powers of the 1D flux power spectrum and of their outer products (include/qfa_hip.h, qfa_p1d_band_f32):
@@ -388,6 +393,11 @@ class P1DBandStack(_SegmentStack):
         return self._export(k_edges=self.k_edges, k_centers=self.k_centers, z_edges=self.z_edges, n=self.n, mean=self.mean, cov=self.cov,
                             **over)
 
+    @staticmethod
+    def bootstrap_estimate(sums):
+        """``mean`` of bootstrap sums (..., 1 + nband) = [sum w | sum w Q_a] of the rows bandpower: (..., nband)"""
+        return sums[..., 1:] / sums[..., 0:1]
+
 
 class XiStack(_SegmentStack):
     """The (lag, z) stack of the pair-weighted line-of-sight correlation function (include/qfa_hip.h, qfa_xi_f32): ``buf`` =
@@ -469,6 +479,17 @@ class XiStack(_SegmentStack):
         return self._export(lags_kms=self.lags_kms, z_centers=self.z_centers, z_edges=self.z_edges, xi=self.xi(),
                             xi_raw=self.xi(subtract_noise=False), err=self.err(), n=self.n, sum_w=self.sum_w, seg_len=self.L, dv=self.dv,
                             sums=self.buf)
+
+    @staticmethod
+    def bootstrap_estimate(sums, nlag, subtract_noise=True):
+        """``xi()`` of bootstrap sums (..., 2 + 2 nlag) = [sum w | sum w N0 | sum w W_l | sum w A_l] of the rows [noise0 | pairs]:
+        (..., nlag), NaN where sum w W_l = 0"""
+        W, A = sums[..., 2:2 + nlag], sums[..., 2 + nlag:2 + 2 * nlag]
+        if subtract_noise:
+            A = A.clone()
+            A[..., 0] -= sums[..., 1]
+        x = A / W
+        return torch.where(W != 0.0, x, torch.full_like(x, float("nan")))
 
 
 class PDFStack(_DrawStack):
@@ -614,6 +635,14 @@ class PDFStack(_DrawStack):
         over = {"std_over_draws": self.std_over_draws, "total_cov": self.total_cov} if self.S > 1 else {}
         return self._export(z=self.z_centers, t_edges=self.t_edges, pdf=self.pdf(), err=self.err(), cov=self.cov(), counts=self.counts,
                             n_segments=self.n_segments, out_of_range=self.out_of_range(), **over)
+
+    @staticmethod
+    def bootstrap_estimate(sums, dt):
+        """``pdf()`` of bootstrap sums (..., 1 + nt) = [sum w | sum w h_a] of the rows hist: (..., nt), NaN without pixels"""
+        H = sums[..., 1:]
+        N = H.sum(-1, keepdim=True)
+        p = H / (N * float(dt))
+        return torch.where(N > 0.0, p, torch.full_like(p, float("nan")))
 
 
 # what ``VarianceStack.fit`` returns: (S, nz) tensors, ``cov`` (S, nz, P, P) in the order (eta, sigma2_lss[, eps]); ``eps`` None
@@ -768,6 +797,14 @@ class VarianceStack(_SegmentStack):
         chi2 = torch.where(good, chi2, nan)
         return VarianceFit(par[..., 0], par[..., 1], par[..., 2] if epsilon else None, cov, chi2, n_bins - P, n_bins)
 
+    @staticmethod
+    def bootstrap_estimate(sums, nv):
+        """``var_delta`` of bootstrap sums (..., 1 + 5 nv) = [sum w | sum w (n_a | sum v | sum d | sum d^2 | sum d^4)] of the rows
+        moments: (..., nv)"""
+        n = sums[..., 1:1 + nv]
+        m = sums[..., 1 + 2 * nv:1 + 3 * nv] / n
+        return sums[..., 1 + 3 * nv:1 + 4 * nv] / n - m * m
+
     def _per_draw(self):
         return self.var_delta
 
@@ -787,3 +824,88 @@ class VarianceStack(_SegmentStack):
                             var_err=self.var_err, mean_delta=self.mean_delta, counts=self.counts, n_segments=self.n_segments,
                             n_pixels=self.n_pixels, out_of_range=self.out_of_range(), seg_len=self.L, sums=self.buf, eta=ft.eta,
                             sigma2_lss=ft.sigma2_lss, cov=ft.cov, chi2=ft.chi2, ndof=ft.ndof, n_bins=ft.n_bins, **over)
+
+
+class BootstrapStack(object):
+    """The sightline bootstrap of a segment statistic (include/qfa_hip.h, qfa_bootstrap_f64): ``buf`` = (S, R, nz, 1 + W) float64
+    [sum w | sum w x_0 .. x_{W-1}] per draw of the continuum, bootstrap replicate and z-bin, over the per-segment rows x of the
+    statistic; w ~ Poisson(1) is drawn per (``seed``, global row of the spectrum, replicate), one weight for all the segments of a
+    quasar.  Sums only, which is what data parallelism all-reduces.  ``estimate``: the map from sums (..., 1 + W) to the statistic
+    (..., n) -- a stack class's ``bootstrap_estimate`` --, None = the weighted mean of the rows.  ``bins`` = (z0, dz, nz) as the
+    kernels binned (None when the caller made the codes itself)."""
+
+    def __init__(self, buf, seed=0, bins=None, estimate=None):
+        if buf.dtype != torch.float64 or buf.dim() != 4 or min(buf.shape) < 1 or buf.shape[3] < 2 or not buf.is_contiguous():
+            raise QFAHipError(f"BootstrapStack: buffer {tuple(buf.shape)} {buf.dtype}, expected contiguous float64 (S, R, nz, 1 + W)")
+        if bins is not None:
+            bins = _DrawStack._round_bins(*bins)
+            if bins[2] != buf.shape[2]:
+                raise QFAHipError(f"BootstrapStack: {bins[2]} z-bins, the buffer has {buf.shape[2]}")
+        self.buf, self.seed, self.bins, self.estimate = buf, int(seed), bins, estimate
+
+    @classmethod
+    def zeros(cls, S, n_boot, nz, W, seed=0, bins=None, estimate=None, device="cpu"):
+        return cls(torch.zeros((int(S), int(n_boot), int(nz), 1 + int(W)), dtype=torch.float64, device=device), seed, bins, estimate)
+
+    S = property(lambda self: int(self.buf.shape[0]))
+    R = property(lambda self: int(self.buf.shape[1]))
+    nz = property(lambda self: int(self.buf.shape[2]))
+    W = property(lambda self: int(self.buf.shape[3]) - 1)
+
+    def _like(self, buf):
+        return BootstrapStack(buf, self.seed, self.bins, self.estimate)
+
+    def draws(self, s0, s1):
+        """the stack of draws [s0, s1): a view of the same buffer"""
+        return self._like(self.buf[s0:s1])
+
+    def clone(self):
+        return self._like(self.buf.clone())
+
+    def all_reduce(self, group=None):
+        """in-place sum over the process group (every rank calls it; an exhausted rank adds zeros)"""
+        from .distributed import all_reduce_accum
+        all_reduce_accum(self.buf.view(-1), group)
+        return self
+
+    @property
+    def n(self):
+        """(S, R, nz) the weighted number of segments of a replicate, sum w"""
+        return self.buf[..., 0]
+
+    @property
+    def mean_rows(self):
+        """(S, R, nz, W) the weighted mean of the rows, sum w x / sum w (NaN in an empty bin)"""
+        return self.buf[..., 1:] / self.buf[..., 0:1]
+
+    def estimates(self, fn=None):
+        """(S, R, nz, n) the statistic of every replicate: ``fn`` (default ``estimate``, else ``mean_rows``) of the sums"""
+        fn = fn if fn is not None else self.estimate
+        return self.mean_rows if fn is None else fn(self.buf)
+
+    def cov(self, across_z=False, fn=None):
+        """the covariance over the R replicates of ``estimates(fn)``: (S, nz, n, n), or (S, nz n, nz n) with ``across_z`` -- the
+        z-bins share quasars, which this carries.  NaN below two replicates"""
+        e = self.estimates(fn)
+        if across_z:
+            e = e.reshape(self.S, self.R, 1, -1)
+        d = e - e.mean(1, keepdim=True)
+        c = torch.einsum("srza,srzb->szab", d, d) / (self.R - 1.0) if self.R > 1 else \
+            torch.full((self.S, e.shape[2], e.shape[3], e.shape[3]), float("nan"), dtype=torch.float64, device=self.buf.device)
+        return c[:, 0] if across_z else c
+
+    def err(self, fn=None):
+        """(S, nz, n) the bootstrap standard error of the statistic: the root of the diagonal of ``cov``"""
+        return torch.sqrt(torch.diagonal(self.cov(fn=fn), dim1=2, dim2=3))
+
+    def corr(self, across_z=False, fn=None):
+        """the correlation matrix of ``cov``: cov_ab / sqrt(cov_aa cov_bb)"""
+        c = self.cov(across_z, fn)
+        d = torch.sqrt(torch.diagonal(c, dim1=-2, dim2=-1))
+        return c / (d[..., :, None] * d[..., None, :])
+
+    def arrays(self):
+        """what <statistic>_bootstrap.npz holds"""
+        z = {} if self.bins is None else {"z_edges": self.bins[0] + self.bins[1] * np.arange(self.nz + 1, dtype=np.float64)}
+        named = dict(estimates=self.estimates(), cov=self.cov(), err=self.err(), n=self.n, n_boot=self.R, seed=self.seed, sums=self.buf, **z)
+        return {k: v.cpu().numpy() if isinstance(v, torch.Tensor) else v for k, v in named.items()}

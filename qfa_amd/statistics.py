@@ -1,20 +1,23 @@
 """The forest statistics of ``QFA``: transmission and its redshift-binned stack (``forest`` / ``mean_transmission``), the 1D flux
 power spectrum (``p1d`` / ``flux_power``), its band powers (``p1d_bands`` / ``band_power``), the line-of-sight correlation function
 (``xi`` / ``flux_correlation``), the flux PDF (``flux_pdf_segments`` / ``flux_pdf``) and the variance function
-(``variance_segments`` / ``variance_function``).  ``ForestStatistics`` is a plain
+(``variance_segments`` / ``variance_function``), and the sightline bootstrap of the segment statistics (``segment_codes``,
+``segment_bootstrap`` / ``bootstrap``).  ``ForestStatistics`` is a plain
 base class of ``qfa_amd.model.QFA`` and uses the model's plumbing (``_batch_struct*``, ``_scratch``, ``predict``, ``sample_latent``,
 ``_loader_slices``) as any other method of it does; every call goes through the C-ABI in ``include/qfa_hip.h``."""
 from __future__ import annotations
 
 import collections
 import ctypes as C
+import functools
+import types
 
 import numpy as np
 import torch
 
 from . import _lib
 from ._lib import QFAHipError, _ptr
-from .stacks import ForestStack, P1DBandStack, P1DStack, PDFStack, VarianceStack, XiStack, _band_map, _check_segments, _edges, _mode_k, _window2
+from .stacks import BootstrapStack, ForestStack, P1DBandStack, P1DStack, PDFStack, VarianceStack, XiStack, _band_map, _check_segments, _edges, _mode_k, _window2
 
 f32 = torch.float32
 
@@ -22,6 +25,19 @@ f32 = torch.float32
 # statistic's parameters, before the first slice --, ``call`` is its method of a slice with its own ``keywords``, ``needs_dv`` False: dv
 # matters only where <T> is made in the loop's own `mean_transmission`
 _LoaderStat = collections.namedtuple("_LoaderStat", "zeros call keywords needs_dv", defaults=(True,))
+
+# what `bootstrap` needs to know of a statistic: its loader method, the (B, S, nseg, W) rows of its slice call's outputs, and
+# (W, the stack class's map from bootstrap sums to the estimate) of its stack
+_BOOT_STATS = {
+    "p1d": ("flux_power", lambda o: torch.cat([o[1].unsqueeze(-1), o[0]], -1),
+            lambda st: (1 + st.M, functools.partial(P1DStack.bootstrap_estimate, dv=st.dv))),
+    "bands": ("band_power", lambda o: o[0], lambda st: (st.nband, P1DBandStack.bootstrap_estimate)),
+    "xi": ("flux_correlation", lambda o: torch.cat([o[1].unsqueeze(-1), o[0].flatten(3)], -1),
+           lambda st: (1 + 2 * st.nlag, functools.partial(XiStack.bootstrap_estimate, nlag=st.nlag))),
+    "pdf": ("flux_pdf", lambda o: o[0], lambda st: (st.nt, functools.partial(PDFStack.bootstrap_estimate, dt=st.dt))),
+    "variance": ("variance_function", lambda o: o[0].flatten(3),
+                 lambda st: (5 * st.nv, functools.partial(VarianceStack.bootstrap_estimate, nv=st.nv))),
+}
 
 
 def _p1d_params(tbar_bins, St, p_lo, L, nseg, min_used, stack):
@@ -369,6 +385,74 @@ class ForestStatistics(object):
         call(0, moments)
         return moments, stack
 
+    # ------------------------------------------------------------------ sightline bootstrap
+    def segment_codes(self, trans, ivar, *, zabs=None, zfac=None, batch=None, tbar, tbar_bins=None, seg_len, n_segments, pixel_start=0,
+                      min_used, bins):
+        """The z-bin of every segment as ``p1d`` and the other segment statistics stack it (qfa_segment_codes_f32; the contract is in
+        include/qfa_hip.h): the inputs and keywords of ``p1d``, ``bins`` = (z0, dz, nz).  Returns codes (B, S, n_segments) int32: the
+        z-bin of a valid segment inside the bins, else -1."""
+        inp = self._p1d_inputs("segment_codes", True, trans, ivar, zabs, zfac, batch, tbar, tbar_bins)
+        B, S, tb, St, tbar_bins, bs, keep = inp
+        L, nseg = int(seg_len), int(n_segments)
+        pp = _p1d_params(tbar_bins, St, int(pixel_start), L, nseg, min_used, types.SimpleNamespace(bins=ForestStack._round_bins(*bins)))
+        codes = torch.empty((B, S, max(nseg, 0)), dtype=torch.int32, device=self.device)
+        _lib.check(_lib.lib().qfa_segment_codes_f32(
+            _lib.require_device_tensor(trans, f32, "trans"), _lib.require_device_tensor(ivar, f32, "ivar"), C.byref(bs), _ptr(tb), B, S,
+            self.Nb, C.byref(pp), _ptr(codes), _lib.current_stream(self.device)), "qfa_segment_codes_f32")
+        return codes
+
+    def segment_bootstrap(self, rows, codes, *, n_boot, seed=0, offset=0, nz, stack=None, bins=None, estimate=None):
+        """The Poisson bootstrap over sightlines of per-segment rows (qfa_bootstrap_f64; the contract is in include/qfa_hip.h).
+        ``rows`` (B, S, n_segments, ...) float32, float64 or int32 as a segment statistic returns them (``power``, ``pairs``,
+        ``hist``, ``bandpower``, ``moments``; the axes behind the third are one row of W values), ``codes`` (B, S, n_segments) int32
+        of ``segment_codes``.  Replicate r weights spectrum b by w(``seed``, ``offset`` + b, r) ~ Poisson(1) -- ``offset``: the global
+        row of spectrum 0, so that a data set cut into calls gets the weights of one call.  ``stack``: a ``BootstrapStack`` of S
+        draws, ``n_boot`` replicates, ``nz`` bins and W columns to ADD to (its seed is used); else a new one (``bins``, ``estimate``:
+        what it should carry).  Returns the ``BootstrapStack``."""
+        if not isinstance(rows, torch.Tensor) or rows.dim() < 3 or str(rows.dtype).replace("torch.", "") not in _lib.ROW_TYPES:
+            raise QFAHipError("segment_bootstrap: rows must be a (B, S, n_segments, ...) float32, float64 or int32 tensor")
+        B, S, nseg = (int(x) for x in rows.shape[:3])
+        W = int(np.prod(rows.shape[3:], dtype=np.int64))
+        if tuple(codes.shape) != (B, S, nseg):
+            raise QFAHipError(f"segment_bootstrap: codes {tuple(codes.shape)}, expected ({B}, {S}, {nseg})")
+        R, nz, dev = int(n_boot), int(nz), self.device
+        h = _lib.lib()
+        need = h.qfa_bootstrap_workspace_bytes(B, S, nseg, W, nz, R)
+        if need == 0:
+            raise QFAHipError(f"segment_bootstrap: unsupported shape B={B} S={S} n_segments={nseg} W={W} nz={nz} n_boot={R}")
+        if stack is None:
+            stack = BootstrapStack.zeros(S, R, nz, W, seed, bins, estimate, dev)
+        elif not isinstance(stack, BootstrapStack) or (stack.S, stack.R, stack.nz, stack.W) != (S, R, nz, W):
+            raise QFAHipError(f"segment_bootstrap(stack=...): expected a BootstrapStack of {S} draws, {R} replicates, {nz} z-bins and "
+                              f"{W} columns")
+        ws = self._scratch("boot_ws", need)
+        _lib.check(h.qfa_bootstrap_f64(
+            _lib.require_device_tensor(rows, rows.dtype, "rows"), _lib.ROW_TYPES[str(rows.dtype).replace("torch.", "")],
+            _lib.require_device_tensor(codes, torch.int32, "codes"), B, S, nseg, W, nz, R, stack.seed, int(offset), 0,
+            _lib.require_device_tensor(stack.buf, torch.float64, "stack"), _ptr(ws), ws.numel(), _lib.current_stream(dev)),
+            "qfa_bootstrap_f64")
+        return stack
+
+    def bootstrap(self, dataloader, statistic, z_min, z_max, n_zbins, n_boot, *, boot_seed=0, **keywords):
+        """A segment statistic of a whole dataloader with its sightline bootstrap: ``statistic`` is "p1d", "bands", "xi", "pdf" or
+        "variance", ``keywords`` those of its loader call (``flux_power``, ``band_power``, ``flux_correlation``, ``flux_pdf``,
+        ``variance_function``).  That call's loop runs with the per-segment rows kept, and every slice adds its ``n_boot`` Poisson
+        replicates (``boot_seed``) to a ``BootstrapStack`` whose ``estimate`` is the statistic's own formula.  The weight of a
+        spectrum depends on its dataloader index alone and every sum is one chain in segment order, so the result does not depend
+        on ``batch_size``; under data parallelism the sums are all-reduced over the model's group.  Returns (stack, boot): the
+        statistic's stack, bit-equal to the plain loader call's, and the ``BootstrapStack``."""
+        if statistic not in _BOOT_STATS:
+            raise QFAHipError(f"bootstrap: statistic = {statistic!r}, expected one of {sorted(_BOOT_STATS)}")
+        if int(n_boot) < 1:
+            raise QFAHipError(f"bootstrap: n_boot = {n_boot}")
+        method, rows, spec = _BOOT_STATS[statistic]
+        self._boot_request = req = {"n_boot": int(n_boot), "seed": int(boot_seed), "rows": rows, "spec": spec, "boot": None}
+        try:
+            stack = getattr(self, method)(dataloader, z_min, z_max, n_zbins, **keywords)
+        finally:
+            self._boot_request = None
+        return stack, req["boot"]
+
     def flux_power(self, dataloader, z_min, z_max, n_zbins, *, n_segments=3, seg_len=None, min_used_frac=0.75, tbar=None,
                    tbar_nbins=64, n_samples=0, seed=0, batch_size=4096, cont_min=0.0, dv=None):
         """The 1D flux power spectrum of a whole dataloader: a ``P1DStack`` of S = max(1, n_samples) draws over ``n_zbins`` bins of
@@ -473,6 +557,10 @@ class ForestStatistics(object):
             raise QFAHipError(f"{what}: tbar must be a ForestStack of 1 or {S} draws")
         tmean = tbar.mean.to(f32)
         row0 = int(getattr(dataloader, "_row0", 0))              # (a data-parallel loader: the global index of its first row)
+        req, self._boot_request = getattr(self, "_boot_request", None), None      # (`bootstrap` asks: the rows are kept and resampled)
+        if req is not None:
+            W, estimate = req["spec"](stack)
+            req["boot"] = BootstrapStack.zeros(S, req["n_boot"], nz, W, req["seed"], stack.bins, estimate, self.device)
         for s, inputs, _ in self._loader_slices(dataloader, int(batch_size)):
             _, hmean, hcov, _, unc = self.predict(**inputs)
             B = int(hmean.shape[0])
@@ -487,8 +575,15 @@ class ForestStatistics(object):
                 hs = h if (s0 == 0 and s1 == S) else h[:, s0:s1].contiguous()
                 tr, iv, _ = self.forest(**inputs, h=hs, unc=unc, cont_min=cont_min)
                 kw = dict(tbar=tmean if tbar.S == 1 else tmean[s0:s1], tbar_bins=tbar.bins, seg_len=L, n_segments=nseg,
-                          min_used=min_used, stack=stack.draws(s0, s1), return_segments=False)
-                stat.call(tr, iv, **zin, **kw, **stat.keywords)
+                          min_used=min_used, stack=stack.draws(s0, s1), return_segments=req is not None)
+                out = stat.call(tr, iv, **zin, **kw, **stat.keywords)
+                if req is not None:
+                    seg = {k: kw[k] for k in ("tbar", "tbar_bins", "seg_len", "n_segments", "min_used")}
+                    codes = self.segment_codes(tr, iv, **zin, **seg, bins=stack.bins)
+                    self.segment_bootstrap(req["rows"](out), codes, n_boot=req["n_boot"], offset=row0 + s, nz=nz,
+                                           stack=req["boot"].draws(s0, s1))
         if self._dp:
             stack.all_reduce(self._dp_group)
+            if req is not None:
+                req["boot"].all_reduce(self._dp_group)
         return stack
