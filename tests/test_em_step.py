@@ -28,32 +28,13 @@ def T(x, dev):
     return torch.tensor(x, dtype=torch.bool if x.dtype == bool else torch.float32, device=dev)
 
 
-def setup(dev, npix, nh, B, seed, random_F=True, junk=True):
-    """model + numpy batch: masks on, one red-only spectrum, one pixel range masked in every spectrum, NaN / inf / -999 under
-    the masks; F ~ U(-0.5, 0.5) like random_init_func"""
-    from qfa_amd import QFA, synthetic
-    wav, nb, nr = synthetic.wavelength_grid(npix)
-    p, mu = synthetic.mock_parameters(npix, nb, nh, seed=seed)
-    dead = (npix // 3, min(npix, npix // 3 + 3)) if npix >= 8 else None
-    # (a pixel axis shorter than a mask run would be masked whole: such shapes get the per-pixel 1 % masks only below)
-    b = synthetic.make_batch_numpy(p, mu, wav, nb, B, seed=seed + 1, masks=npix >= 32,
-                                   red_only=(0,) if (B > 2 and 0 < nb < npix) else (), dead_range=dead)
-    if npix < 32 and B > 1:
-        b["mask"][1::3, ::2] = False
-        for k in ("flux", "error"):
-            b[k] = np.where(b["mask"], b[k], np.float32(-999.0))
-    if random_F:
-        p = dict(p)
-        p["F"] = np.random.default_rng(seed + 2).uniform(-0.5, 0.5, size=(npix, nh)).astype(np.float32)
-    if junk:
-        rng = np.random.default_rng(seed + 3)
-        hole = ~b["mask"]
-        fill = rng.choice(np.array([np.nan, np.inf, -np.inf, -999.0], dtype=np.float32), size=hole.sum())
-        b["delta"] = b["delta"].copy(); b["error"] = b["error"].copy()
-        b["delta"][hole] = fill
-        b["error"][hole] = fill[::-1]
+def setup(dev, npix, nh, B, seed, random_F=True, junk=True, batch_seed=None, plant=None):
+    """model + numpy batch (_em_ref.em_inputs, which the CPU side shares): masks on, one red-only spectrum, one pixel range
+    masked in every spectrum, NaN / inf / -999 under the masks; F ~ U(-0.5, 0.5) like random_init_func"""
+    from qfa_amd import QFA
+    p, b, dead, wav, nb, zf = E.em_inputs(npix, nh, B, seed, random_F=random_F, junk=junk, batch_seed=batch_seed, plant=plant)
     m = QFA(nb, npix - nb, nh, dev, model_params=p)
-    zfac = (T((1.0 + b["zqso"].astype(np.float64)).astype(np.float32), dev), T((wav[:nb] / synthetic.LYA).astype(np.float32), dev))
+    zfac = (T(zf[0], dev), T(zf[1], dev))
     return m, p, b, zfac, dead
 
 
@@ -75,10 +56,7 @@ def check_stats(st, ref, tag):
     assert torch.equal(st.S2, st.S2.transpose(1, 2)), tag            # symmetric bit for bit
 
 
-SHAPES = [  # (npix, nh, B): every N_h class, ragged pixel axes (N_pix = 1 included), B from 1 to 4 096
-    (1, 1, 5), (37, 1, 1), (203, 4, 70), (333, 8, 257), (97, 8, 4096), (501, 16, 130), (75, 16, 1030), (211, 17, 33),
-    (130, 32, 300), (45, 5, 2), (1030, 12, 64),
-]
+SHAPES = E.SHAPES      # (npix, nh, B): every N_h class, ragged pixel axes (N_pix = 1 included), B from 1 to 4 096
 
 
 @pytest.mark.parametrize("npix,nh,B", SHAPES)
