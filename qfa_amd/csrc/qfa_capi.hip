@@ -46,16 +46,6 @@ int check_call(const qfa_params_t *p, const qfa_batch_t *b, const qfa_tau_t *tau
     return 0;
 }
 
-// N_h -> the instantiation of the step's host code: KP = 8 and 16 here, the N_h = 17..32 build in qfa_k32.hip
-template <class R8, class R16, class R32>
-int by_kp(int Nh, R8 run8, R16 run16, R32 run32) {
-    switch (kp_for(Nh)) {
-        case 8: return run8();
-        case 16: return run16();
-        default: return run32();
-    }
-}
-
 // The bias corrections of Adam's step i.  The reference mixes Python floats (double) with float32 tensors: every scalar is
 // formed in double and rounded to float32 once, exactly where torch would round it.
 struct AdamBias { float bc1, bc2; };
@@ -70,12 +60,12 @@ int qfa_estep_check(const qfa_params_t *p, const qfa_batch_t *b, const qfa_tau_t
     return check_call(p, b, tau, true, B, Npix, Nb, Nh, nullptr);
 }
 
-int qfa_estep(const qfa_params_t &p, const qfa_batch_t &b, const qfa_tau_t &tau, int B, int Npix, int Nb, int Nh, float *nll,
-              float *ws, hipStream_t st, QfaEStep *out) {
-    const qfa_batch_t bb = norm_batch(b, Npix);
-    return by_kp(Nh, [&] { return run_estep<8>(p, bb, tau, B, Npix, Nb, Nh, nll, ws, st, out); },
-                 [&] { return run_estep<16>(p, bb, tau, B, Npix, Nb, Nh, nll, ws, st, out); },
-                 [&] { return qfa_k32_estep(p, bb, tau, B, Npix, Nb, Nh, nll, ws, st, out); });
+int qfa_estep(const BatchCall &c, float *nll, QfaEStep *out) {
+    return by_kp(kp_for(c.Nh), [&](auto kp) {
+        constexpr int KP = decltype(kp)::value;
+        if constexpr (KP == 32) return qfa_k32_estep(c, nll, out);      // (the N_h = 17..32 build: qfa_k32.hip)
+        else return run_estep<KP>(c, nll, out);
+    });
 }
 
 extern "C" {
@@ -110,20 +100,15 @@ size_t qfa_accum_floats(int Npix, int Nb, int Nh) {
     return (size_t)Npix * Nh + 3 * (size_t)Npix + (size_t)Nb + 8;
 }
 
-int qfa_nll_grad_events_f32(const qfa_params_t *p, const qfa_batch_t *b, const qfa_tau_t *tau, int B, int Npix,
-                            int Nb, int Nh, float *nll, float *accum, void *workspace, size_t workspace_bytes,
-                            void *stream, void *const *events);
-
 int qfa_nll_grad_f32(const qfa_params_t *p, const qfa_batch_t *b, const qfa_tau_t *tau, int B, int Npix, int Nb,
                      int Nh, float *nll, float *accum, void *workspace, size_t workspace_bytes, void *stream) {
-    return qfa_nll_grad_events_f32(p, b, tau, B, Npix, Nb, Nh, nll, accum, workspace, workspace_bytes, stream, nullptr);
+    return qfa_nll_grad_ex_f32(p, b, tau, B, Npix, Nb, Nh, nll, accum, workspace, workspace_bytes, nullptr, 0, 0u, stream, nullptr);
 }
 
 int qfa_nll_grad_events_f32(const qfa_params_t *p, const qfa_batch_t *b, const qfa_tau_t *tau, int B, int Npix,
                             int Nb, int Nh, float *nll, float *accum, void *workspace, size_t workspace_bytes,
                             void *stream, void *const *events) {
-    return qfa_nll_grad_det_f32(p, b, tau, B, Npix, Nb, Nh, nll, accum, workspace, workspace_bytes, nullptr, 0, stream,
-                                events);
+    return qfa_nll_grad_ex_f32(p, b, tau, B, Npix, Nb, Nh, nll, accum, workspace, workspace_bytes, nullptr, 0, 0u, stream, events);
 }
 
 size_t qfa_det_slab_bytes(int B, int Npix, int Nb, int Nh) {
@@ -143,12 +128,12 @@ int qfa_nll_grad_ex_f32(const qfa_params_t *p, const qfa_batch_t *b, const qfa_t
                         size_t slab_bytes, unsigned flags, void *stream, void *const *events) {
     if (int e = check_call(p, b, tau, accum && workspace, B, Npix, Nb, Nh, &workspace_bytes)) return e;
     if (slab && slab_bytes < det_slab_bytes(B, Npix, Nb, Nh)) return QFA_E_WORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    float *ws = (float *)workspace;
-    const qfa_batch_t bb = norm_batch(*b, Npix);
-    return by_kp(Nh, [&] { return run_nll_grad<8>(*p, bb, *tau, B, Npix, Nb, Nh, nll, accum, ws, st, events, slab, flags); },
-                 [&] { return run_nll_grad<16>(*p, bb, *tau, B, Npix, Nb, Nh, nll, accum, ws, st, events, slab, flags); },
-                 [&] { return qfa_k32_nll_grad(*p, bb, *tau, B, Npix, Nb, Nh, nll, accum, ws, st, events, slab, flags); });
+    const BatchCall c{*p, norm_batch(*b, Npix), *tau, B, Npix, Nb, Nh, (float *)workspace, (hipStream_t)stream, flags};
+    return by_kp(kp_for(Nh), [&](auto kp) {
+        constexpr int KP = decltype(kp)::value;
+        if constexpr (KP == 32) return qfa_k32_nll_grad(c, nll, accum, events, slab);      // (the N_h = 17..32 build: qfa_k32.hip)
+        else return run_nll_grad<KP>(c, nll, accum, events, slab);
+    });
 }
 
 int qfa_finalize_grads_f32(const float *accum, const float *F, int Npix, int Nb, int Nh, int normalize, float *gF,
@@ -165,27 +150,25 @@ int qfa_finalize_grads_f32(const float *accum, const float *F, int Npix, int Nb,
 int qfa_predict_f32(const qfa_params_t *p, const float *mu, const qfa_batch_t *b, const qfa_tau_t *tau, int B,
                     int Npix, int Nb, int Nh, float *ll, float *hmean, float *hcov, float *cont, float *unc,
                     void *workspace, size_t workspace_bytes, void *stream) {
-    return qfa_predict_events_f32(p, mu, b, tau, B, Npix, Nb, Nh, ll, hmean, hcov, cont, unc, workspace, workspace_bytes,
-                                  stream, nullptr);
+    return qfa_predict_ex_f32(p, mu, b, tau, B, Npix, Nb, Nh, ll, hmean, hcov, cont, unc, workspace, workspace_bytes, 0u, stream, nullptr);
 }
 
 int qfa_predict_events_f32(const qfa_params_t *p, const float *mu, const qfa_batch_t *b, const qfa_tau_t *tau, int B,
                            int Npix, int Nb, int Nh, float *ll, float *hmean, float *hcov, float *cont, float *unc,
                            void *workspace, size_t workspace_bytes, void *stream, void *const *events) {
-    return qfa_predict_ex_f32(p, mu, b, tau, B, Npix, Nb, Nh, ll, hmean, hcov, cont, unc, workspace, workspace_bytes, 0u,
-                              stream, events);
+    return qfa_predict_ex_f32(p, mu, b, tau, B, Npix, Nb, Nh, ll, hmean, hcov, cont, unc, workspace, workspace_bytes, 0u, stream, events);
 }
 
 int qfa_predict_ex_f32(const qfa_params_t *p, const float *mu, const qfa_batch_t *b, const qfa_tau_t *tau, int B,
                        int Npix, int Nb, int Nh, float *ll, float *hmean, float *hcov, float *cont, float *unc,
                        void *workspace, size_t workspace_bytes, unsigned flags, void *stream, void *const *events) {
     if (int e = check_call(p, b, tau, mu && ll && hmean && hcov && cont && unc && workspace, B, Npix, Nb, Nh, &workspace_bytes)) return e;
-    hipStream_t st = (hipStream_t)stream;
-    float *ws = (float *)workspace;
-    const qfa_batch_t bb = norm_batch(*b, Npix);
-    return by_kp(Nh, [&] { return run_predict<8>(*p, mu, bb, *tau, B, Npix, Nb, Nh, ll, hmean, hcov, cont, unc, ws, st, events, flags); },
-                 [&] { return run_predict<16>(*p, mu, bb, *tau, B, Npix, Nb, Nh, ll, hmean, hcov, cont, unc, ws, st, events, flags); },
-                 [&] { return qfa_k32_predict(*p, mu, bb, *tau, B, Npix, Nb, Nh, ll, hmean, hcov, cont, unc, ws, st, events, flags); });
+    const BatchCall c{*p, norm_batch(*b, Npix), *tau, B, Npix, Nb, Nh, (float *)workspace, (hipStream_t)stream, flags};
+    return by_kp(kp_for(Nh), [&](auto kp) {
+        constexpr int KP = decltype(kp)::value;
+        if constexpr (KP == 32) return qfa_k32_predict(c, mu, ll, hmean, hcov, cont, unc, events);      // (qfa_k32.hip)
+        else return run_predict<KP>(c, mu, ll, hmean, hcov, cont, unc, events);
+    });
 }
 
 int qfa_adam_clip_f32(const float *p, const float *g, float *m, float *v, float *p_out, size_t n, double lr, double b1,

@@ -43,16 +43,12 @@ EmPlan em_plan(int B, int Npix, int Nh) {
 bool shape_ok(int Npix, int Nh) { return Npix >= 1 && Nh >= 1 && Nh <= 32 && (long long)64 * Npix < (1LL << 31); }
 
 template <int NT>
-void launch_stats(const qfa_params_t &p, const QfaEStep &es, const qfa_tau_t &tau, int B, int Npix, int Nb, int Nh,
-                  const EmPlan &P, int t0, const float *REC, float *SLAB, float *CNT, hipStream_t st) {
-    const dim3 grid((unsigned)((Npix + 63) / 64), (unsigned)P.R);
-    const qfa_batch_t &b = es.batch;
-    if (b.A_blue)
-        k_em_stats<NT, false, true><<<grid, 256, 0, st>>>(p, b, tau, B, Npix, Nb, Nh, P.per, t0, nullptr, nullptr, REC, SLAB, CNT);
-    else if (es.ZS)
-        k_em_stats<NT, true, false><<<grid, 256, 0, st>>>(p, b, tau, B, Npix, Nb, Nh, P.per, t0, es.ZS, es.ZP, REC, SLAB, CNT);
-    else
-        k_em_stats<NT, false, false><<<grid, 256, 0, st>>>(p, b, tau, B, Npix, Nb, Nh, P.per, t0, nullptr, nullptr, REC, SLAB, CNT);
+void launch_stats(const BatchCall &c, const QfaEStep &es, const EmPlan &P, int t0, const float *REC, float *SLAB, float *CNT) {
+    const dim3 grid((unsigned)((c.Npix + 63) / 64), (unsigned)P.R);
+    by_form(c.b, es.ZS != nullptr, false, [&](auto f) {
+        using Fm = decltype(f);
+        k_em_stats<NT, Fm::zf, Fm::hasa><<<grid, 256, 0, c.st>>>(c.p, c.b, c.tau, c.B, c.Npix, c.Nb, c.Nh, P.per, t0, es.ZS, es.ZP, REC, SLAB, CNT);
+    });
 }
 
 }  // namespace
@@ -76,18 +72,19 @@ int qfa_em_stats_f32(const qfa_params_t *p, const qfa_batch_t *b, const qfa_tau_
     if (flags & ~(QFA_F_ZERO_ACCUM | QFA_F_SYNC)) return QFA_E_FLAGS;
     const EmPlan P = em_plan(B, Npix, Nh);
     if (ws_bytes < P.total) return QFA_E_WORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
+    const BatchCall c{*p, norm_batch(*b, Npix), *tau, B, Npix, Nb, Nh, (float *)ws, (hipStream_t)stream, flags};
+    hipStream_t st = c.st;
     char *base = (char *)ws;
     float *REC = (float *)(base + P.oREC), *SLAB = (float *)(base + P.oSLAB), *CNT = (float *)(base + P.oCNT);
     QfaEStep es{};
-    if (int e = qfa_estep(*p, *b, *tau, B, Npix, Nb, Nh, nll, (float *)ws, st, &es)) return e;
+    if (int e = qfa_estep(c, nll, &es)) return e;
     const size_t nrec = (size_t)B * P.ncp;
     k_em_record<<<(unsigned)((nrec + 255) / 256), 256, 0, st>>>(es.SOL, es.nsol, es.KP, es.sol_ci, B, Nh, REC);
     const int ntl = P.ncp / 16;
-    if (ntl <= 2) launch_stats<2>(*p, es, *tau, B, Npix, Nb, Nh, P, 0, REC, SLAB, CNT, st);
-    else if (ntl <= 4) launch_stats<4>(*p, es, *tau, B, Npix, Nb, Nh, P, 0, REC, SLAB, CNT, st);
+    if (ntl <= 2) launch_stats<2>(c, es, P, 0, REC, SLAB, CNT);
+    else if (ntl <= 4) launch_stats<4>(c, es, P, 0, REC, SLAB, CNT);
     else
-        for (int t0 = 0; t0 < ntl; t0 += 10) launch_stats<10>(*p, es, *tau, B, Npix, Nb, Nh, P, t0, REC, SLAB, CNT, st);
+        for (int t0 = 0; t0 < ntl; t0 += 10) launch_stats<10>(c, es, P, t0, REC, SLAB, CNT);
     const int zero = (flags & QFA_F_ZERO_ACCUM) ? 1 : 0;
     const size_t n = (size_t)Npix * ((size_t)Nh * Nh + Nh + 1);
     k_em_reduce<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(SLAB, CNT, P.R, Npix, Nh, zero, stats);

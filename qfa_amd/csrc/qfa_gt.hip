@@ -6,14 +6,14 @@
 
 // ---- pass 2, pixel-resident form (qfa_grads_t.h)
 size_t qfa_gt_state_bytes(int KP, int B) {
-    return KP == 16 ? (size_t)((B + 15) / 16) * GTT<16>::STATE_B : (KP == 8 ? (size_t)((B + 15) / 16) * GTT<8>::STATE_B : 0);
+    return by_kp<16>(KP, [&](auto kp) { return (size_t)((B + 15) / 16) * GTT<decltype(kp)::value>::STATE_B; });
 }
 // tiles, pixel blocks of 8 tiles, ranges of spectra groups: about one workgroup per CU; a multiple of 8 ranges (the
 // workgroups of a range then share an XCD, block = pb R + r) where the batch has the groups for it
 static GtPlan gt_plan(int KP, int B, int Npix, int max_ranges) {
     GtPlan g;
     g.nxcd = xcd_count();
-    const int pxw = KP == 8 ? GTT<8>::PXW : GTT<16>::PXW;       // pixels per wave
+    const int pxw = by_kp<16>(KP, [](auto kp) { return (int)GTT<decltype(kp)::value>::PXW; });       // pixels per wave
     g.T16 = (Npix + pxw - 1) / pxw;
     g.PB = (g.T16 + 7) / 8;
     const int G = (B + 15) / 16, ncu = cu_count();
@@ -37,31 +37,15 @@ static GtPlan gt_plan(int KP, int B, int Npix, int max_ranges) {
 }
 int qfa_gt_items(int KP, int B, int Npix, int max_ranges) { return gt_plan(KP, B, Npix, max_ranges).items(); }
 int qfa_gt_ranges(int KP, int B, int Npix, int max_ranges) { return gt_plan(KP, B, Npix, max_ranges).R; }
-template <int KP>
-static void gt_launch(const qfa_params_t &p, const qfa_batch_t &b, const qfa_tau_t &tau, int B, int Npix, int Nb, int Nh,
-                      const GtPlan &g, const unsigned char *PGT, const unsigned char *PST, const float4 *zs, float *accum,
-                      float *slab, double *slabS, int slab_stride, Scal64 *sc64, int exact, hipStream_t st) {
-    auto go = [&](auto hasa, auto zf, auto ix) {
-        if (exact)
-            k_grads_t<KP, decltype(hasa)::value, decltype(zf)::value, decltype(ix)::value, true><<<g.items(), 512, 0, st>>>(
-                p, b, tau, B, Npix, Nb, Nh, g, PGT, PST, zs, accum, slab, slabS, slab_stride, sc64);
-        else
-            k_grads_t<KP, decltype(hasa)::value, decltype(zf)::value, decltype(ix)::value, false><<<g.items(), 512, 0, st>>>(
-                p, b, tau, B, Npix, Nb, Nh, g, PGT, PST, zs, accum, slab, slabS, slab_stride, sc64);
-    };
-    using T = std::true_type;
-    using F = std::false_type;
-    if (b.A_blue) go(T{}, F{}, F{});                         // (not combined with rows: check_batch)
-    else if (zs) { if (b.rows) go(F{}, T{}, T{}); else go(F{}, T{}, F{}); }
-    else { if (b.rows) go(F{}, F{}, T{}); else go(F{}, F{}, F{}); }
-}
-void qfa_gt_launch(int KP, const qfa_params_t &p, const qfa_batch_t &b, const qfa_tau_t &tau, int B, int Npix, int Nb, int Nh,
-                   int max_ranges, const unsigned char *PGT, const unsigned char *PST, const float *ZS, float *accum,
-                   float *slab, double *slabS, int slab_stride, Scal64 *sc64, int exact, hipStream_t st) {
-    const GtPlan g = gt_plan(KP, B, Npix, max_ranges);        // (g.R rows leave: qfa_gt_ranges)
-    const float4 *zs = reinterpret_cast<const float4 *>(ZS);
-    if (KP == 8) gt_launch<8>(p, b, tau, B, Npix, Nb, Nh, g, PGT, PST, zs, accum, slab, slabS, slab_stride, sc64, exact, st);
-    else gt_launch<16>(p, b, tau, B, Npix, Nb, Nh, g, PGT, PST, zs, accum, slab, slabS, slab_stride, sc64, exact, st);
+void qfa_gt_launch(int KP, const Pass2Call &a, int max_ranges, const unsigned char *PGT, const unsigned char *PST) {
+    const GtPlan g = gt_plan(KP, a.B, a.Npix, max_ranges);        // (g.R rows leave: qfa_gt_ranges)
+    by_kp<16>(KP, [&](auto kp) {
+        by_form(a.b, a.ZS != nullptr, a.exact != 0, [&](auto f) {
+            using Fm = decltype(f);
+            k_grads_t<decltype(kp)::value, Fm::hasa, Fm::zf, Fm::idx, Fm::exact><<<g.items(), 512, 0, a.st>>>(
+                a.p, a.b, a.tau, a.B, a.Npix, a.Nb, a.Nh, g, PGT, PST, a.ZS, a.accum, a.rows, a.rowsS, a.row_stride, a.sc64);
+        });
+    });
 }
 
 #if QFA_GT_STAMPS

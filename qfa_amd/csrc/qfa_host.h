@@ -2,35 +2,55 @@
 // Shared by qfa_capi.hip (N_h <= 16; built with -amdgpu-mfma-vgpr-form so that the MFMA accumulators
 // stay in VGPRs; pass 1 and stage 3 of pass 2 on the bf16 XDL pipe) and qfa_k32.hip (N_h in 17..32: 280 accumulator registers per lane need the AGPR
 // half of the register file, so that translation unit is built without the flag).
+// Every function here takes the call as one block (BatchCall, qfa_estep.h) and pass 2 as one more (Pass2Call); the input form and
+// KP become template arguments in by_form (qfa_estep.h) and by_kp, and nowhere else; k_solve is launched by launch_solve alone.
 #pragma once
 #include "qfa_step_kernels.h"
 #include "qfa_xdl_kernels.h"
 #include "qfa_s12_x.h"
 #include "qfa_estep.h"
 
+// One launch of pass 2: the call plus what every form of pass 2 takes
+struct Pass2Call : BatchCall {
+    const float *SOL;            // the solve's records
+    const float4 *ZS;            // per-spectrum factors of the factored-z form, else NULL
+    float *accum;                // the packed buffer
+    float *rows;                 // rows of the fixed-order reducer and their scalar records (NULL: pass 2 adds to the packed buffer
+    double *rowsS;               // with atomics)
+    int row_stride;              // floats per row
+    Scal64 *sc64;
+    int exact;                   // QFA_F_EXACT_GRAD
+};
+
+// KP -> compile-time constant: the one place that switches on it.  KPMAX = 16 in the translation units that hold no N_h = 17..32 code.
+template <int KPMAX = 32, class Fn>
+inline auto by_kp(int KP, Fn &&fn) {
+    if (KP == 8) return fn(std::integral_constant<int, 8>{});
+    if constexpr (KPMAX == 16) return fn(std::integral_constant<int, 16>{});
+    else {
+        if (KP == 16) return fn(std::integral_constant<int, 16>{});
+        return fn(std::integral_constant<int, 32>{});
+    }
+}
+
 // pass 2 for N_h <= 16 with every contraction on the XDL pipe (qfa_grads_x.h: KP = 8 or 16, built in qfa_gx.hip)
 size_t qfa_gx_image_bytes(int KP, int ntiles32);
-void qfa_gx_launch(int KP, const qfa_params_t &p, const qfa_batch_t &b, const qfa_tau_t &tau, int B, int Npix, int Nb, int Nh,
-                   int ntiles32, const WorkPlan &wp, unsigned char *PGX, const float *SOL, const float *ZS, float *accum,
-                   float *slab, double *slabS, int slab_stride, Scal64 *sc64, unsigned flags, hipStream_t st);
+void qfa_gx_launch(int KP, const Pass2Call &a, int ntiles32, const WorkPlan &wp, unsigned char *PGX);
 // everything a training step derives from the parameters before pass 1, in one launch (N_h <= 16; qfa_gx.hip, k_prep_step)
-void qfa_prep_step_launch(int KP, bool pixres, const qfa_params_t &p, const qfa_batch_t &b, const qfa_tau_t &tau, int B, int Npix,
-                          int Nb, int Nh, int ntiles32, unsigned char *PFX, unsigned char *P2, float *ZS, float *zero,
-                          size_t n_zero, hipStream_t st, unsigned *tick1);
+void qfa_prep_step_launch(int KP, bool pixres, const BatchCall &c, int ntiles32, unsigned char *PFX, unsigned char *P2, float4 *ZS,
+                          float *zero, size_t n_zero, unsigned *tick1);
 
 // the pixel-resident form of the all-XDL pass 2 (qfa_grads_t.h, built in qfa_gx.hip; N_h = 9..16): QFA_F_PASS2_PIXRES
 struct GtPlan;
 size_t qfa_gt_state_bytes(int KP, int B);
 int qfa_gt_items(int KP, int B, int Npix, int max_ranges);
 int qfa_gt_ranges(int KP, int B, int Npix, int max_ranges);
-void qfa_gt_launch(int KP, const qfa_params_t &p, const qfa_batch_t &b, const qfa_tau_t &tau, int B, int Npix, int Nb, int Nh,
-                   int max_ranges, const unsigned char *PGT, const unsigned char *PST, const float *ZS, float *accum,
-                   float *slab, double *slabS, int slab_stride, Scal64 *sc64, int exact, hipStream_t st);
+void qfa_gt_launch(int KP, const Pass2Call &a, int max_ranges, const unsigned char *PGT, const unsigned char *PST);
 
 // posterior writer for N_h <= 16 on the XDL pipe (qfa_predict_x.h, built in qfa_gx.hip)
 size_t qfa_px_image_bytes(int KP, int ntiles32);
-void qfa_px_launch(int KP, const float *F, const float *mu, int B, int Npix, int Nh, int ntiles32, const WorkPlan &wp,
-                   unsigned char *PXI, const float *SOL, float *cont, float *unc, hipStream_t st);
+void qfa_px_launch(int KP, const BatchCall &c, const float *mu, int ntiles32, const WorkPlan &wp, unsigned char *PXI, const float *SOL,
+                   float *cont, float *unc);
 
 namespace {
 
@@ -228,11 +248,7 @@ Layout make_layout_t(int B, int Npix) {
 }
 
 Layout make_layout(int B, int Npix, int Nh) {
-    switch (kp_for(Nh)) {
-        case 8: return make_layout_t<8>(B, Npix);
-        case 16: return make_layout_t<16>(B, Npix);
-        default: return make_layout_t<32>(B, Npix);
-    }
+    return by_kp(kp_for(Nh), [&](auto kp) { return make_layout_t<decltype(kp)::value>(B, Npix); });
 }
 
 // the batch's pointers: delta, error, mask always; the blue side needs zabs, or the factored form zq1 + pix_ratio
@@ -250,13 +266,6 @@ inline int check_batch(const qfa_batch_t &b, int Npix, int Nb) {
                                                                                     // inside a wave's 16 neighbouring rows
     return 0;
 }
-// the batch as the kernels take it: row_stride filled in
-inline qfa_batch_t norm_batch(const qfa_batch_t &b, int Npix) {
-    qfa_batch_t r = b;
-    if (r.row_stride == 0) r.row_stride = Npix;
-    return r;
-}
-
 inline int check_shape(int B, int Npix, int Nb, int Nh) {
     if (B < 1 || Npix < 1 || Nb < 0 || Nb > Npix || Nh < 1 || Nh > 32) return QFA_E_SIZE;
     if ((long long)64 * Npix >= (1LL << 31)) return QFA_E_SIZE;      // 32-bit byte offsets inside a wave's 16 rows
@@ -313,16 +322,47 @@ inline int hip_status(hipStream_t st = nullptr, unsigned flags = 0) {
 
 // the tile-major float32 image PFT: k_grads and k_predict_out (N_h <= 16), k_grads_s3 (N_h = 17..32)
 template <int KP>
-void launch_prep_pft(const qfa_params_t &p, const float4 *ZP, int Npix, int Nb, int Nh, const Layout &L, float *PFT, hipStream_t st) {
+void launch_prep_pft(const BatchCall &c, const float4 *ZP, const Layout &L) {
     dim3 blk(64, 4);
-    k_prep_pft<KP><<<(L.NpixPad + 3) / 4, blk, 0, st>>>(p.F, p.Psi, p.omega, ZP, Npix, Nb, Nh, L.NpixPad, PFT);
+    k_prep_pft<KP><<<(L.NpixPad + 3) / 4, blk, 0, c.st>>>(c.p.F, c.p.Psi, c.p.omega, ZP, c.Npix, c.Nb, c.Nh, L.NpixPad, c.ws + L.oPFT);
 }
 
-// k_solve: KP lanes per spectrum, four waves per block
+// the arrival counters of k_reduce_nll and k_solve in the workspace; Scal64 of pass 2 lies behind them (both zeroed by k_solve)
+inline unsigned *ws_ticket(const BatchCall &c, const Layout &L) {
+    return reinterpret_cast<unsigned *>(reinterpret_cast<double *>(c.ws + L.oRED) + 2 * NRED);
+}
+
+// k_solve (KP lanes per spectrum, four waves per block) from the moment records of pass 1.  What it writes:
+enum class Solve {
+    RECORD,    // the float32 record SOL (the E-step: with exact = 1)
+    STATE,     // the operand images k_grads_t streams (N_h <= 16)
+    NLLRED,    // SOL, and its last block sums the NLL of a small batch into `scal` (no k_reduce_nll; N_h <= 16)
+    PREDICT    // SOL, the log-likelihood `nll`, the posterior mean `hmean` and covariance `hcov`
+};
 template <int KP>
-inline unsigned solve_blocks(int B) {
+void launch_solve(Solve kind, const BatchCall &c, const Layout &L, float *nll, int exact, float *scal = nullptr,
+                  float *hmean = nullptr, float *hcov = nullptr) {
     constexpr int G = 64 / KP;
-    return (unsigned)((B + 4 * G - 1) / (4 * G));
+    const unsigned nblk = (unsigned)((c.B + 4 * G - 1) / (4 * G));
+    float *MOM = c.ws + L.oMOM, *SOL = c.ws + L.oSOL, *NBL = c.ws + L.oNBL;
+    unsigned *ticket = ws_ticket(c, L);
+    switch (kind) {
+        case Solve::RECORD:
+            k_solve<KP, false><<<nblk, 256, 0, c.st>>>(MOM, SOL, nll, NBL, c.B, c.Nh, nullptr, nullptr, ticket, nullptr, nullptr, exact);
+            break;
+        case Solve::STATE:
+            if constexpr (KP <= 16)
+                k_solve<KP, false, true><<<nblk, 256, 0, c.st>>>(MOM, SOL, nll, NBL, c.B, c.Nh, nullptr, nullptr, ticket,
+                                                                 reinterpret_cast<unsigned char *>(c.ws + L.oPST), nullptr, exact);
+            break;
+        case Solve::NLLRED:
+            if constexpr (KP <= 16)
+                k_solve<KP, false, false, true><<<nblk, 256, 0, c.st>>>(MOM, SOL, nll, NBL, c.B, c.Nh, nullptr, nullptr, ticket, nullptr, scal, exact);
+            break;
+        case Solve::PREDICT:
+            k_solve<KP, true><<<nblk, 256, 0, c.st>>>(MOM, SOL, nll, nullptr, c.B, c.Nh, hmean, hcov);
+            break;
+    }
 }
 
 // the caller's stage events (bench.py's stamps; entries may be NULL), recorded on the call's stream
@@ -336,13 +376,14 @@ struct EventMarks {
 
 // MOM[seg 0] += MOM[seg 1..] for the rows of the segmented blocks of pass 1
 template <int KP>
-void sum_segments(float *MOM, const Layout &L, int B, hipStream_t st) {
+void sum_segments(const BatchCall &c, const Layout &L) {
     const WorkPlan &w = L.wp1;
     if (w.rem == 0 || w.nseg <= 1) return;
+    float *MOM = c.ws + L.oMOM;
     const size_t row0 = (size_t)w.full * L.spb1;
     const size_t rows = (size_t)L.Bpad - row0;                  // Bpad is a multiple of 16, NMOM of 4
     const size_t n4 = rows * Cfg<KP>::NMOM / 4;
-    k_sum_segments<<<(unsigned)((n4 + 255) / 256), 256, 0, st>>>(
+    k_sum_segments<<<(unsigned)((n4 + 255) / 256), 256, 0, c.st>>>(
         reinterpret_cast<float4 *>(MOM + row0 * Cfg<KP>::NMOM),
         reinterpret_cast<const float4 *>(MOM + (size_t)L.Bpad * Cfg<KP>::NMOM), w.nseg, n4);
 }
@@ -352,45 +393,37 @@ void sum_segments(float *MOM, const Layout &L, int B, hipStream_t st) {
 struct ZTables {
     const float4 *ZS, *ZP;
 };
-inline bool has_zfac(const qfa_batch_t &b, int Nb) { return b.zq1 && b.pix_ratio && Nb > 0; }
-inline ZTables launch_zfac(const qfa_params_t &p, const qfa_batch_t &b, const qfa_tau_t &tau, int B, int Nb, const Layout &L,
-                           float *ws, hipStream_t st) {
-    if (!has_zfac(b, Nb)) return ZTables{nullptr, nullptr};
-    float4 *ZS = reinterpret_cast<float4 *>(ws + L.oZS), *ZP = reinterpret_cast<float4 *>(ws + L.oZP);
-    k_zfac_spec<<<(B + 255) / 256, 256, 0, st>>>(b.zq1, b.rows, p, tau, B, ZS);
-    k_zfac_pix<<<(Nb + 255) / 256, 256, 0, st>>>(b.pix_ratio, p, tau, Nb, ZP);
+inline bool has_zfac(const BatchCall &c) { return c.b.zq1 && c.b.pix_ratio && c.Nb > 0; }
+inline ZTables launch_zfac(const BatchCall &c, const Layout &L) {
+    if (!has_zfac(c)) return ZTables{nullptr, nullptr};
+    float4 *ZS = reinterpret_cast<float4 *>(c.ws + L.oZS), *ZP = reinterpret_cast<float4 *>(c.ws + L.oZP);
+    k_zfac_spec<<<(c.B + 255) / 256, 256, 0, c.st>>>(c.b.zq1, c.b.rows, c.p, c.tau, c.B, ZS);
+    k_zfac_pix<<<(c.Nb + 255) / 256, 256, 0, c.st>>>(c.b.pix_ratio, c.p, c.tau, c.Nb, ZP);
     return ZTables{ZS, ZP};
 }
 
 // pass 1 on the XDL pipe (split-bf16 operands, 32-pixel tiles) at every N_h
 template <int KP, bool PREDICT>
-void launch_moments(const qfa_params_t &p, const qfa_batch_t &b, const qfa_tau_t &tau, const float *mu, int B, int Npix,
-                   int Nb, int Nh, const Layout &L, const ZTables &zt, float *ws, hipStream_t st, bool prep = true,
-                   bool exact = false) {
-    float *MOM = ws + L.oMOM;
-    unsigned char *PFX = reinterpret_cast<unsigned char *>(ws + L.oPFX);
+void launch_moments(const BatchCall &c, const float *mu, const Layout &L, const ZTables &zt, bool prep = true, bool exact = false) {
+    float *MOM = c.ws + L.oMOM;
+    unsigned char *PFX = reinterpret_cast<unsigned char *>(c.ws + L.oPFX);
     if (prep) {
         if (XCfg<KP>::F16) {
             unsigned *cm = pfx_colmax<KP>(PFX, L.ntiles32);
-            (void)hipMemsetAsync(cm, 0, sizeof(unsigned) * XCfg<KP>::NCOL, st);
-            k_colmax<KP><<<L.ntiles32, 1024, 0, st>>>(p.F, p.Psi, Npix, Nh, cm);
+            (void)hipMemsetAsync(cm, 0, sizeof(unsigned) * XCfg<KP>::NCOL, c.st);
+            k_colmax<KP><<<L.ntiles32, 1024, 0, c.st>>>(c.p.F, c.p.Psi, c.Npix, c.Nh, cm);
         }
-        k_prep_pfx<KP><<<L.ntiles32, 256, 0, st>>>(p.F, p.Psi, p.omega, PREDICT ? mu : nullptr, zt.ZP, -QFA_LOG2E * tau.offset, Npix, Nb, Nh, PFX);
+        k_prep_pfx<KP><<<L.ntiles32, 256, 0, c.st>>>(c.p.F, c.p.Psi, c.p.omega, PREDICT ? mu : nullptr, zt.ZP, -QFA_LOG2E * c.tau.offset,
+                                                     c.Npix, c.Nb, c.Nh, PFX);
     }
     constexpr int NW = 4;                             // (L.spb1 = 16 NW spectra per block)
     // the exact-gradient step's instantiation leaves out the T-side moments where that measured faster (QFA_P1_SKIPT_EXACT_KP)
     constexpr bool SKIP_EX = !PREDICT && KP >= QFA_P1_SKIPT_EXACT_KP;
-    if (SKIP_EX && exact) {
-        if (zt.ZS)
-            k_moments_x<KP, false, NW, true, SKIP_EX><<<L.wp1.items(), 64 * NW, 0, st>>>(p, b, tau, mu, B, L.Bpad, Npix, Nb, L.ntiles32, L.wp1, PFX, zt.ZS, MOM);
-        else
-            k_moments_x<KP, false, NW, false, SKIP_EX><<<L.wp1.items(), 64 * NW, 0, st>>>(p, b, tau, mu, B, L.Bpad, Npix, Nb, L.ntiles32, L.wp1, PFX, nullptr, MOM);
-        return;
-    }
-    if (zt.ZS)
-        k_moments_x<KP, PREDICT, NW, true><<<L.wp1.items(), 64 * NW, 0, st>>>(p, b, tau, mu, B, L.Bpad, Npix, Nb, L.ntiles32, L.wp1, PFX, zt.ZS, MOM);
-    else
-        k_moments_x<KP, PREDICT, NW, false><<<L.wp1.items(), 64 * NW, 0, st>>>(p, b, tau, mu, B, L.Bpad, Npix, Nb, L.ntiles32, L.wp1, PFX, nullptr, MOM);
+    by_form(c.b, zt.ZS != nullptr, exact, [&](auto f) {
+        using Fm = decltype(f);
+        k_moments_x<KP, PREDICT, NW, Fm::zf, SKIP_EX && Fm::exact><<<L.wp1.items(), 64 * NW, 0, c.st>>>(
+            c.p, c.b, c.tau, mu, c.B, L.Bpad, c.Npix, c.Nb, L.ntiles32, L.wp1, PFX, zt.ZS, MOM);
+    });
 }
 
 inline DetLayout det_layout(const Layout &L, int B, int Npix, int Nb, int Nh) {
@@ -412,8 +445,6 @@ inline void launch_reduce_slab(const float *slab, const DetLayout &D, int rows, 
 }
 
 // What a training step launches, decided once from the shape, the flags and whether the caller brought a slab.
-enum class Solve { RECORD, STATE, NLLRED };   // k_solve writes: the float32 record SOL | the operand images k_grads_t streams | SOL, and
-                                              // its last block sums the NLL of a small batch (no k_reduce_nll)
 struct StepPlan {
     int err;               // QFA_E_FLAGS: the call asks for a form that does not exist at this N_h
     Pass2 pass2;
@@ -427,13 +458,14 @@ struct StepPlan {
     int rows, itemwaves;   // rows written, scalar records written (waves per work item x items)
     DetLayout D;           // of the region the rows live in (all zero without one)
 };
-inline StepPlan plan_step(const Layout &L, int B, int Npix, int Nb, int Nh, unsigned flags, bool slab) {
+inline StepPlan plan_step(const Layout &L, const BatchCall &c, bool slab) {
+    const int B = c.B, Npix = c.Npix, Nb = c.Nb, Nh = c.Nh;
     StepPlan P{};
-    if (L.KP <= 16 && (flags & QFA_F_S3_FAST)) {      // (the three-product form exists at N_h = 17..32 only)
+    if (L.KP <= 16 && (c.flags & QFA_F_S3_FAST)) {      // (the three-product form exists at N_h = 17..32 only)
         P.err = QFA_E_FLAGS;
         return P;
     }
-    P.pass2 = pass2_form(L.KP, B, Npix, flags);
+    P.pass2 = pass2_form(L.KP, B, Npix, c.flags);
     P.prep_step = P.pass2 == Pass2::XDL || P.pass2 == Pass2::PIXRES;
     // (pixel-resident pass 2: the solve writes the operand images that form streams instead of the float32 record SOL;
     // small batches -- one block of k_reduce_nll -- on the two-role form: the solve's last block sums the NLL itself)
@@ -456,192 +488,146 @@ inline StepPlan plan_step(const Layout &L, int B, int Npix, int Nb, int Nh, unsi
 
 // pass 2 in its float32-MFMA form (QFA_F_PASS2_F32, N_h <= 16): custom tau table / factored z / zabs
 template <int KP>
-void launch_grads_f32(const qfa_params_t &p, const qfa_batch_t &b, const qfa_tau_t &tau, int B, int Npix, int Nb, int Nh, const Layout &L,
-                      const float4 *ZS, const float *PFT, const float *SOL, float *accum, float *slab, double *slabS, int slab_stride,
-                      Scal64 *sc64, int exact, hipStream_t st) {
-    auto grads = [&](auto ex) {
-        constexpr bool E = decltype(ex)::value;
-        if (b.A_blue)
-            k_grads<KP, true, false, E><<<L.wp2.items(), 256, 0, st>>>(p, b, tau, B, Npix, Nb, Nh, L.ntiles, L.wp2, PFT, SOL, accum, slab, slabS, slab_stride, sc64, nullptr);
-        else if (ZS)
-            k_grads<KP, false, true, E><<<L.wp2.items(), 256, 0, st>>>(p, b, tau, B, Npix, Nb, Nh, L.ntiles, L.wp2, PFT, SOL, accum, slab, slabS, slab_stride, sc64, ZS);
-        else
-            k_grads<KP, false, false, E><<<L.wp2.items(), 256, 0, st>>>(p, b, tau, B, Npix, Nb, Nh, L.ntiles, L.wp2, PFT, SOL, accum, slab, slabS, slab_stride, sc64, nullptr);
-    };
-    if (exact) grads(std::true_type{});
-    else grads(std::false_type{});
+void launch_grads_f32(const Pass2Call &a, const Layout &L, const float *PFT) {
+    by_form(a.b, a.ZS != nullptr, a.exact != 0, [&](auto f) {
+        using Fm = decltype(f);
+        k_grads<KP, Fm::hasa, Fm::zf, Fm::exact><<<L.wp2.items(), 256, 0, a.st>>>(a.p, a.b, a.tau, a.B, a.Npix, a.Nb, a.Nh, L.ntiles, L.wp2, PFT, a.SOL,
+                                                                                 a.accum, a.rows, a.rowsS, a.row_stride, a.sc64, a.ZS);
+    });
 }
 
 // pass 2 at N_h = 17..32: stages 1 and 2 for every (spectrum, pixel) on the XDL pipe, beta / gamma through HBM, then stage 3 per
 // 16 columns
 template <int KP>
-void launch_s12_s3(const qfa_params_t &p, const qfa_batch_t &b, const qfa_tau_t &tau, int B, int Npix, int Nb, int Nh, const Layout &L,
-                   const ZTables &zt, float *ws, float *accum, float *slab, double *slabS, int slab_stride, Scal64 *sc64, int exact,
-                   bool s3_fast, hipStream_t st) {
-    const float *PFT = ws + L.oPFT, *SOL = ws + L.oSOL;
-    float *BG = ws + L.oBG, *GG = BG + (size_t)round_up(B, 64) * L.bg_stride;
-    unsigned char *IMG = reinterpret_cast<unsigned char *>(ws + L.oPGX);
-    k_prep_s12<KP><<<L.ntiles32, 256, 0, st>>>(p.F, p.Psi, p.omega, zt.ZP, Npix, Nb, Nh, IMG);
-    auto s12 = [&](auto hasa, auto zf, auto ex) {
-        k_s12_x<KP, decltype(hasa)::value, decltype(zf)::value, decltype(ex)::value><<<L.wp2x.items(), 256, 0, st>>>(
-            p, b, tau, B, Npix, Nb, Nh, L.ntiles32, L.wp2x, IMG, SOL, BG, GG, L.bg_stride, accum, slab, slabS, slab_stride,
-            sc64, decltype(zf)::value ? zt.ZS : nullptr);
-    };
-    auto s12e = [&](auto hasa, auto zf) {
-        if (exact) s12(hasa, zf, std::true_type{});
-        else s12(hasa, zf, std::false_type{});
-    };
-    if (b.A_blue) s12e(std::true_type{}, std::false_type{});
-    else if (zt.ZS) s12e(std::false_type{}, std::true_type{});
-    else s12e(std::false_type{}, std::false_type{});
-    for (int bh = 0; 16 * bh < Nh; ++bh) {
-        if (s3_fast)
-            k_grads_s3<KP, 3><<<L.wp2.items(), 256, 0, st>>>(B, Npix, Nh, L.ntiles, L.wp2, bh, PFT, SOL, BG, GG, L.bg_stride, accum, slab, slab_stride);
+void launch_s12_s3(const Pass2Call &a, const Layout &L, const float4 *ZP, const float *PFT) {
+    float *BG = a.ws + L.oBG, *GG = BG + (size_t)round_up(a.B, 64) * L.bg_stride;
+    unsigned char *IMG = reinterpret_cast<unsigned char *>(a.ws + L.oPGX);
+    k_prep_s12<KP><<<L.ntiles32, 256, 0, a.st>>>(a.p.F, a.p.Psi, a.p.omega, ZP, a.Npix, a.Nb, a.Nh, IMG);
+    by_form(a.b, a.ZS != nullptr, a.exact != 0, [&](auto f) {
+        using Fm = decltype(f);
+        k_s12_x<KP, Fm::hasa, Fm::zf, Fm::exact><<<L.wp2x.items(), 256, 0, a.st>>>(a.p, a.b, a.tau, a.B, a.Npix, a.Nb, a.Nh, L.ntiles32, L.wp2x, IMG, a.SOL,
+                                                                                  BG, GG, L.bg_stride, a.accum, a.rows, a.rowsS, a.row_stride,
+                                                                                  a.sc64, a.ZS);
+    });
+    for (int bh = 0; 16 * bh < a.Nh; ++bh) {
+        if (a.flags & QFA_F_S3_FAST)
+            k_grads_s3<KP, 3><<<L.wp2.items(), 256, 0, a.st>>>(a.B, a.Npix, a.Nh, L.ntiles, L.wp2, bh, PFT, a.SOL, BG, GG, L.bg_stride, a.accum, a.rows, a.row_stride);
         else
-            k_grads_s3<KP, 6><<<L.wp2.items(), 256, 0, st>>>(B, Npix, Nh, L.ntiles, L.wp2, bh, PFT, SOL, BG, GG, L.bg_stride, accum, slab, slab_stride);
+            k_grads_s3<KP, 6><<<L.wp2.items(), 256, 0, a.st>>>(a.B, a.Npix, a.Nh, L.ntiles, L.wp2, bh, PFT, a.SOL, BG, GG, L.bg_stride, a.accum, a.rows, a.row_stride);
     }
 }
 
 // The training step: plan, preparations, pass 1, solve, NLL sum, pass 2, fixed-order reduction.  The stage events 0..4 stand in
 // front of the preparations, pass 1, the segment sum, pass 2, and behind everything.
 template <int KP>
-int run_nll_grad(const qfa_params_t &p, const qfa_batch_t &b, const qfa_tau_t &tau, int B, int Npix, int Nb, int Nh,
-                 float *nll, float *accum, float *ws, hipStream_t st, void *const *events, void *slabv, unsigned flags) {
-    const Layout L = make_layout_t<KP>(B, Npix);
-    const StepPlan P = plan_step(L, B, Npix, Nb, Nh, flags, slabv != nullptr);
+int run_nll_grad(const BatchCall &c, float *nll, float *accum, void *const *events, void *slabv) {
+    const Layout L = make_layout_t<KP>(c.B, c.Npix);
+    const StepPlan P = plan_step(L, c, slabv != nullptr);
     if (P.err == 0) {
-        float *PFT = ws + L.oPFT, *MOM = ws + L.oMOM, *SOL = ws + L.oSOL, *NBL = ws + L.oNBL;
+        float *ws = c.ws;
+        const float *PFT = ws + L.oPFT;
         float *nllbuf = nll ? nll : ws + L.oNLL;
         unsigned char *P2 = reinterpret_cast<unsigned char *>(ws + L.oPGX), *PST = reinterpret_cast<unsigned char *>(ws + L.oPST);
         // the rows of the fixed-order reducer and their scalar records (NULL: pass 2 adds to the packed buffer with atomics)
         float *rows = P.rows_in_ws ? ws + L.oISLAB : reinterpret_cast<float *>(slabv);
         double *rowsS = rows ? reinterpret_cast<double *>(reinterpret_cast<char *>(rows) + P.D.oS) : nullptr;
-        const size_t accS = det_rows_floats(Npix, Nb, Nh), n_acc = accS + 8;
+        const size_t accS = det_rows_floats(c.Npix, c.Nb, c.Nh), n_acc = accS + 8;
         double *red = reinterpret_cast<double *>(ws + L.oRED);
-        unsigned *ticket = reinterpret_cast<unsigned *>(red + 2 * NRED);
+        unsigned *ticket = ws_ticket(c, L);
         Scal64 *sc64 = reinterpret_cast<Scal64 *>(ticket + 2);      // (zeroed by k_solve, like the ticket)
         // QFA_F_EXACT_GRAD: k_solve forms Z = -C^-1, p = y; pass 2 sums the exact tau0 / c0 / beta terms; the buffer's slot 6
         // counts the spectra of such launches (k_reduce_nll, or the solve's last block), and k_finalize* read the mode there
-        const int exact = (flags & QFA_F_EXACT_GRAD) ? 1 : 0;
-        const EventMarks mark{events, st};
+        const int exact = (c.flags & QFA_F_EXACT_GRAD) ? 1 : 0;
+        const EventMarks mark{events, c.st};
         mark(0);
         ZTables zt{nullptr, nullptr};
         if (P.prep_step) {
             // ONE launch builds the two images and the per-spectrum factors, zeroes accum and the solve's arrival counter ticket[1]
-            if (has_zfac(b, Nb)) zt.ZS = reinterpret_cast<float4 *>(ws + L.oZS);
-            qfa_prep_step_launch(KP, P.pass2 == Pass2::PIXRES, p, b, tau, B, Npix, Nb, Nh, L.ntiles32,
-                                 reinterpret_cast<unsigned char *>(ws + L.oPFX), P2, zt.ZS ? ws + L.oZS : nullptr,
-                                 (flags & QFA_F_ZERO_ACCUM) ? accum : nullptr, n_acc, st, ticket + 1);
+            float4 *ZS = has_zfac(c) ? reinterpret_cast<float4 *>(ws + L.oZS) : nullptr;
+            zt.ZS = ZS;
+            qfa_prep_step_launch(KP, P.pass2 == Pass2::PIXRES, c, L.ntiles32, reinterpret_cast<unsigned char *>(ws + L.oPFX), P2, ZS,
+                                 (c.flags & QFA_F_ZERO_ACCUM) ? accum : nullptr, n_acc, ticket + 1);
         } else {
-            if (flags & QFA_F_ZERO_ACCUM) (void)hipMemsetAsync(accum, 0, n_acc * sizeof(float), st);
-            zt = launch_zfac(p, b, tau, B, Nb, L, ws, st);
-            launch_prep_pft<KP>(p, zt.ZP, Npix, Nb, Nh, L, PFT, st);
+            if (c.flags & QFA_F_ZERO_ACCUM) (void)hipMemsetAsync(accum, 0, n_acc * sizeof(float), c.st);
+            zt = launch_zfac(c, L);
+            launch_prep_pft<KP>(c, zt.ZP, L);
         }
         mark(1);
-        launch_moments<KP, false>(p, b, tau, nullptr, B, Npix, Nb, Nh, L, zt, ws, st, !P.prep_step, exact != 0);
+        launch_moments<KP, false>(c, nullptr, L, zt, !P.prep_step, exact != 0);
         mark(2);
-        sum_segments<KP>(MOM, L, B, st);
-        switch (P.solve) {
-            case Solve::RECORD:
-                k_solve<KP, false><<<solve_blocks<KP>(B), 256, 0, st>>>(MOM, SOL, nllbuf, NBL, B, Nh, nullptr, nullptr, ticket, nullptr, nullptr, exact);
-                break;
-            case Solve::STATE:
-                if constexpr (KP <= 16)
-                    k_solve<KP, false, true><<<solve_blocks<KP>(B), 256, 0, st>>>(MOM, SOL, nllbuf, NBL, B, Nh, nullptr, nullptr, ticket, PST, nullptr, exact);
-                break;
-            case Solve::NLLRED:
-                if constexpr (KP <= 16)
-                    k_solve<KP, false, false, true><<<solve_blocks<KP>(B), 256, 0, st>>>(MOM, SOL, nllbuf, NBL, B, Nh, nullptr, nullptr, ticket, nullptr, accum + accS, exact);
-                break;
-        }
-        if (P.nred) k_reduce_nll<<<P.nred, 256, 0, st>>>(nllbuf, NBL, B, accum + accS, red, ticket, exact);
+        sum_segments<KP>(c, L);
+        launch_solve<KP>(P.solve, c, L, nllbuf, exact, accum + accS);
+        if (P.nred) k_reduce_nll<<<P.nred, 256, 0, c.st>>>(nllbuf, ws + L.oNBL, c.B, accum + accS, red, ticket, exact);
         mark(3);
-        const float *ZS = reinterpret_cast<const float *>(zt.ZS);
+        const Pass2Call a{c, ws + L.oSOL, zt.ZS, accum, rows, rowsS, (int)P.D.stride, sc64, exact};
         switch (P.pass2) {
             case Pass2::F32:
-                if constexpr (KP <= 16)
-                    launch_grads_f32<KP>(p, b, tau, B, Npix, Nb, Nh, L, zt.ZS, PFT, SOL, accum, rows, rowsS, (int)P.D.stride, sc64, exact, st);
+                if constexpr (KP <= 16) launch_grads_f32<KP>(a, L, PFT);
                 break;
-            case Pass2::XDL:
-                qfa_gx_launch(KP, p, b, tau, B, Npix, Nb, Nh, L.ntiles32, L.wp2x, P2, SOL, ZS, accum, rows, rowsS, (int)P.D.stride, sc64, flags, st);
-                break;
-            case Pass2::PIXRES:
-                qfa_gt_launch(KP, p, b, tau, B, Npix, Nb, Nh, P.max_ranges, P2, PST, ZS, accum, rows, rowsS, (int)P.D.stride, sc64, exact, st);
-                break;
+            case Pass2::XDL: qfa_gx_launch(KP, a, L.ntiles32, L.wp2x, P2); break;
+            case Pass2::PIXRES: qfa_gt_launch(KP, a, P.max_ranges, P2, PST); break;
             case Pass2::S12:
-                if constexpr (KP > 16)
-                    launch_s12_s3<KP>(p, b, tau, B, Npix, Nb, Nh, L, zt, ws, accum, rows, rowsS, (int)P.D.stride, sc64, exact, (flags & QFA_F_S3_FAST) != 0, st);
+                if constexpr (KP > 16) launch_s12_s3<KP>(a, L, zt.ZP, PFT);
                 break;
         }
-        if (P.rows) launch_reduce_slab(rows, P.D, P.rows, P.itemwaves, accum, st);
+        if (P.rows) launch_reduce_slab(rows, P.D, P.rows, P.itemwaves, accum, c.st);
         mark(4);
     }
-    return P.err ? P.err : hip_status(st, flags);
+    return P.err ? P.err : hip_status(c.st, c.flags);
 }
 
 template <int KP>
-int run_predict(const qfa_params_t &p, const float *mu, const qfa_batch_t &b, const qfa_tau_t &tau, int B, int Npix,
-                int Nb, int Nh, float *ll, float *hmean, float *hcov, float *cont, float *unc, float *ws,
-                hipStream_t st, void *const *events, unsigned flags) {
-    const Layout L = make_layout_t<KP>(B, Npix);
-    float *PFT = ws + L.oPFT, *MOM = ws + L.oMOM, *SOL = ws + L.oSOL;
-    const EventMarks mark{events, st};
-    const bool writer_xdl = !(flags & QFA_F_PREDICT_F32);        // (the float32-MFMA writer: A/B timing, cross-check)
+int run_predict(const BatchCall &c, const float *mu, float *ll, float *hmean, float *hcov, float *cont, float *unc, void *const *events) {
+    const Layout L = make_layout_t<KP>(c.B, c.Npix);
+    const float *PFT = c.ws + L.oPFT, *SOL = c.ws + L.oSOL;
+    const EventMarks mark{events, c.st};
+    const bool writer_xdl = !(c.flags & QFA_F_PREDICT_F32);        // (the float32-MFMA writer: A/B timing, cross-check)
     mark(0);
-    const ZTables zt = launch_zfac(p, b, tau, B, Nb, L, ws, st);
-    if (!writer_xdl) launch_prep_pft<KP>(p, nullptr, Npix, Nb, Nh, L, PFT, st);      // (k_predict_out)
-    launch_moments<KP, true>(p, b, tau, mu, B, Npix, Nb, Nh, L, zt, ws, st);
+    const ZTables zt = launch_zfac(c, L);
+    if (!writer_xdl) launch_prep_pft<KP>(c, nullptr, L);      // (k_predict_out)
+    launch_moments<KP, true>(c, mu, L, zt);
     mark(1);
-    sum_segments<KP>(MOM, L, B, st);
-    k_solve<KP, true><<<solve_blocks<KP>(B), 256, 0, st>>>(MOM, SOL, ll, nullptr, B, Nh, hmean, hcov);
+    sum_segments<KP>(c, L);
+    launch_solve<KP>(Solve::PREDICT, c, L, ll, 0, nullptr, hmean, hcov);
     mark(2);
     if constexpr (KP > 16) {
         if (writer_xdl) {              // the image of k_s12_x with mu in the place of Psi (qfa_s12_x.h)
-            unsigned char *IMG = reinterpret_cast<unsigned char *>(ws + L.oPGX);
-            k_prep_s12<KP><<<L.ntiles32, 256, 0, st>>>(p.F, mu, p.omega, nullptr, Npix, Nb, Nh, IMG);
-            k_predict_x32<KP><<<L.wp2x.items(), 256, 0, st>>>(B, Npix, L.ntiles32, L.wp2x, IMG, SOL, cont, unc);
+            unsigned char *IMG = reinterpret_cast<unsigned char *>(c.ws + L.oPGX);
+            k_prep_s12<KP><<<L.ntiles32, 256, 0, c.st>>>(c.p.F, mu, c.p.omega, nullptr, c.Npix, c.Nb, c.Nh, IMG);
+            k_predict_x32<KP><<<L.wp2x.items(), 256, 0, c.st>>>(c.B, c.Npix, L.ntiles32, L.wp2x, IMG, SOL, cont, unc);
         }
     }
     if (writer_xdl && KP <= 16)
-        qfa_px_launch(KP, p.F, mu, B, Npix, Nh, L.ntiles32, L.wpp, reinterpret_cast<unsigned char *>(ws + L.oPXI), SOL, cont,
-                      unc, st);
+        qfa_px_launch(KP, c, mu, L.ntiles32, L.wpp, reinterpret_cast<unsigned char *>(c.ws + L.oPXI), SOL, cont, unc);
     else if (!writer_xdl)
-        k_predict_out<KP><<<(B + 63) / 64, 256, 0, st>>>(mu, B, Npix, L.ntiles, PFT, SOL, cont, unc);
+        k_predict_out<KP><<<(c.B + 63) / 64, 256, 0, c.st>>>(mu, c.B, c.Npix, L.ntiles, PFT, SOL, cont, unc);
     mark(3);
-    return hip_status(st, flags);
+    return hip_status(c.st, c.flags);
 }
 
 // The E-step of the EM update of F (qfa_em.hip): the training step's images + pass 1 + solve with the existing kernels (the
 // exact-gradient flavour: pass 1 without the T-side moments where that instantiation exists, the solve's record [y | C^-1' | ..]
 // in SOL) -- no pass 2, no continuum writer.  `nll` (B floats, or NULL = the workspace's own row) gets the per-spectrum NLL.
 template <int KP>
-int run_estep(const qfa_params_t &p, const qfa_batch_t &b, const qfa_tau_t &tau, int B, int Npix, int Nb, int Nh, float *nll,
-              float *ws, hipStream_t st, QfaEStep *out) {
-    const Layout L = make_layout_t<KP>(B, Npix);
-    float *MOM = ws + L.oMOM, *SOL = ws + L.oSOL, *NBL = ws + L.oNBL;
-    float *nllbuf = nll ? nll : ws + L.oNLL;
-    const ZTables zt = launch_zfac(p, b, tau, B, Nb, L, ws, st);
-    launch_moments<KP, false>(p, b, tau, nullptr, B, Npix, Nb, Nh, L, zt, ws, st, true, true);
-    sum_segments<KP>(MOM, L, B, st);
-    unsigned *ticket = reinterpret_cast<unsigned *>(reinterpret_cast<double *>(ws + L.oRED) + 2 * NRED);
-    k_solve<KP, false><<<solve_blocks<KP>(B), 256, 0, st>>>(MOM, SOL, nllbuf, NBL, B, Nh, nullptr, nullptr, ticket, nullptr,
-                                                                 nullptr, 1);
-    out->SOL = SOL;
+int run_estep(const BatchCall &c, float *nll, QfaEStep *out) {
+    const Layout L = make_layout_t<KP>(c.B, c.Npix);
+    float *nllbuf = nll ? nll : c.ws + L.oNLL;
+    const ZTables zt = launch_zfac(c, L);
+    launch_moments<KP, false>(c, nullptr, L, zt, true, true);
+    sum_segments<KP>(c, L);
+    launch_solve<KP>(Solve::RECORD, c, L, nllbuf, 1);
+    out->SOL = c.ws + L.oSOL;
     out->nsol = Cfg<KP>::NSOL;
     out->KP = KP;
     out->sol_ci = Cfg<KP>::SOL_CI;
     out->ZS = zt.ZS;
     out->ZP = zt.ZP;
     out->nll = nllbuf;
-    out->batch = b;
     return hip_status();
 }
 
 }  // namespace
 
 // N_h in 17..32 (defined in qfa_k32.hip)
-int qfa_k32_nll_grad(const qfa_params_t &p, const qfa_batch_t &b, const qfa_tau_t &tau, int B, int Npix, int Nb, int Nh,
-                     float *nll, float *accum, float *ws, hipStream_t st, void *const *events, void *slab, unsigned flags);
-int qfa_k32_predict(const qfa_params_t &p, const float *mu, const qfa_batch_t &b, const qfa_tau_t &tau, int B, int Npix,
-                    int Nb, int Nh, float *ll, float *hmean, float *hcov, float *cont, float *unc, float *ws,
-                    hipStream_t st, void *const *events, unsigned flags);
+int qfa_k32_nll_grad(const BatchCall &c, float *nll, float *accum, void *const *events, void *slab);
+int qfa_k32_predict(const BatchCall &c, const float *mu, float *ll, float *hmean, float *hcov, float *cont, float *unc, void *const *events);

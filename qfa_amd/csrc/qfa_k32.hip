@@ -2,18 +2,12 @@
 // in their own translation unit).
 #include "qfa_host.h"
 
-int qfa_k32_nll_grad(const qfa_params_t &p, const qfa_batch_t &b, const qfa_tau_t &tau, int B, int Npix, int Nb, int Nh,
-                     float *nll, float *accum, float *ws, hipStream_t st, void *const *events, void *slab, unsigned flags) {
-    return run_nll_grad<32>(p, b, tau, B, Npix, Nb, Nh, nll, accum, ws, st, events, slab, flags);
+int qfa_k32_nll_grad(const BatchCall &c, float *nll, float *accum, void *const *events, void *slab) {
+    return run_nll_grad<32>(c, nll, accum, events, slab);
 }
 
-int qfa_k32_estep(const qfa_params_t &p, const qfa_batch_t &b, const qfa_tau_t &tau, int B, int Npix, int Nb, int Nh, float *nll,
-                  float *ws, hipStream_t st, QfaEStep *out) {
-    return run_estep<32>(p, b, tau, B, Npix, Nb, Nh, nll, ws, st, out);
-}
+int qfa_k32_estep(const BatchCall &c, float *nll, QfaEStep *out) { return run_estep<32>(c, nll, out); }
 
-int qfa_k32_predict(const qfa_params_t &p, const float *mu, const qfa_batch_t &b, const qfa_tau_t &tau, int B, int Npix,
-                    int Nb, int Nh, float *ll, float *hmean, float *hcov, float *cont, float *unc, float *ws,
-                    hipStream_t st, void *const *events, unsigned flags) {
-    return run_predict<32>(p, mu, b, tau, B, Npix, Nb, Nh, ll, hmean, hcov, cont, unc, ws, st, events, flags);
+int qfa_k32_predict(const BatchCall &c, const float *mu, float *ll, float *hmean, float *hcov, float *cont, float *unc, void *const *events) {
+    return run_predict<32>(c, mu, ll, hmean, hcov, cont, unc, events);
 }

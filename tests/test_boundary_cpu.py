@@ -55,6 +55,48 @@ def test_host_only_entry_points():
     assert h.qfa_adam_clip_f32(None, None, None, None, None, 4, 0, 0, 0, 0, 0, 0, 0, 0, None) == -1
 
 
+def test_step_entry_points_agree_on_invalid_arguments():
+    """The four qfa_nll_grad* and the three qfa_predict* entry points are one function behind different argument lists: the same
+    invalid arguments give the same QFA_E_* code from each, and the order of the checks (pointers, shape, workspace, flags) decides
+    which.  Every call here returns before any launch (the pointers are never read), so no device is needed."""
+    import ctypes as C
+    from qfa_amd import _lib
+    h = _lib.lib()
+    E_NULL, E_SIZE, E_WORKSPACE, E_FLAGS = -1, -2, -3, -5
+    B, npix, nb, nh = 5, 40, 13, 8
+    fake = 0x1000                                     # stands for a device pointer
+    wsb = h.qfa_workspace_bytes(B, npix, nh)
+    assert wsb > 0
+    tau = _lib.tau_model("becker", 1)
+    batch = _lib.Batch(delta=fake, error=fake, zabs=fake, mask=fake)
+
+    def codes(params, nb_, wsb_):
+        p, b, t = C.byref(params), C.byref(batch), C.byref(tau)
+        shape = (B, npix, nb_, nh)
+        grad = (p, b, t) + shape + (fake, fake, fake, wsb_)
+        pred = (p, fake, b, t) + shape + (fake,) * 6 + (wsb_,)
+        return ([h.qfa_nll_grad_f32(*grad, None), h.qfa_nll_grad_events_f32(*grad, None, None),
+                 h.qfa_nll_grad_det_f32(*grad, None, 0, None, None), h.qfa_nll_grad_ex_f32(*grad, None, 0, 0, None, None)],
+                [h.qfa_predict_f32(*pred, None), h.qfa_predict_events_f32(*pred, None, None), h.qfa_predict_ex_f32(*pred, 0, None, None)])
+
+    good = _lib.Params(*([fake] * 6))
+    no_psi = _lib.Params(F=fake, omega=fake, tau0=fake, c0=fake, beta=fake)
+    for what, args, want in (("NULL parameter pointer", (no_psi, nb, wsb), E_NULL),
+                             ("Nb > Npix", (good, npix + 1, wsb), E_SIZE),
+                             ("workspace one byte short", (good, nb, wsb - 1), E_WORKSPACE),
+                             # the first failing check decides
+                             ("NULL parameter pointer, Nb > Npix, short workspace", (no_psi, npix + 1, wsb - 1), E_NULL),
+                             ("Nb > Npix, short workspace", (good, npix + 1, wsb - 1), E_SIZE)):
+        grad, pred = codes(*args)
+        assert grad == [want] * 4, (what, grad)
+        assert pred == [want] * 3, (what, pred)
+    # QFA_F_S3_FAST names a form that exists at N_h = 17..32 only: the step's plan refuses it in front of the first launch
+    ex = lambda flags, wsb_: h.qfa_nll_grad_ex_f32(C.byref(good), C.byref(batch), C.byref(tau), B, npix, nb, nh, fake, fake, fake,
+                                                   wsb_, None, 0, flags, None, None)
+    assert ex(_lib.F_S3_FAST, wsb) == E_FLAGS
+    assert ex(_lib.F_S3_FAST, wsb - 1) == E_WORKSPACE          # (the workspace is checked first)
+
+
 def test_python_surface_matches_reference_names():
     from qfa_amd import model, optimizer, utils
     sig = inspect.signature(model.QFA.__init__)
