@@ -279,6 +279,154 @@ def gradient_case(npix, nb, nh, B):
     return p, mu, wav, nb, _remask(full, mask, mu_a), rows
 
 
+def long_case(npix, nh, B):
+    """(p, mu, wav, nb, batch of N >= B resident rows, rows) of a case on a long pixel axis: masks with runs, without the
+    thin coverage of gradient_case -- an F element of ONE term at N_pix = 2053 is beyond its bar in the float32 oracle
+    itself (2e-1 against 2.1e-2: the bar was measured on GRADIENT_CASES), and what these cases are about is the walk"""
+    seed = 5 * npix + 17 * nh + B
+    wav, nb, nr = synthetic.wavelength_grid(npix)
+    N = B + 5
+    p, mu, full, mask, mu_a = _draw(npix, nb, nh, N, seed, wav)
+    return p, mu, wav, nb, _remask(full, mask, mu_a), _rows_of(N, B, seed)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# the N_h = 17..32 step at its walk edges (tests/test_s12_walk_edges.py, tests/test_s12_walk_edges_cpu.py)
+# ----------------------------------------------------------------------------------------------------------------------
+# (N_pix, N_b, N_h, B); N_b None: the long axis (long_case: the boundary where the grid puts it, no thin pixels).
+# N_pix = 149 = 16 k + 5: a ragged last tile of 16 and of 32 pixels; N_b = 55: the boundary inside 32-pixel tile 1.
+S12_SHORT = [(149, 55, 17, B) for B in (15, 16, 17, 33, 63, 64, 65, 129, 199)] + [(149, 55, 24, 65), (149, 55, 24, 199)] + \
+            [(149, 55, 32, B) for B in (17, 65, 129)]
+# 1029 = 33 tiles of 32 pixels (two pass-1 chains of 17 and 16 tiles, the last tile of 5 pixels)
+S12_LONG = [(1029, None, 17, 17), (1029, None, 24, 70), (1029, None, 32, 17)]
+# item lengths that the two axes above do not give on 256 compute units (s12_census; test_the_cases_reach_the_walk_edges):
+# 293 = 10 tiles of 32 pixels: items of 4, 4 and 2 tiles; 389 = 13 tiles: items of 4, 4, 4 and 1 (the ragged tile alone);
+# 69 = 5 tiles of 16 pixels with nine blocks of spectra: k_grads_s3 items of 5 tiles, block 8 starts its walk at tile 4 (the
+# smallest N_pix B at which the plan gives that kernel a rotation of 4 or more: a small batch is cut into items of <= 5 tiles)
+S12_PLAN = [(293, 110, 17, 17), (389, 150, 24, 65), (69, 23, 17, 513)]
+# B = 1: every element is ONE term, and the float32 oracle itself is beyond the single-term bars at most (N_b, N_h) -- at N_pix =
+# 149, as a fraction of the worst bar: (55, 17) 38.8, (55, 24) 1.55, (55, 32) 49.1, (55, 20) 23.1, (53, 17) 0.28, (40, 17) 0.21,
+# (64, 17) 3.6, (70, 17) 1.3, (96, 17) 0.91, (75, 24) 5.7, (100, 24) 18.5, (75, 32) 0.19; the two kept are below 0.5
+# (tests/test_s12_walk_edges_cpu.py asserts it): (60, 17) 0.16 and (100, 32) 0.09
+S12_B1 = [(149, 60, 17, 1), (149, 100, 32, 1)]
+S12_CASES = S12_SHORT + S12_LONG + S12_PLAN + S12_B1
+# deterministic accumulation only, zabs form only: 33 slab rows = the second chunk of the fixed-order reducer
+S12_DET_CASE = (149, 55, 17, 64 * 32 + 1)
+S12_FAST_CASES = [(149, 55, 24, 65), (1029, None, 32, 70)]                      # QFA_F_S3_FAST
+
+
+def s12_case(npix, nb, nh, B):
+    return gradient_case(npix, nb, nh, B) if nb is not None else long_case(npix, nh, B)
+
+
+K_MAX_SEG = 32                      # kMaxSeg (qfa_host.h)
+P1_MAX_CHAIN = 32                   # QFA_P1_MAX_CHAIN
+ROT_MUL = 2654435761                # the multiplier of the rotated tile order (qfa_s12_x.h)
+
+
+def plan_work(B, ntiles, pro, slots, spb=64, max_chain=0):
+    """(full, rem, nseg, seg_tiles): plan_work of qfa_host.h, line by line"""
+    nblk = (B + spb - 1) // spb
+    if max_chain > 0 and ntiles > max_chain:
+        nn0 = (ntiles + max_chain - 1) // max_chain
+        st = (ntiles + nn0 - 1) // nn0
+        return 0, nblk, (ntiles + st - 1) // st, st
+    best, best_cost = (0, nblk, 1, ntiles), 1e300
+    full = (nblk // slots) * slots
+    while full >= 0:
+        rem = nblk - full
+        for n in range(1, K_MAX_SEG + 1):
+            latency_bound = full == 0 and rem * n <= slots // 2
+            if n > 1 and ntiles // n < (3 if latency_bound else 8):
+                break
+            if n > 8 and not latency_bound:
+                break
+            st = (ntiles + n - 1) // n
+            nn = (ntiles + st - 1) // st
+            rounds_rem = (rem * nn + slots - 1) // slots if rem else 0           # ((long long) of the C++ double: its floor)
+            cost = float(full // slots) * (ntiles + pro) + float(rounds_rem) * (st + pro)
+            if cost < best_cost - 1e-9:
+                best_cost = cost
+                best = (full, rem, nn if rem else 1, st if rem else ntiles)
+            if not rem:
+                break
+        if full == 0:
+            break
+        full -= slots
+    return best
+
+
+def plan_items(wp, ntiles):
+    """[(blk, seg, t0, t1)] of every work item of a plan, in launch order: plan_item of qfa_common.h"""
+    full, rem, nseg, st = wp
+    out = []
+    for item in range(full + rem * nseg):
+        if item < full:
+            out.append((item, 0, 0, ntiles))
+        else:
+            j = item - full
+            seg = j // rem
+            out.append((full + j % rem, seg, seg * st, min(seg * st + st, ntiles)))
+    return out
+
+
+def rot_of(blk, n, window):
+    """first tile of the rotated walk of an item of n tiles (k_s12_x: window 4, k_grads_s3: window 32); unsigned 32-bit"""
+    return (blk * ROT_MUL) % (1 << 32) % min(n, window) if n > 0 else 0
+
+
+def s12_plans(npix, B, ncu):
+    """{"wp2x": k_s12_x's plan over 32-pixel tiles, "wp2": k_grads_s3's over 16-pixel tiles, "wp1": pass 1's} at N_h = 17..32,
+    each (plan, tiles of the axis), as make_layout_t<32> (qfa_host.h) calls plan_work"""
+    nt32, nt16 = (npix + 31) // 32, (npix + 15) // 16
+    return {"wp2x": (plan_work(B, nt32, 3, ncu), nt32), "wp2": (plan_work(B, nt16, 4, ncu), nt16),
+            "wp1": (plan_work(B, nt32, 1, ncu, 64, P1_MAX_CHAIN), nt32)}
+
+
+def s12_census(cases, ncu):
+    """what the walks of k_s12_x and k_grads_s3 meet over ``cases`` on ``ncu`` compute units"""
+    c = {"n_x": set(), "wrap_ragged": [], "rot_boundary": [], "rot_s3": set(), "inactive": set(), "nseg1": {}}
+    for case in cases:
+        npix, nb, nh, B = case
+        if nb is None:
+            nb = synthetic.wavelength_grid(npix)[1]
+        pl = s12_plans(npix, B, ncu)
+        wp, nt = pl["wp2x"]
+        for blk, seg, t0, t1 in plan_items(wp, nt):
+            n = t1 - t0
+            c["n_x"].add(n)
+            rot = rot_of(blk, n, 4)
+            # the walk starts at tile t0 + rot and wraps behind the item's last tile: the ragged last tile of the axis is walked
+            # at step n - 1 - rot and tile t0 follows it
+            if rot and t1 == nt and npix % 32:
+                c["wrap_ragged"].append((case, blk, seg, rot))
+            if rot and nb % 32 and t0 <= nb // 32 < t1:
+                c["rot_boundary"].append((case, blk, seg, rot))
+        wp, nt = pl["wp2"]
+        for blk, seg, t0, t1 in plan_items(wp, nt):
+            c["rot_s3"].add(rot_of(blk, t1 - t0, 32))
+        for blk in range((B + 63) // 64):
+            c["inactive"].add(4 - (min(64, B - 64 * blk) + 15) // 16)
+        c["nseg1"][case] = pl["wp1"][0][2]
+    return c
+
+
+def assert_s12_census(cases, ncu):
+    """the walk edges that tests/test_s12_walk_edges.py is about, reached by ``cases`` on ``ncu`` compute units; returns the census"""
+    c = s12_census(cases, ncu)
+    nx = c["n_x"]
+    # k_s12_x items of 1, 2, 3 and >= 4 tiles, the long ones odd and even (its walk is unrolled by two tiles)
+    assert {1, 2, 3} <= nx and any(n >= 4 and n % 2 for n in nx) and any(n >= 4 and n % 2 == 0 for n in nx), (ncu, sorted(nx))
+    assert c["wrap_ragged"], ncu                       # rot != 0 and the walk wraps behind the ragged last tile of the axis
+    assert {rot for _, _, _, rot in c["wrap_ragged"]} >= {1, 2, 3}, (ncu, c["wrap_ragged"])
+    assert c["rot_boundary"], ncu                      # rot != 0 in an item that holds the boundary tile
+    assert max(c["rot_s3"]) >= 4, (ncu, sorted(c["rot_s3"]))               # k_grads_s3: a rotation beyond k_s12_x's window
+    assert {0, 1, 2, 3} <= c["inactive"], (ncu, sorted(c["inactive"]))     # inactive waves of a block's last spectra
+    long_axis = [nseg for case, nseg in c["nseg1"].items() if case[0] == 1029]
+    assert len(long_axis) >= 3 and set(long_axis) == {2}, (ncu, c["nseg1"])    # pass 1 in two chains
+    return c
+
+
 def select(batch, rows):
     """the rows of a batch in batch order (what the zabs / zfac input forms are given)"""
     return {k: v[rows] for k, v in batch.items()}

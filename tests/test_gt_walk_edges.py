@@ -76,18 +76,6 @@ def dev():
     return torch.device("cuda:0")
 
 
-def long_case(npix, nh, B):
-    """(p, mu, wav, nb, batch of N >= B resident rows, rows) of a case on the long pixel axis: masks with runs, without the
-    thin coverage of E.gradient_case -- an F element of ONE term at N_pix = 2053 is beyond its bar in the float32 oracle
-    itself (2e-1 against 2.1e-2: the bar was measured on E.GRADIENT_CASES), and what these cases are about is the group count"""
-    from qfa_amd import synthetic
-    seed = 5 * npix + 17 * nh + B
-    wav, nb, nr = synthetic.wavelength_grid(npix)
-    N = B + 5
-    p, mu, full, mask, mu_a = E._draw(npix, nb, nh, N, seed, wav)
-    return p, mu, wav, nb, E._remask(full, mask, mu_a), E._rows_of(N, B, seed)
-
-
 def oracle_sums(p, b, rows):
     """one float64 pass over the spectra: what E.gradient_units gives for F, Psi, omega, and for the three scalar gradients
     (sum of the terms, sum of |terms|, number of non-zero terms)"""
@@ -116,7 +104,7 @@ def test_walk_edges_against_the_oracle_and_k_grads_x(dev, npix, nb, nh, B):
     from qfa_amd import QFA, synthetic
     from qfa_amd.resident import ResidentBatch
     from tools import parity_sections as PS
-    p, mu, wav, nb, b, rows = E.gradient_case(npix, nb, nh, B) if nb is not None else long_case(npix, nh, B)
+    p, mu, wav, nb, b, rows = E.gradient_case(npix, nb, nh, B) if nb is not None else E.long_case(npix, nh, B)
     ref, sc = oracle_sums(p, b, rows)                                          # (once per case)
     sel = E.select(b, rows)
     scale = np.maximum(np.maximum(np.abs(ref["nll"]), sel["mask"].sum(axis=1)), 1.0)
