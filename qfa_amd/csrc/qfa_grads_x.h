@@ -4,9 +4,10 @@
 //   * stage 1 ([f^T y | f^T C^-1 f], K = 16 + 136) ran as 38 v_mfma_f32_16x16x4_f32 per 16x16 outputs -- 1 216 cycles on
 //     the SIMD's float32 datapath, serialised with the VALU work of stage 2 (tools/ubench/mfma_valu.hip);
 //   * stage 3 (F-gradient contraction) ran as 102 K = 16 bf16 MFMAs: the 16x16x16 form keeps the XDL pipe at half rate.
-// Here both are six-term split-bf16 products (qfa_common.h) at the pipe's full rate:
-//   stage 1  v_mfma_f32_16x16x32_bf16: A = [y | Cinv'] of 16 spectra (static, split once per work item, 72 VGPRs),
-//            B = the tile image [F^T | pair products] (static per step, split once by prep_pgx_body), 36 MFMAs / 16 px;
+// Here both are split products (qfa_common.h) at the pipe's full rate:
+//   stage 1  v_mfma_f32_16x16x32_f16 on two float16 pieces, three products per K-step (qfa_stage1.h): A = [y | Cinv'] of
+//            16 spectra (static, split once per work item, 48 VGPRs), B = the tile image [F^T | pair products] (static
+//            per step, split once by prep_pgx_body), 18 MFMAs / 16 px;
 //   stage 3  v_mfma_f32_32x32x16_bf16: per PAIR of spectra G = F_tile (32 px x 16 a) x [Z_s | Z_s'] (16 a x 32), both
 //            static; beta is applied to G on the VALU; the gamma term is one more product with K = spectrum.
 //            48 + 6 MFMAs of 32 cycles per 32 px (was 204 x 16).
@@ -45,21 +46,16 @@
 #pragma once
 #include "qfa_common.h"
 #include "qfa_xdl_kernels.h"      // glds16a / dma_wait / lds_addr: the untracked LDS-DMA and counted-vmcnt helpers
+#include "qfa_stage1.h"           // the lane layout of role A, its image builder, operand and stage 2
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 template <int KP_>
-struct GXT {                                             // KP = 16 (N_h = 9..16) or 8 (N_h <= 8)
-    static constexpr int KP = KP_, KK2 = KP * (KP + 1) / 2;
-    static constexpr int NKS = 1 + (KK2 + 31) / 32;      // K-steps of stage 1: [y, 0 | pair products, 32 per step]: 6 / 3
-    // Round 5: stage 1 on TWO float16 pieces per operand, three products per K-step (qfa_common.h "float16 pieces");
-    // the image holds t f_a and t^2 f_a f_b, 1 / t and 1 / t^2 of a half's pixels in its parameter KiB (floats 80.., 96..)
-    static constexpr int NP = 2;                         // pieces per K-step (float16 h, m; A/B against three bf16 pieces: profiles/r5_ab_f16_small.txt)
-    static constexpr int KS_B = NP * 1024;
-    static constexpr int PAR_IT1 = 80, PAR_IT2 = 96;     // float index in a half's parameter KiB: 1 / t, 1 / t^2 of pixel 2 lo + h
-    static constexpr int S1_HALF = NKS * KS_B;           // bytes of the stage-1 image of one 16-pixel half
-    static constexpr int HALF_B = S1_HALF + 1024;        // ring slot: + float32 Psi[16], omega[16] of its pixels (19 / 10 KiB)
+struct GXT : S1Layout<KP_> {                             // KP = 16 (N_h = 9..16) or 8 (N_h <= 8)
+    using L = S1Layout<KP_>;
+    static constexpr int KP = KP_;
+    static constexpr int S1_HALF = L::NKS * L::KS_B;     // bytes of the stage-1 image of one 16-pixel half (6 / 3 K-steps)
+    static constexpr int HALF_B = S1_HALF + 1024;        // ring slot: + the parameter KiB of its pixels (19 / 10 KiB)
     static constexpr int OFF_FP = 2 * HALF_B;            // F of the tile as float32 rows [pixel 0..31][FROW] (stage 3, W form)
     static constexpr int TILE_B = OFF_FP + 3 * 1024;     // 41 / 23 KiB per 32-pixel tile in global memory
     static constexpr int NCH_HALF = HALF_B / 1024;       // one-KiB DMA pieces per half (+ 3 for the F pieces with h = 1)
@@ -67,9 +63,6 @@ struct GXT {                                             // KP = 16 (N_h = 9..16
     static constexpr int FROW = KP + 4;                  // W form: floats per pixel row of the F block (conflict-free b128 reads)
     static constexpr int NG = 4;                         // groups of 16 spectra per workgroup
     static constexpr int SPB = 16 * NG;                  // spectra per workgroup
-    static constexpr int STG_ARR = 16 * 128;             // staging: one array of one tile, [16 rows][32 px] float
-    static constexpr int STG_MASK = 3 * STG_ARR;         // mask bytes [16 rows][32 px]
-    static constexpr int STG_B = 3 * STG_ARR + 512;      // delta | sigma | zabs | mask (6.5 KiB per wave and tile)
     static constexpr int PARTF = 32 * KP;                // floats of one group's stage-3 sums of a tile: [32 px][KP b]
     // LDS (bytes), per workgroup
     static constexpr int L_IMG = 0;                                  // [2 halves][HALF_B]
@@ -80,7 +73,7 @@ struct GXT {                                             // KP = 16 (N_h = 9..16
     static constexpr int L_PSUM = L_PART + 2 * NG * PARTF * 4;       // [2][NG][4 sums][32 px] float (summed over the wave)
     static constexpr int L_SCAL = L_PSUM + 2 * NG * 512;             // [NG waves][3 sums][64 lanes] double (role A)
     static constexpr int L_STG = L_SCAL + NG * 3 * 64 * 8;           // [NG waves][2 tile parity][STG_B]
-    static constexpr int L_ZS = L_STG + NG * 2 * STG_B;              // [NG waves][16 spectra] float4: factored-z per-spectrum factors
+    static constexpr int L_ZS = L_STG + NG * 2 * L::STG_B;            // [NG waves][16 spectra] float4: factored-z per-spectrum factors
     static constexpr int L_ROWS = L_ZS + NG * 256;                   // [NG waves][16 spectra] unsigned: rows of the batch arrays (ABI v3)
     static constexpr int L_TOTAL = L_ROWS + NG * 64;
 };
@@ -89,9 +82,8 @@ static_assert(32 * GXT<16>::FROW * 4 <= 3072, "F block of the W form fits the F 
 
 // ------------------------------------------------------------------------------------------------
 // prep_pgx_body : F, Psi, omega -> the pass-2 image, one block per 32-pixel tile (a block range of k_prep_step, qfa_gx.hip).
-//   half h (h = 0, 1)  [K-step ks][piece][lane (g, lo)][8 k] bf16: B[k = 32 ks + 8 g + j][px = 2 lo + h]
-//                      ks = 0: k < KP -> F[px][k]; ks >= 1: pair q = 32 (ks - 1) + 8 g + j -> F[px][a_q] F[px][b_q]
-//                      then float32 Psi[lo], omega[lo] of the pixels 2 lo + h
+//   half h (h = 0, 1)  the stage-1 image of qfa_stage1.h: [K-step ks][piece][lane (g, lo)][8 k] float16,
+//                      then the parameter KiB of the pixels 2 lo + h
 //   stage-3 part       float32 F[px 0..31][FROW] (stage 3 in its W form)
 // ------------------------------------------------------------------------------------------------
 template <int KP>
@@ -101,71 +93,14 @@ __device__ __forceinline__ void prep_pgx_body(int bid, const float *__restrict__
     using GX = GXT<KP>;
     unsigned char *tile = PGX + (size_t)bid * GX::TILE_B;
     const int p0 = 32 * bid;
-    __shared__ float f[32][17];
-    for (int i = threadIdx.x; i < 32 * 16; i += 256) {
-        const int px = i >> 4, a = i & 15;
-        f[px][a] = (p0 + px < Npix && a < Nh) ? F[(size_t)(p0 + px) * Nh + a] : 0.f;
-    }
-    __syncthreads();
-    __shared__ float tsc[32][3];                                  // F16: the pixel's power of two t, 1 / t, 1 / t^2
-    if (threadIdx.x < 32) {
-        float mx = 0.f;
-        for (int a = 0; a < KP; ++a) mx = fmaxf(mx, fabsf(f[threadIdx.x][a]));
-        int e = 7;
-        if (mx > 0.f && mx < 3.0e38f) (void)frexpf(mx, &e);       // t f_a in [2^6, 2^7) for the largest: pairs below 2^14
-        e = e < -50 ? -50 : (e > 60 ? 60 : e);
-        tsc[threadIdx.x][0] = ldexpf(1.f, 7 - e);
-        tsc[threadIdx.x][1] = ldexpf(1.f, e - 7);
-        tsc[threadIdx.x][2] = ldexpf(1.f, 2 * (e - 7));
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < 2 * GX::NKS * 64; i += 256) {
-        const int lane = i & 63, ks = (i >> 6) % GX::NKS, h = i / (64 * GX::NKS);
-        const int lo = lane & 15, g = lane >> 4, px = 2 * lo + h;
-        const float t1 = tsc[px][0], t2 = t1 * t1;
-        float v[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int kk = 8 * g + j;
-            float x = 0.f;
-            if (ks == 0) {
-                if (kk < KP) x = f[px][kk] * t1;
-            } else {
-                const int q = 32 * (ks - 1) + kk;
-                if (q < GX::KK2) {
-                    int a = 0;
-                    while (a + 1 < KP && pair_index(a + 1, a + 1, KP) <= q) ++a;
-                    const int b = a + (q - pair_index(a, a, KP));
-                    x = f[px][a] * f[px][b] * t2;
-                }
-            }
-            v[j] = x;
-        }
-        unsigned char *dst = tile + h * GX::HALF_B + ks * GX::KS_B + lane * 16;
-        u32x4 ph, pm;
-        split8h(v, ph, pm);
-        *reinterpret_cast<u32x4 *>(dst) = ph;
-        *reinterpret_cast<u32x4 *>(dst + 1024) = pm;
-    }
-    // Psi, omega of each half's 16 pixels (+ zero padding of the KiB)
-    for (int i = threadIdx.x; i < 512; i += 256) {
-        const int h = i >> 8, j = i & 255;
-        float *po = reinterpret_cast<float *>(tile + h * GX::HALF_B + GX::S1_HALF);
-        const int px = p0 + 2 * (j & 15) + h;
-        float v = 0.f;
-        if (j < 16) v = px < Npix ? Psi[px] : 0.f;
-        else if (j < 32) v = px < Nb ? omega[px] : 0.f;
-        else if (j < 80 && ZP.on() && px < Nb) {            // factored-z form: ti | pwi | l2i of the half's pixels
-            const float4 q = ZP.at(px);
-            v = j < 48 ? q.x : (j < 64 ? q.y : q.z);
-        } else if (j >= GX::PAR_IT1 && j < GX::PAR_IT2 + 16) v = tsc[2 * (j & 15) + h][j < GX::PAR_IT2 ? 1 : 2];
-        po[j] = v;
-    }
+    __shared__ S1Tile<17> T;
+    s1_image<KP>(T, F, p0, Npix, Nh, [&](int h, int ks) { return tile + h * GX::HALF_B + ks * GX::KS_B; }, s1_no_hook);
+    s1_params<KP>(T, p0, Psi, omega, ZP, Npix, Nb, [&](int h) { return reinterpret_cast<float *>(tile + h * GX::HALF_B + GX::S1_HALF); });
     // stage 3 in its W form (role B): F of the tile as float32 rows [pixel 0..31][FROW]
     float *fr = reinterpret_cast<float *>(tile + GX::OFF_FP);
     for (int i = threadIdx.x; i < 32 * GX::FROW; i += 256) {
         const int px = i / GX::FROW, a = i % GX::FROW;
-        fr[i] = a < KP ? f[px][a] : 0.f;
+        fr[i] = a < KP ? T.f[px][a] : 0.f;
     }
 }
 
@@ -245,48 +180,10 @@ __global__ __launch_bounds__(512, 2) void k_grads_x(qfa_params_t p, qfa_batch_t 
         // ================================================================ role A: stage 1 + stage 2
         const int lo = lane & 15, g = lane >> 4;
         // A operand of stage 1: spectrum s0 + lo, k = 32 ks + 8 g + j
-        u32x4 S1h[GX::NKS], S1m[GX::NKS];
-        float is0[4] = {1.f, 1.f, 1.f, 1.f}, is1[4] = {1.f, 1.f, 1.f, 1.f};      // F16: inverse powers of two of the spectra 4 g + r (y | C^-1')
+        S1Op<KP> A;                                        // [y | C^-1'] pieces, inverse powers of two of the spectra 4 g + r
         {
             const bool v = active && (s0 + lo) < B;
-            const float *sol = SOL + (size_t)(v ? s0 + lo : 0) * C::NSOL;
-            auto value = [&](int ks, int kk) __attribute__((always_inline)) {
-                float val = 0.f;
-                if (ks == 0) {
-                    if (v && kk < KP) val = sol[kk];
-                } else {
-                    const int q = 32 * (ks - 1) + kk;
-                    if (v && q < GX::KK2) val = sol[C::SOL_CI + q];
-                }
-                return val;
-            };
-            float xs[GX::NKS][8];                         // (read once: small batches are latency-bound)
-#pragma unroll
-            for (int ks = 0; ks < GX::NKS; ++ks)
-#pragma unroll
-                for (int j = 0; j < 8; ++j) xs[ks][j] = value(ks, 8 * g + j);
-            float sc0 = 1.f, sc1 = 1.f;
-            float m0 = 0.f, m1 = 0.f;
-#pragma unroll
-            for (int ks = 0; ks < GX::NKS; ++ks)
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    if (ks == 0) m0 = fmaxf(m0, fabsf(xs[ks][j])); else m1 = fmaxf(m1, fabsf(xs[ks][j]));
-                }
-#pragma unroll
-            for (int o = 16; o <= 32; o <<= 1) { m0 = fmaxf(m0, __shfl_xor(m0, o)); m1 = fmaxf(m1, __shfl_xor(m1, o)); }
-            float i0, i1;
-            sc0 = f16_row_scale(m0, i0);
-            sc1 = f16_row_scale(m1, i1);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) { is0[r] = __shfl(i0, 4 * g + r); is1[r] = __shfl(i1, 4 * g + r); }
-#pragma unroll
-            for (int ks = 0; ks < GX::NKS; ++ks) {
-                float x[8];
-#pragma unroll
-                for (int j = 0; j < 8; ++j) x[j] = xs[ks][j] * (ks == 0 ? sc0 : sc1);
-                split8h(x, S1h[ks], S1m[ks]);
-            }
+            s1_operand<KP>(SOL + (size_t)(v ? s0 + lo : 0) * C::NSOL, v, g, A);
         }
         bool sv[4];
 #pragma unroll
@@ -338,7 +235,6 @@ __global__ __launch_bounds__(512, 2) void k_grads_x(qfa_params_t p, qfa_batch_t 
             const unsigned zpitch = zreal ? (unsigned)Nb : RS;
             const int zlen = zreal ? Nb : Npix;
             const unsigned dst = wave_uniform(lds_addr(stg + par * GX::STG_B));
-            auto slot_row = [&](int q) __attribute__((always_inline)) { return (unsigned)min(q ^ ((q >> 2) & 1), last_row); };
 #if QFA_TRACKED_LOADS
             {   // test build: ordinary loads and LDS stores for all four arrays (two rows per pass), no counted wait
                 float *sf = reinterpret_cast<float *>(stg + par * GX::STG_B);
@@ -346,7 +242,7 @@ __global__ __launch_bounds__(512, 2) void k_grads_x(qfa_params_t p, qfa_batch_t 
 #pragma unroll
                 for (int i = 0; i < 8; ++i) {
                     const int q = 2 * i + (lane >> 5), pxl = lane & 31;
-                    const unsigned R = rtab[slot_row(q)];
+                    const unsigned R = rtab[slot_row(q, last_row)];
                     const int px = 32 * tg + pxl;
                     const unsigned long long o = (unsigned long long)R * RS + (unsigned)min(px, Npix - 1);
                     sf[0 * (GX::STG_ARR / 4) + q * 32 + pxl] = bt.delta[o];
@@ -361,7 +257,7 @@ __global__ __launch_bounds__(512, 2) void k_grads_x(qfa_params_t p, qfa_batch_t 
             if (fastp) {
                 unsigned R2[2];
 #pragma unroll
-                for (int i = 0; i < 2; ++i) R2[i] = rtab[slot_row(8 * i + (lane >> 3))];
+                for (int i = 0; i < 2; ++i) R2[i] = rtab[slot_row(8 * i + (lane >> 3), last_row)];
 #pragma unroll
                 for (int i = 0; i < 2; ++i) {
                     unsigned pc = 32u * (unsigned)tg + 4u * (unsigned)(lane & 7);             // first pixel of the piece
@@ -379,7 +275,7 @@ __global__ __launch_bounds__(512, 2) void k_grads_x(qfa_params_t p, qfa_batch_t 
 #pragma unroll 1
             for (int i = 0; i < 8; ++i) {
                 const int q = 2 * i + (lane >> 5);
-                const unsigned R = rtab[slot_row(q)];
+                const unsigned R = rtab[slot_row(q, last_row)];
                 int pxl = lane & 31;
                 asm volatile("" : "+v"(pxl));
                 if (!ZF) glds4p(lane_ptr<2>(zb, (unsigned long long)R * zpitch + (unsigned)min(32 * tg + pxl, zlen - 1)), dst + 2 * GX::STG_ARR + i * 256);
@@ -395,7 +291,7 @@ __global__ __launch_bounds__(512, 2) void k_grads_x(qfa_params_t p, qfa_batch_t 
 #pragma unroll 1
             for (int i = 0; i < 8; ++i) {
                 const int q = 2 * i + (lane >> 5);
-                const unsigned R = rtab[slot_row(q)];
+                const unsigned R = rtab[slot_row(q, last_row)];
                 const int px = 32 * tg + (lane & 31);
                 mb[q * 32 + (lane & 31)] = px < Npix ? bt.mask[(unsigned long long)R * RS + (unsigned)px] : (unsigned char)0;
             }
@@ -424,11 +320,8 @@ __global__ __launch_bounds__(512, 2) void k_grads_x(qfa_params_t p, qfa_batch_t 
         // of half t inside the wave -- sched_group_barrier interleave, image requested two half-steps ahead -- was built and
         // measured in round 3: same results, 2.67 against 2.62 ms at c3: the SIMD issues about one instruction per 4.8 cycles
         // over BOTH waves, so ordering the streams inside a wave buys nothing; profiles/r3_ablation_pass2.txt.)
-        struct PixA {
-            float Psi, om, ti, pwi, l2i;
-        };
         float t_tau0 = 0.f, t_c0 = 0.f, t_beta = 0.f;
-        auto stage1A = [&](int slot, f32x4 &ofy, f32x4 &oq, PixA &pp) {
+        auto stage1A = [&](int slot, f32x4 &ofy, f32x4 &oq, S2Pix &pp) {
             const unsigned char *img = lds + GX::L_IMG + slot * GX::HALF_B;
             const unsigned char *bp = img + lane * 16;
             f32x4 afy = {0.f, 0.f, 0.f, 0.f}, aq = {0.f, 0.f, 0.f, 0.f};
@@ -444,25 +337,25 @@ __global__ __launch_bounds__(512, 2) void k_grads_x(qfa_params_t p, qfa_batch_t 
                         bq[(ks + 1) & 1][pc] = *reinterpret_cast<const u32x4 *>(bp + (ks + 1) * GX::KS_B + pc * 1024);
                 }
                 const u32x4 &bh = bq[ks & 1][0], &bm = bq[ks & 1][1];
-                if (ks == 0) afy = xdl3h(S1h[ks], S1m[ks], bh, bm, afy);
-                else aq = xdl3h(S1h[ks], S1m[ks], bh, bm, aq);
+                if (ks == 0) afy = xdl3h(A.h[ks], A.m[ks], bh, bm, afy);
+                else aq = xdl3h(A.h[ks], A.m[ks], bh, bm, aq);
             }
             const float *po = reinterpret_cast<const float *>(img + GX::S1_HALF);
-       // the powers of two back in: element r <-> spectrum 4 g + r, the lane's pixel
+            // the powers of two back in: element r <-> spectrum 4 g + r, the lane's pixel
             const float it1 = po[GX::PAR_IT1 + lo], it2 = po[GX::PAR_IT2 + lo];
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                afy[r] = (afy[r] * is0[r]) * it1;
-                aq[r] = (aq[r] * is1[r]) * it2;
+                afy[r] = (afy[r] * A.is0[r]) * it1;
+                aq[r] = (aq[r] * A.is1[r]) * it2;
             }
-            pp.Psi = po[lo]; pp.om = po[16 + lo];
+            pp.Psi = po[GX::PAR_PSI + lo]; pp.om = po[GX::PAR_OM + lo];
             pp.ti = pp.pwi = pp.l2i = 0.f;
-            if (ZF) { pp.ti = po[32 + lo]; pp.pwi = po[48 + lo]; pp.l2i = po[64 + lo]; }
+            if (ZF) { pp.ti = po[GX::PAR_TI + lo]; pp.pwi = po[GX::PAR_PWI + lo]; pp.l2i = po[GX::PAR_L2I + lo]; }
             ofy = afy;
             oq = aq;
         };
         auto stage2A = [&](auto blue_tag, int tg, int h, const SpecA &cur, int par, const f32x4 &afy, const f32x4 &aq,
-                           const PixA &pp) {
+                           const S2Pix &pp) {
             constexpr bool BLUE = decltype(blue_tag)::value;
             float *bslot = reinterpret_cast<float *>(lds + GX::L_BETA + (par * GX::NG + w) * 2048);
             float *gslot = reinterpret_cast<float *>(lds + GX::L_GAM + (par * GX::NG + w) * 32 * GX::GROW * 4);
@@ -539,18 +432,8 @@ __global__ __launch_bounds__(512, 2) void k_grads_x(qfa_params_t p, qfa_batch_t 
             // [half h][lane][4 floats], one 16-byte store each
             *reinterpret_cast<float4 *>(bslot + (h * 64 + lane) * 4) = float4{betaR[0], betaR[1], betaR[2], betaR[3]};
             *reinterpret_cast<float4 *>(gslot + (h * 64 + lane) * 4) = float4{gamR[0], gamR[1], gamR[2], gamR[3]};
-            // per-pixel sums over the wave's 16 spectra (lanes lo + 16 g'): two cross-lane adds, one store per pixel
-            // (v_permlane16_swap / v_permlane32_swap: three exchanges and three adds leave quantity g's sum over the
-            // four 16-lane rows in row g)
-            {
-                const auto s01 = __builtin_amdgcn_permlane16_swap(__float_as_uint(sA), __float_as_uint(gPsi), false, false);
-                const auto s23 = __builtin_amdgcn_permlane16_swap(__float_as_uint(gOm), __float_as_uint(cnt), false, false);
-                const float u01 = __uint_as_float(s01[0]) + __uint_as_float(s01[1]);   // rows: sA(0+1) gPsi(0+1) sA(2+3) gPsi(2+3)
-                const float u23 = __uint_as_float(s23[0]) + __uint_as_float(s23[1]);   //       gOm     cnt       gOm     cnt
-                const auto t = __builtin_amdgcn_permlane32_swap(__float_as_uint(u01), __float_as_uint(u23), false, false);
-                // t[0] rows: sA(0+1) gPsi(0+1) gOm(0+1) cnt(0+1);  t[1] rows: sA(2+3) gPsi(2+3) gOm(2+3) cnt(2+3)
-                psum[g * 32 + 2 * lo + h] = __uint_as_float(t[0]) + __uint_as_float(t[1]);
-            }
+            // per-pixel sums over the wave's 16 spectra: quantity g's sum in row g, one store per pixel
+            psum[g * 32 + 2 * lo + h] = wave_pixel_sums(sA, gPsi, gOm, cnt);
             if (BLUE && h == 1) {
                 scal[0] += (double)t_tau0;
                 scal[64] += (double)t_c0;
@@ -570,7 +453,7 @@ __global__ __launch_bounds__(512, 2) void k_grads_x(qfa_params_t p, qfa_batch_t 
         step_barrier();                      // (role B's wait in front of this barrier covers the first image half)
         SpecA cur;
         f32x4 afy = {0.f, 0.f, 0.f, 0.f}, aq = {0.f, 0.f, 0.f, 0.f};
-        PixA pxp{0.f, 0.f, 0.f, 0.f, 0.f};
+        S2Pix pxp{0.f, 0.f, 0.f, 0.f, 0.f};
         auto tileA = [&](int c, int &cnt_cur, int cnt_other) {
             const bool work = c < n && active;
             const int tg = work ? tile_of(c) : 0;

@@ -3,92 +3,39 @@
 //
 // k_predict_out (qfa_step_kernels.h) issues [f^T hmean | f^T hcov f] as 38 v_mfma_f32_16x16x4_f32 per 16 x 16 outputs:
 // 1 216 cycles of the SIMD's float32 datapath per 2 KiB written, i.e. compute-bound at 17-22 % of the HBM write rate
-// (bench.py `predict`).  Here the same contraction is the six-term split-bf16 product of qfa_grads_x.h's stage 1
-// (v_mfma_f32_16x16x32_bf16, both operands static: [hmean | hcov'] of 16 spectra in 72 / 36 VGPRs, the tile image
-// [F^T | pair products] staged by LDS-DMA): 36 / 18 MFMAs of 16 cycles per 16 x 16 outputs.
+// (bench.py `predict`).  Here the same contraction is stage 1 of qfa_stage1.h (three v_mfma_f32_16x16x32_f16 per K-step on
+// two float16 pieces, both operands static: [hmean | hcov'] of 16 spectra in 48 / 24 VGPRs, the tile image
+// [F^T | pair products] staged by LDS-DMA): 18 / 9 MFMAs per 16 x 16 outputs.
 //   lane (lo = lane & 15, g = lane >> 4) owns pixels 32 t + 2 lo + h (h = 0, 1) of the spectra s0 + 4 g + r: one 8-byte
 //   store per spectrum row and array, 128 contiguous bytes per row and wave instruction.  A wave serves SPW groups of 16
 //   spectra (template argument; the work plan's blocks are 64 SPW spectra, qfa_host.h).
 #pragma once
 #include "qfa_common.h"
 #include "qfa_xdl_kernels.h"
+#include "qfa_stage1.h"
 
 template <int KP>
-struct PX {
-    static constexpr int KK2 = KP * (KP + 1) / 2;
-    static constexpr int NKS = 1 + (KK2 + 31) / 32;          // K-steps: [hmean, 0 | pair products]; 3 at KP = 8, 6 at 16
-    // Round 5: both operands as TWO float16 pieces, three products per K-step (qfa_common.h "float16 pieces").
-    // The image holds t f_a and t^2 f_a f_b with t the pixel's power of two; 1 / t and 1 / t^2 sit as float32 in K-step 0's
-    // h piece, lanes g = 3 (K slots 24..31: they meet the zeros behind hmean).  [hmean] and [hcov'] of a spectrum get powers
-    // of two of their own where the kernel builds its A operand.
-    static constexpr int NP = 2;                   // pieces per K-step (float16 h, m; A/B against three bf16 pieces: profiles/r5_ab_f16_writer.txt)
-    static constexpr int KS_B = NP * 1024;
+struct PX : S1Layout<KP> {
+    using L = S1Layout<KP>;
+    // No parameter KiB here: 1 / t and 1 / t^2 of a pixel sit as float32 in K-step 0's h piece, lanes g = 3 (K slots 24..31:
+    // they meet the zeros behind hmean).
     static_assert(KP <= 24, "the scales live in K slots 24..31 of K-step 0");
-    static constexpr int S1_HALF = NKS * KS_B;               // bytes of one 16-pixel half: [K-step][piece][lane][8 k]
+    static constexpr int S1_HALF = L::NKS * L::KS_B;         // bytes of one 16-pixel half: [K-step][piece][lane][8 k]
     static constexpr int TILE_B = 2 * S1_HALF;               // per 32-pixel tile
     static constexpr int NCHUNK = TILE_B / 1024;
 };
 
-// image of one 32-pixel tile per block: B[k = 32 ks + 8 g + j][px = 2 lo + h] as three bf16 pieces
+// image of one 32-pixel tile per block (s1_image), the pixel's scales in their slot
 template <int KP>
 __global__ __launch_bounds__(256) void k_prep_px(const float *__restrict__ F, int Npix, int Nh,
                                                  unsigned char *__restrict__ PXI) {
     using X = PX<KP>;
     unsigned char *tile = PXI + (size_t)blockIdx.x * X::TILE_B;
-    const int p0 = 32 * blockIdx.x;
-    __shared__ float f[32][KP + 1];
-    for (int i = threadIdx.x; i < 32 * KP; i += 256) {
-        const int px = i / KP, a = i % KP;
-        f[px][a] = (p0 + px < Npix && a < Nh) ? F[(size_t)(p0 + px) * Nh + a] : 0.f;
-    }
-    __syncthreads();
-    __shared__ float tsc[32][3];                                  // F16: the pixel's power of two t, 1 / t, 1 / t^2
-    if (threadIdx.x < 32) {
-        float mx = 0.f;
-        for (int a = 0; a < KP; ++a) mx = fmaxf(mx, fabsf(f[threadIdx.x][a]));
-        int e = 7;
-        if (mx > 0.f && mx < 3.0e38f) (void)frexpf(mx, &e);       // t f_a in [2^6, 2^7) for the largest: pairs below 2^14
-        e = e < -50 ? -50 : (e > 60 ? 60 : e);
-        tsc[threadIdx.x][0] = ldexpf(1.f, 7 - e);
-        tsc[threadIdx.x][1] = ldexpf(1.f, e - 7);
-        tsc[threadIdx.x][2] = ldexpf(1.f, 2 * (e - 7));
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < 2 * X::NKS * 64; i += 256) {
-        const int lane = i & 63, ks = (i >> 6) % X::NKS, h = i / (64 * X::NKS);
-        const int lo = lane & 15, g = lane >> 4, px = 2 * lo + h;
-        const float t1 = tsc[px][0], t2 = t1 * t1;
-        float v[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int kk = 8 * g + j;
-            float x = 0.f;
-            if (ks == 0) {
-                if (kk < KP) x = f[px][kk] * t1;
-            } else {
-                const int q = 32 * (ks - 1) + kk;
-                if (q < X::KK2) {
-                    int a = 0;
-                    while (a + 1 < KP && pair_index(a + 1, a + 1, KP) <= q) ++a;
-                    const int b = a + (q - pair_index(a, a, KP));
-                    x = f[px][a] * f[px][b] * t2;
-                }
-            }
-            v[j] = x;
-        }
-        unsigned char *dst = tile + h * X::S1_HALF + ks * X::KS_B + lane * 16;
-        u32x4 ph, pm;
-        split8h(v, ph, pm);
-        if (ks == 0 && g == 3) ph = u32x4{__float_as_uint(tsc[px][1]), __float_as_uint(tsc[px][2]), 0u, 0u};
-        *reinterpret_cast<u32x4 *>(dst) = ph;
-        *reinterpret_cast<u32x4 *>(dst + 1024) = pm;
-    }
-}
-
-// cont / unc leave as non-temporal stores (never read back by this call): writer at c3 0.87 - 0.91 -> 0.82 ms, same box
-typedef float pxv2 __attribute__((ext_vector_type(2), aligned(4)));      // 4-byte aligned 8-byte store
-__device__ __forceinline__ void px_store2(float *dst, float a, float b) {
-    __builtin_nontemporal_store(pxv2{a, b}, reinterpret_cast<pxv2 *>(dst));
+    __shared__ S1Tile<KP + 1> T;
+    s1_image<KP>(T, F, 32 * blockIdx.x, Npix, Nh, [&](int h, int ks) { return tile + h * X::S1_HALF + ks * X::KS_B; },
+                 [&](int ks, int g, int px, u32x4 &ph) {
+                     if (ks == 0 && g == 3) ph = u32x4{__float_as_uint(T.tsc[px][1]), __float_as_uint(T.tsc[px][2]), 0u, 0u};
+                 });
 }
 
 // One work item = (block of 64 spectra, range of 32-pixel tiles); SOL as k_solve<KP, true> leaves it
@@ -124,55 +71,11 @@ __global__ __launch_bounds__(256, SPW == 1 ? 4 : 2) void k_predict_x(const float
     const bool active = s0 < B;
     const int lo = lane & 15, g = lane >> 4;
     // A operand: spectrum s0 + lo, k = 32 ks + 8 g + j  (SPW = 2: a second set for the spectra s0 + 16 + lo)
-    u32x4 S1h[X::NKS], S1m[X::NKS];
-    u32x4 T1h[SPW == 2 ? X::NKS : 1], T1m[SPW == 2 ? X::NKS : 1];
-    // F16: the inverse powers of two of the spectra of the lane's OUTPUT rows (4 g + r): hmean, hcov'
-    float ism[SPW][4], isq[SPW][4];
+    S1Op<KP> A[SPW];                                      // [hmean | hcov'] pieces, inverse powers of two of the OUTPUT rows 4 g + r
 #pragma unroll
     for (int grp = 0; grp < SPW; ++grp) {
         const bool v = active && (s0 + 16 * grp + lo) < B;
-        const float *sol = SOL + (size_t)(v ? s0 + 16 * grp + lo : 0) * C::NSOL;
-        auto value = [&](int ks, int j) __attribute__((always_inline)) {
-            const int kk = 8 * g + j;
-            float val = 0.f;
-            if (ks == 0) {
-                if (v && kk < KP) val = sol[kk];
-            } else {
-                const int q = 32 * (ks - 1) + kk;
-                if (v && q < X::KK2) val = sol[C::SOL_CI + q];
-            }
-            return val;
-        };
-        float xs[X::NKS][8];                              // (read once)
-#pragma unroll
-        for (int ks = 0; ks < X::NKS; ++ks)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) xs[ks][j] = value(ks, j);
-        float scm = 1.f, scq = 1.f;
-        float mm = 0.f, mq = 0.f;
-#pragma unroll
-        for (int ks = 0; ks < X::NKS; ++ks)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                if (ks == 0) mm = fmaxf(mm, fabsf(xs[ks][j])); else mq = fmaxf(mq, fabsf(xs[ks][j]));
-            }
-#pragma unroll
-        for (int o = 16; o <= 32; o <<= 1) { mm = fmaxf(mm, __shfl_xor(mm, o)); mq = fmaxf(mq, __shfl_xor(mq, o)); }
-        float im, iq;
-        scm = f16_row_scale(mm, im);
-        scq = f16_row_scale(mq, iq);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) { ism[grp][r] = __shfl(im, 4 * g + r); isq[grp][r] = __shfl(iq, 4 * g + r); }
-#pragma unroll
-        for (int ks = 0; ks < X::NKS; ++ks) {
-            float x[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) x[j] = xs[ks][j] * (ks == 0 ? scm : scq);
-            u32x4 a, b;
-            split8h(x, a, b);
-            if (grp == 0) { S1h[ks] = a; S1m[ks] = b; }
-            else { T1h[SPW == 2 ? ks : 0] = a; T1m[SPW == 2 ? ks : 0] = b; }
-        }
+        s1_operand<KP>(SOL + (size_t)(v ? s0 + 16 * grp + lo : 0) * C::NSOL, v, g, A[grp]);
     }
     // F16: the lane's pixel of half h of the tile in ring slot `img`: 1 / t, 1 / t^2 (k_prep_px)
     auto pixel_scales = [&](const unsigned char *half) __attribute__((always_inline)) {
@@ -250,14 +153,14 @@ __global__ __launch_bounds__(256, SPW == 1 ? 4 : 2) void k_predict_x(const float
             for (int ks = 0; ks < X::NKS; ++ks) {
                 const u32x4 bh = *reinterpret_cast<const u32x4 *>(bp + ks * X::KS_B),
                             bm = *reinterpret_cast<const u32x4 *>(bp + ks * X::KS_B + 1024);
-                if (ks == 0) afy = xdl3h(S1h[ks], S1m[ks], bh, bm, afy);
-                else aq = xdl3h(S1h[ks], S1m[ks], bh, bm, aq);
+                if (ks == 0) afy = xdl3h(A[0].h[ks], A[0].m[ks], bh, bm, afy);
+                else aq = xdl3h(A[0].h[ks], A[0].m[ks], bh, bm, aq);
                 __builtin_amdgcn_sched_barrier(0);           // (four waves per SIMD hide the LDS latency: one B buffer)
             }
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                afy[r] = (afy[r] * ism[0][r]) * its[0];
-                aq[r] = (aq[r] * isq[0][r]) * its[1];
+                afy[r] = (afy[r] * A[0].is0[r]) * its[0];
+                aq[r] = (aq[r] * A[0].is1[r]) * its[1];
             }
         };
         for (int c = 0; c < n; ++c) {
@@ -303,8 +206,8 @@ __global__ __launch_bounds__(256, SPW == 1 ? 4 : 2) void k_predict_x(const float
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         const size_t o = (size_t)(s0 + 4 * g + r) * Npix + px;
-                        px_store2(cont + o, co0[r], afy1[r] + m);
-                        px_store2(unc + o, un0[r], __builtin_amdgcn_sqrtf(aq1[r]));
+                        store2_nt(cont + o, co0[r], afy1[r] + m);
+                        store2_nt(unc + o, un0[r], __builtin_amdgcn_sqrtf(aq1[r]));
                     }
                     counted = true;
                 } else {
@@ -374,7 +277,7 @@ __global__ __launch_bounds__(256, SPW == 1 ? 4 : 2) void k_predict_x(const float
                 const float d0 = __int_as_float(__builtin_amdgcn_ds_bpermute(4 * (16 * g + L0), __float_as_int(slot0)));
                 const float d1 = __int_as_float(__builtin_amdgcn_ds_bpermute(4 * (16 * g + L1), __float_as_int(slot1)));
                 float *q = (arr ? unc : cont) + ((size_t)s * (size_t)Npix + (size_t)(long)P0);
-                if (fast) px_store2(q, d0, d1);
+                if (fast) store2_nt(q, d0, d1);
                 else {
                     if (s < B && P0 >= Pbeg && P0 < Pend) q[0] = d0;
                     if (s < B && P0 + 1 >= Pbeg && P0 + 1 < Pend) q[1] = d1;
@@ -420,19 +323,20 @@ __global__ __launch_bounds__(256, SPW == 1 ? 4 : 2) void k_predict_x(const float
                     }
                     const u32x4 &bh = bq[ks & 1][0], &bm = bq[ks & 1][1];
                     f32x4 &c0 = ks == 0 ? afy : aq, &c1 = ks == 0 ? afy2 : aq2;
+                    const S1Op<KP> &A0 = A[0], &A1 = A[SPW - 1];
                     if constexpr (SPW == 2) {       // two chains alternating (xdl3h's order)
-                        c0 = xdlh(S1h[ks], bm, c0); c1 = xdlh(T1h[ks], bm, c1);
-                        c0 = xdlh(S1m[ks], bh, c0); c1 = xdlh(T1m[ks], bh, c1);
-                        c0 = xdlh(S1h[ks], bh, c0); c1 = xdlh(T1h[ks], bh, c1);
-                    } else c0 = xdl3h(S1h[ks], S1m[ks], bh, bm, c0);
+                        c0 = xdlh(A0.h[ks], bm, c0); c1 = xdlh(A1.h[ks], bm, c1);
+                        c0 = xdlh(A0.m[ks], bh, c0); c1 = xdlh(A1.m[ks], bh, c1);
+                        c0 = xdlh(A0.h[ks], bh, c0); c1 = xdlh(A1.h[ks], bh, c1);
+                    } else c0 = xdl3h(A0.h[ks], A0.m[ks], bh, bm, c0);
                 }
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    afy[r] = (afy[r] * ism[0][r]) * its[0];
-                    aq[r] = (aq[r] * isq[0][r]) * its[1];
+                    afy[r] = (afy[r] * A[0].is0[r]) * its[0];
+                    aq[r] = (aq[r] * A[0].is1[r]) * its[1];
                     if (SPW == 2) {
-                        afy2[r] = (afy2[r] * ism[SPW - 1][r]) * its[0];
-                        aq2[r] = (aq2[r] * isq[SPW - 1][r]) * its[1];
+                        afy2[r] = (afy2[r] * A[SPW - 1].is0[r]) * its[0];
+                        aq2[r] = (aq2[r] * A[SPW - 1].is1[r]) * its[1];
                     }
                 }
                 const float m = mc[h];
@@ -453,15 +357,15 @@ __global__ __launch_bounds__(256, SPW == 1 ? 4 : 2) void k_predict_x(const float
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const size_t o = (size_t)(s0 + 4 * g + r) * Npix + px;
-                    px_store2(cont + o, co[0][r], co[1][r]);
-                    px_store2(unc + o, un[0][r], un[1][r]);
+                    store2_nt(cont + o, co[0][r], co[1][r]);
+                    store2_nt(unc + o, un[0][r], un[1][r]);
                 }
                 if (SPW == 2) {
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         const size_t o = (size_t)(s0 + 16 + 4 * g + r) * Npix + px;
-                        px_store2(cont + o, co2[0][r], co2[1][r]);
-                        px_store2(unc + o, un2[0][r], un2[1][r]);
+                        store2_nt(cont + o, co2[0][r], co2[1][r]);
+                        store2_nt(unc + o, un2[0][r], un2[1][r]);
                     }
                 }
                 counted = true;

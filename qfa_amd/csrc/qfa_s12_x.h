@@ -3,18 +3,19 @@
 // k_grads_x (qfa_grads_x.h) does not scale to KP = 32: its hand-over slots, staging buffers and a 110 KiB image ring
 // need 250 KiB of LDS, and stage 3 would need Z of 16 spectra for 32 columns in registers.  Pass 2 is therefore cut
 // differently there:
-//   k_s12_x      stage 1 ([f^T y | f^T C^-1' f], K = 32 + 528 as 18 K-steps of six v_mfma_f32_16x16x32_bf16) and stage 2
+//   k_s12_x      stage 1 ([f^T y | f^T C^-1' f], K = 32 + 528 as 18 K-steps of three v_mfma_f32_16x16x32_f16) and stage 2
 //                (u, diag Sigma^-1, dG, the Psi / omega / tau0 / beta / c0 sums) for every (spectrum, pixel); the per-pixel
 //                sums are flushed, beta = wD A^2 and gamma = A u go to HBM ([Bpad64][NpixPad] each);
 //   k_grads_s3   (below) stage 3 from beta / gamma, once per 16 output columns.
-// Lane layout as role A of k_grads_x: a wave = 16 spectra, lane (lo = lane & 15, g = lane >> 4) owns spectra
-// s0 + 4 g + r (r = 0..3) at the pixels 32 t + 2 lo + h of half h of tile t; the A operand of stage 1 (y, C^-1' of the
-// wave's spectra as three bf16 pieces, 216 registers) is loaded once per work item -- one wave per SIMD, 512 registers,
-// built in the N_h > 16 translation unit.  Workgroup = 4 such waves = 64 spectra, no roles.
+// Lane layout, image builder, operand and stage 2 are those of role A of k_grads_x (qfa_stage1.h): a wave = 16 spectra,
+// lane (lo = lane & 15, g = lane >> 4) owns spectra s0 + 4 g + r (r = 0..3) at the pixels 32 t + 2 lo + h of half h of
+// tile t; the A operand of stage 1 (y, C^-1' of the wave's spectra as two float16 pieces, 144 registers) is loaded once
+// per work item -- one wave per SIMD, 512 registers, built in the N_h > 16 translation unit.  Workgroup = 4 such waves =
+// 64 spectra, no roles.
 //
-// The image of a 16-pixel half (18 K-steps x 3 pieces x 1 KiB = 54 KiB) moves through LDS in two QUARTERS of 9
-// K-steps (ring of 3 x 28 KiB: a quarter + the KiB with Psi / omega of the half): a tile step is four sub-steps
-// [issue the LDS-DMA of the quarter two ahead | the 54 MFMAs of this one (+ stage 2 of the half behind its second
+// The image of a 16-pixel half (18 K-steps x 2 pieces x 1 KiB = 36 KiB) moves through LDS in two QUARTERS of 9
+// K-steps (ring of 3 x 19 KiB: a quarter + the parameter KiB of the half): a tile step is four sub-steps
+// [issue the LDS-DMA of the quarter two ahead | the 27 MFMAs of this one (+ stage 2 of the half behind its second
 // quarter) | counted wait for the next quarter | barrier].  The spectra go the way of k_grads_x: every wave streams the
 // row segments of its 16 spectra (delta, sigma, zabs, mask) into its own LDS staging buffers by LDS-DMA TWO tiles ahead
 // and copies the tile it starts on into registers.  Every request of the hot path is an asm statement, so hipcc inserts
@@ -23,28 +24,17 @@
 #pragma once
 #include "qfa_common.h"
 #include "qfa_xdl_kernels.h"
+#include "qfa_stage1.h"
 
-typedef float s12_f32x2 __attribute__((ext_vector_type(2)));
 template <int KP>
-struct S12 {
-    static constexpr int KK2 = KP * (KP + 1) / 2;
-    static constexpr int NKS = 1 + (KK2 + 31) / 32;          // 18 at KP = 32
-    static_assert(NKS % 2 == 0, "two quarters of NKS / 2 K-steps");
-    static constexpr int NKQ = NKS / 2;                        // K-steps per quarter
-    // Round 5: stage 1 on TWO float16 pieces per operand and three products per K-step (qfa_common.h "float16
-    // pieces"): 54 MFMAs per 16 spectra x 16 pixels instead of 108.  The image holds t f_a and t^2 f_a f_b (t: the pixel's power of
-    // two, 1 / t and 1 / t^2 in the half's parameter KiB, floats 80.. and 96..); [y] and [C^-1'] (the writer: [hmean], [hcov'])
-    // of a spectrum get powers of two of their own where the kernels build their A operand.
-    static constexpr int NP = 2;                               // pieces per K-step (float16 h, m; A/B against three bf16 pieces: profiles/r5_ab_f16_c5.txt)
-    static constexpr int KS_B = NP * 1024;
-    static constexpr int PAR_IT1 = 80, PAR_IT2 = 96;           // float index in a half's parameter KiB: 1 / t, 1 / t^2 of pixel 2 lo + h
-    static constexpr int Q_B = NKQ * KS_B;                     // bytes of a quarter image (18 KiB; bf16 pieces: 27)
-    static constexpr int SLOT_B = Q_B + 1024;                  // ring slot: + Psi[16], omega[16] of the half (float32, one KiB)
-    static constexpr int HALF_B = 2 * Q_B + 1024;              // global: [quarter 0 | Psi/omega KiB | quarter 1]
-    static constexpr int TILE_B = 2 * HALF_B;                  // 110 KiB per 32-pixel tile
-    static constexpr int STG_ARR = 16 * 128;                   // staging: one array of one tile, [16 rows][32 px] float
-    static constexpr int STG_MASK = 3 * STG_ARR;               // mask bytes [16 rows][32 px]
-    static constexpr int STG_B = 3 * STG_ARR + 512;            // delta | sigma | zabs | mask (6.5 KiB per wave and tile)
+struct S12 : S1Layout<KP> {
+    using L = S1Layout<KP>;
+    static_assert(L::NKS % 2 == 0, "two quarters of NKS / 2 K-steps");
+    static constexpr int NKQ = L::NKS / 2;                     // K-steps per quarter (9 of 18 at KP = 32): 27 MFMAs per 16 spectra x 16 pixels
+    static constexpr int Q_B = NKQ * L::KS_B;                  // bytes of a quarter image (18 KiB)
+    static constexpr int SLOT_B = Q_B + 1024;                  // ring slot: + the parameter KiB of the half
+    static constexpr int HALF_B = 2 * Q_B + 1024;              // global: [quarter 0 | parameter KiB | quarter 1]
+    static constexpr int TILE_B = 2 * HALF_B;                  // 74 KiB per 32-pixel tile
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -59,65 +49,94 @@ __global__ __launch_bounds__(256) void k_prep_s12(const float *__restrict__ F, c
     using X = S12<KP>;
     unsigned char *tile = IMG + (size_t)blockIdx.x * X::TILE_B;
     const int p0 = 32 * blockIdx.x;
-    __shared__ float f[32][KP + 1];
-    for (int i = threadIdx.x; i < 32 * KP; i += 256) {
-        const int px = i / KP, a = i % KP;
-        f[px][a] = (p0 + px < Npix && a < Nh) ? F[(size_t)(p0 + px) * Nh + a] : 0.f;
+    __shared__ S1Tile<KP + 1> T;
+    s1_image<KP>(T, F, p0, Npix, Nh, [&](int h, int ks) {
+        return tile + h * X::HALF_B + (ks / X::NKQ) * (X::Q_B + 1024) + (ks % X::NKQ) * X::KS_B;
+    }, s1_no_hook);
+    s1_params<KP>(T, p0, Psi, omega, zp_table(ZP), Npix, Nb, [&](int h) { return reinterpret_cast<float *>(tile + h * X::HALF_B + X::Q_B); });
+}
+
+// ------------------------------------------------------------------------------------------------
+// The quarter ring of k_s12_x and k_predict_x32: quarter u = 4 c + 2 h + j (tile c of the work item, half h, K-range j) of
+// the image goes into ring slot u % 3 two sub-steps ahead.
+// ------------------------------------------------------------------------------------------------
+// the tile order of a work item, de-phased between workgroups (a small window: the workgroups of an XCD then stream the
+// same few tiles of the image through its L2)
+struct TileWalk {
+    int t0, n, rot;
+    __device__ __forceinline__ TileWalk(int blk, int t0_, int n_)
+        : t0(t0_), n(n_), rot(n_ > 0 ? (int)(((unsigned)blk * 2654435761u) % (unsigned)min(n_, 4)) : 0) {}
+    __device__ __forceinline__ int operator()(int c) const {
+        int x = c + rot;
+        if (x >= n) x -= n;
+        return t0 + x;
     }
-    __syncthreads();
-    __shared__ float tsc[32][3];                                  // F16: the pixel's power of two t, 1 / t, 1 / t^2
-    if (threadIdx.x < 32) {
-        float mx = 0.f;
-        for (int a = 0; a < KP; ++a) mx = fmaxf(mx, fabsf(f[threadIdx.x][a]));
-        int e = 7;
-        if (mx > 0.f && mx < 3.0e38f) (void)frexpf(mx, &e);       // t f_a in [2^6, 2^7) for the largest: pairs below 2^14
-        e = e < -50 ? -50 : (e > 60 ? 60 : e);
-        tsc[threadIdx.x][0] = ldexpf(1.f, 7 - e);
-        tsc[threadIdx.x][1] = ldexpf(1.f, e - 7);
-        tsc[threadIdx.x][2] = ldexpf(1.f, 2 * (e - 7));
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < 2 * X::NKS * 64; i += 256) {
-        const int lane = i & 63, ks = (i >> 6) % X::NKS, h = i / (64 * X::NKS);
-        const int lo = lane & 15, g = lane >> 4, px = 2 * lo + h;
-        const float t1 = tsc[px][0], t2 = t1 * t1;
-        float v[8];
+};
+// LDS-DMA of quarter u of tile tg into `dst`; wave wv moves the 1-KiB pieces wv, wv + 4, ...; the quarter with j = 0 is
+// followed by the half's parameter KiB
+template <int KP>
+__device__ __forceinline__ void get_quarter(const unsigned char *__restrict__ IMG, int tg, int u, unsigned char *dst, int wv, int lane) {
+    using X = S12<KP>;
+    const int h = (u >> 1) & 1, j = u & 1;
+    const unsigned char *src = uniform_ptr(IMG + (size_t)tg * X::TILE_B + h * X::HALF_B + j * (X::Q_B + 1024));
+    constexpr int NCH = X::Q_B / 1024;
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int kk = 8 * g + j;
-            float x = 0.f;
-            if (ks == 0) {
-                if (kk < KP) x = f[px][kk] * t1;
-            } else {
-                const int q = 32 * (ks - 1) + kk;
-                if (q < X::KK2) {
-                    int a = 0;
-                    while (a + 1 < KP && pair_index(a + 1, a + 1, KP) <= q) ++a;
-                    const int b = a + (q - pair_index(a, a, KP));
-                    x = f[px][a] * f[px][b] * t2;
-                }
-            }
-            v[j] = x;
-        }
-        const int qt = ks / X::NKQ, kq = ks % X::NKQ;
-        unsigned char *dst = tile + h * X::HALF_B + qt * (X::Q_B + 1024) + kq * X::KS_B + lane * 16;
-        u32x4 ph, pm;
-        split8h(v, ph, pm);
-        *reinterpret_cast<u32x4 *>(dst) = ph;
-        *reinterpret_cast<u32x4 *>(dst + 1024) = pm;
+    for (int i = 0; i < (NCH + 1 + 3) / 4; ++i) {
+        const int ch = wv + 4 * i;
+        if (ch < NCH) glds16a(src + ch * 1024, (unsigned)lane * 16u, wave_uniform(lds_addr(dst + ch * 1024)));
+        else if (ch == NCH && j == 0)
+            glds16a(src + X::Q_B, (unsigned)lane * 16u, wave_uniform(lds_addr(dst + X::Q_B)));
     }
-    for (int i = threadIdx.x; i < 512; i += 256) {            // Psi, omega of each half's pixels (+ zero padding of the KiB)
-        const int h = i >> 8, j = i & 255;
-        float *po = reinterpret_cast<float *>(tile + h * X::HALF_B + X::Q_B);
-        const int px = p0 + 2 * (j & 15) + h;
-        float v = 0.f;
-        if (j < 16) v = px < Npix ? Psi[px] : 0.f;
-        else if (j < 32) v = px < Nb ? omega[px] : 0.f;
-        else if (j < 80 && ZP && px < Nb) {                 // factored-z form: ti | pwi | l2i of the half's pixels
-            const float4 q = ZP[px];
-            v = j < 48 ? q.x : (j < 64 ? q.y : q.z);
-        } else if (j >= X::PAR_IT1 && j < X::PAR_IT2 + 16) v = tsc[2 * (j & 15) + h][j < X::PAR_IT2 ? 1 : 2];
-        po[j] = v;
+}
+// pieces of quarter u moved by wave wv (get_quarter; piece NCH = the parameter KiB, j = 0): what the counted waits count
+template <int KP>
+__device__ __forceinline__ int cnt_q(int u, int wv) {
+    constexpr int NCHQ = S12<KP>::Q_B / 1024;
+    return (NCHQ - wv + 3) / 4 + ((NCHQ % 4 == wv && !(u & 1)) ? 1 : 0);
+}
+// The K-steps of quarter J of a half on ring slot `img`: B pieces of K-step ks + 1 are read while the three MFMAs of ks
+// run.  J = 0 starts the half: it1 / it2 = 1 / t, 1 / t^2 of the lane's pixel, and par(po) reads what else the kernel
+// takes from the parameter KiB po; J = 1 ends it with the powers of two back in (element r <-> spectrum 4 g + r).
+template <int KP, int J, class Par>
+__device__ __forceinline__ void quarter(const unsigned char *img, int lane, const S1Op<KP> &A, f32x4 &afy, f32x4 &aq, float &it1,
+                                        float &it2, Par par) {
+    using X = S12<KP>;
+    const unsigned char *bp = img + lane * 16;
+    if (J == 0) {
+        afy = f32x4{0.f, 0.f, 0.f, 0.f};
+        aq = f32x4{0.f, 0.f, 0.f, 0.f};
+        const float *po = reinterpret_cast<const float *>(img + X::Q_B);
+        par(po);
+        it1 = po[X::PAR_IT1 + (lane & 15)]; it2 = po[X::PAR_IT2 + (lane & 15)];
+    }
+    constexpr int NP = X::NP;
+    u32x4 bq[2][NP];
+#pragma unroll
+    for (int pc = 0; pc < NP; ++pc) bq[0][pc] = *reinterpret_cast<const u32x4 *>(bp + pc * 1024);
+#pragma unroll
+    for (int kq = 0; kq < X::NKQ; ++kq) {
+        if (kq + 1 < X::NKQ) {
+#pragma unroll
+            for (int pc = 0; pc < NP; ++pc)
+                bq[(kq + 1) & 1][pc] = *reinterpret_cast<const u32x4 *>(bp + (kq + 1) * X::KS_B + pc * 1024);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        const u32x4 &bh = bq[kq & 1][0], &bm = bq[kq & 1][1];
+        // (ks = NKQ J + kq is a compile-time constant per (J, kq))
+        if (J == 0) {
+            if (kq == 0) afy = xdl3h(A.h[0], A.m[0], bh, bm, afy);
+            else aq = xdl3h(A.h[kq], A.m[kq], bh, bm, aq);
+        } else {
+            aq = xdl3h(A.h[X::NKQ + kq], A.m[X::NKQ + kq], bh, bm, aq);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    if (J == 1) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            afy[r] = (afy[r] * A.is0[r]) * it1;
+            aq[r] = (aq[r] * A.is1[r]) * it2;
+        }
     }
 }
 
@@ -153,60 +172,16 @@ __global__ __launch_bounds__(256, 1) void k_s12_x(qfa_params_t p, qfa_batch_t bt
     float *accS = accum + (size_t)Npix * Nh + 3 * (size_t)Npix + Nb;
     for (int i = tid; i < 2 * 4 * 4 * 32; i += 256) (&lpsum[0][0][0][0])[i] = 0.f;      // inactive waves' rows stay 0
 
-    // A operand of stage 1: spectrum s0 + lo, k = 32 ks + 8 g + j
-    u32x4 S1h[X::NKS], S1m[X::NKS];
-    float is0[4] = {1.f, 1.f, 1.f, 1.f}, is1[4] = {1.f, 1.f, 1.f, 1.f};      // F16: inverse powers of two of the spectra 4 g + r (y | C^-1')
+    S1Op<KP> A;                                                // [y | C^-1'] pieces, inverse powers of two of the spectra 4 g + r
     {
         const bool v = active && (s0 + lo) < B;
-        const float *sol = SOL + (size_t)(v ? s0 + lo : 0) * C::NSOL;
-        auto value = [&](int ks, int kk) __attribute__((always_inline)) {
-            float val = 0.f;
-            if (ks == 0) {
-                if (v && kk < KP) val = sol[kk];
-            } else {
-                const int qq = 32 * (ks - 1) + kk;
-                if (v && qq < X::KK2) val = sol[C::SOL_CI + qq];
-            }
-            return val;
-        };
-        float sc0 = 1.f, sc1 = 1.f;                              // powers of two of the spectrum's K-step 0 values / its pair values
-        float m0 = 0.f, m1 = 0.f;
-#pragma unroll
-        for (int ks = 0; ks < X::NKS; ++ks)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const float a = fabsf(value(ks, 8 * g + j));
-                if (ks == 0) m0 = fmaxf(m0, a); else m1 = fmaxf(m1, a);
-            }
-#pragma unroll
-        for (int o = 16; o <= 32; o <<= 1) { m0 = fmaxf(m0, __shfl_xor(m0, o)); m1 = fmaxf(m1, __shfl_xor(m1, o)); }
-        float i0, i1;
-        sc0 = f16_row_scale(m0, i0);
-        sc1 = f16_row_scale(m1, i1);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) { is0[r] = __shfl(i0, 4 * g + r); is1[r] = __shfl(i1, 4 * g + r); }
-#pragma unroll
-        for (int ks = 0; ks < X::NKS; ++ks) {
-            float x[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) x[j] = value(ks, 8 * g + j) * (ks == 0 ? sc0 : sc1);
-            split8h(x, S1h[ks], S1m[ks]);
-        }
+        s1_operand<KP>(SOL + (size_t)(v ? s0 + lo : 0) * C::NSOL, v, g, A);
     }
     bool sv[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) sv[r] = active && (s0 + 4 * g + r) < B;
-    // (a small window: the workgroups of an XCD then stream the same few tiles of the image through its L2)
-    const int rot = n > 0 ? (int)(((unsigned)blk * 2654435761u) % (unsigned)min(n, 4)) : 0;
-    auto tile_of = [&](int c) {
-        int x = c + rot;
-        if (x >= n) x -= n;
-        return t0 + x;
-    };
+    const TileWalk tile_of(blk, t0, n);
 
-    struct Spec {                      // one lane's 4 spectra x 2 pixels of a tile; sigma < 0: masked
-        float d[4][2], sg[4][2], z[4][2];
-    };
     // Staging (qfa_grads_x.h): slot q of an array holds row q ^ ((q >> 2) & 1); 16-byte pieces, two instructions per
     // float array, the mask as 4-byte pieces.  Returns the requests issued: 8 (all 32 pixels inside the row and, on a blue
     // tile, inside the blue side), else 0 = "ragged: ordinary loads and LDS stores, wait for everything".
@@ -214,10 +189,9 @@ __global__ __launch_bounds__(256, 1) void k_s12_x(qfa_params_t p, qfa_batch_t bt
     // Spectrum s0 + r of the batch is row batch_row(s0 + r) of the batch arrays (ABI v3: rows / row_stride, qfa_common.h);
     // the rows of the lane's two 16-byte pieces per array stay in registers (one wave per SIMD: room to spare)
     const unsigned RS = (unsigned)bt.row_stride;                     // (elements; < 2^31: check_batch)
-    auto slot_row = [&](int q) __attribute__((always_inline)) { return (unsigned)min(q ^ ((q >> 2) & 1), last_row); };
     unsigned R2[2];
 #pragma unroll
-    for (int i = 0; i < 2; ++i) R2[i] = (unsigned)batch_row(bt, (active ? s0 : 0) + (int)slot_row(8 * i + (lane >> 3)));
+    for (int i = 0; i < 2; ++i) R2[i] = (unsigned)batch_row(bt, (active ? s0 : 0) + (int)slot_row(8 * i + (lane >> 3), last_row));
     auto stage_tile = [&](int tg, int par) -> int {
         const bool zblue = !ZF && tg < nbt;                                               // wave-uniform
         const bool fast = (32 * tg + 31 < Npix) && (!zblue || 32 * tg + 31 < Nb) && !QFA_TRACKED_LOADS;
@@ -244,7 +218,7 @@ __global__ __launch_bounds__(256, 1) void k_s12_x(qfa_params_t p, qfa_batch_t bt
 #pragma unroll 1
         for (int i = 0; i < 8; ++i) {
             const int q = 2 * i + (lane >> 5), pxl = lane & 31;
-            const unsigned long long R = batch_row(bt, (active ? s0 : 0) + (int)slot_row(q));
+            const unsigned long long R = batch_row(bt, (active ? s0 : 0) + (int)slot_row(q, last_row));
             const int px = 32 * tg + pxl;
             const unsigned long long o = R * RS + (unsigned)min(px, Npix - 1);
             sf[0 * (X::STG_ARR / 4) + q * 32 + pxl] = bt.delta[o];
@@ -254,16 +228,21 @@ __global__ __launch_bounds__(256, 1) void k_s12_x(qfa_params_t p, qfa_batch_t bt
         }
         return 0;
     };
+    // (the copy-out of k_grads_x on scalars: with its float pairs hipcc packs and contracts stage 2 below differently, and
+    // the gradients change in their last bits -- qfa_stage1.h)
+    struct Spec {                      // one lane's 4 spectra x 2 pixels of a tile; sigma < 0: masked
+        float d[4][2], sg[4][2], z[4][2];
+    };
     auto take_tile = [&](int par, Spec &cur) {
         const unsigned char *sb = lstg[wv][par] + 8 * lo;
         const unsigned char *mb = lstg[wv][par] + X::STG_MASK + 2 * lo;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int slot = 4 * g + (r ^ (g & 1));
-            const s12_f32x2 d2 = *reinterpret_cast<const s12_f32x2 *>(sb + 0 * X::STG_ARR + slot * 128);
-            const s12_f32x2 e2 = *reinterpret_cast<const s12_f32x2 *>(sb + 1 * X::STG_ARR + slot * 128);
-            s12_f32x2 z2 = {0.f, 0.f};
-            if (!ZF) z2 = *reinterpret_cast<const s12_f32x2 *>(sb + 2 * X::STG_ARR + slot * 128);
+            const f32x2 d2 = *reinterpret_cast<const f32x2 *>(sb + 0 * X::STG_ARR + slot * 128);
+            const f32x2 e2 = *reinterpret_cast<const f32x2 *>(sb + 1 * X::STG_ARR + slot * 128);
+            f32x2 z2 = {0.f, 0.f};
+            if (!ZF) z2 = *reinterpret_cast<const f32x2 *>(sb + 2 * X::STG_ARR + slot * 128);
             const unsigned mk = *reinterpret_cast<const unsigned short *>(mb + slot * 32);
             cur.d[r][0] = d2[0]; cur.d[r][1] = d2[1];
             cur.sg[r][0] = (mk & 0xffu) ? fabsf(e2[0]) : -1.f;        // (sign bit = masked; only sigma^2 is used)
@@ -271,72 +250,19 @@ __global__ __launch_bounds__(256, 1) void k_s12_x(qfa_params_t p, qfa_batch_t bt
             cur.z[r][0] = z2[0]; cur.z[r][1] = z2[1];
         }
     };
-
-    // LDS-DMA of quarter u (u = 4 c + 2 h + j: tile c, half h, K-range j) into ring slot u % RING; wave w moves the 1-KiB
-    // pieces w, w + 4, ...; the quarter with j = 0 is followed by the half's Psi / omega KiB
-    auto get_quarter = [&](int u) {
-        const int c = u >> 2, h = (u >> 1) & 1, j = u & 1;
-        const unsigned char *src = uniform_ptr(IMG + (size_t)tile_of(c) * X::TILE_B + h * X::HALF_B + j * (X::Q_B + 1024));
-        unsigned char *dst = lds[u % RING];
-        constexpr int NCH = X::Q_B / 1024;
-#pragma unroll
-        for (int i = 0; i < (NCH + 1 + 3) / 4; ++i) {
-            const int ch = wv + 4 * i;
-            if (ch < NCH) glds16a(src + ch * 1024, (unsigned)lane * 16u, wave_uniform(lds_addr(dst + ch * 1024)));
-            else if (ch == NCH && j == 0)
-                glds16a(src + X::Q_B, (unsigned)lane * 16u, wave_uniform(lds_addr(dst + X::Q_B)));
-        }
-    };
+    auto get_q = [&](int u) { get_quarter<KP>(IMG, tile_of(u >> 2), u, lds[u % RING], wv, lane); };
 
     double s_tau0 = 0.0, s_c0 = 0.0, s_beta = 0.0;
     f32x4 afy, aq;
-    float PsiH = 0.f, omH = 0.f, tiH = 0.f, pwiH = 0.f, l2iH = 0.f, it1H = 1.f, it2H = 1.f;
+    S2Pix pxp{0.f, 0.f, 0.f, 0.f, 0.f};
+    float it1H = 1.f, it2H = 1.f;
     ZFac zs[4];                                   // factored-z form: per-spectrum factors of the lane's four spectra
 #pragma unroll
     for (int r = 0; r < 4; ++r) zs[r] = zfac_load(ZS, s0 + 4 * g + r, ZF && sv[r]);
-
-    // the K-steps of quarter j of a half: B pieces of K-step ks + 1 are read while the six MFMAs of ks run
-    auto quarter = [&](auto jtag, const unsigned char *img) {
-        constexpr int j = decltype(jtag)::value;
-        const unsigned char *bp = img + lane * 16;
-        if (j == 0) {
-            afy = f32x4{0.f, 0.f, 0.f, 0.f};
-            aq = f32x4{0.f, 0.f, 0.f, 0.f};
-            const float *po = reinterpret_cast<const float *>(img + X::Q_B);
-            PsiH = po[lo];
-            omH = po[16 + lo];
-            it1H = po[X::PAR_IT1 + lo]; it2H = po[X::PAR_IT2 + lo];
-            if (ZF) { tiH = po[32 + lo]; pwiH = po[48 + lo]; l2iH = po[64 + lo]; }
-        }
-        constexpr int NP = X::NP;
-        u32x4 bq[2][NP];
-#pragma unroll
-        for (int pc = 0; pc < NP; ++pc) bq[0][pc] = *reinterpret_cast<const u32x4 *>(bp + pc * 1024);
-#pragma unroll
-        for (int kq = 0; kq < X::NKQ; ++kq) {
-            if (kq + 1 < X::NKQ) {
-#pragma unroll
-                for (int pc = 0; pc < NP; ++pc)
-                    bq[(kq + 1) & 1][pc] = *reinterpret_cast<const u32x4 *>(bp + (kq + 1) * X::KS_B + pc * 1024);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            const u32x4 &bh = bq[kq & 1][0], &bm = bq[kq & 1][1];
-            // (ks = NKQ j + kq is a compile-time constant per (j, kq): j is passed as a literal below)
-            if (j == 0) {
-                if (kq == 0) afy = xdl3h(S1h[0], S1m[0], bh, bm, afy);
-                else aq = xdl3h(S1h[kq], S1m[kq], bh, bm, aq);
-            } else {
-                aq = xdl3h(S1h[X::NKQ + kq], S1m[X::NKQ + kq], bh, bm, aq);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        if (j == 1) {                      // the powers of two back in: element r <-> spectrum 4 g + r, the lane's pixel
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                afy[r] = (afy[r] * is0[r]) * it1H;
-                aq[r] = (aq[r] * is1[r]) * it2H;
-            }
-        }
+    auto params = [&](const float *po) {          // the lane's pixel of a half, from its parameter KiB
+        pxp.Psi = po[X::PAR_PSI + lo];
+        pxp.om = po[X::PAR_OM + lo];
+        if (ZF) { pxp.ti = po[X::PAR_TI + lo]; pxp.pwi = po[X::PAR_PWI + lo]; pxp.l2i = po[X::PAR_L2I + lo]; }
     };
 
     // stage 2 of the lane's four elements of half h of tile tg (as role A of k_grads_x), beta / gamma to HBM, per-pixel
@@ -347,7 +273,7 @@ __global__ __launch_bounds__(256, 1) void k_s12_x(qfa_params_t p, qfa_batch_t bt
         const int px = 32 * tg + 2 * lo + h;
         const bool inb = px < Npix;
         const bool blue = px < Nb;
-        const float Psi = PsiH, om = omH;
+        const float Psi = pxp.Psi, om = pxp.om;
         float gPsi = 0.f, gOm = 0.f, sA = 0.f, cnt = 0.f;
         float betaR[4], gamR[4];
 #pragma unroll
@@ -358,9 +284,9 @@ __global__ __launch_bounds__(256, 1) void k_s12_x(qfa_params_t p, qfa_batch_t bt
             if (BLUE) {
                 float l2, pw, Ab, re, ex;
                 if (ZF) {                                                                         // qfa_common.h, ZFac
-                    l2 = zs[r].l2 + l2iH;
-                    pw = zs[r].pw * pwiH;
-                    Ab = fast_exp2(fmaf(zs[r].ts, tiH, k.offp));                                  // QFA/model.py:125
+                    l2 = zs[r].l2 + pxp.l2i;
+                    pw = zs[r].pw * pxp.pwi;
+                    Ab = fast_exp2(fmaf(zs[r].ts, pxp.ti, k.offp));                               // QFA/model.py:125
                     ex = fast_exp2(k.k1 * pw);
                     re = k.omc0 - ex;                                                             // QFA/utils.py:91
                 } else {
@@ -419,15 +345,8 @@ __global__ __launch_bounds__(256, 1) void k_s12_x(qfa_params_t p, qfa_batch_t bt
                 GG[o] = gamR[r];
             }
         }
-        // per-pixel sums over the wave's 16 spectra: quantity q ends up in the 16-lane row q (qfa_grads_x.h)
-        {
-            const auto s01 = __builtin_amdgcn_permlane16_swap(__float_as_uint(sA), __float_as_uint(gPsi), false, false);
-            const auto s23 = __builtin_amdgcn_permlane16_swap(__float_as_uint(gOm), __float_as_uint(cnt), false, false);
-            const float u01 = __uint_as_float(s01[0]) + __uint_as_float(s01[1]);
-            const float u23 = __uint_as_float(s23[0]) + __uint_as_float(s23[1]);
-            const auto t = __builtin_amdgcn_permlane32_swap(__float_as_uint(u01), __float_as_uint(u23), false, false);
-            lpsum[par][wv][g][2 * lo + h] = __uint_as_float(t[0]) + __uint_as_float(t[1]);
-        }
+        // per-pixel sums over the wave's 16 spectra: quantity q ends up in the 16-lane row q
+        lpsum[par][wv][g][2 * lo + h] = wave_pixel_sums(sA, gPsi, gOm, cnt);
         if (BLUE && h == 1) {
             s_tau0 += (double)t_tau0;
             s_c0 += (double)t_c0;
@@ -462,13 +381,10 @@ __global__ __launch_bounds__(256, 1) void k_s12_x(qfa_params_t p, qfa_batch_t bt
             stag_a = stage_tile(tile_of(0), 0);
             if (n > 1) stag_b = stage_tile(tile_of(1), 1);
         }
-        get_quarter(0);
-        if (4 * n > 1) get_quarter(1);
+        get_q(0);
+        if (4 * n > 1) get_q(1);
         dma_wait<0>();
         step_barrier();
-        // pieces of quarter u moved by this wave (get_quarter: wave w moves the pieces w, w + 4, ...; piece NCH = the parameter KiB, j = 0)
-        constexpr int NCHQ = X::Q_B / 1024;
-        auto cnt_q = [&](int u) { return (NCHQ - wv + 3) / 4 + ((NCHQ % 4 == wv && !(u & 1)) ? 1 : 0); };
         int rest_prev = 0;                          // requests of the previous sub-step behind its image DMA
         Spec cur;
         auto tile_step = [&](int c, int &stag_cur) {
@@ -479,7 +395,7 @@ __global__ __launch_bounds__(256, 1) void k_s12_x(qfa_params_t p, qfa_batch_t bt
                 for (int j = 0; j < 2; ++j) {
                     const int u = 4 * c + 2 * h + j;
                     const bool more = u + 2 < 4 * n;
-                    if (more) get_quarter(u + 2);                 // (slot of quarter u - 1: free behind the barrier)
+                    if (more) get_q(u + 2);                       // (slot of quarter u - 1: free behind the barrier)
                     int rest = 0;
                     if (h == 0 && j == 0) {
                         if (c >= 1) {
@@ -498,8 +414,8 @@ __global__ __launch_bounds__(256, 1) void k_s12_x(qfa_params_t p, qfa_batch_t bt
                         }
                     }
                     if (active) {
-                        if (j == 0) quarter(std::integral_constant<int, 0>{}, lds[u % RING]);
-                        else quarter(std::integral_constant<int, 1>{}, lds[u % RING]);
+                        if (j == 0) quarter<KP, 0>(lds[u % RING], lane, A, afy, aq, it1H, it2H, params);
+                        else quarter<KP, 1>(lds[u % RING], lane, A, afy, aq, it1H, it2H, params);
                         if (j == 1) {
                             if (tg < nbt) stage2(std::true_type{}, tg, h, cur, c & 1);
                             else stage2(std::false_type{}, tg, h, cur, c & 1);
@@ -509,7 +425,7 @@ __global__ __launch_bounds__(256, 1) void k_s12_x(qfa_params_t p, qfa_batch_t bt
                     // the DMA of quarter u + 1 (issued at the start of the previous sub-step) must have landed; behind it in
                     // the queue: the rest of the previous sub-step, this sub-step's DMA and its rest
                     if (!more || drain) dma_wait<0>();
-                    else dma_wait_n(rest_prev + cnt_q(u + 2) + rest);
+                    else dma_wait_n(rest_prev + cnt_q<KP>(u + 2, wv) + rest);
                     if (drain && (h == 1 && j == 1)) drain = false;       // (everything has been waited for since)
                     rest_prev = rest;
                     step_barrier();
@@ -547,10 +463,6 @@ __global__ __launch_bounds__(256, 1) void k_s12_x(qfa_params_t p, qfa_batch_t bt
 // Lane (lo, g) owns the pixels 32 t + 2 lo + h of the spectra s0 + 4 g + r: one 8-byte store per spectrum row and
 // array behind the second half (128 contiguous bytes per row and wave instruction), eight requests per tile.
 // ------------------------------------------------------------------------------------------------
-struct __attribute__((packed, aligned(4))) s12_pair { float v[2]; };       // 4-byte aligned 8-byte store
-typedef float s12_v2 __attribute__((ext_vector_type(2), aligned(4)));
-// (non-temporal, like k_predict_x's: the prediction outputs are not read back by the call)
-__device__ __forceinline__ void s12_store2(float *dst, float a, float b) { __builtin_nontemporal_store(s12_v2{a, b}, reinterpret_cast<s12_v2 *>(dst)); }
 template <int KP>
 __global__ __launch_bounds__(256, 1) void k_predict_x32(int B, int Npix, int ntiles, WorkPlan wp,
                                                         const unsigned char *__restrict__ IMG,
@@ -569,114 +481,24 @@ __global__ __launch_bounds__(256, 1) void k_predict_x32(int B, int Npix, int nti
     const int n = t1 - t0;
     if (n <= 0) return;
 
-    u32x4 S1h[X::NKS], S1m[X::NKS];   // A operand: spectrum s0 + lo, k = 32 ks + 8 g + j
-    float is0[4] = {1.f, 1.f, 1.f, 1.f}, is1[4] = {1.f, 1.f, 1.f, 1.f};      // F16: inverse powers of two of the spectra 4 g + r (hmean | hcov')
+    S1Op<KP> A;                                                // [hmean | hcov'] pieces, inverse powers of two of the spectra 4 g + r
     {
         const bool v = active && (s0 + lo) < B;
-        const float *sol = SOL + (size_t)(v ? s0 + lo : 0) * C::NSOL;
-        auto value = [&](int ks, int kk) __attribute__((always_inline)) {
-            float val = 0.f;
-            if (ks == 0) {
-                if (v && kk < KP) val = sol[kk];
-            } else {
-                const int qq = 32 * (ks - 1) + kk;
-                if (v && qq < X::KK2) val = sol[C::SOL_CI + qq];
-            }
-            return val;
-        };
-        float sc0 = 1.f, sc1 = 1.f;                              // powers of two of the spectrum's K-step 0 values / its pair values
-        float m0 = 0.f, m1 = 0.f;
-#pragma unroll
-        for (int ks = 0; ks < X::NKS; ++ks)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const float a = fabsf(value(ks, 8 * g + j));
-                if (ks == 0) m0 = fmaxf(m0, a); else m1 = fmaxf(m1, a);
-            }
-#pragma unroll
-        for (int o = 16; o <= 32; o <<= 1) { m0 = fmaxf(m0, __shfl_xor(m0, o)); m1 = fmaxf(m1, __shfl_xor(m1, o)); }
-        float i0, i1;
-        sc0 = f16_row_scale(m0, i0);
-        sc1 = f16_row_scale(m1, i1);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) { is0[r] = __shfl(i0, 4 * g + r); is1[r] = __shfl(i1, 4 * g + r); }
-#pragma unroll
-        for (int ks = 0; ks < X::NKS; ++ks) {
-            float x[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) x[j] = value(ks, 8 * g + j) * (ks == 0 ? sc0 : sc1);
-            split8h(x, S1h[ks], S1m[ks]);
-        }
+        s1_operand<KP>(SOL + (size_t)(v ? s0 + lo : 0) * C::NSOL, v, g, A);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // (the operand loads above are the only tracked loads)
     const bool full_wave = active && s0 + 16 <= B;
-    const int rot = (int)(((unsigned)blk * 2654435761u) % (unsigned)min(n, 4));
-    auto tile_of = [&](int c) {
-        int x = c + rot;
-        if (x >= n) x -= n;
-        return t0 + x;
-    };
-    auto get_quarter = [&](int u) {
-        const int c = u >> 2, h = (u >> 1) & 1, j = u & 1;
-        const unsigned char *src = uniform_ptr(IMG + (size_t)tile_of(c) * X::TILE_B + h * X::HALF_B + j * (X::Q_B + 1024));
-        unsigned char *dst = lds[u % RING];
-        constexpr int NCH = X::Q_B / 1024;
-#pragma unroll
-        for (int i = 0; i < (NCH + 1 + 3) / 4; ++i) {
-            const int ch = wv + 4 * i;
-            if (ch < NCH) glds16a(src + ch * 1024, (unsigned)lane * 16u, wave_uniform(lds_addr(dst + ch * 1024)));
-            else if (ch == NCH && j == 0)
-                glds16a(src + X::Q_B, (unsigned)lane * 16u, wave_uniform(lds_addr(dst + X::Q_B)));
-        }
-    };
+    const TileWalk tile_of(blk, t0, n);
+    auto get_q = [&](int u) { get_quarter<KP>(IMG, tile_of(u >> 2), u, lds[u % RING], wv, lane); };
     f32x4 afy, aq;
     float muH = 0.f, it1H = 1.f, it2H = 1.f;
-    auto quarter = [&](auto jtag, const unsigned char *img) {
-        constexpr int j = decltype(jtag)::value;
-        const unsigned char *bp = img + lane * 16;
-        if (j == 0) {
-            afy = f32x4{0.f, 0.f, 0.f, 0.f};
-            aq = f32x4{0.f, 0.f, 0.f, 0.f};
-            muH = reinterpret_cast<const float *>(img + X::Q_B)[lo];
-            it1H = reinterpret_cast<const float *>(img + X::Q_B)[X::PAR_IT1 + lo]; it2H = reinterpret_cast<const float *>(img + X::Q_B)[X::PAR_IT2 + lo];
-        }
-        constexpr int NP = X::NP;
-        u32x4 bq[2][NP];
-#pragma unroll
-        for (int pc = 0; pc < NP; ++pc) bq[0][pc] = *reinterpret_cast<const u32x4 *>(bp + pc * 1024);
-#pragma unroll
-        for (int kq = 0; kq < X::NKQ; ++kq) {
-            if (kq + 1 < X::NKQ) {
-#pragma unroll
-                for (int pc = 0; pc < NP; ++pc)
-                    bq[(kq + 1) & 1][pc] = *reinterpret_cast<const u32x4 *>(bp + (kq + 1) * X::KS_B + pc * 1024);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            const u32x4 &bh = bq[kq & 1][0], &bm = bq[kq & 1][1];
-            if (j == 0) {
-                if (kq == 0) afy = xdl3h(S1h[0], S1m[0], bh, bm, afy);
-                else aq = xdl3h(S1h[kq], S1m[kq], bh, bm, aq);
-            } else {
-                aq = xdl3h(S1h[X::NKQ + kq], S1m[X::NKQ + kq], bh, bm, aq);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        if (j == 1) {                      // the powers of two back in: element r <-> spectrum 4 g + r, the lane's pixel
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                afy[r] = (afy[r] * is0[r]) * it1H;
-                aq[r] = (aq[r] * is1[r]) * it2H;
-            }
-        }
-    };
+    auto params = [&](const float *po) { muH = po[X::PAR_PSI + lo]; };       // (the image was built with mu in the place of Psi)
 
-    get_quarter(0);
-    if (4 * n > 1) get_quarter(1);
+    get_q(0);
+    if (4 * n > 1) get_q(1);
     dma_wait<0>();
     step_barrier();
-    constexpr int NCHQ = X::Q_B / 1024;            // pieces of quarter u moved by this wave (see k_s12_x)
-    auto cnt_q = [&](int u) { return (NCHQ - wv + 3) / 4 + ((NCHQ % 4 == wv && !(u & 1)) ? 1 : 0); };
-    int rest_prev = 0;                              // stores of the previous sub-step, behind its image DMA in the queue
+    int rest_prev = 0;                             // stores of the previous sub-step, behind its image DMA in the queue
     float co0[4], un0[4];
     for (int c = 0; c < n; ++c) {
         const int tg = tile_of(c);
@@ -686,12 +508,12 @@ __global__ __launch_bounds__(256, 1) void k_predict_x32(int B, int Npix, int nti
             for (int j = 0; j < 2; ++j) {
                 const int u = 4 * c + 2 * h + j;
                 const bool more = u + 2 < 4 * n;
-                if (more) get_quarter(u + 2);
+                if (more) get_q(u + 2);
                 int rest = 0;
                 bool drain = false;
                 if (active) {
-                    if (j == 0) quarter(std::integral_constant<int, 0>{}, lds[u % RING]);
-                    else quarter(std::integral_constant<int, 1>{}, lds[u % RING]);
+                    if (j == 0) quarter<KP, 0>(lds[u % RING], lane, A, afy, aq, it1H, it2H, params);
+                    else quarter<KP, 1>(lds[u % RING], lane, A, afy, aq, it1H, it2H, params);
                     if (j == 1 && h == 0) {
 #pragma unroll
                         for (int r = 0; r < 4; ++r) {
@@ -705,8 +527,8 @@ __global__ __launch_bounds__(256, 1) void k_predict_x32(int B, int Npix, int nti
 #pragma unroll
                             for (int r = 0; r < 4; ++r) {
                                 const size_t o = (size_t)(s0 + 4 * g + r) * Npix + px;
-                                s12_store2(cont + o, co0[r], afy[r] + muH);
-                                s12_store2(unc + o, un0[r], __builtin_amdgcn_sqrtf(aq[r]));
+                                store2_nt(cont + o, co0[r], afy[r] + muH);
+                                store2_nt(unc + o, un0[r], __builtin_amdgcn_sqrtf(aq[r]));
                             }
                             rest = 8;
                         } else {
@@ -729,7 +551,7 @@ __global__ __launch_bounds__(256, 1) void k_predict_x32(int B, int Npix, int nti
                 // the DMA of quarter u + 1 (issued at the start of the previous sub-step) must have landed; behind it in the
                 // queue: the stores of the previous sub-step, this sub-step's DMA and its stores
                 if (!more || drain) dma_wait<0>();
-                else dma_wait_n(rest_prev + cnt_q(u + 2) + rest);
+                else dma_wait_n(rest_prev + cnt_q<KP>(u + 2, wv) + rest);
                 rest_prev = drain ? 0 : rest;
                 step_barrier();
             }

@@ -29,6 +29,7 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NH = (1, 8, 9, 16, 17, 32)
 NPIX_NB = {33: 13, 97: 45, 200: 77}            # N_pix -> the N_b with the blue / red boundary inside a tile
+ALIGNED = (64, 29)                             # (N_pix, N_b) with rows that start on a 64-byte boundary: the aligned store form of the N_h <= 8 writer
 BS = (1, 17, 65, 130)
 FORMS = ("zabs", "zfac", "rows", "ablue")
 # (B, N_pix, N_h) at flags 0: both sides of the pixel-resident thresholds (128 spectra at KP = 16 and 512 at KP = 8 from 1024 pixels on) and
@@ -154,11 +155,21 @@ def run_cases(sink, dev):
             for exact in (0, 1):
                 for slab in (0, 1):
                     step_case(bench, sink, f"threshold/B{B}/npix{npix}/nh{nh}/{form}/ex{exact}/slab{slab}", form, B, 0, exact, slab)
+    # the XDL writer of N_h <= 8 with rows of cont / unc that start on a 64-byte boundary (N_pix a multiple of 16): none of the N_pix above
+    # is one, so every N_h <= 8 prediction there takes the re-aligned store form
+    for nh in (1, 8):
+        seed += 1
+        bench = Bench(dev, nh, ALIGNED[0], ALIGNED[1], max(BS), seed)
+        for B in BS:
+            m, a, kw = bench.args("zabs", B, flux=True)
+            m.flags = 0
+            sink.put(f"predict/nh{nh}/npix{ALIGNED[0]}/mid/B{B}/zabs/f0x0", ("ll", "hmean", "hcov", "cont", "unc"), list(m.predict(*a, **kw)))
 
 
 def run_trace(dev):
     """one training step per branch of the plan: every pass-2 form and solve flavour, with and without the slab, both NLL-sum forms,
-    the separate and the fused preparations, the factored-z form (k_zfac_* / the ZS block range of k_prep_step)"""
+    the separate and the fused preparations, the factored-z form (k_zfac_* / the ZS block range of k_prep_step); a custom tau and exact
+    gradients in the default form (the remaining instantiations of k_grads_x and k_s12_x); the posterior call with the XDL writers"""
     import torch
     from qfa_amd import _lib
     for nh in (8, 16, 24):
@@ -170,6 +181,17 @@ def run_trace(dev):
                     m, a, kw = bench.args(form, 130)
                     m.flags, m.exact_gradients, m.deterministic = flags, False, bool(slab)
                     m.accumulate(*a, **kw)
+        for form, exact in (("ablue", 0), ("ablue", 1), ("zabs", 1), ("zfac", 1)):
+            m, a, kw = bench.args(form, 130)
+            m.flags, m.exact_gradients, m.deterministic = 0, bool(exact), False
+            m.accumulate(*a, **kw)
+        m, a, kw = bench.args("zabs", 130, flux=True)
+        m.flags = 0
+        m.predict(*a, **kw)
+    bench = Bench(dev, 8, ALIGNED[0], ALIGNED[1], 130, 300)
+    m, a, kw = bench.args("zabs", 130, flux=True)
+    m.flags = 0
+    m.predict(*a, **kw)
     for B, npix, nh in THRESHOLDS:
         bench = Bench(dev, nh, npix, npix // 2 - 3, B, 200)
         for slab in (0, 1):
