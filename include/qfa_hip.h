@@ -662,7 +662,74 @@ int qfa_preprocess_f32(const double *wave, const float *flux, const float *ivar,
                        const qfa_preprocess_t *q, float *flux_out, float *error_out, double *record_f64,
                        int32_t *record_i32, void *workspace, size_t workspace_bytes, void *stream);
 
-/* The sightline bootstrap of the segment statistics (additive to ABI v4).  The five calls above take their error bars from the scatter
+/* Catalogued absorbers and bad wavelengths: mask and correct (additive to ABI v4).  A damped Lyman-alpha system wipes out tens of
+ * Angstrom of forest and its Lorentzian wings depress hundreds more; sky lines and Galactic Ca H&K spoil the same observed
+ * wavelengths of every spectrum; a BAL trough spoils rest-frame intervals of one.  This call applies catalogues of the three to the
+ * (N, Npix) rest-frame arrays every loader accepts -- qfa_preprocess_f32's output or data already in the reference's file format --
+ * between preprocessing and everything after it: a spoiled pixel becomes the -999 sentinel, which every kernel of the package
+ * treats as weight zero, the rest is divided by the absorbers' Voigt profile.  The reference ships no such step.
+ *
+ * The contract.
+ *   inputs     flux, error (N, Npix) float32 with -999 sentinels; zqso (float64, N); wav_grid (float64, Npix, rest-frame pixel
+ *              centres).  Absorbers as a CSR list: spectrum i owns entries abs_offsets[i] .. abs_offsets[i + 1] - 1 of abs_z (the
+ *              absorber's redshift, 1 + z_a > 0) and abs_lognhi (log10 of the column density in cm^-2), both float64;
+ *              abs_offsets (int64, N + 1) NULL = no absorbers.  obs_intervals (n_obs, 2) float64 [lo, hi) in observed-frame
+ *              Angstrom, the same for every spectrum (NULL with n_obs = 0).  rest_offsets (int64, N + 1, NULL = none) /
+ *              rest_intervals (., 2) float64 [lo, hi) in rest-frame Angstrom per spectrum.  Everything lives on the device; the
+ *              CALLER checks that the offsets are non-decreasing and every list entry is finite, lo < hi, 1 + z_a > 0.
+ *   profile    all in float64.  lam_obs = wav_grid[k] (1 + z_i)  (one addition, one product).  tau = 0; for each absorber j of
+ *              the spectrum in list order, and for each of its lines in the order Ly-alpha (lam0 = 1215.67, f = 0.4164,
+ *              Gamma = 6.265e8), then under QFA_ABS_LYB Ly-beta (1025.72, 0.07912, 1.897e8):
+ *                x = (c / b) (lam_obs / (lam0 (1 + z_a)) - 1),  c = 299792.458,  b = b_kms;      P = x x
+ *                a = Gamma lam0 1e-13 / (4 pi b)            ka = a / sqrt(pi)
+ *                tau += 1.497e-15 10^logNHI f lam0 / b  H(a, x)
+ *              H is the approximation of Tepper-Garcia (2006), with H0 = exp(-P), Q = 1.5 / P:
+ *                1/16 <= P <= 750   H = H0 - (ka / P) [H0 H0 (4 P P + 7 P + 4 + Q) - Q - 1]
+ *                P > 750            H = (ka / P) (1 + Q)    -- the same value: exp(-P) is 0 in float64 from P = 746 on
+ *                P < 1/16           H = H0 - ka (g_0 + g_1 P + .. + g_9 P^9), the Taylor series of [..] / P, which the form above loses to
+ *                                   cancellation (its 1.5 / P terms) and to 0 / 0 at P = 0:  g_k = 4 E_{k-1} + 7 E_k + 4 E_{k+1} +
+ *                                   1.5 E_{k+2},  E_n = (-2)^n / n!, E_{-1} = 0:
+ *                                   2, -4, 5/3, 14/15, -8/5, 352/315, -169/315, 38/189, -884/14175, 2584/155925
+ *                                   (the next term is below 4e-15 ka at the switch; H(a, 0) = 1 - 2 ka, the Voigt function's value
+ *                                   to first order in a)
+ *              T = exp(-tau); no absorbers: T = 1 exactly.  The approximation is first order in a: against the Faddeeva function T
+ *              is good to float32 grade for damped systems and worse for weaker ones at large b (profiles/absorber_accuracy.txt).
+ *   pixels     an input pixel is valid iff flux != -999 and error != -999.  A valid pixel is MASKED iff T < t_min, or T is not
+ *              finite (absorber-masked), or lam_obs lies in any [lo, hi) of obs_intervals, or wav_grid[k] in any [lo, hi) of the
+ *              spectrum's rest intervals (interval-masked; a pixel masked for both reasons counts as absorber-masked).
+ *   outputs    a masked or invalid pixel: exactly -999.0f in flux_out and error_out (what an invalid pixel holds -- NaN, inf --
+ *              reaches nothing: selects, not products).  A kept pixel: flux_out = float32(double(flux) / T), error_out =
+ *              float32(double(error) / T) under QFA_ABS_CORRECT, else the input's bits.  trans_out (N, Npix) float32 = T of every
+ *              pixel, valid or not; may be NULL.  flux_out == flux and error_out == error (in place) is allowed.
+ *   record     per spectrum, from the OUTPUT arrays, with qfa_preprocess_f32's definitions:  record_i32 (N, 6) = [n_valid |
+ *              n_lead | n_trail | num_mask | n_absorber_masked | n_interval_masked],  record_f64 (N, 1) = [snr], the mean of
+ *              double(flux_out) / double(error_out) over the kept pixels with snr_lo <= wav_grid[k] < snr_hi, NaN if none.
+ *   sums       float64 in one fixed order (per thread in order of k, a butterfly over the wave, the waves in order), no atomics.  A
+ *              spectrum's outputs depend on that spectrum alone -- not on N or on how a set is cut into calls -- and two calls on
+ *              the same inputs give the same bits.
+ * qfa_absorber_workspace_bytes: 0 = unsupported shape (N < 0, Npix outside 1..16 384); nothing is held between kernels, the size
+ * of a supported shape is a token 16 bytes.
+ * Returns QFA_E_NULL for q == NULL; QFA_E_SIZE for an unsupported shape, n_obs < 0, t_min outside [0, 1), b_kms not positive and
+ * finite, an snr window that is empty or not finite; QFA_E_FLAGS for an unknown flag; then N = 0 does nothing and returns 0;
+ * QFA_E_NULL for any other missing pointer (trans_out may be NULL; abs_offsets NULL = no absorbers, else abs_z and abs_lognhi are
+ * required; obs_intervals is required when n_obs > 0; rest_offsets NULL = none, else rest_intervals is required);
+ * QFA_E_WORKSPACE.  Argument checks return before any device work.  The call neither synchronises nor allocates (graph-capturable). */
+enum { QFA_ABS_LYB = 0x1, QFA_ABS_CORRECT = 0x2 };
+typedef struct {
+    double t_min;               /* in [0, 1); 0.8 is the usual choice */
+    double b_kms;               /* Doppler parameter of every absorber, km/s, > 0; 30 */
+    double snr_lo, snr_hi;      /* rest-frame Angstrom, lo < hi */
+    unsigned flags;             /* QFA_ABS_LYB | QFA_ABS_CORRECT */
+} qfa_absorber_t;
+
+size_t qfa_absorber_workspace_bytes(int N, int Npix);
+int qfa_absorber_mask_f32(const float *flux, const float *error, const double *zqso, const double *wav_grid, int N, int Npix,
+                          const int64_t *abs_offsets, const double *abs_z, const double *abs_lognhi,
+                          const double *obs_intervals, int n_obs, const int64_t *rest_offsets, const double *rest_intervals,
+                          const qfa_absorber_t *q, float *flux_out, float *error_out, float *trans_out, double *record_f64,
+                          int32_t *record_i32, void *workspace, size_t workspace_bytes, void *stream);
+
+/* The sightline bootstrap of the segment statistics (additive to ABI v4). The five calls above take their error bars from the scatter
  * of segments, but the segments of one quasar share a continuum, a noise model and a large-scale mode, and nothing but the band stack
  * gives a covariance between modes, lags, flux bins or z-bins.  The published measurements resample quasars.  These calls do that on
  * the per-segment rows the statistics already write (power, pairs, hist, bandpower, moments): R Poisson-bootstrap replicates of the

@@ -24,6 +24,9 @@ _LAZY = {
     #  and calls the function -- qfa_amd/preprocess.py, _CallableModule)
     "preprocess": ("qfa_amd.preprocess", "preprocess"),
     "Preprocessed": ("qfa_amd.preprocess", "Preprocessed"),
+    "AbsorberCatalog": ("qfa_amd.absorbers", "AbsorberCatalog"),
+    "mask_absorbers": ("qfa_amd.absorbers", "mask_absorbers"),
+    "bal_intervals": ("qfa_amd.absorbers", "bal_intervals"),
 }
 
 

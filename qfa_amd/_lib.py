@@ -28,6 +28,7 @@ EXPORTS = (
     "qfa_flux_pdf_stack_doubles", "qfa_flux_pdf_workspace_bytes", "qfa_flux_pdf_f32",
     "qfa_variance_stack_doubles", "qfa_variance_workspace_bytes", "qfa_variance_f32",
     "qfa_preprocess_workspace_bytes", "qfa_preprocess_f32",
+    "qfa_absorber_workspace_bytes", "qfa_absorber_mask_f32",
     "qfa_segment_codes_f32", "qfa_bootstrap_workspace_bytes", "qfa_bootstrap_f64",
 )
 
@@ -42,6 +43,7 @@ F_XI_UNIT_W = 0x400        # qfa_xi_f32: w = 1 on a used pixel instead of 1 / (v
 F_PDF_RELATIVE = 0x800     # qfa_flux_pdf_f32: bin x = T / tbar(z) instead of x = T
 F_PDF_CLAMP = 0x1000       # qfa_flux_pdf_f32: x outside the range counts in the first / last bin
 ROW_TYPES = {"float32": 0, "float64": 1, "int32": 2}    # qfa_bootstrap_f64: QFA_ROW_* by the name of the rows' dtype
+ABS_LYB, ABS_CORRECT = 0x1, 0x2    # qfa_absorber_t.flags (QFA_ABS_*)
 F_EXACT_GRAD = 0x100       # exact gradients of mean NLL (opt-in; QFA.exact_gradients); the buffer carries the mode in slot 6
 
 
@@ -100,6 +102,10 @@ class VarParams(C.Structure):       # qfa_var_t
 class PreprocessParams(C.Structure):   # qfa_preprocess_t
     _fields_ = [("min_coverage", C.c_double), ("norm_lo", C.c_double), ("norm_hi", C.c_double), ("snr_lo", C.c_double),
                 ("snr_hi", C.c_double), ("norm_min_pixels", C.c_int)]
+
+
+class AbsorberParams(C.Structure):     # qfa_absorber_t
+    _fields_ = [("t_min", C.c_double), ("b_kms", C.c_double), ("snr_lo", C.c_double), ("snr_hi", C.c_double), ("flags", C.c_uint)]
 
 
 _lib = None
@@ -186,6 +192,8 @@ def lib():
         "qfa_variance_f32": (i, [p, p, C.POINTER(Batch), p, i, i, i, C.POINTER(P1DParams), C.POINTER(VarParams), C.c_uint, p, p, p, sz, p]),
         "qfa_preprocess_workspace_bytes": (sz, [i, i, i]),
         "qfa_preprocess_f32": (i, [p, p, p, p, p, p, i, i, p, p, i, C.POINTER(PreprocessParams), p, p, p, p, p, sz, p]),
+        "qfa_absorber_workspace_bytes": (sz, [i, i]),
+        "qfa_absorber_mask_f32": (i, [p, p, p, p, i, i, p, p, p, p, i, p, p, C.POINTER(AbsorberParams), p, p, p, p, p, p, sz, p]),
         "qfa_segment_codes_f32": (i, [p, p, C.POINTER(Batch), p, i, i, i, C.POINTER(P1DParams), p, p]),
         "qfa_bootstrap_workspace_bytes": (sz, [i, i, i, i, i, i]),
         "qfa_bootstrap_f64": (i, [p, i, p, i, i, i, i, i, i, C.c_uint64, i64, C.c_uint, p, p, sz, p]),

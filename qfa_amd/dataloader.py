@@ -155,11 +155,14 @@ class DeviceDataloader(object):
 
     @classmethod
     def from_observed(cls, wave, flux, ivar, offsets, zqso, wav_grid, batch_size, device, bad=None, names=None,
-                      snr_min=-np.inf, snr_max=np.inf, z_min=-np.inf, z_max=np.inf, num_mask=np.inf, preprocess_kw=None, **kw):
+                      snr_min=-np.inf, snr_max=np.inf, z_min=-np.inf, z_max=np.inf, num_mask=np.inf, preprocess_kw=None,
+                      absorbers=None, **kw):
         """Observed-frame spectra (the ragged form of ``qfa_amd.preprocess.preprocess``: observed wavelength, flux, inverse
         variance, pixel flags, z) to resident training storage without a host round trip: ``preprocess`` on the device,
         ``Preprocessed.select`` (the reference's catalogue criteria, QFA/dataloader.py:49), and the constructor on the device
         tensors.  ``names`` (N) become ``pathlist``; without them it holds the input row numbers.
+        ``absorbers``: a dict of ``qfa_amd.absorbers.mask_absorbers``'s keywords (``dla``, ``sky``, ``rest``, ``t_min``, ...; ``dla``
+        and ``rest`` cover the N input spectra), applied between ``preprocess`` and ``select``.
         Data parallel (``rank`` / ``world`` in ``kw``): every rank is handed the whole input and preprocesses the spectra
         ``shard_bounds`` gives it; the selected counts are all-reduced, and since the selection of a shard need not have the size
         of the loader's shard of the selected set, the rows a rank lacks -- spectra next to its shard -- are preprocessed in a
@@ -173,8 +176,23 @@ class DeviceDataloader(object):
 
         def run(rows_lo, rows_hi):
             a, b = int(off[rows_lo]), int(off[rows_hi])
-            return preprocess(wave[a:b], flux[a:b], ivar[a:b], off[rows_lo:rows_hi + 1] - a, zqso[rows_lo:rows_hi], wav_grid,
-                              bad=None if bad is None else bad[a:b], device=device, **pk)
+            pre = preprocess(wave[a:b], flux[a:b], ivar[a:b], off[rows_lo:rows_hi + 1] - a, zqso[rows_lo:rows_hi], wav_grid,
+                             bad=None if bad is None else bad[a:b], device=device, **pk)
+            return pre if absorbers is None else pre.mask_absorbers(**absorber_kw(rows_lo, rows_hi))
+
+        def absorber_kw(rows_lo, rows_hi):
+            """the keywords for the spectra rows_lo .. rows_hi - 1: the per-spectrum lists are cut, the rest is shared"""
+            from .absorbers import AbsorberCatalog, _rest_csr
+            ak = dict(absorbers)
+            if ak.get("dla") is not None:
+                cat = ak["dla"] if isinstance(ak["dla"], AbsorberCatalog) else AbsorberCatalog(ak["dla"])
+                if len(cat) != n:
+                    raise ValueError(f"absorbers['dla'] has {len(cat)} rows for {n} spectra")
+                ak["dla"] = cat.rows(rows_lo, rows_hi)
+            if ak.get("rest") is not None:
+                r_off, r_iv = _rest_csr(ak["rest"], n)
+                ak["rest"] = (r_off[rows_lo:rows_hi + 1] - r_off[rows_lo], r_iv[r_off[rows_lo]:r_off[rows_hi]])
+            return ak
 
         def rows_of(pre, idx):
             idx_d = torch.as_tensor(idx, device=pre.flux.device)

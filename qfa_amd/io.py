@@ -79,6 +79,33 @@ def read_observed_npz(paths, nprocs=1):
         np.array([d[4] for d in data], dtype=np.float64)
 
 
+def read_absorber_csv(path):
+    """An absorber catalogue (columns ``file``, ``z_abs``, ``log_nhi``; any number of rows per file) as the table
+    ``qfa_amd.absorbers.AbsorberCatalog.from_table`` takes"""
+    import pandas as pd
+    t = pd.read_csv(path)
+    missing = [c for c in ("file", "z_abs", "log_nhi") if c not in t.columns]
+    if missing:
+        raise ValueError(f"{path}: missing column(s) {missing}")
+    return {"file": t["file"].astype(str).values, "z_abs": t["z_abs"].values.astype(np.float64),
+            "log_nhi": t["log_nhi"].values.astype(np.float64)}
+
+
+def read_intervals(path):
+    """Intervals ``[lo, hi)`` in Angstrom, one per line, two columns separated by blanks or a comma (``#`` starts a comment):
+    float64 (n, 2)"""
+    rows = []
+    with open(path) as f:
+        for line in f:
+            line = line.split("#", 1)[0].replace(",", " ").split()
+            if not line:
+                continue
+            if len(line) != 2:
+                raise ValueError(f"{path}: a line with {len(line)} columns, expected 2")
+            rows.append((float(line[0]), float(line[1])))
+    return np.asarray(rows, dtype=np.float64).reshape(-1, 2)
+
+
 def select_from_catalog(catalog, num, snr_min, snr_max, z_min, z_max, num_mask, output_dir=None, prefix="train"):
     """File names drawn from a catalogue csv with columns file, snr, z, num_mask
     (reference QFA/dataloader.py:48-55): the rows inside the S/N, redshift and masked-pixel limits,

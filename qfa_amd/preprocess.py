@@ -8,6 +8,10 @@ file form the reference's ``--type train --catalog ... --data_dir ...`` reads.
 
     python -m qfa_amd.preprocess --catalog observed.csv --data_dir raw/ --output_dir prepared/ [--lammin 1030 --lammax 1600
                                                                                                --loglam_delta 1e-4 ...]
+                                [--dla_catalog dla.csv --sky_mask sky.txt --dla_tmin 0.8 --dla_b 30 --no_dla_correct]
+
+With ``--dla_catalog`` / ``--sky_mask`` the catalogued absorbers and bad observed wavelengths are masked and corrected
+(``qfa_amd.absorbers``) before the files are written.
 """
 from __future__ import annotations
 
@@ -65,6 +69,21 @@ class Preprocessed(object):
         with np.errstate(invalid="ignore"):
             keep = ok & (snr >= snr_min) & (snr <= snr_max) & (z >= z_min) & (z <= z_max) & (nm <= num_mask)
         return np.nonzero(keep)[0].astype(np.int64)
+
+    def mask_absorbers(self, **kw):
+        """Catalogued absorbers and bad wavelengths (``qfa_amd.absorbers.mask_absorbers``, whose keywords these are) applied to
+        these spectra: a new ``Preprocessed`` with the masked / corrected arrays and ``snr``, ``num_mask``, ``n_valid``,
+        ``n_lead``, ``n_trail`` recomputed on them, ``norm`` and ``ok`` carried over, and the per-spectrum counts
+        ``n_absorber_masked`` / ``n_interval_masked`` as attributes."""
+        from .absorbers import mask_absorbers
+        if kw.pop("return_trans", False):
+            raise QFAHipError("Preprocessed.mask_absorbers returns a Preprocessed: call absorbers.mask_absorbers for the transmission")
+        kw.setdefault("device", self.flux.device)
+        fo, eo, rec = mask_absorbers(self.flux, self.error, self.zqso, self.wav_grid, **kw)
+        new = Preprocessed(fo, eo, self.zqso, self.norm, rec["snr"], rec["num_mask"], rec["n_valid"], rec["n_lead"], rec["n_trail"],
+                           self.ok, self.wav_grid)
+        new.n_absorber_masked, new.n_interval_masked = rec["n_absorber_masked"], rec["n_interval_masked"]
+        return new
 
     @staticmethod
     def _file_names(names):
@@ -199,12 +218,27 @@ def main(argv=None):
     ap.add_argument("--snr_window", type=float, nargs=2, default=(1270., 1600.))
     ap.add_argument("--nprocs", type=int, default=1)
     ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--dla_catalog", default=None, help="csv with columns file, z_abs, log_nhi: mask and correct these absorbers")
+    ap.add_argument("--sky_mask", default=None, help="two-column file of observed-frame intervals [lo, hi) in Angstrom to mask")
+    ap.add_argument("--dla_tmin", type=float, default=0.8, help="mask where the absorbers' transmission is below this")
+    ap.add_argument("--dla_b", type=float, default=30., help="Doppler parameter of the absorbers, km/s")
+    ap.add_argument("--no_dla_correct", action="store_true", help="mask only: do not divide by the absorbers' profile")
     a = ap.parse_args(argv)
     names = [str(x) for x in pd.read_csv(a.catalog).iloc[:, 0].values]
     wave, flux, ivar, bad, offsets, zqso = io.read_observed_npz([os.path.join(a.data_dir, n) for n in names], a.nprocs)
     grid = io.wavelength_grid(a.lammin, a.lammax, a.loglam_delta)
     pre = preprocess(wave, flux, ivar, offsets, zqso, grid, bad=bad, min_coverage=a.min_coverage, norm_window=tuple(a.norm_window),
                      norm_min_pixels=a.norm_min_pixels, snr_window=tuple(a.snr_window), device=a.device)
+    if a.dla_catalog is not None or a.sky_mask is not None:
+        from .absorbers import AbsorberCatalog
+        dla = None
+        if a.dla_catalog is not None:
+            dla = AbsorberCatalog.from_table([os.path.basename(n) for n in names], io.read_absorber_csv(a.dla_catalog))
+            if dla.unmatched:
+                print(f"{len(dla.unmatched)} file names of {a.dla_catalog} match no spectrum, the first: {dla.unmatched[0]}")
+        sky = io.read_intervals(a.sky_mask) if a.sky_mask is not None else None
+        pre = pre.mask_absorbers(dla=dla, sky=sky, t_min=a.dla_tmin, b_kms=a.dla_b, correct=not a.no_dla_correct,
+                                 snr_window=tuple(a.snr_window))
     path = pre.write_npz(a.output_dir, [os.path.basename(n) for n in names])
     print(f"{int(pre.ok.sum())} of {len(pre)} spectra written to {a.output_dir}; catalogue {path}")
     return 0
