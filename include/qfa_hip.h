@@ -729,6 +729,63 @@ int qfa_absorber_mask_f32(const float *flux, const float *error, const double *z
                           const qfa_absorber_t *q, float *flux_out, float *error_out, float *trans_out, double *record_f64,
                           int32_t *record_i32, void *workspace, size_t workspace_bytes, void *stream);
 
+/* The DLA finder: a likelihood-ratio scan of every spectrum over a table of transmission templates (additive to ABI v4).
+ * qfa_absorber_mask_f32 applies a catalogue of damped Lyman-alpha systems; these calls produce one.  The method is the
+ * Gaussian-process finder of Garnett et al. (2017) and Ho, Bird & Garnett (2020) on this package's model: for every spectrum and
+ * every candidate (absorber redshift, column density) the model is multiplied by the candidate's Voigt profile, and the gain in
+ * log-likelihood is the statistic.  The reference ships no such step.
+ *
+ * The rule.  A template is a per-pixel transmission V[c, k] (candidate c, pixel k of the model's rest-frame grid), (nc, Npix)
+ * float32.  With the quantities of qfa_predict_f32 -- x = b->delta the RAW FLUX, sigma = b->error, A = exp(-tau(z)) and
+ * zd = (1 - c0 - exp(-tau0 (1 + z)^beta))^2 on the blue side (A = 1, zd = 0 on the red side) -- candidate c models the spectrum as
+ *   A' = V A        G = A^2 Psi + omega zd        D' = V^2 G + sigma^2        w' = mask / D'
+ *   delta' = x - A' mu      C' = I + sum_k w' A'^2 f f^T      b' = sum_k w' A' delta' f      y' = C'^-1 b'
+ *   NLL'(c) = ( sum_k w' delta'^2 - b'^T y' + n log 2 pi + sum_mask log D' + log det C' ) / 2
+ * (the model's absorption variance omega zd lies behind the absorber too: hence V^2 G).  V = 1 gives NLL0, qfa_predict_f32's ll;
+ * n, the number of used pixels, is the same for every candidate, and the output is
+ *   llr[s, c] = NLL0[s] - NLL'[s, c].
+ *   redshift   z = zabs[r, k], or in the factored form z = fma(zq1[r], pix_ratio[k], -1) (one rounding), r = rows ? rows[s] : s:
+ *              one arithmetic behind both, so a zabs array that holds those z gives the factored form's bits; rows / row_stride
+ *              as everywhere.  A_blue (a custom tau callable) is refused: QFA_E_NULL;
+ *   arithmetic the per-pixel terms in float32, in DIFFERENCE form against V = 1:  w' A'^2 - w A^2,  w' A' delta' - w A delta,
+ *              w' delta'^2 - w delta^2 + ln(1 - (1 - V^2) G / D).  Both members of a difference are formed by the same operations,
+ *              so a pixel with V == 1.0f contributes exact zeros (and blocks of pixels where a whole tile of templates is 1.0f are
+ *              skipped without changing a bit), and the error of llr scales with llr, not with NLL.  The sums over the pixels of
+ *              the first two run on the matrix pipe (v_mfma_f32_16x16x4_f32, float32 accumulators, pixels in order), the third
+ *              and every null sum in float64; C' = C0 + dC is factored in float64 (Cholesky) per candidate:
+ *              llr = ( -ds + (b'^T y' - b0^T y0) - (log det C' - log det C0) ) / 2, rounded to float32 once;
+ *   masks      a masked pixel (mask == 0) may hold NaN, inf or -999 in delta and error: they are not read.  A spectrum with no
+ *              used pixel has nll0 = 0 and llr = 0 for every c.  A non-finite delta or error in a USED pixel makes that spectrum's
+ *              nll0, llr and best_llr NaN and its best_c -1, and touches no other spectrum;
+ *   outputs    llr (B, nc) and nll0 (B,) float32;  best_c (B,) int32 = the c of the largest llr of the row, the lowest c among
+ *              equals, NaN never taken, -1 if every llr is NaN;  best_llr (B,) = that llr (NaN with -1).  best_c and best_llr may
+ *              each be NULL;
+ *   sums       no float atomics; two calls on the same inputs give the same bits.  A spectrum's row depends on that spectrum
+ *              (and the table) alone, bit for bit: not on B, on the spectra beside it or on how the batch is cut into chunks.
+ * qfa_template_scan_workspace_bytes: the images of F and of the table and the rows of one chunk of spectra (the batch is walked in
+ * chunks whose rows stay below 256 MiB, four spectra at least); 0 = unsupported shape (B outside 1..2^24, Npix < 1, Nh outside
+ * 1..32, nc outside 1..262 144).
+ * Returns QFA_E_NULL for a missing pointer (p and its members, mu, b and its members as qfa_predict_f32 needs them, tau, V, llr,
+ * nll0, workspace) or a non-NULL A_blue; QFA_E_SIZE for an unsupported shape, Nb outside 0..Npix or 0 < row_stride < Npix;
+ * QFA_E_FLAGS for any flag but QFA_F_SYNC; QFA_E_WORKSPACE.  Argument checks return before any device work.  The call neither
+ * synchronises nor allocates (graph-capturable).
+ *
+ * DLA templates.  qfa_dla_profiles_f32 fills the table of a grid of candidates that is the same in every quasar's rest frame:
+ * Ly-alpha centres lam_i = lam_hi exp(-i dv_kms / c), i = 0 .. nz - 1, column densities logN_j = logn_lo + j dlogn, j = 0 .. nN - 1,
+ * c = i nN + j, V_out (nz nN, Npix).  In spectrum s candidate i is an absorber at z_a = (1 + z_qso[s]) lam_i / 1215.67 - 1, and
+ * lam_obs / (lam0 (1 + z_a)) = wav_grid[k] / (lam_i lam0 / 1215.67) does not depend on s.  tau and H(a, x) are those of
+ * qfa_absorber_mask_f32's "profile", with x = (c / b) (wav_grid[k] / (lam_i lam0 / 1215.67) - 1): the same constants and three
+ * ranges of P, Ly-alpha and under `lyb` Ly-beta, the same b_kms; float64 throughout, V = exp(-tau) rounded to float32 once.
+ * Returns QFA_E_NULL; QFA_E_SIZE unless Npix >= 1, 1 <= nz <= 4096, 1 <= nN <= 64, lam_hi > 0, dv_kms >= 0, b_kms > 0, all finite,
+ * and wav_grid[0] <= lam_i <= wav_grid[Npix - 1] for every i.  The last check reads the two ends of wav_grid on the host: this call
+ * synchronises `stream` once (it is made once per grid, not per batch). */
+int qfa_dla_profiles_f32(const double *wav_grid, int Npix, double lam_hi, double dv_kms, int nz, double logn_lo, double dlogn, int nN,
+                         double b_kms, int lyb, float *V_out, void *stream);
+size_t qfa_template_scan_workspace_bytes(int B, int Npix, int Nh, int nc);
+int qfa_template_scan_f32(const qfa_params_t *p, const float *mu, const qfa_batch_t *b, const qfa_tau_t *tau, const float *V, int nc,
+                          int B, int Npix, int Nb, int Nh, float *llr, float *nll0, int32_t *best_c, float *best_llr,
+                          void *workspace, size_t workspace_bytes, unsigned flags, void *stream);
+
 /* The sightline bootstrap of the segment statistics (additive to ABI v4). The five calls above take their error bars from the scatter
  * of segments, but the segments of one quasar share a continuum, a noise model and a large-scale mode, and nothing but the band stack
  * gives a covariance between modes, lags, flux bins or z-bins.  The published measurements resample quasars.  These calls do that on

@@ -27,6 +27,7 @@ _LAZY = {
     "AbsorberCatalog": ("qfa_amd.absorbers", "AbsorberCatalog"),
     "mask_absorbers": ("qfa_amd.absorbers", "mask_absorbers"),
     "bal_intervals": ("qfa_amd.absorbers", "bal_intervals"),
+    "DLAScan": ("qfa_amd.dla", "DLAScan"),
 }
 
 

@@ -29,6 +29,7 @@ EXPORTS = (
     "qfa_variance_stack_doubles", "qfa_variance_workspace_bytes", "qfa_variance_f32",
     "qfa_preprocess_workspace_bytes", "qfa_preprocess_f32",
     "qfa_absorber_workspace_bytes", "qfa_absorber_mask_f32",
+    "qfa_dla_profiles_f32", "qfa_template_scan_workspace_bytes", "qfa_template_scan_f32",
     "qfa_segment_codes_f32", "qfa_bootstrap_workspace_bytes", "qfa_bootstrap_f64",
 )
 
@@ -194,6 +195,10 @@ def lib():
         "qfa_preprocess_f32": (i, [p, p, p, p, p, p, i, i, p, p, i, C.POINTER(PreprocessParams), p, p, p, p, p, sz, p]),
         "qfa_absorber_workspace_bytes": (sz, [i, i]),
         "qfa_absorber_mask_f32": (i, [p, p, p, p, i, i, p, p, p, p, i, p, p, C.POINTER(AbsorberParams), p, p, p, p, p, p, sz, p]),
+        "qfa_dla_profiles_f32": (i, [p, i, d, d, i, d, d, i, d, i, p, p]),
+        "qfa_template_scan_workspace_bytes": (sz, [i, i, i, i]),
+        "qfa_template_scan_f32": (i, [C.POINTER(Params), p, C.POINTER(Batch), C.POINTER(TauModel), p, i, i, i, i, i, p, p, p, p, p, sz,
+                                      C.c_uint, p]),
         "qfa_segment_codes_f32": (i, [p, p, C.POINTER(Batch), p, i, i, i, C.POINTER(P1DParams), p, p]),
         "qfa_bootstrap_workspace_bytes": (sz, [i, i, i, i, i, i]),
         "qfa_bootstrap_f64": (i, [p, i, p, i, i, i, i, i, i, C.c_uint64, i64, C.c_uint, p, p, sz, p]),

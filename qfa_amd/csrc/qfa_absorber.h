@@ -23,6 +23,7 @@
 #include <stdint.h>
 
 #include "../../include/qfa_hip.h"
+#include "qfa_voigt.h"
 
 namespace qfa_absorber {
 
@@ -33,14 +34,7 @@ constexpr int kWords = kMaxNpix / 64;
 constexpr int kTileAbs = 16;                    // absorbers per LDS tile
 constexpr int kTileLines = 2 * kTileAbs;
 
-constexpr double kC = 299792.458;               // km/s
-constexpr double kTauCoef = 1.497e-15;
-constexpr double kPSeries = 0.0625, kPWing = 750.0;
-constexpr double kFourPi = 12.566370614359172, kSqrtPi = 1.7724538509055159;
-// lam0 (Angstrom), oscillator strength, damping constant (1/s) of Ly-alpha and Ly-beta
-__device__ constexpr double kLam0[2] = {1215.67, 1025.72};
-__device__ constexpr double kOsc[2] = {0.4164, 0.07912};
-__device__ constexpr double kGamma[2] = {6.265e8, 1.897e8};
+using namespace qfa_voigt;                      // the line constants, h_wing and h_full (qfa_voigt.h)
 
 struct Args {
     const float *flux, *error;                  // (N, Npix); may alias the outputs: no __restrict__ on the four
@@ -67,27 +61,6 @@ __device__ __forceinline__ int wave_isum(int x, int lane) {
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) x += __shfl(x, lane ^ d);
     return x;
-}
-
-// tau of one line at one pixel from 1 / P (wing: a whole wave beyond kPWing, no exp)
-__device__ __forceinline__ double h_wing(double ka, double rP) { return ka * rP * (1.0 + 1.5 * rP); }
-
-__device__ __forceinline__ double h_full(double ka, double P, double rP) {
-    const double H0 = exp(-P), Q = 1.5 * rP;
-    const double full = H0 - ka * rP * (H0 * H0 * (4.0 * P * P + 7.0 * P + 4.0 + Q) - Q - 1.0);
-    double g = 2584.0 / 155925.0;
-    g = g * P + -884.0 / 14175.0;
-    g = g * P + 38.0 / 189.0;
-    g = g * P + -169.0 / 315.0;
-    g = g * P + 352.0 / 315.0;
-    g = g * P + -8.0 / 5.0;
-    g = g * P + 14.0 / 15.0;
-    g = g * P + 5.0 / 3.0;
-    g = g * P + -4.0;
-    g = g * P + 2.0;
-    const double series = H0 - ka * g;
-    const double wing = h_wing(ka, rP);
-    return P < kPSeries ? series : (P > kPWing ? wing : full);
 }
 
 __global__ __launch_bounds__(kThreads) void k_absorber(const Args a) {
