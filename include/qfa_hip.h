@@ -836,6 +836,68 @@ size_t qfa_bootstrap_workspace_bytes(int n_spectra, int S, int nseg, int W, int 
 int qfa_bootstrap_f64(const void *rows, int row_type, const int32_t *codes, int B, int S, int nseg, int W, int nz, int R, uint64_t seed,
                       int64_t row_offset, unsigned flags, double *boot, void *ws, size_t ws_bytes, void *stream);
 
+/* The observed-frame residual stack and the calibration it gives (additive to ABI v4).  Sky-line residuals, Galactic Ca H&K and the
+ * spectrograph's flux-calibration residual spoil the same OBSERVED wavelengths of every spectrum, whatever its redshift.  Forest
+ * analyses measure them from their own data: r = flux / continuum of every spectrum is stacked in bins of observed wavelength; the
+ * stack's mean is the calibration vector, and bins whose scatter or mean stand out are the lines to mask (the intervals that
+ * qfa_absorber_mask_f32 takes as obs_intervals).  qfa_forest_f32 stacks the blue side in at most 4096 float32 redshift bins; this
+ * call stacks any pixel range -- the red side is where the calibration is measured -- in up to 32768 float64 bins, of which a
+ * spectrum touches a contiguous run.
+ *
+ * The contract of qfa_obs_stack_f32.  For spectrum b of a call (row r = rows ? rows[b] : b of the input arrays), draw s (0 <= s < S)
+ * and pixel p (p_lo <= p < p_hi, anywhere in 0 .. Npix):
+ *   inputs     F, mu, b, h, unc exactly as qfa_forest_f32 reads them: b->delta holds the RAW FLUX, b->error the pipeline sigma,
+ *              b->mask may be NULL (every pixel is used), rows / row_stride: the resident form; h (B, S, Nh) and unc (B, Npix) or NULL
+ *              in batch order.  zabs, zq1, pix_ratio and A_blue are ignored.  pix_u (Npix,) float64, finite and NON-DECREASING
+ *              (the caller checks; a run of a bin is found by bisection on it); spec_u (B,) float64 in batch order;
+ *   coordinate float64, every operation rounded once, no contraction:  QFA_OBS_LOG  u = pix_u[p] + spec_u[b]  (the host passes
+ *              log10(wav_grid) and log10(1 + z): both sides of every comparison share their bits);  QFA_OBS_LINEAR  u = pix_u[p]
+ *              spec_u[b]  (the host passes wav_grid and 1 + z);  x = (u - u0) inv_du with inv_du = 1.0 / du formed once on the host;
+ *              k = floor(x).  The pixel is stacked iff 0 <= x < nbin, tested on the double: an edge belongs to the bin above it.  A
+ *              spectrum whose spec_u is not finite stacks nothing (a negative or zero linear spec_u is a coordinate like any other);
+ *   values     those of qfa_forest_f32, verbatim, so that its bounds carry over:  c = mu[p] + sum_j F[p,j] h[b,s,j], the float32 fma
+ *              chain in order of j;  r = flux / c;  den = (r r) u2 + sigma sigma with u2 = unc unc or 0;  iv = (c c) / den; every
+ *              operation rounded once;
+ *   use        mask != 0 && c > cont_min && isfinite(r) && isfinite(iv).  Selects, not products: what flux or error hold under the
+ *              mask (-999, NaN, inf) reaches nothing.  NO transmission model is applied: on blue pixels the stack holds
+ *              <T> x calibration, on red pixels the calibration alone;
+ *   stack      (S, 4, nbin) float64 = [sum w | sum w r | sum w r^2 | n] per draw over the used, stacked pixels; w = (double)iv, or 1
+ *              with QFA_F_OBS_UNIT_W; the terms are w, w r and w (r r) in float64, each product rounded once.  The call ADDS to
+ *              `stack`; QFA_F_ZERO_ACCUM overwrites instead.  Nothing per pixel is written (qfa_forest_f32 writes the blue pixels);
+ *   sums       no float atomics: a thread owns a bin and adds the pixels of its run spectrum by spectrum, in pixel order; chunks of
+ *              spectra leave through rows of the workspace and a fixed-order reducer adds the rows to `stack`.  The cut is a function
+ *              of the shape alone: two calls on the same inputs give the same bits.
+ * qfa_obs_stack_doubles: S 4 nbin, 0 = unsupported (S < 1, nbin outside 1..32768).  qfa_obs_stack_workspace_bytes: the rows of partial
+ * sums; 0 = unsupported shape.
+ * Returns QFA_E_NULL for a missing required pointer (unc and b->mask may be NULL); QFA_E_SIZE for B < 0, S < 1, Npix < 1, Nh outside
+ * 1..32, bad bins (du <= 0 or not finite, 1 / du or u0 not finite, nbin outside 1..32768, not 0 <= p_lo <= p_hi <= Npix, an unknown
+ * mode) or 0 < row_stride < Npix; QFA_E_FLAGS for any flag other than QFA_F_ZERO_ACCUM, QFA_F_SYNC, QFA_F_OBS_UNIT_W;
+ * QFA_E_WORKSPACE.  B = 0 or p_lo == p_hi adds nothing and, under QFA_F_ZERO_ACCUM, still zeroes `stack`.  Argument checks return
+ * before any device work.  The call neither synchronises nor allocates (graph-capturable).
+ *
+ * The contract of qfa_calibrate_f32: divide spectra by a calibration table.  flux, error (N, Npix) float32 with the -999 sentinels (a
+ * pixel is valid iff flux != -999 and error != -999, as for qfa_absorber_mask_f32); pix_u, spec_u (N,), mode, u0, du as above;
+ * cal (ncal >= 2) float64 at the bin CENTRES u0 + (j + 0.5) du; c_min > 0.  Per pixel, in float64, every operation rounded once:
+ *   x = (u - u0) inv_du - 0.5;  j = min(floor(x), ncal - 2);  f = x - j;  c = fma(f, cal[j + 1] - cal[j], cal[j]).
+ * A pixel is calibrated iff it is valid, 0 <= x <= ncal - 1 and c is finite and >= c_min; it gets flux_out = (float)((double)flux / c)
+ * and error_out = (float)((double)error / c).  Every other pixel keeps its input bits, sentinels included.  n_uncal (N,) int32 = the
+ * number of VALID pixels left uncalibrated.  flux_out == flux and error_out == error (in place) is allowed; a spectrum's output
+ * depends on that spectrum alone.  Returns QFA_E_SIZE for N < 0, Npix < 1, ncal < 2, du <= 0 or not finite, 1 / du or u0 not finite,
+ * c_min <= 0 or not finite, an unknown mode; then N = 0 does nothing and returns 0; QFA_E_NULL for a missing pointer.  Argument
+ * checks return before any device work.  The call neither synchronises nor allocates (graph-capturable). */
+typedef struct { double u0, du; int nbin; int p_lo, p_hi; unsigned mode; } qfa_obs_bins_t;   /* du > 0, 1 <= nbin <= 32768, 0 <= p_lo <= p_hi <= Npix */
+enum { QFA_OBS_LOG = 0, QFA_OBS_LINEAR = 1 };
+#define QFA_F_OBS_UNIT_W 0x2000u   /* qfa_obs_stack_f32: stack with w = 1 instead of w = ivar */
+
+size_t qfa_obs_stack_doubles(int S, int nbin);
+size_t qfa_obs_stack_workspace_bytes(int B, int S, int Npix, int Nh, int nbin);
+int qfa_obs_stack_f32(const float *F, const float *mu, const qfa_batch_t *b, const float *h, const float *unc, const double *pix_u,
+                      const double *spec_u, int B, int S, int Npix, int Nh, const qfa_obs_bins_t *bins, float cont_min,
+                      unsigned flags, double *stack, void *workspace, size_t workspace_bytes, void *stream);
+int qfa_calibrate_f32(const float *flux, const float *error, const double *pix_u, const double *spec_u, int N, int Npix,
+                      const double *cal, int ncal, double u0, double du, unsigned mode, double c_min, float *flux_out,
+                      float *error_out, int32_t *n_uncal, void *stream);
+
 /* Replaces Adam.update(reference QFA/optimizer.py:37-52) followed by the clamp of QFA.clip
  * (QFA/model.py:233-241) for ONE tensor of n elements:
  *   g' = g + wd*p; m = (1-b1) g' + b1 m; v = (1-b2) g'^2 + b2 v;

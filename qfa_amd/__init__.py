@@ -28,6 +28,8 @@ _LAZY = {
     "mask_absorbers": ("qfa_amd.absorbers", "mask_absorbers"),
     "bal_intervals": ("qfa_amd.absorbers", "bal_intervals"),
     "DLAScan": ("qfa_amd.dla", "DLAScan"),
+    "ObservedStack": ("qfa_amd.calibration", "ObservedStack"),
+    "calibrate": ("qfa_amd.calibration", "calibrate"),
 }
 
 

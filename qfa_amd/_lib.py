@@ -31,6 +31,7 @@ EXPORTS = (
     "qfa_absorber_workspace_bytes", "qfa_absorber_mask_f32",
     "qfa_dla_profiles_f32", "qfa_template_scan_workspace_bytes", "qfa_template_scan_f32",
     "qfa_segment_codes_f32", "qfa_bootstrap_workspace_bytes", "qfa_bootstrap_f64",
+    "qfa_obs_stack_doubles", "qfa_obs_stack_workspace_bytes", "qfa_obs_stack_f32", "qfa_calibrate_f32",
 )
 
 TAU_IDS = {"becker": 0, "fg": 1, "kamble": 2, "mock": 3}
@@ -43,6 +44,8 @@ F_FOREST_UNIT_W = 0x200    # qfa_forest_f32: stack with w = 1 instead of w = iva
 F_XI_UNIT_W = 0x400        # qfa_xi_f32: w = 1 on a used pixel instead of 1 / (v + sigma2_lss)
 F_PDF_RELATIVE = 0x800     # qfa_flux_pdf_f32: bin x = T / tbar(z) instead of x = T
 F_PDF_CLAMP = 0x1000       # qfa_flux_pdf_f32: x outside the range counts in the first / last bin
+F_OBS_UNIT_W = 0x2000      # qfa_obs_stack_f32: stack with w = 1 instead of w = ivar
+OBS_MODES = {"log": 0, "linear": 1}    # qfa_obs_bins_t.mode (QFA_OBS_*)
 ROW_TYPES = {"float32": 0, "float64": 1, "int32": 2}    # qfa_bootstrap_f64: QFA_ROW_* by the name of the rows' dtype
 ABS_LYB, ABS_CORRECT = 0x1, 0x2    # qfa_absorber_t.flags (QFA_ABS_*)
 F_EXACT_GRAD = 0x100       # exact gradients of mean NLL (opt-in; QFA.exact_gradients); the buffer carries the mode in slot 6
@@ -107,6 +110,10 @@ class PreprocessParams(C.Structure):   # qfa_preprocess_t
 
 class AbsorberParams(C.Structure):     # qfa_absorber_t
     _fields_ = [("t_min", C.c_double), ("b_kms", C.c_double), ("snr_lo", C.c_double), ("snr_hi", C.c_double), ("flags", C.c_uint)]
+
+
+class ObsBins(C.Structure):            # qfa_obs_bins_t
+    _fields_ = [("u0", C.c_double), ("du", C.c_double), ("nbin", C.c_int), ("p_lo", C.c_int), ("p_hi", C.c_int), ("mode", C.c_uint)]
 
 
 _lib = None
@@ -202,6 +209,10 @@ def lib():
         "qfa_segment_codes_f32": (i, [p, p, C.POINTER(Batch), p, i, i, i, C.POINTER(P1DParams), p, p]),
         "qfa_bootstrap_workspace_bytes": (sz, [i, i, i, i, i, i]),
         "qfa_bootstrap_f64": (i, [p, i, p, i, i, i, i, i, i, C.c_uint64, i64, C.c_uint, p, p, sz, p]),
+        "qfa_obs_stack_doubles": (sz, [i, i]),
+        "qfa_obs_stack_workspace_bytes": (sz, [i, i, i, i, i]),
+        "qfa_obs_stack_f32": (i, [p, p, C.POINTER(Batch), p, p, p, p, i, i, i, i, C.POINTER(ObsBins), f, C.c_uint, p, p, sz, p]),
+        "qfa_calibrate_f32": (i, [p, p, p, p, i, i, p, i, d, d, C.c_uint, d, p, p, p, p]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(h, name, None)

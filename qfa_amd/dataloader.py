@@ -156,13 +156,15 @@ class DeviceDataloader(object):
     @classmethod
     def from_observed(cls, wave, flux, ivar, offsets, zqso, wav_grid, batch_size, device, bad=None, names=None,
                       snr_min=-np.inf, snr_max=np.inf, z_min=-np.inf, z_max=np.inf, num_mask=np.inf, preprocess_kw=None,
-                      absorbers=None, **kw):
+                      absorbers=None, calibration=None, **kw):
         """Observed-frame spectra (the ragged form of ``qfa_amd.preprocess.preprocess``: observed wavelength, flux, inverse
         variance, pixel flags, z) to resident training storage without a host round trip: ``preprocess`` on the device,
         ``Preprocessed.select`` (the reference's catalogue criteria, QFA/dataloader.py:49), and the constructor on the device
         tensors.  ``names`` (N) become ``pathlist``; without them it holds the input row numbers.
         ``absorbers``: a dict of ``qfa_amd.absorbers.mask_absorbers``'s keywords (``dla``, ``sky``, ``rest``, ``t_min``, ...; ``dla``
-        and ``rest`` cover the N input spectra), applied between ``preprocess`` and ``select``.
+        and ``rest`` cover the N input spectra), applied between ``preprocess`` and ``select``.  ``calibration``: an
+        ``ObservedStack`` or the dict of ``io.read_calibration``; the spectra are divided by it (``Preprocessed.calibrate``) before
+        ``absorbers``.
         Data parallel (``rank`` / ``world`` in ``kw``): every rank is handed the whole input and preprocesses the spectra
         ``shard_bounds`` gives it; the selected counts are all-reduced, and since the selection of a shard need not have the size
         of the loader's shard of the selected set, the rows a rank lacks -- spectra next to its shard -- are preprocessed in a
@@ -178,6 +180,8 @@ class DeviceDataloader(object):
             a, b = int(off[rows_lo]), int(off[rows_hi])
             pre = preprocess(wave[a:b], flux[a:b], ivar[a:b], off[rows_lo:rows_hi + 1] - a, zqso[rows_lo:rows_hi], wav_grid,
                              bad=None if bad is None else bad[a:b], device=device, **pk)
+            if calibration is not None:
+                pre = pre.calibrate(calibration)
             return pre if absorbers is None else pre.mask_absorbers(**absorber_kw(rows_lo, rows_hi))
 
         def absorber_kw(rows_lo, rows_hi):

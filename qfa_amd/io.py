@@ -106,6 +106,36 @@ def read_intervals(path):
     return np.asarray(rows, dtype=np.float64).reshape(-1, 2)
 
 
+def write_intervals(path, intervals, header=None):
+    """Intervals ``[lo, hi)`` in Angstrom as ``read_intervals`` reads them back bit for bit: one per line, two columns, 17
+    significant digits; ``header``: a comment line"""
+    iv = np.asarray(intervals, dtype=np.float64).reshape(-1, 2)
+    with open(path, "w") as f:
+        if header:
+            f.write("# " + str(header).replace("\n", " ") + "\n")
+        for lo, hi in iv:
+            f.write(f"{float(lo)!r} {float(hi)!r}\n")
+    return path
+
+
+def write_calibration(path, table, half_width=10):
+    """A calibration vector as an npz holding ``u0``, ``du``, ``mode`` ('log' or 'linear') and ``cal`` (float64, at the bin centres
+    u0 + (j + 0.5) du).  ``table``: that dict, or an ``ObservedStack`` (its ``table(half_width)``)."""
+    t = table.table(half_width) if hasattr(table, "table") else table
+    np.savez(path, u0=np.float64(t["u0"]), du=np.float64(t["du"]), mode=np.asarray(str(t["mode"])),
+             cal=np.asarray(t["cal"], dtype=np.float64).reshape(-1))
+    return path
+
+
+def read_calibration(path):
+    """The dict u0, du, mode, cal of ``write_calibration`` (what ``qfa_amd.calibration.calibrate`` takes)"""
+    with np.load(path) as z:
+        missing = [k for k in ("u0", "du", "mode", "cal") if k not in z.files]
+        if missing:
+            raise ValueError(f"{path}: missing {missing}")
+        return {"u0": float(z["u0"]), "du": float(z["du"]), "mode": str(z["mode"]), "cal": z["cal"].astype(np.float64).reshape(-1)}
+
+
 def select_from_catalog(catalog, num, snr_min, snr_max, z_min, z_max, num_mask, output_dir=None, prefix="train"):
     """File names drawn from a catalogue csv with columns file, snr, z, num_mask
     (reference QFA/dataloader.py:48-55): the rows inside the S/N, redshift and masked-pixel limits,

@@ -22,6 +22,9 @@ Additions over the reference (none changes a reference call's result):
     and the covariance matrix between its flux bins per draw and z-bin (include/qfa_hip.h, qfa_flux_pdf_f32);
     ``variance_segments`` / ``variance_function`` / ``VarianceStack`` -- the variance of delta_F of the same segments in bins of the
     pipeline's noise variance and of z, and the fit of eta and sigma2_lss on it (include/qfa_hip.h, qfa_variance_f32);
+  * ``observed_residuals`` / ``observed_stack`` / ``ObservedStack`` -- the observed-frame residual stack, methods of the base class
+    ``ObservedFrame`` (calibration.py): the calibration vector and the sky-line mask from the data themselves (include/qfa_hip.h,
+    qfa_obs_stack_f32, qfa_calibrate_f32);
   * ``dla_profiles`` / ``template_scan`` / ``dla_scan`` / ``DLAScan`` -- the DLA finder, methods of the base class ``DLAFinder``
     (dla.py): a likelihood-ratio scan of every spectrum over a grid of absorber redshift and column density (include/qfa_hip.h,
     qfa_template_scan_f32), whose catalogue ``mask_absorbers`` takes;
@@ -47,6 +50,7 @@ from . import _lib
 from . import utils as _utils
 from .stacks import BootstrapStack, EMStats, ForestStack, P1DBandStack, P1DStack, PDFStack, VarianceStack, XiStack    # (re-exported)
 from .dla import DLAFinder, DLAScan    # (re-exported)
+from .calibration import ObservedFrame, ObservedStack    # (re-exported)
 from .statistics import ForestStatistics
 
 f32 = torch.float32
@@ -79,7 +83,7 @@ def _resolve_tau(tau):
     raise TypeError("tau must be a name, qfa_amd.utils.tau (partial) or a callable")
 
 
-class QFA(ForestStatistics, DLAFinder):
+class QFA(ForestStatistics, DLAFinder, ObservedFrame):
 
     def __init__(self, Nb: int, Nr: int, Nh: int, device: torch.device,
                  tau: Callable[[torch.Tensor], torch.Tensor] = default_tau,

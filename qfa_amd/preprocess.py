@@ -9,9 +9,11 @@ file form the reference's ``--type train --catalog ... --data_dir ...`` reads.
     python -m qfa_amd.preprocess --catalog observed.csv --data_dir raw/ --output_dir prepared/ [--lammin 1030 --lammax 1600
                                                                                                --loglam_delta 1e-4 ...]
                                 [--dla_catalog dla.csv --sky_mask sky.txt --dla_tmin 0.8 --dla_b 30 --no_dla_correct]
+                                [--calibration cal.npz]
 
 With ``--dla_catalog`` / ``--sky_mask`` the catalogued absorbers and bad observed wavelengths are masked and corrected
-(``qfa_amd.absorbers``) before the files are written.
+(``qfa_amd.absorbers``) before the files are written; with ``--calibration`` the spectra are first divided by that calibration
+vector (``qfa_amd.calibration``, the file of ``io.write_calibration``).
 """
 from __future__ import annotations
 
@@ -83,6 +85,18 @@ class Preprocessed(object):
         new = Preprocessed(fo, eo, self.zqso, self.norm, rec["snr"], rec["num_mask"], rec["n_valid"], rec["n_lead"], rec["n_trail"],
                            self.ok, self.wav_grid)
         new.n_absorber_masked, new.n_interval_masked = rec["n_absorber_masked"], rec["n_interval_masked"]
+        return new
+
+    def calibrate(self, table, **kw):
+        """These spectra divided by a calibration vector (``qfa_amd.calibration.calibrate``, whose keywords these are; ``table``: an
+        ``ObservedStack`` or the dict of ``io.read_calibration``): a new ``Preprocessed`` with the calibrated arrays and the count
+        ``n_uncalibrated`` as an attribute.  ``norm`` and ``snr`` are unchanged by a common factor and are carried over."""
+        from .calibration import calibrate
+        kw.setdefault("device", self.flux.device)
+        fo, eo, nu = calibrate(self.flux, self.error, self.zqso, self.wav_grid, table, **kw)
+        new = Preprocessed(fo, eo, self.zqso, self.norm, self.snr, self.num_mask, self.n_valid, self.n_lead, self.n_trail, self.ok,
+                           self.wav_grid)
+        new.n_uncalibrated = nu
         return new
 
     @staticmethod
@@ -223,12 +237,15 @@ def main(argv=None):
     ap.add_argument("--dla_tmin", type=float, default=0.8, help="mask where the absorbers' transmission is below this")
     ap.add_argument("--dla_b", type=float, default=30., help="Doppler parameter of the absorbers, km/s")
     ap.add_argument("--no_dla_correct", action="store_true", help="mask only: do not divide by the absorbers' profile")
+    ap.add_argument("--calibration", default=None, help="npz of io.write_calibration: divide the spectra by this calibration vector")
     a = ap.parse_args(argv)
     names = [str(x) for x in pd.read_csv(a.catalog).iloc[:, 0].values]
     wave, flux, ivar, bad, offsets, zqso = io.read_observed_npz([os.path.join(a.data_dir, n) for n in names], a.nprocs)
     grid = io.wavelength_grid(a.lammin, a.lammax, a.loglam_delta)
     pre = preprocess(wave, flux, ivar, offsets, zqso, grid, bad=bad, min_coverage=a.min_coverage, norm_window=tuple(a.norm_window),
                      norm_min_pixels=a.norm_min_pixels, snr_window=tuple(a.snr_window), device=a.device)
+    if a.calibration is not None:
+        pre = pre.calibrate(io.read_calibration(a.calibration))
     if a.dla_catalog is not None or a.sky_mask is not None:
         from .absorbers import AbsorberCatalog
         dla = None
