@@ -55,11 +55,18 @@ TAU_MODELS = {
 
 
 def tau_eff(z, which="becker", series=1):
-    """Mean Lyman optical depth (QFA/utils.py:149-171)."""
+    """Mean Lyman optical depth (QFA/utils.py:149-171).  ``which`` may also be the four constants themselves, (amp, scale,
+    expo, offset) with the series coefficient already in amp and offset -- the fields of the library's ``qfa_tau_t`` promoted
+    to float64, for judging a kernel against the constants it was actually given; ``series`` must then be 1."""
+    z = np.asarray(z)
+    if isinstance(which, (tuple, list)):
+        if len(which) != 4 or series != 1:
+            raise ValueError("a tau model given by its constants is (amp, scale, expo, offset) at series 1")
+        amp, scale, expo, offset = (float(c) for c in which)
+        return amp * ((1.0 + z) * scale) ** expo + offset
     if which not in TAU_MODELS:
         raise NotImplementedError(which)
     amp, scale, expo, offset = TAU_MODELS[which]
-    z = np.asarray(z)
     return (amp * ((1.0 + z) * scale) ** expo + offset) * LYMAN_COEFF[series - 1]
 
 

@@ -24,13 +24,13 @@ def profiles(wav_grid, lam_hi, dv_kms, nz, logn_lo, dlogn, n_logn, b_kms=30.0, l
     return V
 
 
-def scan_one(params, mu, flux, error, zabs, mask, V):
-    """(nll0, nll (nc,)) of one spectrum in float64; V (nc, Npix)"""
+def scan_one(params, mu, flux, error, zabs, mask, V, tau_which="becker", tau_series=1):
+    """(nll0, nll (nc,)) of one spectrum in float64; V (nc, Npix); the mean-optical-depth model as the oracle names it"""
     p = {k: np.asarray(params[k], dtype=np.float64) for k in ("F", "Psi", "omega", "tau0", "c0", "beta")}
     w = np.asarray(mask, dtype=bool)
     x = np.where(w, np.asarray(flux, dtype=np.float64), 0.0)
     sg = np.where(w, np.asarray(error, dtype=np.float64), 1.0)
-    A, zdep, _ = O.pixel_terms(p, sg, zabs)
+    A, zdep, _ = O.pixel_terms(p, sg, zabs, tau_which, tau_series)
     nb = p["omega"].shape[0]
     G = A * A * p["Psi"]
     G[:nb] += p["omega"] * zdep[:nb]
@@ -40,15 +40,15 @@ def scan_one(params, mu, flux, error, zabs, mask, V):
     return nll0, nll
 
 
-def scan(params, mu, flux, error, zabs, mask, V):
+def scan(params, mu, flux, error, zabs, mask, V, tau_which="becker", tau_series=1):
     """llr (B, nc), nll0 (B,), nll (B, nc) in float64"""
-    out = [scan_one(params, mu, flux[s], error[s], zabs[s], mask[s], V) for s in range(len(flux))]
+    out = [scan_one(params, mu, flux[s], error[s], zabs[s], mask[s], V, tau_which, tau_series) for s in range(len(flux))]
     nll0 = np.array([o[0] for o in out])
     nll = np.stack([o[1] for o in out])
     return nll0[:, None] - nll, nll0, nll
 
 
-def draw(params, mu, wav, nb, B, seed, snr=(20.0, 100.0), masks=True):
+def draw(params, mu, wav, nb, B, seed, snr=(20.0, 100.0), masks=True, tau_which="becker", tau_series=1):
     """B spectra drawn from the model (flux, error, zabs float32; mask bool; zqso float64), the way synthetic.make_batch_numpy draws
     them, with the S/N range as an argument; masked pixels hold -999"""
     rng = np.random.default_rng(seed)
@@ -59,7 +59,7 @@ def draw(params, mu, wav, nb, B, seed, snr=(20.0, 100.0), masks=True):
     zabs = ((1.0 + zq)[:, None] * wav[None, :nb] / LYA - 1.0).astype(np.float32)
     A, zdep = np.ones((B, n)), np.zeros((B, n))
     for s in range(B):
-        A[s], zdep[s], _ = O.pixel_terms(params, np.zeros(n), zabs[s])
+        A[s], zdep[s], _ = O.pixel_terms(params, np.zeros(n), zabs[s], tau_which, tau_series)
     s2n = np.exp(rng.uniform(np.log(snr[0]), np.log(snr[1]), size=B))
     sigma = np.abs(mu)[None, :] / s2n[:, None] * (0.8 + 0.4 * rng.random((B, n)))
     flux = A * (mu[None, :] + rng.standard_normal((B, F.shape[1])) @ F.T + np.sqrt(Psi)[None, :] * rng.standard_normal((B, n)))

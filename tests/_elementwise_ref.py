@@ -36,7 +36,7 @@ GRADIENT_BARS = {"F": (8 * 3.34e-5, 8 * 2.68e-3), "Psi": (8 * 2.62e-6, 8 * 3.84e
 # ----------------------------------------------------------------------------------------------------------------------
 # the gradient judge
 # ----------------------------------------------------------------------------------------------------------------------
-def gradient_units(p, batch, rows=None, dtype=np.float64, keys=GKEYS):
+def gradient_units(p, batch, rows=None, dtype=np.float64, keys=GKEYS, tau_which="becker", tau_series=1):
     """One pass of ``O.nll_and_grads_single`` over the spectra ``rows`` of ``batch`` (all of them by default).
     {key: {"sum": elementwise sum of the terms, "count": number of non-zero terms (as O.forward counts them),
            "abssum": elementwise sum of |terms|, "grad": sum / count (0/0 = NaN)}} plus "nll": the per-spectrum NLL."""
@@ -45,7 +45,7 @@ def gradient_units(p, batch, rows=None, dtype=np.float64, keys=GKEYS):
     nll = np.empty(len(rows))
     for j, r in enumerate(rows):
         nll[j], g = O.nll_and_grads_single(p, batch["delta"][r], batch["error"][r], batch["zabs"][r], batch["mask"][r],
-                                           dtype=dtype)
+                                           tau_which, tau_series, dtype=dtype)
         if out is None:
             out = {k: {"sum": np.zeros_like(g[k]), "count": np.zeros(g[k].shape), "abssum": np.zeros_like(g[k])} for k in keys}
         for k in keys:
@@ -118,12 +118,12 @@ def check_gradient(key, ours, ref, bar, counts=None, what=""):
 # ----------------------------------------------------------------------------------------------------------------------
 # the posterior judge
 # ----------------------------------------------------------------------------------------------------------------------
-def predict_rows(p, mu, batch, rows=None, dtype=np.float64):
+def predict_rows(p, mu, batch, rows=None, dtype=np.float64, tau_which="becker", tau_series=1):
     """``O.predict_single`` of every row, stacked: {"ll": (B,), "hmean": (B, k), "hcov": (B, k, k), "cont": (B, Npix),
     "unc": (B, Npix), "nvalid": (B,) unmasked pixels}."""
     rows = np.arange(len(batch["flux"])) if rows is None else np.asarray(rows)
-    res = [O.predict_single(p, mu, batch["flux"][r], batch["error"][r], batch["zabs"][r], batch["mask"][r], dtype=dtype)
-           for r in rows]
+    res = [O.predict_single(p, mu, batch["flux"][r], batch["error"][r], batch["zabs"][r], batch["mask"][r], tau_which,
+                            tau_series, dtype=dtype) for r in rows]
     out = {k: np.stack([np.asarray(x[i]) for x in res]) for i, k in enumerate(PKEYS)}
     out["nvalid"] = np.array([int(batch["mask"][r].sum()) for r in rows])
     return out

@@ -20,7 +20,7 @@ import numpy as np
 from oracle import qfa_oracle as orc
 
 
-def em_statistics(params, delta, error, zabs, mask, tau_which="becker", A_blue=None):
+def em_statistics(params, delta, error, zabs, mask, tau_which="becker", A_blue=None, tau_series=1):
     """Batch sums: dict S2 (Npix, Nh, Nh), S1 (Npix, Nh), cnt (Npix,), nll_sum, n, nll (B,)."""
     p = orc._as_params(params, np.float64)
     F = p["F"]
@@ -31,7 +31,8 @@ def em_statistics(params, delta, error, zabs, mask, tau_which="becker", A_blue=N
     nlls = np.zeros(len(delta))
     for s in range(len(delta)):
         w = np.asarray(mask[s], dtype=bool)
-        A, _, D = orc.pixel_terms(params, error[s], zabs[s], tau_which, 1, np.float64, None if A_blue is None else A_blue[s])
+        A, _, D = orc.pixel_terms(params, error[s], zabs[s], tau_which, tau_series, np.float64,
+                                  None if A_blue is None else A_blue[s])
         wD, d, _, C, y, _, nll = orc._lowrank_core(F, A, D, w, np.asarray(delta[s], dtype=np.float64))
         E = np.linalg.inv(C) + np.outer(y, y)
         S2 += (wD * A * A)[:, None, None] * E[None, :, :]
@@ -61,9 +62,9 @@ def em_update(F, st, ridge=0.0, damping=1.0):
     return out, skipped
 
 
-def em_step(params, delta, error, zabs, mask, ridge=0.0, damping=1.0, tau_which="becker"):
+def em_step(params, delta, error, zabs, mask, ridge=0.0, damping=1.0, tau_which="becker", tau_series=1):
     """(mean NLL at `params`, params with the updated F, statistics, rows skipped)"""
-    st = em_statistics(params, delta, error, zabs, mask, tau_which)
+    st = em_statistics(params, delta, error, zabs, mask, tau_which, tau_series=tau_series)
     newF, skipped = em_update(params["F"], st, ridge, damping)
     q = dict(params)
     q["F"] = newF
@@ -78,7 +79,7 @@ def pair_indices(nh):
     return np.triu_indices(nh)
 
 
-def em_terms(params, delta, error, zabs, mask, tau_which="becker", A_blue=None, dtype=np.float64):
+def em_terms(params, delta, error, zabs, mask, tau_which="becker", A_blue=None, dtype=np.float64, tau_series=1):
     """``em_statistics`` restated as two matrix products over the spectra, after the per-spectrum E-step of the oracle:
     S2 = W2^T (Npix x B) @ E (B x pairs of N_h), S1 = W1^T @ Y with W2 = wD A^2, W1 = wD A delta -- and the same products of the
     absolute values: absS2[i, a, b] = sum_s |beta_si E_s[a, b]|, absS1[i, a] = sum_s |gamma_si y_s[a]|, the scale an element's
@@ -98,7 +99,7 @@ def em_terms(params, delta, error, zabs, mask, tau_which="becker", A_blue=None, 
     cnt = np.zeros(npix)
     for s in range(B):
         w = np.asarray(mask[s], dtype=bool)
-        A, _, D = orc.pixel_terms(params, error[s], zabs[s], tau_which, 1, dtype, None if A_blue is None else A_blue[s])
+        A, _, D = orc.pixel_terms(params, error[s], zabs[s], tau_which, tau_series, dtype, None if A_blue is None else A_blue[s])
         with np.errstate(invalid="ignore", divide="ignore", over="ignore"):      # (junk under the mask: selected away)
             wD, d, _, C, y, _, nll = orc._lowrank_core(F, A, D, w, np.asarray(delta[s], dtype=dtype))
         E = np.linalg.inv(C) + np.outer(y, y)

@@ -18,14 +18,14 @@ import numpy as np
 from oracle import qfa_oracle as orc
 
 
-def exact_single(params, delta, error, zabs, mask, tau_which="becker", A_blue=None):
+def exact_single(params, delta, error, zabs, mask, tau_which="becker", A_blue=None, tau_series=1):
     """One spectrum: (nll, grads, absum) -- raw (un-normalised) exact gradients and, for the scalar sums, the sum of the
     absolute values of their terms (the scale a float32 implementation is judged against)."""
     p = orc._as_params(params, np.float64)
     F = p["F"]
     Nb = p["omega"].shape[0]
     w = np.asarray(mask, dtype=bool)
-    A, zdep, D = orc.pixel_terms(params, error, zabs, tau_which, 1, np.float64, A_blue)
+    A, zdep, D = orc.pixel_terms(params, error, zabs, tau_which, tau_series, np.float64, A_blue)
     wD, d, M, C, y, u, nll = orc._lowrank_core(F, A, D, w, np.asarray(delta, dtype=np.float64))
     Cinv = np.linalg.inv(C)
     q = np.einsum("ia,ab,ib->i", F, Cinv, F)
@@ -47,14 +47,14 @@ def exact_single(params, delta, error, zabs, mask, tau_which="becker", A_blue=No
     return nll, grads, absum
 
 
-def exact_forward(params, delta, error, zabs, mask, tau_which="becker", A_blue=None, normalize=True):
+def exact_forward(params, delta, error, zabs, mask, tau_which="becker", A_blue=None, normalize=True, tau_series=1):
     """Batch: (loss, grads, absum).  loss = mean NLL; grads = sum over spectra / B (normalize=False: the raw sums);
     absum: the scalar terms' sum of absolute values over the batch, divided likewise."""
     B = len(delta)
     sums, absum, loss = None, {"tau0": 0.0, "c0": 0.0, "beta": 0.0}, 0.0
     for s in range(B):
         nll, g, a = exact_single(params, delta[s], error[s], zabs[s], mask[s], tau_which,
-                                 None if A_blue is None else A_blue[s])
+                                 None if A_blue is None else A_blue[s], tau_series)
         loss += nll
         sums = {k: np.array(v, dtype=np.float64) for k, v in g.items()} if sums is None else \
             {k: sums[k] + g[k] for k in sums}
