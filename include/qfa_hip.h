@@ -174,6 +174,10 @@ int qfa_nll_grad_events_f32(const qfa_params_t *p, const qfa_batch_t *b, const q
  * the per-range sums always leave through such rows, inside the workspace when slab == NULL: no float atomics
  * there in either mode.) */
 size_t qfa_det_slab_bytes(int B, int Npix, int Nb, int Nh);
+/* The split of the pixel-resident pass 2 (N_h <= 16) on this device: `ranges` ranges of `range_groups` groups of 16 spectra each
+ * (the last range takes what is left; range_groups is even at N_h = 9..16, where the pass contracts pairs of groups).
+ * deterministic != 0: the plan of a call with a slab.  Host only. */
+int qfa_pixres_plan(int B, int Npix, int Nh, int deterministic, int *ranges, int *range_groups);
 int qfa_nll_grad_det_f32(const qfa_params_t *p, const qfa_batch_t *b, const qfa_tau_t *tau,
                          int B, int Npix, int Nb, int Nh,
                          float *nll, float *accum, void *workspace, size_t workspace_bytes,

@@ -14,7 +14,7 @@ LIB_PATH = os.path.join(_HERE, "libqfa_hip.so")
 
 EXPORTS = (
     "qfa_abi_version", "qfa_tau_model", "qfa_workspace_bytes", "qfa_accum_floats",
-    "qfa_nll_grad_f32", "qfa_nll_grad_events_f32", "qfa_nll_grad_det_f32", "qfa_nll_grad_ex_f32", "qfa_predict_ex_f32", "qfa_det_slab_bytes", "qfa_finalize_grads_f32", "qfa_predict_f32", "qfa_predict_events_f32",
+    "qfa_nll_grad_f32", "qfa_nll_grad_events_f32", "qfa_nll_grad_det_f32", "qfa_nll_grad_ex_f32", "qfa_predict_ex_f32", "qfa_det_slab_bytes", "qfa_pixres_plan", "qfa_finalize_grads_f32", "qfa_predict_f32", "qfa_predict_events_f32",
     "qfa_adam_clip_f32",
     "qfa_adam_clip_multi_f32", "qfa_clip_f32", "qfa_smooth_f32", "qfa_tau_f32", "qfa_tauhi_f32", "qfa_omega_func_f32", "qfa_woodbury_f32", "qfa_build_batch_f32", "qfa_mu_estimate_f64",
     "qfa_mu_sums_f64", "qfa_mu_finish_f64", "qfa_build_resident_f32", "qfa_finalize_adam_clip_f32", "qfa_zabs_factor_f32",
@@ -209,6 +209,7 @@ def lib():
         "qfa_segment_codes_f32": (i, [p, p, C.POINTER(Batch), p, i, i, i, C.POINTER(P1DParams), p, p]),
         "qfa_bootstrap_workspace_bytes": (sz, [i, i, i, i, i, i]),
         "qfa_bootstrap_f64": (i, [p, i, p, i, i, i, i, i, i, C.c_uint64, i64, C.c_uint, p, p, sz, p]),
+        "qfa_pixres_plan": (i, [i, i, i, i, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
         "qfa_obs_stack_doubles": (sz, [i, i]),
         "qfa_obs_stack_workspace_bytes": (sz, [i, i, i, i, i]),
         "qfa_obs_stack_f32": (i, [p, p, C.POINTER(Batch), p, p, p, p, i, i, i, i, C.POINTER(ObsBins), f, C.c_uint, p, p, sz, p]),

@@ -111,6 +111,15 @@ int qfa_nll_grad_events_f32(const qfa_params_t *p, const qfa_batch_t *b, const q
     return qfa_nll_grad_ex_f32(p, b, tau, B, Npix, Nb, Nh, nll, accum, workspace, workspace_bytes, nullptr, 0, 0u, stream, events);
 }
 
+int qfa_pixres_plan(int B, int Npix, int Nh, int deterministic, int *ranges, int *range_groups) {
+    if (!ranges || !range_groups) return QFA_E_NULL;
+    if (B < 1 || Npix < 1 || Nh < 1 || Nh > 16) return QFA_E_SIZE;
+    const int KP = kp_for(Nh), mr = deterministic ? (int)det_rows(B) : (1 << 30);
+    *ranges = qfa_gt_ranges(KP, B, Npix, mr);
+    *range_groups = qfa_gt_range_groups(KP, B, Npix, mr);
+    return 0;
+}
+
 size_t qfa_det_slab_bytes(int B, int Npix, int Nb, int Nh) {
     if (B < 1 || Npix < 1 || Nb < 0 || Nb > Npix || Nh < 1 || Nh > 32) return 0;
     return det_slab_bytes(B, Npix, Nb, Nh);

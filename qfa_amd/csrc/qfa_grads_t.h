@@ -15,8 +15,8 @@
 //   * beta / gamma never leave the lane: stage 2 leaves them in exactly the layout stage 3's B operand wants;
 //   * F enters once, at the end: accF[px][b] = sum_a F[px][a] W[px][a][b] + the gamma term, then ONE atomic (or slab
 //     store) per output element and spectra range -- no partial sums in LDS, no flush in the loop.
-// Per (16 spectra x 16 pixels) a wave issues 18 + 35 MFMAs (round 5: two float16 pieces and three products per contraction,
-// qfa_common.h "float16 pieces", qfa_gt_layout.h; 36 + 51 with bf16 pieces), 12 + 19 ds_read_b128 for
+// Per (16 spectra x 16 pixels) a wave issues 18 + 27 MFMAs (two float16 pieces and three products per contraction, stage 3 over
+// PAIRS of groups: qfa_common.h "float16 pieces", qfa_gt_layout.h; 18 + 35 per single group, 36 + 51 with bf16 pieces), 12 + 18 ds_read_b128 for
 // their streamed operands, stage 2 of four elements per lane, one float16 split (beta) and one bf16 split (gamma).
 //
 // Workgroup = 512 threads = 8 waves = 8 tiles (strided over the pixel axis: tile pb + PB w, so that every workgroup
@@ -231,10 +231,14 @@ __global__ __launch_bounds__(512, 2) void k_grads_t(qfa_params_t p, qfa_batch_t 
     float gPsi[TPW], gOm[TPW], sA[TPW];
     int cnt[TPW];
     f32x4 betaR[TPW], gamR[TPW];                            // stage 2 -> stage 3 (across one barrier)
+    // stage 3's B operands, the packed float16 pieces of beta of a PAIR of groups: BH = {h01 h23 (even group) | h01 h23 (odd group)},
+    // BM the m pieces likewise; stage 3 of a group packs its half (they live across the walk: a pair's contraction spans two steps)
+    u32x4 BH[TPW], BM[TPW];
 #pragma unroll
     for (int j = 0; j < TPW; ++j) {
 #pragma unroll
         for (int a = 0; a < GT::NWT; ++a) W[j][a] = f32x4{0.f, 0.f, 0.f, 0.f};
+        BH[j] = BM[j] = u32x4{0u, 0u, 0u, 0u};
         gacc[j] = betaR[j] = gamR[j] = f32x4{0.f, 0.f, 0.f, 0.f};
         gPsi[j] = gOm[j] = sA[j] = 0.f;
         cnt[j] = 0;
@@ -543,7 +547,7 @@ __global__ __launch_bounds__(512, 2) void k_grads_t(qfa_params_t p, qfa_batch_t 
     };
     auto issue_Z = [&](int t) __attribute__((always_inline)) {
         const unsigned char *src = uniform_ptr(PST + (size_t)(g0 + t) * GT::STATE_B + GT::S1P_B + z_first * 1024);
-        const unsigned dst = wave_uniform(lds_addr(lds + GT::L_Z + (t & 1) * GT::ZP_B + z_first * 1024));
+        const unsigned dst = wave_uniform(lds_addr(lds + GT::L_Z + (t & (GT::ZRING - 1)) * GT::ZP_B + z_first * 1024));
         for (int j = 0; j < z_req; ++j) glds16a(src + 1024 * j, (unsigned)lane * 16u, dst + 1024 * j);
     };
 
@@ -810,92 +814,126 @@ __global__ __launch_bounds__(512, 2) void k_grads_t(qfa_params_t p, qfa_batch_t 
         else stage2_t(std::false_type{}, full_tag, t, par, pt);
     };
 
-    // ---- stage 3 of group t: W[a] += Z pieces x the lane's own beta pieces (K = spectrum), the gamma term likewise; the Z
-    // operands of a column tile are read once for the wave's TPW tiles
+    // ---- stage 3 of step t: the gamma term of group t, and W[a] += Z pieces x the lane's own beta pieces (K = the 32 spectra of a
+    // PAIR of groups) over HALF of a pair's column tiles -- the Z area of group t - 1 (qfa_gt_layout.h), whose pair has both its
+    // betas by now:
+    //   t even (HALF 0): the upper HT column tiles of the pair (t - 2, t - 1), with BH / BM as the last two steps left them; THEN the
+    //                    pieces of beta (t) replace those of beta (t - 2) in the operands' low halves;
+    //   t odd  (HALF 1): the pieces of beta (t) go into the operands' high halves, then the lower HT column tiles of the pair (t - 1, t).
+    // Three full MFMAs per column tile ({Z_h | Z_h'} x {b_h | b_h'}, {Z_m | Z_m'} x {b_h | b_h'}, {Z_h | Z_h'} x {b_m | b_m'}) where a
+    // group on its own took four half-used ones per two tiles' worth.  Step 0 meets zeros (BH = BM = 0 and a zeroed ring slot, prologue);
+    // the last pair of the range is finished behind the walk (drain).  The Z operands of a column tile are read once for the wave's TPW tiles.
     // The staging requests of group t + 2 (buffer t & 1, read for the last time by stage 2 (t)) are issued here: the running-pointer
     // form one request per column tile in front of the part's pieces, every other form (the first two groups are the prologue's)
     // as a block at the start.  They have the rest of the step to land: every wave waits for everything at the next barrier.
     const int nfull = max(0, min(n, (B >> 4) - g0));         // groups of the range with 16 spectra
     // MODE (mode_tag): 0 = any step; 1 = group t + 2 belongs to the range (its requests are unconditional); 2 = and it is a full
-    // group on a wave with running pointers (runok): one request per site, no general-path code in the stage
-    auto stage3 = [&](auto mode_tag, int t, int par, const auto &pt) __attribute__((always_inline)) {
-        constexpr int MODE = decltype(mode_tag)::value;
+    // group on a wave with running pointers (runok): one request per site, no general-path code in the stage; 3 = behind the walk
+    // (drain): the contraction alone -- no requests, no pieces, no gamma term, beta (t) is taken as it stands in betaR
+    auto stage3 = [&](auto mode_tag, auto half_tag, int t, int par, const auto &pt) __attribute__((always_inline)) {
+        constexpr int MODE = decltype(mode_tag)::value, HALF = decltype(half_tag)::value;
+        constexpr bool DRAIN = MODE == 3;
+        constexpr bool PAIR = GT::PAIR;
+        // (without PAIR: the group's own NWT column tiles in every step, two MFMAs {Z_h | Z_m} x {b_h | b_h}, {Z_h | Z_m} x {b_m | 0} each)
+        constexpr int HT = PAIR ? GT::HT : GT::NWT;
         static_assert(MODE != 2 || RUNP, "running pointers");
+        static_assert(PAIR || !(RUNP || DRAIN), "running pointers and the drain belong to the pair form");
         __builtin_amdgcn_s_setprio(2);
-        const bool run = MODE == 2 || (RUNP && runok && t + 2 < nfull);
-        if constexpr (MODE != 2) {
+        const bool run = MODE == 2 || (!DRAIN && RUNP && runok && t + 2 < nfull);
+        if constexpr (MODE != 2 && !DRAIN) {
             if ((MODE == 1 || t + 2 < n) && !run) {
                 // (batch order: the rows follow from t -- no LDS read; indexed form: stage 2 (t) read them out of the buffer)
                 const RowIdx ri = IDX ? ri_next : read_rows(t + 2, par, std::false_type{});
                 stage_spectra(t + 2, par, ri, std::false_type{});
             }
         }
-        if (!RUNP) part_begin(pt);
-        const unsigned char *zp = lds + GT::L_Z + par * GT::ZP_B + lane * 16;
-        // bf16: three MFMAs per column tile ({l | h} x {h | l}, {h | m} x {m | m}, {h | m} x {h | h}: six products, K = 16 spectra x 2
-        // piece slots); float16: two ({h | m} x {h | h} and {h | m} x {m | 0}: three products)
-        u32x4 bhl[TPW], bmm[TPW], bhh[TPW];
+        if (!RUNP && !DRAIN) part_begin(pt);
+        // column tiles: ring slot of group t - 1; p operands: ring slot of group t
+        // (without PAIR both are the group's own slot, par: a literal in the unrolled walk)
+        const unsigned char *zp = lds + GT::L_Z + (PAIR ? (unsigned)(t + GT::ZRING - 1) & (GT::ZRING - 1) : (unsigned)par) * GT::ZP_B + lane * 16;
+        const unsigned char *pp = lds + GT::L_Z + (PAIR ? (unsigned)t & (GT::ZRING - 1) : (unsigned)par) * GT::ZP_B + GT::Z_B + lane * 16;
+        auto pack = [&]() __attribute__((always_inline)) {
 #pragma unroll
-        for (int j = 0; j < TPW; ++j) {
-            unsigned h01, m01, h23, m23;
-            split2h(betaR[j][0], betaR[j][1], h01, m01);
-            split2h(betaR[j][2], betaR[j][3], h23, m23);
-            bhh[j] = u32x4{h01, h23, h01, h23}; bmm[j] = u32x4{m01, m23, 0u, 0u}; bhl[j] = bhh[j];
-        }
+            for (int j = 0; j < TPW; ++j) {
+                unsigned h01, m01, h23, m23;
+                split2h(betaR[j][0], betaR[j][1], h01, m01);
+                split2h(betaR[j][2], betaR[j][3], h23, m23);
+                if constexpr (PAIR) {
+                    BH[j][2 * HALF] = h01; BH[j][2 * HALF + 1] = h23;
+                    BM[j][2 * HALF] = m01; BM[j][2 * HALF + 1] = m23;
+                } else {
+                    BH[j] = u32x4{h01, h23, h01, h23}; BM[j] = u32x4{m01, m23, 0u, 0u};
+                }
+            }
+        };
+        if (HALF == 1 || !PAIR) pack();
         // The Z operands of column tile a + ZD are requested in front of the MFMAs of tile a, and fences keep it that way (round 5):
         // left to itself hipcc (which schedules this unit for register pressure) asks for tile a + 1 behind the first MFMA of
         // tile a -- 32 cycles in front of its use, an LDS round trip in the open per column tile: 1 670 cycles for 816 of MFMAs.
-        constexpr int ZD = 3 < GT::NWT ? 3 : GT::NWT, ZR = ZD + 1;      // column tiles requested ahead
+        constexpr int ZD = 3 < HT ? 3 : HT, ZR = ZD + 1;      // column tiles requested ahead
         u32x4 zop[ZR][2];
-        auto rdz = [&](int a) __attribute__((always_inline)) {                                   // (a == NWT: the p operands, always two)
-            const unsigned char *q = zp + (a < GT::NWT ? a * GT::ZT_B : GT::Z_B);
+        auto rdz = [&](int a) __attribute__((always_inline)) {                                   // (a == HT: the p operands)
+            const unsigned char *q = a < HT ? zp + a * GT::ZT_B : pp;
             zop[a % ZR][0] = *reinterpret_cast<const u32x4 *>(q);
-            if (a == GT::NWT) zop[a % ZR][1] = *reinterpret_cast<const u32x4 *>(q + 1024);
+            if (PAIR || a == HT) zop[a % ZR][1] = *reinterpret_cast<const u32x4 *>(q + 1024);
         };
 #pragma unroll
         for (int a = 0; a < ZD; ++a) rdz(a);
 #pragma unroll
-        for (int a = 0; a < GT::NWT; ++a) {
-            if (a + ZD <= GT::NWT) rdz(a + ZD);
+        for (int a = 0; a < HT; ++a) {
+            if (a + ZD < HT || (a + ZD == HT && !DRAIN)) rdz(a + ZD);
             __builtin_amdgcn_sched_barrier(0);
-            if constexpr (RUNP) {
-                // RQS = 2 column tiles between two staging requests: tiles 0, RQS, 2 RQS, 3 RQS carry a request each (the third: blue
-                // tiles only); behind them the part's pieces (at most 7)
-                constexpr int RQS = 2, P0 = 3 * RQS + 1;
-                static_assert(P0 + 7 <= GT::NWT, "piece sites");
-                if (a < P0) { if (a % RQS == 0 && run && (a / RQS != 2 || blueTile)) stage_req(par, a / RQS); }
+            if constexpr (DRAIN) {
+            } else if constexpr (RUNP) {
+                // column tiles 0 .. 3 carry a staging request each (the third: blue tiles only); behind them the part's pieces
+                constexpr int P0 = 4;
+                static_assert(P0 + PartZ::MAX <= HT && P0 + PartS::MAX <= HT, "piece sites");
+                if (a < P0) { if (run && (a != 2 || blueTile)) stage_req(par, a); }
                 else {
                     if (a == P0) part_begin(pt);
-                    if (a - P0 < 7) piece(pt, a - P0);
+                    piece(pt, a - P0);
                 }
-            } else if (a % 2 == 0) piece(pt, a / 2);
-            const u32x4 &Z1 = zop[a % ZR][0];
+            } else {
+                static_assert(PartZ::MAX <= GT::HT && PartS::MAX <= GT::HT, "piece sites");
+                if (PAIR) piece(pt, a);
+                else if (a % 2 == 0) piece(pt, a / 2);
+            }
+            const u32x4 &ZH = zop[a % ZR][0], &ZM = zop[a % ZR][1];
+            constexpr int wa0 = PAIR && !HALF ? HT : 0;        // the area's column tiles of W
 #pragma unroll
             for (int j = 0; j < TPW; ++j) {
-                W[j][a] = xdlh(Z1, bhh[j], xdlh(Z1, bmm[j], W[j][a]));
+                if constexpr (PAIR) W[j][wa0 + a] = xdlh(ZH, BH[j], xdlh(ZM, BH[j], xdlh(ZH, BM[j], W[j][wa0 + a])));      // (small terms first)
+                else W[j][a] = xdlh(ZH, BH[j], xdlh(ZH, BM[j], W[j][a]));
             }
             __builtin_amdgcn_sched_barrier(0);
         }
-        const u32x4 &P1 = zop[GT::NWT % ZR][0], &P2 = zop[GT::NWT % ZR][1];
+        if constexpr (!DRAIN) {
+            if (HALF == 0 && PAIR) pack();
+            const u32x4 &P1 = zop[HT % ZR][0], &P2 = zop[HT % ZR][1];
 #pragma unroll
-        for (int j = 0; j < TPW; ++j) {
-            unsigned h01, m01, l01, h23, m23, l23;
-            split2(gamR[j][0], gamR[j][1], h01, m01, l01);
-            split2(gamR[j][2], gamR[j][3], h23, m23, l23);
-            const u32x4 ghl = {h01, h23, l01, l23}, gmm = {m01, m23, m01, m23}, ghh = {h01, h23, h01, h23};
-            gacc[j] = xdl(P2, ghh, xdl(P2, gmm, xdl(P1, ghl, gacc[j])));                            // sum_s p_s[b] gamma[s][px]
+            for (int j = 0; j < TPW; ++j) {
+                unsigned h01, m01, l01, h23, m23, l23;
+                split2(gamR[j][0], gamR[j][1], h01, m01, l01);
+                split2(gamR[j][2], gamR[j][3], h23, m23, l23);
+                const u32x4 ghl = {h01, h23, l01, l23}, gmm = {m01, m23, m01, m23}, ghh = {h01, h23, h01, h23};
+                gacc[j] = xdl(P2, ghh, xdl(P2, gmm, xdl(P1, ghl, gacc[j])));                            // sum_s p_s[b] gamma[s][px]
+            }
+            advance_run();
         }
-        advance_run();
         __builtin_amdgcn_s_setprio(0);
     };
+    using H0 = std::integral_constant<int, 0>;
+    using H1 = std::integral_constant<int, 1>;
 
     // ---- the walk: ONE barrier per group, and the two waves of a SIMD (w, w + 4) a stage apart in the same rotation:
     //   waves 0..3, step t: stage 3 (t)  [Z part of t + 1]   stage 1 (t + 1)  [S1 part of t + 2]   stage 2 (t + 1)
     //   waves 4..7, step t: stage 2 (t)  [Z part of t + 1]   stage 3 (t)      [S1 part of t + 2]   stage 1 (t + 1)
     // so that one wave's VALU phase (stage 2) meets the other's MFMAs.  The barrier of step t says: the Z part of group t
-    // and the S1 part of group t + 1 (requested during step t - 1) have landed, and nobody reads Z(t - 1) and S1(t) any
-    // more -- their slots take Z(t + 1) and S1(t + 2), piece by piece between the MFMA groups / elements of the stages.
-    // Round 5: the staging requests of group t + 2 sit in stage 3 (t) of EVERY wave (one per second column tile, between its
+    // and the S1 part of group t + 1 (requested during step t - 1) have landed, and nobody reads S1(t) any more, nor the column
+    // tiles of Z(t - 2) (PAIR: stage 3 of step t reads the tiles of Z(t - 1) and the p operands of Z(t); the Z ring has four slots,
+    // qfa_gt_layout.h) -- the slots (t + 1) & 3 and t & 1 take Z(t + 1) and S1(t + 2), piece by piece between the MFMA groups /
+    // elements of the stages.
+    // Round 5: the staging requests of group t + 2 sit in stage 3 (t) of EVERY wave (one per column tile, between its
     // MFMAs) and the Z pieces of waves 4..7 in stage 1; every wave waits vmcnt(0) in front of the step's barrier -- nothing stays in
     // flight across it (rounds 3-4: the requests were a block in stage 2 and waves 0..3 left theirs in flight by a counted wait).
     // (Measured forms of this loop, profiles/r3_ablation_pass2.txt: a barrier per half-step with waves 4..7 half a step
@@ -910,6 +948,9 @@ __global__ __launch_bounds__(512, 2) void k_grads_t(qfa_params_t p, qfa_batch_t 
         issue_S1(0);
         if (n > 1) issue_S1(1);
         issue_Z(0);
+        // step 0 contracts the Z area "of group -1" with beta = 0: zeros, so that nothing stale meets the MFMA (NaN x 0)
+        for (int i = tid * 16; GT::PAIR && i < GT::Z_B; i += 512 * 16)
+            *reinterpret_cast<u32x4 *>(lds + GT::L_Z + (GT::ZRING - 1) * GT::ZP_B + i) = u32x4{0u, 0u, 0u, 0u};
     }
     dma_wait<0>();
     step_barrier();
@@ -919,7 +960,7 @@ __global__ __launch_bounds__(512, 2) void k_grads_t(qfa_params_t p, qfa_batch_t 
         stage1(0, none);
         if (lead) stage2(std::false_type{}, 0, 0, none);
     }
-    // The parts' source pointers and ring slots run along the walk: the Z part of group t + 1 goes to slot (t + 1) & 1, the S1
+    // The parts' source pointers and ring slots run along the walk: the Z part of group t + 1 goes to slot (t + 1) & 3, the S1
     // part of group t + 2 to slot t & 1.  (One walk for every kind of wave: instantiated per (blue, duty) -- six loops -- hipcc
     // ran out of registers and spilled the image pieces.)
     auto walk = [&]() __attribute__((always_inline)) {
@@ -928,97 +969,127 @@ __global__ __launch_bounds__(512, 2) void k_grads_t(qfa_params_t p, qfa_batch_t 
         const unsigned char *ssrc = uniform_ptr(PST + (size_t)(g0 + 2) * GT::STATE_B + s1_first * 1024 + PBIAS);
         const unsigned zd0 = wave_uniform(lds_addr(lds + GT::L_Z + z_first * 1024)) + PBIAS;
         const unsigned sd0 = wave_uniform(lds_addr(lds + GT::L_S1 + s1_first * 1024)) + PBIAS;
-        unsigned zdst = zd0 + GT::ZP_B, sdst = sd0;                                        // t = 0: Z(1) -> slot 1, S1(2) -> slot 0
-        auto next = [&]() __attribute__((always_inline)) {
-            zsrc += GT::STATE_B; ssrc += GT::STATE_B;
-            zdst = 2 * zd0 + GT::ZP_B - zdst; sdst = 2 * sd0 + GT::S1P_B - sdst;
-        };
+        const int n2 = n;
+        auto zslot = [&](int u) __attribute__((always_inline)) { return zd0 + ((unsigned)u & (GT::ZRING - 1)) * GT::ZP_B; };   // of group u
         // The steady state, two groups (an even and an odd ring slot) per iteration: the steps t < nst, in which the groups t + 1
         // and t + 2 belong to the range -- every part has its full count, no stage is conditional -- and, with running pointers
         // (RUNP, a wave with runok), t + 2 is a full group as well: the stages run in their FULL / MODE 2 form, which holds no
         // general-path code, and the slot of every LDS address is a literal.  What is left of the range (its last two or three
         // groups, the partial last group of a batch; every step of a ragged or straddling tile) takes the general step
-        // behind it, which starts at an even t: zdst / sdst stand where they stood at t = 0.
+        // behind it, which starts at an even t and is written for an even and an odd step as well (stage 3's half is a literal:
+        // it indexes W).
         constexpr int SMODE = RUNP ? 2 : 1;
         using SFull = std::integral_constant<bool, RUNP>;
         using SMode = std::integral_constant<int, SMODE>;
         const int nst = (RUNP ? (runok ? max(0, nfull - 2) : 0) : max(0, n - 2)) & ~1;
-        const unsigned zdst_s[2] = {zd0 + GT::ZP_B, zd0}, sdst_s[2] = {sd0, sd0 + GT::S1P_B};      // slot of Z(t + 1), S1(t + 2) at step parity 0, 1
-        auto steady_lead = [&](int t, int par) __attribute__((always_inline)) {
+        const unsigned sdst_s[2] = {sd0, sd0 + GT::S1P_B};      // slot of S1(t + 2) at step parity 0, 1
+        auto steady_lead = [&](int t, auto half_tag) __attribute__((always_inline)) {
+            constexpr int par = decltype(half_tag)::value;
             dma_wait<0>();
             GTS(0)
             step_barrier();
             GTS(1)
-            const PartZ pz{{zsrc, zdst_s[par], z_req}};
+            const PartZ pz{{zsrc, zslot(t + 1), z_req}};
             const PartS ps{{ssrc, sdst_s[par], s1_req}};
-            stage3(SMode{}, t, par, pz);
+            stage3(SMode{}, half_tag, t, par, pz);
             GTS(4)
             stage1(par ^ 1, ps);
             stage2(SFull{}, t + 1, par ^ 1, none);
             GTS(3)
             zsrc += GT::STATE_B; ssrc += GT::STATE_B;
         };
-        auto steady_rear = [&](int t, int par) __attribute__((always_inline)) {
+        auto steady_rear = [&](int t, auto half_tag) __attribute__((always_inline)) {
+            constexpr int par = decltype(half_tag)::value;
             dma_wait<0>();
             GTS(0)
             step_barrier();
             GTS(1)
-            const PartZ pz{{zsrc, zdst_s[par], z_req}};
+            const PartZ pz{{zsrc, zslot(t + 1), z_req}};
             const PartS ps{{ssrc, sdst_s[par], s1_req}};
             stage2(SFull{}, t, par, none);
             GTS(3)
-            stage3(SMode{}, t, par, ps);
+            stage3(SMode{}, half_tag, t, par, ps);
             GTS(4)
             stage1(par ^ 1, pz);
             zsrc += GT::STATE_B; ssrc += GT::STATE_B;
         };
         using Any = std::false_type;
         using AnyMode = std::integral_constant<int, 0>;
+        // (without PAIR stage 3 has no halves: one general step for every t, its slot a run-time value)
+        auto general_lead = [&](int t, auto half_tag) __attribute__((always_inline)) {
+            const int par = GT::PAIR ? decltype(half_tag)::value : (t & 1);
+            dma_wait<0>();       // (round 5: the staging requests sit in stage 3, the first stage of the step -- nothing is left in flight)
+            GTS(0)
+            step_barrier();
+            GTS(1)
+            const PartZ pz{{zsrc, zslot(t + 1), t + 1 < n2 ? z_req : 0}};
+            const PartS ps{{ssrc, sdst_s[par], t + 2 < n ? s1_req : 0}};
+            stage3(AnyMode{}, half_tag, t, par, pz);
+            GTS(4)
+            if (t + 1 < n) {
+                stage1(par ^ 1, ps);
+                stage2(Any{}, t + 1, par ^ 1, none);
+                GTS(3)
+            }
+            zsrc += GT::STATE_B; ssrc += GT::STATE_B;
+        };
+        auto general_rear = [&](int t, auto half_tag) __attribute__((always_inline)) {
+            const int par = GT::PAIR ? decltype(half_tag)::value : (t & 1);
+            dma_wait<0>();
+            GTS(0)
+            step_barrier();
+            GTS(1)
+            const PartZ pz{{zsrc, zslot(t + 1), t + 1 < n2 ? z_req : 0}};
+            const PartS ps{{ssrc, sdst_s[par], t + 2 < n ? s1_req : 0}};
+            // waves 4..7: the Z part's pieces between the MFMAs of stage 1 instead of between the elements of stage 2
+            // (a piece issued in stage 2 -- VALU work, nothing to hide behind -- cost the issuing wave ~100 cycles: stage 2 of a RED
+            // duty wave, one reciprocal per element, took 1 134 cycles with its seven pieces; between MFMAs they are free)
+            stage2(Any{}, t, par, none);
+            GTS(3)
+            stage3(AnyMode{}, half_tag, t, par, ps);
+            GTS(4)
+            if (t + 1 < n) stage1(par ^ 1, pz);
+            zsrc += GT::STATE_B; ssrc += GT::STATE_B;
+        };
         if (lead) {
             int t = 0;
             for (; t < nst; t += 2) {
-                steady_lead(t, 0);
-                steady_lead(t + 1, 1);
+                steady_lead(t, H0{});
+                steady_lead(t + 1, H1{});
             }
-            for (; t < n; ++t) {
-                dma_wait<0>();       // (round 5: the staging requests sit in stage 3, the first stage of the step -- nothing is left in flight)
-                GTS(0)
-                step_barrier();
-                GTS(1)
-                const PartZ pz{{zsrc, zdst, t + 1 < n ? z_req : 0}};
-                const PartS ps{{ssrc, sdst, t + 2 < n ? s1_req : 0}};
-                stage3(AnyMode{}, t, t & 1, pz);
-                GTS(4)
-                if (t + 1 < n) {
-                    stage1((t + 1) & 1, ps);
-                    stage2(Any{}, t + 1, (t + 1) & 1, none);
-                    GTS(3)
-                }
-                next();
+            for (; t < n; t += GT::PAIR ? 2 : 1) {
+                general_lead(t, H0{});
+                if (GT::PAIR && t + 1 < n) general_lead(t + 1, H1{});
             }
         } else {
             int t = 0;
             for (; t < nst; t += 2) {
-                steady_rear(t, 0);
-                steady_rear(t + 1, 1);
+                steady_rear(t, H0{});
+                steady_rear(t + 1, H1{});
             }
-            for (; t < n; ++t) {
-                dma_wait<0>();
-                GTS(0)
-                step_barrier();
-                GTS(1)
-                const PartZ pz{{zsrc, zdst, t + 1 < n ? z_req : 0}};
-                const PartS ps{{ssrc, sdst, t + 2 < n ? s1_req : 0}};
-                // waves 4..7: the Z part's pieces between the MFMAs of stage 1 instead of between the elements of stage 2
-                // (a piece issued in stage 2 -- VALU work, nothing to hide behind -- cost the issuing wave ~100 cycles: stage 2 of a RED
-                // duty wave, one reciprocal per element, took 1 134 cycles with its seven pieces; between MFMAs they are free)
-                stage2(Any{}, t, t & 1, none);
-                GTS(3)
-                stage3(AnyMode{}, t, t & 1, ps);
-                GTS(4)
-                if (t + 1 < n) stage1((t + 1) & 1, pz);
-                next();
+            for (; t < n; t += GT::PAIR ? 2 : 1) {
+                general_rear(t, H0{});
+                if (GT::PAIR && t + 1 < n) general_rear(t + 1, H1{});
             }
+        }
+        // ---- drain: the last pair of the range.  n even: its upper column tiles (the Z area of group n - 1, which landed with the
+        // last barrier).  n odd: group n - 1 is the batch's lone last group -- its area holds its lower column tiles in the K slots of an
+        // even group and its upper ones in those of an odd group (build_state): its beta pieces stand in the operands' low halves, the
+        // high halves become zero for the lower tiles; then the halves change places for the upper tiles
+        using Drain = std::integral_constant<int, 3>;
+        if constexpr (!GT::PAIR) {
+        } else if (n & 1) {
+#pragma unroll
+            for (int j = 0; j < TPW; ++j) betaR[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+            stage3(Drain{}, H1{}, n, 0, none);
+#pragma unroll
+            for (int j = 0; j < TPW; ++j) {
+                BH[j] = u32x4{0u, 0u, BH[j][0], BH[j][1]};
+                BM[j] = u32x4{0u, 0u, BM[j][0], BM[j][1]};
+            }
+            stage3(Drain{}, H0{}, n, 0, none);
+        } else if (n > 0) {
+            stage3(Drain{}, H0{}, n, 0, none);
         }
     };
     auto finish = [&]() __attribute__((always_inline)) {

@@ -10,7 +10,8 @@ size_t qfa_gt_state_bytes(int KP, int B) {
 }
 // tiles, pixel blocks of 8 tiles, ranges of spectra groups: about one workgroup per CU; a multiple of 8 ranges (the
 // workgroups of a range then share an XCD, block = pb R + r) where the batch has the groups for it
-static GtPlan gt_plan(int KP, int B, int Npix, int max_ranges) {
+// (even_ranges = false: the plan before the range length is made even -- at least as many ranges and work items as any launch has)
+static GtPlan gt_plan(int KP, int B, int Npix, int max_ranges, bool even_ranges = true) {
     GtPlan g;
     g.nxcd = xcd_count();
     const int pxw = by_kp<16>(KP, [](auto kp) { return (int)GTT<decltype(kp)::value>::PXW; });       // pixels per wave
@@ -32,11 +33,17 @@ static GtPlan gt_plan(int KP, int B, int Npix, int max_ranges) {
     }
     R = std::max(1, std::min(R, max_ranges));
     g.gpr = (G + R - 1) / R;
+    // even where stage 3 contracts pairs of groups: a range starts at an even group, so no pair straddles two ranges
+    if (even_ranges && by_kp<16>(KP, [](auto kp) { return (bool)GTT<decltype(kp)::value>::PAIR; })) g.gpr = (g.gpr + 1) & ~1;
     g.R = (G + g.gpr - 1) / g.gpr;
     return g;
 }
 int qfa_gt_items(int KP, int B, int Npix, int max_ranges) { return gt_plan(KP, B, Npix, max_ranges).items(); }
 int qfa_gt_ranges(int KP, int B, int Npix, int max_ranges) { return gt_plan(KP, B, Npix, max_ranges).R; }
+// what the workspace is sized for: no launch has more ranges or items (an even range length only merges ranges)
+int qfa_gt_range_groups(int KP, int B, int Npix, int max_ranges) { return gt_plan(KP, B, Npix, max_ranges).gpr; }
+int qfa_gt_items_bound(int KP, int B, int Npix) { return gt_plan(KP, B, Npix, 1 << 30, false).items(); }
+int qfa_gt_ranges_bound(int KP, int B, int Npix) { return gt_plan(KP, B, Npix, 1 << 30, false).R; }
 void qfa_gt_launch(int KP, const Pass2Call &a, int max_ranges, const unsigned char *PGT, const unsigned char *PST) {
     const GtPlan g = gt_plan(KP, a.B, a.Npix, max_ranges);        // (g.R rows leave: qfa_gt_ranges)
     by_kp<16>(KP, [&](auto kp) {

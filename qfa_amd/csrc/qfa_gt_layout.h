@@ -7,8 +7,10 @@
 // Stage 1 of k_grads_t runs on TWO float16 pieces per operand and three products (18 MFMAs per group instead of 36 with bf16 pieces;
 // qfa_common.h "float16 pieces", A/B in profiles/r5_ab_f16_stage1.txt): the image carries a power of two per pixel, the state one
 // per spectrum.
-// Stage 3: W += Z beta on TWO float16 pieces per operand, three products in two MFMAs per column tile (35 MFMAs per group instead
-// of 51, profiles/r5_ab_f16_stage3.txt).  beta = A^2 / D <= 1 / Psi of its PIXEL whatever the data (D >= A^2 Psi): the image carries
+// Stage 3: W += Z beta on TWO float16 pieces per operand, three products; the K = 32 of an MFMA holds the 16 spectra of TWO groups
+// (a PAIR: groups 2 i and 2 i + 1 of the batch), so the three products of a pair are three full MFMAs per column tile -- 27 MFMAs per
+// group with the gamma term (35 while a group's two K halves were piece slots and the fourth half ran empty; 51 with bf16 pieces,
+// profiles/r5_ab_f16_stage3.txt).  beta = A^2 / D <= 1 / Psi of its PIXEL whatever the data (D >= A^2 Psi): the image carries
 // the power of two that brings beta below 2^12 and W is a per-pixel sum -- the scale leaves once, when F enters.  Z of a spectrum
 // is scaled by 2^7 (by less where its largest element exceeds 128; the factor rides with the spectrum's stage-1 scales and
 // multiplies its beta).
@@ -43,9 +45,25 @@ struct GTT {
     // (row m <-> a = 2 tile + (m >> 3), b = m & 7): half the MFMAs, operand reads and accumulator registers
     static constexpr int APT = 16 / KP;                      // a per tile (1 or 2)
     static constexpr int NWT = KP / APT;                     // tiles (16 or 4)
-    static constexpr int ZT_B = 1024;                        // bytes per column tile of the Z part
-    static constexpr int Z_B = NWT * ZT_B;                   // bf16: [tile][operand 1, 2][lane (g, lo = row m)][4 dwords]; float16: [tile][lane][h01 h23 m01 m23]
-    static constexpr int ZP_B = Z_B + 2 * 1024;              // + the p operands (gamma term: bf16 pieces, six products)
+    // The Z image belongs to a PAIR of groups (e, e + 1), e even: per column tile two 1-KiB A operands ZH = {Z_h(e) | Z_h(e + 1)} and
+    // ZM = {Z_m(e) | Z_m(e + 1)}, lane (g, lo = row m) x 16 bytes = {x01 x23 of group e | x01 x23 of group e + 1}: K slot 8 g + j is
+    // spectrum 4 g + (j & 3) of group e + (j >> 2), which keeps beta lane-local in stage 3.  A group writes its 8 bytes of every lane.
+    // The first HT column tiles of the pair lie in the Z area of group e's state, the other HT in that of group e + 1: the bytes
+    // and the DMA pieces per group are what they were, and the walk contracts one area (HT tiles) per step.  A batch with an odd
+    // number of groups ends in a LONE group, which has only its own area: there the second 8 bytes of a lane hold the group's OWN
+    // column tile a + HT beside tile a in the first -- the walk contracts the area twice, beta in the low K half and zeros in the high
+    // one for the tiles a, then the other way round for the tiles a + HT (zero times a finite Z is exactly 0; nothing is left unwritten).
+    // PAIR: the form that contracts pairs.  KP = 8 (two pixel tiles per wave) keeps the per-group image [tile][lane][h01 h23 m01 m23]
+    // and two half-used MFMAs per column tile: its kernel stands at 248 - 256 registers and spills with a pair's operands held.
+    static constexpr bool PAIR = KP == 16;
+    static constexpr int HT = NWT / 2;                       // column tiles per Z area
+    static_assert(NWT % 2 == 0, "a pair's column tiles split over the Z areas of its two groups");
+    static constexpr int ZT_B = PAIR ? 2048 : 1024;          // bytes per column tile of a pair: [ZH, ZM][lane][x01 x23 (e) | x01 x23 (e + 1)]
+    static constexpr int Z_B = NWT * 1024;                   // Z area of a group's state (bf16 pieces had [tile][operand 1, 2][lane][4 dwords] per group)
+    static constexpr int ZP_B = Z_B + 2 * 1024;              // + the group's own p operands (gamma term: bf16 pieces, six products)
+    // byte offset of operand o (0 = ZH, 1 = ZM) of column tile wt of a pair, from the start of group e's Z part; STRIDE = distance of
+    // the two groups' Z parts (STATE_B in global memory, ZP_B in the LDS ring)
+    static constexpr int pair_tile(int wt, int o, int stride) { return (wt / HT) * stride + (wt % HT) * 2048 + o * 1024; }
     static constexpr int S1_ZFAC = S1_SCALES + 128;          // stage 3 (float16 pieces): float32 2^(7 - zk) of the 16 spectra (Z is stored as Z 2^zk)
     static constexpr int STATE_B = S1P_B + ZP_B;
     static constexpr int NW = 8;                             // waves per workgroup
@@ -64,8 +82,17 @@ struct GTT {
     // carries them, the lanes read them when they form the addresses of group t + 2 (k_grads_t, stage_spectra)
     static constexpr int STG_ARR = 1024 * TPW, STG_MASK = 3 * STG_ARR, STG_ROWS = STG_MASK + 256 * TPW, STG_B = STG_ROWS + 64;
     static constexpr int L_S1 = 0;                           // [2][S1P_B]
-    static constexpr int L_Z = L_S1 + 2 * S1P_B;             // [2][ZP_B]
-    static constexpr int L_STG = L_Z + 2 * ZP_B;             // [NW][2][STG_B]
+    // The Z part of group u (the half of its pair's column tiles that lies in its area, and its p operands) is requested during step
+    // u - 1, its p operands are read in step u and its column tiles in step u + 1 (stage 3 of a step contracts the area of the group
+    // BEFORE its own: by then both groups' beta of that area's pair exist).  Slot u % ZRING is rewritten during step u + ZRING - 1,
+    // so the ring needs three slots; four keep the slot a mask of the step number.  Without PAIR a group's tiles are read in its own
+    // step: two slots.
+    //   KP = 16: 2 x 12 288 (S1) + 4 x 18 432 (Z) + 8 x 2 x 3 392 (staging) = 152 576 bytes (115 712 with a ring of two)
+    //   KP =  8: 2 x  6 144      + 2 x  6 144     + 8 x 2 x 6 720           = 132 096 bytes (as before)
+    // both inside the 160 KiB of a CU, which one workgroup has to itself as before.
+    static constexpr int ZRING = PAIR ? 4 : 2;
+    static constexpr int L_Z = L_S1 + 2 * S1P_B;             // [ZRING][ZP_B]
+    static constexpr int L_STG = L_Z + ZRING * ZP_B;         // [NW][2][STG_B]
     static constexpr int L_TOTAL = L_STG + NW * 2 * STG_B;
 };
 static_assert(GTT<16>::L_TOTAL <= 160 * 1024 && GTT<8>::L_TOTAL <= 160 * 1024, "k_grads_t LDS");
@@ -74,14 +101,21 @@ static_assert(GTT<16>::L_TOTAL <= 160 * 1024 && GTT<8>::L_TOTAL <= 160 * 1024, "
 // build_state : the solve's output of one group of 16 spectra (`rows`: 16 records of Cfg<KP>::NSOL floats, global memory or
 // LDS) -> the group's state as split-bf16 MFMA operands, in the order the walk streams them.  256 threads.
 //   S1 part: A[m = spectrum lo][k = 8 g + j of block ks] = ks < NKQ: Cinv'[pair 32 ks + 8 g + j] | ks = NKQ: y[8 g + j - YOFF]
-//   Z  part: per column tile, operands ZA1 = {l01, l23, h01, h23}, ZA2 = {h01, h23, m01, m23} of
-//            x[r] = Z_{4 g + r}[a][b] (row m = lo <-> (a, b): GTT::APT; k = 8 g + j <-> spectrum 4 g + (j & 3), piece slot j >> 2);
-//            then the same two operands of p_{4 g + r}[b] (rows b < KP)
+//   Z  part: the group's 8 bytes {x01, x23} of every lane of the operands ZH, ZM of its PAIR's column tiles (GTT::pair_tile),
+//            x[r] = Z_{4 g + r}[a][b] (row m = lo <-> (a, b): GTT::APT; k = 8 g + j <-> spectrum 4 g + (j & 3) of group e + (j >> 2));
+//            the last group of a batch with an odd number of groups fills both halves of its own area (GTT: lone group);
+//            then, per group, the operands {l01, l23, h01, h23}, {h01, h23, m01, m23} of p_{4 g + r}[b] (rows b < KP)
+// `PST`: the state images of the whole batch; the group is s0 / 16.
 // ------------------------------------------------------------------------------------------------
 template <int KP>
-__device__ __forceinline__ void build_state(const float *rows, int s0, int B, int Nh, unsigned char *__restrict__ st, int tid) {
+__device__ __forceinline__ void build_state(const float *rows, int s0, int B, int Nh, unsigned char *__restrict__ PST, int tid) {
     using C = Cfg<KP>;
     using GT = GTT<KP>;
+    const int grp = s0 >> 4, half = grp & 1;
+    unsigned char *st = PST + (size_t)grp * GT::STATE_B;                 // the group's own state
+    unsigned char *zpair = PST + (size_t)(grp - half) * GT::STATE_B + GT::S1P_B;      // Z part of the pair's first group
+    const bool lone = half == 0 && s0 + 16 >= B;                         // no partner: both halves of its own area (GTT)
+    (void)zpair; (void)lone;
     // stage 1 (float16 pieces): the powers of two of the group's 16 spectra (16 threads per spectrum look at its Cinv' and y)
     __shared__ float sc_[16][6];                                         // scale(Cinv'), scale(y), their inverses; stage 3: 2^zk of Z, 2^(7 - zk)
     __syncthreads();                                                 // (k_solve calls this per group: the previous call's readers)
@@ -153,12 +187,20 @@ __device__ __forceinline__ void build_state(const float *rows, int s0, int B, in
             unsigned h01, m01, h23, m23;
             split2h(x[0], x[1], h01, m01);
             split2h(x[2], x[3], h23, m23);
-            *reinterpret_cast<u32x4 *>(st + GT::S1P_B + wt * GT::ZT_B + lane * 16) = u32x4{h01, h23, m01, m23};
+            if constexpr (!GT::PAIR) {
+                *reinterpret_cast<u32x4 *>(st + GT::S1P_B + wt * GT::ZT_B + lane * 16) = u32x4{h01, h23, m01, m23};
+                continue;
+            }
+            typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+            unsigned char *dst = lone ? zpair + GT::pair_tile(wt % GT::HT, 0, GT::STATE_B) + lane * 16 + 8 * (wt / GT::HT)
+                                      : zpair + GT::pair_tile(wt, 0, GT::STATE_B) + lane * 16 + 8 * half;
+            *reinterpret_cast<u32x2 *>(dst) = u32x2{h01, h23};
+            *reinterpret_cast<u32x2 *>(dst + 1024) = u32x2{m01, m23};
         } else {
             unsigned h01, m01, l01, h23, m23, l23;
             split2(x[0], x[1], h01, m01, l01);
             split2(x[2], x[3], h23, m23, l23);
-            unsigned char *dst = st + GT::S1P_B + (wt < GT::NWT ? wt * GT::ZT_B : GT::Z_B) + lane * 16;
+            unsigned char *dst = st + GT::S1P_B + GT::Z_B + lane * 16;
             *reinterpret_cast<u32x4 *>(dst) = u32x4{l01, l23, h01, h23};
             *reinterpret_cast<u32x4 *>(dst + 1024) = u32x4{h01, h23, m01, m23};
         }

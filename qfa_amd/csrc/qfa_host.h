@@ -45,6 +45,9 @@ struct GtPlan;
 size_t qfa_gt_state_bytes(int KP, int B);
 int qfa_gt_items(int KP, int B, int Npix, int max_ranges);
 int qfa_gt_ranges(int KP, int B, int Npix, int max_ranges);
+int qfa_gt_range_groups(int KP, int B, int Npix, int max_ranges);
+int qfa_gt_items_bound(int KP, int B, int Npix);
+int qfa_gt_ranges_bound(int KP, int B, int Npix);
 void qfa_gt_launch(int KP, const Pass2Call &a, int max_ranges, const unsigned char *PGT, const unsigned char *PST);
 
 // posterior writer for N_h <= 16 on the XDL pipe (qfa_predict_x.h, built in qfa_gx.hip)
@@ -239,7 +242,7 @@ Layout make_layout_t(int B, int Npix) {
     // N_h = KP
     L.oISLAB = 0;
     if constexpr (KP == 8 || KP == 16)
-        L.oISLAB = take(pixres_rows_layout(qfa_gt_ranges(KP, B, Npix, 1 << 30), 8 * (size_t)qfa_gt_items(KP, B, Npix, 1 << 30), Npix, Npix, KP).bytes / sizeof(float));
+        L.oISLAB = take(pixres_rows_layout(qfa_gt_ranges_bound(KP, B, Npix), 8 * (size_t)qfa_gt_items_bound(KP, B, Npix), Npix, Npix, KP).bytes / sizeof(float));
     L.oBG = 0;
     L.bg_stride = round_up(Npix, 32);
     if constexpr (KP == 32) L.oBG = take(2 * (size_t)round_up(B, 64) * L.bg_stride);

@@ -331,7 +331,7 @@ __global__ __launch_bounds__(256, KP <= 16 ? 4 : 2) void k_solve(const float *__
         for (int q = 0; q < (4 * G) / 16; ++q) {
             const int grp = (int)blockIdx.x * ((4 * G) / 16) + q;
             if (16 * grp < B)
-                build_state<KP>(s_rows + q * 16 * C::NSOL, 16 * grp, B, Nh, PST + (size_t)grp * GTT<KP>::STATE_B, (int)threadIdx.x);
+                build_state<KP>(s_rows + q * 16 * C::NSOL, 16 * grp, B, Nh, PST, (int)threadIdx.x);
         }
     }
     if constexpr (NLLRED) {
