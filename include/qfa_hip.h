@@ -902,6 +902,92 @@ int qfa_calibrate_f32(const float *flux, const float *error, const double *pix_u
                       const double *cal, int ncal, double u0, double du, unsigned mode, double c_min, float *flux_out,
                       float *error_out, int32_t *n_uncal, void *stream);
 
+/* The BAL finder (additive to ABI v4): balnicity-type indices of r = flux / continuum in velocity windows blueward of emission lines
+ * (BI: Weymann et al. 1991; AI: Hall et al. 2002, Trump et al. 2006), the list of trough velocities, and the mask made from them.
+ * The continuum is the model's posterior continuum mu + F h on the RED side, per draw; no transmission model is applied, so a window
+ * must lie at p_lo >= Nb.  qfa_amd.absorbers.bal_intervals turns the trough velocities back into rest-frame intervals.
+ *
+ * The contract of qfa_bal_scan_f32.  For spectrum b (row r = rows ? rows[b] : b of the input arrays), draw s, line l < n_lines:
+ *   inputs     F, mu, b, h and cont_min exactly as qfa_obs_stack_f32 reads them (b->delta: RAW FLUX, b->error: the pipeline sigma,
+ *              b->mask may be NULL, rows / row_stride: the resident form; h (B, S, Nh) in batch order).  No redshift is read.
+ *   window     the pixels [p_lo[l], p_hi[l]), at most QFA_BAL_MAX_WIN of them, Nb <= p_lo <= p_hi <= Npix; n_win = p_hi - p_lo.  Window
+ *              pixel i (0 = the lowest outflow velocity) is pixel p = p_hi - 1 - i and spans [vedge[i], vedge[i + 1]] km/s of
+ *              v = c (1 - lambda / lambda_line), c = 299792.458.  vedge[l] (n_win + 1) float64 in DEVICE memory is the host's table,
+ *              non-decreasing (the caller checks): centre velocities formed in float64, edges halfway between centres, extrapolated
+ *              at the ends.  The kernel never forms a velocity: every width decision below is subtractions, one addition and min /
+ *              max of float64 numbers of this table and of the index, the same operations on both sides of any comparison;
+ *   pixel      c = mu[p] + sum_j F[p,j] h[b,s,j], the float32 fma chain in order of j;  r = flux / c;  iv = (c c) / (sigma sigma)
+ *              (qfa_obs_stack_f32's with unc = NULL);  used = mask != 0 && c > cont_min && isfinite(r) && isfinite(iv): selects, not
+ *              products -- what flux or error hold under the mask reaches nothing;
+ *   boxcar     `smooth` odd, 1..15, hw = smooth / 2:  r~_i = (sum of r_j over the USED j of [i - hw, i + hw] clipped to [0, n_win),
+ *              float32, added in ascending j from 0) / (float)n_i, n_i the number of those j; defined where i itself is used.
+ *              smooth = 1: r~ = r;
+ *   below      used_i && (double)r~_i < thr;
+ *   index      x < n_indices: {v_lo, v_hi, w_min, mode}.  Pixel i is IN THE DOMAIN iff min(vedge[i+1], v_hi) - max(vedge[i], v_lo) > 0.
+ *              A BRIDGED pixel: max_gap (0..16) > 0, the pixel is unused and in the domain, and the maximal stretch of consecutive
+ *              unused in-domain pixels it lies in has at most max_gap pixels and an in-domain `below` pixel directly on BOTH sides.
+ *              A RUN is a maximal stretch of consecutive pixels that are in-domain-and-below or bridged (it starts and ends on a
+ *              below pixel); any other pixel ends it.  first / last: its ends;  e0 = max(vedge[first], v_lo),
+ *              e1 = min(vedge[last + 1], v_hi).
+ *              QFA_BAL_WHOLE: the run qualifies iff e1 - e0 >= w_min; every below pixel of it contributes
+ *                             width_i = min(vedge[i+1], v_hi) - max(vedge[i], v_lo).
+ *              QFA_BAL_AFTER: a below pixel contributes width_i = max(0, min(vedge[i+1], v_hi) - max(vedge[i], e0 + w_min)); the
+ *                             run qualifies iff some pixel contributes a positive width (equivalently, its last one does).
+ *              Bridged pixels lengthen the run and contribute nothing;
+ *   outputs    per (b, s, l, x):  value = sum_i (1 - (double)r~_i / thr) width_i over the pixels with width_i > 0, float64, each
+ *              operation rounded once;  var = (sum_q (sigma_q / c_q)^2 a_q^2) / (thr thr), the exact noise variance of `value` under
+ *              the pipeline sigma:  a_q = sum of width_i / (double)n_i over the used i of [q - hw, q + hw] with width_i > 0, in
+ *              ascending i (a_q = width_q at smooth = 1), sigma_q / c_q the float32 quotient, squared in float64, over the used q
+ *              with a_q > 0;  counts (B, S, n_lines, n_indices, 3) int32 = [n_pix: pixels with width_i > 0 | n_runs: qualifying
+ *              runs | n_bridged: bridged pixels of qualifying runs].  value, var (B, S, n_lines, n_indices).
+ *              per (b, s, l):  line_counts (B, S, n_lines, 2) int32 = [n_used: used pixels of the window | n_troughs: the TRUE
+ *              number of qualifying runs of index `trough_index`];  troughs (B, S, n_lines, QFA_BAL_MAX_TROUGHS, 2) float64 = [e0, e1]
+ *              of the first QFA_BAL_MAX_TROUGHS of them in order of velocity, NaN where unfilled;
+ *   sums       float64, no atomics.  Lane m of the one wave that owns (b, l) adds the terms of its pixels i = m, m + 64, .. in ascending
+ *              i; the 64 partial sums are added in the tree (m, m ^ 32), (m, m ^ 16), .., (m, m ^ 1).  The order is a function of the
+ *              window alone: two calls give the same bits, draw s does not depend on S nor on how a call cuts the draws into groups,
+ *              a spectrum's rows depend on that spectrum alone, and the resident form equals the gathered batch bit for bit.
+ * There is no workspace.  Returns QFA_E_NULL for b == NULL or q == NULL or a missing vedge; QFA_E_SIZE for B < 0, S < 1, Npix < 1, Nb
+ * outside 0..Npix, Nh outside 1..32, n_lines or n_indices outside 1..4, trough_index outside the indices, smooth even or outside 1..15,
+ * max_gap outside 0..16, thr not positive and finite, a window with p_lo < Nb, p_lo > p_hi, p_hi > Npix or more than QFA_BAL_MAX_WIN
+ * pixels, an index with v_lo >= v_hi, w_min < 0, anything not finite or an unknown mode, 0 < row_stride < Npix, B S n_lines above 2^30;
+ * QFA_E_FLAGS for any flag other than QFA_F_SYNC; then B = 0 does nothing and returns 0; QFA_E_NULL for any other missing pointer
+ * (b->mask may be NULL).  An empty window writes zeros and NaN troughs.  Argument checks
+ * return before any device work.  The call neither synchronises nor allocates (graph-capturable).
+ *
+ * The contract of qfa_bal_mask_f32: the mask of the next predict -> find -> mask iteration, made on the device.  mask_in (B, Npix)
+ * bytes (NULL: all set), wav (Npix,) float64 rest-frame wavelengths, troughs as qfa_bal_scan_f32 wrote them for S draws and n_lines
+ * lines, mask_lines (n_mask_lines <= 4) float64 in HOST memory.  mask_out[b, p] = mask_in[b, p] && !inside, where inside holds iff
+ *   lam (1 - (v_max + pad) / c) <= wav[p] < lam (1 - (v_min - pad) / c)
+ * for some filled trough [v_min, v_max] of draw s_ref of spectrum b (any of its lines) and some lam of mask_lines: float64, the sum or
+ * difference with pad, the division, the subtraction and the product each rounded once, never contracted -- the operations of
+ * bal_intervals(v_min - pad, v_max + pad), so the result equals bal_intervals -> qfa_absorber_mask_f32's rest intervals.  n_masked
+ * (B,) int32 = the pixels of mask_in that the call cleared.  mask_out == mask_in (in place) is allowed.  Returns QFA_E_SIZE for B < 0,
+ * S < 1, Npix < 1, n_lines or n_mask_lines outside 1..4, s_ref outside 0..S-1, pad_kms negative or not finite, a line not positive and
+ * finite; QFA_E_NULL for mask_lines == NULL; then B = 0 does nothing and returns 0; QFA_E_NULL for any other missing pointer.  Argument
+ * checks return before any device work.  The call neither synchronises nor allocates (graph-capturable). */
+#define QFA_BAL_MAX_LINES 4
+#define QFA_BAL_MAX_INDICES 4
+#define QFA_BAL_MAX_TROUGHS 8
+#define QFA_BAL_MAX_WIN 2048
+enum { QFA_BAL_WHOLE = 0, QFA_BAL_AFTER = 1 };
+typedef struct { double v_lo, v_hi, w_min; unsigned mode; } qfa_bal_index_t;   /* BI = {3000, 25000, 2000, AFTER}, AI = {0, 25000, 450, WHOLE} */
+typedef struct {
+    int n_lines, n_indices;
+    int p_lo[QFA_BAL_MAX_LINES], p_hi[QFA_BAL_MAX_LINES];
+    const double *vedge[QFA_BAL_MAX_LINES];      /* device, (p_hi - p_lo + 1) each */
+    qfa_bal_index_t index[QFA_BAL_MAX_INDICES];
+    double thr;
+    int smooth, max_gap, trough_index;
+} qfa_bal_t;
+
+int qfa_bal_scan_f32(const float *F, const float *mu, const qfa_batch_t *b, const float *h, int B, int S, int Npix, int Nb, int Nh,
+                     const qfa_bal_t *q, float cont_min, unsigned flags, double *value, double *var, int32_t *counts,
+                     int32_t *line_counts, double *troughs, void *stream);
+int qfa_bal_mask_f32(const unsigned char *mask_in, const double *wav, const double *troughs, int B, int S, int n_lines, int s_ref,
+                     int Npix, const double *mask_lines, int n_mask_lines, double pad_kms, unsigned char *mask_out, int32_t *n_masked,
+                     void *stream);
+
 /* Replaces Adam.update(reference QFA/optimizer.py:37-52) followed by the clamp of QFA.clip
  * (QFA/model.py:233-241) for ONE tensor of n elements:
  *   g' = g + wd*p; m = (1-b1) g' + b1 m; v = (1-b2) g'^2 + b2 v;

@@ -29,6 +29,7 @@ _LAZY = {
     "bal_intervals": ("qfa_amd.absorbers", "bal_intervals"),
     "DLAScan": ("qfa_amd.dla", "DLAScan"),
     "ObservedStack": ("qfa_amd.calibration", "ObservedStack"),
+    "BALScan": ("qfa_amd.bal", "BALScan"),
     "calibrate": ("qfa_amd.calibration", "calibrate"),
 }
 

@@ -32,6 +32,7 @@ EXPORTS = (
     "qfa_dla_profiles_f32", "qfa_template_scan_workspace_bytes", "qfa_template_scan_f32",
     "qfa_segment_codes_f32", "qfa_bootstrap_workspace_bytes", "qfa_bootstrap_f64",
     "qfa_obs_stack_doubles", "qfa_obs_stack_workspace_bytes", "qfa_obs_stack_f32", "qfa_calibrate_f32",
+    "qfa_bal_scan_f32", "qfa_bal_mask_f32",
 )
 
 TAU_IDS = {"becker": 0, "fg": 1, "kamble": 2, "mock": 3}
@@ -114,6 +115,20 @@ class AbsorberParams(C.Structure):     # qfa_absorber_t
 
 class ObsBins(C.Structure):            # qfa_obs_bins_t
     _fields_ = [("u0", C.c_double), ("du", C.c_double), ("nbin", C.c_int), ("p_lo", C.c_int), ("p_hi", C.c_int), ("mode", C.c_uint)]
+
+
+BAL_MAX_LINES, BAL_MAX_INDICES, BAL_MAX_TROUGHS, BAL_MAX_WIN = 4, 4, 8, 2048    # QFA_BAL_MAX_*
+BAL_MODES = {"whole": 0, "after": 1}   # qfa_bal_index_t.mode (QFA_BAL_*)
+
+
+class BalIndex(C.Structure):           # qfa_bal_index_t
+    _fields_ = [("v_lo", C.c_double), ("v_hi", C.c_double), ("w_min", C.c_double), ("mode", C.c_uint)]
+
+
+class BalParams(C.Structure):          # qfa_bal_t
+    _fields_ = [("n_lines", C.c_int), ("n_indices", C.c_int), ("p_lo", C.c_int * BAL_MAX_LINES), ("p_hi", C.c_int * BAL_MAX_LINES),
+                ("vedge", C.c_void_p * BAL_MAX_LINES), ("index", BalIndex * BAL_MAX_INDICES), ("thr", C.c_double),
+                ("smooth", C.c_int), ("max_gap", C.c_int), ("trough_index", C.c_int)]
 
 
 _lib = None
@@ -214,6 +229,8 @@ def lib():
         "qfa_obs_stack_workspace_bytes": (sz, [i, i, i, i, i]),
         "qfa_obs_stack_f32": (i, [p, p, C.POINTER(Batch), p, p, p, p, i, i, i, i, C.POINTER(ObsBins), f, C.c_uint, p, p, sz, p]),
         "qfa_calibrate_f32": (i, [p, p, p, p, i, i, p, i, d, d, C.c_uint, d, p, p, p, p]),
+        "qfa_bal_scan_f32": (i, [p, p, C.POINTER(Batch), p, i, i, i, i, i, C.POINTER(BalParams), f, C.c_uint, p, p, p, p, p, p]),
+        "qfa_bal_mask_f32": (i, [p, p, p, i, i, i, i, i, C.POINTER(d), i, d, p, p, p]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(h, name, None)

@@ -138,6 +138,12 @@ def main(argv=None):
             raise ValueError("MODEL.VAR_MIN_COUNT must be >= 1")
     if cfg.TYPE == "predict" and not 0 <= int(M.BOOT_N) <= 65536:
         raise ValueError("MODEL.BOOT_N must lie in 0 .. 65536 (0 = off)")
+    if cfg.TYPE == "predict" and bool(M.BAL):
+        from .bal import DEFAULT_LINES, check_scan_params
+        refuse("MODEL.BAL_THR must be positive and finite, MODEL.BAL_SMOOTH odd in 1 .. 15, MODEL.BAL_MAX_GAP in 0 .. 16",
+               check_scan_params, DEFAULT_LINES, M.BAL_THR, M.BAL_SMOOTH, M.BAL_MAX_GAP)
+        if int(M.BAL_NITER) < 1 or not float(M.BAL_PAD_KMS) >= 0.0 or float(M.BAL_PAD_KMS) == float("inf"):
+            raise ValueError("MODEL.BAL_NITER must be >= 1 and MODEL.BAL_PAD_KMS finite and >= 0")
     os.makedirs(cfg.DATA.OUTPUT_DIR, exist_ok=True)
     with open(os.path.join(cfg.DATA.OUTPUT_DIR, "config.yaml"), "w") as f:
         f.write(cfg.dump())
@@ -211,6 +217,15 @@ def main(argv=None):
                 elif int(switch) > 0:
                     done.append(method(dataloader, float(M.FOREST_ZMIN), float(M.FOREST_ZMAX), int(M.P1D_NZBINS), **own(), **shared))
                     save(name, done[-1], **export)
+        if bool(M.BAL):
+            import numpy as np
+            from . import io
+            scan = model.bal_catalog(dataloader, thr=float(M.BAL_THR), smooth=int(M.BAL_SMOOTH), max_gap=int(M.BAL_MAX_GAP),
+                                     n_samples=int(M.N_SAMPLES), seed=int(M.SAMPLE_SEED), n_iter=int(M.BAL_NITER),
+                                     pad_kms=float(M.BAL_PAD_KMS))
+            io.write_bal_csv(os.path.join(cfg.DATA.OUTPUT_DIR, "bal_catalog.csv"),
+                             scan.to_table([os.path.basename(n) for n in scan.names], min_value=float(M.BAL_MIN_AI)))
+            np.savez(os.path.join(cfg.DATA.OUTPUT_DIR, "bal_scan.npz"), **scan.arrays())
         print(f"Finish predicting {len(dataloader)} spectra in {time.time() - ts} seconds...")
     return 0
 

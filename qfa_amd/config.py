@@ -85,7 +85,14 @@ DEFAULTS = {                                        # reference QFA/config.py:15
               # not in the reference: BOOT_N > 0 makes every segment statistic predict mode writes (flux_power, flux_power_bands,
               # flux_correlation, flux_pdf, variance_function) also write <its file stem>_bootstrap.npz: its estimate in BOOT_N Poisson
               # bootstrap replicates over quasars and their covariance matrix per z-bin; BOOT_SEED seeds the weights (QFA.bootstrap)
-              "BOOT_N": 0, "BOOT_SEED": 0},
+              "BOOT_N": 0, "BOOT_SEED": 0,
+              # not in the reference: BAL = True makes predict mode also write bal_catalog.csv (one row per trough: file, line, v_min,
+              # v_max, bi, ai; io.read_bal_csv, python -m qfa_amd.preprocess --bal_catalog) and bal_scan.npz: BI and AI of C IV and
+              # Si IV under the posterior continuum, per posterior draw when N_SAMPLES is set (QFA.bal_catalog).  BAL_THR: the
+              # normalised flux a trough lies below; BAL_SMOOTH: odd boxcar width 1 .. 15; BAL_MAX_GAP: masked pixels 0 .. 16 a trough
+              # may bridge; BAL_NITER > 1 repeats predict -> find -> mask; BAL_MIN_AI: the AI in km/s above which a spectrum's troughs
+              # are listed; BAL_PAD_KMS widens the troughs masked between iterations
+              "BAL": False, "BAL_THR": 0.9, "BAL_SMOOTH": 1, "BAL_MAX_GAP": 0, "BAL_NITER": 1, "BAL_MIN_AI": 0.0, "BAL_PAD_KMS": 0.0},
     "TRAIN": {"NEPOCHS": 500, "LEARNING_RATE": 1e-3, "WEIGHT_DECAY": 1e-1, "DECAY_ALPHA": 0.9, "DECAY_STEP": 10,
               "WINDOW_LENGTH_FOR_MU": 16,
               # not in the reference: "em" = F by its closed-form EM update, Adam for the other parameters (QFA.train
@@ -109,7 +116,8 @@ EXTRA_KEYS = ("MODEL.REFERENCE_C0_QUIRK", "MODEL.N_SAMPLES", "MODEL.SAMPLE_SEED"
               "MODEL.FOREST", "MODEL.FOREST_ZMIN", "MODEL.FOREST_ZMAX", "MODEL.FOREST_NBINS", "MODEL.P1D_SEGMENTS",
               "MODEL.P1D_NZBINS", "MODEL.P1D_MIN_USED_FRAC", "MODEL.P1D_NBANDS", "MODEL.XI_NLAGS", "MODEL.XI_SIGMA2_LSS", "MODEL.PDF_NBINS",
               "MODEL.PDF_TMIN", "MODEL.PDF_TMAX", "MODEL.PDF_CLAMP", "MODEL.PDF_RELATIVE", "MODEL.PDF_IVAR_MIN", "MODEL.VAR_NOCT", "MODEL.VAR_ELO",
-              "MODEL.VAR_SUB", "MODEL.VAR_DMAX", "MODEL.VAR_MIN_COUNT", "MODEL.BOOT_N", "MODEL.BOOT_SEED", "TRAIN.F_UPDATE", "TRAIN.EM_RHO", "TRAIN.EM_RIDGE")
+              "MODEL.VAR_SUB", "MODEL.VAR_DMAX", "MODEL.VAR_MIN_COUNT", "MODEL.BOOT_N", "MODEL.BOOT_SEED", "MODEL.BAL",
+              "MODEL.BAL_THR", "MODEL.BAL_SMOOTH", "MODEL.BAL_MAX_GAP", "MODEL.BAL_NITER", "MODEL.BAL_MIN_AI", "MODEL.BAL_PAD_KMS", "TRAIN.F_UPDATE", "TRAIN.EM_RHO", "TRAIN.EM_RIDGE")
 
 
 def _set(cfg, dotted, value):

@@ -91,6 +91,51 @@ def read_absorber_csv(path):
             "log_nhi": t["log_nhi"].values.astype(np.float64)}
 
 
+BAL_COLUMNS = ("file", "line", "v_min", "v_max", "bi", "ai")
+
+
+def write_bal_csv(path, table):
+    """A BAL catalogue, one row per trough: columns ``file``, ``line`` (Angstrom), ``v_min``, ``v_max`` (km/s of outflow velocity),
+    ``bi``, ``ai`` (km/s, of the spectrum and line the trough belongs to) -- ``BALScan.to_table``; floats with 17 significant digits"""
+    cols = [np.asarray(table[c]).reshape(-1) for c in BAL_COLUMNS]
+    if len({len(c) for c in cols}) != 1:
+        raise ValueError("write_bal_csv: the columns must have one length")
+    with open(path, "w") as f:
+        f.write(",".join(BAL_COLUMNS) + "\n")
+        for row in zip(*cols):
+            f.write(str(row[0]) + "," + ",".join(repr(float(x)) for x in row[1:]) + "\n")
+    return path
+
+
+def read_bal_csv(path):
+    """The table ``write_bal_csv`` wrote, bit for bit: a dict of ``file`` (str) and float64 ``line``, ``v_min``, ``v_max``, ``bi``,
+    ``ai``; ``bi`` / ``ai`` may be missing from a catalogue brought from elsewhere (NaN then)"""
+    import pandas as pd
+    t = pd.read_csv(path, float_precision="round_trip")
+    missing = [c for c in ("file", "v_min", "v_max") if c not in t.columns]
+    if missing:
+        raise ValueError(f"{path}: missing column(s) {missing}")
+    out = {"file": t["file"].astype(str).values}
+    for c in BAL_COLUMNS[1:]:
+        out[c] = t[c].values.astype(np.float64) if c in t.columns else np.full(len(t), np.nan)
+    return out
+
+
+def bal_rest_intervals(names, table, pad_kms=0.0, lines=None):
+    """The per-spectrum ``rest=`` list of ``mask_absorbers`` from a BAL table: for the spectra ``names`` (a trailing ``.npz`` is
+    ignored on both sides) the intervals ``bal_intervals(v_min - pad_kms, v_max + pad_kms, lines)`` of every row of the file"""
+    from .absorbers import BAL_LINES, bal_intervals
+    key = lambda n: str(n)[:-4] if str(n).endswith(".npz") else str(n)
+    by_file = {}
+    for f, a, b in zip(table["file"], table["v_min"], table["v_max"]):
+        by_file.setdefault(key(f), []).append((float(a) - float(pad_kms), float(b) + float(pad_kms)))
+    out = []
+    for n in names:
+        v = np.asarray(by_file.get(key(n), []), dtype=np.float64).reshape(-1, 2)
+        out.append(bal_intervals(v[:, 0], v[:, 1], BAL_LINES if lines is None else lines) if len(v) else np.zeros((0, 2)))
+    return out
+
+
 def read_intervals(path):
     """Intervals ``[lo, hi)`` in Angstrom, one per line, two columns separated by blanks or a comma (``#`` starts a comment):
     float64 (n, 2)"""

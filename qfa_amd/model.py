@@ -25,6 +25,8 @@ Additions over the reference (none changes a reference call's result):
   * ``observed_residuals`` / ``observed_stack`` / ``ObservedStack`` -- the observed-frame residual stack, methods of the base class
     ``ObservedFrame`` (calibration.py): the calibration vector and the sky-line mask from the data themselves (include/qfa_hip.h,
     qfa_obs_stack_f32, qfa_calibrate_f32);
+  * ``bal_scan`` / ``bal_catalog`` / ``BALScan`` -- the BAL finder, methods of the base class ``BALFinder`` (bal.py): BI, AI and the
+    trough velocities per spectrum and posterior draw (include/qfa_hip.h, ``qfa_bal_scan_f32``, ``qfa_bal_mask_f32``);
   * ``dla_profiles`` / ``template_scan`` / ``dla_scan`` / ``DLAScan`` -- the DLA finder, methods of the base class ``DLAFinder``
     (dla.py): a likelihood-ratio scan of every spectrum over a grid of absorber redshift and column density (include/qfa_hip.h,
     qfa_template_scan_f32), whose catalogue ``mask_absorbers`` takes;
@@ -51,6 +53,7 @@ from . import utils as _utils
 from .stacks import BootstrapStack, EMStats, ForestStack, P1DBandStack, P1DStack, PDFStack, VarianceStack, XiStack    # (re-exported)
 from .dla import DLAFinder, DLAScan    # (re-exported)
 from .calibration import ObservedFrame, ObservedStack    # (re-exported)
+from .bal import BALFinder, BALScan    # (re-exported)
 from .statistics import ForestStatistics
 
 f32 = torch.float32
@@ -83,7 +86,7 @@ def _resolve_tau(tau):
     raise TypeError("tau must be a name, qfa_amd.utils.tau (partial) or a callable")
 
 
-class QFA(ForestStatistics, DLAFinder, ObservedFrame):
+class QFA(ForestStatistics, DLAFinder, ObservedFrame, BALFinder):
 
     def __init__(self, Nb: int, Nr: int, Nh: int, device: torch.device,
                  tau: Callable[[torch.Tensor], torch.Tensor] = default_tau,

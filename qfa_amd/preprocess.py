@@ -9,6 +9,7 @@ file form the reference's ``--type train --catalog ... --data_dir ...`` reads.
     python -m qfa_amd.preprocess --catalog observed.csv --data_dir raw/ --output_dir prepared/ [--lammin 1030 --lammax 1600
                                                                                                --loglam_delta 1e-4 ...]
                                 [--dla_catalog dla.csv --sky_mask sky.txt --dla_tmin 0.8 --dla_b 30 --no_dla_correct]
+                                [--bal_catalog bal.csv --bal_pad_kms 0]
                                 [--calibration cal.npz]
 
 With ``--dla_catalog`` / ``--sky_mask`` the catalogued absorbers and bad observed wavelengths are masked and corrected
@@ -237,6 +238,8 @@ def main(argv=None):
     ap.add_argument("--dla_tmin", type=float, default=0.8, help="mask where the absorbers' transmission is below this")
     ap.add_argument("--dla_b", type=float, default=30., help="Doppler parameter of the absorbers, km/s")
     ap.add_argument("--no_dla_correct", action="store_true", help="mask only: do not divide by the absorbers' profile")
+    ap.add_argument("--bal_catalog", default=None, help="csv with columns file, v_min, v_max (io.write_bal_csv): mask these BAL troughs")
+    ap.add_argument("--bal_pad_kms", type=float, default=0., help="widen every BAL trough by this many km/s on both sides")
     ap.add_argument("--calibration", default=None, help="npz of io.write_calibration: divide the spectra by this calibration vector")
     a = ap.parse_args(argv)
     names = [str(x) for x in pd.read_csv(a.catalog).iloc[:, 0].values]
@@ -246,7 +249,7 @@ def main(argv=None):
                      norm_min_pixels=a.norm_min_pixels, snr_window=tuple(a.snr_window), device=a.device)
     if a.calibration is not None:
         pre = pre.calibrate(io.read_calibration(a.calibration))
-    if a.dla_catalog is not None or a.sky_mask is not None:
+    if a.dla_catalog is not None or a.sky_mask is not None or a.bal_catalog is not None:
         from .absorbers import AbsorberCatalog
         dla = None
         if a.dla_catalog is not None:
@@ -254,7 +257,10 @@ def main(argv=None):
             if dla.unmatched:
                 print(f"{len(dla.unmatched)} file names of {a.dla_catalog} match no spectrum, the first: {dla.unmatched[0]}")
         sky = io.read_intervals(a.sky_mask) if a.sky_mask is not None else None
-        pre = pre.mask_absorbers(dla=dla, sky=sky, t_min=a.dla_tmin, b_kms=a.dla_b, correct=not a.no_dla_correct,
+        rest = None
+        if a.bal_catalog is not None:
+            rest = io.bal_rest_intervals([os.path.basename(n) for n in names], io.read_bal_csv(a.bal_catalog), a.bal_pad_kms)
+        pre = pre.mask_absorbers(dla=dla, sky=sky, rest=rest, t_min=a.dla_tmin, b_kms=a.dla_b, correct=not a.no_dla_correct,
                                  snr_window=tuple(a.snr_window))
     path = pre.write_npz(a.output_dir, [os.path.basename(n) for n in names])
     print(f"{int(pre.ok.sum())} of {len(pre)} spectra written to {a.output_dir}; catalogue {path}")
