@@ -917,7 +917,8 @@ int qfa_calibrate_f32(const float *flux, const float *error, const double *pix_u
  *              at the ends.  The kernel never forms a velocity: every width decision below is subtractions, one addition and min /
  *              max of float64 numbers of this table and of the index, the same operations on both sides of any comparison;
  *   pixel      c = mu[p] + sum_j F[p,j] h[b,s,j], the float32 fma chain in order of j;  r = flux / c;  iv = (c c) / (sigma sigma)
- *              (qfa_obs_stack_f32's with unc = NULL);  used = mask != 0 && c > cont_min && isfinite(r) && isfinite(iv): selects, not
+ *              (qfa_obs_stack_f32's with unc = NULL, except where r r overflows while r is finite: that call forms (r r) 0 = NaN and
+ *              drops the pixel, this one keeps it);  used = mask != 0 && c > cont_min && isfinite(r) && isfinite(iv): selects, not
  *              products -- what flux or error hold under the mask reaches nothing;
  *   boxcar     `smooth` odd, 1..15, hw = smooth / 2:  r~_i = (sum of r_j over the USED j of [i - hw, i + hw] clipped to [0, n_win),
  *              float32, added in ascending j from 0) / (float)n_i, n_i the number of those j; defined where i itself is used.

@@ -277,8 +277,8 @@ class BALFinder(object):
         """BI, AI and the trough velocities of a batch under the posterior continuum (the contract is in include/qfa_hip.h,
         qfa_bal_scan_f32).  ``wav_grid`` (Npix,) gives every line its velocity window; ``lines`` (1..4) in Angstrom, all on the red
         side of the model; ``indices``: {name: (v_lo, v_hi, w_min, 'after' | 'whole')}, default BI and AI; ``trough_index``: the index
-        whose qualifying runs are listed as troughs (default 'AI' if present, else the last).  The latent is resolved as
-        ``observed_residuals`` resolves it: ``h`` | ``hmean`` | ``hmean`` + ``hcov`` + ``n_samples``, else ``predict`` runs on the
+        whose qualifying runs are listed as troughs (default 'AI' if present, else the last).  The latent
+        (``QFA._resolve_latent``): ``h`` | ``hmean`` | ``hmean`` + ``hcov`` + ``n_samples``, else ``predict`` runs on the
         inputs first (``zabs`` or ``zfac`` only serve that ``predict``).  Every input form of a batch: the tensors, or ``batch`` = a
         ``ResidentBatch``.  ``n_iter`` > 1 repeats predict -> scan -> mask: the pixels inside draw 0's troughs of all scanned lines,
         imaged onto every line of ``mask_lines`` and widened by ``pad_kms``, are cleared from a copy of ``mask`` on the device
@@ -298,13 +298,6 @@ class BALFinder(object):
         if len(grid) != self.Npix:
             raise QFAHipError(f"len(wav_grid) = {len(grid)}, the model has {self.Npix} pixels")
         windows = self._bal_windows(grid, lines, indices)       # (raises for a blue-side window before anything runs)
-        if hcov is not None and hmean is None:
-            raise QFAHipError("bal_scan: hcov without hmean")
-        if h is not None and hmean is not None:
-            raise QFAHipError("bal_scan: pass h or hmean / hcov, not both")
-        S = int(n_samples)
-        if S < 0 or (S > 0 and h is None and hmean is not None and hcov is None):
-            raise QFAHipError("bal_scan: n_samples > 0 needs hcov next to hmean")
         n_iter = int(n_iter)
         if n_iter < 1:
             raise QFAHipError(f"n_iter = {n_iter}, expected >= 1")
@@ -324,23 +317,13 @@ class BALFinder(object):
                 if not isinstance(t, torch.Tensor) or tuple(t.shape) != (B, self.Npix):
                     raise QFAHipError(f"{name}: expected a ({B}, {self.Npix}) tensor")
         n_masked, pmask = None, mask                            # pmask: what predict sees; the scan always reads the caller's mask
-        given = h is not None or hmean is not None
         for it in range(n_iter):
-            h_it, hm, hc = h, hmean, hcov
-            if not given:
-                _, hm, hc, _, _ = self.predict(flux, error, zabs, pmask, zfac=zfac, batch=batch)
-            if h_it is None:
-                if tuple(hm.shape) != (B, self.Nh):
-                    raise QFAHipError(f"hmean: shape {tuple(hm.shape)}, expected ({B}, {self.Nh})")
-                h_it = self.sample_latent(hm, hc, S, seed=seed, offset=offset) if S > 0 else hm.reshape(B, 1, self.Nh).contiguous()
-            elif h_it.dim() != 3 or h_it.shape[0] != B or h_it.shape[2] != self.Nh or h_it.shape[1] < 1 or (S > 0 and h_it.shape[1] != S):
-                raise QFAHipError(f"h: shape {tuple(h_it.shape)}, expected ({B}, {S if S > 0 else 'S'}, {self.Nh})")
-            if batch is not None:
-                bs, keep = self._batch_struct_rows(batch, raw_flux=True)
-            else:
-                bs, keep = self._obs_batch(flux, error, mask)
+            h_it, _, _ = self._resolve_latent("bal_scan", B, h=h, hmean=hmean, hcov=hcov, n_samples=n_samples, seed=seed, offset=offset,
+                                              unc=None, predict_inputs=dict(flux=flux, error=error, zabs=zabs, mask=pmask, zfac=zfac,
+                                                                            batch=batch))
+            bs, keep = self._batch_struct_rows(batch, raw_flux=True) if batch is not None else self._flux_batch(flux, error, mask)
             bs.A_blue = bs.zabs = bs.zq1 = bs.pix_ratio = None      # (not read by the call)
-            scan = self._bal_call(bs, h_it, B, windows, lines, indices, thr, smooth, max_gap, cont_min, trough_index)
+            scan = self._bal_call(bs, h_it if h is not None else h_it.contiguous(), B, windows, lines, indices, thr, smooth, max_gap, cont_min, trough_index)
             del keep
             if it + 1 < n_iter:                                 # (from the caller's mask every time: the troughs are measured anew)
                 pmask, n_masked = bal_mask(mask, grid, scan.troughs, draw=0, lines=mask_lines, pad_kms=pad_kms)

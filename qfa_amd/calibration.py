@@ -260,19 +260,12 @@ class ObservedFrame(object):
         observed wavelength (the contract is in include/qfa_hip.h).  ``zqso`` (B,) in batch order and ``wav_grid`` (Npix,) give the
         coordinate in float64.  The bins: ``stack`` -- an ``ObservedStack`` to ADD to -- or ``lam_min``, ``nbin`` and ``dloglam``
         (bins of log10 lambda) or ``dlam`` (bins of lambda).  ``rest_range`` = (lo, hi) in Angstrom restricts the stacked pixels
-        to lo <= wav_grid < hi (the red side: (1216, inf)); default all.  The latent is resolved as ``forest`` resolves it: ``h`` |
+        to lo <= wav_grid < hi (the red side: (1216, inf)); default all.  The latent (``QFA._resolve_latent``): ``h`` |
         ``hmean`` | ``hmean`` + ``hcov`` + ``n_samples``, else ``predict`` runs on the inputs first and its ``unc`` enters the
         weights when S = 1.  Every input form of a batch: the tensors (``zabs`` or ``zfac`` only serve that ``predict``), or
         ``batch`` = a ``ResidentBatch``.  Returns the ``ObservedStack``."""
         if self.mu is None:
             raise QFAHipError("observed_residuals needs model.mu (load_from_npz or train first)")
-        if hcov is not None and hmean is None:
-            raise QFAHipError("observed_residuals: hcov without hmean")
-        if h is not None and hmean is not None:
-            raise QFAHipError("observed_residuals: pass h or hmean / hcov, not both")
-        S = int(n_samples)
-        if S < 0 or (S > 0 and h is None and hmean is not None and hcov is None):
-            raise QFAHipError("observed_residuals: n_samples > 0 needs hcov next to hmean")
         dev = self.device
         self._params_struct()
         if stack is not None:
@@ -285,13 +278,8 @@ class ObservedFrame(object):
             if lam_min is None or nbin is None:
                 raise QFAHipError("observed_residuals: give stack=, or lam_min, nbin and dloglam or dlam")
             u0, du, nb, mode = obs_grid(lam_min, nbin, dloglam, dlam)
-        if h is None and hmean is None:
-            _, hmean, hcov, _, punc = self.predict(flux, error, zabs, mask, zfac=zfac, batch=batch)
-            if S == 0 and unc is None:
-                unc = punc
         if batch is not None:
             B = batch.B
-            bs, keep = self._batch_struct_rows(batch, raw_flux=True)
         else:
             if not isinstance(flux, torch.Tensor) or flux.dim() != 2:
                 raise QFAHipError("observed_residuals: flux must be a (B, Npix) tensor")
@@ -299,19 +287,11 @@ class ObservedFrame(object):
             for t, name in ((flux, "flux"), (error, "error"), (mask if mask is not None else flux, "mask")):
                 if tuple(t.shape) != (B, self.Npix):
                     raise QFAHipError(f"{name}: shape {tuple(t.shape)}, expected ({B}, {self.Npix})")
-            bs, keep = self._obs_batch(flux, error, mask)
+        h, S, unc = self._resolve_latent("observed_residuals", B, h=h, hmean=hmean, hcov=hcov, n_samples=n_samples, seed=seed,
+                                         offset=offset, unc=unc,
+                                         predict_inputs=dict(flux=flux, error=error, zabs=zabs, mask=mask, zfac=zfac, batch=batch))
+        bs, keep = self._batch_struct_rows(batch, raw_flux=True) if batch is not None else self._flux_batch(flux, error, mask)
         bs.A_blue = bs.zabs = bs.zq1 = bs.pix_ratio = None      # (not read by the call)
-        if h is None:
-            if tuple(hmean.shape) != (B, self.Nh):
-                raise QFAHipError(f"hmean: shape {tuple(hmean.shape)}, expected ({B}, {self.Nh})")
-            if S > 0:
-                h = self.sample_latent(hmean, hcov, S, seed=seed, offset=offset)
-            else:
-                S, h = 1, hmean.reshape(B, 1, self.Nh)
-        else:
-            if h.dim() != 3 or h.shape[0] != B or h.shape[2] != self.Nh or h.shape[1] < 1 or (S > 0 and h.shape[1] != S):
-                raise QFAHipError(f"h: shape {tuple(h.shape)}, expected ({B}, {S if S > 0 else 'S'}, {self.Nh})")
-            S = int(h.shape[1])
         ph = _lib.require_device_tensor(h, f32, "h")
         pu = None
         if unc is not None:
@@ -344,20 +324,6 @@ class ObservedFrame(object):
             _lib.current_stream(dev)), "qfa_obs_stack_f32")
         del keep
         return stack
-
-    def _obs_batch(self, flux, error, mask):
-        """qfa_batch_t of flux / error / mask alone (the call reads no redshift)"""
-        if mask is not None and mask.dtype != torch.bool:
-            raise QFAHipError(f"mask: dtype {mask.dtype}, expected torch.bool")
-        bs = _lib.Batch()
-        flux = flux if (flux.dtype == f32 and flux.is_contiguous()) else flux.to(f32).contiguous()
-        error = error if (error.dtype == f32 and error.is_contiguous()) else error.to(f32).contiguous()
-        mask = mask if mask is None or mask.is_contiguous() else mask.contiguous()
-        bs.delta = _lib.require_device_tensor(flux, f32, "flux").value
-        bs.error = _lib.require_device_tensor(error, f32, "error").value
-        bs.mask = _lib.require_device_tensor(mask, torch.bool, "mask").value if mask is not None else None
-        bs.rows, bs.row_stride = None, 0
-        return bs, [flux, error, mask]
 
     def observed_stack(self, dataloader, lam_min, nbin, dloglam=None, dlam=None, rest_range=None, n_samples=0, seed=0, batch_size=4096,
                        cont_min=0.0, unit_weights=False):

@@ -45,11 +45,11 @@ struct Args {
     float cont_min;
 };
 
-__device__ __forceinline__ void pin(double &x) { asm volatile("" : "+v"(x)); }
 __device__ __forceinline__ double dmax(double a, double b) { return a > b ? a : b; }
 __device__ __forceinline__ double dmin(double a, double b) { return a < b ? a : b; }
 
 // sum over the wave in a fixed tree (lanes l and l ^ m, m = 32, 16, .., 1): every lane ends with the same bits
+// (not qfa_forest::wave_sum: that one adds the lanes l ^ 1, 2, .., 32, and the float64 sums differ in the last bit)
 __device__ __forceinline__ double wave_tree_sum(double x) {
 #pragma clang fp contract(off)
 #pragma unroll
@@ -117,7 +117,7 @@ __global__ __launch_bounds__(kWave) void k_bal_scan(const Args a) {
     for (int s = s0; s < s1; ++s) {
         const float *hr = a.h + ((int64_t)b * S + s) * Nh;
         const size_t o_line = ((size_t)b * S + s) * L + line;
-        // (A) the pixel values of qfa_obs_stack_f32 with unc = NULL
+        // (A) the pixel rule in its noise-only form (qfa_continuum.h: den = sigma^2; where it parts from k_obs_stack with unc = NULL)
         int n_used = 0;
         for (int k = 0; k < nchunks; ++k) {
             const int i = k * kWave + lane;

@@ -1,6 +1,7 @@
 // qfa_bal.hip -- C-ABI of the BAL finder (include/qfa_hip.h: qfa_bal_scan_f32, qfa_bal_mask_f32): argument checks, the launch shape
 // and the launches.  Kernels in qfa_bal.h.
 #include "qfa_bal.h"
+#include "qfa_call.h"
 
 #include <math.h>
 
@@ -10,11 +11,6 @@ using namespace qfa_bal;
 
 constexpr int64_t kBlocks = 4096;             // blocks a call aims at before it cuts the draws of a (spectrum, line) into groups
 constexpr int64_t kMaskGrid = 2048;
-
-template <int NHM>
-void launch(const Args &a, unsigned grid, size_t lds, hipStream_t st) {
-    k_bal_scan<NHM><<<grid, kWave, lds, st>>>(a);
-}
 
 }  // namespace
 
@@ -49,8 +45,7 @@ int qfa_bal_scan_f32(const float *F, const float *mu, const qfa_batch_t *b, cons
     if (!F || !mu || !h || !value || !var || !counts || !line_counts || !troughs || !b->delta || !b->error) return QFA_E_NULL;
     hipStream_t st = (hipStream_t)stream;
     Args a;
-    a.bt = *b;
-    if (a.bt.row_stride == 0) a.bt.row_stride = Npix;
+    a.bt = norm_batch(*b, Npix);
     a.F = F; a.mu = mu; a.h = h;
     for (int l = 0; l < QFA_BAL_MAX_LINES; ++l) {
         const bool on = l < q->n_lines;
@@ -75,14 +70,8 @@ int qfa_bal_scan_f32(const float *F, const float *mu, const qfa_batch_t *b, cons
     a.cont_min = cont_min;
     const size_t lds = (size_t)a.nmax * kLdsPerPixel;
     const unsigned grid = (unsigned)(pairs * a.nsg);
-    if (Nh <= 8) launch<8>(a, grid, lds, st);
-    else if (Nh <= 16) launch<16>(a, grid, lds, st);
-    else launch<32>(a, grid, lds, st);
-    if (flags & QFA_F_SYNC) {
-        hipError_t s = hipStreamSynchronize(st);
-        if (s != hipSuccess) { (void)hipGetLastError(); return (int)s; }
-    }
-    return (int)hipGetLastError();
+    by_nhm(Nh, [&](auto nhm) { k_bal_scan<decltype(nhm)::value><<<grid, kWave, lds, st>>>(a); });
+    return hip_status(st, flags);
 }
 
 int qfa_bal_mask_f32(const unsigned char *mask_in, const double *wav, const double *troughs, int B, int S, int n_lines, int s_ref,

@@ -2,7 +2,7 @@
 // qfa_bootstrap_f64): argument checks and the launch.  Kernels in qfa_bootstrap.h; qfa_segment_codes_f32 lives in qfa_p1d.hip, beside
 // the checks of qfa_p1d_f32 it shares.
 #include "qfa_bootstrap.h"
-#include "../../include/qfa_hip.h"
+#include "qfa_call.h"
 
 namespace {
 
@@ -58,11 +58,7 @@ int qfa_bootstrap_f64(const void *rows, int row_type, const int32_t *codes, int 
     if (row_type == QFA_ROW_F32) launch<float>(rows, codes, B, S, nseg, W, nz, R, seed, row_offset, zero, boot, st);
     else if (row_type == QFA_ROW_F64) launch<double>(rows, codes, B, S, nseg, W, nz, R, seed, row_offset, zero, boot, st);
     else launch<int32_t>(rows, codes, B, S, nseg, W, nz, R, seed, row_offset, zero, boot, st);
-    if (flags & QFA_F_SYNC) {
-        hipError_t s = hipStreamSynchronize(st);
-        if (s != hipSuccess) { (void)hipGetLastError(); return (int)s; }
-    }
-    return (int)hipGetLastError();
+    return hip_status(st, flags);
 }
 
 }  // extern "C"

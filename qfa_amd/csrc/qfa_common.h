@@ -399,6 +399,8 @@ __device__ __forceinline__ void glds16(const void *g, void *lds_base) {
 // keep a value's computation in front of this point (IR passes otherwise sink pure arithmetic past
 // the sched_barrier fences of the hand-woven MFMA/VALU regions)
 __device__ __forceinline__ void pin(float &x) { asm volatile("" : "+v"(x)); }
+// (float64: a product that a sum or difference follows is pinned first -- the backend fuses them whatever `fp contract` says)
+__device__ __forceinline__ void pin(double &x) { asm volatile("" : "+v"(x)); }
 template <typename... T>
 __device__ __forceinline__ void pin(float &x, T &...rest) {
     pin(x);

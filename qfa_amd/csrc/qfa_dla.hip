@@ -117,11 +117,7 @@ int qfa_template_scan_f32(const qfa_params_t *p, const float *mu, const qfa_batc
         k_scan_solve<<<(unsigned)(((size_t)ns * nc + 3) / 4), 256, 0, st>>>(MOM, NULLM, NUL0, ns, nc, P.ncp, Nh, 0, llr + (size_t)s0 * nc);
     }
     if (best_c || best_llr) k_scan_best<<<(unsigned)B, 256, 0, st>>>(llr, nc, best_c, best_llr);
-    if (flags & QFA_F_SYNC) {
-        hipError_t s = hipStreamSynchronize(st);
-        if (s != hipSuccess) { (void)hipGetLastError(); return (int)s; }
-    }
-    return (int)hipGetLastError();
+    return hip_status(st, flags);
 }
 
 }  // extern "C"

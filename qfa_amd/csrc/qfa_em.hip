@@ -89,11 +89,7 @@ int qfa_em_stats_f32(const qfa_params_t *p, const qfa_batch_t *b, const qfa_tau_
     const size_t n = (size_t)Npix * ((size_t)Nh * Nh + Nh + 1);
     k_em_reduce<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(SLAB, CNT, P.R, Npix, Nh, zero, stats);
     k_em_nll<<<1, 1024, 0, st>>>(es.nll, B, zero, stats + n);
-    if (flags & QFA_F_SYNC) {
-        hipError_t s = hipStreamSynchronize(st);
-        if (s != hipSuccess) { (void)hipGetLastError(); return (int)s; }
-    }
-    return (int)hipGetLastError();
+    return hip_status(st, flags);
 }
 
 int qfa_em_update_f_f32(const float *stats, const float *F, int Npix, int Nh, double ridge, double damping, float *F_out,

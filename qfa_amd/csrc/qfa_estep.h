@@ -6,14 +6,7 @@
 
 #include <type_traits>
 
-#include "../../include/qfa_hip.h"
-
-// the batch as the kernels take it: row_stride filled in
-inline qfa_batch_t norm_batch(const qfa_batch_t &b, int Npix) {
-    qfa_batch_t r = b;
-    if (r.row_stride == 0) r.row_stride = Npix;
-    return r;
-}
+#include "qfa_call.h"
 
 // One call on a batch, as every level of the host code passes it on.  The C entry point fills it once, behind its argument checks.
 struct BatchCall {

@@ -22,8 +22,11 @@
 #include <stdint.h>
 
 #include "qfa_common.h"
+#include "qfa_continuum.h"
 
 namespace qfa_forest {
+
+using namespace qfa_continuum;
 
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
@@ -52,26 +55,7 @@ static __global__ void k_forest_image(const float *__restrict__ F, const float *
     img[i] = v;
 }
 
-// four values of pixels p0 .. p0 + 3 of a row (`n` of them exist); `vec`: the row's p0 is 16-byte aligned
-__device__ __forceinline__ void load4(const float *__restrict__ src, int n, float v[4]) {
-    if (n == 4 && (reinterpret_cast<uintptr_t>(src) & 15) == 0) {
-        const float4 q = *reinterpret_cast<const float4 *>(src);
-        v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) v[k] = k < n ? src[k] : 0.f;
-    }
-}
-__device__ __forceinline__ void store4(float *__restrict__ dst, int n, const float v[4]) {
-    if (n == 4 && (reinterpret_cast<uintptr_t>(dst) & 15) == 0) {
-        *reinterpret_cast<float4 *>(dst) = float4{v[0], v[1], v[2], v[3]};
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if (k < n) dst[k] = v[k];
-    }
-}
-
+// (not qfa_bal::wave_tree_sum: that one adds the lanes l ^ 32, 16, .., 1, and the float64 sums differ in the last bit)
 __device__ __forceinline__ double wave_sum(double x) {
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) x = __dadd_rn(x, __shfl_xor(x, d));

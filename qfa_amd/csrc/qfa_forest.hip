@@ -1,7 +1,7 @@
 // qfa_forest.hip -- C-ABI of the Lyman-alpha forest transmission and its stack (include/qfa_hip.h: qfa_forest_stack_doubles,
 // qfa_forest_workspace_bytes, qfa_forest_f32): argument checks, the launch plan and the launches.  Kernels in qfa_forest.h.
 #include "qfa_forest.h"
-#include "../../include/qfa_hip.h"
+#include "qfa_call.h"
 
 #include <math.h>
 
@@ -110,8 +110,7 @@ int qfa_forest_f32(const float *F, const float *mu, const qfa_batch_t *b, const 
     double *rows = (double *)(img + P.img_floats);
     k_forest_image<<<(unsigned)((P.img_floats + 255) / 256), 256, 0, st>>>(F, mu, Nb, Nh, P.pad, img);
     Args a;
-    a.bt = *b;
-    if (a.bt.row_stride == 0) a.bt.row_stride = Npix;
+    a.bt = norm_batch(*b, Npix);
     a.img = img;
     a.h = h;
     a.unc = unc;
@@ -135,20 +134,14 @@ int qfa_forest_f32(const float *F, const float *mu, const qfa_batch_t *b, const 
             hipError_t e = hipMemsetAsync(rows, 0, (size_t)P.rows * P.rowlen * sizeof(double), st);
             if (e != hipSuccess) return (int)e;
         }
-        if (Nh <= 8) launch<8>(a, P, st);
-        else if (Nh <= 16) launch<16>(a, P, st);
-        else launch<32>(a, P, st);
+        by_nhm(Nh, [&](auto nhm) { launch<decltype(nhm)::value>(a, P, st); });
         if (stack) {
             const int nent = a.Sc * 4 * nbin;
             k_forest_reduce<<<(unsigned)((nent + 31) / 32), 256, 0, st>>>(rows, (int)P.rows, P.rowlen, nent, zero,
                                                                            stack + (size_t)s0 * 4 * nbin);
         }
     }
-    if (flags & QFA_F_SYNC) {
-        hipError_t s = hipStreamSynchronize(st);
-        if (s != hipSuccess) { (void)hipGetLastError(); return (int)s; }
-    }
-    return (int)hipGetLastError();
+    return hip_status(st, flags);
 }
 
 }  // extern "C"

@@ -313,16 +313,6 @@ inline Pass2 pass2_form(int KP, int B, int Npix, unsigned flags) {
     return (KP == 16 ? B >= 128 : B >= 512) ? Pass2::PIXRES : Pass2::XDL;
 }
 
-// launch errors of the calls just made; with QFA_F_SYNC also the asynchronous ones (the stream is drained first)
-inline int hip_status(hipStream_t st = nullptr, unsigned flags = 0) {
-    if (flags & QFA_F_SYNC) {
-        hipError_t s = hipStreamSynchronize(st);
-        if (s != hipSuccess) { (void)hipGetLastError(); return (int)s; }
-    }
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
-}
-
 // the tile-major float32 image PFT: k_grads and k_predict_out (N_h <= 16), k_grads_s3 (N_h = 17..32)
 template <int KP>
 void launch_prep_pft(const BatchCall &c, const float4 *ZP, const Layout &L) {

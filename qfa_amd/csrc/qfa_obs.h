@@ -39,8 +39,6 @@ struct Args {
     float cont_min;
 };
 
-__device__ __forceinline__ void pin(double &x) { asm volatile("" : "+v"(x)); }
-
 // x = (u - u0) inv_du with u = pix_u + spec_u (log) or pix_u spec_u (linear): three roundings
 __device__ __forceinline__ double coord(double pu, double su, int linear, double u0, double inv_du) {
 #pragma clang fp contract(off)

@@ -2,6 +2,7 @@
 // qfa_obs_stack_workspace_bytes, qfa_obs_stack_f32, qfa_calibrate_f32): argument checks, the launch plan and the launches.
 // Kernels in qfa_obs.h.
 #include "qfa_obs.h"
+#include "qfa_call.h"
 
 #include <math.h>
 
@@ -95,8 +96,7 @@ int qfa_obs_stack_f32(const float *F, const float *mu, const qfa_batch_t *b, con
         return 0;
     }
     Args a;
-    a.bt = *b;
-    if (a.bt.row_stride == 0) a.bt.row_stride = Npix;
+    a.bt = norm_batch(*b, Npix);
     a.F = F; a.mu = mu; a.h = h; a.unc = unc; a.pix_u = pix_u; a.spec_u = spec_u;
     a.rows = (double *)(((uintptr_t)workspace + 15) & ~(uintptr_t)15);
     a.u0 = bins->u0;
@@ -106,15 +106,9 @@ int qfa_obs_stack_f32(const float *F, const float *mu, const qfa_batch_t *b, con
     a.linear = bins->mode == QFA_OBS_LINEAR ? 1 : 0;
     a.unit_w = (flags & QFA_F_OBS_UNIT_W) ? 1 : 0;
     a.cont_min = cont_min;
-    if (Nh <= 8) launch<8>(a, P, st);
-    else if (Nh <= 16) launch<16>(a, P, st);
-    else launch<32>(a, P, st);
+    by_nhm(Nh, [&](auto nhm) { launch<decltype(nhm)::value>(a, P, st); });
     k_obs_reduce<<<(unsigned)((P.nent + 255) / 256), 256, 0, st>>>(a.rows, (int)P.chunks, P.nent, zero, stack);
-    if (flags & QFA_F_SYNC) {
-        hipError_t s = hipStreamSynchronize(st);
-        if (s != hipSuccess) { (void)hipGetLastError(); return (int)s; }
-    }
-    return (int)hipGetLastError();
+    return hip_status(st, flags);
 }
 
 int qfa_calibrate_f32(const float *flux, const float *error, const double *pix_u, const double *spec_u, int N, int Npix,

@@ -13,7 +13,7 @@
 #include "qfa_pdf.h"
 #include "qfa_variance.h"
 #include "qfa_bootstrap.h"
-#include "../../include/qfa_hip.h"
+#include "qfa_call.h"
 
 #include <math.h>
 
@@ -169,11 +169,7 @@ int run_call(A &a, int B, int step, unsigned flags, double *stack, size_t double
         launch(zero);
         if (stack) zero = 0;
     }
-    if (flags & QFA_F_SYNC) {
-        hipError_t s = hipStreamSynchronize(st);
-        if (s != hipSuccess) { (void)hipGetLastError(); return (int)s; }
-    }
-    return (int)hipGetLastError();
+    return hip_status(st, flags);
 }
 
 // stack (S, nz, head + n^2) += the partials (chunks, S, nz, head + n (n + 1) / 2) of a launch

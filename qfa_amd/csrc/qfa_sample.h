@@ -14,8 +14,11 @@
 #include <stdint.h>
 
 #include "qfa_common.h"
+#include "qfa_continuum.h"
 
 namespace qfa_sample {
+
+using namespace qfa_continuum;
 
 constexpr int kWriterThreads = 256;       // k_sample_cont: 4 waves on 256 consecutive pixels of the same rows
 constexpr int kLatentThreads = 64;        // k_sample_latent: one wave
@@ -204,26 +207,6 @@ __global__ void k_mock_image(const float *__restrict__ F, const float *__restric
     img[i] = v;
 }
 
-// four values of pixels p0 .. p0 + 3 of a row (`n` of them exist); `vec`: the row's p0 is 16-byte aligned
-__device__ __forceinline__ void mock_load4(const float *__restrict__ src, int n, bool vec, float fill, float v[4]) {
-    if (vec && n == 4) {
-        const float4 q = *reinterpret_cast<const float4 *>(src);
-        v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) v[k] = k < n ? src[k] : fill;
-    }
-}
-__device__ __forceinline__ void mock_store4(float *__restrict__ dst, int n, bool vec, const float v[4]) {
-    if (vec && n == 4) {
-        *reinterpret_cast<float4 *>(dst) = float4{v[0], v[1], v[2], v[3]};
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if (k < n) dst[k] = v[k];
-    }
-}
-
 // grid (strips * chunks), block x = chunk * strips + strip as in k_sample_cont.  NHM >= Nh (8, 16 or 32): the columns
 // [Nh, NHM) of the image registers and of the latent row are zeros, which leave the fma chain's value as it is.
 template <int NHM>
@@ -277,7 +260,7 @@ __global__ __launch_bounds__(kMockThreads) void k_mock_spectra(qfa_params_t p, q
             const unsigned long long row = batch_row(bt, b);
             const float *er = bt.error + row * (unsigned long long)bt.row_stride + (unsigned)p0;
             float sg[4];
-            mock_load4(er, n, (reinterpret_cast<uintptr_t>(er) & 15) == 0, 0.f, sg);
+            load4(er, n, sg);
             bool use[4];
 #pragma unroll
             for (int k = 0; k < 4; ++k) use[k] = k < n;
@@ -325,8 +308,8 @@ __global__ __launch_bounds__(kMockThreads) void k_mock_spectra(qfa_params_t p, q
                     fl[k] = use[k] ? v : -999.0f;
                     dl[k] = use[k] ? __fsub_rn(v, mA[k]) : -999.0f;
                 }
-                if (flux) mock_store4(flux + o, n, (reinterpret_cast<uintptr_t>(flux + o) & 15) == 0, fl);
-                if (delta) mock_store4(delta + o, n, (reinterpret_cast<uintptr_t>(delta + o) & 15) == 0, dl);
+                if (flux) store4(flux + o, n, fl);
+                if (delta) store4(delta + o, n, dl);
             }
         }
     }

@@ -1,7 +1,7 @@
 // qfa_sample.hip -- C-ABI of the draws from the model (include/qfa_hip.h: qfa_sample_latent_f32, qfa_continua_workspace_bytes,
 // qfa_continua_f32, qfa_mock_workspace_bytes, qfa_mock_spectra_f32): argument checks and launch geometry.  Kernels in qfa_sample.h.
 #include "qfa_sample.h"
-#include "../../include/qfa_hip.h"
+#include "qfa_call.h"
 
 namespace {
 
@@ -54,12 +54,9 @@ int qfa_sample_latent_f32(const float *hmean, const float *hcov, int B, int Nh, 
     const dim3 grid((unsigned)B, (unsigned)((S + (int64_t)spb - 1) / spb));
     const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
     hipStream_t st = (hipStream_t)stream;
-    if (Nh <= 8)
-        k_sample_latent<8><<<grid, kLatentThreads, 0, st>>>(hmean, hcov, Nh, S, spb, k0, k1, row0, h);
-    else if (Nh <= 16)
-        k_sample_latent<16><<<grid, kLatentThreads, 0, st>>>(hmean, hcov, Nh, S, spb, k0, k1, row0, h);
-    else
-        k_sample_latent<32><<<grid, kLatentThreads, 0, st>>>(hmean, hcov, Nh, S, spb, k0, k1, row0, h);
+    by_nhm(Nh, [&](auto nhm) {
+        k_sample_latent<decltype(nhm)::value><<<grid, kLatentThreads, 0, st>>>(hmean, hcov, Nh, S, spb, k0, k1, row0, h);
+    });
     return (int)hipGetLastError();
 }
 
@@ -99,8 +96,7 @@ int qfa_mock_spectra_f32(const qfa_params_t *p, const float *mu, const qfa_batch
     if (workspace_bytes < qfa_mock_workspace_bytes(Npix, Nh)) return QFA_E_WORKSPACE;
     if (B == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
-    qfa_batch_t bt = *b;
-    if (bt.row_stride == 0) bt.row_stride = Npix;
+    const qfa_batch_t bt = norm_batch(*b, Npix);
     const int pad = mock_pad_of(Npix);
     float *img = (float *)(((uintptr_t)workspace + 15) & ~(uintptr_t)15);
     float4 *ZP = (float4 *)(img + (size_t)(Nh + 3) * pad);
@@ -124,13 +120,10 @@ int qfa_mock_spectra_f32(const qfa_params_t *p, const float *mu, const qfa_batch
     const int64_t chunks = (B + rpb - 1) / rpb;
     const unsigned grid = (unsigned)(chunks * strips);
     const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-#define QFA_MOCK_LAUNCH(NHM)                                                                                                    \
-    k_mock_spectra<NHM><<<grid, kMockThreads, 0, st>>>(*p, bt, *tau, mode, img, pad, ZP, h, B, S, Npix, Nb, Nh, strips, (int)rpb, \
-                                                       k0, k1, row0, flux, delta)
-    if (Nh <= 8) QFA_MOCK_LAUNCH(8);
-    else if (Nh <= 16) QFA_MOCK_LAUNCH(16);
-    else QFA_MOCK_LAUNCH(32);
-#undef QFA_MOCK_LAUNCH
+    by_nhm(Nh, [&](auto nhm) {
+        k_mock_spectra<decltype(nhm)::value><<<grid, kMockThreads, 0, st>>>(*p, bt, *tau, mode, img, pad, ZP, h, B, S, Npix, Nb, Nh, strips,
+                                                                           (int)rpb, k0, k1, row0, flux, delta);
+    });
     return (int)hipGetLastError();
 }
 

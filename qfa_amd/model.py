@@ -391,6 +391,47 @@ class QFA(ForestStatistics, DLAFinder, ObservedFrame, BALFinder):
                 f"do not match (B,{self.Npix}), (B,{self.Npix}), (B,{self.Nb}), (B,{self.Npix})")
         return B
 
+    def _resolve_latent(self, what, B, *, h, hmean, hcov, n_samples, seed, offset, unc, predict_inputs):
+        """The latent of a call on posterior draws (``forest``, ``observed_residuals``, ``bal_scan``): ``h`` (B, S, Nh) as it is; else
+        ``hmean`` alone (or with ``hcov`` and ``n_samples`` = 0), S = 1; else ``hmean`` + ``hcov`` + ``n_samples`` > 0 through
+        ``sample_latent``; with none of them ``predict(**predict_inputs)`` runs first, and its unc is handed back when S = 1 and
+        none was passed.  Returns ``(h, S, unc)``; ``what`` names the caller in the messages."""
+        if hcov is not None and hmean is None:
+            raise _lib.QFAHipError(f"{what}: hcov without hmean")
+        if h is not None and hmean is not None:
+            raise _lib.QFAHipError(f"{what}: pass h or hmean / hcov, not both")
+        S = int(n_samples)
+        if S < 0 or (S > 0 and h is None and hmean is not None and hcov is None):
+            raise _lib.QFAHipError(f"{what}: n_samples > 0 needs hcov next to hmean")
+        if h is None and hmean is None:
+            _, hmean, hcov, _, punc = self.predict(**predict_inputs)
+            if S == 0 and unc is None:
+                unc = punc
+        if h is not None:
+            if h.dim() != 3 or h.shape[0] != B or h.shape[2] != self.Nh or h.shape[1] < 1 or (S > 0 and h.shape[1] != S):
+                raise _lib.QFAHipError(f"h: shape {tuple(h.shape)}, expected ({B}, {S if S > 0 else 'S'}, {self.Nh})")
+            return h, int(h.shape[1]), unc
+        if tuple(hmean.shape) != (B, self.Nh):
+            raise _lib.QFAHipError(f"hmean: shape {tuple(hmean.shape)}, expected ({B}, {self.Nh})")
+        if S > 0:
+            return self.sample_latent(hmean, hcov, S, seed=seed, offset=offset), S, unc
+        return hmean.reshape(B, 1, self.Nh), 1, unc
+
+    def _flux_batch(self, flux, error, mask):
+        """qfa_batch_t of flux / error / mask alone and the tensors it points into: the tensor form of a call that reads no
+        redshift (``observed_residuals``, ``bal_scan``).  The callers check the shapes: their messages differ."""
+        if mask is not None and mask.dtype != torch.bool:
+            raise _lib.QFAHipError(f"mask: dtype {mask.dtype}, expected torch.bool")
+        bs = _lib.Batch()
+        flux = flux if (flux.dtype == f32 and flux.is_contiguous()) else flux.to(f32).contiguous()
+        error = error if (error.dtype == f32 and error.is_contiguous()) else error.to(f32).contiguous()
+        mask = mask if mask is None or mask.is_contiguous() else mask.contiguous()
+        bs.delta = _lib.require_device_tensor(flux, f32, "flux").value
+        bs.error = _lib.require_device_tensor(error, f32, "error").value
+        bs.mask = _lib.require_device_tensor(mask, torch.bool, "mask").value if mask is not None else None
+        bs.rows, bs.row_stride = None, 0
+        return bs, [flux, error, mask]
+
     # ------------------------------------------------------------------ data parallel
     def enable_data_parallel(self, group=None, optimizer=None, sync=True):
         """Shard spectra across ranks: every rank calls forward/step on its own shard; the packed

@@ -69,44 +69,25 @@ class ForestStatistics(object):
         the ``ForestStack`` (None when neither ``bins`` nor ``stack`` was given)."""
         if self.mu is None:
             raise QFAHipError("forest needs model.mu (load_from_npz or train first)")
-        if hcov is not None and hmean is None:
-            raise QFAHipError("forest: hcov without hmean")
-        if h is not None and hmean is not None:
-            raise QFAHipError("forest: pass h or hmean / hcov, not both")
-        S = int(n_samples)
-        if S < 0:
+        if int(n_samples) < 0:
             raise QFAHipError(f"forest: n_samples = {n_samples}, expected >= 0")
-        if S > 0 and h is None and hmean is not None and hcov is None:
-            raise QFAHipError("forest: n_samples > 0 needs hcov next to hmean")
         if bins is None and stack is None and not return_pixels:
             raise QFAHipError("forest: nothing asked for (no bins, no stack, return_pixels = False)")
         dev = self.device
         self._params_struct()                                   # (F as a contiguous float32 device tensor)
-        if h is None and hmean is None:
-            _, hmean, hcov, _, punc = self.predict(flux, error, zabs, mask, zfac=zfac, batch=batch)
-            if S == 0 and unc is None:
-                unc = punc
         if batch is not None:
             B = batch.B
-            bs, keep = self._batch_struct_rows(batch, raw_flux=True)
         else:
             if not isinstance(flux, torch.Tensor) or flux.dim() != 2:
                 raise QFAHipError("forest: flux must be a (B, Npix) tensor")
             B = self._check_batch_shapes(flux, error, zabs, mask if mask is not None else flux)
+        h, S, unc = self._resolve_latent("forest", B, h=h, hmean=hmean, hcov=hcov, n_samples=n_samples, seed=seed, offset=offset, unc=unc,
+                                         predict_inputs=dict(flux=flux, error=error, zabs=zabs, mask=mask, zfac=zfac, batch=batch))
+        if batch is not None:
+            bs, keep = self._batch_struct_rows(batch, raw_flux=True)
+        else:
             bs, keep = self._batch_struct(flux, error, zabs, mask, zfac, allow_no_mask=True, auto_factor=False)
         bs.A_blue = None                                        # (not read by the call)
-        if h is None:
-            if tuple(hmean.shape) != (B, self.Nh):
-                raise QFAHipError(f"hmean: shape {tuple(hmean.shape)}, expected ({B}, {self.Nh})")
-            if S > 0:
-                h = self.sample_latent(hmean, hcov, S, seed=seed, offset=offset)
-            else:
-                S = 1
-                h = hmean.reshape(B, 1, self.Nh)
-        else:
-            if h.dim() != 3 or h.shape[0] != B or h.shape[2] != self.Nh or h.shape[1] < 1 or (S > 0 and h.shape[1] != S):
-                raise QFAHipError(f"h: shape {tuple(h.shape)}, expected ({B}, {S if S > 0 else 'S'}, {self.Nh})")
-            S = int(h.shape[1])
         ph = _lib.require_device_tensor(h, f32, "h")
         pu = None
         if unc is not None:

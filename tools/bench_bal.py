@@ -96,7 +96,7 @@ def main():
                 scan = fn()
             torch.cuda.synchronize()
             ms = float(np.median(timed(fn, a.steps)))
-            bs, keep = m._obs_batch(flux, error, mask)
+            bs, keep = m._flux_batch(flux, error, mask)
             dwin = m._bal_windows(wav, DEFAULT_LINES, ind)
             cfn = lambda: m._bal_call(bs, h, a.batch, dwin, DEFAULT_LINES, ind, 0.9, 1, 0, 0.0, "AI")
             for _ in range(a.warmup):
