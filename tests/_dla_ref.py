@@ -48,6 +48,69 @@ def scan(params, mu, flux, error, zabs, mask, V, tau_which="becker", tau_series=
     return nll0[:, None] - nll, nll0, nll
 
 
+def scan_one_batched(params, mu, flux, error, zabs, mask, V, tau_which="becker", tau_series=1, block=2048):
+    """scan_one for a long table: the same float64 quantities for `block` candidates at once -- the moments C' - I and b' by one
+    matrix product against the products f_a f_b of F and against F, then numpy's batched Cholesky and solve;
+    b'^T C'^-1 b' = |L^-1 b'|^2.  Working memory is a few (block, N_h, N_h) float64 arrays: about 50 MB at N_h = 32, whatever nc.
+    An unmasked non-finite pixel is not this function's business (the batched Cholesky raises on it)."""
+    p = {k: np.asarray(params[k], dtype=np.float64) for k in ("F", "Psi", "omega", "tau0", "c0", "beta")}
+    w = np.asarray(mask, dtype=bool)
+    x = np.where(w, np.asarray(flux, dtype=np.float64), 0.0)
+    sg = np.where(w, np.asarray(error, dtype=np.float64), 1.0)
+    A, zdep, _ = O.pixel_terms(p, sg, zabs, tau_which, tau_series)
+    nb = p["omega"].shape[0]
+    G = A * A * p["Psi"]
+    G[:nb] += p["omega"] * zdep[:nb]
+    mu = np.asarray(mu, dtype=np.float64)
+    F = p["F"]
+    k = F.shape[1]
+    pairs = (F[:, :, None] * F[:, None, :]).reshape(len(F), k * k)
+    n = float(np.sum(w))
+
+    def nll_of(v):                                                 # v (m, Npix)
+        Ap = v * A
+        D = v * v * G + sg * sg
+        wD = np.where(w, 1.0 / np.where(w, D, 1.0), 0.0)
+        d = np.where(w, x - Ap * mu, 0.0)
+        L = np.linalg.cholesky(((wD * Ap * Ap) @ pairs).reshape(len(v), k, k) + np.eye(k))
+        z = np.linalg.solve(L, ((wD * Ap * d) @ F)[:, :, None])[:, :, 0]
+        quad = np.sum(wD * d * d, axis=1) - np.sum(z * z, axis=1)
+        logdet = np.sum(np.where(w, np.log(np.where(w, D, 1.0)), 0.0), axis=1) + 2.0 * np.sum(np.log(np.diagonal(L, axis1=1, axis2=2)), axis=1)
+        return 0.5 * (quad + n * O.LOG2PI + logdet)
+
+    V = np.asarray(V)
+    nll0 = float(nll_of(np.ones((1, len(w))))[0])
+    nll = np.concatenate([nll_of(V[c:c + block].astype(np.float64)) for c in range(0, len(V), block)])
+    return nll0, nll
+
+
+def scan_batched(params, mu, flux, error, zabs, mask, V, tau_which="becker", tau_series=1, block=2048):
+    """scan through scan_one_batched: llr (B, nc), nll0 (B,), nll (B, nc) in float64"""
+    out = [scan_one_batched(params, mu, flux[s], error[s], zabs[s], mask[s], V, tau_which, tau_series, block) for s in range(len(flux))]
+    nll0 = np.array([o[0] for o in out])
+    nll = np.stack([o[1] for o in out])
+    return nll0[:, None] - nll, nll0, nll
+
+
+def chunk_size(ws_bytes, npix, nh, nc, limit=64):
+    """the number of spectra Bc that one chunk of the scan's batch walk holds, read off the library's own size function
+    (`ws_bytes(B, Npix, Nh, nc)`: qfa_template_scan_workspace_bytes): the workspace grows strictly with B while B <= Bc and is
+    constant after.  Returns the smallest b with ws(b + 1) == ws(b), after checking both halves of that statement up to `limit`."""
+    ws = [int(ws_bytes(b, npix, nh, nc)) for b in range(1, limit + 2)]
+    assert all(v > 0 for v in ws)
+    flat = [i for i in range(limit) if ws[i + 1] == ws[i]]
+    assert flat, "the workspace still grows at B = %d" % limit
+    bc = flat[0] + 1
+    assert all(ws[i + 1] > ws[i] for i in range(bc - 1)) and all(v == ws[bc - 1] for v in ws[bc - 1:])
+    return bc
+
+
+# the chunked case both test files use: (133, 64, 32), a 256 x 64 table, nine spectra
+CHUNK_SHAPE = (133, 64, 32)
+CHUNK_GRID = (256, 64)
+CHUNK_B = 9
+
+
 def draw(params, mu, wav, nb, B, seed, snr=(20.0, 100.0), masks=True, tau_which="becker", tau_series=1):
     """B spectra drawn from the model (flux, error, zabs float32; mask bool; zqso float64), the way synthetic.make_batch_numpy draws
     them, with the S/N range as an argument; masked pixels hold -999"""
