@@ -790,6 +790,48 @@ int qfa_template_scan_f32(const qfa_params_t *p, const float *mu, const qfa_batc
                           int B, int Npix, int Nb, int Nh, float *llr, float *nll0, int32_t *best_c, float *best_llr,
                           void *workspace, size_t workspace_bytes, unsigned flags, void *stream);
 
+/* The quasar-redshift finder: the likelihood of every spectrum under the model at 2 m + 1 integer pixel shifts (additive to ABI v4).
+ * Every other call takes the catalogue redshift as exact; this one measures it.  On a rest-frame grid that is uniform in log
+ * wavelength (step Delta in log10) a change of the redshift by one grid step is an integer shift between data and model pixels: no
+ * interpolation, and the rule is exact.  The reference ships no such step.
+ *
+ * The rule.  Inputs per spectrum: x = b->delta the RAW FLUX, sigma = b->error, w = b->mask, zq1 = b->zq1 = 1 + z_cat (required when
+ * Nb > 0: a (B, Nb) zabs cannot give z beyond Nb); shared: the model, mu, tau, pix_ratio_full[p] = wav_grid[p] / 1215.67 for ALL
+ * Npix pixels, max_shift = m >= 0.  Candidates s = -m .. m (n_s = 2 m + 1, column c = s + m): candidate s says that data pixel p is
+ * model pixel q = p + s, i.e. 1 + z_s = (1 + z_cat) 10^(-s Delta).
+ *   window     the data pixels p in [m, Npix - m), the same for every candidate: every candidate explains the same data, n is
+ *              common to all and the ratio is a likelihood ratio.  Pixels outside the window have weight 0;
+ *   per pixel  z_p = fma(zq1[r], pix_ratio_full[p], -1) (one rounding, r = rows ? rows[s] : s) does not depend on s.  The pixel is
+ *              blue iff q < Nb: there A = exp(-tau(z_p)), zd = (1 - c0 - exp(-tau0 (1 + z_p)^beta))^2; else A = 1, zd = 0.
+ *              D = A^2 Psi_q + omega_q zd + sigma_p^2,  delta = x_p - A mu_q,  the factor row f_q;
+ *   candidate  C = I + sum w/D A^2 f_q f_q^T,  b = sum w/D A delta f_q,
+ *              NLL_s = ( sum w/D delta^2 - b^T C^-1 b + n log 2 pi + sum w log D + log det C ) / 2;
+ *   arithmetic the per-pixel terms in float32; the sums of C and b on the matrix pipe (v_mfma_f32_16x16x4_f32) with float32
+ *              accumulators over a block of 16 pixels, the blocks added in float64 in pixel order; sum w/D delta^2, sum w log D
+ *              and n in float64 / integers; C factored in float64 (Cholesky) and NLL_s kept as a double;
+ *   outputs    llr (B, n_s) float32 = NLL_0 - NLL_s, the difference taken in float64 before the one rounding: llr[:, m] == 0
+ *              exactly;  nll0 (B,) float32 = NLL_0 (with m = 0 the window is the whole spectrum and nll0 is qfa_predict_f32's ll);
+ *              best_s (B,) int32 = the s of the largest llr, among equals the lowest |s|, then the lowest s, NaN never taken;
+ *              best_llr (B,) = that llr;  off, sig (B,) float64: with y-, y0, y+ the float32 llr at best_s - 1, best_s, best_s + 1
+ *              and cv = (y- - y0) + (y+ - y0):  off = (y- - y+) / (2 cv), the vertex of the parabola in pixels relative to best_s,
+ *              sig = 1 / sqrt(-cv);  both NaN where best_s = +-m or cv is not negative.  best_s, best_llr, off, sig may be NULL;
+ *   masks      a masked pixel may hold NaN, inf or -999 in delta and error: they are not read.  A spectrum with no used pixel in
+ *              the window has nll0 = 0, llr = 0, best_s = 0.  A non-finite delta or error in a USED pixel of the window makes that
+ *              spectrum's nll0, llr and best_llr NaN and its best_s 0, and touches no other spectrum;
+ *   sums       no atomics; two calls give the same bits, and a spectrum's row depends on that spectrum alone, bit for bit: not on B,
+ *              on the spectra beside it or on how the batch is cut into chunks.
+ * qfa_zscan_workspace_bytes: the images of F and of the model and the rows of one chunk of spectra (chunks whose rows stay below
+ * 64 MiB, four spectra at least); 0 = unsupported shape (B outside 1..2^24, Nh outside 1..32, max_shift outside 0..4096,
+ * Npix < 2 max_shift + 1).
+ * Returns QFA_E_NULL for a missing pointer (p and its members, mu, b and its members as qfa_predict_f32 needs them, zq1 when Nb > 0,
+ * tau, pix_ratio_full, llr, nll0, workspace) or a non-NULL A_blue; QFA_E_SIZE for an unsupported shape, Nb outside 0..Npix or
+ * 0 < row_stride < Npix; QFA_E_FLAGS for any flag but QFA_F_SYNC; QFA_E_WORKSPACE.  Argument checks return before any device work.
+ * The call neither synchronises nor allocates (graph-capturable). */
+size_t qfa_zscan_workspace_bytes(int B, int Npix, int Nh, int max_shift);
+int qfa_redshift_scan_f32(const qfa_params_t *p, const float *mu, const qfa_batch_t *b, const qfa_tau_t *tau, const float *pix_ratio_full,
+                          int max_shift, int B, int Npix, int Nb, int Nh, float *llr, float *nll0, int32_t *best_s, float *best_llr,
+                          double *off, double *sig, void *workspace, size_t workspace_bytes, unsigned flags, void *stream);
+
 /* The sightline bootstrap of the segment statistics (additive to ABI v4). The five calls above take their error bars from the scatter
  * of segments, but the segments of one quasar share a continuum, a noise model and a large-scale mode, and nothing but the band stack
  * gives a covariance between modes, lags, flux bins or z-bins.  The published measurements resample quasars.  These calls do that on

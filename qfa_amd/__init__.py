@@ -30,6 +30,7 @@ _LAZY = {
     "DLAScan": ("qfa_amd.dla", "DLAScan"),
     "ObservedStack": ("qfa_amd.calibration", "ObservedStack"),
     "BALScan": ("qfa_amd.bal", "BALScan"),
+    "RedshiftScan": ("qfa_amd.redshift", "RedshiftScan"),
     "calibrate": ("qfa_amd.calibration", "calibrate"),
 }
 

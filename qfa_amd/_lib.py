@@ -33,6 +33,7 @@ EXPORTS = (
     "qfa_segment_codes_f32", "qfa_bootstrap_workspace_bytes", "qfa_bootstrap_f64",
     "qfa_obs_stack_doubles", "qfa_obs_stack_workspace_bytes", "qfa_obs_stack_f32", "qfa_calibrate_f32",
     "qfa_bal_scan_f32", "qfa_bal_mask_f32",
+    "qfa_zscan_workspace_bytes", "qfa_redshift_scan_f32",
 )
 
 TAU_IDS = {"becker": 0, "fg": 1, "kamble": 2, "mock": 3}
@@ -220,6 +221,9 @@ def lib():
         "qfa_dla_profiles_f32": (i, [p, i, d, d, i, d, d, i, d, i, p, p]),
         "qfa_template_scan_workspace_bytes": (sz, [i, i, i, i]),
         "qfa_template_scan_f32": (i, [C.POINTER(Params), p, C.POINTER(Batch), C.POINTER(TauModel), p, i, i, i, i, i, p, p, p, p, p, sz,
+                                      C.c_uint, p]),
+        "qfa_zscan_workspace_bytes": (sz, [i, i, i, i]),
+        "qfa_redshift_scan_f32": (i, [C.POINTER(Params), p, C.POINTER(Batch), C.POINTER(TauModel), p, i, i, i, i, i, p, p, p, p, p, p, p, sz,
                                       C.c_uint, p]),
         "qfa_segment_codes_f32": (i, [p, p, C.POINTER(Batch), p, i, i, i, C.POINTER(P1DParams), p, p]),
         "qfa_bootstrap_workspace_bytes": (sz, [i, i, i, i, i, i]),

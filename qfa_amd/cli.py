@@ -144,6 +144,10 @@ def main(argv=None):
                check_scan_params, DEFAULT_LINES, M.BAL_THR, M.BAL_SMOOTH, M.BAL_MAX_GAP)
         if int(M.BAL_NITER) < 1 or not float(M.BAL_PAD_KMS) >= 0.0 or float(M.BAL_PAD_KMS) == float("inf"):
             raise ValueError("MODEL.BAL_NITER must be >= 1 and MODEL.BAL_PAD_KMS finite and >= 0")
+    if cfg.TYPE == "predict" and bool(M.ZSCAN):
+        from .redshift import MAX_SHIFT
+        if not 0 <= int(M.ZSCAN_MAX_SHIFT) <= MAX_SHIFT:
+            raise ValueError(f"MODEL.ZSCAN_MAX_SHIFT must lie in 0 .. {MAX_SHIFT}")
     os.makedirs(cfg.DATA.OUTPUT_DIR, exist_ok=True)
     with open(os.path.join(cfg.DATA.OUTPUT_DIR, "config.yaml"), "w") as f:
         f.write(cfg.dump())
@@ -226,6 +230,13 @@ def main(argv=None):
             io.write_bal_csv(os.path.join(cfg.DATA.OUTPUT_DIR, "bal_catalog.csv"),
                              scan.to_table([os.path.basename(n) for n in scan.names], min_value=float(M.BAL_MIN_AI)))
             np.savez(os.path.join(cfg.DATA.OUTPUT_DIR, "bal_scan.npz"), **scan.arrays())
+        if bool(M.ZSCAN):
+            import numpy as np
+            from . import io
+            scan = model.redshift_catalog(dataloader, int(M.ZSCAN_MAX_SHIFT))
+            io.write_redshift_csv(os.path.join(cfg.DATA.OUTPUT_DIR, "redshift_catalog.csv"),
+                                  scan.to_table([os.path.basename(n) for n in scan.names]))
+            np.savez(os.path.join(cfg.DATA.OUTPUT_DIR, "redshift_scan.npz"), **scan.arrays())
         print(f"Finish predicting {len(dataloader)} spectra in {time.time() - ts} seconds...")
     return 0
 

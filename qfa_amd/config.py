@@ -92,7 +92,12 @@ DEFAULTS = {                                        # reference QFA/config.py:15
               # normalised flux a trough lies below; BAL_SMOOTH: odd boxcar width 1 .. 15; BAL_MAX_GAP: masked pixels 0 .. 16 a trough
               # may bridge; BAL_NITER > 1 repeats predict -> find -> mask; BAL_MIN_AI: the AI in km/s above which a spectrum's troughs
               # are listed; BAL_PAD_KMS widens the troughs masked between iterations
-              "BAL": False, "BAL_THR": 0.9, "BAL_SMOOTH": 1, "BAL_MAX_GAP": 0, "BAL_NITER": 1, "BAL_MIN_AI": 0.0, "BAL_PAD_KMS": 0.0},
+              "BAL": False, "BAL_THR": 0.9, "BAL_SMOOTH": 1, "BAL_MAX_GAP": 0, "BAL_NITER": 1, "BAL_MIN_AI": 0.0, "BAL_PAD_KMS": 0.0,
+              # not in the reference: ZSCAN = True makes predict mode also write redshift_catalog.csv (one row per spectrum: file,
+              # z_cat, z, sigma_z, dv_kms, sigma_kms, best_s, offset, best_llr, at_edge; io.read_redshift_csv) and redshift_scan.npz:
+              # the likelihood of every spectrum at the pixel shifts -ZSCAN_MAX_SHIFT .. ZSCAN_MAX_SHIFT between data and model
+              # (QFA.redshift_catalog; the grid must be uniform in log wavelength)
+              "ZSCAN": False, "ZSCAN_MAX_SHIFT": 20},
     "TRAIN": {"NEPOCHS": 500, "LEARNING_RATE": 1e-3, "WEIGHT_DECAY": 1e-1, "DECAY_ALPHA": 0.9, "DECAY_STEP": 10,
               "WINDOW_LENGTH_FOR_MU": 16,
               # not in the reference: "em" = F by its closed-form EM update, Adam for the other parameters (QFA.train
@@ -117,7 +122,8 @@ EXTRA_KEYS = ("MODEL.REFERENCE_C0_QUIRK", "MODEL.N_SAMPLES", "MODEL.SAMPLE_SEED"
               "MODEL.P1D_NZBINS", "MODEL.P1D_MIN_USED_FRAC", "MODEL.P1D_NBANDS", "MODEL.XI_NLAGS", "MODEL.XI_SIGMA2_LSS", "MODEL.PDF_NBINS",
               "MODEL.PDF_TMIN", "MODEL.PDF_TMAX", "MODEL.PDF_CLAMP", "MODEL.PDF_RELATIVE", "MODEL.PDF_IVAR_MIN", "MODEL.VAR_NOCT", "MODEL.VAR_ELO",
               "MODEL.VAR_SUB", "MODEL.VAR_DMAX", "MODEL.VAR_MIN_COUNT", "MODEL.BOOT_N", "MODEL.BOOT_SEED", "MODEL.BAL",
-              "MODEL.BAL_THR", "MODEL.BAL_SMOOTH", "MODEL.BAL_MAX_GAP", "MODEL.BAL_NITER", "MODEL.BAL_MIN_AI", "MODEL.BAL_PAD_KMS", "TRAIN.F_UPDATE", "TRAIN.EM_RHO", "TRAIN.EM_RIDGE")
+              "MODEL.BAL_THR", "MODEL.BAL_SMOOTH", "MODEL.BAL_MAX_GAP", "MODEL.BAL_NITER", "MODEL.BAL_MIN_AI", "MODEL.BAL_PAD_KMS",
+              "MODEL.ZSCAN", "MODEL.ZSCAN_MAX_SHIFT", "TRAIN.F_UPDATE", "TRAIN.EM_RHO", "TRAIN.EM_RIDGE")
 
 
 def _set(cfg, dotted, value):

@@ -121,6 +121,38 @@ def read_bal_csv(path):
     return out
 
 
+REDSHIFT_COLUMNS = ("file", "z_cat", "z", "sigma_z", "dv_kms", "sigma_kms", "best_s", "offset", "best_llr", "at_edge")
+
+
+def write_redshift_csv(path, table):
+    """A redshift catalogue, one row per spectrum: ``file``, the catalogue redshift ``z_cat``, the refined ``z`` and ``sigma_z``,
+    the velocity offset ``dv_kms`` and ``sigma_kms``, the best pixel shift ``best_s`` (int), the parabola's ``offset`` in pixels, the
+    log-likelihood gain ``best_llr`` and ``at_edge`` (0 / 1) -- ``RedshiftScan.to_table``; floats with 17 significant digits"""
+    cols = [np.asarray(table[c]).reshape(-1) for c in REDSHIFT_COLUMNS]
+    if len({len(c) for c in cols}) != 1:
+        raise ValueError("write_redshift_csv: the columns must have one length")
+    ints = {REDSHIFT_COLUMNS.index("best_s"), REDSHIFT_COLUMNS.index("at_edge")}
+    with open(path, "w") as f:
+        f.write(",".join(REDSHIFT_COLUMNS) + "\n")
+        for row in zip(*cols):
+            f.write(str(row[0]) + "," + ",".join(str(int(x)) if k in ints else repr(float(x)) for k, x in enumerate(row) if k > 0) + "\n")
+    return path
+
+
+def read_redshift_csv(path):
+    """The table ``write_redshift_csv`` wrote, bit for bit: a dict of ``file`` (str), int64 ``best_s`` and ``at_edge`` and float64
+    for the rest (NaN stays NaN)"""
+    import pandas as pd
+    t = pd.read_csv(path, float_precision="round_trip")
+    missing = [c for c in REDSHIFT_COLUMNS if c not in t.columns]
+    if missing:
+        raise ValueError(f"{path}: missing column(s) {missing}")
+    out = {"file": t["file"].astype(str).values}
+    for c in REDSHIFT_COLUMNS[1:]:
+        out[c] = t[c].values.astype(np.int64 if c in ("best_s", "at_edge") else np.float64)
+    return out
+
+
 def bal_rest_intervals(names, table, pad_kms=0.0, lines=None):
     """The per-spectrum ``rest=`` list of ``mask_absorbers`` from a BAL table: for the spectra ``names`` (a trailing ``.npz`` is
     ignored on both sides) the intervals ``bal_intervals(v_min - pad_kms, v_max + pad_kms, lines)`` of every row of the file"""

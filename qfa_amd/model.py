@@ -30,6 +30,9 @@ Additions over the reference (none changes a reference call's result):
   * ``dla_profiles`` / ``template_scan`` / ``dla_scan`` / ``DLAScan`` -- the DLA finder, methods of the base class ``DLAFinder``
     (dla.py): a likelihood-ratio scan of every spectrum over a grid of absorber redshift and column density (include/qfa_hip.h,
     qfa_template_scan_f32), whose catalogue ``mask_absorbers`` takes;
+  * ``redshift_scan`` / ``redshift_catalog`` / ``RedshiftScan`` -- the quasar-redshift finder, methods of the base class
+    ``RedshiftFinder`` (redshift.py): the likelihood of every spectrum at integer pixel shifts between data and model
+    (include/qfa_hip.h, qfa_redshift_scan_f32), whose ``z()`` a second ``preprocess`` takes;
   * ``step`` -- forward + Adam + clip without a host sync (what ``train`` and bench.py run);
   * data parallelism: ``enable_data_parallel()`` all-reduces the packed sum/count buffer over
     RCCL once per step before the normalisation (SURVEY.md 8(e));
@@ -54,6 +57,7 @@ from .stacks import BootstrapStack, EMStats, ForestStack, P1DBandStack, P1DStack
 from .dla import DLAFinder, DLAScan    # (re-exported)
 from .calibration import ObservedFrame, ObservedStack    # (re-exported)
 from .bal import BALFinder, BALScan    # (re-exported)
+from .redshift import RedshiftFinder, RedshiftScan    # (re-exported)
 from .statistics import ForestStatistics
 
 f32 = torch.float32
@@ -86,7 +90,7 @@ def _resolve_tau(tau):
     raise TypeError("tau must be a name, qfa_amd.utils.tau (partial) or a callable")
 
 
-class QFA(ForestStatistics, DLAFinder, ObservedFrame, BALFinder):
+class QFA(ForestStatistics, DLAFinder, ObservedFrame, BALFinder, RedshiftFinder):
 
     def __init__(self, Nb: int, Nr: int, Nh: int, device: torch.device,
                  tau: Callable[[torch.Tensor], torch.Tensor] = default_tau,
